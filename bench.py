@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1 works both ways: started by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (RANK / LOCAL_RANK /
 WORLD_SIZE in the environment), or started plainly as `python bench.py --gpus N`, in which case THIS process starts the N ranks
@@ -402,6 +402,28 @@ def pmc_valu_active(kernel="k_resjac<false"):
     return best
 
 
+DUMP_BYTES = 48_000_000
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """--dump-outputs: what the last timed step left in its output buffers ({name: [B, N, ...] fp64 device tensor}) as <out_dir>/<name>.npy.
+    All of it when it fits in DUMP_BYTES; otherwise the same seeded sample of sequences from every array (and only the first frames of each when
+    one sequence alone is larger), so that two builds can be compared output for output.  Returns the local indices of the sequences and the
+    frame count written."""
+    import torch
+    first = next(iter(arrays.values()))
+    B, N = first.shape[:2]
+    per_frame = sum(8 * a[0, 0].numel() for a in arrays.values())
+    nf = int(min(N, max(1, DUMP_BYTES // per_frame)))
+    nb = int(min(B, max(1, DUMP_BYTES // (per_frame * nf))))
+    seqs = np.sort(np.random.default_rng(seed).choice(B, nb, replace=False)) if nb < B else np.arange(B)
+    idx = torch.as_tensor(seqs, dtype=torch.long, device=first.device)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.index_select(0, idx)[:, :nf].cpu().numpy().astype(np.float64, copy=False))
+    return seqs, nf
+
+
 def spawn_ranks(n: int) -> int:
     """`python bench.py --gpus N` without a launcher: start the N ranks as fresh child processes (this parent never imports torch
     or touches the GPU), one per GPU, rendezvous on 127.0.0.1; rank 0 prints the JSON line.  Returns the worst exit status."""
@@ -436,7 +458,11 @@ def main():
     ap.add_argument("--cfg4-batch", type=int, default=512, help="sequences of the config-4 timing (one launch window; 44 GB of node workspace)")
     ap.add_argument("--gen-workers", type=int, default=0, help="processes that generate the synthetic sequences (0 = as many as the CPU share allows; 1 under a profiler, whose preloaded tool does not survive fork)")
     ap.add_argument("--cfg4-cams", type=int, default=6, choices=(1, 6), help="cameras of the physics-based timing (1 = monocular + pose prior, as the reference runs it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed -- residual, Jacobian and acceleration "
+                    f"slack of a fixed, seeded sample of rank 0's sequences, fp64 -- as DIR/<name>.npy (at most {DUMP_BYTES // 1000000} MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))                    # nothing above this line has initialised the GPU
@@ -557,6 +583,11 @@ def main():
     frames_total = world * B * N * args.steps
     value = frames_total / elapsed
     progress(f"rank {rank}: residual + Jacobian pass timed ({kern_ms:.3f} ms per launch)")
+    dumped = None
+    if args.dump_outputs and rank == 0:                # before anything else runs on r, J, eps
+        seqs, nf = dump_outputs(args.dump_outputs, {"residual": r, "jacobian": J, "accel_slack": eps})
+        dumped = {"dir": args.dump_outputs, "names": ["residual", "jacobian", "accel_slack"], "sequences": [int(mine[i]) for i in seqs], "frames": nf}
+        progress(f"rank {rank}: outputs of the last timed step written to {args.dump_outputs}")
     # the variant that also reads the weights and writes the robust cost (k_resjac<true>), for the record
     ms_cost = time_resjac(h, t, r, J, eps, cost, 5, stream) if world == 1 else None
 
@@ -679,7 +710,7 @@ def main():
             "preheat": {"seconds": args.preheat, "launches": n_heat, "note": "untimed launches of the same kernel before the warm-up: steady memory rate of the device (tools/ab_resjac_box.py)"},
             "config": {"workload": "cfg2: synthetic 200-frame x 6-cam x 25-marker sequences, phantom skeleton, const-accel model",
                        "frames": N, "cams": C, "markers": L, "sequences_per_gpu": B, "parallelism": f"shard{world} (independent sequences, no collective)"},
-            "solves": solves, "solves_cfg3": cfg3, "solves_cfg4": cfg4, "markers24": l24,
+            "solves": solves, "solves_cfg3": cfg3, "solves_cfg4": cfg4, "markers24": l24, "dump_outputs": dumped,
             "roofline": {"bound": "hbm", "achieved": ach / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": ach / HBM_PEAK,
                          "traffic": pmc_traffic(B, N, C, L), "kernel": "k_resjac<false>", "kernel_ms": kern_ms, "bytes_per_frame": bpf, "sq": pmc_valu_active()},
         }

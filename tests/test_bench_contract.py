@@ -69,3 +69,30 @@ def test_plain_invocation_spawns_its_ranks():
     assert len(lines) == 1
     j = json.loads(lines[0])
     assert j["dryrun"] and j["n_gpus"] == 2 and j["owned"] == list(range(8)) and j["max_over_ranks"] == 2.0
+
+
+def test_dump_outputs_writes_a_fixed_fp64_sample_within_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: every array of the timed step as <dir>/<name>.npy in fp64, the whole batch when it fits, otherwise the same seeded sample of
+    sequences from every array (first frames only when one sequence is too large), and never more than DUMP_BYTES in all"""
+    import torch
+    b = _bench()
+    B, N = 16, 10
+    arrays = {"residual": torch.randn(B, N, 3, 2, dtype=torch.float64), "accel_slack": torch.randn(B, N, 4, dtype=torch.float64)}
+    per_seq = 8 * N * (3 * 2 + 4)
+    seqs, nf = b.dump_outputs(str(tmp_path / "all"), arrays)
+    assert list(seqs) == list(range(B)) and nf == N
+    for k, a in arrays.items():
+        got = np.load(tmp_path / "all" / f"{k}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, a.numpy())
+    monkeypatch.setattr(b, "DUMP_BYTES", 5 * per_seq)
+    seqs, nf = b.dump_outputs(str(tmp_path / "a"), arrays)
+    again, _ = b.dump_outputs(str(tmp_path / "b"), arrays)
+    assert len(seqs) == 5 and nf == N and list(seqs) == sorted(set(seqs)) and np.array_equal(seqs, again)
+    for k, a in arrays.items():
+        got = np.load(tmp_path / "a" / f"{k}.npy")
+        assert np.array_equal(got, a.numpy()[seqs]) and np.array_equal(got, np.load(tmp_path / "b" / f"{k}.npy"))
+    assert sum(os.path.getsize(tmp_path / "a" / f"{k}.npy") - 128 for k in arrays) <= 5 * per_seq
+    monkeypatch.setattr(b, "DUMP_BYTES", per_seq // 2)
+    seqs, nf = b.dump_outputs(str(tmp_path / "c"), arrays)
+    assert len(seqs) == 1 and nf == N // 2
+    assert np.array_equal(np.load(tmp_path / "c" / "residual.npy"), arrays["residual"].numpy()[seqs, :nf])

@@ -91,10 +91,11 @@ def test_second_size_of_both_models_matches_sklearn(oracle):
     assert np.count_nonzero(coef) > 0.9 * coef.size                                   # dense: no lasso
 
 
-REF_TABLE = "/root/reference/models/data-driven/dataset_full_pose.csv"
+# the reference's pose table models/data-driven/dataset_full_pose.csv cut to the columns fit_priors reads (the frame index and the 28 pose
+# variables), every field kept as the original text so that it parses to the same numbers
+REF_TABLE = os.path.join(os.path.dirname(__file__), "golden", "dataset_full_pose_28cols.csv.gz")
 
 
-@pytest.mark.skipif(not os.path.isfile(REF_TABLE), reason="the reference's pose table is not on this machine")
 def test_fit_priors_repeats_the_packaged_fit_and_refuses_what_the_solver_cannot_hold(tmp_path):
     """priors.fit_priors with the defaults is the packaged file, number for number (same recipe, deterministic); sizes outside cpe_priors are refused
     with the reason; a fitted size is cached"""
