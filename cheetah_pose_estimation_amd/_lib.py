@@ -161,6 +161,24 @@ class Handle:
     def _leave(self):
         _check(self.lib.cpe_stream_signal(self._h, self._torch_stream()), "cpe_stream_signal")
 
+    def _call(self, fn, what, *args, allow=(abi.OK,)):
+        """fn(handle, *args) bracketed by _enter / _leave (also when it fails); returns its status, raises unless it is in `allow`"""
+        self._enter()
+        try:
+            st = fn(self._h, *args)
+        finally:
+            self._leave()
+        return _check(st, what, allow)
+
+    # staging of numpy arrays for the *_host methods
+    def _to_device(self, a, dtype=np.float64):
+        import torch
+        return torch.tensor(np.ascontiguousarray(a, dtype=dtype), device=torch.device("cuda", self.device))
+
+    def _empty(self, *shape):
+        import torch
+        return torch.empty(shape, dtype=torch.float64, device=torch.device("cuda", self.device))
+
     PROFILE_SLOTS = ("k_frame_normal", "k_lr_band", "k_lm_step", "k_build_act", "k_finalize", "k_dyn_eval", "k_dyn_gather", "k_lm_back",
                      "k_dyn_assemble", "k_dyn_schur", "k_dyn_jac", "_free11")
 
@@ -185,113 +203,79 @@ class Handle:
 
     # ---- device-pointer entry points (torch-ROCm tensors on self.device) -------------------------------
     def eval_resjac(self, q, meas, weight, r, J, eps, cost=None):
-        B, N = q.shape[0], q.shape[1]
-        self._enter()
-        _check(self.lib.cpe_eval_resjac(self._h, B, N, _ptr(q), _ptr(meas), _ptr(weight), _ptr(r), _ptr(J), _ptr(eps), _ptr(cost)),
-               "cpe_eval_resjac")
-        self._leave()
+        self._call(self.lib.cpe_eval_resjac, "cpe_eval_resjac", q.shape[0], q.shape[1], _ptr(q), _ptr(meas), _ptr(weight), _ptr(r), _ptr(J),
+                   _ptr(eps), _ptr(cost))
 
     def project_joints(self, q):
-        self._enter()
-        st = _check(self.lib.cpe_project_joints(self._h, q.shape[0], q.shape[1], _ptr(q)), "cpe_project_joints",
-                    allow=(abi.OK, abi.NUMERICAL))
-        self._leave()
-        return st
+        return self._call(self.lib.cpe_project_joints, "cpe_project_joints", q.shape[0], q.shape[1], _ptr(q), allow=(abi.OK, abi.NUMERICAL))
 
     def forward_kinematics(self, q, positions, com=None):
-        self._enter()
-        _check(self.lib.cpe_forward_kinematics(self._h, q.shape[0], q.shape[1], _ptr(q), _ptr(positions), _ptr(com)),
-               "cpe_forward_kinematics")
-        self._leave()
+        self._call(self.lib.cpe_forward_kinematics, "cpe_forward_kinematics", q.shape[0], q.shape[1], _ptr(q), _ptr(positions), _ptr(com))
 
     def marker_velocities(self, q, dq, velocities):
         """v_l = (d p_l / d q) dq for every marker (device tensors; velocities [B, N, L, 3])"""
-        self._enter()
-        _check(self.lib.cpe_marker_velocities(self._h, q.shape[0], q.shape[1], _ptr(q), _ptr(dq), _ptr(velocities)),
-               "cpe_marker_velocities")
-        self._leave()
+        self._call(self.lib.cpe_marker_velocities, "cpe_marker_velocities", q.shape[0], q.shape[1], _ptr(q), _ptr(dq), _ptr(velocities))
 
     def reproject(self, positions, uv):
         """stored 3D markers -> pixels in every camera (device tensors; uv [B, N, C, L, 2])"""
-        self._enter()
-        _check(self.lib.cpe_reproject(self._h, positions.shape[0], positions.shape[1], _ptr(positions), _ptr(uv)), "cpe_reproject")
-        self._leave()
+        self._call(self.lib.cpe_reproject, "cpe_reproject", positions.shape[0], positions.shape[1], _ptr(positions), _ptr(uv))
 
     def reproject_host(self, positions):
         """numpy [B, N, L, 3] -> numpy [B, N, C, L, 2] (staged through HBM with torch)"""
-        import torch
-        dev = torch.device("cuda", self.device)
-        pd = torch.tensor(np.ascontiguousarray(positions, dtype=np.float64), device=dev)
-        uv = torch.empty((pd.shape[0], pd.shape[1], self.n_cams, self.L, 2), dtype=torch.float64, device=dev)
+        pd = self._to_device(positions)
+        uv = self._empty(pd.shape[0], pd.shape[1], self.n_cams, self.L, 2)
         self.reproject(pd, uv)
         self.synchronize()
         return uv.cpu().numpy()
 
     def triangulate_host(self, cam_a, cam_b, uv_a, uv_b, depth=3.0):
         """n detection pairs -> xyz [n, 3] (cpe_triangulate; cam_b < 0: back-projection of uv_a to `depth`); numpy in / out"""
-        import torch
-        dev = torch.device("cuda", self.device)
-        ca = torch.tensor(np.ascontiguousarray(cam_a, dtype=np.int32), device=dev)
-        cb = torch.tensor(np.ascontiguousarray(cam_b, dtype=np.int32), device=dev)
-        ua = torch.tensor(np.ascontiguousarray(uv_a, dtype=np.float64).reshape(-1, 2), device=dev)
-        ub = torch.tensor(np.ascontiguousarray(uv_b, dtype=np.float64).reshape(-1, 2), device=dev)
+        ca, cb = self._to_device(cam_a, np.int32), self._to_device(cam_b, np.int32)
+        ua = self._to_device(np.reshape(uv_a, (-1, 2)))
+        ub = self._to_device(np.reshape(uv_b, (-1, 2)))
         n = int(ca.shape[0])
         if not (cb.shape[0] == n and ua.shape[0] == n and ub.shape[0] == n):
             raise CpeError("triangulate_host: array lengths differ")
-        xyz = torch.empty((n, 3), dtype=torch.float64, device=dev)
-        self._enter()
-        _check(self.lib.cpe_triangulate(self._h, n, _ptr(ca), _ptr(cb), _ptr(ua), _ptr(ub), float(depth), _ptr(xyz)), "cpe_triangulate")
+        xyz = self._empty(n, 3)
+        self._call(self.lib.cpe_triangulate, "cpe_triangulate", n, _ptr(ca), _ptr(cb), _ptr(ua), _ptr(ub), float(depth), _ptr(xyz))
         self.synchronize()
         return xyz.cpu().numpy()
 
     def tensorise_dlc_host(self, tables, first_rows, part_of_marker, inv_sigma, thresh, N):
         """per-camera DLC tables (numpy [rows, 3*parts]) -> meas [N, C, L, 2], weight [N, C, L] (numpy) through cpe_tensorise_dlc"""
-        import torch
-        dev = torch.device("cuda", self.device)
         Cn = len(tables)
-        meas = torch.empty((N, Cn, self.L, 2), dtype=torch.float64, device=dev)
-        weight = torch.empty((N, Cn, self.L), dtype=torch.float64, device=dev)
-        pm = torch.tensor(np.ascontiguousarray(part_of_marker, dtype=np.int32), device=dev)
-        isg = torch.tensor(np.ascontiguousarray(inv_sigma, dtype=np.float64), device=dev)
+        meas, weight = self._empty(N, Cn, self.L, 2), self._empty(N, Cn, self.L)
+        pm, isg = self._to_device(part_of_marker, np.int32), self._to_device(inv_sigma)
         if pm.shape[0] != self.L or isg.shape[0] != self.L:
             raise CpeError("tensorise_dlc_host: one body part and one sigma per marker of the handle")
         for c, tab in enumerate(tables):
-            t = torch.tensor(np.ascontiguousarray(tab, dtype=np.float64), device=dev)
+            t = self._to_device(tab)
             if t.dim() != 2 or t.shape[1] % 3:
                 raise CpeError("tensorise_dlc_host: a DLC table has 3 columns per body part")
-            self._enter()
-            _check(self.lib.cpe_tensorise_dlc(self._h, N, Cn, c, _ptr(t), int(t.shape[0]), int(t.shape[1] // 3), int(first_rows[c]), _ptr(pm), _ptr(isg),
-                                              float(thresh), _ptr(meas), _ptr(weight)), "cpe_tensorise_dlc")
+            self._call(self.lib.cpe_tensorise_dlc, "cpe_tensorise_dlc", N, Cn, c, _ptr(t), int(t.shape[0]), int(t.shape[1] // 3), int(first_rows[c]),
+                       _ptr(pm), _ptr(isg), float(thresh), _ptr(meas), _ptr(weight))
             self.synchronize()                      # `t` must outlive the launch
         return meas.cpu().numpy(), weight.cpu().numpy()
 
     def kinematics_host(self, q, dq):
         """numpy in, numpy out (staged through HBM with torch): positions [B, N, L, 3], marker velocities [B, N, L, 3]"""
-        import torch
-        dev = torch.device("cuda", self.device)
-        qd = torch.tensor(np.ascontiguousarray(q, dtype=np.float64), device=dev)
-        dqd = torch.tensor(np.ascontiguousarray(dq, dtype=np.float64), device=dev)
+        qd, dqd = self._to_device(q), self._to_device(dq)
         B, N = qd.shape[0], qd.shape[1]
-        pos = torch.empty((B, N, self.L, 3), dtype=torch.float64, device=dev); vel = torch.empty_like(pos)
+        pos, vel = self._empty(B, N, self.L, 3), self._empty(B, N, self.L, 3)
         self.forward_kinematics(qd, pos, None)
         self.marker_velocities(qd, dqd, vel)
         self.synchronize()
         return pos.cpu().numpy(), vel.cpu().numpy()
 
     def eval_normal(self, q, meas, weight, g, Bm, cost, gam=None, q_out=None):
-        self._enter()
-        _check(self.lib.cpe_eval_normal(self._h, q.shape[0], q.shape[1], _ptr(q), _ptr(meas), _ptr(weight), _ptr(g), _ptr(Bm), _ptr(cost),
-                                        _ptr(gam), _ptr(q_out)), "cpe_eval_normal")
-        self._leave()
+        self._call(self.lib.cpe_eval_normal, "cpe_eval_normal", q.shape[0], q.shape[1], _ptr(q), _ptr(meas), _ptr(weight), _ptr(g), _ptr(Bm),
+                   _ptr(cost), _ptr(gam), _ptr(q_out))
 
     def solve(self, q_init, meas, weight, q, dq, ddq, positions, meas_err):
         B, N = q_init.shape[0], q_init.shape[1]
         stats = (abi.Stats * max(B, 1))()
-        self._enter()
-        st = self.lib.cpe_solve(self._h, B, N, _ptr(q_init), _ptr(meas), _ptr(weight), _ptr(q), _ptr(dq), _ptr(ddq),
-                                _ptr(positions), _ptr(meas_err), stats)
-        self._leave()
-        _check(st, "cpe_solve", allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
+        st = self._call(self.lib.cpe_solve, "cpe_solve", B, N, _ptr(q_init), _ptr(meas), _ptr(weight), _ptr(q), _ptr(dq), _ptr(ddq),
+                        _ptr(positions), _ptr(meas_err), stats, allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
         return st, list(stats)[:B]
 
     def solve_shutter(self, q_init, meas, weight, tau_bound, q, dq, ddq, positions, meas_err, tau, max_rounds=8, tol_tau=1e-6):
@@ -299,20 +283,15 @@ class Handle:
         B, N = q_init.shape[0], q_init.shape[1]
         stats = (abi.Stats * max(B, 1))()
         rounds = C.c_int32(0)
-        self._enter()
-        st = self.lib.cpe_solve_shutter(self._h, B, N, _ptr(q_init), _ptr(meas), _ptr(weight), float(tau_bound), int(max_rounds), float(tol_tau),
-                                        _ptr(q), _ptr(dq), _ptr(ddq), _ptr(positions), _ptr(meas_err), _ptr(tau), stats, C.byref(rounds))
-        self._leave()
-        _check(st, "cpe_solve_shutter", allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
+        st = self._call(self.lib.cpe_solve_shutter, "cpe_solve_shutter", B, N, _ptr(q_init), _ptr(meas), _ptr(weight), float(tau_bound),
+                        int(max_rounds), float(tol_tau), _ptr(q), _ptr(dq), _ptr(ddq), _ptr(positions), _ptr(meas_err), _ptr(tau), stats,
+                        C.byref(rounds), allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
         return st, list(stats)[:B], rounds.value
 
     def solve_shutter_host(self, q_init, meas, weight, tau_bound, max_rounds=8, tol_tau=1e-6):
         """numpy in, numpy out (staged through HBM with torch)"""
-        import torch
-        dev = torch.device("cuda", self.device)
-        T = lambda a: torch.tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)
-        E = lambda *sh: torch.empty(sh, dtype=torch.float64, device=dev)
-        qi, me, we = T(q_init), T(meas), T(weight)
+        E = self._empty
+        qi, me, we = self._to_device(q_init), self._to_device(meas), self._to_device(weight)
         B, N, nq = qi.shape
         q, dq, ddq = E(B, N, nq), E(B, N, nq), E(B, N, nq)
         pos, err, tau = E(B, N, self.L, 3), E(B, N, self.n_cams, self.L, 2), E(B, self.n_cams)
@@ -323,33 +302,23 @@ class Handle:
 
     def eom_rows(self, eopt, q, dq, ddq, rows):
         """all rows of d/dt dL/dq' - dL/dq (device tensors [B, N, nq])"""
-        self._enter()
-        _check(self.lib.cpe_eom_rows(self._h, C.byref(eopt), q.shape[0], q.shape[1], _ptr(q), _ptr(dq), _ptr(ddq), _ptr(rows)), "cpe_eom_rows")
-        self._leave()
+        self._call(self.lib.cpe_eom_rows, "cpe_eom_rows", C.byref(eopt), q.shape[0], q.shape[1], _ptr(q), _ptr(dq), _ptr(ddq), _ptr(rows))
 
     def eom_residual(self, dopt, q, dq, ddq, tau, lam, grf, residual):
         """rows of the equations of motion minus the generalised forces (device tensors; tau / lam / grf may be None)"""
-        self._enter()
-        _check(self.lib.cpe_eom_residual(self._h, C.byref(dopt), q.shape[0], q.shape[1], _ptr(q), _ptr(dq), _ptr(ddq), _ptr(tau), _ptr(lam),
-                                         _ptr(grf), _ptr(residual)), "cpe_eom_residual")
-        self._leave()
+        self._call(self.lib.cpe_eom_residual, "cpe_eom_residual", C.byref(dopt), q.shape[0], q.shape[1], _ptr(q), _ptr(dq), _ptr(ddq), _ptr(tau),
+                   _ptr(lam), _ptr(grf), _ptr(residual))
 
     def grf_fit(self, gopt, q, dq, ddq, contact, grfz, grfxy, residual=None):
         """per-frame ground-reaction-force fit (device tensors); contact int32 [B, N, n_feet]"""
-        self._enter()
-        _check(self.lib.cpe_grf_fit(self._h, C.byref(gopt), q.shape[0], q.shape[1], _ptr(q), _ptr(dq), _ptr(ddq), _ptr(contact),
-                                    _ptr(grfz), _ptr(grfxy), _ptr(residual)), "cpe_grf_fit")
-        self._leave()
+        self._call(self.lib.cpe_grf_fit, "cpe_grf_fit", C.byref(gopt), q.shape[0], q.shape[1], _ptr(q), _ptr(dq), _ptr(ddq), _ptr(contact),
+                   _ptr(grfz), _ptr(grfxy), _ptr(residual))
 
     def grf_fit_host(self, gopt, q, dq, ddq, contact):
         """numpy in, numpy out (staged through HBM with torch): grfz [B, N, nf], grfxy [B, N, nf, 4], residual [B, N, 6]"""
-        import torch
-        dev = torch.device("cuda", self.device)
-        T = lambda a, dt: torch.tensor(np.ascontiguousarray(a, dtype=dt), device=dev)
-        qd, dqd, ddqd, cd = T(q, np.float64), T(dq, np.float64), T(ddq, np.float64), T(contact, np.int32)
+        qd, dqd, ddqd, cd = self._to_device(q), self._to_device(dq), self._to_device(ddq), self._to_device(contact, np.int32)
         B, N, nf = qd.shape[0], qd.shape[1], gopt.n_feet
-        gz = torch.empty((B, N, nf), dtype=torch.float64, device=dev); gxy = torch.empty((B, N, nf, 4), dtype=torch.float64, device=dev)
-        res = torch.empty((B, N, 6), dtype=torch.float64, device=dev)
+        gz, gxy, res = self._empty(B, N, nf), self._empty(B, N, nf, 4), self._empty(B, N, 6)
         self.grf_fit(gopt, qd, dqd, ddqd, cd, gz, gxy, res)
         self.synchronize()
         return gz.cpu().numpy(), gxy.cpu().numpy(), res.cpu().numpy()
@@ -363,11 +332,9 @@ class Handle:
         if sum(a is not None for a in (grf_fixed, tau_box, grf_box)) > 1:
             raise ValueError("prescribed foot forces, torque boxes and force boxes are separate entry points")
         fn = self.lib.cpe_solve_kinetic_bounded if tau_box is not None else (self.lib.cpe_solve_kinetic_force_box if grf_box is not None else self.lib.cpe_solve_kinetic_fixed)
-        self._enter()
-        st = fn(self._h, C.byref(kopts), B, N, _ptr(q_init), _ptr(meas), _ptr(weight), _ptr(stance), _ptr(tau_box if tau_box is not None else (grf_box if grf_box is not None else grf_fixed)), _ptr(q), _ptr(dq), _ptr(ddq),
-                _ptr(positions), _ptr(meas_err), _ptr(tau), _ptr(lam), _ptr(grf), _ptr(slack), stats, ks)
-        self._leave()
-        _check(st, "cpe_solve_kinetic", allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
+        st = self._call(fn, "cpe_solve_kinetic", C.byref(kopts), B, N, _ptr(q_init), _ptr(meas), _ptr(weight), _ptr(stance),
+                        _ptr(tau_box if tau_box is not None else (grf_box if grf_box is not None else grf_fixed)), _ptr(q), _ptr(dq), _ptr(ddq),
+                        _ptr(positions), _ptr(meas_err), _ptr(tau), _ptr(lam), _ptr(grf), _ptr(slack), stats, ks, allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
         return st, list(stats)[:B], list(ks)[:B]
 
     def n_constraint_rows(self):
@@ -375,15 +342,10 @@ class Handle:
 
     def solve_kinetic_host(self, kopts, q_init, meas, weight, stance, grf_fixed=None, tau_box=None, grf_box=None):
         """numpy in, numpy out (staged through HBM with torch)"""
-        import torch
-        dev = torch.device("cuda", self.device)
-        T = lambda a, dt=np.float64: torch.tensor(np.ascontiguousarray(a, dtype=dt), device=dev)
+        T, E = self._to_device, self._empty
         qi, me, we, stn = T(q_init), T(meas), T(weight), T(stance, np.int32)
-        gfx = None if grf_fixed is None else T(grf_fixed)
-        tbx = None if tau_box is None else T(tau_box)
-        gbx = None if grf_box is None else T(grf_box)
+        gfx, tbx, gbx = (None if a is None else T(a) for a in (grf_fixed, tau_box, grf_box))
         B, N = qi.shape[0], qi.shape[1]
-        E = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
         nm, nf, nc = kopts.dyn.n_motors, kopts.dyn.n_feet, self.n_constraint_rows()
         q, dq, ddq = E(B, N, self.nq), E(B, N, self.nq), E(B, N, self.nq)
         pos, err = E(B, N, self.L, 3), E(B, N, self.n_cams, self.L, 2)
@@ -397,17 +359,13 @@ class Handle:
     def eval_kinetic_nodes_host(self, kopts, q, meas, weight, stance):
         """one evaluation of the physics terms per node (cpe_eval_kinetic_nodes); numpy in, dict of numpy arrays out"""
         import torch
-        dev = torch.device("cuda", self.device)
-        T = lambda a, dt=np.float64: torch.tensor(np.ascontiguousarray(a, dtype=dt), device=dev)
+        T, E = self._to_device, self._empty
         qd, me, we, stn = T(q), T(meas), T(weight), T(stance, np.int32)
         B, N = qd.shape[0], qd.shape[1]
-        E = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
         out = dict(f=E(B, N, 64), stat=E(B, N, 8), g=E(B, N, 84), Huu=E(B, N, 84, 84), Hfu=E(B, N, 64, 84), Hff=E(B, N, 64, 64))
-        meta = torch.zeros((B, N, 65), dtype=torch.int32, device=dev)
-        self._enter()
-        _check(self.lib.cpe_eval_kinetic_nodes(self._h, C.byref(kopts), B, N, _ptr(qd), _ptr(me), _ptr(we), _ptr(stn), _ptr(out["f"]), _ptr(out["stat"]),
-                                               _ptr(out["g"]), _ptr(out["Huu"]), _ptr(out["Hfu"]), _ptr(out["Hff"]), _ptr(meta)), "cpe_eval_kinetic_nodes")
-        self._leave()
+        meta = torch.empty((B, N, 65), dtype=torch.int32, device=qd.device)
+        self._call(self.lib.cpe_eval_kinetic_nodes, "cpe_eval_kinetic_nodes", C.byref(kopts), B, N, _ptr(qd), _ptr(me), _ptr(we), _ptr(stn),
+                   _ptr(out["f"]), _ptr(out["stat"]), _ptr(out["g"]), _ptr(out["Huu"]), _ptr(out["Hfu"]), _ptr(out["Hff"]), _ptr(meta))
         self.synchronize()
         res = {k: v.cpu().numpy() for k, v in out.items()}
         res["meta"] = meta.cpu().numpy()

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 #include <algorithm>
@@ -27,8 +28,9 @@ struct cpe_handle {
     DevModel hm;                 // host copy
     DevModel* dm = nullptr;      // device copy
     cpe_options opts;
-    // solver workspace
+    // solver workspace (its device buffers are recorded in ws_bufs as they are allocated, see ws_alloc)
     size_t ws_frames = 0; int ws_B = 0;
+    std::vector<void**> ws_bufs;
     double *qbuf = nullptr, *gbuf = nullptr, *Bbuf = nullptr, *costbuf = nullptr, *Lbuf = nullptr, *zbuf = nullptr,
            *gtbuf = nullptr, *dgbuf = nullptr, *cmax = nullptr, *mu = nullptr, *gambuf = nullptr;
     SeqState* st = nullptr;
@@ -52,6 +54,7 @@ struct cpe_handle {
     // physics-based model (cpe_solve_kinetic): device options and workspace
     DevKin* dk = nullptr; DevKin hk;
     size_t kws_frames = 0;
+    std::vector<void**> kws_bufs;
     double *kmut = nullptr;       // multipliers of the torque boxes [F][2 CPE_MAX_MOTORS] (cpe_solve_kinetic_bounded)
     double *kmus = nullptr;       // multipliers of the box on the residual [F][2 CPE_MAX_NQ] (bound_eom_error)
     double *fbuf = nullptr, *kmu = nullptr, *Jbuf = nullptr, *Abuf = nullptr, *pieces = nullptr, *gTb = nullptr, *dstat = nullptr, *slackb = nullptr,
@@ -65,6 +68,18 @@ struct DevBuf {
     ~DevBuf() { if (p) (void)hipFree(p); }
     hipError_t alloc(size_t n) { return hipMalloc(&p, sizeof(double) * (n ? n : 1)); }
 };
+
+// A workspace buffer is allocated through ws_alloc, which records the member's address: ws_free walks that record, so every buffer
+// is named once.
+template <class T>
+static hipError_t ws_alloc(std::vector<void**>& rec, T*& p, size_t n) {
+    rec.push_back(reinterpret_cast<void**>(&p));
+    return hipMalloc(&p, sizeof(T) * n);
+}
+static void ws_free(std::vector<void**>& rec) {
+    for (void** p : rec) { (void)hipFree(*p); *p = nullptr; }      // (hipFree of a null pointer does nothing)
+    rec.clear();
+}
 
 static double host_rho0(double a, double b, double c) {
     // rho(0) of acinoset_misc.py:2001-2015
@@ -435,9 +450,9 @@ static cpe_status create_impl(cpe_handle* h, const cpe_skeleton* skel, const cpe
         HIPCHK(hipGetDeviceProperties(&prop, device));
         h->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
         // dynamic LDS above 64 KiB needs an explicit opt-in per kernel
-        // dynamic LDS above 64 KiB needs an explicit opt-in per kernel
         const void* ks[] = {(const void*)&k_resjac<true, 4, 3, 2>, (const void*)&k_resjac<false, 4, 3, 2>,
-                            (const void*)&k_resjac<true, 4, 4, 2>, (const void*)&k_resjac<false, 4, 4, 2>};
+                            (const void*)&k_resjac<true, 4, 4, 2>, (const void*)&k_resjac<false, 4, 4, 2>,
+                            (const void*)&k_dyn_eval, (const void*)&k_dyn_assemble, (const void*)&k_dyn_schur, (const void*)&k_dyn_jac};
         for (const void* k : ks) HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     }
     HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
@@ -538,17 +553,13 @@ cpe_status cpe_create(const cpe_skeleton* skel, const cpe_camera* cams, int32_t 
 }
 
 static void free_kws(cpe_handle* h) {
-    void* ptrs[] = {h->kmut, h->kmus, h->fbuf, h->kmu, h->Jbuf, h->Abuf, h->pieces, h->gTb, h->dstat, h->slackb, h->Tbuf, h->gk, h->Bk, h->Hk, h->pmeta};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    h->kmut = h->kmus = h->fbuf = h->kmu = h->Jbuf = h->Abuf = h->pieces = h->gTb = h->dstat = h->slackb = h->Tbuf = h->gk = h->Bk = h->Hk = nullptr; h->pmeta = nullptr;
+    ws_free(h->kws_bufs);
     h->kws_frames = 0;
 }
 
-static void free_ws(cpe_handle* h) {
+static void free_ws(cpe_handle* h) {       // the kinetic workspace goes with it
     free_kws(h);
-    void* ptrs[] = {h->qbuf, h->gbuf, h->Bbuf, h->costbuf, h->Lbuf, h->zbuf, h->gtbuf, h->dgbuf, h->cmax, h->mu, h->gambuf, h->st, h->Hlr, h->act};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    h->qbuf = h->gbuf = h->Bbuf = h->costbuf = h->Lbuf = h->zbuf = h->gtbuf = h->dgbuf = h->cmax = h->mu = h->gambuf = h->Hlr = nullptr; h->st = nullptr; h->act = nullptr;
+    ws_free(h->ws_bufs);
     h->ws_frames = 0; h->ws_B = 0;
 }
 
@@ -639,14 +650,21 @@ cpe_status cpe_independent_dofs(const cpe_handle* h, int32_t* dofs) {
     return CPE_OK;
 }
 
+// The size check of every entry point that takes a batch of B sequences of N frames: F = B N frames, at most one launch grid of them.
+static cpe_status frames(int32_t B, int32_t N, size_t* F) {
+    if (B < 0 || N < 0) return fail(CPE_BAD_ARG, "negative size");
+    *F = (size_t)B * N;
+    if (*F > 0x7fffffffULL) return fail(CPE_BAD_ARG, "too many frames for one launch");
+    return CPE_OK;
+}
+
 cpe_status cpe_eval_resjac(cpe_handle* h, int32_t B, int32_t N, const double* q, const double* meas, const double* weight,
                            double* r, double* J, double* eps, double* cost) {
     if (!h || !q || !meas || !r || !J || !eps) return fail(CPE_BAD_ARG, "null argument");
     if (cost && !weight) return fail(CPE_BAD_ARG, "cost requested without weights");
-    if (B < 0 || N < 0) return fail(CPE_BAD_ARG, "negative size");
-    const size_t F = (size_t)B * N;
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
     if (F == 0) return CPE_OK;
-    if (F > 0x7fffffffULL) return fail(CPE_BAD_ARG, "too many frames for one launch");
     HIPCHK(hipSetDevice(h->device));
     const DevModel& m = h->hm;
     if (m.C * m.L > RJ_MAXPASS * WAVE) return fail(CPE_BAD_ARG, "cpe_eval_resjac supports at most 256 (camera, marker) pairs");
@@ -672,7 +690,8 @@ cpe_status cpe_eval_resjac(cpe_handle* h, int32_t B, int32_t N, const double* q,
 
 cpe_status cpe_project_joints(cpe_handle* h, int32_t B, int32_t N, double* q) {
     if (!h || !q) return fail(CPE_BAD_ARG, "null argument");
-    const size_t F = (size_t)B * N;
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
     if (F == 0) return CPE_OK;
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipMemsetAsync(h->flag, 0, sizeof(int), h->stream));
@@ -687,12 +706,12 @@ cpe_status cpe_project_joints(cpe_handle* h, int32_t B, int32_t N, double* q) {
 cpe_status cpe_grf_fit(cpe_handle* h, const cpe_grf_options* opt, int32_t B, int32_t N, const double* q, const double* dq,
                        const double* ddq, const int32_t* contact, double* grfz, double* grfxy, double* residual) {
     if (!h || !opt || !q || !dq || !ddq || !contact || !grfz || !grfxy) return fail(CPE_BAD_ARG, "null argument");
-    if (B < 0 || N < 0) return fail(CPE_BAD_ARG, "negative size");
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
     if (opt->n_feet < 1 || opt->n_feet > 4 || opt->iterations < 1 || !(opt->gravity > 0) || !(opt->force_max > 0) || !(opt->friction_ratio >= 0))
         return fail(CPE_BAD_ARG, "grf options out of range");
     for (int f = 0; f < opt->n_feet; f++)
         if (opt->foot_marker[f] < 0 || opt->foot_marker[f] >= h->hm.L) return fail(CPE_BAD_ARG, "foot marker index out of range");
-    const size_t F = (size_t)B * N;
     if (F == 0) return CPE_OK;
     HIPCHK(hipSetDevice(h->device));
     hipLaunchKernelGGL(k_grf, dim3((unsigned)((F + GRF_PACK - 1) / GRF_PACK)), dim3(WAVE), 0, h->stream, h->dm, *opt, F, q, dq, ddq, contact, grfz, grfxy, residual);
@@ -703,8 +722,8 @@ cpe_status cpe_grf_fit(cpe_handle* h, const cpe_grf_options* opt, int32_t B, int
 cpe_status cpe_eom_rows(cpe_handle* h, const cpe_eom_options* opt, int32_t B, int32_t N, const double* q, const double* dq,
                         const double* ddq, double* rows) {
     if (!h || !opt || !q || !dq || !ddq || !rows) return fail(CPE_BAD_ARG, "null argument");
-    if (B < 0 || N < 0) return fail(CPE_BAD_ARG, "negative size");
-    const size_t F = (size_t)B * N;
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
     if (F == 0) return CPE_OK;
     HIPCHK(hipSetDevice(h->device));
     if (!h->eom) HIPCHK(hipMalloc(&h->eom, sizeof(cpe_eom_options)));
@@ -722,9 +741,10 @@ cpe_status cpe_eom_residual(cpe_handle* h, const cpe_dyn_options* opt, int32_t B
     for (int m = 0; m < opt->n_motors; m++)
         if (opt->motor_first[m] < 0 || opt->motor_first[m] >= h->hm.nl || opt->motor_second[m] < 0 || opt->motor_second[m] >= h->hm.nl ||
             opt->motor_axis[m] < 0 || opt->motor_axis[m] > 2) return fail(CPE_BAD_ARG, "motor definition out of range");
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
     cpe_status s = cpe_eom_rows(h, &opt->eom, B, N, q, dq, ddq, residual);
     if (s != CPE_OK) return s;
-    const size_t F = (size_t)B * N;
     if (F == 0 || (!tau && !lambda && !grf)) return CPE_OK;
     if (!h->dyn) HIPCHK(hipMalloc(&h->dyn, sizeof(cpe_dyn_options)));
     HIPCHK(hipMemcpyAsync(h->dyn, opt, sizeof(cpe_dyn_options), hipMemcpyHostToDevice, h->stream));
@@ -737,7 +757,8 @@ cpe_status cpe_eom_residual(cpe_handle* h, const cpe_dyn_options* opt, int32_t B
 
 cpe_status cpe_forward_kinematics(cpe_handle* h, int32_t B, int32_t N, const double* q, double* positions, double* com) {
     if (!h || !q || !positions) return fail(CPE_BAD_ARG, "null argument");
-    const size_t F = (size_t)B * N;
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
     if (F == 0) return CPE_OK;
     HIPCHK(hipSetDevice(h->device));
     hipLaunchKernelGGL(k_fk, dim3((unsigned)F), dim3(WAVE), lds_fk(h->hm), h->stream, h->dm, q, positions, com);
@@ -747,11 +768,10 @@ cpe_status cpe_forward_kinematics(cpe_handle* h, int32_t B, int32_t N, const dou
 
 cpe_status cpe_marker_velocities(cpe_handle* h, int32_t B, int32_t N, const double* q, const double* dq, double* velocities) {
     if (!h) return fail(CPE_BAD_ARG, "null argument");
-    if (B < 0 || N < 0) return fail(CPE_BAD_ARG, "negative size");
-    const size_t F = (size_t)B * N;
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
     if (F == 0) return CPE_OK;
     if (!q || !dq || !velocities) return fail(CPE_BAD_ARG, "null argument");
-    if (F > 0x7fffffffULL) return fail(CPE_BAD_ARG, "too many frames for one launch");
     HIPCHK(hipSetDevice(h->device));
     const size_t lds = sizeof(double) * (2 * h->hm.nq + 6 * h->hm.nl + 36 * h->hm.nl);
     hipLaunchKernelGGL(k_marker_vel, dim3((unsigned)F), dim3(WAVE), lds, h->stream, h->dm, q, dq, velocities);
@@ -761,11 +781,10 @@ cpe_status cpe_marker_velocities(cpe_handle* h, int32_t B, int32_t N, const doub
 
 cpe_status cpe_reproject(cpe_handle* h, int32_t B, int32_t N, const double* positions, double* uv) {
     if (!h) return fail(CPE_BAD_ARG, "null argument");
-    if (B < 0 || N < 0) return fail(CPE_BAD_ARG, "negative size");
-    const size_t F = (size_t)B * N;
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
     if (F == 0) return CPE_OK;
     if (!positions || !uv) return fail(CPE_BAD_ARG, "null argument");
-    if (F > 0x7fffffffULL) return fail(CPE_BAD_ARG, "too many frames for one launch");
     HIPCHK(hipSetDevice(h->device));
     hipLaunchKernelGGL(k_reproject, dim3((unsigned)F), dim3(WAVE), 0, h->stream, h->dm, positions, uv);
     HIPCHK(hipGetLastError());
@@ -806,43 +825,52 @@ cpe_status cpe_tensorise_dlc(cpe_handle* h, int32_t N, int32_t n_slots, int32_t 
     return CPE_OK;
 }
 
+static size_t n_mu(const DevModel& m, size_t F) { return F * (size_t)(m.nb > 0 ? m.nb : 1) * 2; }   // bound multipliers
+
 static cpe_status ensure_ws(cpe_handle* h, int B, int N) {
     const size_t F = (size_t)B * N;
     if (F <= h->ws_frames && B <= h->ws_B) return CPE_OK;
     free_ws(h);
-    const int nq = h->hm.nq, nu = h->hm.nu;
-    HIPCHK(hipMalloc(&h->qbuf, sizeof(double) * 2 * F * h->hm.ns));
-    HIPCHK(hipMalloc(&h->gambuf, sizeof(double) * 2 * F * (size_t)(GAM_STRIDE * (h->hm.nrev > 0 ? h->hm.nrev : 1))));
-    HIPCHK(hipMalloc(&h->gbuf, sizeof(double) * 2 * F * nu));
-    HIPCHK(hipMalloc(&h->Bbuf, sizeof(double) * 2 * F * nu * nu));
-    HIPCHK(hipMalloc(&h->costbuf, sizeof(double) * 2 * F * COST_STRIDE));
-    HIPCHK(hipMalloc(&h->mu, sizeof(double) * (F * (size_t)(h->hm.nb > 0 ? h->hm.nb : 1) * 2)));
-    HIPCHK(hipMalloc(&h->Lbuf, sizeof(double) * F * (h->pb + 1) * nu * nu));
-    HIPCHK(hipMalloc(&h->zbuf, sizeof(double) * F * nu));
-    HIPCHK(hipMalloc(&h->gtbuf, sizeof(double) * F * nu));
-    HIPCHK(hipMalloc(&h->dgbuf, sizeof(double) * F * nu));
-    HIPCHK(hipMalloc(&h->cmax, sizeof(double) * F));
-    HIPCHK(hipMalloc(&h->st, sizeof(SeqState) * B));
-    HIPCHK(hipMalloc(&h->act, sizeof(int) * B));
-    if (h->lr_window > 0) HIPCHK(hipMalloc(&h->Hlr, sizeof(double) * 2 * F * h->pb * nu * nu));
+    const int nu = h->hm.nu;
+    auto& w = h->ws_bufs;
+    HIPCHK(ws_alloc(w, h->qbuf, 2 * F * h->hm.ns));
+    HIPCHK(ws_alloc(w, h->gambuf, 2 * F * (size_t)(GAM_STRIDE * (h->hm.nrev > 0 ? h->hm.nrev : 1))));
+    HIPCHK(ws_alloc(w, h->gbuf, 2 * F * nu));
+    HIPCHK(ws_alloc(w, h->Bbuf, 2 * F * nu * nu));
+    HIPCHK(ws_alloc(w, h->costbuf, 2 * F * COST_STRIDE));
+    HIPCHK(ws_alloc(w, h->mu, n_mu(h->hm, F)));
+    HIPCHK(ws_alloc(w, h->Lbuf, F * (h->pb + 1) * nu * nu));
+    HIPCHK(ws_alloc(w, h->zbuf, F * nu));
+    HIPCHK(ws_alloc(w, h->gtbuf, F * nu));
+    HIPCHK(ws_alloc(w, h->dgbuf, F * nu));
+    HIPCHK(ws_alloc(w, h->cmax, F));
+    HIPCHK(ws_alloc(w, h->st, B));
+    HIPCHK(ws_alloc(w, h->act, B));
+    if (h->lr_window > 0) HIPCHK(ws_alloc(w, h->Hlr, 2 * F * h->pb * nu * nu));
     h->ws_frames = F; h->ws_B = B;
     return CPE_OK;
 }
 
-static cpe_status ensure_ws(cpe_handle* h, int B, int N);
+// Cold start of every sequence from Euler q (device pointer): state buffer 0 = (q, alpha), sequence states and bound multipliers zero.
+static cpe_status state_reset(cpe_handle* h, int B, int N, const double* q) {
+    const size_t F = (size_t)B * N;
+    hipLaunchKernelGGL(k_state_init, dim3((unsigned)F), dim3(WAVE), 0, h->stream, h->dm, q, h->qbuf);   // Euler q -> (q, alpha)
+    HIPCHK(hipMemsetAsync(h->st, 0, sizeof(SeqState) * B, h->stream));
+    HIPCHK(hipMemsetAsync(h->mu, 0, sizeof(double) * n_mu(h->hm, F), h->stream));
+    return CPE_OK;
+}
 
 cpe_status cpe_eval_normal(cpe_handle* h, int32_t B, int32_t N, const double* q, const double* meas, const double* weight,
                            double* g, double* Bm, double* cost, double* gam, double* q_out) {
     if (!h || !q || !meas || !weight || !g || !Bm || !cost) return fail(CPE_BAD_ARG, "null argument");
-    const size_t F = (size_t)B * N;
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
     if (F == 0) return CPE_OK;
     HIPCHK(hipSetDevice(h->device));
     cpe_status s = ensure_ws(h, B, N);
     if (s != CPE_OK) return s;
+    if ((s = state_reset(h, B, N, q)) != CPE_OK) return s;
     const DevModel& m = h->hm;
-    hipLaunchKernelGGL(k_state_init, dim3((unsigned)F), dim3(WAVE), 0, h->stream, h->dm, q, h->qbuf);
-    HIPCHK(hipMemsetAsync(h->st, 0, sizeof(SeqState) * B, h->stream));
-    HIPCHK(hipMemsetAsync(h->mu, 0, sizeof(double) * (F * (size_t)(m.nb > 0 ? m.nb : 1) * 2), h->stream));
     hipLaunchKernelGGL(FRAME_NORMAL(h->gmm_k == 0), dim3((unsigned)F), dim3(WAVE), lds_normal(m, h->gmm_k, h->gmm_dim), h->stream, h->dm, h->st, N, 1, F, h->qbuf, meas, weight,
                        h->gbuf, h->Bbuf, h->costbuf, h->mu, h->gambuf, h->pri, nullptr, nullptr, ShutterArgs{nullptr, nullptr, nullptr});
     HIPCHK(hipMemcpyAsync(g, h->gbuf, sizeof(double) * F * m.nu, hipMemcpyDeviceToDevice, h->stream));
@@ -852,62 +880,27 @@ cpe_status cpe_eval_normal(cpe_handle* h, int32_t B, int32_t N, const double* q,
     return CPE_OK;
 }
 
-// restart of an LM run from the current iterate (shutter-delay outer loop): every sequence runs again, its buffers stay
-__global__ void k_reset_status(SeqState* __restrict__ st, int B) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < B) { st[b].status = 0; st[b].al_pending = 0; }
-}
-
-// The LM loop of cpe_solve on the handle's workspace: cold start from q_init (device pointer) or, with q_init == nullptr, a restart from
-// the current iterate of every sequence.  sh: shutter-delay buffers (all null = off).
-static cpe_status lm_run(cpe_handle* h, int B, int N, const double* q_init, const double* meas, const double* weight, ShutterArgs sh) {
-    const size_t F = (size_t)B * N;
-    const DevModel& m = h->hm;
-    const size_t Fw = F;   // buffers are laid out for exactly this call's F (strides use F)
-    if (q_init) {
-        hipLaunchKernelGGL(k_state_init, dim3((unsigned)F), dim3(WAVE), 0, h->stream, h->dm, q_init, h->qbuf);   // Euler q -> (q, alpha)
-        HIPCHK(hipMemsetAsync(h->st, 0, sizeof(SeqState) * B, h->stream));
-        HIPCHK(hipMemsetAsync(h->mu, 0, sizeof(double) * (F * (size_t)(m.nb > 0 ? m.nb : 1) * 2), h->stream));
-    } else hipLaunchKernelGGL(k_reset_status, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->st, B);
+static LmParams lm_params(const cpe_handle* h, int B, int N) {
     LmParams prm;
     prm.tol_step = h->opts.tol_step; prm.tol_cost = h->opts.tol_cost; prm.lambda0 = h->opts.lambda0; prm.B = B; prm.N = N;
     prm.bound_tol = h->opts.bound_tol; prm.max_outer = h->opts.max_outer; prm.max_iter = h->opts.max_iter;
-    const size_t ldsn = lds_normal(m, h->gmm_k, h->gmm_dim, sh.tau != nullptr);
-    const bool lr = h->lr_window > 0;
-    // One LM iteration = k_frame_normal (+ k_lr_band) on the evaluated buffer, then k_lm_step, for the first *n_act sequences listed
-    // in `act` (device arrays; nullptr = all B).  The grids are sized for `slots` sequences; workgroups past *n_act leave at once.
-    auto iterate = [&](int first, const int* act, const int* n_act, int slots) {
-        const unsigned gf = (unsigned)((size_t)slots * N);
-        const double* hiu = lr ? reinterpret_cast<const double*>(reinterpret_cast<const char*>(h->pri) + offsetof(DevPriors, lr_HIu)) + CPE_NX * CPE_NX : nullptr;
-        prof_begin(h, 0);
-        hipLaunchKernelGGL(FRAME_NORMAL(h->gmm_k == 0 && sh.tau == nullptr), dim3(gf), dim3(WAVE), ldsn, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, meas, weight, h->gbuf, h->Bbuf,
-                           h->costbuf, h->mu, h->gambuf, h->pri, act, n_act, sh);
-        prof_end(h);
-        if (lr) {
-            prof_begin(h, 1);
-            hipLaunchKernelGGL(k_lr_band, dim3(gf), dim3(WAVE), 0, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, h->gambuf, h->pri, h->pb, h->gbuf, h->Bbuf,
-                               h->Hlr, h->costbuf, act, n_act);
-            prof_end(h);
-        }
-        prof_begin(h, 2);
-        if (h->pb == 3) hipLaunchKernelGGL((k_lm_step<3, 0>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gbuf, h->Bbuf, h->costbuf,
-                                           h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hlr, act, n_act, 2, sh.gx, h->dgbuf, hiu, h->lr_window);
-        else hipLaunchKernelGGL((k_lm_step<4, 0>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gbuf, h->Bbuf, h->costbuf,
-                                h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hlr, act, n_act, 2, sh.gx, h->dgbuf, hiu, h->lr_window);
-        prof_end(h);
-        prof_begin(h, 7);
-        if (h->pb == 3) hipLaunchKernelGGL((k_lm_back<3>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf, h->gtbuf, h->dgbuf, act, n_act);
-        else hipLaunchKernelGGL((k_lm_back<4>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf, h->gtbuf, h->dgbuf, act, n_act);
-        prof_end(h);
-    };
+    return prm;
+}
+
+// One LM iteration of the sequences listed in `act` (device arrays; nullptr = all B), `first` = 1 in the first pass.  The grids are sized
+// for `slots` sequences; workgroups past *n_act leave at once.
+using LmIterate = std::function<void(int first, const int* act, const int* n_act, int slots)>;
+
+// The LM loop of both models on the handle's workspace, from the first pass over every sequence to the last sequence's end.
+// Active window: k_lm_step runs one workgroup per sequence and its duration is the sequential depth of ONE sequence,
+// whatever the grid (3.3 ms for <= 256 workgroups, 4.4 ms for 512 = 2 per CU), so the launches are kept exactly full: before
+// every iteration k_build_act lists the first `window` unfinished sequences ON THE DEVICE, so a sequence that converges hands
+// its slot to the next waiting one at once and the host never waits for an iteration: it queues POLL iterations, then reads
+// the PREVIOUS batch's snapshot of the list length (pinned memory + event) -- the stream stays at least one batch ahead and
+// is never drained inside the loop.  The price is at most 2 POLL iterations of empty launches after the last sequence ends.
+static cpe_status lm_drive(cpe_handle* h, int B, const LmIterate& iterate) {
     iterate(1, nullptr, nullptr, B);        // first evaluation and first step of every sequence
     HIPCHK(hipGetLastError());
-    // Active window: k_lm_step runs one workgroup per sequence and its duration is the sequential depth of ONE sequence,
-    // whatever the grid (3.3 ms for <= 256 workgroups, 4.4 ms for 512 = 2 per CU), so the launches are kept exactly full: before
-    // every iteration k_build_act lists the first `window` unfinished sequences ON THE DEVICE, so a sequence that converges hands
-    // its slot to the next waiting one at once and the host never waits for an iteration: it queues POLL iterations, then reads
-    // the PREVIOUS batch's snapshot of the list length (pinned memory + event) -- the stream stays at least one batch ahead and
-    // is never drained inside the loop.  The price is at most 2 POLL iterations of empty launches after the last sequence ends.
     const int window = std::min(B, h->n_cu * (h->pb == 3 ? 2 : 1));
     constexpr int POLL = 4;
     const long per_seq = (long)h->opts.max_iter + 2L * (h->opts.max_outer > 0 ? h->opts.max_outer : 0) + POLL;
@@ -936,21 +929,85 @@ static cpe_status lm_run(cpe_handle* h, int B, int N, const double* q_init, cons
     return CPE_OK;
 }
 
-// outputs of a finished LM run (k_finalize) and the per-sequence statistics; `iters_extra[b]` iterations of earlier runs are added
-static cpe_status lm_finish(cpe_handle* h, int B, int N, const double* meas, double* q, double* dq, double* ddq, double* positions, double* meas_err,
-                            const double* tau, cpe_stats* stats, const std::vector<int>* iters_extra) {
-    const size_t F = (size_t)B * N;
+// restart of an LM run from the current iterate (shutter-delay outer loop): every sequence runs again, its buffers stay
+__global__ void k_reset_status(SeqState* __restrict__ st, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) { st[b].status = 0; st[b].al_pending = 0; }
+}
+
+// The LM run of cpe_solve on the handle's workspace: cold start from q_init (device pointer) or, with q_init == nullptr, a restart from
+// the current iterate of every sequence.  sh: shutter-delay buffers (all null = off).
+static cpe_status lm_run(cpe_handle* h, int B, int N, const double* q_init, const double* meas, const double* weight, ShutterArgs sh) {
     const DevModel& m = h->hm;
+    const size_t Fw = (size_t)B * N;   // buffers are laid out for exactly this call's F (strides use F)
+    if (q_init) {
+        const cpe_status s = state_reset(h, B, N, q_init);
+        if (s != CPE_OK) return s;
+    } else hipLaunchKernelGGL(k_reset_status, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->st, B);
+    const LmParams prm = lm_params(h, B, N);
+    const size_t ldsn = lds_normal(m, h->gmm_k, h->gmm_dim, sh.tau != nullptr);
+    const bool lr = h->lr_window > 0;
+    // k_frame_normal (+ k_lr_band) on the evaluated buffer, then k_lm_step and k_lm_back
+    auto iterate = [&](int first, const int* act, const int* n_act, int slots) {
+        const unsigned gf = (unsigned)((size_t)slots * N);
+        const double* hiu = lr ? reinterpret_cast<const double*>(reinterpret_cast<const char*>(h->pri) + offsetof(DevPriors, lr_HIu)) + CPE_NX * CPE_NX : nullptr;
+        prof_begin(h, 0);
+        hipLaunchKernelGGL(FRAME_NORMAL(h->gmm_k == 0 && sh.tau == nullptr), dim3(gf), dim3(WAVE), ldsn, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, meas, weight, h->gbuf, h->Bbuf,
+                           h->costbuf, h->mu, h->gambuf, h->pri, act, n_act, sh);
+        prof_end(h);
+        if (lr) {
+            prof_begin(h, 1);
+            hipLaunchKernelGGL(k_lr_band, dim3(gf), dim3(WAVE), 0, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, h->gambuf, h->pri, h->pb, h->gbuf, h->Bbuf,
+                               h->Hlr, h->costbuf, act, n_act);
+            prof_end(h);
+        }
+        prof_begin(h, 2);
+        if (h->pb == 3) hipLaunchKernelGGL((k_lm_step<3, 0>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gbuf, h->Bbuf, h->costbuf,
+                                           h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hlr, act, n_act, 2, sh.gx, h->dgbuf, hiu, h->lr_window);
+        else hipLaunchKernelGGL((k_lm_step<4, 0>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gbuf, h->Bbuf, h->costbuf,
+                                h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hlr, act, n_act, 2, sh.gx, h->dgbuf, hiu, h->lr_window);
+        prof_end(h);
+        prof_begin(h, 7);
+        if (h->pb == 3) hipLaunchKernelGGL((k_lm_back<3>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf, h->gtbuf, h->dgbuf, act, n_act);
+        else hipLaunchKernelGGL((k_lm_back<4>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf, h->gtbuf, h->dgbuf, act, n_act);
+        prof_end(h);
+    };
+    return lm_drive(h, B, iterate);
+}
+
+// Outputs of a finished LM run: k_finalize (tau: the shutter delays, or null), then `more` (what else the caller enqueues there, or
+// empty), then the sequence states and the max |joint equality| of every sequence are read back; the stream is drained.
+static cpe_status lm_readback(cpe_handle* h, int B, int N, const double* meas, double* q, double* dq, double* ddq, double* positions, double* meas_err,
+                              const double* tau, const std::function<void()>& more, std::vector<SeqState>& hs, std::vector<double>& hc) {
+    const size_t F = (size_t)B * N;
     HIPCHK(hipMemsetAsync(h->cmax, 0, sizeof(double) * B, h->stream));
-    hipLaunchKernelGGL(k_finalize, dim3((unsigned)F), dim3(WAVE), lds_fk(m), h->stream, h->dm, h->st, N, F, h->qbuf, meas, q, dq, ddq, positions, meas_err,
+    hipLaunchKernelGGL(k_finalize, dim3((unsigned)F), dim3(WAVE), lds_fk(h->hm), h->stream, h->dm, h->st, N, F, h->qbuf, meas, q, dq, ddq, positions, meas_err,
                        reinterpret_cast<unsigned long long*>(h->cmax), tau);
+    if (more) more();
     HIPCHK(hipGetLastError());
-    std::vector<double> hc(B);
-    std::vector<SeqState> hs(B);
+    hs.resize(B);
+    hc.resize(B);
     HIPCHK(hipMemcpyAsync(hs.data(), h->st, sizeof(SeqState) * B, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(hc.data(), h->cmax, sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     prof_collect(h);
+    return CPE_OK;
+}
+
+// The cost terms each model reports (SeqState.terms).  The kinematic model: measurements, constant-acceleration model, pose prior,
+// motion prior.  The physics-based model has no motion prior; its model cost is terms[4].
+static void kinematic_costs(const SeqState& S, double scale, cpe_stats& o) {
+    o.cost_meas = S.terms[0]; o.cost_model = S.terms[1]; o.cost_pose = S.terms[3]; o.cost_motion = S.terms[4];
+    o.cost = scale * (S.terms[0] + S.terms[1] + S.terms[3] + S.terms[4]);
+}
+static void kinetic_costs(const SeqState& S, double scale, cpe_stats& o) {
+    o.cost_meas = S.terms[0]; o.cost_model = S.terms[4]; o.cost_pose = S.terms[3]; o.cost_motion = 0.0;
+    o.cost = scale * (S.terms[0] + S.terms[3] + S.terms[4]);
+}
+
+// Status of every sequence and, when `stats` is given, its cpe_stats (`iters_extra[b]` iterations of earlier runs added).  Returns the worst status.
+static cpe_status seq_stats(const cpe_handle* h, int B, const std::vector<SeqState>& hs, const std::vector<double>& hc, const std::vector<int>* iters_extra,
+                            void (*costs)(const SeqState&, double, cpe_stats&), cpe_stats* stats) {
     cpe_status worst = CPE_OK;
     for (int b = 0; b < B; b++) {
         const SeqState& S = hs[b];
@@ -960,21 +1017,29 @@ static cpe_status lm_finish(cpe_handle* h, int B, int N, const double* meas, dou
             cpe_stats& o = stats[b];
             o.status = sb; o.iterations = S.iters + (iters_extra ? (*iters_extra)[b] : 0); o.lambda = S.lambda; o.max_constraint = hc[b];
             o.max_bound_violation = S.maxviol; o.outer = S.outer; o._pad = 0;
-            o.cost_meas = S.terms[0]; o.cost_model = S.terms[1]; o.cost_pose = S.terms[3]; o.cost_motion = S.terms[4];
-            o.cost = h->opts.cost_scale * (S.terms[0] + S.terms[1] + S.terms[3] + S.terms[4]);
+            costs(S, h->opts.cost_scale, o);
         }
     }
     return worst;
+}
+
+// outputs and statistics of a finished kinematic LM run; `iters_extra[b]` iterations of earlier runs are added
+static cpe_status lm_finish(cpe_handle* h, int B, int N, const double* meas, double* q, double* dq, double* ddq, double* positions, double* meas_err,
+                            const double* tau, cpe_stats* stats, const std::vector<int>* iters_extra) {
+    std::vector<SeqState> hs;
+    std::vector<double> hc;
+    const cpe_status s = lm_readback(h, B, N, meas, q, dq, ddq, positions, meas_err, tau, nullptr, hs, hc);
+    if (s != CPE_OK) return s;
+    return seq_stats(h, B, hs, hc, iters_extra, kinematic_costs, stats);
 }
 
 cpe_status cpe_solve(cpe_handle* h, int32_t B, int32_t N, const double* q_init, const double* meas, const double* weight,
                      double* q, double* dq, double* ddq, double* positions, double* meas_err, cpe_stats* stats) {
     if (!h || !q_init || !meas || !weight || !q) return fail(CPE_BAD_ARG, "null argument");
     if ((dq == nullptr) != (ddq == nullptr)) return fail(CPE_BAD_ARG, "dq and ddq must be given together");
-    if (B < 0 || N < 0) return fail(CPE_BAD_ARG, "negative size");
-    const size_t F = (size_t)B * N;
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
     if (F == 0) return CPE_OK;
-    if (F > 0x7fffffffULL) return fail(CPE_BAD_ARG, "too many frames for one launch");
     HIPCHK(hipSetDevice(h->device));
     cpe_status s = ensure_ws(h, B, N);
     if (s != CPE_OK) return s;
@@ -1035,10 +1100,10 @@ cpe_status cpe_solve_shutter(cpe_handle* h, int32_t B, int32_t N, const double* 
                              double* tau_out, cpe_stats* stats, int32_t* rounds_out) {
     if (!h || !q_init || !meas || !weight || !q || !tau_out) return fail(CPE_BAD_ARG, "null argument");
     if ((dq == nullptr) != (ddq == nullptr)) return fail(CPE_BAD_ARG, "dq and ddq must be given together");
-    if (B < 0 || N < 0 || max_rounds < 1 || !(tau_bound > 0) || !(tol_tau > 0)) return fail(CPE_BAD_ARG, "bad size or tolerance");
-    const size_t F = (size_t)B * N;
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
+    if (max_rounds < 1 || !(tau_bound > 0) || !(tol_tau > 0)) return fail(CPE_BAD_ARG, "bad round count or tolerance");
     if (F == 0) return CPE_OK;
-    if (F > 0x7fffffffULL) return fail(CPE_BAD_ARG, "too many frames for one launch");
     HIPCHK(hipSetDevice(h->device));
     cpe_status s = ensure_ws(h, B, N);
     if (s != CPE_OK) return s;
@@ -1207,24 +1272,33 @@ static cpe_status ensure_kws(cpe_handle* h, int B, int N) {
     if (F <= h->kws_frames) return CPE_OK;
     free_kws(h);
     const int BB = CPE_NX * CPE_NX;
-    HIPCHK(hipMalloc(&h->fbuf, sizeof(double) * 2 * F * KIN_LS));
-    HIPCHK(hipMalloc(&h->kmu, sizeof(double) * F * 4 * KIN_MU));
-    HIPCHK(hipMalloc(&h->kmut, sizeof(double) * F * 2 * CPE_MAX_MOTORS));
-    HIPCHK(hipMalloc(&h->kmus, sizeof(double) * F * 2 * CPE_MAX_NQ));
-    HIPCHK(hipMalloc(&h->Jbuf, sizeof(double) * F * KIN_JSTRIDE));
-    HIPCHK(hipMalloc(&h->Abuf, sizeof(double) * F * CPE_MAX_NQ * KIN_LS));
-    HIPCHK(hipMalloc(&h->pieces, sizeof(double) * 2 * F * KIN_PIECE));
-    HIPCHK(hipMalloc(&h->pmeta, sizeof(int) * 2 * F * (KIN_LS + 1)));
-    HIPCHK(hipMalloc(&h->gTb, sizeof(double) * 2 * (F + 2) * KIN_NC3));
-    HIPCHK(hipMalloc(&h->dstat, sizeof(double) * 2 * F * KIN_STAT));
-    HIPCHK(hipMalloc(&h->slackb, sizeof(double) * 2 * F * CPE_MAX_NQ));
-    HIPCHK(hipMalloc(&h->Tbuf, sizeof(double) * (F + 2) * 6 * BB));
-    HIPCHK(hipMalloc(&h->gk, sizeof(double) * F * CPE_NX));
-    HIPCHK(hipMalloc(&h->Bk, sizeof(double) * F * BB));
-    HIPCHK(hipMalloc(&h->Hk, sizeof(double) * F * 3 * BB));
-    const void* ks[] = {(const void*)&k_dyn_eval, (const void*)&k_dyn_assemble, (const void*)&k_dyn_schur, (const void*)&k_dyn_jac};
-    for (const void* k : ks) HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    auto& w = h->kws_bufs;
+    HIPCHK(ws_alloc(w, h->fbuf, 2 * F * KIN_LS));
+    HIPCHK(ws_alloc(w, h->kmu, F * 4 * KIN_MU));
+    HIPCHK(ws_alloc(w, h->kmut, F * 2 * CPE_MAX_MOTORS));
+    HIPCHK(ws_alloc(w, h->kmus, F * 2 * CPE_MAX_NQ));
+    HIPCHK(ws_alloc(w, h->Jbuf, F * KIN_JSTRIDE));
+    HIPCHK(ws_alloc(w, h->Abuf, F * CPE_MAX_NQ * KIN_LS));
+    HIPCHK(ws_alloc(w, h->pieces, 2 * F * KIN_PIECE));
+    HIPCHK(ws_alloc(w, h->pmeta, 2 * F * (KIN_LS + 1)));
+    HIPCHK(ws_alloc(w, h->gTb, 2 * (F + 2) * KIN_NC3));
+    HIPCHK(ws_alloc(w, h->dstat, 2 * F * KIN_STAT));
+    HIPCHK(ws_alloc(w, h->slackb, 2 * F * CPE_MAX_NQ));
+    HIPCHK(ws_alloc(w, h->Tbuf, (F + 2) * 6 * BB));
+    HIPCHK(ws_alloc(w, h->gk, F * CPE_NX));
+    HIPCHK(ws_alloc(w, h->Bk, F * BB));
+    HIPCHK(ws_alloc(w, h->Hk, F * 3 * BB));
     h->kws_frames = F;
+    return CPE_OK;
+}
+
+// Cold start of the physics terms (after state_reset): node forces and their multipliers, those of the box on the residual and, with
+// torque boxes, theirs.
+static cpe_status kin_state_reset(cpe_handle* h, size_t F, bool torque_box) {
+    HIPCHK(hipMemsetAsync(h->fbuf, 0, sizeof(double) * 2 * F * KIN_LS, h->stream));
+    HIPCHK(hipMemsetAsync(h->kmu, 0, sizeof(double) * F * 4 * KIN_MU, h->stream));
+    HIPCHK(hipMemsetAsync(h->kmus, 0, sizeof(double) * F * 2 * CPE_MAX_NQ, h->stream));
+    if (torque_box) HIPCHK(hipMemsetAsync(h->kmut, 0, sizeof(double) * F * 2 * CPE_MAX_MOTORS, h->stream));
     return CPE_OK;
 }
 
@@ -1249,46 +1323,15 @@ static void launch_dyn_pieces(cpe_handle* h, int N, int first, size_t Fw, const 
     prof_end(h);
 }
 
-cpe_status cpe_solve_kinetic(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q_init, const double* meas,
-                             const double* weight, const int32_t* stance, double* q, double* dq, double* ddq, double* positions,
-                             double* meas_err, double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats, cpe_kinetic_stats* kstats) {
-    return cpe_solve_kinetic_fixed(h, opt, B, N, q_init, meas, weight, stance, nullptr, q, dq, ddq, positions, meas_err, tau, lambda, grf, slack, stats, kstats);
-}
-
-static cpe_status solve_kinetic_impl(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q_init, const double* meas,
-                                     const double* weight, const int32_t* stance, const double* grf_fixed, const double* tau_box, const double* grf_box, double* q, double* dq, double* ddq,
-                                     double* positions, double* meas_err, double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats,
-                                     cpe_kinetic_stats* kstats);
-cpe_status cpe_solve_kinetic_fixed(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q_init, const double* meas,
-                                   const double* weight, const int32_t* stance, const double* grf_fixed, double* q, double* dq, double* ddq,
-                                   double* positions, double* meas_err, double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats,
-                                   cpe_kinetic_stats* kstats) {
-    return solve_kinetic_impl(h, opt, B, N, q_init, meas, weight, stance, grf_fixed, nullptr, nullptr, q, dq, ddq, positions, meas_err, tau, lambda, grf, slack, stats, kstats);
-}
-cpe_status cpe_solve_kinetic_force_box(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q_init, const double* meas,
-                                       const double* weight, const int32_t* stance, const double* grf_box, double* q, double* dq, double* ddq,
-                                       double* positions, double* meas_err, double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats,
-                                       cpe_kinetic_stats* kstats) {
-    if (!grf_box) return fail(CPE_BAD_ARG, "null argument");
-    return solve_kinetic_impl(h, opt, B, N, q_init, meas, weight, stance, nullptr, nullptr, grf_box, q, dq, ddq, positions, meas_err, tau, lambda, grf, slack, stats, kstats);
-}
-cpe_status cpe_solve_kinetic_bounded(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q_init, const double* meas,
-                                     const double* weight, const int32_t* stance, const double* tau_box, double* q, double* dq, double* ddq,
-                                     double* positions, double* meas_err, double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats,
-                                     cpe_kinetic_stats* kstats) {
-    if (!tau_box) return fail(CPE_BAD_ARG, "null argument");
-    return solve_kinetic_impl(h, opt, B, N, q_init, meas, weight, stance, nullptr, tau_box, nullptr, q, dq, ddq, positions, meas_err, tau, lambda, grf, slack, stats, kstats);
-}
 static cpe_status solve_kinetic_impl(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q_init, const double* meas,
                                      const double* weight, const int32_t* stance, const double* grf_fixed, const double* tau_box, const double* grf_box, double* q, double* dq, double* ddq,
                                      double* positions, double* meas_err, double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats,
                                      cpe_kinetic_stats* kstats) {
     if (!h || !opt || !q_init || !meas || !weight || !stance || !q) return fail(CPE_BAD_ARG, "null argument");
     if ((dq == nullptr) != (ddq == nullptr)) return fail(CPE_BAD_ARG, "dq and ddq must be given together");
-    if (B < 0 || N < 0) return fail(CPE_BAD_ARG, "negative size");
-    const size_t F = (size_t)B * N;
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
     if (F == 0) return CPE_OK;
-    if (F > 0x7fffffffULL) return fail(CPE_BAD_ARG, "too many frames for one launch");
     if (h->pb != 3) return fail(CPE_BAD_ARG, "the physics-based model runs on the half-bandwidth-3 solver");
     HIPCHK(hipSetDevice(h->device));
     cpe_status s = ensure_ws(h, B, N);
@@ -1299,16 +1342,8 @@ static cpe_status solve_kinetic_impl(cpe_handle* h, const cpe_kinetic_options* o
     if (s != CPE_OK) return s;
     const DevModel& m = h->hm;
     const size_t Fw = F;
-    hipLaunchKernelGGL(k_state_init, dim3((unsigned)F), dim3(WAVE), 0, h->stream, h->dm, q_init, h->qbuf);
-    HIPCHK(hipMemsetAsync(h->st, 0, sizeof(SeqState) * B, h->stream));
-    HIPCHK(hipMemsetAsync(h->mu, 0, sizeof(double) * (F * (size_t)(m.nb > 0 ? m.nb : 1) * 2), h->stream));
-    HIPCHK(hipMemsetAsync(h->fbuf, 0, sizeof(double) * 2 * F * KIN_LS, h->stream));
-    HIPCHK(hipMemsetAsync(h->kmu, 0, sizeof(double) * F * 4 * KIN_MU, h->stream));
-    HIPCHK(hipMemsetAsync(h->kmus, 0, sizeof(double) * F * 2 * CPE_MAX_NQ, h->stream));
-    if (tau_box) HIPCHK(hipMemsetAsync(h->kmut, 0, sizeof(double) * F * 2 * CPE_MAX_MOTORS, h->stream));
-    LmParams prm;
-    prm.tol_step = h->opts.tol_step; prm.tol_cost = h->opts.tol_cost; prm.lambda0 = h->opts.lambda0; prm.B = B; prm.N = N;
-    prm.bound_tol = h->opts.bound_tol; prm.max_outer = h->opts.max_outer; prm.max_iter = h->opts.max_iter;
+    if ((s = state_reset(h, B, N, q_init)) != CPE_OK || (s = kin_state_reset(h, F, tau_box != nullptr)) != CPE_OK) return s;
+    const LmParams prm = lm_params(h, B, N);
     const size_t ldsn = lds_normal(m, h->gmm_k, h->gmm_dim);
     // One iteration: per-frame terms and physics terms of the evaluated buffer, accept / reject (new damping), elimination of the node
     // forces at that damping for the CURRENT iterate, band system, factor + solve + next trial.
@@ -1338,49 +1373,18 @@ static cpe_status solve_kinetic_impl(cpe_handle* h, const cpe_kinetic_options* o
         hipLaunchKernelGGL((k_lm_back<3>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf, h->gtbuf, h->dgbuf, act, n_act);
         prof_end(h);
     };
-    iterate(1, nullptr, nullptr, B);
-    HIPCHK(hipGetLastError());
-    const int window = std::min(B, h->n_cu * 2);
-    constexpr int POLL = 4;
-    const long per_seq = (long)h->opts.max_iter + 2L * (h->opts.max_outer > 0 ? h->opts.max_outer : 0) + POLL;
-    const long max_rounds = ((long)(B + window - 1) / window + 1) * per_seq;
-    bool pending[2] = {false, false};
-    int slot = 0;
-    for (long it = 0; it < max_rounds; it += POLL) {
-        for (int k = 0; k < POLL; k++) {
-            hipLaunchKernelGGL(k_build_act, dim3(1), dim3(256), 0, h->stream, h->st, B, window, h->act, h->n_act);
-            iterate(0, h->act, h->n_act, window);
-        }
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(h->poll_host + slot, h->n_act, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipEventRecord(h->poll_ev[slot], h->stream));
-        pending[slot] = true;
-        const int prev = 1 - slot;
-        if (pending[prev]) {
-            HIPCHK(hipEventSynchronize(h->poll_ev[prev]));
-            pending[prev] = false;
-            if (h->poll_host[prev] == 0) break;
-        }
-        slot = prev;
-    }
-    HIPCHK(hipMemsetAsync(h->cmax, 0, sizeof(double) * B, h->stream));
-    hipLaunchKernelGGL(k_finalize, dim3((unsigned)F), dim3(WAVE), lds_fk(m), h->stream, h->dm, h->st, N, Fw, h->qbuf, meas, q, dq, ddq, positions, meas_err,
-                       reinterpret_cast<unsigned long long*>(h->cmax));
-    hipLaunchKernelGGL(k_dyn_outputs, dim3((unsigned)F), dim3(64), 0, h->stream, h->dk, h->st, N, Fw, h->fbuf, h->Abuf, nullptr, tau, lambda, grf);
-    HIPCHK(hipGetLastError());
-    std::vector<double> hc(B);
-    std::vector<SeqState> hs(B);
-    HIPCHK(hipMemcpyAsync(hs.data(), h->st, sizeof(SeqState) * B, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(hc.data(), h->cmax, sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    prof_collect(h);
+    if ((s = lm_drive(h, B, iterate)) != CPE_OK) return s;
+    std::vector<SeqState> hs;
+    std::vector<double> hc;
+    s = lm_readback(h, B, N, meas, q, dq, ddq, positions, meas_err, nullptr, [&] {
+        hipLaunchKernelGGL(k_dyn_outputs, dim3((unsigned)F), dim3(64), 0, h->stream, h->dk, h->st, N, Fw, h->fbuf, h->Abuf, nullptr, tau, lambda, grf);
+    }, hs, hc);
+    if (s != CPE_OK) return s;
     // slack and the per-node statistics live in the buffer of each sequence's final iterate
-    std::vector<double> hd;
-    if (kstats) hd.resize(2 * F * KIN_STAT);
-    if (kstats) HIPCHK(hipMemcpyAsync(hd.data(), h->dstat, sizeof(double) * 2 * F * KIN_STAT, hipMemcpyDeviceToHost, h->stream));
-    std::vector<int> hit;                                  // last word of every node's meta record: Newton iterations of its force solve
+    std::vector<double> hd(kstats ? 2 * F * KIN_STAT : 0);
+    std::vector<int> hit(kstats ? 2 * F : 0);               // last word of every node's meta record: Newton iterations of its force solve
     if (kstats) {
-        hit.resize(2 * F);
+        HIPCHK(hipMemcpyAsync(hd.data(), h->dstat, sizeof(double) * 2 * F * KIN_STAT, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipMemcpy2DAsync(hit.data(), sizeof(int), h->pmeta + KIN_LS, sizeof(int) * (KIN_LS + 1), sizeof(int), 2 * F, hipMemcpyDeviceToHost, h->stream));
     }
     if (slack)
@@ -1388,19 +1392,9 @@ static cpe_status solve_kinetic_impl(cpe_handle* h, const cpe_kinetic_options* o
             HIPCHK(hipMemcpy2DAsync(slack + (size_t)b * N * m.nq, sizeof(double) * m.nq, h->slackb + ((size_t)hs[b].cur * F + (size_t)b * N) * CPE_MAX_NQ,
                                     sizeof(double) * CPE_MAX_NQ, sizeof(double) * m.nq, N, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    cpe_status worst = CPE_OK;
-    for (int b = 0; b < B; b++) {
-        const SeqState& S = hs[b];
-        const cpe_status sb = S.status == 1 ? CPE_OK : ((S.status == 0 || S.status == 3) ? CPE_MAX_ITER : CPE_NUMERICAL);
-        if (sb > worst) worst = sb;
-        if (stats) {
-            cpe_stats& o = stats[b];
-            o.status = sb; o.iterations = S.iters; o.lambda = S.lambda; o.max_constraint = hc[b];
-            o.max_bound_violation = S.maxviol; o.outer = S.outer; o._pad = 0;
-            o.cost_meas = S.terms[0]; o.cost_model = S.terms[4]; o.cost_pose = S.terms[3]; o.cost_motion = 0.0;
-            o.cost = h->opts.cost_scale * (S.terms[0] + S.terms[3] + S.terms[4]);
-        }
-        if (kstats) {
+    if (kstats)
+        for (int b = 0; b < B; b++) {
+            const SeqState& S = hs[b];
             cpe_kinetic_stats& k = kstats[b];
             memset(&k, 0, sizeof(k));
             for (int n = 0; n < N; n++) {
@@ -1410,8 +1404,33 @@ static cpe_status solve_kinetic_impl(cpe_handle* h, const cpe_kinetic_options* o
                 k.inner_max = std::max(k.inner_max, hit[(size_t)S.cur * F + (size_t)b * N + n]);
             }
         }
-    }
-    return worst;
+    return seq_stats(h, B, hs, hc, nullptr, kinetic_costs, stats);
+}
+
+cpe_status cpe_solve_kinetic(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q_init, const double* meas,
+                             const double* weight, const int32_t* stance, double* q, double* dq, double* ddq, double* positions,
+                             double* meas_err, double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats, cpe_kinetic_stats* kstats) {
+    return cpe_solve_kinetic_fixed(h, opt, B, N, q_init, meas, weight, stance, nullptr, q, dq, ddq, positions, meas_err, tau, lambda, grf, slack, stats, kstats);
+}
+cpe_status cpe_solve_kinetic_fixed(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q_init, const double* meas,
+                                   const double* weight, const int32_t* stance, const double* grf_fixed, double* q, double* dq, double* ddq,
+                                   double* positions, double* meas_err, double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats,
+                                   cpe_kinetic_stats* kstats) {
+    return solve_kinetic_impl(h, opt, B, N, q_init, meas, weight, stance, grf_fixed, nullptr, nullptr, q, dq, ddq, positions, meas_err, tau, lambda, grf, slack, stats, kstats);
+}
+cpe_status cpe_solve_kinetic_force_box(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q_init, const double* meas,
+                                       const double* weight, const int32_t* stance, const double* grf_box, double* q, double* dq, double* ddq,
+                                       double* positions, double* meas_err, double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats,
+                                       cpe_kinetic_stats* kstats) {
+    if (!grf_box) return fail(CPE_BAD_ARG, "null argument");
+    return solve_kinetic_impl(h, opt, B, N, q_init, meas, weight, stance, nullptr, nullptr, grf_box, q, dq, ddq, positions, meas_err, tau, lambda, grf, slack, stats, kstats);
+}
+cpe_status cpe_solve_kinetic_bounded(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q_init, const double* meas,
+                                     const double* weight, const int32_t* stance, const double* tau_box, double* q, double* dq, double* ddq,
+                                     double* positions, double* meas_err, double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats,
+                                     cpe_kinetic_stats* kstats) {
+    if (!tau_box) return fail(CPE_BAD_ARG, "null argument");
+    return solve_kinetic_impl(h, opt, B, N, q_init, meas, weight, stance, nullptr, tau_box, nullptr, q, dq, ddq, positions, meas_err, tau, lambda, grf, slack, stats, kstats);
 }
 
 // diagnostic building block (as cpe_eval_normal): one evaluation of the physics terms at Euler q, multipliers zero, forces from a cold start.
@@ -1420,23 +1439,17 @@ static cpe_status solve_kinetic_impl(cpe_handle* h, const cpe_kinetic_options* o
 cpe_status cpe_eval_kinetic_nodes(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q, const double* meas, const double* weight,
                                   const int32_t* stance, double* f, double* stat, double* g, double* Huu, double* Hfu, double* Hff, int32_t* meta) {
     if (!h || !opt || !q || !meas || !weight || !stance) return fail(CPE_BAD_ARG, "null argument");
-    if (B < 0 || N < 0) return fail(CPE_BAD_ARG, "negative size");
-    const size_t F = (size_t)B * N;
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
     if (F == 0) return CPE_OK;
-    if (F > 0x7fffffffULL) return fail(CPE_BAD_ARG, "too many frames for one launch");
     if (h->pb != 3) return fail(CPE_BAD_ARG, "the physics-based model runs on the half-bandwidth-3 solver");
     HIPCHK(hipSetDevice(h->device));
     cpe_status s = ensure_ws(h, B, N);                     // the workspaces first: build_kin records pointers into them
     if (s != CPE_OK) return s;
     if ((s = ensure_kws(h, B, N)) != CPE_OK) return s;
     if ((s = build_kin(h, opt)) != CPE_OK) return s;
+    if ((s = state_reset(h, B, N, q)) != CPE_OK || (s = kin_state_reset(h, F, false)) != CPE_OK) return s;
     const DevModel& m = h->hm;
-    hipLaunchKernelGGL(k_state_init, dim3((unsigned)F), dim3(WAVE), 0, h->stream, h->dm, q, h->qbuf);
-    HIPCHK(hipMemsetAsync(h->st, 0, sizeof(SeqState) * B, h->stream));
-    HIPCHK(hipMemsetAsync(h->mu, 0, sizeof(double) * (F * (size_t)(m.nb > 0 ? m.nb : 1) * 2), h->stream));
-    HIPCHK(hipMemsetAsync(h->fbuf, 0, sizeof(double) * 2 * F * KIN_LS, h->stream));
-    HIPCHK(hipMemsetAsync(h->kmu, 0, sizeof(double) * F * 4 * KIN_MU, h->stream));
-    HIPCHK(hipMemsetAsync(h->kmus, 0, sizeof(double) * F * 2 * CPE_MAX_NQ, h->stream));
     hipLaunchKernelGGL(FRAME_NORMAL(h->gmm_k == 0), dim3((unsigned)F), dim3(WAVE), lds_normal(m, h->gmm_k, h->gmm_dim), h->stream, h->dm, h->st, N, 1, F, h->qbuf, meas, weight,
                        h->gbuf, h->Bbuf, h->costbuf, h->mu, h->gambuf, h->pri, nullptr, nullptr, ShutterArgs{nullptr, nullptr, nullptr});
     launch_dyn_eval(h, N, 1, F, stance, nullptr, nullptr, B);
@@ -1490,8 +1503,10 @@ cpe_status cpe_debug_lm_stamps(unsigned long long* out32) {
 cpe_status cpe_eval_resjac_host(cpe_handle* h, int32_t B, int32_t N, const double* q, const double* meas, const double* weight,
                                 double* r, double* J, double* eps, double* cost) {
     if (!h || !q || !meas || !r || !J || !eps) return fail(CPE_BAD_ARG, "null argument");
-    const size_t F = (size_t)B * N; const DevModel& m = h->hm;
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
     if (F == 0) return CPE_OK;
+    const DevModel& m = h->hm;
     HIPCHK(hipSetDevice(h->device));
     DevBuf dq_, dm_, dw_, dr_, dJ_, de_, dc_;
     const size_t nm = F * m.C * m.L;
@@ -1513,8 +1528,10 @@ cpe_status cpe_eval_resjac_host(cpe_handle* h, int32_t B, int32_t N, const doubl
 cpe_status cpe_solve_host(cpe_handle* h, int32_t B, int32_t N, const double* q_init, const double* meas, const double* weight,
                           double* q, double* dq, double* ddq, double* positions, double* meas_err, cpe_stats* stats) {
     if (!h || !q_init || !meas || !weight || !q) return fail(CPE_BAD_ARG, "null argument");
-    const size_t F = (size_t)B * N; const DevModel& m = h->hm;
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
     if (F == 0) return CPE_OK;
+    const DevModel& m = h->hm;
     HIPCHK(hipSetDevice(h->device));
     const size_t nm = F * m.C * m.L;
     DevBuf di, dm_, dw_, oq, odq, oddq, op, ome;

@@ -725,6 +725,37 @@ def test_error_behaviour_of_the_abi(sk25, cams6, gpu_handle_factory):
     assert lib.cpe_tensorise_dlc(*args(1, 1, 25)) == abi.BAD_ARG and b"slot" in lib.cpe_last_error()
     assert lib.cpe_tensorise_dlc(*args(1, 0, 0)) == abi.BAD_ARG
     assert lib.cpe_tensorise_dlc(*args(1, 0, 25)) == abi.OK
+    # a negative B or N is refused by every entry point that takes (B, N), with valid non-null pointers: only the size check stands
+    # between such a call and a launch
+    dbuf, hbuf = torch.zeros(4096, dtype=torch.float64, device="cuda:0"), np.zeros(4096)
+    p, hp = dbuf.data_ptr(), hbuf.ctypes.data
+    eo, do, go = C.byref(abi.EomOptions()), C.byref(abi.DynOptions()), C.byref(abi.GrfOptions())
+    ko = C.byref(abi.default_kinetic_options(skeleton.dyn_options("phantom")))
+    stats, kstats, rounds = (abi.Stats * 1)(), (abi.KineticStats * 1)(), C.c_int32(0)
+    calls = {
+        "cpe_forward_kinematics": lambda B, N: lib.cpe_forward_kinematics(h._h, B, N, p, p, p),
+        "cpe_project_joints": lambda B, N: lib.cpe_project_joints(h._h, B, N, p),
+        "cpe_eval_normal": lambda B, N: lib.cpe_eval_normal(h._h, B, N, *[p] * 8),
+        "cpe_eval_resjac": lambda B, N: lib.cpe_eval_resjac(h._h, B, N, *[p] * 7),
+        "cpe_reproject": lambda B, N: lib.cpe_reproject(h._h, B, N, p, p),
+        "cpe_marker_velocities": lambda B, N: lib.cpe_marker_velocities(h._h, B, N, p, p, p),
+        "cpe_eom_rows": lambda B, N: lib.cpe_eom_rows(h._h, eo, B, N, *[p] * 4),
+        "cpe_eom_residual": lambda B, N: lib.cpe_eom_residual(h._h, do, B, N, *[p] * 7),
+        "cpe_grf_fit": lambda B, N: lib.cpe_grf_fit(h._h, go, B, N, *[p] * 7),
+        "cpe_solve": lambda B, N: lib.cpe_solve(h._h, B, N, *[p] * 8, stats),
+        "cpe_solve_shutter": lambda B, N: lib.cpe_solve_shutter(h._h, B, N, p, p, p, 1e-3, 4, 1e-6, *[p] * 6, stats, C.byref(rounds)),
+        "cpe_solve_kinetic": lambda B, N: lib.cpe_solve_kinetic(h._h, ko, B, N, *[p] * 13, stats, kstats),
+        "cpe_solve_kinetic_fixed": lambda B, N: lib.cpe_solve_kinetic_fixed(h._h, ko, B, N, *[p] * 14, stats, kstats),
+        "cpe_solve_kinetic_force_box": lambda B, N: lib.cpe_solve_kinetic_force_box(h._h, ko, B, N, *[p] * 14, stats, kstats),
+        "cpe_solve_kinetic_bounded": lambda B, N: lib.cpe_solve_kinetic_bounded(h._h, ko, B, N, *[p] * 14, stats, kstats),
+        "cpe_eval_kinetic_nodes": lambda B, N: lib.cpe_eval_kinetic_nodes(h._h, ko, B, N, *[p] * 11),
+        "cpe_eval_resjac_host": lambda B, N: lib.cpe_eval_resjac_host(h._h, B, N, *[hp] * 7),
+        "cpe_solve_host": lambda B, N: lib.cpe_solve_host(h._h, B, N, *[hp] * 8, stats),
+    }
+    for name, call in calls.items():
+        for B, N in ((-2, 1), (1, -2)):
+            assert call(B, N) == abi.BAD_ARG, (name, B, N)
+            assert b"negative size" in lib.cpe_last_error(), (name, B, N, lib.cpe_last_error())
 
 
 @pytest.mark.parametrize("C", [1, 2, 8])
