@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: it generates the B sequences of the timed pass, pre-heats and warms up, times
+the K steps, writes the outputs when asked and prints the JSON line.  `--full` adds every other leg: the cost variant of the kernel,
+the 24-marker size, the solves of configs 2-4 with their per-kernel rooflines, and the CPU baselines (`--no-*` trim it).
 
 N > 1 works both ways: started by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (RANK / LOCAL_RANK /
 WORLD_SIZE in the environment), or started plainly as `python bench.py --gpus N`, in which case THIS process starts the N ranks
@@ -9,8 +13,8 @@ as child processes before anything here has touched the GPU, waits for them and 
 
 Workload (config.workload = "cfg2"): synthetic 200-frame x 6-camera x 25-marker sequences, phantom skeleton, fp64.
 One "step" = one pass of the residual+Jacobian hot path (k_resjac) over a batch of B sequences resident in HBM.  `value` =
-frames/s of that pass over all ranks; full-trajectory solves/s (cpe_solve: LM + block-banded Cholesky) are timed next to it and
-reported in "solves" with their own roofline object.  Sequences are independent: the global list of sequences is dealt to the
+frames/s of that pass over all ranks; with --full, full-trajectory solves/s (cpe_solve: LM + block-banded Cholesky) are timed next to it
+and reported in "solves" with their own roofline object.  Sequences are independent: the global list of sequences is dealt to the
 ranks round-robin (cheetah_pose_estimation_amd.sharding), there is no collective on the data path (weak scaling).
 """
 import argparse
@@ -450,6 +454,8 @@ def main():
     ap.add_argument("--solve-batch", type=int, default=8192, help="sequences per GPU for the solve timing (8 MB of solver workspace each: 64 GB of the 288 GB)")
     ap.add_argument("--markers", type=int, default=25)
     ap.add_argument("--frames", type=int, default=200)
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run the legs the headline figure does not need: the cost variant, "
+                    "24 markers, the solves of configs 2-4 with per-kernel rooflines and the CPU baselines (the --no-* options below trim them)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-solve", action="store_true")
     ap.add_argument("--no-l24", action="store_true", help="skip the extra 24-marker residual+Jacobian measurement")
@@ -503,13 +509,15 @@ def main():
     opts = abi.default_options(120.0)
     # ---- synthetic inputs, generated BEFORE this process touches the GPU (the generator forks numpy-only workers).  SURVEY 8d: the sequence with
     # global index b has seed 1234 + b; the global list is dealt to the ranks round-robin: no two ranks (and no two slots of a rank) share one
+    # (a rank's first B sequences do not depend on Bgen: a plain run times the same inputs as a --full one)
     B = args.batch
-    Bgen = max(B, 0 if args.no_solve else args.solve_batch)
+    solve = args.full and not args.no_solve
+    Bgen = max(B, args.solve_batch if solve else 0)
     workers = args.gen_workers if args.gen_workers > 0 else max(1, min(16, usable_cores()[0] // max(1, min(world, 8))))
     mine = sharding.shard_indices(world * Bgen, rank, world)
     d = make_sequences("run", L, None, N, [1234 + int(i) for i in mine], workers)
-    d24 = make_sequences("run", 24, None, N, [1234 + int(i) for i in mine[:B]], workers) if (L == 25 and world == 1 and not args.no_l24) else None
-    extra = world == 1 and not args.no_solve and not args.no_extra
+    d24 = make_sequences("run", 24, None, N, [1234 + int(i) for i in mine[:B]], workers) if (args.full and L == 25 and world == 1 and not args.no_l24) else None
+    extra = world == 1 and solve and not args.no_extra
     d3 = make_sequences("run", 24, [2], N, [1234 + i for i in range(args.cfg3_batch)], workers) if extra else None
     d4 = make_sequences("gallop", 24, [2] if args.cfg4_cams == 1 else None, N, [4321 + i for i in range(args.cfg4_batch)], workers) if extra else None
     torch.cuda.set_device(local)
@@ -589,7 +597,7 @@ def main():
         dumped = {"dir": args.dump_outputs, "names": ["residual", "jacobian", "accel_slack"], "sequences": [int(mine[i]) for i in seqs], "frames": nf}
         progress(f"rank {rank}: outputs of the last timed step written to {args.dump_outputs}")
     # the variant that also reads the weights and writes the robust cost (k_resjac<true>), for the record
-    ms_cost = time_resjac(h, t, r, J, eps, cost, 5, stream) if world == 1 else None
+    ms_cost = time_resjac(h, t, r, J, eps, cost, 5, stream) if args.full and world == 1 else None
 
     # "also report L=24" -- the reference's own 24 markers, same cameras and sequence shape, same kernel
     l24 = None
@@ -612,7 +620,7 @@ def main():
         del t24
 
     solves = None
-    if not args.no_solve:
+    if solve:
         Bs = args.solve_batch
         del t
         ts_ = upload(torch, {k: v[:Bs] for k, v in d.items()}, dev, keys=("q_init", "meas", "weight"))
@@ -704,7 +712,7 @@ def main():
         ach = bpf * B * N / (kern_ms * 1e-3)
         out = {
             "metric": "frames/sec residual+Jacobian eval + full-traj solves/sec, 200-frame 6-cam seq",
-            "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f64", "data": "synthetic",
             "preheat": {"seconds": args.preheat, "launches": n_heat, "note": "untimed launches of the same kernel before the warm-up: steady memory rate of the device (tools/ab_resjac_box.py)"},
@@ -718,7 +726,7 @@ def main():
             bc = resjac_bytes_per_frame(C, L, S, sk.nq, True)
             out["with_cost"] = {"kernel": "k_resjac<true>", "kernel_ms": ms_cost, "bytes_per_frame": bc, "value": B * N / (ms_cost * 1e-3),
                                 "frac": bc * B * N / (ms_cost * 1e-3) / HBM_PEAK}
-        if not args.no_cpu and world == 1:          # the CPU leg is timed on rank 0 of the single-GPU run only
+        if args.full and not args.no_cpu and world == 1:          # the CPU leg is timed on rank 0 of the single-GPU run only
             out["cpu_baseline"] = cpu_baseline(sk, cams, opts, {k: v[:32] for k, v in d.items()})
         print(json.dumps(out), flush=True)
     if h is not None:

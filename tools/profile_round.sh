@@ -7,9 +7,9 @@ set -o pipefail
 R=${1:-r03}
 OUT=/root/repo/gpurun_out
 T=/root/repo/tools
-PMC_ARGS="--steps 1 --warmup 0 --batch 512 --solve-batch 512 --cfg3-batch 256 --cfg4-batch 16 --no-cpu --no-l24 --gen-workers 1"
+PMC_ARGS="--full --steps 1 --warmup 0 --batch 512 --solve-batch 512 --cfg3-batch 256 --cfg4-batch 16 --no-cpu --no-l24 --gen-workers 1"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d /tmp/${R}_stats -o ${R} -- python3 /root/repo/bench.py --steps 10 --warmup 10 --solve-batch 2048 --cfg4-batch 16 --no-cpu --gen-workers 1 > $OUT/${R}_bench_rocprof.log 2>&1 &&
+rocprofv3 --kernel-trace --stats -d $TMPDIR/${R}_stats -o ${R} -- python3 $T/../bench.py --full --steps 10 --warmup 10 --solve-batch 2048 --cfg4-batch 16 --no-cpu --gen-workers 1 > $OUT/${R}_bench_rocprof.log 2>&1 &&
 python3 $T/export_rocprof_stats.py /tmp/${R}_stats/${R}_results.db $OUT/${R}_kernel_stats.csv && echo "stats pass done" &&
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d /tmp/${R}_pmc_fetch -o ${R} -- python3 /root/repo/bench.py $PMC_ARGS > $OUT/${R}_pmc_fetch.log 2>&1 && echo "fetch pass done" &&
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d /tmp/${R}_pmc_write -o ${R} -- python3 /root/repo/bench.py $PMC_ARGS > $OUT/${R}_pmc_write.log 2>&1 && echo "write pass done" &&

@@ -8,7 +8,7 @@ WRITE_SIZE costs 2, so the two never share a pass; SQ has 8 slots):
 ONE derived TCC counter per pass: round 1's `error code 38: Request exceeds the capabilities of the hardware to collect` (gpurun_out/pmc_m2.log)
 came from asking for TA_* and several TCC_EA0_* counters together with a derived one -- the profile configuration is rejected before any kernel
 runs.  The round-1 pass that stayed silent for 7 minutes had the full-size workload (13.7 GB per launch, every dispatch replayed per counter
-group): PMC passes here use `--steps 1 --warmup 0 --batch 256 --solve-batch 256 --no-cpu --no-l24`.  Put `python3 bench.py ...` directly after
+group): PMC passes here use `--full --steps 1 --warmup 0 --batch 256 --solve-batch 256 --no-cpu --no-l24`.  Put `python3 bench.py ...` directly after
 `--` (no env / bash -c wrappers: the profiler's preloaded library has initialised the GPU before the program starts).
 
 usage: python tools/summarise_pmc.py <fetch_dir> <write_dir> <out.json> <frames per launch> <kernel-substring>=<algorithmic bytes per frame> [...]
