@@ -80,6 +80,10 @@ def load():
     lib.cpe_solve_shutter.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_double, C.c_int32, C.c_double, vp, vp, vp, vp, vp, vp,
                                       C.POINTER(abi.Stats), C.POINTER(C.c_int32)]
     lib.cpe_solve_host.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(abi.Stats)]
+    lib.cpe_create_multi.argtypes = [C.c_int32, C.POINTER(abi.Skeleton), C.POINTER(abi.Camera), ip, C.POINTER(abi.Options), C.POINTER(abi.Priors),
+                                     C.c_int32, C.POINTER(C.c_void_p)]
+    lib.cpe_solve_ragged.argtypes = [vp, C.c_int32, C.c_int32, ip, ip, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(abi.Stats)]
+    lib.cpe_solve_ragged_host.argtypes = [vp, C.c_int32, C.c_int32, ip, ip, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(abi.Stats)]
     lib.cpe_eom_rows.argtypes = [vp, C.POINTER(abi.EomOptions), C.c_int32, C.c_int32, vp, vp, vp, vp]
     lib.cpe_eom_residual.argtypes = [vp, C.POINTER(abi.DynOptions), C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
     lib.cpe_grf_fit.argtypes = [vp, C.POINTER(abi.GrfOptions), C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
@@ -98,6 +102,26 @@ def _check(status: int, what: str, allow=(abi.OK,)):
     if status not in allow:
         raise CpeError(f"{what} failed with status {status}: {load().cpe_last_error().decode()}")
     return status
+
+
+def shape_signature(sk: abi.Skeleton) -> bytes:
+    """The part of a skeleton that models of one cpe_create_multi handle must share (include/cpe.h): link tree, markers' links, joints, bound pairs
+    and the relative-angle convention.  Link geometry, masses, marker offsets, bound limits and motion weights may differ."""
+    nl, L, nj, nb = sk.n_links, sk.n_markers, sk.n_joints, sk.n_bounds
+    nq = 3 + 3 * nl
+    parts = [np.array([nl, L, nj, nb], np.int32), np.ctypeslib.as_array(sk.parent)[:nl], np.ctypeslib.as_array(sk.marker_link)[:L],
+             np.ctypeslib.as_array(sk.joint_parent)[:nj], np.ctypeslib.as_array(sk.joint_child)[:nj], np.ctypeslib.as_array(sk.joint_kind)[:nj],
+             np.ctypeslib.as_array(sk.bound_a)[:nb], np.ctypeslib.as_array(sk.bound_b)[:nb], np.ctypeslib.as_array(sk.rel_ref)[:nq],
+             np.ctypeslib.as_array(sk.rel_sign)[:nq]]
+    return b"".join(np.ascontiguousarray(p).tobytes() for p in parts)
+
+
+SHARED_OPTIONS = ("lambda0", "tol_step", "tol_cost", "max_iter", "max_outer", "curvature", "bound_tol", "cost_scale")
+
+
+def shared_options_signature(opts: abi.Options) -> tuple:
+    """The options the models of one cpe_create_multi handle must share (the LM driver reads them per batch)"""
+    return tuple(getattr(opts, k) for k in SHARED_OPTIONS)
 
 
 def _ptr(t):
@@ -129,6 +153,36 @@ class Handle:
         self.S = self.lib.cpe_jacobian_slots(self._h)
         self.nu = self.lib.cpe_num_independent(self._h)
         self.nq, self.L = sk.nq, sk.n_markers
+
+    @classmethod
+    def multi(cls, skels, cams_list, opts_list=None, priors: abi.Priors = None, device: int = 0) -> "Handle":
+        """One handle over several models of the same shape (cpe_create_multi): model k = (skels[k], cams_list[k], opts_list[k]).  Its
+        solve_ragged_host solves sequences of any of them, each with its own length, in one call."""
+        n = len(skels)
+        if n < 1 or len(cams_list) != n or (opts_list is not None and len(opts_list) != n):
+            raise ValueError("Handle.multi: one camera list and one options struct per skeleton")
+        opts_list = list(opts_list) if opts_list is not None else [abi.default_options() for _ in range(n)]
+        sks = (abi.Skeleton * n)(*skels)
+        cams = (abi.Camera * (n * abi.MAX_CAMS))()
+        for k, cl in enumerate(cams_list):
+            for c, cam in enumerate(cl):
+                cams[k * abi.MAX_CAMS + c] = cam
+        ncam = (C.c_int32 * n)(*[len(cl) for cl in cams_list])
+        ops = (abi.Options * n)(*opts_list)
+        self = cls.__new__(cls)
+        self.lib = load()
+        self._h = C.c_void_p()
+        st = self.lib.cpe_create_multi(n, sks, cams, ncam, ops, C.byref(priors) if priors is not None else None, device, C.byref(self._h))
+        if st == abi.NO_DEVICE:
+            raise CpeError("no HIP device visible: the solve path has no CPU fallback (" + self.lib.cpe_last_error().decode() + ")")
+        _check(st, "cpe_create_multi")
+        self.sk, self.cams, self.n_cams, self.opts = skels[0], cams_list[0], max(len(cl) for cl in cams_list), opts_list[0]
+        self.model_n_cams = [len(cl) for cl in cams_list]
+        self.device = device
+        self.S = self.lib.cpe_jacobian_slots(self._h)
+        self.nu = self.lib.cpe_num_independent(self._h)
+        self.nq, self.L = skels[0].nq, skels[0].n_markers
+        return self
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -278,6 +332,16 @@ class Handle:
                         _ptr(positions), _ptr(meas_err), stats, allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
         return st, list(stats)[:B]
 
+    def solve_ragged(self, model, n_frames, q_init, meas, weight, q, dq, ddq, positions, meas_err):
+        """cpe_solve_ragged on device tensors laid out for N_max = q_init.shape[1] frames and C_max cameras; model / n_frames: int sequences
+        (one per sequence).  Returns (status, [Stats])."""
+        B, N = q_init.shape[0], q_init.shape[1]
+        stats = (abi.Stats * max(B, 1))()
+        mo, nf = (C.c_int32 * max(B, 1))(*[int(m) for m in model]), (C.c_int32 * max(B, 1))(*[int(n) for n in n_frames])
+        st = self._call(self.lib.cpe_solve_ragged, "cpe_solve_ragged", B, N, mo, nf, _ptr(q_init), _ptr(meas), _ptr(weight), _ptr(q), _ptr(dq),
+                        _ptr(ddq), _ptr(positions), _ptr(meas_err), stats, allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
+        return st, list(stats)[:B]
+
     def solve_shutter(self, q_init, meas, weight, tau_bound, q, dq, ddq, positions, meas_err, tau, max_rounds=8, tol_tau=1e-6):
         """trajectory + per-camera shutter delays (acinoset_misc.py:283-285); device tensors, tau [B, C]"""
         B, N = q_init.shape[0], q_init.shape[1]
@@ -393,3 +457,33 @@ class Handle:
                                      _ptr(pos), _ptr(me), stats)
         _check(st, "cpe_solve_host", allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
         return dict(status=st, q=q, dq=dq, ddq=ddq, positions=pos, meas_err=me, stats=list(stats)[:B])
+
+    def solve_ragged_host(self, q_init_list, meas_list, weight_list, model_list=None):
+        """cpe_solve_ragged_host over sequences of their own length and model: q_init [N_b, nq], meas [N_b, C_m, L, 2], weight [N_b, C_m, L]
+        per sequence (C_m = the camera count of its model, model_list[b]; None = model 0 for all).  Pads, solves, unpads: returns dict(status,
+        q, dq, ddq, positions, meas_err = lists of per-sequence arrays of the sequence's own shapes, stats = list of Stats)."""
+        B = len(q_init_list)
+        models = [0] * B if model_list is None else [int(m) for m in model_list]
+        ncams = getattr(self, "model_n_cams", [self.n_cams])
+        if len(meas_list) != B or len(weight_list) != B or len(models) != B:
+            raise ValueError("solve_ragged_host: one q_init, meas, weight and model per sequence")
+        if any(m < 0 or m >= len(ncams) for m in models):
+            raise ValueError("solve_ragged_host: model index out of range")
+        lens = [int(np.shape(q)[0]) for q in q_init_list]
+        Nm, Cm, L, nq = max(lens), self.n_cams, self.L, self.nq
+        qi = np.zeros((B, Nm, nq)); me = np.zeros((B, Nm, Cm, L, 2)); we = np.zeros((B, Nm, Cm, L))
+        for b in range(B):
+            n, c = lens[b], ncams[models[b]]
+            if np.shape(meas_list[b]) != (n, c, L, 2) or np.shape(weight_list[b]) != (n, c, L) or np.shape(q_init_list[b]) != (n, nq):
+                raise ValueError(f"solve_ragged_host: sequence {b} does not have the shapes of its model ({n} frames, {c} cameras)")
+            qi[b, :n], me[b, :n, :c], we[b, :n, :c] = q_init_list[b], meas_list[b], weight_list[b]
+        q, dq, ddq = np.empty_like(qi), np.empty_like(qi), np.empty_like(qi)
+        pos, err = np.empty((B, Nm, L, 3)), np.empty((B, Nm, Cm, L, 2))
+        stats = (abi.Stats * max(B, 1))()
+        mo, nf = (C.c_int32 * max(B, 1))(*models), (C.c_int32 * max(B, 1))(*lens)
+        st = self.lib.cpe_solve_ragged_host(self._h, B, Nm, mo, nf, _ptr(qi), _ptr(me), _ptr(we), _ptr(q), _ptr(dq), _ptr(ddq), _ptr(pos), _ptr(err), stats)
+        _check(st, "cpe_solve_ragged_host", allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
+        cut = lambda a, b, c=None: np.ascontiguousarray(a[b, :lens[b]] if c is None else a[b, :lens[b], :c])
+        return dict(status=st, q=[cut(q, b) for b in range(B)], dq=[cut(dq, b) for b in range(B)], ddq=[cut(ddq, b) for b in range(B)],
+                    positions=[cut(pos, b) for b in range(B)], meas_err=[cut(err, b, ncams[models[b]]) for b in range(B)],
+                    stats=list(stats)[:B], padded=dict(q=q, dq=dq, ddq=ddq, positions=pos, meas_err=err))

@@ -27,6 +27,8 @@ struct cpe_handle {
     hipStream_t stream = nullptr;
     DevModel hm;                 // host copy
     DevModel* dm = nullptr;      // device copy
+    // cpe_create_multi: host copies of all the handle's models (models[0] = hm; empty for cpe_create) -- dm holds them in this order
+    std::vector<DevModel> models;
     cpe_options opts;
     // solver workspace (its device buffers are recorded in ws_bufs as they are allocated, see ws_alloc)
     size_t ws_frames = 0; int ws_B = 0;
@@ -36,6 +38,7 @@ struct cpe_handle {
     SeqState* st = nullptr;
     int* flag = nullptr;
     int* act = nullptr;          // [ws_B] sequences of the current launch window (written by k_build_act)
+    int2* rseq = nullptr;        // [ws_B] (model, frames) of every sequence of a cpe_solve_ragged call
     int* n_act = nullptr;        // device word: entries of act in use
     int* poll_host = nullptr;    // pinned host memory: two snapshots of n_act, read without draining the stream
     hipEvent_t poll_ev[2] = {nullptr, nullptr};
@@ -414,6 +417,7 @@ static cpe_status build_model(const cpe_skeleton* s, const cpe_camera* cams, int
 
 // the plain variant of k_frame_normal (no Gaussian-mixture prior, no shutter delay) writes H straight to HBM and needs 6 KB less LDS per wave
 #define FRAME_NORMAL(plain) ((plain) ? k_frame_normal<true> : k_frame_normal<false>)
+#define FRAME_NORMAL_RAGGED(plain) ((plain) ? k_frame_normal<true, true> : k_frame_normal<false, true>)
 static size_t lds_fk(const DevModel& m) { return sizeof(double) * (m.nq + 6 * m.nl + 36 * m.nl + 3 * m.L + 23 * m.C); }
 static size_t lds_normal(const DevModel& m, int gmm_k = 0, int gmm_dim = 0, bool shutter = false) {
     // g (and, unless the plain variant writes H straight to HBM, H | g) overlay the S rows, which are dead once Dp is built
@@ -427,6 +431,23 @@ static size_t lds_normal(const DevModel& m, int gmm_k = 0, int gmm_dim = 0, bool
     if (shutter) n += 15 * m.C + 6 * m.L + 6;          // shift | coefficients | rc | Mc per camera, M1 per marker, M2
     return sizeof(double) * n;
 }
+// the dynamic LDS a ragged launch needs: the most any of the handle's models needs
+static size_t lds_fk_all(const cpe_handle* h) {
+    size_t n = lds_fk(h->hm);
+    for (const DevModel& m : h->models) n = std::max(n, lds_fk(m));
+    return n;
+}
+static size_t lds_normal_all(const cpe_handle* h) {
+    size_t n = lds_normal(h->hm, h->gmm_k, h->gmm_dim);
+    for (const DevModel& m : h->models) n = std::max(n, lds_normal(m, h->gmm_k, h->gmm_dim));
+    return n;
+}
+static int n_models(const cpe_handle* h) { return h->models.empty() ? 1 : (int)h->models.size(); }
+static int cams_max(const cpe_handle* h) {
+    int c = h->hm.C;
+    for (const DevModel& m : h->models) c = std::max(c, m.C);
+    return c;
+}
 
 extern "C" {
 
@@ -439,11 +460,12 @@ void cpe_default_options(cpe_options* o) {
 }
 
 void cpe_destroy(cpe_handle* h);
+// models: the models cpe_create_multi has built already (h->hm is models[0]), or null: build the one of (skel, cams, opts)
 static cpe_status create_impl(cpe_handle* h, const cpe_skeleton* skel, const cpe_camera* cams, int32_t n_cams, const cpe_options* opts,
-                              const cpe_priors* priors, bool use_pri) {
+                              const cpe_priors* priors, bool use_pri, const std::vector<DevModel>* models = nullptr) {
     const int device = h->device;
-    cpe_status s = build_model(skel, cams, n_cams, opts, h->hm);
-    if (s != CPE_OK) return s;
+    if (models) { h->models = *models; h->hm = h->models[0]; }
+    else if (cpe_status s = build_model(skel, cams, n_cams, opts, h->hm); s != CPE_OK) return s;
     HIPCHK(hipSetDevice(device));
     {
         hipDeviceProp_t prop;
@@ -460,8 +482,8 @@ static cpe_status create_impl(cpe_handle* h, const cpe_skeleton* skel, const cpe
     for (int i = 0; i < 2; i++) HIPCHK(hipEventCreateWithFlags(&h->poll_ev[i], hipEventDisableTiming));
     HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->poll_host), 2 * sizeof(int), hipHostMallocDefault));
     HIPCHK(hipMalloc(&h->n_act, sizeof(int)));
-    HIPCHK(hipMalloc(&h->dm, sizeof(DevModel)));
-    HIPCHK(hipMemcpy(h->dm, &h->hm, sizeof(DevModel), hipMemcpyHostToDevice));
+    HIPCHK(hipMalloc(&h->dm, sizeof(DevModel) * n_models(h)));
+    HIPCHK(hipMemcpy(h->dm, h->models.empty() ? &h->hm : h->models.data(), sizeof(DevModel) * n_models(h), hipMemcpyHostToDevice));
     HIPCHK(hipMalloc(&h->flag, sizeof(int)));
     if (use_pri) {
         if (h->hm.nu != CPE_NX) return fail(CPE_BAD_ARG, "learned priors need the 28 relative angles of the reference's skeleton");
@@ -532,15 +554,21 @@ static cpe_status create_impl(cpe_handle* h, const cpe_skeleton* skel, const cpe
     return CPE_OK;
 }
 
-cpe_status cpe_create(const cpe_skeleton* skel, const cpe_camera* cams, int32_t n_cams, const cpe_options* opts,
-                      const cpe_priors* priors, int32_t device, cpe_handle** out) {
-    if (!skel || !cams || !opts || !out) return fail(CPE_BAD_ARG, "null argument");
-    const bool use_pri = priors && (priors->gmm_k > 0 || priors->lr_window > 0);
-    if (use_pri) {
+static cpe_status check_priors(const cpe_priors* priors, bool* use_pri) {
+    *use_pri = priors && (priors->gmm_k > 0 || priors->lr_window > 0);
+    if (*use_pri) {
         if (priors->gmm_k < 0 || priors->gmm_k > CPE_MAX_GMM || priors->gmm_dim < 0 || priors->gmm_dim > CPE_NX || (priors->gmm_k > 0 && priors->gmm_dim < 1))
             return fail(CPE_BAD_ARG, "pose prior: component count / dimension out of range");
         if (priors->lr_window < 0 || priors->lr_window > CPE_MAX_WINDOW) return fail(CPE_BAD_ARG, "motion prior: window out of range");
     }
+    return CPE_OK;
+}
+
+cpe_status cpe_create(const cpe_skeleton* skel, const cpe_camera* cams, int32_t n_cams, const cpe_options* opts,
+                      const cpe_priors* priors, int32_t device, cpe_handle** out) {
+    if (!skel || !cams || !opts || !out) return fail(CPE_BAD_ARG, "null argument");
+    bool use_pri;
+    if (cpe_status s = check_priors(priors, &use_pri); s != CPE_OK) return s;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(CPE_NO_DEVICE, "no HIP device: this library has no CPU fallback");
     if (device < 0 || device >= ndev) return fail(CPE_BAD_ARG, "device index out of range");
@@ -561,6 +589,63 @@ static void free_ws(cpe_handle* h) {       // the kinetic workspace goes with it
     free_kws(h);
     ws_free(h->ws_bufs);
     h->ws_frames = 0; h->ws_B = 0;
+}
+
+// The fields two models of one cpe_create_multi handle must share (include/cpe.h): the skeleton's shape, the relative-angle convention the priors
+// are built in, and the options the LM driver reads as launch parameters or applies on the host.  Returns the first field that differs, or null.
+static const char* shape_mismatch(const cpe_skeleton& a, const cpe_skeleton& b, const cpe_options& oa, const cpe_options& ob) {
+    auto same = [](const auto& x, const auto& y, int n) { return memcmp(&x, &y, sizeof(x[0]) * (size_t)n) == 0; };
+    if (a.n_links != b.n_links) return "n_links";
+    if (!same(a.parent, b.parent, a.n_links)) return "parent";
+    if (a.n_markers != b.n_markers) return "n_markers";
+    if (!same(a.marker_link, b.marker_link, a.n_markers)) return "marker_link";
+    if (a.n_joints != b.n_joints) return "n_joints";
+    if (!same(a.joint_parent, b.joint_parent, a.n_joints)) return "joint_parent";
+    if (!same(a.joint_child, b.joint_child, a.n_joints)) return "joint_child";
+    if (!same(a.joint_kind, b.joint_kind, a.n_joints)) return "joint_kind";
+    if (a.n_bounds != b.n_bounds) return "n_bounds";
+    if (!same(a.bound_a, b.bound_a, a.n_bounds)) return "bound_a";
+    if (!same(a.bound_b, b.bound_b, a.n_bounds)) return "bound_b";
+    const int nq = 3 + 3 * a.n_links;
+    if (!same(a.rel_ref, b.rel_ref, nq)) return "rel_ref";
+    if (!same(a.rel_sign, b.rel_sign, nq)) return "rel_sign";
+    if (oa.lambda0 != ob.lambda0) return "lambda0";
+    if (oa.tol_step != ob.tol_step) return "tol_step";
+    if (oa.tol_cost != ob.tol_cost) return "tol_cost";
+    if (oa.max_iter != ob.max_iter) return "max_iter";
+    if (oa.max_outer != ob.max_outer) return "max_outer";
+    if (oa.curvature != ob.curvature) return "curvature";
+    if (oa.bound_tol != ob.bound_tol) return "bound_tol";
+    if (oa.cost_scale != ob.cost_scale) return "cost_scale";
+    return nullptr;
+}
+
+cpe_status cpe_create_multi(int32_t n_models, const cpe_skeleton* skels, const cpe_camera* cams, const int32_t* n_cams, const cpe_options* opts,
+                            const cpe_priors* priors, int32_t device, cpe_handle** out) {
+    if (!skels || !cams || !n_cams || !opts || !out) return fail(CPE_BAD_ARG, "null argument");
+    if (n_models < 1) return fail(CPE_BAD_ARG, "n_models must be at least 1");
+    bool use_pri;
+    if (cpe_status s = check_priors(priors, &use_pri); s != CPE_OK) return s;
+    // every refusal below comes before the device is opened
+    std::vector<DevModel> models((size_t)n_models);
+    for (int k = 0; k < n_models; k++) {
+        if (cpe_status s = build_model(&skels[k], cams + (size_t)k * CPE_MAX_CAMS, n_cams[k], &opts[k], models[k]); s != CPE_OK)   // (checks the counts)
+            return fail(s, std::string("cpe_create_multi: model ") + std::to_string(k) + ": " + g_err);
+        if (k > 0)
+            if (const char* field = shape_mismatch(skels[0], skels[k], opts[0], opts[k]))
+                return fail(CPE_BAD_ARG, std::string("cpe_create_multi: model ") + std::to_string(k) + " differs from model 0 in " + field);
+        if (k > 0 && (models[k].nu != models[0].nu || memcmp(models[k].indep, models[0].indep, sizeof(models[0].indep)) != 0))
+            return fail(CPE_BAD_ARG, std::string("cpe_create_multi: model ") + std::to_string(k) + " differs from model 0 in its independent dofs");
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(CPE_NO_DEVICE, "no HIP device: this library has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(CPE_BAD_ARG, "device index out of range");
+    cpe_handle* h = new cpe_handle();
+    h->device = device; h->opts = opts[0];
+    const cpe_status s = create_impl(h, &skels[0], cams, n_cams[0], &opts[0], priors, use_pri, &models);
+    if (s != CPE_OK) { cpe_destroy(h); return s; }
+    *out = h;
+    return CPE_OK;
 }
 
 void cpe_destroy(cpe_handle* h) {
@@ -846,15 +931,18 @@ static cpe_status ensure_ws(cpe_handle* h, int B, int N) {
     HIPCHK(ws_alloc(w, h->cmax, F));
     HIPCHK(ws_alloc(w, h->st, B));
     HIPCHK(ws_alloc(w, h->act, B));
+    HIPCHK(ws_alloc(w, h->rseq, B));
     if (h->lr_window > 0) HIPCHK(ws_alloc(w, h->Hlr, 2 * F * h->pb * nu * nu));
     h->ws_frames = F; h->ws_B = B;
     return CPE_OK;
 }
 
 // Cold start of every sequence from Euler q (device pointer): state buffer 0 = (q, alpha), sequence states and bound multipliers zero.
-static cpe_status state_reset(cpe_handle* h, int B, int N, const double* q) {
+// rg: the ragged table of cpe_solve_ragged (N = nmax), or null
+static cpe_status state_reset(cpe_handle* h, int B, int N, const double* q, const RaggedArgs* rg = nullptr) {
     const size_t F = (size_t)B * N;
-    hipLaunchKernelGGL(k_state_init, dim3((unsigned)F), dim3(WAVE), 0, h->stream, h->dm, q, h->qbuf);   // Euler q -> (q, alpha)
+    if (rg) hipLaunchKernelGGL(k_state_init<true>, dim3((unsigned)F), dim3(WAVE), 0, h->stream, h->dm, q, h->qbuf, *rg);
+    else hipLaunchKernelGGL(k_state_init<>, dim3((unsigned)F), dim3(WAVE), 0, h->stream, h->dm, q, h->qbuf);   // Euler q -> (q, alpha)
     HIPCHK(hipMemsetAsync(h->st, 0, sizeof(SeqState) * B, h->stream));
     HIPCHK(hipMemsetAsync(h->mu, 0, sizeof(double) * n_mu(h->hm, F), h->stream));
     return CPE_OK;
@@ -872,7 +960,7 @@ cpe_status cpe_eval_normal(cpe_handle* h, int32_t B, int32_t N, const double* q,
     if ((s = state_reset(h, B, N, q)) != CPE_OK) return s;
     const DevModel& m = h->hm;
     hipLaunchKernelGGL(FRAME_NORMAL(h->gmm_k == 0), dim3((unsigned)F), dim3(WAVE), lds_normal(m, h->gmm_k, h->gmm_dim), h->stream, h->dm, h->st, N, 1, F, h->qbuf, meas, weight,
-                       h->gbuf, h->Bbuf, h->costbuf, h->mu, h->gambuf, h->pri, nullptr, nullptr, ShutterArgs{nullptr, nullptr, nullptr});
+                       h->gbuf, h->Bbuf, h->costbuf, h->mu, h->gambuf, h->pri, nullptr, nullptr, ShutterArgs{nullptr, nullptr, nullptr}, RaggedArgs{});
     HIPCHK(hipMemcpyAsync(g, h->gbuf, sizeof(double) * F * m.nu, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(Bm, h->Bbuf, sizeof(double) * F * m.nu * m.nu, hipMemcpyDeviceToDevice, h->stream));
     hipLaunchKernelGGL(k_gather_normal, dim3((unsigned)F), dim3(128), 0, h->stream, h->dm, F, h->qbuf, h->costbuf, h->gambuf, cost, gam, q_out);
@@ -937,27 +1025,54 @@ __global__ void k_reset_status(SeqState* __restrict__ st, int B) {
 
 // The LM run of cpe_solve on the handle's workspace: cold start from q_init (device pointer) or, with q_init == nullptr, a restart from
 // the current iterate of every sequence.  sh: shutter-delay buffers (all null = off).
-static cpe_status lm_run(cpe_handle* h, int B, int N, const double* q_init, const double* meas, const double* weight, ShutterArgs sh) {
+// rg: the ragged table of cpe_solve_ragged (N = nmax; no shutter delay), or null.
+static cpe_status lm_run(cpe_handle* h, int B, int N, const double* q_init, const double* meas, const double* weight, ShutterArgs sh,
+                         const RaggedArgs* rg = nullptr) {
     const DevModel& m = h->hm;
     const size_t Fw = (size_t)B * N;   // buffers are laid out for exactly this call's F (strides use F)
     if (q_init) {
-        const cpe_status s = state_reset(h, B, N, q_init);
+        const cpe_status s = state_reset(h, B, N, q_init, rg);
         if (s != CPE_OK) return s;
     } else hipLaunchKernelGGL(k_reset_status, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->st, B);
     const LmParams prm = lm_params(h, B, N);
-    const size_t ldsn = lds_normal(m, h->gmm_k, h->gmm_dim, sh.tau != nullptr);
+    const size_t ldsn = rg ? lds_normal_all(h) : lds_normal(m, h->gmm_k, h->gmm_dim, sh.tau != nullptr);
     const bool lr = h->lr_window > 0;
     // k_frame_normal (+ k_lr_band) on the evaluated buffer, then k_lm_step and k_lm_back
     auto iterate = [&](int first, const int* act, const int* n_act, int slots) {
         const unsigned gf = (unsigned)((size_t)slots * N);
         const double* hiu = lr ? reinterpret_cast<const double*>(reinterpret_cast<const char*>(h->pri) + offsetof(DevPriors, lr_HIu)) + CPE_NX * CPE_NX : nullptr;
+        if (rg) {      // the same launches in their ragged forms
+            prof_begin(h, 0);
+            hipLaunchKernelGGL(FRAME_NORMAL_RAGGED(h->gmm_k == 0), dim3(gf), dim3(WAVE), ldsn, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, meas, weight,
+                               h->gbuf, h->Bbuf, h->costbuf, h->mu, h->gambuf, h->pri, act, n_act, ShutterArgs{nullptr, nullptr, nullptr}, *rg);
+            prof_end(h);
+            if (lr) {
+                prof_begin(h, 1);
+                hipLaunchKernelGGL(k_lr_band<true>, dim3(gf), dim3(WAVE), 0, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, h->gambuf, h->pri, h->pb, h->gbuf,
+                                   h->Bbuf, h->Hlr, h->costbuf, act, n_act, *rg);
+                prof_end(h);
+            }
+            prof_begin(h, 2);
+            if (h->pb == 3) hipLaunchKernelGGL((k_lm_step<3, 0, true>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gbuf,
+                                               h->Bbuf, h->costbuf, h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hlr, act, n_act, 2, nullptr, h->dgbuf, hiu, h->lr_window, *rg);
+            else hipLaunchKernelGGL((k_lm_step<4, 0, true>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gbuf,
+                                    h->Bbuf, h->costbuf, h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hlr, act, n_act, 2, nullptr, h->dgbuf, hiu, h->lr_window, *rg);
+            prof_end(h);
+            prof_begin(h, 7);
+            if (h->pb == 3) hipLaunchKernelGGL((k_lm_back<3, true>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf,
+                                               h->gtbuf, h->dgbuf, act, n_act, *rg);
+            else hipLaunchKernelGGL((k_lm_back<4, true>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf,
+                                    h->gtbuf, h->dgbuf, act, n_act, *rg);
+            prof_end(h);
+            return;
+        }
         prof_begin(h, 0);
         hipLaunchKernelGGL(FRAME_NORMAL(h->gmm_k == 0 && sh.tau == nullptr), dim3(gf), dim3(WAVE), ldsn, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, meas, weight, h->gbuf, h->Bbuf,
-                           h->costbuf, h->mu, h->gambuf, h->pri, act, n_act, sh);
+                           h->costbuf, h->mu, h->gambuf, h->pri, act, n_act, sh, RaggedArgs{});
         prof_end(h);
         if (lr) {
             prof_begin(h, 1);
-            hipLaunchKernelGGL(k_lr_band, dim3(gf), dim3(WAVE), 0, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, h->gambuf, h->pri, h->pb, h->gbuf, h->Bbuf,
+            hipLaunchKernelGGL(k_lr_band<>, dim3(gf), dim3(WAVE), 0, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, h->gambuf, h->pri, h->pb, h->gbuf, h->Bbuf,
                                h->Hlr, h->costbuf, act, n_act);
             prof_end(h);
         }
@@ -977,12 +1092,16 @@ static cpe_status lm_run(cpe_handle* h, int B, int N, const double* q_init, cons
 
 // Outputs of a finished LM run: k_finalize (tau: the shutter delays, or null), then `more` (what else the caller enqueues there, or
 // empty), then the sequence states and the max |joint equality| of every sequence are read back; the stream is drained.
+// rg: the ragged table (N = nmax, tau null), or null.
 static cpe_status lm_readback(cpe_handle* h, int B, int N, const double* meas, double* q, double* dq, double* ddq, double* positions, double* meas_err,
-                              const double* tau, const std::function<void()>& more, std::vector<SeqState>& hs, std::vector<double>& hc) {
+                              const double* tau, const std::function<void()>& more, std::vector<SeqState>& hs, std::vector<double>& hc,
+                              const RaggedArgs* rg = nullptr) {
     const size_t F = (size_t)B * N;
     HIPCHK(hipMemsetAsync(h->cmax, 0, sizeof(double) * B, h->stream));
-    hipLaunchKernelGGL(k_finalize, dim3((unsigned)F), dim3(WAVE), lds_fk(h->hm), h->stream, h->dm, h->st, N, F, h->qbuf, meas, q, dq, ddq, positions, meas_err,
-                       reinterpret_cast<unsigned long long*>(h->cmax), tau);
+    if (rg) hipLaunchKernelGGL(k_finalize<true>, dim3((unsigned)F), dim3(WAVE), lds_fk_all(h), h->stream, h->dm, h->st, N, F, h->qbuf, meas, q, dq, ddq,
+                               positions, meas_err, reinterpret_cast<unsigned long long*>(h->cmax), nullptr, *rg);
+    else hipLaunchKernelGGL(k_finalize<>, dim3((unsigned)F), dim3(WAVE), lds_fk(h->hm), h->stream, h->dm, h->st, N, F, h->qbuf, meas, q, dq, ddq, positions, meas_err,
+                            reinterpret_cast<unsigned long long*>(h->cmax), tau);
     if (more) more();
     HIPCHK(hipGetLastError());
     hs.resize(B);
@@ -1025,10 +1144,10 @@ static cpe_status seq_stats(const cpe_handle* h, int B, const std::vector<SeqSta
 
 // outputs and statistics of a finished kinematic LM run; `iters_extra[b]` iterations of earlier runs are added
 static cpe_status lm_finish(cpe_handle* h, int B, int N, const double* meas, double* q, double* dq, double* ddq, double* positions, double* meas_err,
-                            const double* tau, cpe_stats* stats, const std::vector<int>* iters_extra) {
+                            const double* tau, cpe_stats* stats, const std::vector<int>* iters_extra, const RaggedArgs* rg = nullptr) {
     std::vector<SeqState> hs;
     std::vector<double> hc;
-    const cpe_status s = lm_readback(h, B, N, meas, q, dq, ddq, positions, meas_err, tau, nullptr, hs, hc);
+    const cpe_status s = lm_readback(h, B, N, meas, q, dq, ddq, positions, meas_err, tau, nullptr, hs, hc, rg);
     if (s != CPE_OK) return s;
     return seq_stats(h, B, hs, hc, iters_extra, kinematic_costs, stats);
 }
@@ -1046,6 +1165,39 @@ cpe_status cpe_solve(cpe_handle* h, int32_t B, int32_t N, const double* q_init, 
     s = lm_run(h, B, N, q_init, meas, weight, ShutterArgs{nullptr, nullptr, nullptr});
     if (s != CPE_OK) return s;
     return lm_finish(h, B, N, meas, q, dq, ddq, positions, meas_err, nullptr, stats, nullptr);
+}
+
+// The arguments of cpe_solve_ragged, checked before anything is launched: the (model, frames) table of the batch.
+static cpe_status ragged_table(const cpe_handle* h, int B, int N_max, const int32_t* model, const int32_t* n_frames, std::vector<int2>& seq) {
+    seq.resize((size_t)B);
+    for (int b = 0; b < B; b++) {
+        if (model[b] < 0 || model[b] >= n_models(h))
+            return fail(CPE_BAD_ARG, "cpe_solve_ragged: model index of sequence " + std::to_string(b) + " out of range");
+        if (n_frames[b] < 1 || n_frames[b] > N_max)
+            return fail(CPE_BAD_ARG, "cpe_solve_ragged: frame count of sequence " + std::to_string(b) + " outside 1..N_max");
+        seq[(size_t)b] = make_int2(model[b], n_frames[b]);
+    }
+    return CPE_OK;
+}
+
+cpe_status cpe_solve_ragged(cpe_handle* h, int32_t B, int32_t N_max, const int32_t* model, const int32_t* n_frames, const double* q_init,
+                            const double* meas, const double* weight, double* q, double* dq, double* ddq, double* positions, double* meas_err,
+                            cpe_stats* stats) {
+    if (!h || !model || !n_frames || !q_init || !meas || !weight || !q) return fail(CPE_BAD_ARG, "null argument");
+    if ((dq == nullptr) != (ddq == nullptr)) return fail(CPE_BAD_ARG, "dq and ddq must be given together");
+    size_t F;
+    if (cpe_status s = frames(B, N_max, &F); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    std::vector<int2> seq;
+    if (cpe_status s = ragged_table(h, B, N_max, model, n_frames, seq); s != CPE_OK) return s;
+    HIPCHK(hipSetDevice(h->device));
+    cpe_status s = ensure_ws(h, B, N_max);
+    if (s != CPE_OK) return s;
+    HIPCHK(hipMemcpyAsync(h->rseq, seq.data(), sizeof(int2) * B, hipMemcpyHostToDevice, h->stream));     // (seq outlives the stream: lm_finish drains it)
+    const RaggedArgs rg{h->rseq, N_max, cams_max(h)};
+    s = lm_run(h, B, N_max, q_init, meas, weight, ShutterArgs{nullptr, nullptr, nullptr}, &rg);
+    if (s != CPE_OK) return s;
+    return lm_finish(h, B, N_max, meas, q, dq, ddq, positions, meas_err, nullptr, stats, nullptr, &rg);
 }
 
 // ---- shutter-delay estimation (include/cpe.h, cpe_solve_shutter) ------------------------------------------------------------------
@@ -1351,7 +1503,7 @@ static cpe_status solve_kinetic_impl(cpe_handle* h, const cpe_kinetic_options* o
         const unsigned gf = (unsigned)((size_t)slots * N);
         prof_begin(h, 0);
         hipLaunchKernelGGL(FRAME_NORMAL(h->gmm_k == 0), dim3(gf), dim3(WAVE), ldsn, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, meas, weight, h->gbuf, h->Bbuf,
-                           h->costbuf, h->mu, h->gambuf, h->pri, act, n_act, ShutterArgs{nullptr, nullptr, nullptr});
+                           h->costbuf, h->mu, h->gambuf, h->pri, act, n_act, ShutterArgs{nullptr, nullptr, nullptr}, RaggedArgs{});
         prof_end(h);
         launch_dyn_eval(h, N, first, Fw, stance, act, n_act, slots);
         prof_begin(h, 2);
@@ -1451,7 +1603,7 @@ cpe_status cpe_eval_kinetic_nodes(cpe_handle* h, const cpe_kinetic_options* opt,
     if ((s = state_reset(h, B, N, q)) != CPE_OK || (s = kin_state_reset(h, F, false)) != CPE_OK) return s;
     const DevModel& m = h->hm;
     hipLaunchKernelGGL(FRAME_NORMAL(h->gmm_k == 0), dim3((unsigned)F), dim3(WAVE), lds_normal(m, h->gmm_k, h->gmm_dim), h->stream, h->dm, h->st, N, 1, F, h->qbuf, meas, weight,
-                       h->gbuf, h->Bbuf, h->costbuf, h->mu, h->gambuf, h->pri, nullptr, nullptr, ShutterArgs{nullptr, nullptr, nullptr});
+                       h->gbuf, h->Bbuf, h->costbuf, h->mu, h->gambuf, h->pri, nullptr, nullptr, ShutterArgs{nullptr, nullptr, nullptr}, RaggedArgs{});
     launch_dyn_eval(h, N, 1, F, stance, nullptr, nullptr, B);
     launch_dyn_pieces(h, N, 1, F, nullptr, nullptr, B);
     HIPCHK(hipGetLastError());
@@ -1523,6 +1675,35 @@ cpe_status cpe_eval_resjac_host(cpe_handle* h, int32_t B, int32_t N, const doubl
     if (cost && weight) HIPCHK(hipMemcpyAsync(cost, dc_.p, sizeof(double) * F, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return CPE_OK;
+}
+
+cpe_status cpe_solve_ragged_host(cpe_handle* h, int32_t B, int32_t N_max, const int32_t* model, const int32_t* n_frames, const double* q_init,
+                                 const double* meas, const double* weight, double* q, double* dq, double* ddq, double* positions, double* meas_err,
+                                 cpe_stats* stats) {
+    if (!h || !model || !n_frames || !q_init || !meas || !weight || !q) return fail(CPE_BAD_ARG, "null argument");
+    size_t F;
+    if (cpe_status s = frames(B, N_max, &F); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    std::vector<int2> seq;
+    if (cpe_status s = ragged_table(h, B, N_max, model, n_frames, seq); s != CPE_OK) return s;
+    const DevModel& m = h->hm;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t nm = F * cams_max(h) * m.L;
+    DevBuf di, dm_, dw_, oq, odq, oddq, op, ome;
+    HIPCHK(di.alloc(F * m.nq)); HIPCHK(dm_.alloc(nm * 2)); HIPCHK(dw_.alloc(nm)); HIPCHK(oq.alloc(F * m.nq));
+    HIPCHK(odq.alloc(F * m.nq)); HIPCHK(oddq.alloc(F * m.nq)); HIPCHK(op.alloc(F * m.L * 3)); HIPCHK(ome.alloc(nm * 2));
+    HIPCHK(hipMemcpyAsync(di.p, q_init, sizeof(double) * F * m.nq, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(dm_.p, meas, sizeof(double) * nm * 2, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(dw_.p, weight, sizeof(double) * nm, hipMemcpyHostToDevice, h->stream));
+    cpe_status s = cpe_solve_ragged(h, B, N_max, model, n_frames, di.p, dm_.p, dw_.p, oq.p, odq.p, oddq.p, op.p, ome.p, stats);
+    if (s < 0) return s;
+    HIPCHK(hipMemcpyAsync(q, oq.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
+    if (dq) HIPCHK(hipMemcpyAsync(dq, odq.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
+    if (ddq) HIPCHK(hipMemcpyAsync(ddq, oddq.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
+    if (positions) HIPCHK(hipMemcpyAsync(positions, op.p, sizeof(double) * F * m.L * 3, hipMemcpyDeviceToHost, h->stream));
+    if (meas_err) HIPCHK(hipMemcpyAsync(meas_err, ome.p, sizeof(double) * nm * 2, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return s;
 }
 
 cpe_status cpe_solve_host(cpe_handle* h, int32_t B, int32_t N, const double* q_init, const double* meas, const double* weight,

@@ -46,6 +46,11 @@ struct LmParams {
     double tol_step, tol_cost, lambda0, bound_tol;
     int32_t B, N, max_outer, max_iter;
 };
+// Ragged batch (cpe_solve_ragged, DESIGN.md 7): sequence b solves device model seq[b].x (an index into the handle's model array) over the
+// first seq[b].y frames of the nmax its buffers are laid out for; meas / weight / meas_err carry cstride cameras per frame.  The kernels of the
+// kinematic solve take it as a compile-time form (RAGGED = true, launched with the table); their plain forms never read it.
+struct RaggedArgs { const int2* seq; int nmax; int cstride; };
+
 #define COST_STRIDE 8   // per-frame cost record: meas, bound(AL), pose, clamped, max bound violation, autoregressive prior
 
 // --------------------------------------------------------------------------------------------------
@@ -88,9 +93,16 @@ __device__ __forceinline__ void leg_euler(const double* RB, const double* scB, d
 
 // --------------------------------------------------------------------------------------------------
 // initial state from an Euler q: alpha_r = rotation of R_B^T R_c about y.  One wave per frame.
-__global__ __launch_bounds__(WAVE) void k_state_init(const DevModel* __restrict__ M, const double* __restrict__ q, double* __restrict__ state) {
+template <bool RAGGED = false>
+__global__ __launch_bounds__(WAVE) void k_state_init(const DevModel* __restrict__ M, const double* __restrict__ q, double* __restrict__ state,
+                                                    RaggedArgs rg = RaggedArgs{}) {
     const int lane = threadIdx.x;
     const size_t f = blockIdx.x;
+    if constexpr (RAGGED) {                                // padding frames stay unset: nothing reads them
+        const int2 rs = rg.seq[f / (unsigned)rg.nmax];
+        if ((int)(f % (unsigned)rg.nmax) >= rs.y) return;
+        M += rs.x;
+    }
     const int nq = M->nq, ns = M->ns;
     if (lane < nq) state[f * ns + lane] = q[f * nq + lane];
     if (lane < M->nrev) {
@@ -121,7 +133,7 @@ __global__ __launch_bounds__(WAVE) void k_state_init(const DevModel* __restrict_
 // HBM, the few bound terms follow as global atomics -- which takes 6 KB off the wave's LDS: 11 waves per CU instead of 8, and this kernel's time
 // goes with 1 / occupancy (measured by padding its LDS: 8 waves 1.87 ms, 6 waves 2.32, 5 waves 3.19).
 struct ShutterArgs { const double* tau; double* gx; double* rcb; };
-template <bool PLAIN>
+template <bool PLAIN, bool RAGGED = false>
 __global__ __launch_bounds__(WAVE) void k_frame_normal(const DevModel* __restrict__ M, const SeqState* __restrict__ st,
                                                        int N, int which, size_t n_frames,
                                                        double* __restrict__ qbuf, const double* __restrict__ meas,
@@ -130,11 +142,17 @@ __global__ __launch_bounds__(WAVE) void k_frame_normal(const DevModel* __restric
                                                        double* __restrict__ mu, double* __restrict__ gambuf,
                                                        const DevPriors* __restrict__ pri, const int* __restrict__ act /* sequences of this launch, or null = all */,
                                                        const int* __restrict__ n_act /* entries of act in use (device word written by k_build_act), or null */,
-                                                       ShutterArgs sh = ShutterArgs{nullptr, nullptr, nullptr}) {
+                                                       ShutterArgs sh = ShutterArgs{nullptr, nullptr, nullptr},
+                                                       RaggedArgs rg = RaggedArgs{} /* RAGGED: N = nmax, no shutter delay */) {
     extern __shared__ double smem[];
     const int lane = threadIdx.x;
     if (n_act && (int)(blockIdx.x / (unsigned)N) >= *n_act) return;
     const int b = act ? act[blockIdx.x / (unsigned)N] : (int)(blockIdx.x / (unsigned)N);
+    if constexpr (RAGGED) {                              // frames past the sequence's own length leave at once
+        const int2 rs = rg.seq[b];
+        if ((int)(blockIdx.x % (unsigned)N) >= rs.y) return;
+        M += rs.x;
+    }
     const size_t f = (size_t)b * N + blockIdx.x % (unsigned)N;
     const SeqState S = st[b];
     if (S.status != 0) return;
@@ -286,7 +304,7 @@ __global__ __launch_bounds__(WAVE) void k_frame_normal(const DevModel* __restric
     // measurements and weights of the first PAIR_PF rounds of the pair loop and the multipliers of the bounds: loaded here, used two phases on
     // (this kernel is a latency chain -- its time goes with 1 / occupancy -- so an HBM round trip taken in the shadow of other work is time gained)
     constexpr int PAIR_PF = 3;
-    const size_t pair0 = f * (size_t)(C * L);
+    const size_t pair0 = f * (size_t)((RAGGED ? rg.cstride : C) * L);
     const int n_pairs = C * L;
     const int pt0 = lane < n_pairs ? lane : n_pairs - 1, pt1 = WAVE + lane < n_pairs ? WAVE + lane : n_pairs - 1,      // clamped: the loads
               pt2 = 2 * WAVE + lane < n_pairs ? 2 * WAVE + lane : n_pairs - 1;                                            // themselves are unconditional
@@ -633,11 +651,12 @@ __global__ __launch_bounds__(WAVE) void k_frame_normal(const DevModel* __restric
 // blocks (a, a-1..a-nk) to Hlr and the cost of slack_a to the frame's cost record.  x-space blocks: see DevPriors.
 // x = X' u with the constant X' of the cost pitch: the blocks in the reduced coordinates are constants of the model too (DevPriors::lr_PKu, lr_HIu) --
 // this kernel only picks and sums them (rounds 2-3 rebuilt X' per frame and multiplied X_a^T H_x X_b out in LDS: 1.7 ms per 51 200 frames).
+template <bool RAGGED = false>
 __global__ __launch_bounds__(WAVE) void k_lr_band(const DevModel* __restrict__ M, const SeqState* __restrict__ st, int N, int which,
                                                   size_t n_frames, const double* __restrict__ qbuf, const double* __restrict__ gambuf,
                                                   const DevPriors* __restrict__ pri, int nk, double* __restrict__ gbuf, double* __restrict__ Bbuf,
                                                   double* __restrict__ Hlr, double* __restrict__ costbuf, const int* __restrict__ act,
-                                                  const int* __restrict__ n_act) {
+                                                  const int* __restrict__ n_act, RaggedArgs rg = RaggedArgs{}) {
     if (n_act && (int)(blockIdx.x / (unsigned)N) >= *n_act) return;
     __shared__ double sx[(2 * CPE_MAX_WINDOW + 1) * CPE_NX];
     __shared__ double ssl[(CPE_MAX_WINDOW + 1) * CPE_NX];
@@ -646,6 +665,12 @@ __global__ __launch_bounds__(WAVE) void k_lr_band(const DevModel* __restrict__ M
     const int lane = threadIdx.x;
     const int b = act ? act[blockIdx.x / (unsigned)N] : (int)(blockIdx.x / (unsigned)N), a = (int)(blockIdx.x % (unsigned)N);
     const size_t f = (size_t)b * N + a;
+    int NL = N;                                          // N: the buffers' frames per sequence, NL: this sequence's length
+    if constexpr (RAGGED) {
+        const int2 rs = rg.seq[b];
+        if (a >= rs.y) return;
+        M += rs.x; NL = rs.y;
+    }
     const SeqState S = st[b];
     if (S.status != 0) return;
     const int buf = (which || S.al_pending) ? S.cur : 1 - S.cur;
@@ -658,7 +683,7 @@ __global__ __launch_bounds__(WAVE) void k_lr_band(const DevModel* __restrict__ M
     for (int t = lane; t < (2 * W + 1) * nu; t += WAVE) {
         const int d = t / nu, k = t - d * nu, n = a - W + d;
         double v = 0.0;
-        if (n >= 0 && n < N) {
+        if (n >= 0 && n < NL) {
             const double* qn = qs + (size_t)n * ns;
             const int r = M->rel_ref_u[k];
             v = M->rel_sign_u[k] * (cost_coord(M, qn, k) - (r >= 0 ? cost_coord(M, qn, r) : 0.0));
@@ -671,7 +696,7 @@ __global__ __launch_bounds__(WAVE) void k_lr_band(const DevModel* __restrict__ M
     for (int t = lane; t < (W + 1) * nu; t += WAVE) {
         const int d = t / nu, p = t - d * nu, n = a + d;
         double sl = 0.0;
-        if (n >= W && n < N) {
+        if (n >= W && n < NL) {
             sl = sx[(d + W) * nu + p] - pri->p.lr_b[p];
             // over the features the model uses (ascending: the same order of the same non-zero products as the dense double loop)
             const double* xs = sx + d * nu;
@@ -697,11 +722,11 @@ __global__ __launch_bounds__(WAVE) void k_lr_band(const DevModel* __restrict__ M
     if (lane < nu) { double gacc = 0.0; for (int r = 0; r < nu; r++) gacc += pri->Xc[r][lane] * sgx[r]; sgu[lane] = gacc; }
     wave_lds_sync();
     if (lane < nu) gbuf[fo * nu + lane] += sgu[lane];
-    const bool row_interior = a >= W && a <= N - W;          // every block of the row is the constant lr_HIu[k]: k_lm_step reads the table, not Hlr
+    const bool row_interior = a >= W && a <= NL - W;          // every block of the row is the constant lr_HIu[k]: k_lm_step reads the table, not Hlr
     for (int k = 0; k <= nk && k <= a; k++) {
         if (k > 0 && row_interior) break;
         // block (a, a - k): sum over the lags ta of frame a with tb = ta - k, terms n = a - ta + W inside [W, N-1]
-        const int ta_lo = k > a - N + 1 + W ? k : a - N + 1 + W, ta_hi = W < a ? W : a;
+        const int ta_lo = k > a - NL + 1 + W ? k : a - NL + 1 + W, ta_hi = W < a ? W : a;
         const bool interior = ta_lo == k && ta_hi == W;
         for (int t = lane; t < nu * nu; t += WAVE) {
             double v = 0.0;
@@ -962,7 +987,7 @@ __device__ __forceinline__ void p2_tiles(double* W, int n, int i, int tr, int g0
 // MODE 0: the whole step.  The physics-based model puts kernels between the two halves (the elimination of the node forces needs the
 // damping the accept step has just set): MODE 1 = accept / reject only, MODE 2 = assemble, factor, solve, trial only.
 // hb = number of buffers of gbuf / Bbuf / Hlr: 2 (indexed by the current buffer) or 1 (already those of the current iterate).
-template <int PB, int MODE = 0>
+template <int PB, int MODE = 0, bool RAGGED = false>
 __global__ __launch_bounds__(LM_THREADS, PB == 3 ? 2 : 1) void k_lm_step(const DevModel* __restrict__ M, SeqState* __restrict__ st,
                                                         LmParams prm, int first, double* __restrict__ qbuf,
                                                         const double* __restrict__ gbuf, const double* __restrict__ Bbuf,
@@ -974,7 +999,7 @@ __global__ __launch_bounds__(LM_THREADS, PB == 3 ? 2 : 1) void k_lm_step(const D
                                                         const double* __restrict__ gxbuf = nullptr /* shutter delay: cross-frame gradient parts [2][F][6], or null */,
                                                         double* __restrict__ dgbuf = nullptr /* [F][NU]: diagonal of H before damping, for k_lm_back */,
                                                         const double* __restrict__ HIu = nullptr /* motion prior: DevPriors::lr_HIu[1], the constant blocks of a frame away from the sequence ends */,
-                                                        int lrW = 0 /* its window */) {
+                                                        int lrW = 0 /* its window */, RaggedArgs rg = RaggedArgs{}) {
     if (n_act && (int)blockIdx.x >= *n_act) return;     // uniform: the whole workgroup leaves
     constexpr int RING = PB + 1;                       // frames in the sliding window
     constexpr int NBLK = RING * (RING + 1) / 2;        // lower-triangle blocks of the window
@@ -1003,9 +1028,12 @@ __global__ __launch_bounds__(LM_THREADS, PB == 3 ? 2 : 1) void k_lm_step(const D
 #ifdef CPE_LM_STAMPS
     unsigned long long* g_tu = nullptr;
 #endif
-    const int b = act ? act[blockIdx.x] : (int)blockIdx.x, N = prm.N, nq = M->ns;     // NOTE: nq is the STATE stride here (Euler q + leg angles)
+    const int b = act ? act[blockIdx.x] : (int)blockIdx.x, NS = prm.N;       // NS: the buffers' frames per sequence
+    int N = NS;                                                                // N: this sequence's length
+    if constexpr (RAGGED) { const int2 rs = rg.seq[b]; M += rs.x; N = rs.y; }
+    const int nq = M->ns;     // NOTE: nq is the STATE stride here (Euler q + leg angles)
     const int nrev = M->nrev, GS = GAM_STRIDE * nrev;
-    const size_t n_frames = (size_t)prm.B * N;
+    const size_t n_frames = (size_t)prm.B * NS;
     SeqState S = st[b];
     if (S.status != 0) return;
 #ifdef CPE_LM_STAMPS
@@ -1017,8 +1045,8 @@ __global__ __launch_bounds__(LM_THREADS, PB == 3 ? 2 : 1) void k_lm_step(const D
     if (MODE != 2) {
         const int mode = first ? 1 : (S.al_pending ? 2 : 0);     // 1/2: the CURRENT buffer was (re-)evaluated
         const int eb = mode ? S.cur : 1 - S.cur;
-        const double* cb = costbuf + ((size_t)eb * n_frames + (size_t)b * N) * COST_STRIDE;
-        const double* qe = qbuf + (size_t)eb * n_frames * nq + (size_t)b * N * nq;
+        const double* cb = costbuf + ((size_t)eb * n_frames + (size_t)b * NS) * COST_STRIDE;
+        const double* qe = qbuf + (size_t)eb * n_frames * nq + (size_t)b * NS * nq;
         double acc[6] = {0, 0, 0, 0, 0, 0};   // meas, model, bound, pose, clamped, autoregressive prior
         double vmax = 0.0;
         for (int n = tid; n < N; n += LM_THREADS) {
@@ -1095,14 +1123,14 @@ __global__ __launch_bounds__(LM_THREADS, PB == 3 ? 2 : 1) void k_lm_step(const D
     // ---------------- (2) forward: sliding-window block Cholesky + forward substitution
     const int cur = S.cur;
     const double lam = S.lambda;
-    const double* qc = qbuf + (size_t)cur * n_frames * nq + (size_t)b * N * nq;
+    const double* qc = qbuf + (size_t)cur * n_frames * nq + (size_t)b * NS * nq;
     const size_t hcur = hb == 2 ? (size_t)cur * n_frames : 0;
-    const double* gc = gbuf + (hcur + (size_t)b * N) * NU;
-    const double* Bc = Bbuf + (hcur + (size_t)b * N) * (NU * NU);
-    double* Lb = Lbuf + (size_t)b * N * RING * (NU * NU);
-    double* zb = zbuf + (size_t)b * N * NU;
-    double* gtb = gtbuf + (size_t)b * N * NU;
-    double* dgb = dgbuf + (size_t)b * N * NU;
+    const double* gc = gbuf + (hcur + (size_t)b * NS) * NU;
+    const double* Bc = Bbuf + (hcur + (size_t)b * NS) * (NU * NU);
+    double* Lb = Lbuf + (size_t)b * NS * RING * (NU * NU);
+    double* zb = zbuf + (size_t)b * NS * NU;
+    double* gtb = gtbuf + (size_t)b * NS * NU;
+    double* dgb = dgbuf + (size_t)b * NS * NU;
     const double mscale = 2.0 * M->ih2 * M->ih2;
 
     if (tid < NU) {
@@ -1114,8 +1142,8 @@ __global__ __launch_bounds__(LM_THREADS, PB == 3 ? 2 : 1) void k_lm_step(const D
     for (int t = tid; t < nq; t += LM_THREADS) scoord_of_state[t] = -1;
     __syncthreads();
     if (tid < NU) scoord_of_state[M->ucoord_src[tid]] = tid;
-    const double* gamc = gambuf + ((size_t)cur * n_frames + (size_t)b * N) * GS;
-    const double* Hlc = Hlr ? Hlr + (hcur + (size_t)b * N) * PB * (NU * NU) : nullptr;
+    const double* gamc = gambuf + ((size_t)cur * n_frames + (size_t)b * NS) * GS;
+    const double* Hlc = Hlr ? Hlr + (hcur + (size_t)b * NS) * PB * (NU * NU) : nullptr;
     __syncthreads();
 
     // motion-model Gauss-Newton term of element (i, j) of block (frame a, frame b): sum_p Gamma_a[p][i] w_p Gamma_b[p][j]
@@ -1277,7 +1305,7 @@ __global__ __launch_bounds__(LM_THREADS, PB == 3 ? 2 : 1) void k_lm_step(const D
             st_tu = tu;
             double gv = gc[(size_t)m * NU + lane];
             if (gxbuf && lane < 3) {        // the residuals of frames m+1, m+2 also depend on this frame's base position (shutter delay)
-                const double* gxc = gxbuf + ((size_t)cur * n_frames + (size_t)b * N) * 6;
+                const double* gxc = gxbuf + ((size_t)cur * n_frames + (size_t)b * NS) * 6;
                 if (m + 1 < N) gv += gxc[(size_t)(m + 1) * 6 + lane];
                 if (m + 2 < N) gv += gxc[(size_t)(m + 2) * 6 + 3 + lane];
             }
@@ -1620,7 +1648,7 @@ __global__ __launch_bounds__(LM_THREADS, PB == 3 ? 2 : 1) void k_lm_step(const D
     if (s_int[2]) {
         // factorisation failed (matrix not positive definite at this damping): raise lambda, retry next call
         for (size_t t = tid; t < (size_t)N * nq; t += LM_THREADS)
-            qbuf[(size_t)(1 - cur) * n_frames * nq + (size_t)b * N * nq + t] = qc[t];
+            qbuf[(size_t)(1 - cur) * n_frames * nq + (size_t)b * NS * nq + t] = qc[t];
         if (tid == 0) { S = st[b]; S.lambda *= 10.0; S.pred = 0.0; S.maxstep = 1.0; S.back_pending = 0; st[b] = S; }
 #ifdef CPE_LM_STAMPS
         if (tid == 0) atomicAdd(&g_lm_stamps[8], 1ull);       // factorisation failures over all workgroups
@@ -1640,10 +1668,11 @@ __global__ __launch_bounds__(LM_THREADS, PB == 3 ? 2 : 1) void k_lm_step(const D
 // registers, nothing to wait for but its own vmcnt), two columns ahead of wave 0, which owns the arithmetic: lane k < 28 holds component
 // k of delta_n; delta_{n+1..n+PB} sit in a small LDS ring and are read back as broadcasts.  One LDS barrier per column joins the two.
 #define BACK_SLOTS 3
-template <int PB>
+template <int PB, bool RAGGED = false>
 __global__ __launch_bounds__(2 * WAVE) void k_lm_back(const DevModel* __restrict__ M, SeqState* __restrict__ st, LmParams prm, double* __restrict__ qbuf,
                                                       const double* __restrict__ Lbuf, double* __restrict__ zbuf, const double* __restrict__ gtbuf,
-                                                      const double* __restrict__ dgbuf, const int* __restrict__ act, const int* __restrict__ n_act) {
+                                                      const double* __restrict__ dgbuf, const int* __restrict__ act, const int* __restrict__ n_act,
+                                                      RaggedArgs rg = RaggedArgs{}) {
     if (n_act && (int)blockIdx.x >= *n_act) return;
     constexpr int RING = PB + 1, COLD = RING * NU * NU;
     constexpr int COLB = COLD * 8, NCH = (COLB + 1023) / 1024;       // bytes per factor column, 1 KB LDS-DMA pieces per column
@@ -1652,10 +1681,13 @@ __global__ __launch_bounds__(2 * WAVE) void k_lm_back(const DevModel* __restrict
     __shared__ __attribute__((aligned(16))) double dsh[PB * NU];
     __shared__ double far_part[2 * NU];                       // [n & 1]: sum over blocks 2..PB of column n, left by wave 1 one step ahead
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int b = act ? act[blockIdx.x] : (int)blockIdx.x, N = prm.N, ns = M->ns;
+    const int b = act ? act[blockIdx.x] : (int)blockIdx.x, NS = prm.N;       // NS: the buffers' frames per sequence
+    int N = NS;                                                                // N: this sequence's length
+    if constexpr (RAGGED) { const int2 rs = rg.seq[b]; M += rs.x; N = rs.y; }
+    const int ns = M->ns;
     const SeqState S = st[b];
     if (S.status != 0 || !S.back_pending) return;             // uniform
-    const double* Lb = Lbuf + (size_t)b * N * COLD;
+    const double* Lb = Lbuf + (size_t)b * NS * COLD;
     const int k = lane < NU ? lane : NU - 1;                  // idle lanes shadow lane 27 (reads stay in bounds, results unused)
     for (int t = threadIdx.x; t < PB * NU; t += 2 * WAVE) dsh[t] = 0.0;
     if (threadIdx.x < 2 * NU) far_part[threadIdx.x] = 0.0;    // column N-1 has no later frames
@@ -1713,14 +1745,14 @@ __global__ __launch_bounds__(2 * WAVE) void k_lm_back(const DevModel* __restrict
     }
 
     // ---- wave 0: the arithmetic
-    const size_t n_frames = (size_t)prm.B * N;
+    const size_t n_frames = (size_t)prm.B * NS;
     const int cur = S.cur;
     const double lam = S.lambda;
-    double* zb = zbuf + (size_t)b * N * NU;
-    const double* gtb = gtbuf + (size_t)b * N * NU;
-    const double* dgb = dgbuf + (size_t)b * N * NU;
-    const double* qc = qbuf + ((size_t)cur * n_frames + (size_t)b * N) * ns;
-    double* qt = qbuf + ((size_t)(1 - cur) * n_frames + (size_t)b * N) * ns;
+    double* zb = zbuf + (size_t)b * NS * NU;
+    const double* gtb = gtbuf + (size_t)b * NS * NU;
+    const double* dgb = dgbuf + (size_t)b * NS * NU;
+    const double* qc = qbuf + ((size_t)cur * n_frames + (size_t)b * NS) * ns;
+    double* qt = qbuf + ((size_t)(1 - cur) * n_frames + (size_t)b * NS) * ns;
     // state entry p moves with coordinate ck (or with none)
     int ck0 = -1, ck1 = -1;
     for (int c = 0; c < NU; c++) { const int p = M->ucoord_src[c]; if (p == lane) ck0 = c; if (p == lane + WAVE) ck1 = c; }
@@ -2128,16 +2160,24 @@ __global__ __launch_bounds__(WAVE) void k_dyn_forces(const DevModel* __restrict_
 // solver outputs as CheetahEstimator.save writes them (acinoset_opt.py:289-361): q, dq, ddq (implicit
 // Euler with the free-initial-state gauge ddq0 = ddq1 = ddq2), marker positions, meas_err.
 // dynamic LDS: q[nq] | sc[6nl] | R[36nl] | pos[3L] | cam[23C]
+template <bool RAGGED = false>
 __global__ __launch_bounds__(WAVE) void k_finalize(const DevModel* __restrict__ M, const SeqState* __restrict__ st, int N,
                                                    size_t n_frames, const double* __restrict__ qbuf,
                                                    const double* __restrict__ meas, double* __restrict__ q,
                                                    double* __restrict__ dq, double* __restrict__ ddq,
                                                    double* __restrict__ positions, double* __restrict__ meas_err,
                                                    unsigned long long* __restrict__ cmax_seq /* [B] bit patterns of max |joint equality| */,
-                                                   const double* __restrict__ tau = nullptr /* shutter delays [B][C], or null */) {
+                                                   const double* __restrict__ tau = nullptr /* shutter delays [B][C], or null */,
+                                                   RaggedArgs rg = RaggedArgs{} /* RAGGED: N = nmax; frames and cameras past a sequence's own are written as zeros */) {
     extern __shared__ double smem[];
     const int lane = threadIdx.x;
+    int NL = N;                                          // N: the buffers' frames per sequence, NL: this sequence's length
+    if constexpr (RAGGED) {
+        const int2 rs = rg.seq[blockIdx.x / (unsigned)N];
+        M += rs.x; NL = rs.y;
+    }
     const int nq = M->nq, nl = M->nl, L = M->L, C = M->C;
+    const int cst = RAGGED ? rg.cstride : C;             // cameras per frame of meas / meas_err
     double* sq = smem;
     double* ssc = sq + nq;
     double* sR = ssc + 6 * nl;
@@ -2146,6 +2186,12 @@ __global__ __launch_bounds__(WAVE) void k_finalize(const DevModel* __restrict__ 
     const size_t f = blockIdx.x;
     const int b = (int)(f / (size_t)N), n = (int)(f - (size_t)b * N);
     const int ns = M->ns;                                                                  // state stride (Euler q + leg angles)
+    if (RAGGED && n >= NL) {
+        for (int t = lane; t < nq; t += WAVE) { q[f * nq + t] = 0.0; if (dq && ddq) { dq[f * nq + t] = 0.0; ddq[f * nq + t] = 0.0; } }
+        if (positions) for (int t = lane; t < 3 * L; t += WAVE) positions[f * (size_t)(3 * L) + t] = 0.0;
+        if (meas_err) for (int t = lane; t < 2 * cst * L; t += WAVE) meas_err[f * (size_t)(2 * cst * L) + t] = 0.0;
+        return;
+    }
     const double* qs = qbuf + (size_t)st[b].cur * n_frames * ns + (size_t)b * N * ns;   // sequence base
     if (lane < nq) {
         const double h = M->h;
@@ -2154,12 +2200,12 @@ __global__ __launch_bounds__(WAVE) void k_finalize(const DevModel* __restrict__ 
         q[f * nq + lane] = q0;
         if (dq && ddq) {
             double v = 0.0, a = 0.0;
-            if (N >= 3) {
+            if (NL >= 3) {
                 const int m = n < 2 ? 2 : n;      // ddq0 = ddq1 = ddq2
                 a = (qs[(size_t)m * ns + lane] - 2.0 * qs[(size_t)(m - 1) * ns + lane] + qs[(size_t)(m - 2) * ns + lane]) / (h * h);
             }
             if (n >= 1) v = (q0 - qs[(size_t)(n - 1) * ns + lane]) / h;
-            else if (N >= 2) v = (qs[(size_t)ns + lane] - q0) / h - h * a;   // dq0 = dq1 - h ddq1
+            else if (NL >= 2) v = (qs[(size_t)ns + lane] - q0) / h - h * a;   // dq0 = dq1 - h ddq1
             dq[f * nq + lane] = v; ddq[f * nq + lane] = a;
         }
     }
@@ -2187,7 +2233,7 @@ __global__ __launch_bounds__(WAVE) void k_finalize(const DevModel* __restrict__ 
     if (positions) for (int t = lane; t < 3 * L; t += WAVE) positions[f * (size_t)(3 * L) + t] = spos[t];
     if (meas_err) {
         const cpe_camera* cams = reinterpret_cast<const cpe_camera*>(scam);
-        const size_t pair0 = f * (size_t)(C * L);
+        const size_t pair0 = f * (size_t)(cst * L);
         for (int t = lane; t < C * L; t += WAVE) {
             const int c = t / L, l = t - c * L;
             double u, v, s3[3] = {0.0, 0.0, 0.0};
@@ -2200,5 +2246,6 @@ __global__ __launch_bounds__(WAVE) void k_finalize(const DevModel* __restrict__ 
             const double2 z = reinterpret_cast<const double2*>(meas)[pair0 + t];
             reinterpret_cast<double2*>(meas_err)[pair0 + t] = make_double2(u - z.x, v - z.y);
         }
+        if (RAGGED) for (int t = C * L + lane; t < cst * L; t += WAVE) reinterpret_cast<double2*>(meas_err)[pair0 + t] = make_double2(0.0, 0.0);
     }
 }

@@ -632,15 +632,24 @@ def _struct_bytes(x) -> bytes:
     return bytes(_C.string_at(_C.addressof(x), _C.sizeof(x)))
 
 
+def ragged_group_key(sk: abi.Skeleton, opts: abi.Options, pri: Optional[abi.Priors], device: int) -> tuple:
+    """What sequences must share to go through one cpe_solve_ragged call (Handle.multi): the skeleton's shape, the solver options the LM driver
+    reads per batch, the priors and the device.  Rig, length, frame rate and the skeleton's numbers may differ."""
+    return (_lib.shape_signature(sk), _lib.shared_options_signature(opts), None if pri is None else _struct_bytes(pri), device)
+
+
 def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_output: bool = False, monocular_constraints: bool = False,
                               disable_pose_prior: bool = False, disable_motion_prior: bool = False, out_dir_prefix: Optional[str] = None,
-                              options: Optional[abi.Options] = None) -> List[bool]:
+                              options: Optional[abi.Options] = None, ragged: bool = False) -> List[bool]:
     """estimate_kinematics for MANY sequences at once: the loop of run_dataset.py:1145-1196 (`for seq in dataset: init_trajectory; estimate_kinematics`)
     as batched launches.  Sequences that share a skeleton, a camera rig, a length and a frame rate go through ONE solver handle and ONE cpe_solve
     call (B = the group's size: the GPU solves thousands of sequences per second batched, one at a time it is latency-bound at 7 - 30 ms each);
     every sequence then gets its own centre of mass, costs and files exactly as estimate_kinematics writes them.  All estimators must live on the
     same device; shutter-delay estimation is per sequence (cpe_solve_shutter) and goes through estimate_kinematics.  Returns one bool per
-    estimator, in order."""
+    estimator, in order.
+    ragged=True: sequences need only share the skeleton's shape, the batch-level solver options, the priors and the device (ragged_group_key);
+    each group is ONE cpe_solve_ragged call over a Handle.multi of its distinct (skeleton, rig, options) models, whatever the lengths.  Every
+    sequence's results are bit-equal to those of ragged=False."""
     ests = list(estimators)
     out: List[Optional[bool]] = [None] * len(ests)
     groups: Dict[tuple, List[int]] = {}
@@ -652,9 +661,16 @@ def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_out
         q_init, opts, pri = _kin_prepare(est, monocular_constraints, disable_pose_prior, disable_motion_prior, 5, 4, True, None,
                                          None if options is None else _copy_options(options))
         prepared[i] = (q_init, opts, pri)
-        key = (_struct_bytes(est.skeleton), b"".join(_struct_bytes(est.cams[c]) for c in range(len(est.cams))), q_init.shape[0], _struct_bytes(opts),
-               None if pri is None else _struct_bytes(pri), est.device)
+        if ragged:
+            key = ragged_group_key(est.skeleton, opts, pri, est.device)
+        else:
+            key = (_struct_bytes(est.skeleton), b"".join(_struct_bytes(est.cams[c]) for c in range(len(est.cams))), q_init.shape[0], _struct_bytes(opts),
+                   None if pri is None else _struct_bytes(pri), est.device)
         groups.setdefault(key, []).append(i)
+    if ragged:
+        for idx in groups.values():
+            _solve_ragged_group(ests, idx, prepared, out, solver_output, monocular_constraints, out_dir_prefix)
+        return [bool(v) for v in out]
     for idx in groups.values():
         e0 = ests[idx[0]]
         _, opts, pri = prepared[idx[0]]
@@ -671,6 +687,43 @@ def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_out
         finally:
             h.close()
     return [bool(v) for v in out]
+
+
+def _model_bytes(est: CheetahEstimator, opts: abi.Options) -> bytes:
+    return _struct_bytes(est.skeleton) + b"".join(_struct_bytes(est.cams[c]) for c in range(len(est.cams))) + _struct_bytes(opts)
+
+
+def _solve_ragged_group(ests, idx, prepared, out, solver_output, monocular_constraints, out_dir_prefix) -> None:
+    """estimate_kinematics_batch(ragged=True) for one group: one model per distinct (skeleton, rig, options), one cpe_solve_ragged call, then every
+    sequence's centre of mass, costs and files through _kin_finish with a plain handle of its own model (forward kinematics of that skeleton)"""
+    models: Dict[bytes, int] = {}
+    of = []
+    for i in idx:
+        of.append(models.setdefault(_model_bytes(ests[i], prepared[i][1]), len(models)))
+    first = {}
+    for b, i in enumerate(idx):
+        first.setdefault(of[b], i)
+    reps = [first[k] for k in range(len(models))]
+    pri = prepared[idx[0]][2]
+    dev = ests[idx[0]].device
+    h = _lib.Handle.multi([ests[i].skeleton for i in reps], [ests[i].cams for i in reps], [prepared[i][1] for i in reps], pri, device=dev)
+    fk = {}
+    try:
+        t0 = time()
+        res = h.solve_ragged_host([prepared[i][0] for i in idx], [ests[i].meas for i in idx], [ests[i].weight for i in idx], of)
+        dt = (time() - t0) / len(idx)                                                # processing_time_s of a sequence: its share of the batched solve
+        for b, i in enumerate(idx):
+            one = {k: res[k][b][None] for k in ("q", "dq", "ddq", "positions", "meas_err")}
+            one["stats"] = [res["stats"][b]]; one["status"] = res["stats"][b].status
+            if of[b] not in fk:
+                r = reps[of[b]]
+                fk[of[b]] = _lib.Handle(ests[r].skeleton, ests[r].cams, prepared[r][1], None, device=dev)
+            ests[i].shutter_delay = None
+            out[i] = _kin_finish(ests[i], fk[of[b]], one, dt, solver_output, monocular_constraints, out_dir_prefix)
+    finally:
+        h.close()
+        for f in fk.values():
+            f.close()
 
 
 def _copy_options(o: abi.Options) -> abi.Options:

@@ -244,6 +244,33 @@ cpe_status cpe_solve_host(cpe_handle* h, int32_t B, int32_t N, const double* q_i
                           const double* weight, double* q, double* dq, double* ddq, double* positions,
                           double* meas_err, cpe_stats* stats);
 
+/* ---- ragged batches: sequences of their own length, rig and skeleton in ONE solve -----------------------------------------
+ * cpe_create_multi: one handle over n_models models, model k = (skels[k], cams[k * CPE_MAX_CAMS .. + n_cams[k]], opts[k]); one set of priors
+ * for all of them.  The models must share their shape: n_links, parent, n_markers, marker_link, the joints (joint_parent / child / kind),
+ * n_bounds with bound_a / bound_b, rel_ref / rel_sign and the independent dofs; and the options the solver reads per batch: lambda0, tol_step,
+ * tol_cost, max_iter, max_outer, curvature, bound_tol, cost_scale.  Everything else may differ per model: h (frame rate), link geometry,
+ * masses, marker offsets, bound limits, motion weights, cameras and their count, loss knots, bound_penalty.  A mismatch fails with
+ * CPE_BAD_ARG and cpe_last_error() names the field and the model, before the device is opened.  Entry points without a model argument
+ * (cpe_solve, cpe_eval_*, cpe_forward_kinematics, the shutter-delay and physics-based solves, ...) see model 0 of such a handle. */
+cpe_status cpe_create_multi(int32_t n_models, const cpe_skeleton* skels /*[n_models]*/, const cpe_camera* cams /*[n_models][CPE_MAX_CAMS]*/,
+                            const int32_t* n_cams /*[n_models]*/, const cpe_options* opts /*[n_models]*/, const cpe_priors* priors,
+                            int32_t device, cpe_handle** out);
+/* cpe_solve for B sequences of their own length and model, on any handle (a cpe_create handle has one model: ragged lengths only).
+ * model[b] (index into the handle's models) and n_frames[b] (1 .. N_max) are HOST arrays; the others are laid out as cpe_solve's with
+ * N = N_max frames per sequence and C_max cameras per frame (the largest camera count of the handle's models):
+ *   q_init, q, dq, ddq [B][N_max][nq] ; meas [B][N_max][C_max][L][2] ; weight [B][N_max][C_max][L] ; positions [B][N_max][L][3] ;
+ *   meas_err [B][N_max][C_max][L][2] ; stats[B] (HOST).
+ * Sequence b reads only its frames n < n_frames[b] and cameras c < its model's count; every output past those is written as 0.0.  Each
+ * sequence's outputs and stats are bit-equal to a cpe_solve of that sequence alone on a cpe_create handle of its own model.
+ * Kinematic model only (no shutter delay).  Device pointers. */
+cpe_status cpe_solve_ragged(cpe_handle* h, int32_t B, int32_t N_max, const int32_t* model /*[B] host*/, const int32_t* n_frames /*[B] host*/,
+                            const double* q_init, const double* meas, const double* weight, double* q, double* dq, double* ddq,
+                            double* positions, double* meas_err, cpe_stats* stats);
+/* host-pointer twin of cpe_solve_ragged (stages through HBM) */
+cpe_status cpe_solve_ragged_host(cpe_handle* h, int32_t B, int32_t N_max, const int32_t* model, const int32_t* n_frames,
+                                 const double* q_init, const double* meas, const double* weight, double* q, double* dq, double* ddq,
+                                 double* positions, double* meas_err, cpe_stats* stats);
+
 /* ---- per-frame ground-reaction-force fit (CheetahEstimator.estimate_grf, acinoset_opt.py:176-270).
  * Rows 0-5 (root x, y, z, phi, theta, psi) of d/dt dL/dq' - dL/dq for L = sum_i (m_i |P_i'|^2 / 2 + w_i^T I_i w_i / 2
  * - m_i g P_i,z) are balanced against B = sum_feet (d foot / dq)^T M g (GRFz e_z + sum_k D_k GRFxy_k),
