@@ -6,6 +6,7 @@ Torch is used only as plumbing for device memory (tensor.data_ptr()).
 import ctypes as C
 import os
 import subprocess
+from typing import Optional
 
 import numpy as np
 
@@ -93,6 +94,8 @@ def load():
     lib.cpe_solve_kinetic_fixed.argtypes = [vp, C.POINTER(abi.KineticOptions), C.c_int32, C.c_int32] + [vp] * 14 + [C.POINTER(abi.Stats), C.POINTER(abi.KineticStats)]
     lib.cpe_solve_kinetic_force_box.argtypes = [vp, C.POINTER(abi.KineticOptions), C.c_int32, C.c_int32] + [vp] * 14 + [C.POINTER(abi.Stats), C.POINTER(abi.KineticStats)]
     lib.cpe_solve_kinetic_bounded.argtypes = [vp, C.POINTER(abi.KineticOptions), C.c_int32, C.c_int32] + [vp] * 14 + [C.POINTER(abi.Stats), C.POINTER(abi.KineticStats)]
+    lib.cpe_solve_kinetic_ragged.argtypes = [vp, C.POINTER(abi.KineticOptions), C.c_int32, C.c_int32, ip, ip] + [vp] * 16 + [C.POINTER(abi.Stats), C.POINTER(abi.KineticStats)]
+    lib.cpe_solve_kinetic_ragged_host.argtypes = [vp, C.POINTER(abi.KineticOptions), C.c_int32, C.c_int32, ip, ip] + [vp] * 16 + [C.POINTER(abi.Stats), C.POINTER(abi.KineticStats)]
     lib.cpe_eval_kinetic_nodes.argtypes = [vp, C.POINTER(abi.KineticOptions), C.c_int32, C.c_int32] + [vp] * 11
     _LIB = lib
     return lib
@@ -122,6 +125,58 @@ SHARED_OPTIONS = ("lambda0", "tol_step", "tol_cost", "max_iter", "max_outer", "c
 def shared_options_signature(opts: abi.Options) -> tuple:
     """The options the models of one cpe_create_multi handle must share (the LM driver reads them per batch)"""
     return tuple(getattr(opts, k) for k in SHARED_OPTIONS)
+
+
+def kinetic_shape_signature(ko: abi.KineticOptions) -> tuple:
+    """The kinetic option fields the models of one cpe_solve_kinetic_ragged call must share (include/cpe.h): feet, their markers, motors and
+    their link pairs and axes.  Every other field may differ per model."""
+    d = ko.dyn
+    nf, nm = int(d.n_feet), int(d.n_motors)
+    return (nf, tuple(d.foot_marker[:max(min(nf, 4), 0)]), nm, tuple(d.motor_first[:max(nm, 0)]), tuple(d.motor_second[:max(nm, 0)]),
+            tuple(d.motor_axis[:max(nm, 0)]))
+
+
+def _pad(arrs, n_max: int, tail) -> np.ndarray:
+    """per-sequence arrays [N_b, *shape_b] -> [B, n_max, *tail], zero-filled past each sequence's own frames (and, on every axis, its own extent)"""
+    out = np.zeros((len(arrs), n_max) + tuple(tail), dtype=np.result_type(*[np.asarray(a).dtype for a in arrs]) if arrs else np.float64)
+    for b, a in enumerate(arrs):
+        a = np.asarray(a)
+        out[(b,) + tuple(slice(0, k) for k in a.shape)] = a
+    return out
+
+
+KINETIC_INPUTS = ("q_init", "meas", "weight", "stance", "force")
+KINETIC_OUTPUTS = ("q", "dq", "ddq", "positions", "meas_err", "tau", "lam", "grf", "slack")
+
+
+def pad_kinetic(q_init_list, meas_list, weight_list, stance_list, force_list=None, n_cams_max: Optional[int] = None) -> dict:
+    """The inputs of cpe_solve_kinetic_ragged_host from per-sequence arrays: q_init [N_b, nq], meas [N_b, C_b, L, 2], weight [N_b, C_b, L],
+    stance [N_b, n_feet], force (grf_fixed / tau_box / grf_box of the sequence, or None) -> zero-padded [B, N_max, ...] arrays (C_max cameras,
+    n_cams_max or the largest C_b).  Pure numpy."""
+    lens = [int(np.shape(q)[0]) for q in q_init_list]
+    nmax = max(lens) if lens else 0
+    cm = n_cams_max if n_cams_max is not None else max(int(np.shape(m)[1]) for m in meas_list)
+    L = int(np.shape(meas_list[0])[2])
+    out = dict(lens=lens, q_init=_pad([np.asarray(q, np.float64) for q in q_init_list], nmax, np.shape(q_init_list[0])[1:]),
+               meas=_pad([np.asarray(m, np.float64) for m in meas_list], nmax, (cm, L, 2)),
+               weight=_pad([np.asarray(w, np.float64) for w in weight_list], nmax, (cm, L)),
+               stance=_pad([np.asarray(x, np.int32) for x in stance_list], nmax, np.shape(stance_list[0])[1:]).astype(np.int32),
+               force=None)
+    if force_list is not None:
+        out["force"] = _pad([np.asarray(f, np.float64) for f in force_list], nmax, np.shape(force_list[0])[1:])
+    return out
+
+
+def unpad_kinetic(padded: dict, lens, n_cams) -> dict:
+    """The per-sequence outputs of a padded cpe_solve_kinetic_ragged_host result: every array of KINETIC_OUTPUTS in `padded` [B, N_max, ...] ->
+    list of [N_b, ...] (meas_err also cut to the sequence's n_cams[b] cameras).  Pure numpy."""
+    out = {}
+    for k in KINETIC_OUTPUTS:
+        if k not in padded:
+            continue
+        a = padded[k]
+        out[k] = [np.ascontiguousarray(a[b, :lens[b], :n_cams[b]] if k == "meas_err" else a[b, :lens[b]]) for b in range(len(lens))]
+    return out
 
 
 def _ptr(t):
@@ -419,6 +474,78 @@ class Handle:
         c = lambda t: t.cpu().numpy()
         return dict(status=st, q=c(q), dq=c(dq), ddq=c(ddq), positions=c(pos), meas_err=c(err), tau=c(tau), lam=c(lam), grf=c(grf), slack=c(slack),
                     stats=stats, kstats=ks)
+
+    def _kinetic_options_array(self, kopts_list):
+        n = len(getattr(self, "model_n_cams", [self.n_cams]))
+        kl = list(kopts_list)
+        if len(kl) != n:
+            raise ValueError(f"solve_kinetic_ragged: one kinetic options struct per model of the handle ({n}), got {len(kl)}")
+        return (abi.KineticOptions * n)(*kl)
+
+    def solve_kinetic_ragged(self, kopts_list, model, n_frames, q_init, meas, weight, stance, q, dq, ddq, positions, meas_err, tau=None, lam=None,
+                             grf=None, slack=None, grf_fixed=None, tau_box=None, grf_box=None):
+        """cpe_solve_kinetic_ragged on device tensors laid out for N_max = q_init.shape[1] frames and C_max cameras; kopts_list: one
+        KineticOptions per model of the handle; model / n_frames: int sequences (one per sequence); at most one of grf_fixed / tau_box / grf_box
+        (the variant of the whole batch).  Returns (status, [Stats], [KineticStats])."""
+        if sum(a is not None for a in (grf_fixed, tau_box, grf_box)) > 1:
+            raise ValueError("solve_kinetic_ragged: at most one of grf_fixed, tau_box, grf_box")
+        ko = self._kinetic_options_array(kopts_list)
+        B, N = q_init.shape[0], q_init.shape[1]
+        if len(model) != B or len(n_frames) != B:
+            raise ValueError("solve_kinetic_ragged: one model index and one frame count per sequence")
+        stats = (abi.Stats * max(B, 1))(); ks = (abi.KineticStats * max(B, 1))()
+        mo, nf = (C.c_int32 * max(B, 1))(*[int(m) for m in model]), (C.c_int32 * max(B, 1))(*[int(n) for n in n_frames])
+        st = self._call(self.lib.cpe_solve_kinetic_ragged, "cpe_solve_kinetic_ragged", ko, B, N, mo, nf, _ptr(q_init), _ptr(meas), _ptr(weight),
+                        _ptr(stance), _ptr(grf_fixed), _ptr(tau_box), _ptr(grf_box), _ptr(q), _ptr(dq), _ptr(ddq), _ptr(positions), _ptr(meas_err),
+                        _ptr(tau), _ptr(lam), _ptr(grf), _ptr(slack), stats, ks, allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
+        return st, list(stats)[:B], list(ks)[:B]
+
+    def solve_kinetic_ragged_host(self, kopts_list, q_init_list, meas_list, weight_list, stance_list, model_list=None, grf_fixed=None, tau_box=None,
+                                  grf_box=None):
+        """cpe_solve_kinetic_ragged_host over sequences of their own length and model: per sequence q_init [N_b, nq], meas [N_b, C_m, L, 2],
+        weight [N_b, C_m, L], stance [N_b, n_feet] (C_m = the camera count of its model, model_list[b]; None = model 0 for all); at most one of
+        grf_fixed / tau_box / grf_box, each a list of one array per sequence ([N_b, n_feet, 3] / [N_b, n_motors, 2] / [N_b, n_feet, 3, 2]).
+        Pads, solves, unpads: returns dict(status, q, dq, ddq, positions, meas_err, tau, lam, grf, slack = lists of per-sequence arrays, stats,
+        kstats = lists, padded = the padded outputs)."""
+        B = len(q_init_list)
+        models = [0] * B if model_list is None else [int(m) for m in model_list]
+        ncams = getattr(self, "model_n_cams", [self.n_cams])
+        given = [a for a in (grf_fixed, tau_box, grf_box) if a is not None]
+        if len(given) > 1:
+            raise ValueError("solve_kinetic_ragged_host: at most one of grf_fixed, tau_box, grf_box")
+        force = given[0] if given else None
+        if len(meas_list) != B or len(weight_list) != B or len(stance_list) != B or len(models) != B or (force is not None and len(force) != B):
+            raise ValueError("solve_kinetic_ragged_host: one q_init, meas, weight, stance, model (and force array) per sequence")
+        if len(kopts_list) != len(ncams):
+            raise ValueError(f"solve_kinetic_ragged_host: one kinetic options struct per model of the handle ({len(ncams)}), got {len(kopts_list)}")
+        if any(m < 0 or m >= len(ncams) for m in models):
+            raise ValueError("solve_kinetic_ragged_host: model index out of range")
+        L, nq = self.L, self.nq
+        d0 = kopts_list[0].dyn
+        nf, nm, nc = int(d0.n_feet), int(d0.n_motors), self.n_constraint_rows()
+        ftail = None if force is None else ((nf, 3) if grf_fixed is not None else ((nm, 2) if tau_box is not None else (nf, 3, 2)))
+        for b in range(B):
+            n, c = int(np.shape(q_init_list[b])[0]), ncams[models[b]]
+            if np.shape(q_init_list[b]) != (n, nq) or np.shape(meas_list[b]) != (n, c, L, 2) or np.shape(weight_list[b]) != (n, c, L) \
+                    or np.shape(stance_list[b]) != (n, nf) or (force is not None and np.shape(force[b]) != (n,) + ftail):
+                raise ValueError(f"solve_kinetic_ragged_host: sequence {b} does not have the shapes of its model ({n} frames, {c} cameras)")
+        p = pad_kinetic(q_init_list, meas_list, weight_list, stance_list, force, n_cams_max=self.n_cams)
+        lens, Nm, Cm = p["lens"], p["q_init"].shape[1], self.n_cams
+        E = np.empty
+        out = dict(q=E((B, Nm, nq)), dq=E((B, Nm, nq)), ddq=E((B, Nm, nq)), positions=E((B, Nm, L, 3)), meas_err=E((B, Nm, Cm, L, 2)),
+                   tau=E((B, Nm, nm)), lam=E((B, Nm, nc)), grf=E((B, Nm, nf, 5)), slack=E((B, Nm, nq)))
+        stats = (abi.Stats * max(B, 1))(); ks = (abi.KineticStats * max(B, 1))()
+        mo, nfr = (C.c_int32 * max(B, 1))(*models), (C.c_int32 * max(B, 1))(*lens)
+        ko = self._kinetic_options_array(kopts_list)
+        fx = p["force"]
+        st = self.lib.cpe_solve_kinetic_ragged_host(self._h, ko, B, Nm, mo, nfr, _ptr(p["q_init"]), _ptr(p["meas"]), _ptr(p["weight"]),
+                                                    p["stance"].ctypes.data, _ptr(fx) if grf_fixed is not None else None,
+                                                    _ptr(fx) if tau_box is not None else None, _ptr(fx) if grf_box is not None else None,
+                                                    *[_ptr(out[k]) for k in KINETIC_OUTPUTS], stats, ks)
+        _check(st, "cpe_solve_kinetic_ragged_host", allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
+        res = unpad_kinetic(out, lens, [ncams[m] for m in models])
+        res.update(status=st, stats=list(stats)[:B], kstats=list(ks)[:B], padded=out)
+        return res
 
     def eval_kinetic_nodes_host(self, kopts, q, meas, weight, stance):
         """one evaluation of the physics terms per node (cpe_eval_kinetic_nodes); numpy in, dict of numpy arrays out"""

@@ -55,7 +55,8 @@ struct cpe_handle {
     int gmm_k = 0, gmm_dim = 0, lr_window = 0;
     double* Hlr = nullptr;       // [2][F][pb][nu*nu] off-diagonal Gauss-Newton blocks of the autoregressive prior
     // physics-based model (cpe_solve_kinetic): device options and workspace
-    DevKin* dk = nullptr; DevKin hk;
+    DevKin* dk = nullptr; DevKin hk;  // dk: one entry per model (n_models); hk: host copy of entry 0
+    std::vector<DevKin> hks;          // cpe_solve_kinetic_ragged: host copies of every entry
     size_t kws_frames = 0;
     std::vector<void**> kws_bufs;
     double *kmut = nullptr;       // multipliers of the torque boxes [F][2 CPE_MAX_MOTORS] (cpe_solve_kinetic_bounded)
@@ -474,8 +475,13 @@ static cpe_status create_impl(cpe_handle* h, const cpe_skeleton* skel, const cpe
         // dynamic LDS above 64 KiB needs an explicit opt-in per kernel
         const void* ks[] = {(const void*)&k_resjac<true, 4, 3, 2>, (const void*)&k_resjac<false, 4, 3, 2>,
                             (const void*)&k_resjac<true, 4, 4, 2>, (const void*)&k_resjac<false, 4, 4, 2>,
-                            (const void*)&k_dyn_eval, (const void*)&k_dyn_assemble, (const void*)&k_dyn_schur, (const void*)&k_dyn_jac};
-        for (const void* k : ks) HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                            (const void*)&k_dyn_eval<>, (const void*)&k_dyn_assemble<>, (const void*)&k_dyn_schur<>, (const void*)&k_dyn_jac<>,
+                            (const void*)&k_dyn_eval<true>, (const void*)&k_dyn_assemble<true>, (const void*)&k_dyn_schur<true>, (const void*)&k_dyn_jac<true>};
+        for (const void* k : ks) {         // all of the CU's 160 KiB that the kernel's static LDS leaves (k_dyn_schur<*> holds a word of its own)
+            hipFuncAttributes fa;
+            HIPCHK(hipFuncGetAttributes(&fa, k));
+            HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)fa.sharedSizeBytes));
+        }
     }
     HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     HIPCHK(hipEventCreateWithFlags(&h->order_ev, hipEventDisableTiming));
@@ -1320,9 +1326,10 @@ void cpe_default_kinetic_options(cpe_kinetic_options* o, double fps, int32_t kin
     o->inner_iterations = 30; o->_pad = 0;
 }
 
-static cpe_status build_kin(cpe_handle* h, const cpe_kinetic_options* opt, const double* grf_fix = nullptr, const double* tau_box = nullptr, const double* grf_box = nullptr) {
-    const DevModel& m = h->hm;
-    DevKin& K = h->hk;
+// The kinetic tables K of model m under options opt (the batch's buffers grf_fix / tau_box / grf_box as given; the workspace is sized before this
+// is called).  Host side only.
+static cpe_status build_kin_entry(cpe_handle* h, const DevModel& m, const cpe_kinetic_options* opt, const double* grf_fix, const double* tau_box,
+                                  const double* grf_box, DevKin& K) {
     memset(&K, 0, sizeof(K));
     K.o = *opt;
     const cpe_dyn_options& d = opt->dyn;
@@ -1347,7 +1354,7 @@ static cpe_status build_kin(cpe_handle* h, const cpe_kinetic_options* opt, const
     if (m.nq > KS_NQ || m.nl > KS_NL || m.L > KS_L || m.ns > KS_NS || m.nrev > 32 || K.nrow > KS_NROW || K.nrow > KIN_ROWS_MAX)
         return fail(CPE_BAD_ARG, "skeleton too large for the kinetic kernels (at most 54 coordinates, 17 links, 24 markers)");
     double mt = 0; for (int i = 0; i < m.nl; i++) mt += m.mass[i];
-    K.Mg = mt * d.eom.gravity; K.h = h->opts.h; K.ih = 1.0 / h->opts.h;
+    K.Mg = mt * d.eom.gravity; K.h = m.h; K.ih = 1.0 / m.h;          // (m.h: the frame interval of the model's options)
     for (int i = 0; i < m.nl; i++) { uint32_t mask = 0; for (int j = 0; j < m.nl; j++) { int a = j; while (a >= 0 && a != i) a = m.parent[a]; if (a == i) mask |= 1u << j; } K.sub_mask[i] = mask; }
     K.grf_fix = grf_fix;
     K.grf_box = grf_box;
@@ -1409,9 +1416,43 @@ static cpe_status build_kin(cpe_handle* h, const cpe_kinetic_options* opt, const
     for (int l = 0; l < m.L; l++) if (m.chain_len[l] > KJ_CHAIN) return fail(CPE_BAD_ARG, "skeleton too deep for the kinetic kernels (a marker more than 5 links from the root)");
     K.mu_slack = h->kmus; K.sbox = (opt->slack_hi < 1e9 || opt->slack_lo > -1e9) ? 1 : 0;
     if (K.sbox && (!(opt->kappa_slack > 0) || !(opt->slack_lo < opt->slack_hi))) return fail(CPE_BAD_ARG, "kinetic options: slack box needs lo < hi and a positive penalty");
-    if (!h->dk) HIPCHK(hipMalloc(&h->dk, sizeof(DevKin)));
-    HIPCHK(hipMemcpyAsync(h->dk, &K, sizeof(DevKin), hipMemcpyHostToDevice, h->stream));
     return CPE_OK;
+}
+
+// entry 0 of the device tables, from the handle's first model
+static cpe_status build_kin(cpe_handle* h, const cpe_kinetic_options* opt, const double* grf_fix = nullptr, const double* tau_box = nullptr, const double* grf_box = nullptr) {
+    if (cpe_status s = build_kin_entry(h, h->hm, opt, grf_fix, tau_box, grf_box, h->hk); s != CPE_OK) return s;
+    if (!h->dk) HIPCHK(hipMalloc(&h->dk, sizeof(DevKin) * n_models(h)));
+    HIPCHK(hipMemcpyAsync(h->dk, &h->hk, sizeof(DevKin), hipMemcpyHostToDevice, h->stream));
+    return CPE_OK;
+}
+
+// every entry, model k under opts[k] (cpe_solve_kinetic_ragged)
+static cpe_status build_kin_all(cpe_handle* h, const cpe_kinetic_options* opts, const double* grf_fix, const double* tau_box, const double* grf_box) {
+    const int nmod = n_models(h);
+    h->hks.resize((size_t)nmod);
+    for (int k = 0; k < nmod; k++)
+        if (cpe_status s = build_kin_entry(h, h->models.empty() ? h->hm : h->models[(size_t)k], &opts[k], grf_fix, tau_box, grf_box, h->hks[(size_t)k]); s != CPE_OK)
+            return fail(s, std::string("cpe_solve_kinetic_ragged: model ") + std::to_string(k) + ": " + g_err);
+    h->hk = h->hks[0];
+    if (!h->dk) HIPCHK(hipMalloc(&h->dk, sizeof(DevKin) * nmod));
+    HIPCHK(hipMemcpyAsync(h->dk, h->hks.data(), sizeof(DevKin) * nmod, hipMemcpyHostToDevice, h->stream));
+    return CPE_OK;
+}
+
+// The kinetic option fields the models of one cpe_solve_kinetic_ragged call must share (include/cpe.h): they fix which node forces and rows every
+// node has and the layout of stance, tau, grf and the force arrays.  Returns the first field that differs, or null.
+static const char* kinetic_shape_mismatch(const cpe_kinetic_options& a, const cpe_kinetic_options& b) {
+    const cpe_dyn_options &x = a.dyn, &y = b.dyn;
+    auto same = [](const auto& u, const auto& v, int n) { return n <= 0 || memcmp(&u, &v, sizeof(u[0]) * (size_t)n) == 0; };
+    if (x.n_feet != y.n_feet) return "dyn.n_feet";
+    if (!same(x.foot_marker, y.foot_marker, std::min(x.n_feet, 4))) return "dyn.foot_marker";
+    if (x.n_motors != y.n_motors) return "dyn.n_motors";
+    const int nm = std::min(x.n_motors, CPE_MAX_MOTORS);
+    if (!same(x.motor_first, y.motor_first, nm)) return "dyn.motor_first";
+    if (!same(x.motor_second, y.motor_second, nm)) return "dyn.motor_second";
+    if (!same(x.motor_axis, y.motor_axis, nm)) return "dyn.motor_axis";
+    return nullptr;
 }
 
 static_assert(KE_R1 >= KS_NQ * KIN_LS && KE_R1 >= KIN_SLOT && KE_R2 >= 3 * KIN_SLOT, "regions of k_dyn_eval hold A, an evaluation slot / the three base slots");
@@ -1454,84 +1495,117 @@ static cpe_status kin_state_reset(cpe_handle* h, size_t F, bool torque_box) {
     return CPE_OK;
 }
 
-// one evaluation pass of the physics terms on the evaluated buffer (after k_frame_normal): rows, node forces, cost
-static void launch_dyn_eval(cpe_handle* h, int N, int first, size_t Fw, const int32_t* stance, const int* act, const int* n_act, int slots) {
+extern "C++" {     // (the launch templates below; the file's own functions are extern "C")
+
+// one evaluation pass of the physics terms on the evaluated buffer (after k_frame_normal): rows, node forces, cost.
+// RAGGED: the forms of cpe_solve_kinetic_ragged, launched with its table rg (N = nmax)
+template <bool RAGGED = false>
+static void launch_dyn_eval(cpe_handle* h, int N, int first, size_t Fw, const int32_t* stance, const int* act, const int* n_act, int slots, RaggedArgs rg = RaggedArgs{}) {
     const unsigned gf = (unsigned)((size_t)slots * N);
     prof_begin(h, 5);
-    hipLaunchKernelGGL(k_dyn_eval, dim3(gf), dim3(KIN_THREADS), lds_kin_eval(), h->stream, h->dm, h->dk, h->st, N, first, Fw, h->qbuf, stance, h->fbuf, h->kmu, h->costbuf,
-                       h->Jbuf, h->Abuf, h->pieces, h->pmeta, h->dstat, h->slackb, act, n_act);
+    hipLaunchKernelGGL(k_dyn_eval<RAGGED>, dim3(gf), dim3(KIN_THREADS), lds_kin_eval(), h->stream, h->dm, h->dk, h->st, N, first, Fw, h->qbuf, stance, h->fbuf, h->kmu,
+                       h->costbuf, h->Jbuf, h->Abuf, h->pieces, h->pmeta, h->dstat, h->slackb, act, n_act, rg);
     prof_end(h);
 }
 // Jacobian and second-order pieces of the CURRENT iterate -- after the accept step, and only for sequences whose iterate is new: a rejected trial
 // costs its evaluation only (a quarter to a third of the iterations of a physics-based solve are rejections)
-static void launch_dyn_pieces(cpe_handle* h, int N, int first, size_t Fw, const int* act, const int* n_act, int slots) {
+template <bool RAGGED = false>
+static void launch_dyn_pieces(cpe_handle* h, int N, int first, size_t Fw, const int* act, const int* n_act, int slots, RaggedArgs rg = RaggedArgs{}) {
     const unsigned gf = (unsigned)((size_t)slots * N);
     prof_begin(h, 10);
-    hipLaunchKernelGGL(k_dyn_jac, dim3(gf), dim3(KJ_THREADS), sizeof(double) * KJ_DOUBLES, h->stream, h->dm, h->dk, h->st, N, first, Fw, h->qbuf, h->fbuf, h->Jbuf, act, n_act);
+    hipLaunchKernelGGL(k_dyn_jac<RAGGED>, dim3(gf), dim3(KJ_THREADS), sizeof(double) * KJ_DOUBLES, h->stream, h->dm, h->dk, h->st, N, first, Fw, h->qbuf, h->fbuf, h->Jbuf,
+                       act, n_act, rg);
     prof_end(h);
     prof_begin(h, 8);
-    hipLaunchKernelGGL(k_dyn_assemble, dim3(gf), dim3(KIN_THREADS), lds_kin_assemble(), h->stream, h->dm, h->dk, h->st, N, first, Fw, h->Jbuf, h->Abuf, h->pieces, h->pmeta,
-                       h->gTb, act, n_act);
+    hipLaunchKernelGGL(k_dyn_assemble<RAGGED>, dim3(gf), dim3(KIN_THREADS), lds_kin_assemble(), h->stream, h->dm, h->dk, h->st, N, first, Fw, h->Jbuf, h->Abuf, h->pieces,
+                       h->pmeta, h->gTb, act, n_act, rg);
     prof_end(h);
 }
 
-static cpe_status solve_kinetic_impl(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q_init, const double* meas,
-                                     const double* weight, const int32_t* stance, const double* grf_fixed, const double* tau_box, const double* grf_box, double* q, double* dq, double* ddq,
-                                     double* positions, double* meas_err, double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats,
-                                     cpe_kinetic_stats* kstats) {
+// One iteration of the physics-based solve: per-frame terms and physics terms of the evaluated buffer, accept / reject (new damping), elimination
+// of the node forces at that damping for the CURRENT iterate, band system, factor + solve + next trial.  RAGGED: with the table rg (N = nmax).
+template <bool RAGGED>
+static void kin_iterate(cpe_handle* h, const LmParams& prm, int N, size_t Fw, size_t ldsn, const double* meas, const double* weight, const int32_t* stance,
+                        RaggedArgs rg, int first, const int* act, const int* n_act, int slots) {
+    const unsigned gf = (unsigned)((size_t)slots * N);
+    const bool plain = h->gmm_k == 0;
+    prof_begin(h, 0);
+    hipLaunchKernelGGL(RAGGED ? FRAME_NORMAL_RAGGED(plain) : FRAME_NORMAL(plain), dim3(gf), dim3(WAVE), ldsn, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, meas,
+                       weight, h->gbuf, h->Bbuf, h->costbuf, h->mu, h->gambuf, h->pri, act, n_act, ShutterArgs{nullptr, nullptr, nullptr}, rg);
+    prof_end(h);
+    launch_dyn_eval<RAGGED>(h, N, first, Fw, stance, act, n_act, slots, rg);
+    prof_begin(h, 2);
+    hipLaunchKernelGGL((k_lm_step<3, 1, RAGGED>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gbuf, h->Bbuf, h->costbuf,
+                       h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, nullptr, act, n_act, 2, nullptr, h->dgbuf, nullptr, 0, rg);
+    prof_end(h);
+    launch_dyn_pieces<RAGGED>(h, N, 0, Fw, act, n_act, slots, rg);      // (`which` = 0 also in the first pass: the accept step has just marked every sequence new)
+    prof_begin(h, 9);
+    hipLaunchKernelGGL(k_dyn_schur<RAGGED>, dim3(gf), dim3(KIN_THREADS), lds_kin_schur(), h->stream, h->dk, h->st, N, Fw, h->pieces, h->pmeta, h->fbuf, h->kmu, stance,
+                       h->Tbuf, act, n_act, rg);
+    prof_end(h);
+    prof_begin(h, 6);
+    hipLaunchKernelGGL(k_dyn_gather<RAGGED>, dim3(gf), dim3(KIN_THREADS), 0, h->stream, h->st, N, Fw, h->gbuf, h->Bbuf, h->Tbuf, h->gTb, h->gk, h->Bk, h->Hk, act,
+                       n_act, rg);
+    prof_end(h);
+    prof_begin(h, 2);
+    hipLaunchKernelGGL((k_lm_step<3, 2, RAGGED>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gk, h->Bk, h->costbuf,
+                       h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hk, act, n_act, 1, nullptr, h->dgbuf, nullptr, 0, rg);
+    prof_end(h);
+    prof_begin(h, 7);
+    hipLaunchKernelGGL((k_lm_back<3, RAGGED>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf, h->gtbuf, h->dgbuf, act, n_act, rg);
+    prof_end(h);
+}
+
+}  // extern "C++"
+
+// The physics-based solve of every entry point: cpe_solve_kinetic* (model == null: B sequences of N frames of the handle's first model, options
+// opt[0]) and cpe_solve_kinetic_ragged (model / n_frames: host arrays of the batch, N = N_max, options opt[k] for model k).  At most one of
+// grf_fixed / tau_box / grf_box is given (the entry points check it).
+static cpe_status solve_kinetic_impl(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const int32_t* model, const int32_t* n_frames,
+                                     const double* q_init, const double* meas, const double* weight, const int32_t* stance, const double* grf_fixed,
+                                     const double* tau_box, const double* grf_box, double* q, double* dq, double* ddq, double* positions, double* meas_err,
+                                     double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats, cpe_kinetic_stats* kstats) {
     if (!h || !opt || !q_init || !meas || !weight || !stance || !q) return fail(CPE_BAD_ARG, "null argument");
     if ((dq == nullptr) != (ddq == nullptr)) return fail(CPE_BAD_ARG, "dq and ddq must be given together");
     size_t F;
     if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
     if (F == 0) return CPE_OK;
+    const bool ragged = model != nullptr;
+    std::vector<int2> seq;
+    if (ragged) {           // every refusal of the batch comes before anything is launched
+        if (cpe_status s = ragged_table(h, B, N, model, n_frames, seq); s != CPE_OK) return s;
+        for (int k = 1; k < n_models(h); k++)
+            if (const char* field = kinetic_shape_mismatch(opt[0], opt[k]))
+                return fail(CPE_BAD_ARG, std::string("cpe_solve_kinetic_ragged: kinetic options of model ") + std::to_string(k) + " differ from model 0 in " + field);
+    }
     if (h->pb != 3) return fail(CPE_BAD_ARG, "the physics-based model runs on the half-bandwidth-3 solver");
     HIPCHK(hipSetDevice(h->device));
     cpe_status s = ensure_ws(h, B, N);
     if (s != CPE_OK) return s;
     s = ensure_kws(h, B, N);
     if (s != CPE_OK) return s;
-    s = build_kin(h, opt, grf_fixed, tau_box, grf_box);
+    s = ragged ? build_kin_all(h, opt, grf_fixed, tau_box, grf_box) : build_kin(h, opt, grf_fixed, tau_box, grf_box);
     if (s != CPE_OK) return s;
     const DevModel& m = h->hm;
     const size_t Fw = F;
-    if ((s = state_reset(h, B, N, q_init)) != CPE_OK || (s = kin_state_reset(h, F, tau_box != nullptr)) != CPE_OK) return s;
+    const RaggedArgs rg = ragged ? RaggedArgs{h->rseq, N, cams_max(h)} : RaggedArgs{};
+    if (ragged) HIPCHK(hipMemcpyAsync(h->rseq, seq.data(), sizeof(int2) * B, hipMemcpyHostToDevice, h->stream));     // (seq outlives the stream: drained below)
+    if ((s = state_reset(h, B, N, q_init, ragged ? &rg : nullptr)) != CPE_OK || (s = kin_state_reset(h, F, tau_box != nullptr)) != CPE_OK) return s;
     const LmParams prm = lm_params(h, B, N);
-    const size_t ldsn = lds_normal(m, h->gmm_k, h->gmm_dim);
-    // One iteration: per-frame terms and physics terms of the evaluated buffer, accept / reject (new damping), elimination of the node
-    // forces at that damping for the CURRENT iterate, band system, factor + solve + next trial.
+    const size_t ldsn = ragged ? lds_normal_all(h) : lds_normal(m, h->gmm_k, h->gmm_dim);
     auto iterate = [&](int first, const int* act, const int* n_act, int slots) {
-        const unsigned gf = (unsigned)((size_t)slots * N);
-        prof_begin(h, 0);
-        hipLaunchKernelGGL(FRAME_NORMAL(h->gmm_k == 0), dim3(gf), dim3(WAVE), ldsn, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, meas, weight, h->gbuf, h->Bbuf,
-                           h->costbuf, h->mu, h->gambuf, h->pri, act, n_act, ShutterArgs{nullptr, nullptr, nullptr}, RaggedArgs{});
-        prof_end(h);
-        launch_dyn_eval(h, N, first, Fw, stance, act, n_act, slots);
-        prof_begin(h, 2);
-        hipLaunchKernelGGL((k_lm_step<3, 1>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gbuf, h->Bbuf, h->costbuf,
-                           h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, nullptr, act, n_act, 2, nullptr, h->dgbuf);
-        prof_end(h);
-        launch_dyn_pieces(h, N, 0, Fw, act, n_act, slots);        // (`which` = 0 also in the first pass: the accept step has just marked every sequence new)
-        prof_begin(h, 9);
-        hipLaunchKernelGGL(k_dyn_schur, dim3(gf), dim3(KIN_THREADS), lds_kin_schur(), h->stream, h->dk, h->st, N, Fw, h->pieces, h->pmeta, h->fbuf, h->kmu, stance, h->Tbuf, act, n_act);
-        prof_end(h);
-        prof_begin(h, 6);
-        hipLaunchKernelGGL(k_dyn_gather, dim3(gf), dim3(KIN_THREADS), 0, h->stream, h->st, N, Fw, h->gbuf, h->Bbuf, h->Tbuf, h->gTb, h->gk, h->Bk, h->Hk, act, n_act);
-        prof_end(h);
-        prof_begin(h, 2);
-        hipLaunchKernelGGL((k_lm_step<3, 2>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gk, h->Bk, h->costbuf,
-                           h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hk, act, n_act, 1, nullptr, h->dgbuf);
-        prof_end(h);
-        prof_begin(h, 7);
-        hipLaunchKernelGGL((k_lm_back<3>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf, h->gtbuf, h->dgbuf, act, n_act);
-        prof_end(h);
+        if (ragged) kin_iterate<true>(h, prm, N, Fw, ldsn, meas, weight, stance, rg, first, act, n_act, slots);
+        else kin_iterate<false>(h, prm, N, Fw, ldsn, meas, weight, stance, rg, first, act, n_act, slots);
     };
     if ((s = lm_drive(h, B, iterate)) != CPE_OK) return s;
     std::vector<SeqState> hs;
     std::vector<double> hc;
     s = lm_readback(h, B, N, meas, q, dq, ddq, positions, meas_err, nullptr, [&] {
-        hipLaunchKernelGGL(k_dyn_outputs, dim3((unsigned)F), dim3(64), 0, h->stream, h->dk, h->st, N, Fw, h->fbuf, h->Abuf, nullptr, tau, lambda, grf);
-    }, hs, hc);
+        if (ragged) hipLaunchKernelGGL(k_dyn_outputs<true>, dim3((unsigned)F), dim3(64), 0, h->stream, h->dk, h->st, N, Fw, h->fbuf, h->Abuf, nullptr, tau, lambda, grf, rg);
+        else hipLaunchKernelGGL(k_dyn_outputs<>, dim3((unsigned)F), dim3(64), 0, h->stream, h->dk, h->st, N, Fw, h->fbuf, h->Abuf, nullptr, tau, lambda, grf);
+    }, hs, hc, ragged ? &rg : nullptr);
     if (s != CPE_OK) return s;
+    auto len = [&](int b) { return ragged ? n_frames[b] : N; };          // the sequence's own frames
     // slack and the per-node statistics live in the buffer of each sequence's final iterate
     std::vector<double> hd(kstats ? 2 * F * KIN_STAT : 0);
     std::vector<int> hit(kstats ? 2 * F : 0);               // last word of every node's meta record: Newton iterations of its force solve
@@ -1539,17 +1613,19 @@ static cpe_status solve_kinetic_impl(cpe_handle* h, const cpe_kinetic_options* o
         HIPCHK(hipMemcpyAsync(hd.data(), h->dstat, sizeof(double) * 2 * F * KIN_STAT, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipMemcpy2DAsync(hit.data(), sizeof(int), h->pmeta + KIN_LS, sizeof(int) * (KIN_LS + 1), sizeof(int), 2 * F, hipMemcpyDeviceToHost, h->stream));
     }
-    if (slack)
+    if (slack) {
+        if (ragged) HIPCHK(hipMemsetAsync(slack, 0, sizeof(double) * F * m.nq, h->stream));        // the padding rows
         for (int b = 0; b < B; b++)
             HIPCHK(hipMemcpy2DAsync(slack + (size_t)b * N * m.nq, sizeof(double) * m.nq, h->slackb + ((size_t)hs[b].cur * F + (size_t)b * N) * CPE_MAX_NQ,
-                                    sizeof(double) * CPE_MAX_NQ, sizeof(double) * m.nq, N, hipMemcpyDeviceToDevice, h->stream));
+                                    sizeof(double) * CPE_MAX_NQ, sizeof(double) * m.nq, len(b), hipMemcpyDeviceToDevice, h->stream));
+    }
     HIPCHK(hipStreamSynchronize(h->stream));
     if (kstats)
         for (int b = 0; b < B; b++) {
             const SeqState& S = hs[b];
             cpe_kinetic_stats& k = kstats[b];
             memset(&k, 0, sizeof(k));
-            for (int n = 0; n < N; n++) {
+            for (int n = 0; n < len(b); n++) {
                 const double* d = hd.data() + ((size_t)S.cur * F + (size_t)b * N + n) * KIN_STAT;
                 k.cost_eom += d[0]; k.cost_torque += d[1]; k.cost_energy += d[3];
                 k.max_slack = std::max(k.max_slack, d[5]); k.max_base_rows = std::max(k.max_base_rows, d[6]); k.max_violation = std::max(k.max_violation, d[7]);
@@ -1568,21 +1644,32 @@ cpe_status cpe_solve_kinetic_fixed(cpe_handle* h, const cpe_kinetic_options* opt
                                    const double* weight, const int32_t* stance, const double* grf_fixed, double* q, double* dq, double* ddq,
                                    double* positions, double* meas_err, double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats,
                                    cpe_kinetic_stats* kstats) {
-    return solve_kinetic_impl(h, opt, B, N, q_init, meas, weight, stance, grf_fixed, nullptr, nullptr, q, dq, ddq, positions, meas_err, tau, lambda, grf, slack, stats, kstats);
+    return solve_kinetic_impl(h, opt, B, N, nullptr, nullptr, q_init, meas, weight, stance, grf_fixed, nullptr, nullptr, q, dq, ddq, positions, meas_err, tau, lambda, grf, slack, stats, kstats);
 }
 cpe_status cpe_solve_kinetic_force_box(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q_init, const double* meas,
                                        const double* weight, const int32_t* stance, const double* grf_box, double* q, double* dq, double* ddq,
                                        double* positions, double* meas_err, double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats,
                                        cpe_kinetic_stats* kstats) {
     if (!grf_box) return fail(CPE_BAD_ARG, "null argument");
-    return solve_kinetic_impl(h, opt, B, N, q_init, meas, weight, stance, nullptr, nullptr, grf_box, q, dq, ddq, positions, meas_err, tau, lambda, grf, slack, stats, kstats);
+    return solve_kinetic_impl(h, opt, B, N, nullptr, nullptr, q_init, meas, weight, stance, nullptr, nullptr, grf_box, q, dq, ddq, positions, meas_err, tau, lambda, grf, slack, stats, kstats);
 }
 cpe_status cpe_solve_kinetic_bounded(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q_init, const double* meas,
                                      const double* weight, const int32_t* stance, const double* tau_box, double* q, double* dq, double* ddq,
                                      double* positions, double* meas_err, double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats,
                                      cpe_kinetic_stats* kstats) {
     if (!tau_box) return fail(CPE_BAD_ARG, "null argument");
-    return solve_kinetic_impl(h, opt, B, N, q_init, meas, weight, stance, nullptr, tau_box, nullptr, q, dq, ddq, positions, meas_err, tau, lambda, grf, slack, stats, kstats);
+    return solve_kinetic_impl(h, opt, B, N, nullptr, nullptr, q_init, meas, weight, stance, nullptr, tau_box, nullptr, q, dq, ddq, positions, meas_err, tau, lambda, grf, slack, stats, kstats);
+}
+
+cpe_status cpe_solve_kinetic_ragged(cpe_handle* h, const cpe_kinetic_options* opts, int32_t B, int32_t N_max, const int32_t* model, const int32_t* n_frames,
+                                    const double* q_init, const double* meas, const double* weight, const int32_t* stance, const double* grf_fixed,
+                                    const double* tau_box, const double* grf_box, double* q, double* dq, double* ddq, double* positions, double* meas_err,
+                                    double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats, cpe_kinetic_stats* kstats) {
+    if (!h || !opts || !model || !n_frames) return fail(CPE_BAD_ARG, "null argument");
+    if ((grf_fixed != nullptr) + (tau_box != nullptr) + (grf_box != nullptr) > 1)
+        return fail(CPE_BAD_ARG, "cpe_solve_kinetic_ragged: at most one of grf_fixed, tau_box, grf_box");
+    return solve_kinetic_impl(h, opts, B, N_max, model, n_frames, q_init, meas, weight, stance, grf_fixed, tau_box, grf_box, q, dq, ddq, positions, meas_err,
+                              tau, lambda, grf, slack, stats, kstats);
 }
 
 // diagnostic building block (as cpe_eval_normal): one evaluation of the physics terms at Euler q, multipliers zero, forces from a cold start.
@@ -1604,8 +1691,8 @@ cpe_status cpe_eval_kinetic_nodes(cpe_handle* h, const cpe_kinetic_options* opt,
     const DevModel& m = h->hm;
     hipLaunchKernelGGL(FRAME_NORMAL(h->gmm_k == 0), dim3((unsigned)F), dim3(WAVE), lds_normal(m, h->gmm_k, h->gmm_dim), h->stream, h->dm, h->st, N, 1, F, h->qbuf, meas, weight,
                        h->gbuf, h->Bbuf, h->costbuf, h->mu, h->gambuf, h->pri, nullptr, nullptr, ShutterArgs{nullptr, nullptr, nullptr}, RaggedArgs{});
-    launch_dyn_eval(h, N, 1, F, stance, nullptr, nullptr, B);
-    launch_dyn_pieces(h, N, 1, F, nullptr, nullptr, B);
+    launch_dyn_eval<>(h, N, 1, F, stance, nullptr, nullptr, B);
+    launch_dyn_pieces<>(h, N, 1, F, nullptr, nullptr, B);
     HIPCHK(hipGetLastError());
     if (f) HIPCHK(hipMemcpyAsync(f, h->fbuf, sizeof(double) * F * KIN_LS, hipMemcpyDeviceToDevice, h->stream));
     if (stat) HIPCHK(hipMemcpyAsync(stat, h->dstat, sizeof(double) * F * KIN_STAT, hipMemcpyDeviceToDevice, h->stream));
@@ -1728,6 +1815,57 @@ cpe_status cpe_solve_host(cpe_handle* h, int32_t B, int32_t N, const double* q_i
     if (ddq) HIPCHK(hipMemcpyAsync(ddq, oddq.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
     if (positions) HIPCHK(hipMemcpyAsync(positions, op.p, sizeof(double) * F * m.L * 3, hipMemcpyDeviceToHost, h->stream));
     if (meas_err) HIPCHK(hipMemcpyAsync(meas_err, ome.p, sizeof(double) * nm * 2, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return s;
+}
+
+// joint equalities of a model: two rows per revolute joint, one per Hooke joint (the node forces lambda, build_kin_entry)
+static int n_con(const DevModel& m) {
+    int n = 0;
+    for (int j = 0; j < m.nj; j++) n += m.joint_kind[j] == CPE_JOINT_REVOLUTE_Y ? 2 : 1;
+    return n;
+}
+
+cpe_status cpe_solve_kinetic_ragged_host(cpe_handle* h, const cpe_kinetic_options* opts, int32_t B, int32_t N_max, const int32_t* model, const int32_t* n_frames,
+                                         const double* q_init, const double* meas, const double* weight, const int32_t* stance, const double* grf_fixed,
+                                         const double* tau_box, const double* grf_box, double* q, double* dq, double* ddq, double* positions, double* meas_err,
+                                         double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats, cpe_kinetic_stats* kstats) {
+    if (!h || !opts || !model || !n_frames || !q_init || !meas || !weight || !stance || !q) return fail(CPE_BAD_ARG, "null argument");
+    if ((grf_fixed != nullptr) + (tau_box != nullptr) + (grf_box != nullptr) > 1)
+        return fail(CPE_BAD_ARG, "cpe_solve_kinetic_ragged: at most one of grf_fixed, tau_box, grf_box");
+    size_t F;
+    if (cpe_status s = frames(B, N_max, &F); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    const cpe_dyn_options& d = opts[0].dyn;       // (the staging sizes: the counts every model shares, checked again by the solve)
+    if (d.n_feet < 1 || d.n_feet > 4 || d.n_motors < 0 || d.n_motors > CPE_MAX_MOTORS) return fail(CPE_BAD_ARG, "kinetic options: feet / motors out of range");
+    const DevModel& m = h->hm;
+    const size_t nf = (size_t)d.n_feet, nmo = (size_t)d.n_motors, nc = (size_t)n_con(m), nm = F * cams_max(h) * m.L;
+    HIPCHK(hipSetDevice(h->device));
+    DevBuf di, dm_, dw_, dst, dfx, oq, odq, oddq, op, ome, ot, ol, og, osl;
+    const size_t n_fx = grf_fixed ? F * nf * 3 : (tau_box ? F * nmo * 2 : (grf_box ? F * nf * 6 : 0));
+    const double* fx = grf_fixed ? grf_fixed : (tau_box ? tau_box : grf_box);
+    HIPCHK(di.alloc(F * m.nq)); HIPCHK(dm_.alloc(nm * 2)); HIPCHK(dw_.alloc(nm)); HIPCHK(dst.alloc((F * nf + 1) / 2)); HIPCHK(dfx.alloc(n_fx));
+    HIPCHK(oq.alloc(F * m.nq)); HIPCHK(odq.alloc(F * m.nq)); HIPCHK(oddq.alloc(F * m.nq)); HIPCHK(op.alloc(F * m.L * 3)); HIPCHK(ome.alloc(nm * 2));
+    HIPCHK(ot.alloc(F * nmo)); HIPCHK(ol.alloc(F * nc)); HIPCHK(og.alloc(F * nf * 5)); HIPCHK(osl.alloc(F * m.nq));
+    int32_t* dstance = reinterpret_cast<int32_t*>(dst.p);
+    HIPCHK(hipMemcpyAsync(di.p, q_init, sizeof(double) * F * m.nq, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(dm_.p, meas, sizeof(double) * nm * 2, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(dw_.p, weight, sizeof(double) * nm, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(dstance, stance, sizeof(int32_t) * F * nf, hipMemcpyHostToDevice, h->stream));
+    if (fx) HIPCHK(hipMemcpyAsync(dfx.p, fx, sizeof(double) * n_fx, hipMemcpyHostToDevice, h->stream));
+    cpe_status s = cpe_solve_kinetic_ragged(h, opts, B, N_max, model, n_frames, di.p, dm_.p, dw_.p, dstance, grf_fixed ? dfx.p : nullptr,
+                                            tau_box ? dfx.p : nullptr, grf_box ? dfx.p : nullptr, oq.p, odq.p, oddq.p, op.p, ome.p, ot.p, ol.p, og.p, osl.p,
+                                            stats, kstats);
+    if (s < 0) return s;
+    HIPCHK(hipMemcpyAsync(q, oq.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
+    if (dq) HIPCHK(hipMemcpyAsync(dq, odq.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
+    if (ddq) HIPCHK(hipMemcpyAsync(ddq, oddq.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
+    if (positions) HIPCHK(hipMemcpyAsync(positions, op.p, sizeof(double) * F * m.L * 3, hipMemcpyDeviceToHost, h->stream));
+    if (meas_err) HIPCHK(hipMemcpyAsync(meas_err, ome.p, sizeof(double) * nm * 2, hipMemcpyDeviceToHost, h->stream));
+    if (tau) HIPCHK(hipMemcpyAsync(tau, ot.p, sizeof(double) * F * nmo, hipMemcpyDeviceToHost, h->stream));
+    if (lambda) HIPCHK(hipMemcpyAsync(lambda, ol.p, sizeof(double) * F * nc, hipMemcpyDeviceToHost, h->stream));
+    if (grf) HIPCHK(hipMemcpyAsync(grf, og.p, sizeof(double) * F * nf * 5, hipMemcpyDeviceToHost, h->stream));
+    if (slack) HIPCHK(hipMemcpyAsync(slack, osl.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return s;
 }

@@ -531,16 +531,23 @@ __device__ __forceinline__ bool kin_partial_cholesky_lds(double* H, int n, int n
 //   R2: three evaluation slots (base positions, base evaluations)   ->  G [na][KIN_LS] = A_a^T diag(omega) A_a, kept until H_ff is written
 //   R1: A [nq][KIN_LS]  ->  M [(na + 1)][KIN_MS], the node's normal matrix with the right-hand side as its last row, + work  ->  the slot of the evaluation at f*
 // (A is written to global memory for k_dyn_assemble anyway; a further active-set round reads it back)
+// RAGGED (cpe_solve_kinetic_ragged): N = nmax; the sequence's model picks M and K, frames past its own length leave at once (as in every kernel below)
+template <bool RAGGED = false>
 __global__ __launch_bounds__(KIN_THREADS) void k_dyn_eval(const DevModel* __restrict__ M, const DevKin* __restrict__ K, const SeqState* __restrict__ st, int N,
                                                           int which, size_t n_frames, const double* __restrict__ qbuf, const int32_t* __restrict__ stance,
                                                           double* __restrict__ fbuf, double* __restrict__ kmu, double* __restrict__ costbuf,
                                                           double* __restrict__ Jbuf, double* __restrict__ Abuf, double* __restrict__ pieces, int* __restrict__ pmeta,
                                                           double* __restrict__ dstat, double* __restrict__ slackbuf, const int* __restrict__ act,
-                                                          const int* __restrict__ n_act) {
+                                                          const int* __restrict__ n_act, RaggedArgs rg = RaggedArgs{}) {
     extern __shared__ double smem[];
     if (n_act && (int)(blockIdx.x / (unsigned)N) >= *n_act) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l = lane & 31;
     const int b = act ? act[blockIdx.x / (unsigned)N] : (int)(blockIdx.x / (unsigned)N), n = (int)(blockIdx.x % (unsigned)N);
+    if constexpr (RAGGED) {
+        const int2 rs = rg.seq[b];
+        if (n >= rs.y) return;
+        M += rs.x; K += rs.x;
+    }
     const size_t f_ = (size_t)b * N + n;
     const SeqState Sq = st[b];
     if (Sq.status != 0) return;
@@ -984,14 +991,20 @@ __global__ __launch_bounds__(KIN_THREADS) void k_dyn_eval(const DevModel* __rest
 #define KA_RC 72
 #define KA_RS (KIN_NC3 + 2)        // even (16-byte rows), not a multiple of 8
 static_assert(2 * KA_RC >= KS_NROW && KA_RC >= KS_NQ && KIN_NC3 % 4 == 0 && KIN_NC3 / 4 * (KIN_NC3 / 4 + 1) / 2 <= KIN_THREADS - KIN_NC3 / 4, "tiling of k_dyn_assemble");
+template <bool RAGGED = false>
 __global__ __launch_bounds__(KIN_THREADS, 2) void k_dyn_assemble(const DevModel* __restrict__ M, const DevKin* __restrict__ K, const SeqState* __restrict__ st, int N,
                                                               int which, size_t n_frames, const double* __restrict__ Jbuf, const double* __restrict__ Abuf,
                                                               double* __restrict__ pieces, const int* __restrict__ pmeta, double* __restrict__ gT,
-                                                              const int* __restrict__ act, const int* __restrict__ n_act) {
+                                                              const int* __restrict__ act, const int* __restrict__ n_act, RaggedArgs rg = RaggedArgs{}) {
     extern __shared__ double smem[];
     if (n_act && (int)(blockIdx.x / (unsigned)N) >= *n_act) return;
     const int tid = threadIdx.x;
     const int b = act ? act[blockIdx.x / (unsigned)N] : (int)(blockIdx.x / (unsigned)N), n = (int)(blockIdx.x % (unsigned)N);
+    if constexpr (RAGGED) {
+        const int2 rs = rg.seq[b];
+        if (n >= rs.y) return;
+        M += rs.x; K += rs.x;
+    }
     const size_t f_ = (size_t)b * N + n;
     const SeqState Sq = st[b];
     if (Sq.status != 0 || (!which && (!Sq.fresh || Sq.al_pending))) return;      // after the accept step, current iterate, only when it is new (see k_dyn_jac)
@@ -1095,15 +1108,21 @@ __global__ __launch_bounds__(KIN_THREADS, 2) void k_dyn_assemble(const DevModel*
 // k_dyn_schur: per node of the CURRENT iterate, S = H_uu - H_uf (H_ff + lam_f diag H_ff)^-1 H_fu with lam_f = lambda * lm_force_damping
 // (trust region in force space), written as the six lower 28 x 28 blocks [n,n] [n,n-1] [n,n-2] [n-1,n-1] [n-1,n-2] [n-2,n-2].
 // dynamic LDS: H [na][KIN_LS] | Y [na][84]
+template <bool RAGGED = false>
 __global__ __launch_bounds__(KIN_THREADS) void k_dyn_schur(const DevKin* __restrict__ K, const SeqState* __restrict__ st, int N, size_t n_frames,
                                                            const double* __restrict__ pieces, const int* __restrict__ pmeta, const double* __restrict__ fbuf,
                                                            const double* __restrict__ kmu, const int32_t* __restrict__ stance, double* __restrict__ Tbuf,
-                                                           const int* __restrict__ act, const int* __restrict__ n_act) {
+                                                           const int* __restrict__ act, const int* __restrict__ n_act, RaggedArgs rg = RaggedArgs{}) {
     extern __shared__ double smem[];
     __shared__ int flag;
     if (n_act && (int)(blockIdx.x / (unsigned)N) >= *n_act) return;
     const int tid = threadIdx.x;
     const int b = act ? act[blockIdx.x / (unsigned)N] : (int)(blockIdx.x / (unsigned)N), n = (int)(blockIdx.x % (unsigned)N);
+    if constexpr (RAGGED) {
+        const int2 rs = rg.seq[b];
+        if (n >= rs.y) return;
+        K += rs.x;
+    }
     const size_t f_ = (size_t)b * N + n;
     const SeqState Sq = st[b];
     if (Sq.status != 0 || Sq.al_pending) return;
@@ -1188,20 +1207,26 @@ __global__ __launch_bounds__(KIN_THREADS) void k_dyn_schur(const DevKin* __restr
 //   Bk[m]    = B_meas[m] + T_m[n,n] + T_m+1[n-1,n-1] + T_m+2[n-2,n-2]
 //   Hk[m][0] = block (m, m-1) = T_m[n,n-1] + T_m+1[n-1,n-2] ;  Hk[m][1] = block (m, m-2) = T_m[n,n-2] ;  Hk[m][2] = 0
 //   gk[m]    = g_meas[m] + gT_m[0] + gT_m+1[1] + gT_m+2[2]
+template <bool RAGGED = false>
 __global__ __launch_bounds__(KIN_THREADS) void k_dyn_gather(const SeqState* __restrict__ st, int N, size_t n_frames, const double* __restrict__ gbuf,
                                                             const double* __restrict__ Bbuf, const double* __restrict__ Tbuf, const double* __restrict__ gT,
                                                             double* __restrict__ gk, double* __restrict__ Bk, double* __restrict__ Hk,
-                                                            const int* __restrict__ act, const int* __restrict__ n_act) {
+                                                            const int* __restrict__ act, const int* __restrict__ n_act, RaggedArgs rg = RaggedArgs{}) {
     if (n_act && (int)(blockIdx.x / (unsigned)N) >= *n_act) return;
     const int tid = threadIdx.x;
     const int b = act ? act[blockIdx.x / (unsigned)N] : (int)(blockIdx.x / (unsigned)N), m = (int)(blockIdx.x % (unsigned)N);
     const size_t f_ = (size_t)b * N + m;
+    int NL = N;                                          // N: the buffers' frames per sequence, NL: this sequence's length (nodes m + 1, m + 2 inside it)
+    if constexpr (RAGGED) {
+        NL = rg.seq[b].y;
+        if (m >= NL) return;
+    }
     const SeqState Sq = st[b];
     if (Sq.status != 0 || Sq.al_pending) return;
     const size_t fo = (size_t)Sq.cur * n_frames + f_;
     constexpr int BB = CPE_NX * CPE_NX;
     const double* T0 = Tbuf + f_ * (size_t)(6 * BB); const double* T1 = T0 + 6 * BB; const double* T2 = T1 + 6 * BB;
-    const bool h0 = m >= 2, h1 = m + 1 < N && m + 1 >= 2, h2 = m + 2 < N;
+    const bool h0 = m >= 2, h1 = m + 1 < NL && m + 1 >= 2, h2 = m + 2 < NL;
     for (int e = tid; e < BB; e += KIN_THREADS) {
         double v = Bbuf[fo * BB + e];
         if (h0) v += T0[e];
@@ -1225,13 +1250,18 @@ __global__ __launch_bounds__(KIN_THREADS) void k_dyn_gather(const SeqState* __re
 }
 
 // outputs of the physics-based solve: node forces of the final iterate as the reference stores them (tau, Fr, GRFz / GRFxy) and slack_eom
+template <bool RAGGED = false>
 __global__ void k_dyn_outputs(const DevKin* __restrict__ K, const SeqState* __restrict__ st, int N, size_t n_frames, const double* __restrict__ fbuf,
                               const double* __restrict__ Abuf, const double* __restrict__ dummy, double* __restrict__ tau, double* __restrict__ lam,
-                              double* __restrict__ grf) {
+                              double* __restrict__ grf, RaggedArgs rg = RaggedArgs{} /* RAGGED: frames past a sequence's own are written as zeros */) {
     const size_t f_ = blockIdx.x;
     const int b = (int)(f_ / (size_t)N), n = (int)(f_ - (size_t)b * N), t = threadIdx.x;
     const double* f = fbuf + ((size_t)st[b].cur * n_frames + f_) * KIN_LS;
-    const bool on = n >= 2;
+    bool on = n >= 2;
+    if constexpr (RAGGED) {                                // (the counts nm, nc, nf are the same in every model of the handle)
+        const int2 rs = rg.seq[b];
+        K += rs.x; on = on && n < rs.y;
+    }
     if (tau && t < K->nm) tau[f_ * K->nm + t] = on ? f[t] : 0.0;
     if (lam && t < K->nc) lam[f_ * K->nc + t] = on ? f[K->nm + t] : 0.0;
     if (grf && t < K->nf) {

@@ -151,13 +151,19 @@ __device__ __forceinline__ void kj_nearest(const double* r, const double* a, dou
 #define KJ_TT (KJ_TL + 4 * KS_NL * 12)           // [4 waves][12]            translation part: raw of frames 0, 1, 2 (3), d x' (3), d x'' (3), pad
 #define KJ_DOUBLES (KJ_TT + 4 * 12)
 
+template <bool RAGGED = false>
 __global__ __launch_bounds__(KJ_THREADS) void k_dyn_jac(const DevModel* __restrict__ M, const DevKin* __restrict__ K, const SeqState* __restrict__ st, int N, int which,
                                                          size_t n_frames, const double* __restrict__ qbuf, const double* __restrict__ fbuf, double* __restrict__ Jbuf,
-                                                         const int* __restrict__ act, const int* __restrict__ n_act) {
+                                                         const int* __restrict__ act, const int* __restrict__ n_act, RaggedArgs rg = RaggedArgs{}) {
     extern __shared__ double sm[];
     if (n_act && (int)(blockIdx.x / (unsigned)N) >= *n_act) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = act ? act[blockIdx.x / (unsigned)N] : (int)(blockIdx.x / (unsigned)N), n = (int)(blockIdx.x % (unsigned)N);
+    if constexpr (RAGGED) {                                  // (see k_dyn_eval)
+        const int2 rs = rg.seq[b];
+        if (n >= rs.y) return;
+        M += rs.x; K += rs.x;
+    }
     const size_t f_ = (size_t)b * N + n;
     const SeqState Sq = st[b];
     // runs AFTER the accept step, on the current iterate, and only when that iterate is new (a rejected trial leaves the pieces of the current

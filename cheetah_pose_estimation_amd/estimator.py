@@ -918,7 +918,25 @@ def estimate_kinetics(estimator: CheetahEstimator, init_torques: bool = True, au
     polygon sides (a side is non-negative), friction polyhedron kept; feet outside the profile's contact carry no force (the reference would let
     them take up to 0.2 body weights: its box around zero).  The whole NLP runs on the GPU.  `init_torques` has no effect here: the torques are
     minimised out exactly at every evaluation, so they need no starting value."""
-    est, params, scene, sk = estimator, estimator.params, estimator.scene, estimator.skeleton
+    prep = _kinetic_prepare(estimator, auto, use_2d_reprojections, init_prev_kinematic_solution, synthesised_grf, no_slip, joint_estimation, fix_grf,
+                            ground_constraint, disable_pose_prior, disable_motion_prior, out_dir_prefix, options, kinetic_options)
+    est = estimator
+    h = _lib.Handle(prep["skeleton"], est.cams, prep["opts"], prep["pri"], device=est.device)
+    try:
+        t0 = time()
+        gfx, gbx = prep["grf_fixed"], prep["grf_box"]
+        res = h.solve_kinetic_host(prep["ko"], prep["q_init"][None], est.meas[None], est.weight[None], prep["stance"][None],
+                                   grf_fixed=None if gfx is None else gfx[None], grf_box=None if gbx is None else gbx[None])
+        return _kinetic_finish(est, h, res, time() - t0, prep, solver_output, out_fname, out_dir_prefix)
+    finally:
+        h.close()
+
+
+def _kinetic_prepare(est: CheetahEstimator, auto: bool, use_2d_reprojections: bool, init_prev_kinematic_solution: bool, synthesised_grf: bool,
+                     no_slip: bool, joint_estimation: bool, fix_grf: bool, ground_constraint: bool, disable_pose_prior: bool, disable_motion_prior: bool,
+                     out_dir_prefix: Optional[str], options: Optional[abi.Options], kinetic_options: Optional[abi.KineticOptions]) -> dict:
+    """what estimate_kinetics sets up before the solver call: initial guess, contacts, stance, the force profile or its boxes, options, priors"""
+    params, scene, sk = est.params, est.scene, est.skeleton
     if est.kinematic_model:
         raise AssertionError("Dynamic model of the cheetah is required.")          # the reference asserts hasattr(model, 'eom_f')
     if not use_2d_reprojections:
@@ -1000,21 +1018,23 @@ def estimate_kinetics(estimator: CheetahEstimator, init_torques: bool = True, au
     if est.bound_eom_error is not None:
         ko.slack_lo, ko.slack_hi = float(est.bound_eom_error[0]), float(est.bound_eom_error[1])      # make_pyomo_model(bound_eom_error=...), acinoset_opt.py:510-514
     skk = skeleton.without_motion_model(sk)              # the physics-based cost has no constant-acceleration term (acinoset_opt.py:905-921)
-    h = _lib.Handle(skk, est.cams, opts, pri, device=est.device)
-    try:
-        t0 = time()
-        res = h.solve_kinetic_host(ko, q_init[None], est.meas[None], est.weight[None], stance[None],
-                                   grf_fixed=None if grf_fixed is None else grf_fixed[None], grf_box=None if grf_box is None else grf_box[None])
-        est.opt_time_s = time() - t0
-        import torch
-        dev = torch.device("cuda", est.device)
-        qd = torch.tensor(res["q"], device=dev)
-        pos = torch.empty((1, N, 24, 3), dtype=torch.float64, device=dev); com = torch.empty((1, N, 3), dtype=torch.float64, device=dev)
-        h.forward_kinematics(qd, pos, com); h.synchronize()
-        est.com_pos = com[0].cpu().numpy()
-        est.com_vel = (est.com_pos[1:] - est.com_pos[:-1]) * scene.fps
-    finally:
-        h.close()
+    variant = "fixed" if grf_fixed is not None else ("force_box" if grf_box is not None else "free")
+    return dict(q_init=q_init, stance=stance, grf_fixed=grf_fixed, grf_box=grf_box, pri=pri, opts=opts, ko=ko, skeleton=skk, N=N, variant=variant)
+
+
+def _kinetic_finish(est: CheetahEstimator, h, res: dict, seconds: float, prep: dict, solver_output: bool, out_fname: str,
+                    out_dir_prefix: Optional[str]) -> bool:
+    """what estimate_kinetics does after the solver call: centre of mass, costs, `ok`, files.  `res` holds ONE sequence; h: a handle of its model."""
+    params, scene = est.params, est.scene
+    N, q_init, stance, ko = prep["N"], prep["q_init"], prep["stance"], prep["ko"]
+    est.opt_time_s = seconds
+    import torch
+    dev = torch.device("cuda", est.device)
+    qd = torch.tensor(res["q"], device=dev)
+    pos = torch.empty((1, N, 24, 3), dtype=torch.float64, device=dev); com = torch.empty((1, N, 3), dtype=torch.float64, device=dev)
+    h.forward_kinematics(qd, pos, com); h.synchronize()
+    est.com_pos = com[0].cpu().numpy()
+    est.com_vel = (est.com_pos[1:] - est.com_pos[:-1]) * scene.fps
     st, ks = res["stats"][0], res["kstats"][0]
     est.result = res
     est.kinetic = dict(tau=res["tau"][0], lam=res["lam"][0], grf=res["grf"][0], slack=res["slack"][0], stance=stance, ground_height=ko.ground_height)
@@ -1032,6 +1052,110 @@ def estimate_kinetics(estimator: CheetahEstimator, init_torques: bool = True, au
         dname = dname if scene.cam_idx is None else f"{dname}_{scene.cam_idx}"
         est.save(dname, fname=out_fname, out_dir_prefix=out_dir_prefix)
     return ok
+
+
+def _copy_kinetic_options(o: abi.KineticOptions) -> abi.KineticOptions:
+    import ctypes as _C
+    c = abi.KineticOptions()
+    _C.memmove(_C.byref(c), _C.byref(o), _C.sizeof(abi.KineticOptions))
+    return c
+
+
+def kinetic_ragged_group_key(sk: abi.Skeleton, opts: abi.Options, ko: abi.KineticOptions, pri: Optional[abi.Priors], variant: str, device: int) -> tuple:
+    """What sequences must share to go through one cpe_solve_kinetic_ragged call (Handle.multi): the skeleton's shape, the solver options the LM
+    driver reads per batch, the kinetic option fields that fix every node's unknowns and rows (_lib.kinetic_shape_signature), the priors, the
+    variant (free, prescribed or boxed foot forces) and the device.  Rig, length, frame rate, masses and the other kinetic options may differ."""
+    return (_lib.shape_signature(sk), _lib.shared_options_signature(opts), _lib.kinetic_shape_signature(ko), None if pri is None else _struct_bytes(pri),
+            variant, device)
+
+
+def _kinetic_model_bytes(est: CheetahEstimator, prep: dict) -> bytes:
+    return _model_bytes(est, prep["opts"]) + _struct_bytes(prep["skeleton"]) + _struct_bytes(prep["ko"])
+
+
+def _kinetic_one(res: dict, b: int) -> dict:
+    """sequence b of a batched kinetic result as solve_kinetic_host returns ONE sequence"""
+    one = {k: (res[k][b][None] if isinstance(res[k], list) else res[k][b:b + 1]) for k in ("q", "dq", "ddq", "positions", "meas_err", "tau", "lam", "grf", "slack")}
+    one["stats"] = [res["stats"][b]]; one["kstats"] = [res["kstats"][b]]; one["status"] = res["stats"][b].status
+    return one
+
+
+def estimate_kinetics_batch(estimators: Sequence[CheetahEstimator], init_torques: bool = True, auto: bool = True, use_2d_reprojections: bool = True,
+                            solver_output: bool = False, init_prev_kinematic_solution: bool = True, synthesised_grf: bool = False,
+                            no_slip: bool = True, joint_estimation: bool = False, fix_grf: bool = True, ground_constraint: bool = False,
+                            disable_pose_prior: bool = False, disable_motion_prior: bool = False, plot: bool = False, out_fname: str = "fte",
+                            out_dir_prefix: Optional[str] = None, options: Optional[abi.Options] = None,
+                            kinetic_options: Optional[abi.KineticOptions] = None, ragged: bool = False) -> List[bool]:
+    """estimate_kinetics for MANY sequences at once, with its keyword arguments (applied to every sequence).  Each sequence is prepared as
+    estimate_kinetics prepares it (the per-frame force fit of the fix_grf=True, synthesised_grf=False branch included, one sequence at a time),
+    then solved in a batch, then gets its centre of mass, costs and files exactly as estimate_kinetics writes them; only processing_time_s (its
+    share of the batched solve) differs.  All estimators must live on the same device.  Returns one bool per estimator, in order.
+    ragged=False: sequences with the same skeleton, rig, length, options, kinetic options, priors, variant and device share ONE solve_kinetic_host
+    call.  ragged=True: they need only share kinetic_ragged_group_key; each group is ONE cpe_solve_kinetic_ragged call over a Handle.multi of its
+    distinct (skeleton, rig, options, kinetic options) models, whatever the lengths.  Every sequence's results are bit-equal either way."""
+    ests = list(estimators)
+    out: List[Optional[bool]] = [None] * len(ests)
+    groups: Dict[tuple, List[int]] = {}
+    prepared = {}
+    for i, est in enumerate(ests):
+        p = _kinetic_prepare(est, auto, use_2d_reprojections, init_prev_kinematic_solution, synthesised_grf, no_slip, joint_estimation, fix_grf,
+                             ground_constraint, disable_pose_prior, disable_motion_prior, out_dir_prefix,
+                             None if options is None else _copy_options(options), None if kinetic_options is None else _copy_kinetic_options(kinetic_options))
+        prepared[i] = p
+        if ragged:
+            key = kinetic_ragged_group_key(p["skeleton"], p["opts"], p["ko"], p["pri"], p["variant"], est.device)
+        else:
+            key = (_kinetic_model_bytes(est, p), p["N"], None if p["pri"] is None else _struct_bytes(p["pri"]), p["variant"], est.device)
+        groups.setdefault(key, []).append(i)
+    for idx in groups.values():
+        (_solve_kinetic_ragged_group if ragged else _solve_kinetic_group)(ests, idx, prepared, out, solver_output, out_fname, out_dir_prefix)
+    return [bool(v) for v in out]
+
+
+def _solve_kinetic_group(ests, idx, prepared, out, solver_output, out_fname, out_dir_prefix) -> None:
+    """estimate_kinetics_batch(ragged=False) for one group: one handle, one solve_kinetic_host call with B = the group's size"""
+    e0, p0 = ests[idx[0]], prepared[idx[0]]
+    stack = lambda k: None if p0[k] is None else np.stack([prepared[i][k] for i in idx])
+    h = _lib.Handle(p0["skeleton"], e0.cams, p0["opts"], p0["pri"], device=e0.device)
+    try:
+        t0 = time()
+        res = h.solve_kinetic_host(p0["ko"], stack("q_init"), np.stack([ests[i].meas for i in idx]), np.stack([ests[i].weight for i in idx]),
+                                   stack("stance"), grf_fixed=stack("grf_fixed"), grf_box=stack("grf_box"))
+        dt = (time() - t0) / len(idx)                                                # processing_time_s of a sequence: its share of the batched solve
+        for b, i in enumerate(idx):
+            out[i] = _kinetic_finish(ests[i], h, _kinetic_one(res, b), dt, prepared[i], solver_output, out_fname, out_dir_prefix)
+    finally:
+        h.close()
+
+
+def _solve_kinetic_ragged_group(ests, idx, prepared, out, solver_output, out_fname, out_dir_prefix) -> None:
+    """estimate_kinetics_batch(ragged=True) for one group: one model per distinct (skeleton, rig, options, kinetic options), one
+    cpe_solve_kinetic_ragged call, then every sequence's centre of mass, costs and files through _kinetic_finish with a plain handle of its model"""
+    models: Dict[bytes, int] = {}
+    of = [models.setdefault(_kinetic_model_bytes(ests[i], prepared[i]), len(models)) for i in idx]
+    first = {}
+    for b, i in enumerate(idx):
+        first.setdefault(of[b], i)
+    reps = [first[k] for k in range(len(models))]
+    p0, dev = prepared[idx[0]], ests[idx[0]].device
+    h = _lib.Handle.multi([prepared[i]["skeleton"] for i in reps], [ests[i].cams for i in reps], [prepared[i]["opts"] for i in reps], p0["pri"], device=dev)
+    fk = {}
+    try:
+        force = "grf_fixed" if p0["variant"] == "fixed" else ("grf_box" if p0["variant"] == "force_box" else None)
+        t0 = time()
+        res = h.solve_kinetic_ragged_host([prepared[i]["ko"] for i in reps], [prepared[i]["q_init"] for i in idx], [ests[i].meas for i in idx],
+                                          [ests[i].weight for i in idx], [prepared[i]["stance"] for i in idx], of,
+                                          **({} if force is None else {force: [prepared[i][force] for i in idx]}))
+        dt = (time() - t0) / len(idx)                                                # processing_time_s of a sequence: its share of the batched solve
+        for b, i in enumerate(idx):
+            if of[b] not in fk:
+                r = reps[of[b]]
+                fk[of[b]] = _lib.Handle(prepared[r]["skeleton"], ests[r].cams, prepared[r]["opts"], None, device=dev)
+            out[i] = _kinetic_finish(ests[i], fk[of[b]], _kinetic_one(res, b), dt, prepared[i], solver_output, out_fname, out_dir_prefix)
+    finally:
+        h.close()
+        for f in fk.values():
+            f.close()
 
 
 def bound_value(val, slack_percentage: float) -> np.ndarray:

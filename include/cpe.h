@@ -440,6 +440,34 @@ cpe_status cpe_solve_kinetic_force_box(cpe_handle* h, const cpe_kinetic_options*
                                        double* positions, double* meas_err, double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats,
                                        cpe_kinetic_stats* kstats);
 
+/* ---- ragged physics-based solve: cpe_solve_kinetic for B sequences of their own length and model in ONE solve, on any handle
+ * (a cpe_create_multi handle; a cpe_create handle has one model: ragged lengths only).  opts[k] are the kinetic options of model k (one per model
+ * of the handle); model[b] and n_frames[b] (1 .. N_max) are HOST arrays.  The three optional arrays select the variant of the whole batch: all
+ * NULL = free foot forces (cpe_solve_kinetic), grf_fixed (cpe_solve_kinetic_fixed), tau_box (cpe_solve_kinetic_bounded) or grf_box
+ * (cpe_solve_kinetic_force_box); more than one non-NULL is CPE_BAD_ARG.  Layout as cpe_solve_ragged's, N_max frames and C_max cameras:
+ *   q_init, q, dq, ddq, slack [B][N_max][nq] ; meas, meas_err [B][N_max][C_max][L][2] ; weight [B][N_max][C_max][L] ; positions [B][N_max][L][3] ;
+ *   stance [B][N_max][n_feet] ; grf_fixed [B][N_max][n_feet][3] ; tau_box [B][N_max][n_motors][2] ; grf_box [B][N_max][n_feet][3][2] ;
+ *   tau [B][N_max][n_motors] ; lambda [B][N_max][n_constraints] ; grf [B][N_max][n_feet][5] ; stats, kstats [B] (HOST; kstats may be NULL).
+ * Sequence b reads only its frames n < n_frames[b] and cameras c < its model's count; every output past those is written as 0.0.
+ * Contract: each sequence's outputs, cpe_stats and cpe_kinetic_stats are BIT-EQUAL to those of the matching cpe_solve_kinetic* call of that
+ * sequence alone, on a cpe_create handle of its own model, with its own opts[k] and the same optional array.
+ * The kinetic options of all models must agree in the fields that fix the node's unknowns and rows and the arrays' layout: dyn.n_feet,
+ * dyn.foot_marker, dyn.n_motors, dyn.motor_first / motor_second / motor_axis.  A mismatch fails with CPE_BAD_ARG before anything is launched
+ * and cpe_last_error() names the field and the model.  Every other field may differ per model (inertias, gravity, weights, w_smooth per frame
+ * rate, foot_height_tol, zvel_max, slip_max, the slack box, penalties, damping, inner_iterations).  As for cpe_solve_kinetic, motion_w of every
+ * model's skeleton must be zero.  Device pointers. */
+cpe_status cpe_solve_kinetic_ragged(cpe_handle* h, const cpe_kinetic_options* opts /*[n_models of h]*/, int32_t B, int32_t N_max,
+                                    const int32_t* model /*[B] host*/, const int32_t* n_frames /*[B] host*/, const double* q_init, const double* meas,
+                                    const double* weight, const int32_t* stance, const double* grf_fixed, const double* tau_box, const double* grf_box,
+                                    double* q, double* dq, double* ddq, double* positions, double* meas_err, double* tau, double* lambda, double* grf,
+                                    double* slack, cpe_stats* stats, cpe_kinetic_stats* kstats);
+/* host-pointer twin of cpe_solve_kinetic_ragged (stages through HBM) */
+cpe_status cpe_solve_kinetic_ragged_host(cpe_handle* h, const cpe_kinetic_options* opts, int32_t B, int32_t N_max, const int32_t* model,
+                                         const int32_t* n_frames, const double* q_init, const double* meas, const double* weight, const int32_t* stance,
+                                         const double* grf_fixed, const double* tau_box, const double* grf_box, double* q, double* dq, double* ddq,
+                                         double* positions, double* meas_err, double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats,
+                                         cpe_kinetic_stats* kstats);
+
 /* diagnostic building block of cpe_solve_kinetic (as cpe_eval_normal is of cpe_solve): ONE evaluation of the physics terms of every node at
  * Euler q, multipliers zero, forces from a cold start -- what ASL hands IPOPT per node for the constraints of make_pyomo_model(include_eom_slack=True)
  * (acinoset_opt.py:510-514) after the node forces are minimised out.  Device pointers, each may be NULL: f [B][N][64] node forces (tau | lambda |
