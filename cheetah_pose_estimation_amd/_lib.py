@@ -97,6 +97,7 @@ def load():
     lib.cpe_solve_kinetic_ragged.argtypes = [vp, C.POINTER(abi.KineticOptions), C.c_int32, C.c_int32, ip, ip] + [vp] * 16 + [C.POINTER(abi.Stats), C.POINTER(abi.KineticStats)]
     lib.cpe_solve_kinetic_ragged_host.argtypes = [vp, C.POINTER(abi.KineticOptions), C.c_int32, C.c_int32, ip, ip] + [vp] * 16 + [C.POINTER(abi.Stats), C.POINTER(abi.KineticStats)]
     lib.cpe_eval_kinetic_nodes.argtypes = [vp, C.POINTER(abi.KineticOptions), C.c_int32, C.c_int32] + [vp] * 11
+    lib.cpe_eval_kinetic_system.argtypes = [vp, C.POINTER(abi.KineticOptions), C.c_int32, C.c_int32] + [vp] * 17
     _LIB = lib
     return lib
 
@@ -549,14 +550,23 @@ class Handle:
 
     def eval_kinetic_nodes_host(self, kopts, q, meas, weight, stance):
         """one evaluation of the physics terms per node (cpe_eval_kinetic_nodes); numpy in, dict of numpy arrays out"""
+        return self.eval_kinetic_system_host(kopts, q, meas, weight, stance, band=False)
+
+    def eval_kinetic_system_host(self, kopts, q, meas, weight, stance, grf_fixed=None, tau_box=None, grf_box=None, band=True):
+        """cpe_eval_kinetic_system: the per-node outputs of eval_kinetic_nodes_host and (band) the band system at the handle's lambda0 --
+        gk [B, N, 28], Bk [B, N, 28, 28], Hk [B, N, 2, 28, 28]; grf_fixed / tau_box / grf_box (at most one) in solve_kinetic_host's layouts"""
         import torch
         T, E = self._to_device, self._empty
         qd, me, we, stn = T(q), T(meas), T(weight), T(stance, np.int32)
+        var = [None if a is None else T(a) for a in (grf_fixed, tau_box, grf_box)]
         B, N = qd.shape[0], qd.shape[1]
         out = dict(f=E(B, N, 64), stat=E(B, N, 8), g=E(B, N, 84), Huu=E(B, N, 84, 84), Hfu=E(B, N, 64, 84), Hff=E(B, N, 64, 64))
+        if band:
+            out.update(gk=E(B, N, 28), Bk=E(B, N, 28, 28), Hk=E(B, N, 2, 28, 28))
         meta = torch.empty((B, N, 65), dtype=torch.int32, device=qd.device)
-        self._call(self.lib.cpe_eval_kinetic_nodes, "cpe_eval_kinetic_nodes", C.byref(kopts), B, N, _ptr(qd), _ptr(me), _ptr(we), _ptr(stn),
-                   _ptr(out["f"]), _ptr(out["stat"]), _ptr(out["g"]), _ptr(out["Huu"]), _ptr(out["Hfu"]), _ptr(out["Hff"]), _ptr(meta))
+        self._call(self.lib.cpe_eval_kinetic_system, "cpe_eval_kinetic_system", C.byref(kopts), B, N, _ptr(qd), _ptr(me), _ptr(we), _ptr(stn),
+                   *[_ptr(v) for v in var], _ptr(out["f"]), _ptr(out["stat"]), _ptr(out["g"]), _ptr(out["Huu"]), _ptr(out["Hfu"]), _ptr(out["Hff"]),
+                   _ptr(meta), _ptr(out.get("gk")), _ptr(out.get("Bk")), _ptr(out.get("Hk")))
         self.synchronize()
         res = {k: v.cpu().numpy() for k, v in out.items()}
         res["meta"] = meta.cpu().numpy()

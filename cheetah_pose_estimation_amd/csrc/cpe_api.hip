@@ -1677,7 +1677,18 @@ cpe_status cpe_solve_kinetic_ragged(cpe_handle* h, const cpe_kinetic_options* op
 // meta int32 [B][N][65] = (number of free node forces, their indices).  (What ASL would hand IPOPT for the physics constraints of one node.)
 cpe_status cpe_eval_kinetic_nodes(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q, const double* meas, const double* weight,
                                   const int32_t* stance, double* f, double* stat, double* g, double* Huu, double* Hfu, double* Hff, int32_t* meta) {
+    return cpe_eval_kinetic_system(h, opt, B, N, q, meas, weight, stance, nullptr, nullptr, nullptr, f, stat, g, Huu, Hfu, Hff, meta, nullptr, nullptr, nullptr);
+}
+
+// cpe_eval_kinetic_nodes with the variants of cpe_solve_kinetic_ragged (grf_fixed / tau_box / grf_box, at most one) and the band system that
+// k_lm_step<3, 2> receives at the damping a solve starts with (opts.lambda0): gk [B][N][28], Bk [B][N][28][28], Hk [B][N][2][28][28] (blocks
+// (m, m-1), (m, m-2)), made by k_dyn_schur and k_dyn_gather after the node pieces.
+cpe_status cpe_eval_kinetic_system(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q, const double* meas, const double* weight,
+                                   const int32_t* stance, const double* grf_fixed, const double* tau_box, const double* grf_box, double* f, double* stat,
+                                   double* g, double* Huu, double* Hfu, double* Hff, int32_t* meta, double* gk, double* Bk, double* Hk) {
     if (!h || !opt || !q || !meas || !weight || !stance) return fail(CPE_BAD_ARG, "null argument");
+    if ((grf_fixed != nullptr) + (tau_box != nullptr) + (grf_box != nullptr) > 1)
+        return fail(CPE_BAD_ARG, "cpe_eval_kinetic_system: at most one of grf_fixed, tau_box, grf_box");
     size_t F;
     if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
     if (F == 0) return CPE_OK;
@@ -1686,22 +1697,44 @@ cpe_status cpe_eval_kinetic_nodes(cpe_handle* h, const cpe_kinetic_options* opt,
     cpe_status s = ensure_ws(h, B, N);                     // the workspaces first: build_kin records pointers into them
     if (s != CPE_OK) return s;
     if ((s = ensure_kws(h, B, N)) != CPE_OK) return s;
-    if ((s = build_kin(h, opt)) != CPE_OK) return s;
-    if ((s = state_reset(h, B, N, q)) != CPE_OK || (s = kin_state_reset(h, F, false)) != CPE_OK) return s;
+    if ((s = build_kin(h, opt, grf_fixed, tau_box, grf_box)) != CPE_OK) return s;
+    if ((s = state_reset(h, B, N, q)) != CPE_OK || (s = kin_state_reset(h, F, tau_box != nullptr)) != CPE_OK) return s;
+    // the kernels write the pieces of nodes n >= 2 and their free forces only: the rest of what is copied out below is defined as zero here
+    // (not left from an earlier call)
+    HIPCHK(hipMemsetAsync(h->pieces, 0, sizeof(double) * F * KIN_PIECE, h->stream));
+    HIPCHK(hipMemsetAsync(h->gTb, 0, sizeof(double) * F * KIN_NC3, h->stream));
+    HIPCHK(hipMemsetAsync(h->dstat, 0, sizeof(double) * F * KIN_STAT, h->stream));
+    const bool band = gk || Bk || Hk;
+    std::vector<SeqState> hs;
+    if (band) {          // state_reset has cleared every state (status 0, al_pending 0: k_dyn_schur / k_dyn_gather run); the damping is a solve's first
+        hs.assign((size_t)B, SeqState{});
+        for (SeqState& S : hs) S.lambda = h->opts.lambda0;
+        HIPCHK(hipMemcpyAsync(h->st, hs.data(), sizeof(SeqState) * B, hipMemcpyHostToDevice, h->stream));
+    }
     const DevModel& m = h->hm;
     hipLaunchKernelGGL(FRAME_NORMAL(h->gmm_k == 0), dim3((unsigned)F), dim3(WAVE), lds_normal(m, h->gmm_k, h->gmm_dim), h->stream, h->dm, h->st, N, 1, F, h->qbuf, meas, weight,
                        h->gbuf, h->Bbuf, h->costbuf, h->mu, h->gambuf, h->pri, nullptr, nullptr, ShutterArgs{nullptr, nullptr, nullptr}, RaggedArgs{});
     launch_dyn_eval<>(h, N, 1, F, stance, nullptr, nullptr, B);
     launch_dyn_pieces<>(h, N, 1, F, nullptr, nullptr, B);
+    if (band) {
+        hipLaunchKernelGGL(k_dyn_schur<>, dim3((unsigned)F), dim3(KIN_THREADS), lds_kin_schur(), h->stream, h->dk, h->st, N, F, h->pieces, h->pmeta, h->fbuf, h->kmu,
+                           stance, h->Tbuf, nullptr, nullptr, RaggedArgs{});
+        hipLaunchKernelGGL(k_dyn_gather<>, dim3((unsigned)F), dim3(KIN_THREADS), 0, h->stream, h->st, N, F, h->gbuf, h->Bbuf, h->Tbuf, h->gTb, h->gk, h->Bk, h->Hk,
+                           nullptr, nullptr, RaggedArgs{});
+    }
     HIPCHK(hipGetLastError());
     if (f) HIPCHK(hipMemcpyAsync(f, h->fbuf, sizeof(double) * F * KIN_LS, hipMemcpyDeviceToDevice, h->stream));
     if (stat) HIPCHK(hipMemcpyAsync(stat, h->dstat, sizeof(double) * F * KIN_STAT, hipMemcpyDeviceToDevice, h->stream));
     if (g) HIPCHK(hipMemcpyAsync(g, h->gTb, sizeof(double) * F * KIN_NC3, hipMemcpyDeviceToDevice, h->stream));
     if (meta) HIPCHK(hipMemcpyAsync(meta, h->pmeta, sizeof(int) * F * (KIN_LS + 1), hipMemcpyDeviceToDevice, h->stream));
-    const size_t w = sizeof(double);
+    const size_t w = sizeof(double), BB = (size_t)CPE_NX * CPE_NX;
     if (Huu) HIPCHK(hipMemcpy2DAsync(Huu, w * KIN_NC3 * KIN_NC3, h->pieces, w * KIN_PIECE, w * KIN_NC3 * KIN_NC3, F, hipMemcpyDeviceToDevice, h->stream));
     if (Hfu) HIPCHK(hipMemcpy2DAsync(Hfu, w * KIN_LS * KIN_NC3, h->pieces + KIN_NC3 * KIN_NC3, w * KIN_PIECE, w * KIN_LS * KIN_NC3, F, hipMemcpyDeviceToDevice, h->stream));
     if (Hff) HIPCHK(hipMemcpy2DAsync(Hff, w * KIN_LS * KIN_LS, h->pieces + KIN_NC3 * KIN_NC3 + KIN_LS * KIN_NC3, w * KIN_PIECE, w * KIN_LS * KIN_LS, F, hipMemcpyDeviceToDevice, h->stream));
+    if (gk) HIPCHK(hipMemcpyAsync(gk, h->gk, w * F * CPE_NX, hipMemcpyDeviceToDevice, h->stream));
+    if (Bk) HIPCHK(hipMemcpyAsync(Bk, h->Bk, w * F * BB, hipMemcpyDeviceToDevice, h->stream));
+    if (Hk) HIPCHK(hipMemcpy2DAsync(Hk, w * 2 * BB, h->Hk, w * 3 * BB, w * 2 * BB, F, hipMemcpyDeviceToDevice, h->stream));     // (the third block is zero)
+    if (band) HIPCHK(hipStreamSynchronize(h->stream));      // (hs is read by the copy above)
     return CPE_OK;
 }
 

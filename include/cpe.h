@@ -477,6 +477,16 @@ cpe_status cpe_solve_kinetic_ragged_host(cpe_handle* h, const cpe_kinetic_option
 cpe_status cpe_eval_kinetic_nodes(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q, const double* meas,
                                   const double* weight, const int32_t* stance, double* f, double* stat, double* g, double* Huu, double* Hfu,
                                   double* Hff, int32_t* meta);
+/* cpe_eval_kinetic_nodes with the variants of cpe_solve_kinetic_ragged -- grf_fixed [B][N][nf][3], tau_box [B][N][n_motors][2], grf_box
+ * [B][N][nf][3][2], device pointers, at most one non-NULL (else CPE_BAD_ARG) -- and the band system of the physics-based solve that this
+ * evaluation gives at the damping a solve starts with (opts.lambda0 of the handle), device pointers, each may be NULL: gk [B][N][28] gradient,
+ * Bk [B][N][28][28] diagonal block, Hk [B][N][2][28][28] blocks (m, m-1) and (m, m-2) of frame m; the node forces enter the band through
+ * their elimination at that damping (lm_force_damping, lm_wall_damping).  In both entries the per-node outputs of nodes 0 and 1, and the
+ * entries past a node's free forces, are zero. */
+cpe_status cpe_eval_kinetic_system(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q, const double* meas,
+                                   const double* weight, const int32_t* stance, const double* grf_fixed, const double* tau_box, const double* grf_box,
+                                   double* f, double* stat, double* g, double* Huu, double* Hfu, double* Hff, int32_t* meta, double* gk, double* Bk,
+                                   double* Hk);
 
 /* forward kinematics only (get_pose_state / get_com, acinoset_misc.py:1581-1659, :722-742); device ptrs */
 cpe_status cpe_forward_kinematics(cpe_handle* h, int32_t B, int32_t N, const double* q,

@@ -1146,22 +1146,35 @@ void cpo_default_kinetic_options(cpe_kinetic_options* o, double fps, int kinetic
     o->reg_force = 1e-4; o->kappa_force = 1e5; o->kappa_height = 1e6; o->kappa_slip = 1e2; o->lm_force_damping = 10.0; o->lm_wall_damping = 10.0; o->inner_iterations = 30; o->_pad = 0;
 }
 
-/* objective of the physics-based model at a point (multipliers zero), its reduced gradient and, optionally, the band matrix:
- * for finite-difference checks of kin_term (tests) */
-double cpo_kinetic_objective(const cpe_skeleton* s, const cpe_camera* cams, int C, const cpe_options* o, const cpe_priors* pr,
-                             const cpe_kinetic_options* ko, int N, double* q, const double* meas, const double* weight, const int32_t* stance,
-                             double* g /*[N*nu] or NULL*/, double* Hband /*[N*nu][4 nu] or NULL*/, double* terms /*[8] or NULL*/) {
-    ctx_t x; ctx_init(&x, s, cams, C, o, pr);
-    kin_t K; memset(&K, 0, sizeof(K));
-    K.ko = ko; K.stance = stance; K.N = N; K.nm = ko->dyn.n_motors; K.nf = ko->dyn.n_feet; K.h = o->h; K.numeric_jacobian = g_numeric_jacobian;
-    for (int j = 0; j < s->n_joints; j++) K.nc += s->joint_kind[j] == CPE_JOINT_REVOLUTE_Y ? 2 : 1;
-    K.nlat = K.nm + K.nc + 3 * K.nf;
+/* the kin_t of one evaluation at a point, outside a solve: multipliers zero, node forces from a cold start; grf_fix / tau_box / grf_box (at
+ * most one, NULL = none) in the layouts of cpo_solve_kinetic_fixed / _bounded / _force_box.  kin_point_free releases it. */
+static void kin_point_init(kin_t* K, const cpe_skeleton* s, const cpe_options* o, const cpe_kinetic_options* ko, int N, const int32_t* stance,
+                           const double* grf_fix, const double* tau_box, const double* grf_box) {
+    memset(K, 0, sizeof(*K));
+    K->ko = ko; K->stance = stance; K->N = N; K->nm = ko->dyn.n_motors; K->nf = ko->dyn.n_feet; K->h = o->h; K->numeric_jacobian = g_numeric_jacobian;
+    K->grf_fix = grf_fix; K->tau_box = tau_box; K->grf_box = grf_box;
+    for (int j = 0; j < s->n_joints; j++) K->nc += s->joint_kind[j] == CPE_JOINT_REVOLUTE_Y ? 2 : 1;
+    K->nlat = K->nm + K->nc + 3 * K->nf;
     double M = 0; for (int i = 0; i < s->n_links; i++) M += s->mass[i];
-    K.Mg = M * ko->dyn.eom.gravity;
-    K.f_cur = (double*)calloc((size_t)N * K.nlat + 1, sizeof(double)); K.f_try = (double*)calloc((size_t)N * K.nlat + 1, sizeof(double));
-    K.mu = (double*)calloc((size_t)N * K.nf * KIN_MU + 1, sizeof(double)); K.mu_slack = (double*)calloc((size_t)N * CPE_MAX_NQ * 2 + 1, sizeof(double));
-    K.pHuu = (double*)malloc(sizeof(double) * (size_t)N * KIN_NC3 * KIN_NC3); K.pHfu = (double*)malloc(sizeof(double) * (size_t)N * CPE_KIN_MAXLAT * KIN_NC3);
-    K.pHff = (double*)malloc(sizeof(double) * (size_t)N * CPE_KIN_MAXLAT * CPE_KIN_MAXLAT); K.pna = (int*)calloc(N + 1, sizeof(int));
+    K->Mg = M * ko->dyn.eom.gravity;
+    K->f_cur = (double*)calloc((size_t)N * K->nlat + 1, sizeof(double)); K->f_try = (double*)calloc((size_t)N * K->nlat + 1, sizeof(double));
+    K->mu = (double*)calloc((size_t)N * K->nf * KIN_MU + 1, sizeof(double)); K->mu_slack = (double*)calloc((size_t)N * CPE_MAX_NQ * 2 + 1, sizeof(double));
+    K->mu_tau = (double*)calloc((size_t)N * K->nm * 2 + 1, sizeof(double));
+    K->pHuu = (double*)malloc(sizeof(double) * (size_t)N * KIN_NC3 * KIN_NC3); K->pHfu = (double*)malloc(sizeof(double) * (size_t)N * CPE_KIN_MAXLAT * KIN_NC3);
+    K->pHff = (double*)malloc(sizeof(double) * (size_t)N * CPE_KIN_MAXLAT * CPE_KIN_MAXLAT); K->pna = (int*)calloc(N + 1, sizeof(int));
+}
+static void kin_point_free(kin_t* K) {
+    free(K->f_cur); free(K->f_try); free(K->mu); free(K->mu_slack); free(K->mu_tau); free(K->pHuu); free(K->pHfu); free(K->pHff); free(K->pna);
+}
+
+/* objective of the physics-based model at a point (multipliers zero), its reduced gradient and, optionally, the band matrix:
+ * for finite-difference checks of kin_term (tests).  grf_fix / tau_box / grf_box: as kin_point_init */
+double cpo_kinetic_objective_variant(const cpe_skeleton* s, const cpe_camera* cams, int C, const cpe_options* o, const cpe_priors* pr,
+                                     const cpe_kinetic_options* ko, int N, double* q, const double* meas, const double* weight, const int32_t* stance,
+                                     const double* grf_fix, const double* tau_box, const double* grf_box,
+                                     double* g /*[N*nu] or NULL*/, double* Hband /*[N*nu][4 nu] or NULL*/, double* terms /*[8] or NULL*/) {
+    ctx_t x; ctx_init(&x, s, cams, C, o, pr);
+    kin_t K; kin_point_init(&K, s, o, ko, N, stance, grf_fix, tau_box, grf_box);
     x.kin = &K;
     int kd = 4 * x.nu - 1;
     costs_t ct;
@@ -1173,26 +1186,26 @@ double cpo_kinetic_objective(const cpe_skeleton* s, const cpe_camera* cams, int 
     if (terms) { terms[0] = ct.meas; terms[1] = ct.model; terms[2] = ct.pose; terms[3] = ct.bound; terms[4] = K.torque; terms[5] = K.energy; terms[6] = K.eom; terms[7] = K.al; }
     if (g && ab) kin_add_schur(&x, N, kd, 0.0, ab);           /* exact variable-projection Gauss-Newton matrix */
     if (g && !Hband) free(ab);
-    free(st); free(K.f_cur); free(K.f_try); free(K.mu); free(K.mu_slack); free(K.pHuu); free(K.pHfu); free(K.pHff); free(K.pna);
+    free(st); kin_point_free(&K);
     return ct.total;
+}
+double cpo_kinetic_objective(const cpe_skeleton* s, const cpe_camera* cams, int C, const cpe_options* o, const cpe_priors* pr,
+                             const cpe_kinetic_options* ko, int N, double* q, const double* meas, const double* weight, const int32_t* stance,
+                             double* g /*[N*nu] or NULL*/, double* Hband /*[N*nu][4 nu] or NULL*/, double* terms /*[8] or NULL*/) {
+    return cpo_kinetic_objective_variant(s, cams, C, o, pr, ko, N, q, meas, weight, stance, NULL, NULL, NULL, g, Hband, terms);
 }
 
 
-/* per-node quantities of one evaluation of the physics terms (multipliers zero, cold start), in cpe_eval_kinetic_nodes' layout:
- * f [N][64], stat [N][8], g [N][84], Huu [N][84][84], Hfu [N][64][84], Hff [N][64][64], meta [N][65] */
-void cpo_kinetic_nodes(const cpe_skeleton* s, const cpe_camera* cams, int C, const cpe_options* o, const cpe_kinetic_options* ko, int N,
-                       const double* q, const int32_t* stance, double* f, double* stat, double* g, double* Huu, double* Hfu, double* Hff, int32_t* meta) {
-    ctx_t x; ctx_init(&x, s, cams, C, o, NULL);
-    kin_t K; memset(&K, 0, sizeof(K));
-    K.ko = ko; K.stance = stance; K.N = N; K.nm = ko->dyn.n_motors; K.nf = ko->dyn.n_feet; K.h = o->h; K.numeric_jacobian = g_numeric_jacobian;
-    for (int j = 0; j < s->n_joints; j++) K.nc += s->joint_kind[j] == CPE_JOINT_REVOLUTE_Y ? 2 : 1;
-    K.nlat = K.nm + K.nc + 3 * K.nf;
-    double M = 0; for (int i = 0; i < s->n_links; i++) M += s->mass[i];
-    K.Mg = M * ko->dyn.eom.gravity;
-    K.f_cur = (double*)calloc((size_t)N * K.nlat + 1, sizeof(double)); K.f_try = (double*)calloc((size_t)N * K.nlat + 1, sizeof(double));
-    K.mu = (double*)calloc((size_t)N * K.nf * KIN_MU + 1, sizeof(double)); K.mu_slack = (double*)calloc((size_t)N * CPE_MAX_NQ * 2 + 1, sizeof(double));
-    K.pHuu = (double*)malloc(sizeof(double) * (size_t)N * KIN_NC3 * KIN_NC3); K.pHfu = (double*)malloc(sizeof(double) * (size_t)N * CPE_KIN_MAXLAT * KIN_NC3);
-    K.pHff = (double*)malloc(sizeof(double) * (size_t)N * CPE_KIN_MAXLAT * CPE_KIN_MAXLAT); K.pna = (int*)calloc(N + 1, sizeof(int));
+/* one evaluation of the physics terms (multipliers zero, cold start) in cpe_eval_kinetic_system's layout.  Per node, each may be NULL:
+ * f [N][64], stat [N][8], g [N][84], Huu [N][84][84], Hfu [N][64][84], Hff [N][64][64], meta [N][65].  The band system at damping lam, per
+ * frame (needs meas / weight): gk [N][28] the gradient, Bk [N][28][28] the diagonal block, Hk [N][2][28][28] the blocks (m, m-1) and (m, m-2)
+ * -- the per-frame terms of seq_eval plus kin_add_schur(lam).  grf_fix / tau_box / grf_box: as kin_point_init */
+void cpo_kinetic_system(const cpe_skeleton* s, const cpe_camera* cams, int C, const cpe_options* o, const cpe_priors* pr, const cpe_kinetic_options* ko,
+                        int N, const double* q, const double* meas, const double* weight, const int32_t* stance, const double* grf_fix,
+                        const double* tau_box, const double* grf_box, double lam, double* f, double* stat, double* g, double* Huu, double* Hfu,
+                        double* Hff, int32_t* meta, double* gk, double* Bk, double* Hk) {
+    ctx_t x; ctx_init(&x, s, cams, C, o, pr);
+    kin_t K; kin_point_init(&K, s, o, ko, N, stance, grf_fix, tau_box, grf_box);
     x.kin = &K;
     K.dbgJ = g_dbgJ; K.dbgJ_node = g_dbgJ_node;
     double* st = (double*)malloc(sizeof(double) * (size_t)N * x.ns);
@@ -1206,9 +1219,9 @@ void cpo_kinetic_nodes(const cpe_skeleton* s, const cpe_camera* cams, int C, con
         if (n >= 2) {
             kin_term(&x, &K, n, st + (size_t)n * x.ns, st + (size_t)(n - 1) * x.ns, st + (size_t)(n - 2) * x.ns, gT, HT, &R);
             na = K.pna[n];
-            for (int m = 0; m < K.nm + K.nc; m++) idx[m] = m;
-            int a = K.nm + K.nc;
-            for (int k = 0; k < K.nf; k++) if (stance[(size_t)n * K.nf + k]) for (int d = 0; d < 3; d++) idx[a++] = K.nm + K.nc + 3 * k + d;
+            int a = 0;                                     /* the free node forces in kin_inner's order */
+            for (int m = 0; m < K.nm + K.nc; m++) idx[a++] = m;
+            if (!grf_fix) for (int k = 0; k < K.nf; k++) if (stance[(size_t)n * K.nf + k]) for (int d = 0; d < 3; d++) idx[a++] = K.nm + K.nc + 3 * k + d;
         }
         if (f) { for (int i = 0; i < 64; i++) f[(size_t)n * 64 + i] = i < K.nlat && n >= 2 ? K.f_cur[(size_t)n * K.nlat + i] : 0.0; }
         if (stat) { double* d = stat + (size_t)n * 8; d[0] = R.eom; d[1] = R.torque; d[2] = R.reg; d[3] = R.energy; d[4] = R.al; d[5] = R.max_slack; d[6] = R.max_base; d[7] = R.max_viol; }
@@ -1219,7 +1232,33 @@ void cpo_kinetic_nodes(const cpe_skeleton* s, const cpe_camera* cams, int C, con
         if (Hfu) for (int i = 0; i < na; i++) memcpy(Hfu + ((size_t)n * 64 + i) * nc3, K.pHfu + (size_t)n * CPE_KIN_MAXLAT * nc3 + (size_t)i * nc3, sizeof(double) * nc3);
         if (Hff) for (int i = 0; i < na; i++) for (int j = 0; j < na; j++) Hff[((size_t)n * 64 + i) * 64 + j] = K.pHff[(size_t)n * CPE_KIN_MAXLAT * CPE_KIN_MAXLAT + (size_t)i * na + j];
     }
-    free(gT); free(HT); free(st); free(K.f_cur); free(K.f_try); free(K.mu); free(K.mu_slack); free(K.pHuu); free(K.pHfu); free(K.pHff); free(K.pna);
+    if (gk || Bk || Hk) {
+        /* the band: cpo_kinetic_objective_variant's evaluation (cold start again: the loop above has left its forces in f_cur), then the
+         * elimination of the node forces at damping lam */
+        int nu = x.nu, kd = 4 * nu - 1;
+        memset(K.f_cur, 0, sizeof(double) * (size_t)N * K.nlat);
+        double* gg = (double*)malloc(sizeof(double) * (size_t)N * nu); double* ab = (double*)malloc(sizeof(double) * (size_t)N * nu * (kd + 1));
+        costs_t ct;
+        seq_eval(&x, N, kd, st, meas, weight, NULL, &ct, gg, ab);
+        kin_add_schur(&x, N, kd, lam, ab);
+        for (int m = 0; m < N; m++) {
+            if (gk) memcpy(gk + (size_t)m * nu, gg + (size_t)m * nu, sizeof(double) * nu);
+            for (int i = 0; i < nu; i++) for (int j = 0; j < nu; j++) {
+                int ia = m * nu + i;
+                if (Bk) Bk[((size_t)m * nu + i) * nu + j] = j <= i ? AB(ia, m * nu + j) : AB(m * nu + j, ia);
+                if (Hk) for (int t = 0; t < 2; t++) Hk[(((size_t)m * 2 + t) * nu + i) * nu + j] = m >= t + 1 ? AB(ia, (m - 1 - t) * nu + j) : 0.0;
+            }
+        }
+        free(gg); free(ab);
+    }
+    free(gT); free(HT); free(st); kin_point_free(&K);
+}
+
+/* per-node quantities of one evaluation of the physics terms (multipliers zero, cold start), in cpe_eval_kinetic_nodes' layout:
+ * f [N][64], stat [N][8], g [N][84], Huu [N][84][84], Hfu [N][64][84], Hff [N][64][64], meta [N][65] */
+void cpo_kinetic_nodes(const cpe_skeleton* s, const cpe_camera* cams, int C, const cpe_options* o, const cpe_kinetic_options* ko, int N,
+                       const double* q, const int32_t* stance, double* f, double* stat, double* g, double* Huu, double* Hfu, double* Hff, int32_t* meta) {
+    cpo_kinetic_system(s, cams, C, o, NULL, ko, N, q, NULL, NULL, stance, NULL, NULL, NULL, 0.0, f, stat, g, Huu, Hfu, Hff, meta, NULL, NULL, NULL);
 }
 
 /* physics-based trajectory model: include/cpe.h, cpe_solve_kinetic (estimate_kinetics, acinoset_opt.py:693-963) */

@@ -119,19 +119,28 @@ def solve_kinetic(sk, cams, opts, priors, kopts, q_init, meas, weight, stance, g
     return dict(status=rc, q=q, dq=dq, ddq=ddq, positions=pos, meas_err=me, tau=tau, lam=lam, grf=grf, slack=slack, stats=st, kstats=ks)
 
 
-def kinetic_objective(sk, cams, opts, priors, kopts, q, meas, weight, stance, want_grad=True, want_band=False):
-    """(total, g [N, nu] or None, consistent q, terms[8], band or None) of the physics-based model's objective at q"""
+def kinetic_objective(sk, cams, opts, priors, kopts, q, meas, weight, stance, want_grad=True, want_band=False, grf_fixed=None, tau_box=None, grf_box=None):
+    """(total, g [N, nu] or None, consistent q, terms[8], band or None) of the physics-based model's objective at q; grf_fixed / tau_box /
+    grf_box (at most one): the variants of solve_kinetic"""
     q, meas, weight = _c(q).copy(), _c(meas), _c(weight)
     stance = np.ascontiguousarray(stance, dtype=np.int32)
+    gf, tb, gb = _variants(grf_fixed, tau_box, grf_box)
     N, Cn, L = weight.shape
     nu = 28
     g = np.zeros((N, nu)) if want_grad else None
     band = np.zeros((N * nu, 4 * nu)) if want_band else None
     terms = np.zeros(8)
-    lib().cpo_kinetic_objective.restype = C.c_double
-    f = lib().cpo_kinetic_objective(C.byref(sk), cams, Cn, C.byref(opts), C.byref(priors) if priors is not None else None, C.byref(kopts), N,
-                                    _p(q), _p(meas), _p(weight), stance.ctypes.data_as(C.POINTER(C.c_int32)), _p(g), _p(band), _p(terms))
+    lib().cpo_kinetic_objective_variant.restype = C.c_double
+    f = lib().cpo_kinetic_objective_variant(C.byref(sk), cams, Cn, C.byref(opts), C.byref(priors) if priors is not None else None, C.byref(kopts), N,
+                                            _p(q), _p(meas), _p(weight), stance.ctypes.data_as(C.POINTER(C.c_int32)), _p(gf), _p(tb), _p(gb),
+                                            _p(g), _p(band), _p(terms))
     return float(f), g, q, terms, band
+
+
+def _variants(grf_fixed, tau_box, grf_box):
+    out = tuple(None if a is None else _c(a) for a in (grf_fixed, tau_box, grf_box))
+    assert sum(a is not None for a in out) <= 1, "at most one of grf_fixed, tau_box, grf_box"
+    return out
 
 
 def set_numeric_jacobian(on: bool):
@@ -148,14 +157,35 @@ def kinetic_nodes(sk, cams, opts, kopts, q, stance, jac_node=None):
     if jac_node is not None:
         Jd = np.zeros((sk.nq + 4 * kopts.dyn.n_feet + 3 * sk.n_markers, 84))
         lib().cpo_set_debug_jacobian(_p(Jd), int(jac_node))
-    out = dict(f=np.zeros((N, 64)), stat=np.zeros((N, 8)), g=np.zeros((N, 84)), Huu=np.zeros((N, 84, 84)), Hfu=np.zeros((N, 64, 84)),
-               Hff=np.zeros((N, 64, 64)), meta=np.zeros((N, 65), dtype=np.int32))
+    out = _node_outputs(N)
     lib().cpo_kinetic_nodes(C.byref(sk), cams, len(cams), C.byref(opts), C.byref(kopts), N, _p(q), stance.ctypes.data_as(C.POINTER(C.c_int32)),
                             _p(out["f"]), _p(out["stat"]), _p(out["g"]), _p(out["Huu"]), _p(out["Hfu"]), _p(out["Hff"]),
                             out["meta"].ctypes.data_as(C.POINTER(C.c_int32)))
     if Jd is not None:
         lib().cpo_set_debug_jacobian(None, -1)
         out["J"] = Jd
+    return out
+
+
+def _node_outputs(N):
+    return dict(f=np.zeros((N, 64)), stat=np.zeros((N, 8)), g=np.zeros((N, 84)), Huu=np.zeros((N, 84, 84)), Hfu=np.zeros((N, 64, 84)),
+                Hff=np.zeros((N, 64, 64)), meta=np.zeros((N, 65), dtype=np.int32))
+
+
+def kinetic_system(sk, cams, opts, priors, kopts, q, meas, weight, stance, lam=0.0, grf_fixed=None, tau_box=None, grf_box=None):
+    """one evaluation of the physics terms in cpe_eval_kinetic_system's layout (dict of arrays): kinetic_nodes' per-node outputs, plus the band
+    system at damping lam -- gk [N, 28], Bk [N, 28, 28], Hk [N, 2, 28, 28] (blocks (m, m-1), (m, m-2)); grf_fixed / tau_box / grf_box (at most
+    one): the variants of solve_kinetic"""
+    q, meas, weight = _c(q), _c(meas), _c(weight)
+    stance = np.ascontiguousarray(stance, dtype=np.int32)
+    gf, tb, gb = _variants(grf_fixed, tau_box, grf_box)
+    N = q.shape[0]
+    out = _node_outputs(N)
+    out.update(gk=np.zeros((N, 28)), Bk=np.zeros((N, 28, 28)), Hk=np.zeros((N, 2, 28, 28)))
+    lib().cpo_kinetic_system(C.byref(sk), cams, len(cams), C.byref(opts), C.byref(priors) if priors is not None else None, C.byref(kopts), N,
+                             _p(q), _p(meas), _p(weight), stance.ctypes.data_as(C.POINTER(C.c_int32)), _p(gf), _p(tb), _p(gb), C.c_double(lam),
+                             _p(out["f"]), _p(out["stat"]), _p(out["g"]), _p(out["Huu"]), _p(out["Hfu"]), _p(out["Hff"]),
+                             out["meta"].ctypes.data_as(C.POINTER(C.c_int32)), _p(out["gk"]), _p(out["Bk"]), _p(out["Hk"]))
     return out
 
 

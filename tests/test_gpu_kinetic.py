@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import kinetic_compare as KC
 from cheetah_pose_estimation_amd import abi, skeleton, synth
 
 pytestmark = pytest.mark.gpu
@@ -38,6 +39,8 @@ def test_node_terms_match_oracle(oracle, gpu_handle_factory):
         for key, tol in (("f", 1e-10), ("stat", 1e-10), ("g", 1e-9), ("Huu", 1e-9), ("Hfu", 1e-9), ("Hff", 1e-12)):
             den = np.abs(R[key]).max()
             assert np.abs(G[key][b] - R[key]).max() < tol * den, (key, np.abs(G[key][b] - R[key]).max() / den)
+        # and entry by entry, each against the scale the oracle sets for it (tests/kinetic_compare.py)
+        KC.check({k: v[b] for k, v in G.items()}, R, sk, ko, {k: KC.TOL[k] for k in KC.NODE_KEYS}, label=f"node terms {b}")
 
 
 def _compare_solves(oracle, gpu_handle_factory, N, B, n_oracle, max_iter, seed=4321):
@@ -480,6 +483,7 @@ def test_kinetic_dataset_variant_matches_oracle(oracle, gpu_handle_factory):
         R = oracle.kinetic_nodes(sk, cams, opts, ko, kin["q"][b], d["stance"][b])
         for key, tol in (("f", 1e-10), ("stat", 1e-10), ("g", 1e-9), ("Huu", 1e-9), ("Hfu", 1e-9), ("Hff", 1e-12)):
             assert np.abs(G[key][b] - R[key]).max() < tol * np.abs(R[key]).max(), key
+        KC.check({k: v[b] for k, v in G.items()}, R, sk, ko, {k: KC.TOL[k] for k in KC.NODE_KEYS}, label=f"kinetic dataset node terms {b}")
         ro = oracle.solve_kinetic(sk, cams, opts, None, ko, kin["q"][b], d["meas"][b], d["weight"][b], d["stance"][b])
         st, so, ks = r["stats"][b], ro["stats"], r["kstats"][b]
         rmse = float(np.sqrt(((r["positions"][b] - ro["positions"]) ** 2).sum(-1).mean()))
