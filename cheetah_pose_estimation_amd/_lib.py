@@ -98,6 +98,7 @@ def load():
     lib.cpe_solve_kinetic_ragged_host.argtypes = [vp, C.POINTER(abi.KineticOptions), C.c_int32, C.c_int32, ip, ip] + [vp] * 16 + [C.POINTER(abi.Stats), C.POINTER(abi.KineticStats)]
     lib.cpe_eval_kinetic_nodes.argtypes = [vp, C.POINTER(abi.KineticOptions), C.c_int32, C.c_int32] + [vp] * 11
     lib.cpe_eval_kinetic_system.argtypes = [vp, C.POINTER(abi.KineticOptions), C.c_int32, C.c_int32] + [vp] * 17
+    lib.cpe_eval_lm_step.argtypes = [vp, C.POINTER(abi.KineticOptions), C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_double] + [vp] * 6
     _LIB = lib
     return lib
 
@@ -206,6 +207,7 @@ class Handle:
             raise CpeError("no HIP device visible: the solve path has no CPU fallback (" + self.lib.cpe_last_error().decode() + ")")
         _check(st, "cpe_create")
         self.device = device
+        self.pb = max(3, priors.lr_window) if priors is not None else 3     # half-bandwidth of the solver's band in frames
         self.S = self.lib.cpe_jacobian_slots(self._h)
         self.nu = self.lib.cpe_num_independent(self._h)
         self.nq, self.L = sk.nq, sk.n_markers
@@ -235,6 +237,7 @@ class Handle:
         self.sk, self.cams, self.n_cams, self.opts = skels[0], cams_list[0], max(len(cl) for cl in cams_list), opts_list[0]
         self.model_n_cams = [len(cl) for cl in cams_list]
         self.device = device
+        self.pb = max(3, priors.lr_window) if priors is not None else 3     # half-bandwidth of the solver's band in frames
         self.S = self.lib.cpe_jacobian_slots(self._h)
         self.nu = self.lib.cpe_num_independent(self._h)
         self.nq, self.L = skels[0].nq, skels[0].n_markers
@@ -570,6 +573,26 @@ class Handle:
         self.synchronize()
         res = {k: v.cpu().numpy() for k, v in out.items()}
         res["meta"] = meta.cpu().numpy()
+        return res
+
+    def eval_lm_step_host(self, q, meas, weight, lam, kopts=None, stance=None):
+        """cpe_eval_lm_step: the first LM iteration of a solve from Euler q at damping lam -- the kinematic model, or with kopts and stance the
+        physics-based one.  numpy in, dict of numpy arrays out: g, dg, delta [B, N, 28], L [B, N, pb + 1, 28, 28] (block [n][i] = block
+        (n + i, n) of the lower Cholesky factor), state [B, N, 2, ns] (current, trial), seq [B, 8] (cost terms meas, model, bound, pose, motion;
+        pred, maxstep, status)"""
+        import torch
+        T, E = self._to_device, self._empty
+        qd, me, we = T(q), T(meas), T(weight)
+        stn = None if stance is None else T(stance, np.int32)
+        B, N = qd.shape[0], qd.shape[1]
+        ns = self.nq + sum(1 for j in range(self.sk.n_joints) if self.sk.joint_kind[j] == abi.JOINT_REVOLUTE_Y)
+        out = dict(g=E(B, N, 28), dg=E(B, N, 28), L=E(B, N, self.pb + 1, 28, 28), delta=E(B, N, 28), state=E(B, N, 2, ns))
+        seq = np.zeros((B, 8))
+        self._call(self.lib.cpe_eval_lm_step, "cpe_eval_lm_step", C.byref(kopts) if kopts is not None else None, B, N, _ptr(qd), _ptr(me), _ptr(we),
+                   _ptr(stn), float(lam), _ptr(out["g"]), _ptr(out["dg"]), _ptr(out["L"]), _ptr(out["delta"]), _ptr(out["state"]), _ptr(seq))
+        self.synchronize()
+        res = {k: v.cpu().numpy() for k, v in out.items()}
+        res["seq"] = seq
         return res
 
     # ---- host-pointer conveniences (numpy in, numpy out; PCIe-inclusive) -------------------------------

@@ -1029,6 +1029,60 @@ __global__ void k_reset_status(SeqState* __restrict__ st, int B) {
     if (b < B) { st[b].status = 0; st[b].al_pending = 0; }
 }
 
+// One iteration of the kinematic solve (the LmIterate of lm_run): k_frame_normal (+ k_lr_band) on the evaluated buffer, then k_lm_step and
+// k_lm_back.  sh: shutter-delay buffers (all null = off); rg: the ragged table (N = nmax), or null.
+static void lm_iterate(cpe_handle* h, const LmParams& prm, int N, size_t Fw, size_t ldsn, const double* meas, const double* weight, ShutterArgs sh,
+                       const RaggedArgs* rg, int first, const int* act, const int* n_act, int slots) {
+    const bool lr = h->lr_window > 0;
+    const unsigned gf = (unsigned)((size_t)slots * N);
+    const double* hiu = lr ? reinterpret_cast<const double*>(reinterpret_cast<const char*>(h->pri) + offsetof(DevPriors, lr_HIu)) + CPE_NX * CPE_NX : nullptr;
+    if (rg) {      // the same launches in their ragged forms
+        prof_begin(h, 0);
+        hipLaunchKernelGGL(FRAME_NORMAL_RAGGED(h->gmm_k == 0), dim3(gf), dim3(WAVE), ldsn, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, meas, weight,
+                           h->gbuf, h->Bbuf, h->costbuf, h->mu, h->gambuf, h->pri, act, n_act, ShutterArgs{nullptr, nullptr, nullptr}, *rg);
+        prof_end(h);
+        if (lr) {
+            prof_begin(h, 1);
+            hipLaunchKernelGGL(k_lr_band<true>, dim3(gf), dim3(WAVE), 0, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, h->gambuf, h->pri, h->pb, h->gbuf,
+                               h->Bbuf, h->Hlr, h->costbuf, act, n_act, *rg);
+            prof_end(h);
+        }
+        prof_begin(h, 2);
+        if (h->pb == 3) hipLaunchKernelGGL((k_lm_step<3, 0, true>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gbuf,
+                                           h->Bbuf, h->costbuf, h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hlr, act, n_act, 2, nullptr, h->dgbuf, hiu, h->lr_window, *rg);
+        else hipLaunchKernelGGL((k_lm_step<4, 0, true>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gbuf,
+                                h->Bbuf, h->costbuf, h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hlr, act, n_act, 2, nullptr, h->dgbuf, hiu, h->lr_window, *rg);
+        prof_end(h);
+        prof_begin(h, 7);
+        if (h->pb == 3) hipLaunchKernelGGL((k_lm_back<3, true>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf,
+                                           h->gtbuf, h->dgbuf, act, n_act, *rg);
+        else hipLaunchKernelGGL((k_lm_back<4, true>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf,
+                                h->gtbuf, h->dgbuf, act, n_act, *rg);
+        prof_end(h);
+        return;
+    }
+    prof_begin(h, 0);
+    hipLaunchKernelGGL(FRAME_NORMAL(h->gmm_k == 0 && sh.tau == nullptr), dim3(gf), dim3(WAVE), ldsn, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, meas, weight, h->gbuf, h->Bbuf,
+                       h->costbuf, h->mu, h->gambuf, h->pri, act, n_act, sh, RaggedArgs{});
+    prof_end(h);
+    if (lr) {
+        prof_begin(h, 1);
+        hipLaunchKernelGGL(k_lr_band<>, dim3(gf), dim3(WAVE), 0, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, h->gambuf, h->pri, h->pb, h->gbuf, h->Bbuf,
+                           h->Hlr, h->costbuf, act, n_act);
+        prof_end(h);
+    }
+    prof_begin(h, 2);
+    if (h->pb == 3) hipLaunchKernelGGL((k_lm_step<3, 0>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gbuf, h->Bbuf, h->costbuf,
+                                       h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hlr, act, n_act, 2, sh.gx, h->dgbuf, hiu, h->lr_window);
+    else hipLaunchKernelGGL((k_lm_step<4, 0>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gbuf, h->Bbuf, h->costbuf,
+                            h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hlr, act, n_act, 2, sh.gx, h->dgbuf, hiu, h->lr_window);
+    prof_end(h);
+    prof_begin(h, 7);
+    if (h->pb == 3) hipLaunchKernelGGL((k_lm_back<3>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf, h->gtbuf, h->dgbuf, act, n_act);
+    else hipLaunchKernelGGL((k_lm_back<4>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf, h->gtbuf, h->dgbuf, act, n_act);
+    prof_end(h);
+}
+
 // The LM run of cpe_solve on the handle's workspace: cold start from q_init (device pointer) or, with q_init == nullptr, a restart from
 // the current iterate of every sequence.  sh: shutter-delay buffers (all null = off).
 // rg: the ragged table of cpe_solve_ragged (N = nmax; no shutter delay), or null.
@@ -1042,58 +1096,9 @@ static cpe_status lm_run(cpe_handle* h, int B, int N, const double* q_init, cons
     } else hipLaunchKernelGGL(k_reset_status, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->st, B);
     const LmParams prm = lm_params(h, B, N);
     const size_t ldsn = rg ? lds_normal_all(h) : lds_normal(m, h->gmm_k, h->gmm_dim, sh.tau != nullptr);
-    const bool lr = h->lr_window > 0;
-    // k_frame_normal (+ k_lr_band) on the evaluated buffer, then k_lm_step and k_lm_back
-    auto iterate = [&](int first, const int* act, const int* n_act, int slots) {
-        const unsigned gf = (unsigned)((size_t)slots * N);
-        const double* hiu = lr ? reinterpret_cast<const double*>(reinterpret_cast<const char*>(h->pri) + offsetof(DevPriors, lr_HIu)) + CPE_NX * CPE_NX : nullptr;
-        if (rg) {      // the same launches in their ragged forms
-            prof_begin(h, 0);
-            hipLaunchKernelGGL(FRAME_NORMAL_RAGGED(h->gmm_k == 0), dim3(gf), dim3(WAVE), ldsn, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, meas, weight,
-                               h->gbuf, h->Bbuf, h->costbuf, h->mu, h->gambuf, h->pri, act, n_act, ShutterArgs{nullptr, nullptr, nullptr}, *rg);
-            prof_end(h);
-            if (lr) {
-                prof_begin(h, 1);
-                hipLaunchKernelGGL(k_lr_band<true>, dim3(gf), dim3(WAVE), 0, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, h->gambuf, h->pri, h->pb, h->gbuf,
-                                   h->Bbuf, h->Hlr, h->costbuf, act, n_act, *rg);
-                prof_end(h);
-            }
-            prof_begin(h, 2);
-            if (h->pb == 3) hipLaunchKernelGGL((k_lm_step<3, 0, true>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gbuf,
-                                               h->Bbuf, h->costbuf, h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hlr, act, n_act, 2, nullptr, h->dgbuf, hiu, h->lr_window, *rg);
-            else hipLaunchKernelGGL((k_lm_step<4, 0, true>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gbuf,
-                                    h->Bbuf, h->costbuf, h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hlr, act, n_act, 2, nullptr, h->dgbuf, hiu, h->lr_window, *rg);
-            prof_end(h);
-            prof_begin(h, 7);
-            if (h->pb == 3) hipLaunchKernelGGL((k_lm_back<3, true>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf,
-                                               h->gtbuf, h->dgbuf, act, n_act, *rg);
-            else hipLaunchKernelGGL((k_lm_back<4, true>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf,
-                                    h->gtbuf, h->dgbuf, act, n_act, *rg);
-            prof_end(h);
-            return;
-        }
-        prof_begin(h, 0);
-        hipLaunchKernelGGL(FRAME_NORMAL(h->gmm_k == 0 && sh.tau == nullptr), dim3(gf), dim3(WAVE), ldsn, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, meas, weight, h->gbuf, h->Bbuf,
-                           h->costbuf, h->mu, h->gambuf, h->pri, act, n_act, sh, RaggedArgs{});
-        prof_end(h);
-        if (lr) {
-            prof_begin(h, 1);
-            hipLaunchKernelGGL(k_lr_band<>, dim3(gf), dim3(WAVE), 0, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, h->gambuf, h->pri, h->pb, h->gbuf, h->Bbuf,
-                               h->Hlr, h->costbuf, act, n_act);
-            prof_end(h);
-        }
-        prof_begin(h, 2);
-        if (h->pb == 3) hipLaunchKernelGGL((k_lm_step<3, 0>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gbuf, h->Bbuf, h->costbuf,
-                                           h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hlr, act, n_act, 2, sh.gx, h->dgbuf, hiu, h->lr_window);
-        else hipLaunchKernelGGL((k_lm_step<4, 0>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gbuf, h->Bbuf, h->costbuf,
-                                h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hlr, act, n_act, 2, sh.gx, h->dgbuf, hiu, h->lr_window);
-        prof_end(h);
-        prof_begin(h, 7);
-        if (h->pb == 3) hipLaunchKernelGGL((k_lm_back<3>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf, h->gtbuf, h->dgbuf, act, n_act);
-        else hipLaunchKernelGGL((k_lm_back<4>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf, h->gtbuf, h->dgbuf, act, n_act);
-        prof_end(h);
-    };
-    return lm_drive(h, B, iterate);
+    return lm_drive(h, B, [&](int first, const int* act, const int* n_act, int slots) {
+        lm_iterate(h, prm, N, Fw, ldsn, meas, weight, sh, rg, first, act, n_act, slots);
+    });
 }
 
 // Outputs of a finished LM run: k_finalize (tau: the shutter delays, or null), then `more` (what else the caller enqueues there, or
@@ -1735,6 +1740,85 @@ cpe_status cpe_eval_kinetic_system(cpe_handle* h, const cpe_kinetic_options* opt
     if (Bk) HIPCHK(hipMemcpyAsync(Bk, h->Bk, w * F * BB, hipMemcpyDeviceToDevice, h->stream));
     if (Hk) HIPCHK(hipMemcpy2DAsync(Hk, w * 2 * BB, h->Hk, w * 3 * BB, w * 2 * BB, F, hipMemcpyDeviceToDevice, h->stream));     // (the third block is zero)
     if (band) HIPCHK(hipStreamSynchronize(h->stream));      // (hs is read by the copy above)
+    return CPE_OK;
+}
+
+// Diagnostic (include/cpe.h): the first LM iteration of a solve from Euler q at damping lam -- the launches of the first pass of cpe_solve
+// (lm_iterate) or, with kopt, of cpe_solve_kinetic (kin_iterate) -- and what k_lm_step / k_lm_back leave behind, in plain layouts.
+cpe_status cpe_eval_lm_step(cpe_handle* h, const cpe_kinetic_options* kopt, int32_t B, int32_t N, const double* q, const double* meas,
+                            const double* weight, const int32_t* stance, double lam, double* g, double* dg, double* L, double* delta, double* state,
+                            double* seq) {
+    if (!h || !q || !meas || !weight || !seq) return fail(CPE_BAD_ARG, "null argument");
+    if ((kopt == nullptr) != (stance == nullptr)) return fail(CPE_BAD_ARG, "cpe_eval_lm_step: stance is given with the kinetic options, and only then");
+    if (!(lam > 0.0) || !std::isfinite(lam)) return fail(CPE_BAD_ARG, "cpe_eval_lm_step: the damping must be positive and finite");
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    if (kopt && h->pb != 3) return fail(CPE_BAD_ARG, "the physics-based model runs on the half-bandwidth-3 solver");
+    HIPCHK(hipSetDevice(h->device));
+    cpe_status s = ensure_ws(h, B, N);                     // the workspaces first: build_kin records pointers into them
+    if (s != CPE_OK) return s;
+    if (kopt) {
+        if ((s = ensure_kws(h, B, N)) != CPE_OK) return s;
+        if ((s = build_kin(h, kopt)) != CPE_OK) return s;
+    }
+    if ((s = state_reset(h, B, N, q)) != CPE_OK) return s;
+    if (kopt && (s = kin_state_reset(h, F, false)) != CPE_OK) return s;
+    const DevModel& m = h->hm;
+    const int ns = m.ns, RING = h->pb + 1;
+    const size_t BB = (size_t)CPE_NX * CPE_NX, w = sizeof(double), LC = (size_t)RING * BB;
+    // what a sequence without a step leaves is defined here, not left from an earlier call: g, dg, L and delta zero, trial = current
+    HIPCHK(hipMemsetAsync(h->gtbuf, 0, w * F * CPE_NX, h->stream));
+    HIPCHK(hipMemsetAsync(h->dgbuf, 0, w * F * CPE_NX, h->stream));
+    HIPCHK(hipMemsetAsync(h->zbuf, 0, w * F * CPE_NX, h->stream));
+    HIPCHK(hipMemsetAsync(h->Lbuf, 0, w * F * LC, h->stream));
+    HIPCHK(hipMemcpyAsync(h->qbuf + F * ns, h->qbuf, w * F * ns, hipMemcpyDeviceToDevice, h->stream));
+    LmParams prm = lm_params(h, B, N);
+    prm.lambda0 = lam;                                     // the accept stage of the first pass sets S.lambda from it
+    const size_t ldsn = lds_normal(m, h->gmm_k, h->gmm_dim);
+    if (kopt) kin_iterate<false>(h, prm, N, F, ldsn, meas, weight, stance, RaggedArgs{}, 1, nullptr, nullptr, B);
+    else lm_iterate(h, prm, N, F, ldsn, meas, weight, ShutterArgs{nullptr, nullptr, nullptr}, nullptr, 1, nullptr, nullptr, B);
+    HIPCHK(hipGetLastError());
+    std::vector<SeqState> hs((size_t)B);
+    HIPCHK(hipMemcpyAsync(hs.data(), h->st, sizeof(SeqState) * B, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    // a step was made where the evaluation is finite (status 0) and the factor exists: a failed factorisation multiplies the damping by 10
+    std::vector<char> step((size_t)B);
+    for (int b = 0; b < B; b++) {
+        const SeqState& S = hs[b];
+        step[b] = S.status == 0 && S.lambda == lam;
+        double* o = seq + (size_t)b * 8;
+        for (int t = 0; t < 5; t++) o[t] = S.terms[t];
+        o[5] = S.pred; o[6] = S.maxstep; o[7] = step[b] ? CPE_OK : CPE_NUMERICAL;
+        if (!step[b] && S.status == 0) {                   // partly written before the factorisation failed
+            HIPCHK(hipMemsetAsync(h->gtbuf + (size_t)b * N * CPE_NX, 0, w * N * CPE_NX, h->stream));
+            HIPCHK(hipMemsetAsync(h->dgbuf + (size_t)b * N * CPE_NX, 0, w * N * CPE_NX, h->stream));
+            HIPCHK(hipMemsetAsync(h->zbuf + (size_t)b * N * CPE_NX, 0, w * N * CPE_NX, h->stream));
+            HIPCHK(hipMemsetAsync(h->Lbuf + (size_t)b * N * LC, 0, w * N * LC, h->stream));
+        }
+    }
+    if (g) HIPCHK(hipMemcpyAsync(g, h->gtbuf, w * F * CPE_NX, hipMemcpyDeviceToDevice, h->stream));
+    if (dg) HIPCHK(hipMemcpyAsync(dg, h->dgbuf, w * F * CPE_NX, hipMemcpyDeviceToDevice, h->stream));
+    if (delta) HIPCHK(hipMemcpyAsync(delta, h->zbuf, w * F * CPE_NX, hipMemcpyDeviceToDevice, h->stream));
+    if (state)
+        for (int b = 0; b < B; b++)
+            for (int t = 0; t < 2; t++) {                  // t = 0: the current buffer, 1: the trial
+                const int buf = t == 0 ? hs[b].cur : 1 - hs[b].cur;
+                HIPCHK(hipMemcpy2DAsync(state + ((size_t)b * N * 2 + t) * ns, w * 2 * ns, h->qbuf + ((size_t)buf * F + (size_t)b * N) * ns, w * ns, w * ns, N,
+                                        hipMemcpyDeviceToDevice, h->stream));
+            }
+    if (L) {
+        // Lbuf, column n: block 0 = L(n, n) with 1 / L[k][k] on its diagonal, block i = L(n + i, n), entries [row * 28 + col]; the plain form
+        // has the true diagonal (the reciprocal of the stored one)
+        std::vector<double> hl(F * LC);
+        HIPCHK(hipMemcpyAsync(hl.data(), h->Lbuf, w * F * LC, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        for (size_t f = 0; f < F; f++)
+            if (step[f / (size_t)N])
+                for (int k = 0; k < CPE_NX; k++) { double& d = hl[f * LC + (size_t)k * (CPE_NX + 1)]; d = 1.0 / d; }
+        HIPCHK(hipMemcpyAsync(L, hl.data(), w * F * LC, hipMemcpyHostToDevice, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));                // (hl is read by the copy above)
     return CPE_OK;
 }
 

@@ -487,6 +487,27 @@ cpe_status cpe_eval_kinetic_system(cpe_handle* h, const cpe_kinetic_options* opt
                                    const double* weight, const int32_t* stance, const double* grf_fixed, const double* tau_box, const double* grf_box,
                                    double* f, double* stat, double* g, double* Huu, double* Hfu, double* Hff, int32_t* meta, double* gk, double* Bk,
                                    double* Hk);
+/* Diagnostic building block of both solves, for tests: exactly the first LM iteration of cpe_solve (kopt NULL, stance NULL) or of
+ * cpe_solve_kinetic (kopt and stance given; free foot forces; the handle's half-bandwidth must be 3) from Euler q, at the damping lam > 0 in
+ * place of opts.lambda0 -- the same launches as the solve's first pass: evaluation, band assembly, block Cholesky factor, forward and back
+ * substitution, trial iterate.  In the physics-based model the node forces are eliminated at that damping too.  Outputs, device pointers
+ * except seq, each may be NULL except seq (pb = the half-bandwidth in frames: 3, or the motion prior's window when that is larger):
+ *   g [B][N][28]      total gradient of the objective in the reduced coordinates (per-frame terms, constant-acceleration model, motion prior,
+ *                     eliminated physics terms)
+ *   dg [B][N][28]     diagonal of the Gauss-Newton matrix H before damping; the damped matrix is H + lam diag(max(dg, floor)), floor 0.1
+ *                     for N < 4, else 1e-12
+ *   L [B][N][pb+1][28][28]  block [n][i] = block (n + i, n) of the lower Cholesky factor of the damped matrix, row-major, with its true
+ *                     diagonal; zero where n + i >= N
+ *   delta [B][N][28]  the step: (H + lam diag(...)) delta = -g
+ *   state [B][N][2][ns]  the current state (Euler q made consistent, then the leg angles) and the trial state = current + delta at the slot
+ *                     of every reduced coordinate
+ *   seq [B][8]        HOST: cost terms of the evaluation (meas, model, bound, pose, motion -- the physics-based model reports its own cost
+ *                     in the last), predicted decrease, max |delta|, status: CPE_OK where a step was made, CPE_NUMERICAL where the
+ *                     evaluation is not finite or the damped matrix has no Cholesky factor -- that sequence has g, dg, L and delta zero
+ *                     and its trial state is not defined. */
+cpe_status cpe_eval_lm_step(cpe_handle* h, const cpe_kinetic_options* kopt, int32_t B, int32_t N, const double* q, const double* meas,
+                            const double* weight, const int32_t* stance, double lam, double* g, double* dg, double* L, double* delta, double* state,
+                            double* seq);
 
 /* forward kinematics only (get_pose_state / get_com, acinoset_misc.py:1581-1659, :722-742); device ptrs */
 cpe_status cpe_forward_kinematics(cpe_handle* h, int32_t B, int32_t N, const double* q,
