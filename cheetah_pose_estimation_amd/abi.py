@@ -9,7 +9,7 @@ MAX_BOUNDS = 32
 MAX_NQ = 3 + 3 * MAX_LINKS
 MAX_GMM = 8
 NX = 28
-MAX_WINDOW = 4
+MAX_WINDOW = 6
 
 OK, MAX_ITER, NUMERICAL, BAD_ARG, NO_DEVICE, HIP_ERROR = 0, 1, 2, -1, -2, -3
 JOINT_REVOLUTE_Y, JOINT_HOOKE_YZ = 0, 1

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 #include <algorithm>
+#include <type_traits>
 
 #include "cpe_kernels.hip"
 
@@ -64,7 +65,7 @@ struct cpe_handle {
     double *fbuf = nullptr, *kmu = nullptr, *Jbuf = nullptr, *Abuf = nullptr, *pieces = nullptr, *gTb = nullptr, *dstat = nullptr, *slackb = nullptr,
            *Tbuf = nullptr, *gk = nullptr, *Bk = nullptr, *Hk = nullptr;
     int* pmeta = nullptr;
-    int pb = 3;                  // half-bandwidth of the normal equations in frames (4 with a window-4 motion prior)
+    int pb = 3;                  // half-bandwidth of the normal equations in frames (W with a window-W motion prior, W = 4..6)
 };
 
 struct DevBuf {
@@ -565,7 +566,8 @@ static cpe_status check_priors(const cpe_priors* priors, bool* use_pri) {
     if (*use_pri) {
         if (priors->gmm_k < 0 || priors->gmm_k > CPE_MAX_GMM || priors->gmm_dim < 0 || priors->gmm_dim > CPE_NX || (priors->gmm_k > 0 && priors->gmm_dim < 1))
             return fail(CPE_BAD_ARG, "pose prior: component count / dimension out of range");
-        if (priors->lr_window < 0 || priors->lr_window > CPE_MAX_WINDOW) return fail(CPE_BAD_ARG, "motion prior: window out of range");
+        if (priors->lr_window < 0 || priors->lr_window > CPE_MAX_WINDOW)
+            return fail(CPE_BAD_ARG, "motion prior: window " + std::to_string(priors->lr_window) + " out of range (0 = off, 1.." + std::to_string(CPE_MAX_WINDOW) + ")");
     }
     return CPE_OK;
 }
@@ -930,7 +932,7 @@ static cpe_status ensure_ws(cpe_handle* h, int B, int N) {
     HIPCHK(ws_alloc(w, h->Bbuf, 2 * F * nu * nu));
     HIPCHK(ws_alloc(w, h->costbuf, 2 * F * COST_STRIDE));
     HIPCHK(ws_alloc(w, h->mu, n_mu(h->hm, F)));
-    HIPCHK(ws_alloc(w, h->Lbuf, F * (h->pb + 1) * nu * nu));
+    HIPCHK(ws_alloc(w, h->Lbuf, F * (h->pb + 1) * nu * nu + (size_t)B * lm_spill_doubles(h->pb)));     // + k_lm_step's window blocks past LDS
     HIPCHK(ws_alloc(w, h->zbuf, F * nu));
     HIPCHK(ws_alloc(w, h->gtbuf, F * nu));
     HIPCHK(ws_alloc(w, h->dgbuf, F * nu));
@@ -995,7 +997,7 @@ using LmIterate = std::function<void(int first, const int* act, const int* n_act
 static cpe_status lm_drive(cpe_handle* h, int B, const LmIterate& iterate) {
     iterate(1, nullptr, nullptr, B);        // first evaluation and first step of every sequence
     HIPCHK(hipGetLastError());
-    const int window = std::min(B, h->n_cu * (h->pb == 3 ? 2 : 1));
+    const int window = std::min(B, h->n_cu * (h->pb == 3 ? 2 : 1));          // k_lm_step: 2 workgroups per CU at PB = 3, 1 at PB = 4..6
     constexpr int POLL = 4;
     const long per_seq = (long)h->opts.max_iter + 2L * (h->opts.max_outer > 0 ? h->opts.max_outer : 0) + POLL;
     const long max_rounds = ((long)(B + window - 1) / window + 1) * per_seq;
@@ -1029,6 +1031,17 @@ __global__ void k_reset_status(SeqState* __restrict__ st, int B) {
     if (b < B) { st[b].status = 0; st[b].al_pending = 0; }
 }
 
+// f(std::integral_constant<int, PB>{}) for the handle's half-bandwidth PB = 3..6: k_lm_step and k_lm_back are instantiated per PB
+extern "C++" template <class Fn>
+static void with_pb(int pb, Fn&& f) {
+    switch (pb) {
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    default: f(std::integral_constant<int, 6>{}); break;
+    }
+}
+
 // One iteration of the kinematic solve (the LmIterate of lm_run): k_frame_normal (+ k_lr_band) on the evaluated buffer, then k_lm_step and
 // k_lm_back.  sh: shutter-delay buffers (all null = off); rg: the ragged table (N = nmax), or null.
 static void lm_iterate(cpe_handle* h, const LmParams& prm, int N, size_t Fw, size_t ldsn, const double* meas, const double* weight, ShutterArgs sh,
@@ -1048,16 +1061,16 @@ static void lm_iterate(cpe_handle* h, const LmParams& prm, int N, size_t Fw, siz
             prof_end(h);
         }
         prof_begin(h, 2);
-        if (h->pb == 3) hipLaunchKernelGGL((k_lm_step<3, 0, true>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gbuf,
-                                           h->Bbuf, h->costbuf, h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hlr, act, n_act, 2, nullptr, h->dgbuf, hiu, h->lr_window, *rg);
-        else hipLaunchKernelGGL((k_lm_step<4, 0, true>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gbuf,
-                                h->Bbuf, h->costbuf, h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hlr, act, n_act, 2, nullptr, h->dgbuf, hiu, h->lr_window, *rg);
+        with_pb(h->pb, [&](auto pbc) {
+            hipLaunchKernelGGL((k_lm_step<decltype(pbc)::value, 0, true>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf,
+                               h->gbuf, h->Bbuf, h->costbuf, h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hlr, act, n_act, 2, nullptr, h->dgbuf, hiu, h->lr_window, *rg);
+        });
         prof_end(h);
         prof_begin(h, 7);
-        if (h->pb == 3) hipLaunchKernelGGL((k_lm_back<3, true>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf,
-                                           h->gtbuf, h->dgbuf, act, n_act, *rg);
-        else hipLaunchKernelGGL((k_lm_back<4, true>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf,
-                                h->gtbuf, h->dgbuf, act, n_act, *rg);
+        with_pb(h->pb, [&](auto pbc) {
+            hipLaunchKernelGGL((k_lm_back<decltype(pbc)::value, true>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf,
+                               h->zbuf, h->gtbuf, h->dgbuf, act, n_act, *rg);
+        });
         prof_end(h);
         return;
     }
@@ -1072,14 +1085,16 @@ static void lm_iterate(cpe_handle* h, const LmParams& prm, int N, size_t Fw, siz
         prof_end(h);
     }
     prof_begin(h, 2);
-    if (h->pb == 3) hipLaunchKernelGGL((k_lm_step<3, 0>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gbuf, h->Bbuf, h->costbuf,
-                                       h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hlr, act, n_act, 2, sh.gx, h->dgbuf, hiu, h->lr_window);
-    else hipLaunchKernelGGL((k_lm_step<4, 0>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gbuf, h->Bbuf, h->costbuf,
-                            h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hlr, act, n_act, 2, sh.gx, h->dgbuf, hiu, h->lr_window);
+    with_pb(h->pb, [&](auto pbc) {
+        hipLaunchKernelGGL((k_lm_step<decltype(pbc)::value, 0>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gbuf,
+                           h->Bbuf, h->costbuf, h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hlr, act, n_act, 2, sh.gx, h->dgbuf, hiu, h->lr_window);
+    });
     prof_end(h);
     prof_begin(h, 7);
-    if (h->pb == 3) hipLaunchKernelGGL((k_lm_back<3>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf, h->gtbuf, h->dgbuf, act, n_act);
-    else hipLaunchKernelGGL((k_lm_back<4>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf, h->gtbuf, h->dgbuf, act, n_act);
+    with_pb(h->pb, [&](auto pbc) {
+        hipLaunchKernelGGL((k_lm_back<decltype(pbc)::value>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf,
+                           h->gtbuf, h->dgbuf, act, n_act);
+    });
     prof_end(h);
 }
 

@@ -947,18 +947,33 @@ __device__ __forceinline__ void mfma_frag_cols(const double* blk, int col0, int 
     for (int s = 0; s < 7; s++) f[s] = p[4 * s * LDB];
 }
 
+// Window blocks of k_lm_step resident in LDS: the whole window up to PB = 5 (21 blocks, 136 KB).  From PB = 6 on the slots past these
+// live in global memory (a per-sequence area behind the factor columns in Lbuf, L2-resident): win_blk maps a slot to its place.
+#define LM_LDS_BLOCKS 21
+// doubles of global memory per sequence for the window blocks of k_lm_step<PB> past LM_LDS_BLOCKS, with room for the tiles' over-read (the
+// fragment of rows 16..31 of a block reads up to 115 doubles past its end; those rows only reach results that are never stored)
+__host__ __device__ constexpr size_t lm_spill_doubles(int pb) {
+    return (pb + 1) * (pb + 2) / 2 <= LM_LDS_BLOCKS ? 0 : (size_t)((pb + 1) * (pb + 2) / 2 - LM_LDS_BLOCKS) * BLK + 4 * LDB;
+}
+template <int RING>
+__device__ __forceinline__ double* win_blk(double* W, double* Wg, int slot) {
+    constexpr int NLDS = RING * (RING + 1) / 2 < LM_LDS_BLOCKS ? RING * (RING + 1) / 2 : LM_LDS_BLOCKS;
+    if constexpr (RING * (RING + 1) / 2 <= LM_LDS_BLOCKS) { (void)Wg; return W + slot * BLK; }
+    else return slot < NLDS ? W + slot * BLK : Wg + (slot - NLDS) * BLK;
+}
+
 // LDS slot of block (row frame r, col frame c) -- defined above (blk_slot).  CNT tiles (idx = g0 .. g0+CNT-1: block j = 1 + idx / 2, column
 // half idx & 1) of the trailing update of half panel (i, tr): A_ij -= X_i X_j^T with CNT independent accumulators in flight (a dependent
 // fp64 MFMA waits ~116 cycles, an independent one issues every ~64)
 template <int RING, int CNT>
-__device__ __forceinline__ void p2_tiles(double* W, int n, int i, int tr, int g0, const double (&xa)[7], int lane) {
+__device__ __forceinline__ void p2_tiles(double* W, int n, int i, int tr, int g0, const double (&xa)[7], int lane, double* Wg = nullptr) {
     constexpr int SPLIT = CNT <= 2 ? 2 : 1;            // one or two tiles: the 7 k-steps of a tile go to two accumulators (even / odd), four chains in flight
     double xb[CNT][7];
     d4_t acc[CNT][SPLIT];
 #pragma unroll
     for (int q = 0; q < CNT; q++) {
         const int idx = g0 + q;
-        mfma_frag_rows(W + blk_slot<RING>(n + 1 + idx / 2, n) * BLK, 16 * (idx & 1), lane, xb[q]);
+        mfma_frag_rows(win_blk<RING>(W, Wg, blk_slot<RING>(n + 1 + idx / 2, n)), 16 * (idx & 1), lane, xb[q]);
 #pragma unroll
         for (int h = 0; h < SPLIT; h++) acc[q][h] = d4_t{0.0, 0.0, 0.0, 0.0};
     }
@@ -969,7 +984,7 @@ __device__ __forceinline__ void p2_tiles(double* W, int n, int i, int tr, int g0
 #pragma unroll
     for (int q = 0; q < CNT; q++) {
         const int idx = g0 + q, j = 1 + idx / 2, col = 16 * (idx & 1) + (lane & 15);
-        double* Cd = W + blk_slot<RING>(n + i, n + j) * BLK;
+        double* Cd = win_blk<RING>(W, Wg, blk_slot<RING>(n + i, n + j));
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             const int row = 16 * tr + (lane >> 4) + 4 * r;
@@ -983,7 +998,8 @@ __device__ __forceinline__ void p2_tiles(double* W, int n, int i, int tr, int g0
 // One LM step per sequence: (1) accept / reject the pending trial, (2) assemble H = blockdiag(B_n) +
 // motion band + lambda diag(H), factor it with a sliding-window block Cholesky in LDS, (3) solve,
 // (4) write the next trial iterate.  One 256-thread workgroup per sequence.  PB = half-bandwidth in frames: 3 for the
-// constant-acceleration model (2 workgroups per CU), 4 when the window-4 autoregressive prior is on (1 per CU).
+// constant-acceleration model (2 workgroups per CU), W = 4..6 when the window-W autoregressive prior is on (1 per CU).  The window's
+// (PB+1)(PB+2)/2 blocks sit in LDS up to PB = 5; from PB = 6 on the slots past LM_LDS_BLOCKS are in global memory (win_blk).
 // MODE 0: the whole step.  The physics-based model puts kernels between the two halves (the elimination of the node forces needs the
 // damping the accept step has just set): MODE 1 = accept / reject only, MODE 2 = assemble, factor, solve, trial only.
 // hb = number of buffers of gbuf / Bbuf / Hlr: 2 (indexed by the current buffer) or 1 (already those of the current iterate).
@@ -1004,7 +1020,9 @@ __global__ __launch_bounds__(LM_THREADS, PB == 3 ? 2 : 1) void k_lm_step(const D
     constexpr int RING = PB + 1;                       // frames in the sliding window
     constexpr int NBLK = RING * (RING + 1) / 2;        // lower-triangle blocks of the window
     constexpr int NRH = 2 * PB;                        // half panels (16 rows) below the diagonal block: (i, tr), i = 1..PB, index 2 (i - 1) + tr
-    __shared__ double W[NBLK * BLK];
+    constexpr int NLDS = NBLK < LM_LDS_BLOCKS ? NBLK : LM_LDS_BLOCKS, NSPILL = NBLK - NLDS;     // window blocks in LDS / in global memory
+    static_assert(PB >= 3 && PB <= 6, "the tile deal of P2 below is written for PB = 3..6");
+    __shared__ double W[NLDS * BLK];
     __shared__ __attribute__((aligned(16))) double colbuf[NU * 4];     // the four columns of a pivot group, rows in order (factor sweep, wave 0 only)
     __shared__ double dummy_row[NU + 4];     // sink for idle lanes of the factor sweep
     __shared__ double Tm[BLK + 4 * LDB];     // L00^-T of the current diagonal block (upper triangular), padded for the tiles' rows 28..31
@@ -1128,6 +1146,8 @@ __global__ __launch_bounds__(LM_THREADS, PB == 3 ? 2 : 1) void k_lm_step(const D
     const double* gc = gbuf + (hcur + (size_t)b * NS) * NU;
     const double* Bc = Bbuf + (hcur + (size_t)b * NS) * (NU * NU);
     double* Lb = Lbuf + (size_t)b * NS * RING * (NU * NU);
+    double* Wg = nullptr;                                    // the window blocks past NLDS: this sequence's area behind the factor columns
+    if constexpr (NSPILL > 0) Wg = Lbuf + n_frames * RING * (NU * NU) + (size_t)b * lm_spill_doubles(PB);
     double* zb = zbuf + (size_t)b * NS * NU;
     double* gtb = gtbuf + (size_t)b * NS * NU;
     double* dgb = dgbuf + (size_t)b * NS * NU;
@@ -1171,10 +1191,15 @@ __global__ __launch_bounds__(LM_THREADS, PB == 3 ? 2 : 1) void k_lm_step(const D
     int hcnt = 0, ht = 0;
 
     // Synchronisation of the look-ahead (LDS counters, polled): wave 0 and the update waves meet through s_cnt, never at s_barrier
-    auto lds_release = [&]() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local"); };
+    // (with window blocks in global memory the fences order those too)
+    auto lds_release = [&]() {
+        if constexpr (NSPILL > 0) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        else __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    };
     auto wait_ge = [&](int idx, int target) {
         while (__atomic_load_n(&s_cnt[idx], __ATOMIC_RELAXED) < target) __builtin_amdgcn_s_sleep(1);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+        if constexpr (NSPILL > 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        else __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
     };
     int sync_epoch = 0;
     auto sync3 = [&]() {                                  // barrier of the three update waves
@@ -1338,6 +1363,10 @@ __global__ __launch_bounds__(LM_THREADS, PB == 3 ? 2 : 1) void k_lm_step(const D
         // the prior's blocks of row m: away from the sequence ends (k_lr_band's `interior`, for every k) they are constants of the model, read from the
         // 25 KB table that stays in L2 instead of 25 KB of HBM per frame; k_lr_band writes Hlr for the other rows only
         const double* Hrow = prior ? ((HIu && m >= lrW && m <= N - lrW) ? HIu : Hlc + (size_t)m * PB * (NU * NU)) : nullptr;
+        auto wput = [&](int bo, int off, double v) {                // an off-diagonal block of the row (the diagonal one is always in LDS)
+            if constexpr (NSPILL == 0) W[bo + off] = v;
+            else { if (bo < NLDS * BLK) W[bo + off] = v; else Wg[bo - NLDS * BLK + off] = v; }
+        };
         auto put = [&](int t, int where, double bval, const double (&acc)[4]) {
             const int off = where & 1023;
             double v = bval + Tk[0] * acc[0];
@@ -1346,11 +1375,11 @@ __global__ __launch_bounds__(LM_THREADS, PB == 3 ? 2 : 1) void k_lm_step(const D
             if (prior) {
 #pragma unroll
                 for (int k = 1; k <= PB; k++)
-                    if (m - k >= 0) W[base[k] + off] = Hrow[(k - 1) * (NU * NU) + t] + (k <= 3 ? Tk[k] * acc[k] : 0.0);
+                    if (m - k >= 0) wput(base[k], off, Hrow[(k - 1) * (NU * NU) + t] + (k <= 3 ? Tk[k] * acc[k] : 0.0));
             } else {
 #pragma unroll
                 for (int k = 1; k <= PB; k++)
-                    if (m - k >= 0) W[base[k] + off] = k <= 3 ? Tk[k] * acc[k] : 0.0;
+                    if (m - k >= 0) wput(base[k], off, k <= 3 ? Tk[k] * acc[k] : 0.0);
             }
         };
 #pragma unroll
@@ -1463,7 +1492,7 @@ __global__ __launch_bounds__(LM_THREADS, PB == 3 ? 2 : 1) void k_lm_step(const D
                 // rows0 in the prologue, three per column, the first after P1).  The update waves keep their hands off block 1's tiles.
                 wait_ge(3, 3 * (rows0 + 3 * (n - 1) + 1));
                 STAMP(3);
-                const double* X1 = W + blk_slot<RING>(n, n - 1) * BLK;
+                const double* X1 = win_blk<RING>(W, Wg, blk_slot<RING>(n, n - 1));
                 if (lane < NU) {
                     const double* Li = X1 + lane * LDB;
                     const double* z = rw + ((n - 1) % RING) * NU;
@@ -1474,9 +1503,9 @@ __global__ __launch_bounds__(LM_THREADS, PB == 3 ? 2 : 1) void k_lm_step(const D
                 }
                 double xa[7];
                 mfma_frag_rows(X1, 0, lane, xa);
-                p2_tiles<RING, 1>(W, n - 1, 1, 0, 0, xa, lane);
+                p2_tiles<RING, 1>(W, n - 1, 1, 0, 0, xa, lane, Wg);
                 mfma_frag_rows(X1, 16, lane, xa);
-                p2_tiles<RING, 2>(W, n - 1, 1, 1, 0, xa, lane);
+                p2_tiles<RING, 2>(W, n - 1, 1, 1, 0, xa, lane, Wg);
                 lds_release();
                 if (lane == 0) __atomic_store_n(&s_cnt[2], n, __ATOMIC_RELAXED);     // X_1 of column n-1 is no longer read here: its slot may take the entering row
             }
@@ -1520,7 +1549,7 @@ __global__ __launch_bounds__(LM_THREADS, PB == 3 ? 2 : 1) void k_lm_step(const D
 #pragma unroll
             for (int q = 0; q < QN; q++) {
                 const int rh = rh_lo + (q < rh_n ? q : 0);
-                mfma_frag_rows(W + blk_slot<RING>(n + 1 + rh / 2, n) * BLK, 16 * (rh & 1), lane, fa[q]);
+                mfma_frag_rows(win_blk<RING>(W, Wg, blk_slot<RING>(n + 1 + rh / 2, n)), 16 * (rh & 1), lane, fa[q]);
             }
             wait_ge(0, n + 1);
             USTAMP(10);
@@ -1551,7 +1580,7 @@ __global__ __launch_bounds__(LM_THREADS, PB == 3 ? 2 : 1) void k_lm_step(const D
                 for (int q = 0; q < QN; q++) {
                     if (q < rh_n) {
                         const int rh = rh_lo + q, i = 1 + rh / 2;
-                        double* Xi = W + blk_slot<RING>(n + i, n) * BLK;
+                        double* Xi = win_blk<RING>(W, Wg, blk_slot<RING>(n + i, n));
 #pragma unroll
                         for (int tc = 0; tc < 2; tc++) {
                             const int col = 16 * tc + (lane & 15);
@@ -1595,23 +1624,34 @@ __global__ __launch_bounds__(LM_THREADS, PB == 3 ? 2 : 1) void k_lm_step(const D
             // ---- P2: rhs_i -= X_i z, A_ij -= X_i X_j^T for the blocks below the first (block 1's rows are wave 0's)
             if (ut >= NU && ut < nrows) {
                 const int i = 1 + ut / NU, a = ut - (i - 1) * NU;
-                const double* Li = W + blk_slot<RING>(n + i, n) * BLK + a * LDB;
+                const double* Li = win_blk<RING>(W, Wg, blk_slot<RING>(n + i, n)) + a * LDB;
                 const double* z = rw + (n % RING) * NU;
                 double acc0 = 0.0, acc1 = 0.0;
 #pragma unroll
                 for (int k = 0; k < NU; k += 2) { acc0 = fma(Li[k], z[k], acc0); acc1 = fma(Li[k + 1], z[k + 1], acc1); }
                 rw[((n + i) % RING) * NU + a] -= acc0 + acc1;
             }
-            // tiles of this wave: (half panel, first tile, tiles).  PB = 3 (18 tiles, 6 a wave): {rh5: 6}, {rh4: 5, rh2: tile 0}, {rh3: 4, rh2: tiles 1-2};
-            // PB = 4 (33 tiles): {rh7: 8, rh2: 3}, {rh6: 7, rh3: 4}, {rh5: 6, rh4: 5}
-            constexpr int NMINE = 2;
+            // tiles of this wave: (half panel, first tile, tiles); half panel rh has rh + 1 tiles.  PB = 3 (18 tiles, 6 a wave): {rh5: 6},
+            // {rh4: 5, rh2: tile 0}, {rh3: 4, rh2: tiles 1-2}; PB = 4 (33 tiles): {rh7: 8, rh2: 3}, {rh6: 7, rh3: 4}, {rh5: 6, rh4: 5};
+            // PB = 5 (52): {rh9: 10, rh5: 6, rh2: tile 0}, {rh8: 9, rh6: 7, rh2: tiles 1-2}, {rh7: 8, rh4: 5, rh3: 4};
+            // PB = 6 (75, 25 a wave): {rh11: 12, rh8: 9, rh3: 4}, {rh10: 11, rh7: 8, rh5: 6}, {rh9: 10, rh6: 7, rh4: 5, rh2: 3}
+            constexpr int NMINE = PB <= 4 ? 2 : PB - 2;
             int m_rh[NMINE], m_lo[NMINE], m_n[NMINE];
-            if (PB == 3) {
+            if constexpr (PB == 3) {
                 m_rh[0] = 5 - uw; m_lo[0] = 0; m_n[0] = 6 - uw;
                 m_rh[1] = uw == 0 ? -1 : 2; m_lo[1] = uw == 1 ? 0 : 1; m_n[1] = uw == 1 ? 1 : 2;
-            } else {
+            } else if constexpr (PB == 4) {
                 m_rh[0] = 7 - uw; m_lo[0] = 0; m_n[0] = 8 - uw;
                 m_rh[1] = 2 + uw; m_lo[1] = 0; m_n[1] = 3 + uw;
+            } else if constexpr (PB == 5) {
+                m_rh[0] = 9 - uw; m_lo[0] = 0; m_n[0] = 10 - uw;
+                m_rh[1] = uw == 0 ? 5 : (uw == 1 ? 6 : 4); m_lo[1] = 0; m_n[1] = m_rh[1] + 1;
+                m_rh[2] = uw == 2 ? 3 : 2; m_lo[2] = uw == 1 ? 1 : 0; m_n[2] = uw == 0 ? 1 : (uw == 1 ? 2 : 4);
+            } else {
+                m_rh[0] = 11 - uw; m_lo[0] = 0; m_n[0] = 12 - uw;
+                m_rh[1] = 8 - uw; m_lo[1] = 0; m_n[1] = 9 - uw;
+                m_rh[2] = uw == 0 ? 3 : (uw == 1 ? 5 : 4); m_lo[2] = 0; m_n[2] = m_rh[2] + 1;
+                m_rh[3] = uw == 2 ? 2 : -1; m_lo[3] = 0; m_n[3] = 3;
             }
 #pragma unroll
             for (int pass = 0; pass < NMINE; pass++) {                   // (unrolled: the three small tables stay in registers)
@@ -1620,14 +1660,14 @@ __global__ __launch_bounds__(LM_THREADS, PB == 3 ? 2 : 1) void k_lm_step(const D
                 const int i = 1 + rh / 2, tr = rh & 1;
                 if (i > nb_i) continue;                                  // uniform per wave
                 double xa[7];
-                mfma_frag_rows(W + blk_slot<RING>(n + i, n) * BLK, 16 * tr, lane, xa);
+                mfma_frag_rows(win_blk<RING>(W, Wg, blk_slot<RING>(n + i, n)), 16 * tr, lane, xa);
                 const int gend = m_lo[pass] + m_n[pass];                 // tiles (j, tc) of a half panel: j < i both column halves, j = i up to the diagonal tile
                 for (int g = m_lo[pass]; g < gend;) {
                     const int left = gend - g, cnt = left >= 7 ? 4 : (left >= 5 ? 3 : left);    // 5 = 3 + 2, 6 = 3 + 3, 7 = 4 + 3, 8 = 4 + 4
-                    if (cnt == 4) p2_tiles<RING, 4>(W, n, i, tr, g, xa, lane);
-                    else if (cnt == 3) p2_tiles<RING, 3>(W, n, i, tr, g, xa, lane);
-                    else if (cnt == 2) p2_tiles<RING, 2>(W, n, i, tr, g, xa, lane);
-                    else p2_tiles<RING, 1>(W, n, i, tr, g, xa, lane);
+                    if (cnt == 4) p2_tiles<RING, 4>(W, n, i, tr, g, xa, lane, Wg);
+                    else if (cnt == 3) p2_tiles<RING, 3>(W, n, i, tr, g, xa, lane, Wg);
+                    else if (cnt == 2) p2_tiles<RING, 2>(W, n, i, tr, g, xa, lane, Wg);
+                    else p2_tiles<RING, 1>(W, n, i, tr, g, xa, lane, Wg);
                     g += cnt;
                 }
             }
@@ -1667,6 +1707,8 @@ __global__ __launch_bounds__(LM_THREADS, PB == 3 ? 2 : 1) void k_lm_step(const D
 // sequence.  Wave 1 only moves factor columns from HBM into a three-column LDS ring with LDS-DMA loads (global_load_lds_dwordx4: no
 // registers, nothing to wait for but its own vmcnt), two columns ahead of wave 0, which owns the arithmetic: lane k < 28 holds component
 // k of delta_n; delta_{n+1..n+PB} sit in a small LDS ring and are read back as broadcasts.  One LDS barrier per column joins the two.
+// From PB = 5 on a column is more than 31 1-KB pieces and two columns in flight would overrun vmcnt: the loader then waits for column
+// n-1 before it issues column n-2 (still two columns ahead of wave 0, one in flight).
 #define BACK_SLOTS 3
 template <int PB, bool RAGGED = false>
 __global__ __launch_bounds__(2 * WAVE) void k_lm_back(const DevModel* __restrict__ M, SeqState* __restrict__ st, LmParams prm, double* __restrict__ qbuf,
@@ -1676,7 +1718,8 @@ __global__ __launch_bounds__(2 * WAVE) void k_lm_back(const DevModel* __restrict
     if (n_act && (int)blockIdx.x >= *n_act) return;
     constexpr int RING = PB + 1, COLD = RING * NU * NU;
     constexpr int COLB = COLD * 8, NCH = (COLB + 1023) / 1024;       // bytes per factor column, 1 KB LDS-DMA pieces per column
-    static_assert(NU % 4 == 0 && COLB % 16 == 0 && NCH < 32, "four accumulation chains; 16-byte pieces; two columns in flight fit vmcnt");
+    constexpr bool TWO = NCH < 32;                                    // two columns in flight fit vmcnt (6 bits)
+    static_assert(NU % 4 == 0 && COLB % 16 == 0 && NCH < 64, "four accumulation chains; 16-byte pieces; a column in flight fits vmcnt");
     __shared__ __attribute__((aligned(16))) double ring[BACK_SLOTS * COLD];
     __shared__ __attribute__((aligned(16))) double dsh[PB * NU];
     __shared__ double far_part[2 * NU];                       // [n & 1]: sum over blocks 2..PB of column n, left by wave 1 one step ahead
@@ -1707,14 +1750,18 @@ __global__ __launch_bounds__(2 * WAVE) void k_lm_back(const DevModel* __restrict
         unsigned long long tb_last = __builtin_amdgcn_s_memtime();
 #endif
         issue(N - 1);
-        if (N > 1) issue(N - 2);
+        if (TWO && N > 1) issue(N - 2);
         // (raw barriers in this wave: a fenced one would wait for EVERY LDS-DMA load in flight, vmcnt(0), and the ring would never run ahead)
-        if (N > 1) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NCH) : "memory"); else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        if (TWO && N > 1) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(TWO ? NCH : 0) : "memory"); else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                         // column N-1 has landed (and this wave's share of the zeroing above)
         asm volatile("" ::: "memory");
+        if (!TWO && N > 1) issue(N - 2);
         for (int n = N - 1; n >= 0; n--) {
             // wave 0 works on column n; column n+1's slot is free (the barrier that ended its step is behind us): column n-2 goes there
-            if (n >= 2) { issue(n - 2); BSTAMP(9); asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NCH) : "memory"); }     // all but the newest column: n-1 has landed
+            if constexpr (!TWO) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                     // column n-1 has landed
+                if (n >= 2) { issue(n - 2); BSTAMP(9); }
+            } else if (n >= 2) { issue(n - 2); BSTAMP(9); asm volatile("s_waitcnt vmcnt(%0)" ::"n"(TWO ? NCH : 0) : "memory"); }     // all but the newest column: n-1 has landed
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             BSTAMP(14);
             // the blocks 2..PB of column n-1 meet delta_{n+1..n+PB-1}, which are known already: their part of t is summed here, off

@@ -546,7 +546,7 @@ def _kin_prepare(est: CheetahEstimator, monocular_constraints: bool, disable_pos
     if monocular_constraints and scene.cam_idx is not None and not (disable_pose_prior and disable_motion_prior):
         # acinoset_opt.py:593-600.  The fitted numbers of the defaults ship as package data (tools/fit_priors.py re-runs the reference's recipe:
         # 5-component GMM, window-4 multi-task lasso); another size -- the grid search of run_dataset.py:814-915 -- is fitted here as the reference
-        # does at run time (priors.fit_priors: up to 8 components, windows up to 4 frames) and cached.
+        # does at run time (priors.fit_priors: up to 8 components, windows up to 6 frames) and cached.
         from . import priors as _priors
         default = (disable_pose_prior or pose_model_num_components == 5) and \
             (disable_motion_prior or (motion_model_window_size == 4 and motion_model_sparse_solution))

@@ -3,8 +3,8 @@
 (acinoset_misc.py:291-336, acinoset_models.py:173-274).  The fitted numbers are package data
 (data/priors_full_pose.npz, produced by tools/fit_priors.py with the reference's own recipe); this module only
 packs them into the C-ABI struct `cpe_priors`.  Other sizes of the two models -- the reference's grid search varies the number of mixture
-components and the window (run_dataset.py:814-915) -- are fitted on request with the same recipe (`fit_priors`), from the pose table the reference
-ships beside its models, and cached as plain arrays."""
+components and the window (run_dataset.py:814-915) -- are fitted on request with the same recipe (`fit_priors`: up to 8 components, windows of 1
+to 6 frames; the sweep's window 7 is refused), from the pose table the reference ships beside its models, and cached as plain arrays."""
 import os
 
 import numpy as np
@@ -71,7 +71,7 @@ def fit_priors(n_components: int = 5, window: int = 4, sparse: bool = True, data
     if not (1 <= n_components <= abi.MAX_GMM):
         raise NotImplementedError(f"pose prior with {n_components} components: cpe_priors holds at most {abi.MAX_GMM}")
     if not (1 <= window <= abi.MAX_WINDOW):
-        raise NotImplementedError(f"motion prior with a window of {window} frames: the band of the solver's normal equations covers at most {abi.MAX_WINDOW}")
+        raise NotImplementedError(f"motion prior with a window of {window} frames: cpe_priors and the solver's band hold windows of 1 to {abi.MAX_WINDOW} frames")
     cache_dir = cache_dir or os.environ.get("CPE_CACHE_DIR") or os.path.join(os.path.expanduser("~"), ".cache", "cheetah_pose_estimation_amd")
     out = os.path.join(cache_dir, f"priors_k{n_components}_w{window}_{'lasso' if sparse else 'dense'}.npz")
     if os.path.isfile(out):

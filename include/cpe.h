@@ -35,7 +35,7 @@ extern "C" {
 #define CPE_MAX_NQ (3 + 3 * CPE_MAX_LINKS)
 #define CPE_MAX_GMM 8        /* mixture components of the pose prior */
 #define CPE_NX 28            /* size of the reduced / relative-angle vector x (acinoset_misc.py:1699-1757) */
-#define CPE_MAX_WINDOW 4     /* window of the linear motion prior (acinoset_opt.py:545) */
+#define CPE_MAX_WINDOW 6     /* window of the linear motion prior (acinoset_opt.py:545): 1..6 (the grid search of run_dataset.py:814-915 also asks for 7) */
 
 typedef int32_t cpe_status;
 #define CPE_OK 0              /* converged                                             */
