@@ -99,6 +99,14 @@ def load():
     lib.cpe_eval_kinetic_nodes.argtypes = [vp, C.POINTER(abi.KineticOptions), C.c_int32, C.c_int32] + [vp] * 11
     lib.cpe_eval_kinetic_system.argtypes = [vp, C.POINTER(abi.KineticOptions), C.c_int32, C.c_int32] + [vp] * 17
     lib.cpe_eval_lm_step.argtypes = [vp, C.POINTER(abi.KineticOptions), C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_double] + [vp] * 6
+    lib.cpe_default_track_weights.argtypes = [vp]
+    lib.cpe_default_track_weights.restype = None
+    ko_p = C.POINTER(abi.KineticOptions)
+    lib.cpe_solve_kinetic_tracked.argtypes = [vp, ko_p, vp, C.c_int32, C.c_int32] + [vp] * 17 + [C.POINTER(abi.Stats), C.POINTER(abi.KineticStats)]
+    lib.cpe_solve_kinetic_tracked_host.argtypes = lib.cpe_solve_kinetic_tracked.argtypes
+    lib.cpe_solve_kinetic_tracked_ragged.argtypes = [vp, ko_p, vp, C.c_int32, C.c_int32, ip, ip] + [vp] * 17 + [C.POINTER(abi.Stats), C.POINTER(abi.KineticStats)]
+    lib.cpe_solve_kinetic_tracked_ragged_host.argtypes = lib.cpe_solve_kinetic_tracked_ragged.argtypes
+    lib.cpe_eval_normal_tracked.argtypes = [vp, vp, C.c_int32, C.c_int32] + [vp] * 7
     _LIB = lib
     return lib
 
@@ -167,6 +175,38 @@ def pad_kinetic(q_init_list, meas_list, weight_list, stance_list, force_list=Non
     if force_list is not None:
         out["force"] = _pad([np.asarray(f, np.float64) for f in force_list], nmax, np.shape(force_list[0])[1:])
     return out
+
+
+def pad_kinetic_tracked(q_init_list, q_target_list, stance_list, meas_list=None, weight_list=None, force_list=None,
+                        n_cams_max: Optional[int] = None) -> dict:
+    """pad_kinetic for cpe_solve_kinetic_tracked_ragged_host: q_target [N_b, nq] is padded as q_init is; meas / weight may be None together (then
+    the result's meas and weight are None).  Pure numpy."""
+    if (meas_list is None) != (weight_list is None):
+        raise ValueError("pad_kinetic_tracked: meas and weight are given together or not at all")
+    lens = [int(np.shape(q)[0]) for q in q_init_list]
+    if [int(np.shape(t)[0]) for t in q_target_list] != lens:
+        raise ValueError("pad_kinetic_tracked: every q_target has its q_init's frames")
+    if meas_list is not None:
+        out = pad_kinetic(q_init_list, meas_list, weight_list, stance_list, force_list, n_cams_max=n_cams_max)
+    else:
+        nmax = max(lens) if lens else 0
+        out = dict(lens=lens, q_init=_pad([np.asarray(q, np.float64) for q in q_init_list], nmax, np.shape(q_init_list[0])[1:]), meas=None, weight=None,
+                   stance=_pad([np.asarray(x, np.int32) for x in stance_list], nmax, np.shape(stance_list[0])[1:]).astype(np.int32), force=None)
+        if force_list is not None:
+            out["force"] = _pad([np.asarray(f, np.float64) for f in force_list], nmax, np.shape(force_list[0])[1:])
+    out["q_target"] = _pad([np.asarray(t, np.float64) for t in q_target_list], out["q_init"].shape[1], np.shape(q_init_list[0])[1:])
+    return out
+
+
+def track_weights(track_w, rows: int) -> np.ndarray:
+    """[rows, NX] float64 weights of the 3D kinematic cost: None = the reference's (abi.default_track_weights) for every row, one NX vector =
+    the same for every row, or one row per model"""
+    w = abi.default_track_weights() if track_w is None else np.asarray(track_w, dtype=np.float64)
+    if w.ndim == 1:
+        w = np.broadcast_to(w, (rows, w.shape[0]))
+    if w.shape != (rows, abi.NX):
+        raise ValueError(f"track weights: expected {abi.NX} entries per model ({rows} models), got shape {w.shape}")
+    return np.ascontiguousarray(w, dtype=np.float64)
 
 
 def unpad_kinetic(padded: dict, lens, n_cams) -> dict:
@@ -550,6 +590,106 @@ class Handle:
         res = unpad_kinetic(out, lens, [ncams[m] for m in models])
         res.update(status=st, stats=list(stats)[:B], kstats=list(ks)[:B], padded=out)
         return res
+
+    # ---- physics-based solve with the 3D kinematic cost (estimate_kinetics(use_2d_reprojections=False); include/cpe.h) ----------------------
+    def solve_kinetic_tracked(self, kopts, q_init, q_target, stance, q, dq, ddq, positions, meas=None, weight=None, meas_err=None, tau=None, lam=None,
+                              grf=None, slack=None, grf_fixed=None, tau_box=None, grf_box=None, track_w=None):
+        """cpe_solve_kinetic_tracked on device tensors (q_target [B, N, nq]; meas / weight may be None together, meas_err is then not written);
+        track_w: None (the reference's weights) or NX numbers (host).  Returns (status, [Stats], [KineticStats])"""
+        if sum(a is not None for a in (grf_fixed, tau_box, grf_box)) > 1:
+            raise ValueError("solve_kinetic_tracked: at most one of grf_fixed, tau_box, grf_box")
+        B, N = q_init.shape[0], q_init.shape[1]
+        w = track_weights(track_w, 1)
+        stats = (abi.Stats * max(B, 1))(); ks = (abi.KineticStats * max(B, 1))()
+        st = self._call(self.lib.cpe_solve_kinetic_tracked, "cpe_solve_kinetic_tracked", C.byref(kopts), w.ctypes.data, B, N, _ptr(q_init), _ptr(q_target),
+                        _ptr(meas), _ptr(weight), _ptr(stance), _ptr(grf_fixed), _ptr(tau_box), _ptr(grf_box), _ptr(q), _ptr(dq), _ptr(ddq),
+                        _ptr(positions), _ptr(meas_err), _ptr(tau), _ptr(lam), _ptr(grf), _ptr(slack), stats, ks, allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
+        return st, list(stats)[:B], list(ks)[:B]
+
+    def solve_kinetic_tracked_host(self, kopts, q_init, q_target, stance, meas=None, weight=None, grf_fixed=None, tau_box=None, grf_box=None,
+                                   track_w=None):
+        """cpe_solve_kinetic_tracked_host: numpy in, numpy out -- solve_kinetic_host's dict (meas_err None when meas is None)"""
+        if sum(a is not None for a in (grf_fixed, tau_box, grf_box)) > 1:
+            raise ValueError("solve_kinetic_tracked_host: at most one of grf_fixed, tau_box, grf_box")
+        if (meas is None) != (weight is None):
+            raise ValueError("solve_kinetic_tracked_host: meas and weight are given together or not at all")
+        f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+        qi, qt, me, we = f64(q_init), f64(q_target), f64(meas), f64(weight)
+        stn = np.ascontiguousarray(stance, dtype=np.int32)
+        fx = f64(grf_fixed if grf_fixed is not None else (tau_box if tau_box is not None else grf_box))
+        B, N = qi.shape[0], qi.shape[1]
+        if qt.shape != qi.shape:
+            raise ValueError("solve_kinetic_tracked_host: q_target has q_init's shape")
+        nm, nf, nc = kopts.dyn.n_motors, kopts.dyn.n_feet, self.n_constraint_rows()
+        E = np.empty
+        out = dict(q=E((B, N, self.nq)), dq=E((B, N, self.nq)), ddq=E((B, N, self.nq)), positions=E((B, N, self.L, 3)),
+                   meas_err=None if me is None else E((B, N, self.n_cams, self.L, 2)), tau=E((B, N, nm)), lam=E((B, N, nc)), grf=E((B, N, nf, 5)),
+                   slack=E((B, N, self.nq)))
+        w = track_weights(track_w, 1)
+        stats = (abi.Stats * max(B, 1))(); ks = (abi.KineticStats * max(B, 1))()
+        st = self.lib.cpe_solve_kinetic_tracked_host(self._h, C.byref(kopts), w.ctypes.data, B, N, _ptr(qi), _ptr(qt), _ptr(me), _ptr(we), stn.ctypes.data,
+                                                     _ptr(fx) if grf_fixed is not None else None, _ptr(fx) if tau_box is not None else None,
+                                                     _ptr(fx) if grf_box is not None else None, *[_ptr(out[k]) for k in KINETIC_OUTPUTS], stats, ks)
+        _check(st, "cpe_solve_kinetic_tracked_host", allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
+        out.update(status=st, stats=list(stats)[:B], kstats=list(ks)[:B])
+        return out
+
+    def solve_kinetic_tracked_ragged_host(self, kopts_list, q_init_list, q_target_list, stance_list, meas_list=None, weight_list=None, model_list=None,
+                                          grf_fixed=None, tau_box=None, grf_box=None, track_w=None):
+        """cpe_solve_kinetic_tracked_ragged_host over sequences of their own length and model (solve_kinetic_ragged_host's arguments and result,
+        plus q_target [N_b, nq] per sequence; meas_list / weight_list may be None together, meas_err is then None); track_w: None, NX numbers
+        for every model, or [n_models, NX]"""
+        B = len(q_init_list)
+        models = [0] * B if model_list is None else [int(m) for m in model_list]
+        ncams = getattr(self, "model_n_cams", [self.n_cams])
+        given = [a for a in (grf_fixed, tau_box, grf_box) if a is not None]
+        if len(given) > 1:
+            raise ValueError("solve_kinetic_tracked_ragged_host: at most one of grf_fixed, tau_box, grf_box")
+        force = given[0] if given else None
+        if len(q_target_list) != B or len(stance_list) != B or len(models) != B or (force is not None and len(force) != B) \
+                or (meas_list is not None and (len(meas_list) != B or weight_list is None or len(weight_list) != B)):
+            raise ValueError("solve_kinetic_tracked_ragged_host: one q_init, q_target, stance, model (and meas, weight, force array) per sequence")
+        if len(kopts_list) != len(ncams):
+            raise ValueError(f"solve_kinetic_tracked_ragged_host: one kinetic options struct per model of the handle ({len(ncams)}), got {len(kopts_list)}")
+        if any(m < 0 or m >= len(ncams) for m in models):
+            raise ValueError("solve_kinetic_tracked_ragged_host: model index out of range")
+        L, nq = self.L, self.nq
+        d0 = kopts_list[0].dyn
+        nf, nm, nc = int(d0.n_feet), int(d0.n_motors), self.n_constraint_rows()
+        ftail = None if force is None else ((nf, 3) if grf_fixed is not None else ((nm, 2) if tau_box is not None else (nf, 3, 2)))
+        for b in range(B):
+            n, c = int(np.shape(q_init_list[b])[0]), ncams[models[b]]
+            if np.shape(q_init_list[b]) != (n, nq) or np.shape(q_target_list[b]) != (n, nq) or np.shape(stance_list[b]) != (n, nf) \
+                    or (meas_list is not None and (np.shape(meas_list[b]) != (n, c, L, 2) or np.shape(weight_list[b]) != (n, c, L))) \
+                    or (force is not None and np.shape(force[b]) != (n,) + ftail):
+                raise ValueError(f"solve_kinetic_tracked_ragged_host: sequence {b} does not have the shapes of its model ({n} frames, {c} cameras)")
+        p = pad_kinetic_tracked(q_init_list, q_target_list, stance_list, meas_list, weight_list, force, n_cams_max=self.n_cams)
+        lens, Nm, Cm = p["lens"], p["q_init"].shape[1], self.n_cams
+        E = np.empty
+        out = dict(q=E((B, Nm, nq)), dq=E((B, Nm, nq)), ddq=E((B, Nm, nq)), positions=E((B, Nm, L, 3)),
+                   meas_err=None if meas_list is None else E((B, Nm, Cm, L, 2)), tau=E((B, Nm, nm)), lam=E((B, Nm, nc)), grf=E((B, Nm, nf, 5)),
+                   slack=E((B, Nm, nq)))
+        stats = (abi.Stats * max(B, 1))(); ks = (abi.KineticStats * max(B, 1))()
+        mo, nfr = (C.c_int32 * max(B, 1))(*models), (C.c_int32 * max(B, 1))(*lens)
+        ko = self._kinetic_options_array(kopts_list)
+        w = track_weights(track_w, len(ncams))
+        fx = p["force"]
+        st = self.lib.cpe_solve_kinetic_tracked_ragged_host(self._h, ko, w.ctypes.data, B, Nm, mo, nfr, _ptr(p["q_init"]), _ptr(p["q_target"]),
+                                                            _ptr(p["meas"]), _ptr(p["weight"]), p["stance"].ctypes.data,
+                                                            _ptr(fx) if grf_fixed is not None else None, _ptr(fx) if tau_box is not None else None,
+                                                            _ptr(fx) if grf_box is not None else None, *[_ptr(out[k]) for k in KINETIC_OUTPUTS], stats, ks)
+        _check(st, "cpe_solve_kinetic_tracked_ragged_host", allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
+        res = unpad_kinetic({k: v for k, v in out.items() if v is not None}, lens, [ncams[m] for m in models])
+        if meas_list is None:
+            res["meas_err"] = None
+        res.update(status=st, stats=list(stats)[:B], kstats=list(ks)[:B], padded=out)
+        return res
+
+    def eval_normal_tracked(self, q, q_target, g, Bm, cost, track_w=None, gam=None, q_out=None):
+        """cpe_eval_normal_tracked on device tensors: the per-frame terms of the tracked solve (T_n, bounds, pose prior) at Euler q"""
+        w = track_weights(track_w, 1)
+        self._call(self.lib.cpe_eval_normal_tracked, "cpe_eval_normal_tracked", w.ctypes.data, q.shape[0], q.shape[1], _ptr(q), _ptr(q_target), _ptr(g),
+                   _ptr(Bm), _ptr(cost), _ptr(gam), _ptr(q_out))
 
     def eval_kinetic_nodes_host(self, kopts, q, meas, weight, stance):
         """one evaluation of the physics terms per node (cpe_eval_kinetic_nodes); numpy in, dict of numpy arrays out"""

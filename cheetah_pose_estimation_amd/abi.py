@@ -137,6 +137,14 @@ def default_kinetic_options(dyn: DynOptions, fps: float = 120.0, kinetic_dataset
     return o
 
 
+def default_track_weights():
+    """the weights of the 3D kinematic cost on x (NX entries, link order; acinoset_misc.py:531-589 restated: base x, y, z 10, base angles 5,
+    bodyF / neck / tails theta and psi 5 / 2 / 5, leg pitches upper 5, lower 2, hock 1, every roll 0); same numbers as
+    cpe_default_track_weights() in csrc/cpe_api.hip"""
+    import numpy as np
+    return np.array([10, 10, 10, 5, 5, 5, 0, 5, 5, 0, 2, 2, 5, 5, 5, 5, 5, 2, 1, 5, 2, 1, 5, 2, 5, 2, 1, 1], dtype=np.float64)
+
+
 def default_options(fps: float = 120.0) -> Options:
     """Same defaults as cpe_default_options() in csrc/cpe_api.cpp."""
     o = Options()

@@ -65,7 +65,10 @@ struct cpe_handle {
     double *fbuf = nullptr, *kmu = nullptr, *Jbuf = nullptr, *Abuf = nullptr, *pieces = nullptr, *gTb = nullptr, *dstat = nullptr, *slackb = nullptr,
            *Tbuf = nullptr, *gk = nullptr, *Bk = nullptr, *Hk = nullptr;
     int* pmeta = nullptr;
-    int pb = 3;                  // half-bandwidth of the normal equations in frames (W with a window-W motion prior, W = 4..6)
+    // 3D kinematic cost of the physics-based solve (cpe_solve_kinetic_tracked*): per-model tables, their host copies, x* of every frame
+    DevTrack* dtrack = nullptr; std::vector<DevTrack> htrack;
+    double* xtgt = nullptr; size_t xtgt_frames = 0;
+    int pb = 3;                // half-bandwidth of the normal equations in frames (W with a window-W motion prior, W = 4..6)
 };
 
 struct DevBuf {
@@ -444,6 +447,19 @@ static size_t lds_normal_all(const cpe_handle* h) {
     for (const DevModel& m : h->models) n = std::max(n, lds_normal(m, h->gmm_k, h->gmm_dim));
     return n;
 }
+// k_frame_tracked (cpe_tracked.hip.inc): state | sin / cos | trunk rotations | Gamma | weighted residual | H | g, then the pose prior's scratch
+#define FRAME_TRACKED(gmm) ((gmm) ? k_frame_tracked<true> : k_frame_tracked<false>)
+#define FRAME_TRACKED_RAGGED(gmm) ((gmm) ? k_frame_tracked<true, true> : k_frame_tracked<false, true>)
+static size_t lds_tracked(const DevModel& m, int gmm_k, int gmm_dim) {
+    size_t n = m.ns + 6 * m.nl + 2 * m.nrev + 36 * m.n_trunk + GAM_STRIDE * m.nrev + m.nu + m.nu * m.nu + m.nu;
+    if (gmm_k > 0) n += CPE_NX + gmm_k * gmm_dim + CPE_MAX_GMM + CPE_NX;          // x | P_k (x - mu_k) | log p_k | gradient in x
+    return sizeof(double) * n;
+}
+static size_t lds_tracked_all(const cpe_handle* h) {
+    size_t n = lds_tracked(h->hm, h->gmm_k, h->gmm_dim);
+    for (const DevModel& m : h->models) n = std::max(n, lds_tracked(m, h->gmm_k, h->gmm_dim));
+    return n;
+}
 static int n_models(const cpe_handle* h) { return h->models.empty() ? 1 : (int)h->models.size(); }
 static int cams_max(const cpe_handle* h) {
     int c = h->hm.C;
@@ -666,6 +682,8 @@ void cpe_destroy(cpe_handle* h) {
     if (h->eom) (void)hipFree(h->eom);
     if (h->dyn) (void)hipFree(h->dyn);
     if (h->dk) (void)hipFree(h->dk);
+    if (h->dtrack) (void)hipFree(h->dtrack);
+    if (h->xtgt) (void)hipFree(h->xtgt);
     if (h->n_act) (void)hipFree(h->n_act);
     if (h->poll_host) (void)hipHostFree(h->poll_host);
     for (int i = 0; i < 2; i++) if (h->poll_ev[i]) (void)hipEventDestroy(h->poll_ev[i]);
@@ -1544,14 +1562,17 @@ static void launch_dyn_pieces(cpe_handle* h, int N, int first, size_t Fw, const 
 
 // One iteration of the physics-based solve: per-frame terms and physics terms of the evaluated buffer, accept / reject (new damping), elimination
 // of the node forces at that damping for the CURRENT iterate, band system, factor + solve + next trial.  RAGGED: with the table rg (N = nmax).
+// xt: x* of every frame (the 3D kinematic cost, k_frame_tracked in place of k_frame_normal), or null (reprojections).
 template <bool RAGGED>
 static void kin_iterate(cpe_handle* h, const LmParams& prm, int N, size_t Fw, size_t ldsn, const double* meas, const double* weight, const int32_t* stance,
-                        RaggedArgs rg, int first, const int* act, const int* n_act, int slots) {
+                        const double* xt, RaggedArgs rg, int first, const int* act, const int* n_act, int slots) {
     const unsigned gf = (unsigned)((size_t)slots * N);
     const bool plain = h->gmm_k == 0;
     prof_begin(h, 0);
-    hipLaunchKernelGGL(RAGGED ? FRAME_NORMAL_RAGGED(plain) : FRAME_NORMAL(plain), dim3(gf), dim3(WAVE), ldsn, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, meas,
-                       weight, h->gbuf, h->Bbuf, h->costbuf, h->mu, h->gambuf, h->pri, act, n_act, ShutterArgs{nullptr, nullptr, nullptr}, rg);
+    if (xt) hipLaunchKernelGGL(RAGGED ? FRAME_TRACKED_RAGGED(!plain) : FRAME_TRACKED(!plain), dim3(gf), dim3(WAVE), ldsn, h->stream, h->dm, h->dtrack, h->st, N, first, Fw,
+                               h->qbuf, xt, h->gbuf, h->Bbuf, h->costbuf, h->mu, h->gambuf, h->pri, act, n_act, rg);
+    else hipLaunchKernelGGL(RAGGED ? FRAME_NORMAL_RAGGED(plain) : FRAME_NORMAL(plain), dim3(gf), dim3(WAVE), ldsn, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, meas,
+                            weight, h->gbuf, h->Bbuf, h->costbuf, h->mu, h->gambuf, h->pri, act, n_act, ShutterArgs{nullptr, nullptr, nullptr}, rg);
     prof_end(h);
     launch_dyn_eval<RAGGED>(h, N, first, Fw, stance, act, n_act, slots, rg);
     prof_begin(h, 2);
@@ -1578,14 +1599,106 @@ static void kin_iterate(cpe_handle* h, const LmParams& prm, int N, size_t Fw, si
 
 }  // extern "C++"
 
+// ---- 3D kinematic cost (cpe_solve_kinetic_tracked*) ----------------------------------------------------------------------
+void cpe_default_track_weights(double w[CPE_NX]) {
+    // acinoset_misc.py:531-589 (its 54 weights per relative Euler angle) restated on x, in link order: base x, y, z | base phi, theta, psi |
+    // bodyF, neck: phi, theta, psi | tail0, tail1: theta, psi | leg pitches of UFL LFL HFL UFR LFR HFR UBL LBL UBR LBR HBL HBR (upper 5, lower 2,
+    // hock 1).  Every roll and every leg yaw the reference weights 0; of those only bodyF phi and neck phi are entries of x.
+    static const double t[CPE_NX] = {10, 10, 10, 5, 5, 5, 0, 5, 5, 0, 2, 2, 5, 5, 5, 5, 5, 2, 1, 5, 2, 1, 5, 2, 5, 2, 1, 1};
+    for (int k = 0; k < CPE_NX; k++) w[k] = t[k];
+}
+
+// The tables of the tracked cost for every model of the handle: weights w (rows of CPE_NX; model k takes row min(k, rows - 1)), X^T and
+// 2 X^T diag(w) X with X = dx/du of the cost view (the construction of DevPriors::Xc).  Refuses negative or non-finite weights.
+static cpe_status build_track(cpe_handle* h, const double* w, int rows) {
+    for (int i = 0; i < rows * CPE_NX; i++)
+        if (!std::isfinite(w[i]) || w[i] < 0.0)
+            return fail(CPE_BAD_ARG, "track_w: weights must be finite and non-negative (row " + std::to_string(i / CPE_NX) + ", entry " + std::to_string(i % CPE_NX) + ")");
+    const int nmod = n_models(h);
+    h->htrack.assign((size_t)nmod, DevTrack{});
+    for (int k = 0; k < nmod; k++) {
+        const DevModel& m = h->models.empty() ? h->hm : h->models[(size_t)k];
+        const double* wk = w + (size_t)std::min(k, rows - 1) * CPE_NX;
+        const int nu = m.nu;
+        double X[CPE_NX][CPE_NX] = {};
+        for (int i = 0; i < nu; i++)
+            for (int side = 0; side < 2; side++) {
+                const int kk = side == 0 ? i : m.rel_ref_u[i];
+                if (kk < 0) continue;
+                const double sgn = side == 0 ? m.rel_sign_u[i] : -m.rel_sign_u[i];
+                X[i][kk] += sgn;
+                const int r = m.rev_of_u[kk];
+                if (r >= 0) X[i][m.rev_body_u[r][1]] += sgn;
+            }
+        DevTrack& T = h->htrack[(size_t)k];
+        for (int i = 0; i < nu; i++) T.w[i] = wk[i];
+        for (int i = 0; i < nu; i++)
+            for (int j = 0; j < nu; j++) {
+                T.Xt[j][i] = X[i][j];
+                double a = 0.0;
+                for (int p = 0; p < nu; p++) a += X[p][i] * wk[p] * X[p][j];
+                T.H[i * nu + j] = 2.0 * a;
+            }
+    }
+    if (!h->dtrack) HIPCHK(hipMalloc(&h->dtrack, sizeof(DevTrack) * nmod));
+    HIPCHK(hipMemcpyAsync(h->dtrack, h->htrack.data(), sizeof(DevTrack) * nmod, hipMemcpyHostToDevice, h->stream));
+    return CPE_OK;
+}
+
+// CPE_BAD_ARG unless every entry of the target's own frames (host pointer [B][N][nq]; lens: the sequences' frame counts, or null) is finite
+static cpe_status check_target(const double* hq, int B, int N, int nq, const int32_t* lens) {
+    for (int b = 0; b < B; b++)
+        for (size_t i = 0; i < (size_t)(lens ? lens[b] : N) * nq; i++)
+            if (!std::isfinite(hq[(size_t)b * N * nq + i]))
+                return fail(CPE_BAD_ARG, "q_target: non-finite entry (sequence " + std::to_string(b) + ", frame " + std::to_string(i / nq) + ")");
+    return CPE_OK;
+}
+
+// x* of every frame from the Euler target (device pointer [B][N][nq]) into h->xtgt.  Unless the caller has checked it on the host already
+// (checked: the _host entries), the target is copied to the host and checked first (a non-finite entry is CPE_BAD_ARG, nothing launched).
+// rg: the ragged table (N = nmax), or null; lens: the sequences' frame counts, or null.
+static cpe_status track_target(cpe_handle* h, int B, int N, const double* q_target, const RaggedArgs* rg, const int32_t* lens, bool checked) {
+    const size_t F = (size_t)B * N;
+    const int nq = h->hm.nq;
+    if (!checked) {
+        std::vector<double> hq(F * nq);
+        HIPCHK(hipMemcpyAsync(hq.data(), q_target, sizeof(double) * F * nq, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (cpe_status s = check_target(hq.data(), B, N, nq, lens); s != CPE_OK) return s;
+    }
+    if (F > h->xtgt_frames) {
+        if (h->xtgt) (void)hipFree(h->xtgt);
+        h->xtgt = nullptr; h->xtgt_frames = 0;
+        HIPCHK(hipMalloc(&h->xtgt, sizeof(double) * F * CPE_NX));
+        h->xtgt_frames = F;
+    }
+    if (rg) hipLaunchKernelGGL(k_track_target<true>, dim3((unsigned)F), dim3(WAVE), 0, h->stream, h->dm, q_target, h->xtgt, *rg);
+    else hipLaunchKernelGGL(k_track_target<>, dim3((unsigned)F), dim3(WAVE), 0, h->stream, h->dm, q_target, h->xtgt, RaggedArgs{});
+    HIPCHK(hipGetLastError());
+    return CPE_OK;
+}
+
+// what the tracked entries add to solve_kinetic_impl: weights (rows of CPE_NX) and the Euler target (device pointer)
+struct TrackIn { const double* w; int rows; const double* q_target; bool checked; };   // checked: q_target checked on the host
+
 // The physics-based solve of every entry point: cpe_solve_kinetic* (model == null: B sequences of N frames of the handle's first model, options
 // opt[0]) and cpe_solve_kinetic_ragged (model / n_frames: host arrays of the batch, N = N_max, options opt[k] for model k).  At most one of
-// grf_fixed / tau_box / grf_box is given (the entry points check it).
+// grf_fixed / tau_box / grf_box is given (the entry points check it).  tr: the 3D kinematic cost in place of the reprojections (meas / weight
+// may then be null together: meas_err is not written), or null.
 static cpe_status solve_kinetic_impl(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const int32_t* model, const int32_t* n_frames,
                                      const double* q_init, const double* meas, const double* weight, const int32_t* stance, const double* grf_fixed,
                                      const double* tau_box, const double* grf_box, double* q, double* dq, double* ddq, double* positions, double* meas_err,
-                                     double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats, cpe_kinetic_stats* kstats) {
-    if (!h || !opt || !q_init || !meas || !weight || !stance || !q) return fail(CPE_BAD_ARG, "null argument");
+                                     double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats, cpe_kinetic_stats* kstats,
+                                     const TrackIn* tr = nullptr) {
+    if (!h || !opt || !q_init || !stance || !q) return fail(CPE_BAD_ARG, "null argument");
+    if (!tr && (!meas || !weight)) return fail(CPE_BAD_ARG, "null argument");
+    if (tr) {
+        if (!tr->w) return fail(CPE_BAD_ARG, "track_w is null");
+        if (!tr->q_target) return fail(CPE_BAD_ARG, "q_target is null");
+        if (meas && !weight) return fail(CPE_BAD_ARG, "meas is given without weight");
+        if (weight && !meas) return fail(CPE_BAD_ARG, "weight is given without meas");
+        if (!meas) meas_err = nullptr;
+    }
     if ((dq == nullptr) != (ddq == nullptr)) return fail(CPE_BAD_ARG, "dq and ddq must be given together");
     size_t F;
     if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
@@ -1606,16 +1719,20 @@ static cpe_status solve_kinetic_impl(cpe_handle* h, const cpe_kinetic_options* o
     if (s != CPE_OK) return s;
     s = ragged ? build_kin_all(h, opt, grf_fixed, tau_box, grf_box) : build_kin(h, opt, grf_fixed, tau_box, grf_box);
     if (s != CPE_OK) return s;
+    if (tr && (s = build_track(h, tr->w, tr->rows)) != CPE_OK) return s;
     const DevModel& m = h->hm;
     const size_t Fw = F;
     const RaggedArgs rg = ragged ? RaggedArgs{h->rseq, N, cams_max(h)} : RaggedArgs{};
     if (ragged) HIPCHK(hipMemcpyAsync(h->rseq, seq.data(), sizeof(int2) * B, hipMemcpyHostToDevice, h->stream));     // (seq outlives the stream: drained below)
+    if (tr && (s = track_target(h, B, N, tr->q_target, ragged ? &rg : nullptr, n_frames, tr->checked)) != CPE_OK) return s;
     if ((s = state_reset(h, B, N, q_init, ragged ? &rg : nullptr)) != CPE_OK || (s = kin_state_reset(h, F, tau_box != nullptr)) != CPE_OK) return s;
     const LmParams prm = lm_params(h, B, N);
-    const size_t ldsn = ragged ? lds_normal_all(h) : lds_normal(m, h->gmm_k, h->gmm_dim);
+    const size_t ldsn = tr ? (ragged ? lds_tracked_all(h) : lds_tracked(m, h->gmm_k, h->gmm_dim))
+                           : (ragged ? lds_normal_all(h) : lds_normal(m, h->gmm_k, h->gmm_dim));
+    const double* xt = tr ? h->xtgt : nullptr;
     auto iterate = [&](int first, const int* act, const int* n_act, int slots) {
-        if (ragged) kin_iterate<true>(h, prm, N, Fw, ldsn, meas, weight, stance, rg, first, act, n_act, slots);
-        else kin_iterate<false>(h, prm, N, Fw, ldsn, meas, weight, stance, rg, first, act, n_act, slots);
+        if (ragged) kin_iterate<true>(h, prm, N, Fw, ldsn, meas, weight, stance, xt, rg, first, act, n_act, slots);
+        else kin_iterate<false>(h, prm, N, Fw, ldsn, meas, weight, stance, xt, rg, first, act, n_act, slots);
     };
     if ((s = lm_drive(h, B, iterate)) != CPE_OK) return s;
     std::vector<SeqState> hs;
@@ -1690,6 +1807,53 @@ cpe_status cpe_solve_kinetic_ragged(cpe_handle* h, const cpe_kinetic_options* op
         return fail(CPE_BAD_ARG, "cpe_solve_kinetic_ragged: at most one of grf_fixed, tau_box, grf_box");
     return solve_kinetic_impl(h, opts, B, N_max, model, n_frames, q_init, meas, weight, stance, grf_fixed, tau_box, grf_box, q, dq, ddq, positions, meas_err,
                               tau, lambda, grf, slack, stats, kstats);
+}
+
+cpe_status cpe_solve_kinetic_tracked(cpe_handle* h, const cpe_kinetic_options* opt, const double* track_w, int32_t B, int32_t N, const double* q_init,
+                                     const double* q_target, const double* meas, const double* weight, const int32_t* stance, const double* grf_fixed,
+                                     const double* tau_box, const double* grf_box, double* q, double* dq, double* ddq, double* positions, double* meas_err,
+                                     double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats, cpe_kinetic_stats* kstats) {
+    if ((grf_fixed != nullptr) + (tau_box != nullptr) + (grf_box != nullptr) > 1)
+        return fail(CPE_BAD_ARG, "cpe_solve_kinetic_tracked: at most one of grf_fixed, tau_box, grf_box");
+    const TrackIn tr{track_w, 1, q_target, false};
+    return solve_kinetic_impl(h, opt, B, N, nullptr, nullptr, q_init, meas, weight, stance, grf_fixed, tau_box, grf_box, q, dq, ddq, positions, meas_err,
+                              tau, lambda, grf, slack, stats, kstats, &tr);
+}
+
+cpe_status cpe_solve_kinetic_tracked_ragged(cpe_handle* h, const cpe_kinetic_options* opts, const double* track_w, int32_t B, int32_t N_max,
+                                            const int32_t* model, const int32_t* n_frames, const double* q_init, const double* q_target, const double* meas,
+                                            const double* weight, const int32_t* stance, const double* grf_fixed, const double* tau_box,
+                                            const double* grf_box, double* q, double* dq, double* ddq, double* positions, double* meas_err, double* tau,
+                                            double* lambda, double* grf, double* slack, cpe_stats* stats, cpe_kinetic_stats* kstats) {
+    if (!h || !opts || !model || !n_frames) return fail(CPE_BAD_ARG, "null argument");
+    if ((grf_fixed != nullptr) + (tau_box != nullptr) + (grf_box != nullptr) > 1)
+        return fail(CPE_BAD_ARG, "cpe_solve_kinetic_tracked_ragged: at most one of grf_fixed, tau_box, grf_box");
+    const TrackIn tr{track_w, n_models(h), q_target, false};
+    return solve_kinetic_impl(h, opts, B, N_max, model, n_frames, q_init, meas, weight, stance, grf_fixed, tau_box, grf_box, q, dq, ddq, positions, meas_err,
+                              tau, lambda, grf, slack, stats, kstats, &tr);
+}
+
+cpe_status cpe_eval_normal_tracked(cpe_handle* h, const double* track_w, int32_t B, int32_t N, const double* q, const double* q_target, double* g,
+                                   double* Bm, double* cost, double* gam, double* q_out) {
+    if (!h || !q || !g || !Bm || !cost) return fail(CPE_BAD_ARG, "null argument");
+    if (!track_w) return fail(CPE_BAD_ARG, "track_w is null");
+    if (!q_target) return fail(CPE_BAD_ARG, "q_target is null");
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    HIPCHK(hipSetDevice(h->device));
+    cpe_status s = ensure_ws(h, B, N);
+    if (s != CPE_OK) return s;
+    if ((s = build_track(h, track_w, 1)) != CPE_OK || (s = track_target(h, B, N, q_target, nullptr, nullptr, false)) != CPE_OK) return s;
+    if ((s = state_reset(h, B, N, q)) != CPE_OK) return s;
+    const DevModel& m = h->hm;
+    hipLaunchKernelGGL(FRAME_TRACKED(h->gmm_k > 0), dim3((unsigned)F), dim3(WAVE), lds_tracked(m, h->gmm_k, h->gmm_dim), h->stream, h->dm, h->dtrack, h->st, N, 1, F,
+                       h->qbuf, h->xtgt, h->gbuf, h->Bbuf, h->costbuf, h->mu, h->gambuf, h->pri, nullptr, nullptr, RaggedArgs{});
+    HIPCHK(hipMemcpyAsync(g, h->gbuf, sizeof(double) * F * m.nu, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(Bm, h->Bbuf, sizeof(double) * F * m.nu * m.nu, hipMemcpyDeviceToDevice, h->stream));
+    hipLaunchKernelGGL(k_gather_normal, dim3((unsigned)F), dim3(128), 0, h->stream, h->dm, F, h->qbuf, h->costbuf, h->gambuf, cost, gam, q_out);
+    HIPCHK(hipGetLastError());
+    return CPE_OK;
 }
 
 // diagnostic building block (as cpe_eval_normal): one evaluation of the physics terms at Euler q, multipliers zero, forces from a cold start.
@@ -1791,7 +1955,7 @@ cpe_status cpe_eval_lm_step(cpe_handle* h, const cpe_kinetic_options* kopt, int3
     LmParams prm = lm_params(h, B, N);
     prm.lambda0 = lam;                                     // the accept stage of the first pass sets S.lambda from it
     const size_t ldsn = lds_normal(m, h->gmm_k, h->gmm_dim);
-    if (kopt) kin_iterate<false>(h, prm, N, F, ldsn, meas, weight, stance, RaggedArgs{}, 1, nullptr, nullptr, B);
+    if (kopt) kin_iterate<false>(h, prm, N, F, ldsn, meas, weight, stance, nullptr, RaggedArgs{}, 1, nullptr, nullptr, B);
     else lm_iterate(h, prm, N, F, ldsn, meas, weight, ShutterArgs{nullptr, nullptr, nullptr}, nullptr, 1, nullptr, nullptr, B);
     HIPCHK(hipGetLastError());
     std::vector<SeqState> hs((size_t)B);
@@ -2000,6 +2164,84 @@ cpe_status cpe_solve_kinetic_ragged_host(cpe_handle* h, const cpe_kinetic_option
     if (slack) HIPCHK(hipMemcpyAsync(slack, osl.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return s;
+}
+
+// host-pointer twins of cpe_solve_kinetic_tracked (model == null) and cpe_solve_kinetic_tracked_ragged: stage through HBM
+static cpe_status kinetic_tracked_host(cpe_handle* h, const cpe_kinetic_options* opts, const double* track_w, int32_t B, int32_t N, const int32_t* model,
+                                       const int32_t* n_frames, const double* q_init, const double* q_target, const double* meas, const double* weight,
+                                       const int32_t* stance, const double* grf_fixed, const double* tau_box, const double* grf_box, double* q, double* dq,
+                                       double* ddq, double* positions, double* meas_err, double* tau, double* lambda, double* grf, double* slack,
+                                       cpe_stats* stats, cpe_kinetic_stats* kstats) {
+    if (!h || !opts || !q_init || !stance || !q) return fail(CPE_BAD_ARG, "null argument");
+    if (!track_w) return fail(CPE_BAD_ARG, "track_w is null");
+    if (!q_target) return fail(CPE_BAD_ARG, "q_target is null");
+    if (meas && !weight) return fail(CPE_BAD_ARG, "meas is given without weight");
+    if (weight && !meas) return fail(CPE_BAD_ARG, "weight is given without meas");
+    if ((grf_fixed != nullptr) + (tau_box != nullptr) + (grf_box != nullptr) > 1)
+        return fail(CPE_BAD_ARG, "cpe_solve_kinetic_tracked: at most one of grf_fixed, tau_box, grf_box");
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    const cpe_dyn_options& d = opts[0].dyn;
+    if (d.n_feet < 1 || d.n_feet > 4 || d.n_motors < 0 || d.n_motors > CPE_MAX_MOTORS) return fail(CPE_BAD_ARG, "kinetic options: feet / motors out of range");
+    const DevModel& m = h->hm;
+    if (cpe_status s = check_target(q_target, B, N, m.nq, n_frames); s != CPE_OK) return s;
+    const size_t nf = (size_t)d.n_feet, nmo = (size_t)d.n_motors, nc = (size_t)n_con(m), nm = meas ? F * (model ? cams_max(h) : m.C) * m.L : 0;
+    HIPCHK(hipSetDevice(h->device));
+    DevBuf di, dt, dm_, dw_, dst, dfx, oq, odq, oddq, op, ome, ot, ol, og, osl;
+    const size_t n_fx = grf_fixed ? F * nf * 3 : (tau_box ? F * nmo * 2 : (grf_box ? F * nf * 6 : 0));
+    const double* fx = grf_fixed ? grf_fixed : (tau_box ? tau_box : grf_box);
+    HIPCHK(di.alloc(F * m.nq)); HIPCHK(dt.alloc(F * m.nq)); HIPCHK(dm_.alloc(nm * 2)); HIPCHK(dw_.alloc(nm)); HIPCHK(dst.alloc((F * nf + 1) / 2));
+    HIPCHK(dfx.alloc(n_fx)); HIPCHK(oq.alloc(F * m.nq)); HIPCHK(odq.alloc(F * m.nq)); HIPCHK(oddq.alloc(F * m.nq)); HIPCHK(op.alloc(F * m.L * 3));
+    HIPCHK(ome.alloc(nm * 2)); HIPCHK(ot.alloc(F * nmo)); HIPCHK(ol.alloc(F * nc)); HIPCHK(og.alloc(F * nf * 5)); HIPCHK(osl.alloc(F * m.nq));
+    int32_t* dstance = reinterpret_cast<int32_t*>(dst.p);
+    HIPCHK(hipMemcpyAsync(di.p, q_init, sizeof(double) * F * m.nq, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(dt.p, q_target, sizeof(double) * F * m.nq, hipMemcpyHostToDevice, h->stream));
+    if (meas) {
+        HIPCHK(hipMemcpyAsync(dm_.p, meas, sizeof(double) * nm * 2, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(dw_.p, weight, sizeof(double) * nm, hipMemcpyHostToDevice, h->stream));
+    }
+    HIPCHK(hipMemcpyAsync(dstance, stance, sizeof(int32_t) * F * nf, hipMemcpyHostToDevice, h->stream));
+    if (fx) HIPCHK(hipMemcpyAsync(dfx.p, fx, sizeof(double) * n_fx, hipMemcpyHostToDevice, h->stream));
+    const double *dmp = meas ? dm_.p : nullptr, *dwp = meas ? dw_.p : nullptr;
+    double* omp = meas ? ome.p : nullptr;
+    const double *gf = grf_fixed ? dfx.p : nullptr, *tb = tau_box ? dfx.p : nullptr, *gb = grf_box ? dfx.p : nullptr;
+    // the target is checked here, on the host copy the caller handed in: the device entries' own copy back is skipped
+    const TrackIn tr{track_w, model ? n_models(h) : 1, dt.p, true};
+    cpe_status s = solve_kinetic_impl(h, opts, B, N, model, n_frames, di.p, dmp, dwp, dstance, gf, tb, gb, oq.p, odq.p, oddq.p, op.p, omp, ot.p, ol.p, og.p,
+                                      osl.p, stats, kstats, &tr);
+    if (s < 0) return s;
+    HIPCHK(hipMemcpyAsync(q, oq.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
+    if (dq) HIPCHK(hipMemcpyAsync(dq, odq.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
+    if (ddq) HIPCHK(hipMemcpyAsync(ddq, oddq.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
+    if (positions) HIPCHK(hipMemcpyAsync(positions, op.p, sizeof(double) * F * m.L * 3, hipMemcpyDeviceToHost, h->stream));
+    if (meas_err && meas) HIPCHK(hipMemcpyAsync(meas_err, ome.p, sizeof(double) * nm * 2, hipMemcpyDeviceToHost, h->stream));
+    if (tau) HIPCHK(hipMemcpyAsync(tau, ot.p, sizeof(double) * F * nmo, hipMemcpyDeviceToHost, h->stream));
+    if (lambda) HIPCHK(hipMemcpyAsync(lambda, ol.p, sizeof(double) * F * nc, hipMemcpyDeviceToHost, h->stream));
+    if (grf) HIPCHK(hipMemcpyAsync(grf, og.p, sizeof(double) * F * nf * 5, hipMemcpyDeviceToHost, h->stream));
+    if (slack) HIPCHK(hipMemcpyAsync(slack, osl.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return s;
+}
+
+cpe_status cpe_solve_kinetic_tracked_host(cpe_handle* h, const cpe_kinetic_options* opt, const double* track_w, int32_t B, int32_t N, const double* q_init,
+                                          const double* q_target, const double* meas, const double* weight, const int32_t* stance, const double* grf_fixed,
+                                          const double* tau_box, const double* grf_box, double* q, double* dq, double* ddq, double* positions,
+                                          double* meas_err, double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats,
+                                          cpe_kinetic_stats* kstats) {
+    return kinetic_tracked_host(h, opt, track_w, B, N, nullptr, nullptr, q_init, q_target, meas, weight, stance, grf_fixed, tau_box, grf_box, q, dq, ddq,
+                                positions, meas_err, tau, lambda, grf, slack, stats, kstats);
+}
+
+cpe_status cpe_solve_kinetic_tracked_ragged_host(cpe_handle* h, const cpe_kinetic_options* opts, const double* track_w, int32_t B, int32_t N_max,
+                                                 const int32_t* model, const int32_t* n_frames, const double* q_init, const double* q_target,
+                                                 const double* meas, const double* weight, const int32_t* stance, const double* grf_fixed,
+                                                 const double* tau_box, const double* grf_box, double* q, double* dq, double* ddq, double* positions,
+                                                 double* meas_err, double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats,
+                                                 cpe_kinetic_stats* kstats) {
+    if (!model || !n_frames) return fail(CPE_BAD_ARG, "null argument");
+    return kinetic_tracked_host(h, opts, track_w, B, N_max, model, n_frames, q_init, q_target, meas, weight, stance, grf_fixed, tau_box, grf_box, q, dq, ddq,
+                                positions, meas_err, tau, lambda, grf, slack, stats, kstats);
 }
 
 }  // extern "C"

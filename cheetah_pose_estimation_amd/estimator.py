@@ -925,11 +925,29 @@ def estimate_kinetics(estimator: CheetahEstimator, init_torques: bool = True, au
     try:
         t0 = time()
         gfx, gbx = prep["grf_fixed"], prep["grf_box"]
-        res = h.solve_kinetic_host(prep["ko"], prep["q_init"][None], est.meas[None], est.weight[None], prep["stance"][None],
-                                   grf_fixed=None if gfx is None else gfx[None], grf_box=None if gbx is None else gbx[None])
+        if prep["tracked"]:
+            res = h.solve_kinetic_tracked_host(prep["ko"], prep["q_init"][None], prep["q_target"][None], prep["stance"][None], est.meas[None],
+                                               est.weight[None], grf_fixed=None if gfx is None else gfx[None], grf_box=None if gbx is None else gbx[None])
+        else:
+            res = h.solve_kinetic_host(prep["ko"], prep["q_init"][None], est.meas[None], est.weight[None], prep["stance"][None],
+                                       grf_fixed=None if gfx is None else gfx[None], grf_box=None if gbx is None else gbx[None])
         return _kinetic_finish(est, h, res, time() - t0, prep, solver_output, out_fname, out_dir_prefix)
     finally:
         h.close()
+
+
+def kinematic_result_path(data_dir: str, cam_idx: Optional[int], init_prev_kinematic_solution: bool) -> str:
+    """the kinematic result estimate_kinetics starts from, and with use_2d_reprojections=False also tracks (init_q, acinoset_opt.py:739-744):
+    fte_kinematic_<cam>/fte.pickle for a monocular estimator with init_prev_kinematic_solution, else fte_kinematic/fte.pickle"""
+    mono = cam_idx is not None and init_prev_kinematic_solution
+    return os.path.join(data_dir, f"fte_kinematic_{cam_idx}" if mono else "fte_kinematic", "fte.pickle")
+
+
+def tracked_motion_options(ko: abi.KineticOptions, fps: float) -> abi.KineticOptions:
+    """the motion energy of the 3D kinematic cost (acinoset_opt.py:913, :919-920): 1e-2 x torque in place of the marker smoothing, weighted
+    0.1 fps^-2 -> w_torque = 1 + 1e-3 fps^-2, w_smooth = 0 (in place; returns ko)"""
+    ko.w_torque, ko.w_smooth = 1.0 + 1e-3 / (fps * fps), 0.0
+    return ko
 
 
 def _kinetic_prepare(est: CheetahEstimator, auto: bool, use_2d_reprojections: bool, init_prev_kinematic_solution: bool, synthesised_grf: bool,
@@ -939,16 +957,13 @@ def _kinetic_prepare(est: CheetahEstimator, auto: bool, use_2d_reprojections: bo
     params, scene, sk = est.params, est.scene, est.skeleton
     if est.kinematic_model:
         raise AssertionError("Dynamic model of the cheetah is required.")          # the reference asserts hasattr(model, 'eom_f')
-    if not use_2d_reprojections:
-        raise NotImplementedError("the 3D kinematic cost (use_2d_reprojections=False) is not built")
     if not est.enable_eom_slack:
         raise NotImplementedError("enable_eom_slack=False (hard equations of motion, no slack cost, acinoset_opt.py:914): the slack IS the residual of this "
                                   "solver's least-squares model; no driver of the reference switches it off")
     if params.enable_shutter_delay_estimation and scene.cam_idx is None:
         raise NotImplementedError("shutter delays are estimated by estimate_kinematics only (cpe_solve_shutter); not inside the physics-based model")
     data_dir = params.data_dir if out_dir_prefix is None else os.path.join(out_dir_prefix, est.data_path)
-    mono = scene.cam_idx is not None and init_prev_kinematic_solution
-    fte = load_result_pickle(os.path.join(data_dir, f"fte_kinematic_{scene.cam_idx}" if mono else "fte_kinematic", "fte.pickle"))
+    fte = load_result_pickle(kinematic_result_path(data_dir, scene.cam_idx, init_prev_kinematic_solution))
     est.com_vel, est.com_pos = fte["com_vel"], fte["com_pos"]
     N = params.end_frame - params.start_frame
     if init_prev_kinematic_solution:
@@ -1013,13 +1028,18 @@ def _kinetic_prepare(est: CheetahEstimator, auto: bool, use_2d_reprojections: bo
         ko.zvel_max = 0.0                                                            # the joint-estimation branch always has them (:803-810)
     if not joint_estimation and not ground_constraint:
         ko.foot_height_tol = 1e9                                                     # the feet are not tied to the ground (:832)
+    q_target = None
+    if not use_2d_reprojections:                                                     # the 3D kinematic cost (acinoset_opt.py:911-913): the target is
+        q_target = np.ascontiguousarray(fte["q"][:N], dtype=np.float64)              # init_q, the stored kinematic solution (:739-744)
+        tracked_motion_options(ko, scene.fps)
     if disable_motion_prior:
         ko.w_torque, ko.w_smooth = 0.0, 0.0                                          # acinoset_opt.py:918-920
     if est.bound_eom_error is not None:
         ko.slack_lo, ko.slack_hi = float(est.bound_eom_error[0]), float(est.bound_eom_error[1])      # make_pyomo_model(bound_eom_error=...), acinoset_opt.py:510-514
     skk = skeleton.without_motion_model(sk)              # the physics-based cost has no constant-acceleration term (acinoset_opt.py:905-921)
     variant = "fixed" if grf_fixed is not None else ("force_box" if grf_box is not None else "free")
-    return dict(q_init=q_init, stance=stance, grf_fixed=grf_fixed, grf_box=grf_box, pri=pri, opts=opts, ko=ko, skeleton=skk, N=N, variant=variant)
+    return dict(q_init=q_init, stance=stance, grf_fixed=grf_fixed, grf_box=grf_box, pri=pri, opts=opts, ko=ko, skeleton=skk, N=N, variant=variant,
+                q_target=q_target, tracked=q_target is not None)
 
 
 def _kinetic_finish(est: CheetahEstimator, h, res: dict, seconds: float, prep: dict, solver_output: bool, out_fname: str,
@@ -1039,6 +1059,8 @@ def _kinetic_finish(est: CheetahEstimator, h, res: dict, seconds: float, prep: d
     est.result = res
     est.kinetic = dict(tau=res["tau"][0], lam=res["lam"][0], grf=res["grf"][0], slack=res["slack"][0], stance=stance, ground_height=ko.ground_height)
     est.costs = {"measurement": st.cost_meas, "pose": st.cost_pose, "energy": ks.cost_energy, "eom_error": ks.cost_eom, "torque": ks.cost_torque}
+    if prep.get("tracked"):                                                          # measurement = the kinematic cost, energy = 1e-2 torque (acinoset_opt.py:912-913)
+        est.costs["energy"] = 1e-2 * ks.cost_torque
     base_err = float(np.sqrt(np.mean((q_init[:, :6] - res["q"][0][:, :6]) ** 2)))
     rel_err = float(np.sqrt(np.mean((q_init[:, 6:] - res["q"][0][:, 6:]) ** 2)))
     if solver_output:
@@ -1061,12 +1083,14 @@ def _copy_kinetic_options(o: abi.KineticOptions) -> abi.KineticOptions:
     return c
 
 
-def kinetic_ragged_group_key(sk: abi.Skeleton, opts: abi.Options, ko: abi.KineticOptions, pri: Optional[abi.Priors], variant: str, device: int) -> tuple:
+def kinetic_ragged_group_key(sk: abi.Skeleton, opts: abi.Options, ko: abi.KineticOptions, pri: Optional[abi.Priors], variant: str, device: int,
+                             tracked: bool = False) -> tuple:
     """What sequences must share to go through one cpe_solve_kinetic_ragged call (Handle.multi): the skeleton's shape, the solver options the LM
     driver reads per batch, the kinetic option fields that fix every node's unknowns and rows (_lib.kinetic_shape_signature), the priors, the
-    variant (free, prescribed or boxed foot forces) and the device.  Rig, length, frame rate, masses and the other kinetic options may differ."""
+    variant (free, prescribed or boxed foot forces), the device and the mode (2D reprojections, or the 3D kinematic cost: tracked = True,
+    cpe_solve_kinetic_tracked_ragged).  Rig, length, frame rate, masses and the other kinetic options may differ."""
     return (_lib.shape_signature(sk), _lib.shared_options_signature(opts), _lib.kinetic_shape_signature(ko), None if pri is None else _struct_bytes(pri),
-            variant, device)
+            variant, device, "tracked" if tracked else "2d")
 
 
 def _kinetic_model_bytes(est: CheetahEstimator, prep: dict) -> bytes:
@@ -1103,9 +1127,9 @@ def estimate_kinetics_batch(estimators: Sequence[CheetahEstimator], init_torques
                              None if options is None else _copy_options(options), None if kinetic_options is None else _copy_kinetic_options(kinetic_options))
         prepared[i] = p
         if ragged:
-            key = kinetic_ragged_group_key(p["skeleton"], p["opts"], p["ko"], p["pri"], p["variant"], est.device)
+            key = kinetic_ragged_group_key(p["skeleton"], p["opts"], p["ko"], p["pri"], p["variant"], est.device, tracked=p["tracked"])
         else:
-            key = (_kinetic_model_bytes(est, p), p["N"], None if p["pri"] is None else _struct_bytes(p["pri"]), p["variant"], est.device)
+            key = (_kinetic_model_bytes(est, p), p["N"], None if p["pri"] is None else _struct_bytes(p["pri"]), p["variant"], est.device, p["tracked"])
         groups.setdefault(key, []).append(i)
     for idx in groups.values():
         (_solve_kinetic_ragged_group if ragged else _solve_kinetic_group)(ests, idx, prepared, out, solver_output, out_fname, out_dir_prefix)
@@ -1119,8 +1143,12 @@ def _solve_kinetic_group(ests, idx, prepared, out, solver_output, out_fname, out
     h = _lib.Handle(p0["skeleton"], e0.cams, p0["opts"], p0["pri"], device=e0.device)
     try:
         t0 = time()
-        res = h.solve_kinetic_host(p0["ko"], stack("q_init"), np.stack([ests[i].meas for i in idx]), np.stack([ests[i].weight for i in idx]),
-                                   stack("stance"), grf_fixed=stack("grf_fixed"), grf_box=stack("grf_box"))
+        meas, weight = np.stack([ests[i].meas for i in idx]), np.stack([ests[i].weight for i in idx])
+        if p0["tracked"]:
+            res = h.solve_kinetic_tracked_host(p0["ko"], stack("q_init"), stack("q_target"), stack("stance"), meas, weight, grf_fixed=stack("grf_fixed"),
+                                               grf_box=stack("grf_box"))
+        else:
+            res = h.solve_kinetic_host(p0["ko"], stack("q_init"), meas, weight, stack("stance"), grf_fixed=stack("grf_fixed"), grf_box=stack("grf_box"))
         dt = (time() - t0) / len(idx)                                                # processing_time_s of a sequence: its share of the batched solve
         for b, i in enumerate(idx):
             out[i] = _kinetic_finish(ests[i], h, _kinetic_one(res, b), dt, prepared[i], solver_output, out_fname, out_dir_prefix)
@@ -1143,9 +1171,14 @@ def _solve_kinetic_ragged_group(ests, idx, prepared, out, solver_output, out_fna
     try:
         force = "grf_fixed" if p0["variant"] == "fixed" else ("grf_box" if p0["variant"] == "force_box" else None)
         t0 = time()
-        res = h.solve_kinetic_ragged_host([prepared[i]["ko"] for i in reps], [prepared[i]["q_init"] for i in idx], [ests[i].meas for i in idx],
-                                          [ests[i].weight for i in idx], [prepared[i]["stance"] for i in idx], of,
-                                          **({} if force is None else {force: [prepared[i][force] for i in idx]}))
+        fkw = {} if force is None else {force: [prepared[i][force] for i in idx]}
+        if p0["tracked"]:
+            res = h.solve_kinetic_tracked_ragged_host([prepared[i]["ko"] for i in reps], [prepared[i]["q_init"] for i in idx],
+                                                      [prepared[i]["q_target"] for i in idx], [prepared[i]["stance"] for i in idx],
+                                                      [ests[i].meas for i in idx], [ests[i].weight for i in idx], of, **fkw)
+        else:
+            res = h.solve_kinetic_ragged_host([prepared[i]["ko"] for i in reps], [prepared[i]["q_init"] for i in idx], [ests[i].meas for i in idx],
+                                              [ests[i].weight for i in idx], [prepared[i]["stance"] for i in idx], of, **fkw)
         dt = (time() - t0) / len(idx)                                                # processing_time_s of a sequence: its share of the batched solve
         for b, i in enumerate(idx):
             if of[b] not in fk:

@@ -128,6 +128,46 @@ def cost_view_numpy(sk: abi.Skeleton, q: np.ndarray) -> np.ndarray:
     return qc
 
 
+def tracked_x(sk: abi.Skeleton, q: np.ndarray) -> np.ndarray:
+    """x[..., NX] of the 3D kinematic cost: the skeleton's relative angles (rel_ref / rel_sign, acinoset_misc.py:508-528) of the cost
+    view of an Euler trajectory q[..., nq], at the independent dofs"""
+    qc = cost_view_numpy(sk, q)
+    ref = np.array(sk.rel_ref[:sk.nq]); sgn = np.array(sk.rel_sign[:sk.nq])
+    rel = np.where(ref < 0, qc, sgn * (qc - qc[..., np.maximum(ref, 0)]))
+    return rel[..., independent_dofs(sk)]
+
+
+def tracked_x_jacobian(sk: abi.Skeleton) -> np.ndarray:
+    """X = dx / du [NX, NX] from the skeleton's tables: u = the independent dofs, a leg's slot holding its angle alpha about the body's y axis
+    (DESIGN.md 2); x_i = sign_i (c_i - c_ref(i)) with c = the coordinate itself or, for a leg link, theta_B + alpha"""
+    ind = independent_dofs(sk)
+    u_of = {int(p): k for k, p in enumerate(ind)}
+    body = dict(leg_layout(sk))
+    X = np.zeros((len(ind), len(ind)))
+    for i, p in enumerate(ind):
+        r = sk.rel_ref[p]
+        s0 = 1.0 if r < 0 else sk.rel_sign[p]
+        for pp, s in ((int(p), s0), (int(r), -s0)):
+            if pp < 0:
+                continue
+            X[i, u_of[pp]] += s
+            link = (pp - 3) // 3
+            if pp >= 3 and link in body:
+                X[i, u_of[dof(LINKS[body[link]], THETA)]] += s
+    return X
+
+
+def q_from_u(sk: abi.Skeleton, u: np.ndarray) -> np.ndarray:
+    """Euler q[..., nq] of reduced coordinates u[..., NX] (trunk dofs, then alpha at each leg's pitch slot); dependent trunk angles (the tails'
+    roll) stay 0 -- x does not read them"""
+    ind = independent_dofs(sk)
+    q = np.zeros(u.shape[:-1] + (sk.nq,))
+    q[..., ind] = u
+    lay = leg_layout(sk)
+    alpha = np.stack([u[..., list(ind).index(dof(LINKS[c], THETA))] for c, _ in lay], axis=-1)
+    return legs_from_alpha(sk, q, alpha)
+
+
 # ---------------------------------------------------------------------------------------------------
 def look_at_camera(pos, target, fx, fy, cx, cy, D, model=abi.CAM_FISHEYE, mult=1.0) -> abi.Camera:
     pos, target = np.asarray(pos, float), np.asarray(target, float)

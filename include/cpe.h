@@ -468,6 +468,46 @@ cpe_status cpe_solve_kinetic_ragged_host(cpe_handle* h, const cpe_kinetic_option
                                          double* positions, double* meas_err, double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats,
                                          cpe_kinetic_stats* kstats);
 
+/* ---- physics-based solve with the 3D kinematic cost (estimate_kinetics(use_2d_reprojections=False), acinoset_opt.py:908-913):
+ * inverse dynamics of a given trajectory.  The reprojection cost of every frame is replaced by
+ *     T_n = sum_p w_p (x_p(u_n) - x*_{n,p})^2        (acinoset_misc.py:531-590, kinematic_cost)
+ * over the CPE_NX relative angles x (base 6, then child-minus-parent angles; the leg pitch on the cost view theta_B + alpha), x* = the same
+ * view of q_target [B][N][nq] (Euler; alpha from R_B^T R_c, so either triple of a link gives the same x*).  Everything else is the physics-based
+ * model of cpe_solve_kinetic*: the pose prior of the handle, angle bounds, torque / smoothing / slack costs of `opt`, contact rules, the variant
+ * chosen by grf_fixed / tau_box / grf_box (at most one non-NULL).  The reference's motion energy in this mode (1e-2 x torque) is expressed
+ * through the options: w_smooth = 0, w_torque = 1 + 1e-3 fps^-2.  cpe_stats.cost_meas reports sum_n T_n.
+ * track_w [CPE_NX] (ragged: [n_models of h][CPE_NX]), HOST: the weights, finite and >= 0 (cpe_default_track_weights gives the reference's).
+ * meas, weight and meas_err may be NULL together (measurements are never read; with meas given, meas_err reports the reprojection errors of
+ * the result).  Refused with CPE_BAD_ARG before anything is launched, cpe_last_error() naming the argument: NULL q_target or track_w, meas
+ * without weight (or weight without meas), negative or non-finite weights, a non-finite entry of q_target within a sequence's own frames.
+ * Layouts, outputs and the ragged contract as cpe_solve_kinetic / cpe_solve_kinetic_ragged; q_target takes q_init's layout. */
+void cpe_default_track_weights(double w[CPE_NX]);
+cpe_status cpe_solve_kinetic_tracked(cpe_handle* h, const cpe_kinetic_options* opt, const double* track_w, int32_t B, int32_t N, const double* q_init,
+                                     const double* q_target, const double* meas, const double* weight, const int32_t* stance, const double* grf_fixed,
+                                     const double* tau_box, const double* grf_box, double* q, double* dq, double* ddq, double* positions, double* meas_err,
+                                     double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats, cpe_kinetic_stats* kstats);
+cpe_status cpe_solve_kinetic_tracked_host(cpe_handle* h, const cpe_kinetic_options* opt, const double* track_w, int32_t B, int32_t N, const double* q_init,
+                                          const double* q_target, const double* meas, const double* weight, const int32_t* stance, const double* grf_fixed,
+                                          const double* tau_box, const double* grf_box, double* q, double* dq, double* ddq, double* positions,
+                                          double* meas_err, double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats,
+                                          cpe_kinetic_stats* kstats);
+cpe_status cpe_solve_kinetic_tracked_ragged(cpe_handle* h, const cpe_kinetic_options* opts, const double* track_w, int32_t B, int32_t N_max,
+                                            const int32_t* model /*[B] host*/, const int32_t* n_frames /*[B] host*/, const double* q_init,
+                                            const double* q_target, const double* meas, const double* weight, const int32_t* stance, const double* grf_fixed,
+                                            const double* tau_box, const double* grf_box, double* q, double* dq, double* ddq, double* positions,
+                                            double* meas_err, double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats,
+                                            cpe_kinetic_stats* kstats);
+cpe_status cpe_solve_kinetic_tracked_ragged_host(cpe_handle* h, const cpe_kinetic_options* opts, const double* track_w, int32_t B, int32_t N_max,
+                                                 const int32_t* model, const int32_t* n_frames, const double* q_init, const double* q_target,
+                                                 const double* meas, const double* weight, const int32_t* stance, const double* grf_fixed,
+                                                 const double* tau_box, const double* grf_box, double* q, double* dq, double* ddq, double* positions,
+                                                 double* meas_err, double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats,
+                                                 cpe_kinetic_stats* kstats);
+/* diagnostic twin of cpe_eval_normal for the tracked per-frame terms (k_frame_tracked): T_n, angle bounds, pose prior at Euler q, multipliers
+ * zero.  track_w [CPE_NX]; q, q_target [B][N][nq]; outputs as cpe_eval_normal's (device pointers). */
+cpe_status cpe_eval_normal_tracked(cpe_handle* h, const double* track_w, int32_t B, int32_t N, const double* q, const double* q_target, double* g,
+                                   double* Bm, double* cost, double* gam, double* q_out);
+
 /* diagnostic building block of cpe_solve_kinetic (as cpe_eval_normal is of cpe_solve): ONE evaluation of the physics terms of every node at
  * Euler q, multipliers zero, forces from a cold start -- what ASL hands IPOPT per node for the constraints of make_pyomo_model(include_eom_slack=True)
  * (acinoset_opt.py:510-514) after the node forces are minimised out.  Device pointers, each may be NULL: f [B][N][64] node forces (tau | lambda |
