@@ -19,7 +19,7 @@ def rot_zyx(ang: np.ndarray) -> np.ndarray:
     sf, cf = np.sin(ang[..., 0]), np.cos(ang[..., 0])
     st, ct = np.sin(ang[..., 1]), np.cos(ang[..., 1])
     sp, cp = np.sin(ang[..., 2]), np.cos(ang[..., 2])
-    R = np.empty(ang.shape[:-1] + (3, 3))
+    R = np.empty(ang.shape[:-1] + (3, 3), dtype=ang.dtype)      # (keeps np.longdouble: the extended-precision reference of tests/resjac_compare.py)
     R[..., 0, 0] = cp * ct; R[..., 0, 1] = sf * st * cp - sp * cf; R[..., 0, 2] = sf * sp + st * cf * cp
     R[..., 1, 0] = sp * ct; R[..., 1, 1] = sf * sp * st + cf * cp; R[..., 1, 2] = -sf * cp + sp * st * cf
     R[..., 2, 0] = -st;     R[..., 2, 1] = sf * ct;                R[..., 2, 2] = cf * ct
