@@ -107,6 +107,8 @@ def load():
     lib.cpe_solve_kinetic_tracked_ragged.argtypes = [vp, ko_p, vp, C.c_int32, C.c_int32, ip, ip] + [vp] * 17 + [C.POINTER(abi.Stats), C.POINTER(abi.KineticStats)]
     lib.cpe_solve_kinetic_tracked_ragged_host.argtypes = lib.cpe_solve_kinetic_tracked_ragged.argtypes
     lib.cpe_eval_normal_tracked.argtypes = [vp, vp, C.c_int32, C.c_int32] + [vp] * 7
+    for name in abi.COVARIANCE_ENTRIES:
+        getattr(lib, name).argtypes = abi.covariance_argtypes(name)
     _LIB = lib
     return lib
 
@@ -115,6 +117,13 @@ def _check(status: int, what: str, allow=(abi.OK,)):
     if status not in allow:
         raise CpeError(f"{what} failed with status {status}: {load().cpe_last_error().decode()}")
     return status
+
+
+def covariance_supported(priors: Optional[abi.Priors], ridge: float) -> int:
+    """cpe_covariance_supported: what the covariance entries refuse, without a handle.  Returns the status (abi.OK, abi.NO_DEVICE where no GPU
+    is visible); raises CpeError with the library's reason on abi.BAD_ARG (negative or non-finite ridge, motion-prior window above 4)."""
+    st = load().cpe_covariance_supported(C.byref(priors) if priors is not None else None, float(ridge))
+    return _check(st, "cpe_covariance_supported", allow=(abi.OK, abi.NO_DEVICE))
 
 
 def shape_signature(sk: abi.Skeleton) -> bytes:
@@ -733,6 +742,77 @@ class Handle:
         self.synchronize()
         res = {k: v.cpu().numpy() for k, v in out.items()}
         res["seq"] = seq
+        return res
+
+    # ---- posterior covariance of the kinematic estimate (include/cpe.h, cpe_covariance) -----------------------------------------------
+    def band_inverse(self, L, cov_diag, cov_off=None):
+        """cpe_band_inverse on device tensors: L [B, N, pb + 1, 28, 28] (eval_lm_step_host's layout) -> cov_diag [B, N, 28, 28], cov_off
+        [B, N, pb, 28, 28] (block [n][i-1] = Sigma(n + i, n)) or None"""
+        self._call(self.lib.cpe_band_inverse, "cpe_band_inverse", L.shape[0], L.shape[1], _ptr(L), _ptr(cov_diag), _ptr(cov_off))
+
+    def band_inverse_host(self, L):
+        """numpy in, numpy out (staged through HBM with torch): (cov_diag, cov_off)"""
+        Ld = self._to_device(L)
+        B, N = Ld.shape[0], Ld.shape[1]
+        cd, co = self._empty(B, N, 28, 28), self._empty(B, N, self.pb, 28, 28)
+        self.band_inverse(Ld, cd, co)
+        self.synchronize()
+        return cd.cpu().numpy(), co.cpu().numpy()
+
+    def covariance(self, q, meas, weight, ridge, cov_diag, cov_off=None, cov_pos=None, L=None):
+        """cpe_covariance on device tensors: Sigma = (H + ridge D)^-1 at Euler q [B, N, nq] on its block band; cov_diag [B, N, 28, 28], cov_off
+        [B, N, pb, 28, 28], cov_pos [B, N, L, 3, 3], L [B, N, pb + 1, 28, 28] (each of the last three may be None).  Returns (status, [status of
+        every sequence]): abi.OK, or abi.NUMERICAL where the matrix has no Cholesky factor (that sequence's outputs are zero)."""
+        B, N = q.shape[0], q.shape[1]
+        seq = (C.c_int32 * max(B, 1))()
+        st = self._call(self.lib.cpe_covariance, "cpe_covariance", B, N, _ptr(q), _ptr(meas), _ptr(weight), float(ridge), _ptr(cov_diag), _ptr(cov_off),
+                        _ptr(cov_pos), _ptr(L), seq, allow=(abi.OK, abi.NUMERICAL))
+        return st, list(seq)[:B]
+
+    def _covariance_outputs(self, B, N, want_off, want_pos, want_L):
+        E = np.empty
+        return dict(cov_diag=E((B, N, 28, 28)), cov_off=E((B, N, self.pb, 28, 28)) if want_off else None,
+                    cov_pos=E((B, N, self.L, 3, 3)) if want_pos else None, L=E((B, N, self.pb + 1, 28, 28)) if want_L else None)
+
+    def covariance_host(self, q, meas, weight, ridge=0.0, want_off=True, want_pos=True, want_L=False):
+        """cpe_covariance_host: numpy in, dict of numpy arrays out (cov_diag, cov_off, cov_pos, L as in covariance(); status, seq_status)"""
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        q, meas, weight = f64(q), f64(meas), f64(weight)
+        B, N = q.shape[:2]
+        out = self._covariance_outputs(B, N, want_off, want_pos, want_L)
+        seq = (C.c_int32 * max(B, 1))()
+        st = self.lib.cpe_covariance_host(self._h, B, N, _ptr(q), _ptr(meas), _ptr(weight), float(ridge), _ptr(out["cov_diag"]), _ptr(out["cov_off"]),
+                                          _ptr(out["cov_pos"]), _ptr(out["L"]), seq)
+        _check(st, "cpe_covariance_host", allow=(abi.OK, abi.NUMERICAL))
+        out.update(status=st, seq_status=list(seq)[:B])
+        return out
+
+    def covariance_ragged_host(self, q_list, meas_list, weight_list, model_list=None, ridge=0.0, want_off=True, want_pos=True, want_L=False):
+        """cpe_covariance_ragged_host over sequences of their own length and model (solve_ragged_host's arguments): pads, runs, unpads.  Returns
+        dict(cov_diag, cov_off, cov_pos, L = lists of per-sequence arrays [N_b, ...] or None, status, seq_status, padded = the padded outputs)."""
+        B = len(q_list)
+        models = [0] * B if model_list is None else [int(m) for m in model_list]
+        ncams = getattr(self, "model_n_cams", [self.n_cams])
+        if len(meas_list) != B or len(weight_list) != B or len(models) != B:
+            raise ValueError("covariance_ragged_host: one q, meas, weight and model per sequence")
+        if any(m < 0 or m >= len(ncams) for m in models):
+            raise ValueError("covariance_ragged_host: model index out of range")
+        lens = [int(np.shape(q)[0]) for q in q_list]
+        Nm, Cm, L, nq = max(lens), self.n_cams, self.L, self.nq
+        qi = np.zeros((B, Nm, nq)); me = np.zeros((B, Nm, Cm, L, 2)); we = np.zeros((B, Nm, Cm, L))
+        for b in range(B):
+            n, c = lens[b], ncams[models[b]]
+            if np.shape(meas_list[b]) != (n, c, L, 2) or np.shape(weight_list[b]) != (n, c, L) or np.shape(q_list[b]) != (n, nq):
+                raise ValueError(f"covariance_ragged_host: sequence {b} does not have the shapes of its model ({n} frames, {c} cameras)")
+            qi[b, :n], me[b, :n, :c], we[b, :n, :c] = q_list[b], meas_list[b], weight_list[b]
+        out = self._covariance_outputs(B, Nm, want_off, want_pos, want_L)
+        seq = (C.c_int32 * max(B, 1))()
+        mo, nf = (C.c_int32 * max(B, 1))(*models), (C.c_int32 * max(B, 1))(*lens)
+        st = self.lib.cpe_covariance_ragged_host(self._h, B, Nm, mo, nf, _ptr(qi), _ptr(me), _ptr(we), float(ridge), _ptr(out["cov_diag"]),
+                                                 _ptr(out["cov_off"]), _ptr(out["cov_pos"]), _ptr(out["L"]), seq)
+        _check(st, "cpe_covariance_ragged_host", allow=(abi.OK, abi.NUMERICAL))
+        res = {k: (None if v is None else [np.ascontiguousarray(v[b, :lens[b]]) for b in range(B)]) for k, v in out.items()}
+        res.update(status=st, seq_status=list(seq)[:B], padded=out)
         return res
 
     # ---- host-pointer conveniences (numpy in, numpy out; PCIe-inclusive) -------------------------------

@@ -160,3 +160,22 @@ def default_options(fps: float = 120.0) -> Options:
     o.max_iter = 200
     o.curvature = 0
     return o
+
+
+# ---- posterior covariance (include/cpe.h, cpe_covariance): argument lists of the entry points, mirrored for _lib.load().  "h" handle,
+# "i" int32, "d" double, "p" pointer to double, "ip" pointer to int32 (host), "pr" pointer to Priors
+COVARIANCE_ENTRIES = {
+    "cpe_covariance_supported": ("pr", "d"),
+    "cpe_band_inverse": ("h", "i", "i", "p", "p", "p"),
+    "cpe_covariance": ("h", "i", "i", "p", "p", "p", "d", "p", "p", "p", "p", "ip"),
+    "cpe_covariance_host": ("h", "i", "i", "p", "p", "p", "d", "p", "p", "p", "p", "ip"),
+    "cpe_covariance_ragged": ("h", "i", "i", "ip", "ip", "p", "p", "p", "d", "p", "p", "p", "p", "ip"),
+    "cpe_covariance_ragged_host": ("h", "i", "i", "ip", "ip", "p", "p", "p", "d", "p", "p", "p", "p", "ip"),
+}
+COVARIANCE_MAX_PB = 4        # largest half-bandwidth (frames) the covariance sweep supports: motion-prior windows 5 and 6 are refused
+
+
+def covariance_argtypes(name: str) -> list:
+    """ctypes argument list of a covariance entry point"""
+    kinds = {"h": C.c_void_p, "i": C.c_int32, "d": C.c_double, "p": C.c_void_p, "ip": C.POINTER(C.c_int32), "pr": C.POINTER(Priors)}
+    return [kinds[k] for k in COVARIANCE_ENTRIES[name]]

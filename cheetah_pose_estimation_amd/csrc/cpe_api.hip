@@ -68,6 +68,7 @@ struct cpe_handle {
     // 3D kinematic cost of the physics-based solve (cpe_solve_kinetic_tracked*): per-model tables, their host copies, x* of every frame
     DevTrack* dtrack = nullptr; std::vector<DevTrack> htrack;
     double* xtgt = nullptr; size_t xtgt_frames = 0;
+    double* covG = nullptr; size_t covG_n = 0;     // cpe_covariance / cpe_band_inverse: the sweep's operands T^T T | G_1 .. G_pb of every column
     int pb = 3;                // half-bandwidth of the normal equations in frames (W with a window-W motion prior, W = 4..6)
 };
 
@@ -684,6 +685,7 @@ void cpe_destroy(cpe_handle* h) {
     if (h->dk) (void)hipFree(h->dk);
     if (h->dtrack) (void)hipFree(h->dtrack);
     if (h->xtgt) (void)hipFree(h->xtgt);
+    if (h->covG) (void)hipFree(h->covG);
     if (h->n_act) (void)hipFree(h->n_act);
     if (h->poll_host) (void)hipHostFree(h->poll_host);
     for (int i = 0; i < 2; i++) if (h->poll_ev[i]) (void)hipEventDestroy(h->poll_ev[i]);
@@ -1061,9 +1063,10 @@ static void with_pb(int pb, Fn&& f) {
 }
 
 // One iteration of the kinematic solve (the LmIterate of lm_run): k_frame_normal (+ k_lr_band) on the evaluated buffer, then k_lm_step and
-// k_lm_back.  sh: shutter-delay buffers (all null = off); rg: the ragged table (N = nmax), or null.
+// k_lm_back.  sh: shutter-delay buffers (all null = off); rg: the ragged table (N = nmax), or null.  back = false (cpe_covariance): stop after
+// k_lm_step -- the factor is in Lbuf and every factored sequence has back_pending = 1.
 static void lm_iterate(cpe_handle* h, const LmParams& prm, int N, size_t Fw, size_t ldsn, const double* meas, const double* weight, ShutterArgs sh,
-                       const RaggedArgs* rg, int first, const int* act, const int* n_act, int slots) {
+                       const RaggedArgs* rg, int first, const int* act, const int* n_act, int slots, bool back = true) {
     const bool lr = h->lr_window > 0;
     const unsigned gf = (unsigned)((size_t)slots * N);
     const double* hiu = lr ? reinterpret_cast<const double*>(reinterpret_cast<const char*>(h->pri) + offsetof(DevPriors, lr_HIu)) + CPE_NX * CPE_NX : nullptr;
@@ -1084,6 +1087,7 @@ static void lm_iterate(cpe_handle* h, const LmParams& prm, int N, size_t Fw, siz
                                h->gbuf, h->Bbuf, h->costbuf, h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hlr, act, n_act, 2, nullptr, h->dgbuf, hiu, h->lr_window, *rg);
         });
         prof_end(h);
+        if (!back) return;
         prof_begin(h, 7);
         with_pb(h->pb, [&](auto pbc) {
             hipLaunchKernelGGL((k_lm_back<decltype(pbc)::value, true>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf,
@@ -1108,6 +1112,7 @@ static void lm_iterate(cpe_handle* h, const LmParams& prm, int N, size_t Fw, siz
                            h->Bbuf, h->costbuf, h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hlr, act, n_act, 2, sh.gx, h->dgbuf, hiu, h->lr_window);
     });
     prof_end(h);
+    if (!back) return;
     prof_begin(h, 7);
     with_pb(h->pb, [&](auto pbc) {
         hipLaunchKernelGGL((k_lm_back<decltype(pbc)::value>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf,
@@ -1999,6 +2004,177 @@ cpe_status cpe_eval_lm_step(cpe_handle* h, const cpe_kinetic_options* kopt, int3
     }
     HIPCHK(hipStreamSynchronize(h->stream));                // (hl is read by the copy above)
     return CPE_OK;
+}
+
+// ---- posterior covariance of the kinematic estimate (include/cpe.h; kernels in cpe_covariance.hip.inc) --------------------------------------
+// What every covariance entry refuses, before the device is touched: pb < 0 = the half-bandwidth is not known yet
+static cpe_status cov_check(const char* who, int pb, double ridge) {
+    if (!(ridge >= 0.0) || !std::isfinite(ridge)) return fail(CPE_BAD_ARG, std::string(who) + ": ridge must be finite and >= 0");
+    if (pb > 4)
+        return fail(CPE_BAD_ARG, std::string(who) + ": half-bandwidth " + std::to_string(pb) + " (motion-prior window above 4) is not supported by the covariance sweep");
+    return CPE_OK;
+}
+
+static cpe_status ensure_cov(cpe_handle* h, size_t F) {
+    const size_t n = F * (size_t)(h->pb + 1) * CPE_NX * CPE_NX;
+    if (n <= h->covG_n) return CPE_OK;
+    if (h->covG) { HIPCHK(hipStreamSynchronize(h->stream)); (void)hipFree(h->covG); h->covG = nullptr; h->covG_n = 0; }
+    HIPCHK(hipMalloc(&h->covG, sizeof(double) * n));
+    h->covG_n = n;
+    return CPE_OK;
+}
+
+// pre-pass + sweep over the factor columns Lsrc (recip: reciprocal diagonal, as in Lbuf); st: sequence states or null (all sequences)
+static void cov_launch(cpe_handle* h, int B, int N, const SeqState* st, const double* Lsrc, int recip, double* cov_diag, double* cov_off,
+                       const RaggedArgs* rg) {
+    const unsigned gf = (unsigned)((size_t)B * N);
+    auto go = [&](auto pbc) {
+        constexpr int PB = decltype(pbc)::value;
+        if (rg) {
+            hipLaunchKernelGGL((k_cov_prep<PB, true>), dim3(gf), dim3(WAVE), 0, h->stream, st, Lsrc, h->covG, N, recip, *rg);
+            hipLaunchKernelGGL((k_lm_selinv<PB, true>), dim3(B), dim3(COV_THREADS), 0, h->stream, st, h->covG, cov_diag, cov_off, N, *rg);
+        } else {
+            hipLaunchKernelGGL((k_cov_prep<PB>), dim3(gf), dim3(WAVE), 0, h->stream, st, Lsrc, h->covG, N, recip, RaggedArgs{});
+            hipLaunchKernelGGL((k_lm_selinv<PB>), dim3(B), dim3(COV_THREADS), 0, h->stream, st, h->covG, cov_diag, cov_off, N, RaggedArgs{});
+        }
+    };
+    if (h->pb == 3) go(std::integral_constant<int, 3>{}); else go(std::integral_constant<int, 4>{});
+}
+
+cpe_status cpe_covariance_supported(const cpe_priors* priors, double ridge) {
+    bool use_pri;
+    if (cpe_status s = check_priors(priors, &use_pri); s != CPE_OK) return s;
+    const int pb = use_pri && priors->lr_window > 3 ? priors->lr_window : 3;
+    if (cpe_status s = cov_check("cpe_covariance", pb, ridge); s != CPE_OK) return s;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(CPE_NO_DEVICE, "no HIP device: this library has no CPU fallback");
+    return CPE_OK;
+}
+
+cpe_status cpe_band_inverse(cpe_handle* h, int32_t B, int32_t N, const double* L, double* cov_diag, double* cov_off) {
+    if (!h || !L || !cov_diag) return fail(CPE_BAD_ARG, "null argument");
+    if (cpe_status s = cov_check("cpe_band_inverse", h->pb, 0.0); s != CPE_OK) return s;
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    HIPCHK(hipSetDevice(h->device));
+    if (cpe_status s = ensure_cov(h, F); s != CPE_OK) return s;
+    cov_launch(h, B, N, nullptr, L, 0, cov_diag, cov_off, nullptr);
+    HIPCHK(hipGetLastError());
+    return CPE_OK;
+}
+
+// cpe_covariance (model == nullptr) and cpe_covariance_ragged
+static cpe_status covariance_impl(cpe_handle* h, int32_t B, int32_t N, const int32_t* model, const int32_t* n_frames, const double* q,
+                                  const double* meas, const double* weight, double ridge, double* cov_diag, double* cov_off, double* cov_pos,
+                                  double* L, cpe_status* status) {
+    const char* who = model ? "cpe_covariance_ragged" : "cpe_covariance";
+    if (cpe_status s = cov_check(who, -1, ridge); s != CPE_OK) return s;
+    if (!h || !q || !meas || !weight || !cov_diag || !status || ((model == nullptr) != (n_frames == nullptr))) return fail(CPE_BAD_ARG, "null argument");
+    if (cpe_status s = cov_check(who, h->pb, ridge); s != CPE_OK) return s;
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    std::vector<int2> seq;
+    if (model) { if (cpe_status s = ragged_table(h, B, N, model, n_frames, seq); s != CPE_OK) return s; }
+    HIPCHK(hipSetDevice(h->device));
+    cpe_status s = ensure_ws(h, B, N);
+    if (s != CPE_OK) return s;
+    if ((s = ensure_cov(h, F)) != CPE_OK) return s;
+    RaggedArgs rgv{h->rseq, N, cams_max(h)};
+    const RaggedArgs* rg = model ? &rgv : nullptr;
+    if (model) HIPCHK(hipMemcpyAsync(h->rseq, seq.data(), sizeof(int2) * B, hipMemcpyHostToDevice, h->stream));     // (seq outlives the stream: it is drained below)
+    if ((s = state_reset(h, B, N, q, rg)) != CPE_OK) return s;
+    const DevModel& m = h->hm;
+    const int RING = h->pb + 1;
+    const size_t BB = (size_t)CPE_NX * CPE_NX, w = sizeof(double), LC = (size_t)RING * BB;
+    // a sequence without a factor, and every frame past a sequence's own, has all outputs zero
+    HIPCHK(hipMemsetAsync(cov_diag, 0, w * F * BB, h->stream));
+    if (cov_off) HIPCHK(hipMemsetAsync(cov_off, 0, w * F * h->pb * BB, h->stream));
+    if (cov_pos) HIPCHK(hipMemsetAsync(cov_pos, 0, w * F * m.L * 9, h->stream));
+    // the launches of a solve's first pass up to the factor, multipliers zero, at damping ridge in place of opts.lambda0
+    LmParams prm = lm_params(h, B, N);
+    prm.lambda0 = ridge;
+    const size_t ldsn = rg ? lds_normal_all(h) : lds_normal(m, h->gmm_k, h->gmm_dim);
+    lm_iterate(h, prm, N, F, ldsn, meas, weight, ShutterArgs{nullptr, nullptr, nullptr}, rg, 1, nullptr, nullptr, B, false);
+    cov_launch(h, B, N, h->st, h->Lbuf, 1, cov_diag, cov_off, rg);
+    if (cov_pos) {
+        // (k_marker_cov's arrays are a subset of k_frame_normal's, plus Sigma(n,n) and one int per (marker, column) item)
+        const size_t ldsm = lds_normal_all(h) + w * BB + sizeof(int) * (size_t)(CPE_MAX_MARKERS * CPE_MAX_MCOL);
+        if (rg) hipLaunchKernelGGL(k_marker_cov<true>, dim3((unsigned)F), dim3(WAVE), ldsm, h->stream, h->dm, h->st, N, F, h->qbuf, cov_diag, cov_pos, *rg);
+        else hipLaunchKernelGGL(k_marker_cov<>, dim3((unsigned)F), dim3(WAVE), ldsm, h->stream, h->dm, h->st, N, F, h->qbuf, cov_diag, cov_pos, RaggedArgs{});
+    }
+    if (L) {
+        if (rg) hipLaunchKernelGGL(k_cov_export<true>, dim3((unsigned)F), dim3(COV_THREADS), 0, h->stream, h->st, h->Lbuf, L, N, (int)LC, *rg);
+        else hipLaunchKernelGGL(k_cov_export<>, dim3((unsigned)F), dim3(COV_THREADS), 0, h->stream, h->st, h->Lbuf, L, N, (int)LC, RaggedArgs{});
+    }
+    HIPCHK(hipGetLastError());
+    std::vector<SeqState> hs((size_t)B);
+    HIPCHK(hipMemcpyAsync(hs.data(), h->st, sizeof(SeqState) * B, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    cpe_status worst = CPE_OK;
+    for (int b = 0; b < B; b++) {
+        status[b] = hs[b].status == 0 && hs[b].back_pending == 1 ? CPE_OK : CPE_NUMERICAL;
+        if (status[b] > worst) worst = status[b];
+    }
+    return worst;
+}
+
+cpe_status cpe_covariance(cpe_handle* h, int32_t B, int32_t N, const double* q, const double* meas, const double* weight, double ridge,
+                          double* cov_diag, double* cov_off, double* cov_pos, double* L, cpe_status* status) {
+    return covariance_impl(h, B, N, nullptr, nullptr, q, meas, weight, ridge, cov_diag, cov_off, cov_pos, L, status);
+}
+
+cpe_status cpe_covariance_ragged(cpe_handle* h, int32_t B, int32_t N_max, const int32_t* model, const int32_t* n_frames, const double* q,
+                                 const double* meas, const double* weight, double ridge, double* cov_diag, double* cov_off, double* cov_pos,
+                                 double* L, cpe_status* status) {
+    if (!model || !n_frames) return fail(CPE_BAD_ARG, "null argument");
+    return covariance_impl(h, B, N_max, model, n_frames, q, meas, weight, ridge, cov_diag, cov_off, cov_pos, L, status);
+}
+
+// host-pointer twins (stage through HBM)
+static cpe_status covariance_host_impl(cpe_handle* h, int32_t B, int32_t N, const int32_t* model, const int32_t* n_frames, const double* q,
+                                       const double* meas, const double* weight, double ridge, double* cov_diag, double* cov_off, double* cov_pos,
+                                       double* L, cpe_status* status) {
+    const char* who = model ? "cpe_covariance_ragged_host" : "cpe_covariance_host";
+    if (cpe_status s = cov_check(who, -1, ridge); s != CPE_OK) return s;
+    if (!h || !q || !meas || !weight || !cov_diag || !status) return fail(CPE_BAD_ARG, "null argument");
+    if (cpe_status s = cov_check(who, h->pb, ridge); s != CPE_OK) return s;
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    const DevModel& m = h->hm;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t nm = F * cams_max(h) * m.L, BB = (size_t)CPE_NX * CPE_NX, w = sizeof(double);
+    DevBuf dq_, dm_, dw_, od, oo, op, ol;
+    HIPCHK(dq_.alloc(F * m.nq)); HIPCHK(dm_.alloc(nm * 2)); HIPCHK(dw_.alloc(nm)); HIPCHK(od.alloc(F * BB));
+    if (cov_off) HIPCHK(oo.alloc(F * h->pb * BB));
+    if (cov_pos) HIPCHK(op.alloc(F * m.L * 9));
+    if (L) HIPCHK(ol.alloc(F * (h->pb + 1) * BB));
+    HIPCHK(hipMemcpyAsync(dq_.p, q, w * F * m.nq, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(dm_.p, meas, w * nm * 2, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(dw_.p, weight, w * nm, hipMemcpyHostToDevice, h->stream));
+    const cpe_status s = covariance_impl(h, B, N, model, n_frames, dq_.p, dm_.p, dw_.p, ridge, od.p, cov_off ? oo.p : nullptr, cov_pos ? op.p : nullptr,
+                                         L ? ol.p : nullptr, status);
+    if (s < 0) return s;
+    HIPCHK(hipMemcpyAsync(cov_diag, od.p, w * F * BB, hipMemcpyDeviceToHost, h->stream));
+    if (cov_off) HIPCHK(hipMemcpyAsync(cov_off, oo.p, w * F * h->pb * BB, hipMemcpyDeviceToHost, h->stream));
+    if (cov_pos) HIPCHK(hipMemcpyAsync(cov_pos, op.p, w * F * m.L * 9, hipMemcpyDeviceToHost, h->stream));
+    if (L) HIPCHK(hipMemcpyAsync(L, ol.p, w * F * (h->pb + 1) * BB, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return s;
+}
+
+cpe_status cpe_covariance_host(cpe_handle* h, int32_t B, int32_t N, const double* q, const double* meas, const double* weight, double ridge,
+                               double* cov_diag, double* cov_off, double* cov_pos, double* L, cpe_status* status) {
+    return covariance_host_impl(h, B, N, nullptr, nullptr, q, meas, weight, ridge, cov_diag, cov_off, cov_pos, L, status);
+}
+
+cpe_status cpe_covariance_ragged_host(cpe_handle* h, int32_t B, int32_t N_max, const int32_t* model, const int32_t* n_frames, const double* q,
+                                      const double* meas, const double* weight, double ridge, double* cov_diag, double* cov_off, double* cov_pos,
+                                      double* L, cpe_status* status) {
+    if (!model || !n_frames) return fail(CPE_BAD_ARG, "null argument");
+    return covariance_host_impl(h, B, N_max, model, n_frames, q, meas, weight, ridge, cov_diag, cov_off, cov_pos, L, status);
 }
 
 #ifdef CPE_LM_STAMPS

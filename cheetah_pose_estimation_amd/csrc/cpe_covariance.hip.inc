@@ -1,0 +1,391 @@
+// cpe_covariance.hip.inc -- posterior covariance of the kinematic estimate (include/cpe.h, cpe_covariance; DESIGN.md 2 "What is inverted").
+// Sigma = (H + ridge D)^-1 on its block band, by selected inversion (Takahashi recurrence) of the block Cholesky factor k_lm_step leaves in
+// Lbuf.  With T_n = L(n,n)^-1 and G_k = L(n+k,n) T_n (k = 1..PB), columns n = N-1 .. 0:
+//     Sigma(n+i,n) = - sum_k Sigma(n+i,n+k) G_k                       i = 1..PB   (Sigma(a,b) = Sigma(b,a)^T for a < b)
+//     Sigma(n,n)   = T_n^T T_n - sum_k G_k^T Sigma(n+k,n)
+// Every Sigma on the right lies inside the band.  Three kernels: k_cov_prep (frame-parallel: T, G, T^T T -- the whole factor is known up
+// front, so the 28-step triangular inverse is not part of the serial chain), k_lm_selinv (the serial sweep, one workgroup per sequence)
+// and k_marker_cov (3x3 covariance of every marker position).  No atomics; every sum has a fixed order.
+
+#define COV_THREADS 256
+
+// A sequence takes part when its evaluation was finite and k_lm_step factored its matrix (it then leaves back_pending = 1; the covariance
+// entry does not run k_lm_back).  st == nullptr (cpe_band_inverse): every sequence does.
+__device__ __forceinline__ bool cov_seq_ok(const SeqState* __restrict__ st, int b) {
+    return st == nullptr || (st[b].status == 0 && st[b].back_pending == 1);
+}
+
+// ---- pre-pass, one wave per frame.  Column n of the factor: block 0 = L(n,n), block i = L(n+i,n), [row * 28 + col].  `recip` != 0: the
+// diagonal of block 0 holds 1 / L[k][k] (Lbuf as k_lm_step writes it), else L[k][k] itself (the plain layout of cpe_eval_lm_step).  Both
+// forms go through the same arithmetic, r = 1 / d with d the true diagonal, so a factor exported by cpe_covariance and handed back to
+// cpe_band_inverse gives the same bits.  Output column n of Gbuf, same shape: block 0 = T^T T, block i = G_i (zero where n + i >= N).
+template <int PB, bool RAGGED = false>
+__global__ __launch_bounds__(WAVE) void k_cov_prep(const SeqState* __restrict__ st, const double* __restrict__ Lsrc, double* __restrict__ Gbuf,
+                                                   int NS, int recip, RaggedArgs rg = RaggedArgs{}) {
+    constexpr int RING = PB + 1, BB = NU * NU;
+    __shared__ double sL[RING * BB];
+    __shared__ double sT[BB];
+    __shared__ double sr[NU];
+    const int lane = threadIdx.x;
+    const int b = (int)(blockIdx.x / (unsigned)NS), n = (int)(blockIdx.x % (unsigned)NS);
+    int N = NS;
+    if constexpr (RAGGED) N = rg.seq[b].y;
+    if (n >= N || !cov_seq_ok(st, b)) return;                 // uniform
+    const size_t col = ((size_t)b * NS + n) * (size_t)(RING * BB);
+    const double* Lc = Lsrc + col;
+    double* Gc = Gbuf + col;
+    for (int t = lane; t < RING * BB; t += WAVE) sL[t] = Lc[t];
+    wave_lds_sync();
+    if (lane < NU) {
+        const double x = sL[lane * NU + lane];
+        const double d = recip ? 1.0 / x : x;
+        sr[lane] = 1.0 / d;
+    }
+    wave_lds_sync();
+    // T = L00^-1 by forward substitution, one column per lane: lanes 0..27 and 28..55 both hold columns 0..27 (each half takes every
+    // second row of the products below), lanes 56..63 shadow columns 0..7 and store nothing
+    const int c = lane % NU, hh = lane / NU;
+    double t[NU];
+#pragma unroll
+    for (int i = 0; i < NU; i++) {
+        double s = i == c ? 1.0 : 0.0;
+#pragma unroll
+        for (int k = 0; k < i; k++) s = fma(-sL[i * NU + k], t[k], s);
+        t[i] = s * sr[i];
+    }
+    if (hh == 0) {
+#pragma unroll
+        for (int k = 0; k < NU; k++) sT[k * NU + c] = t[k];
+    }
+    wave_lds_sync();
+    if (hh < 2) {
+        // (T^T T)[a][c] = sum_k T[k][a] T[k][c]: the same products in the same order for [a][c] and [c][a] -- bit-symmetric
+        for (int a = hh; a < NU; a += 2) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k < NU; k++) s = fma(sT[k * NU + a], t[k], s);
+            Gc[a * NU + c] = s;
+        }
+#pragma unroll
+        for (int i = 1; i <= PB; i++) {
+            const double* Li = sL + i * BB;
+            const bool in = n + i < N;
+            for (int r = hh; r < NU; r += 2) {
+                double s = 0.0;
+#pragma unroll
+                for (int k = 0; k < NU; k++) s = fma(Li[r * NU + k], t[k], s);
+                Gc[i * BB + r * NU + c] = in ? s : 0.0;
+            }
+        }
+    }
+}
+
+// ---- the serial sweep, one 256-thread workgroup per sequence, columns N-1 .. 0.  LDS: the window of Sigma as a ring over the frame index
+// mod PB + 1 (blk_slot: PB (PB + 1) / 2 blocks of the frames n+1 .. n+PB plus the PB + 1 blocks of column n under construction -- 6 + 4 at
+// PB = 3, 10 + 5 at PB = 4), the operands T^T T | G_1 .. G_PB of the column, and PB partial products of the diagonal block; blocks are
+// [28][LDB] doubles as k_lm_step keeps them.  The operands of column n-1 are requested into registers before column n is computed.
+// Block products by 4 x 4 register tiles on the vector ALU (DESIGN.md 4 has the reason): 49 PB tile jobs for the off-diagonal blocks, one
+// per thread, each the whole sum over k and m in that order; then 28 PB jobs (lower-triangle tile, k) for G_k^T Sigma(n+k,n), summed over
+// k in order by the thread that stores the element and its mirror -- Sigma(n,n) is exactly symmetric.
+template <int PB, bool RAGGED = false>
+__global__ __launch_bounds__(COV_THREADS, 1) void k_lm_selinv(const SeqState* __restrict__ st, const double* __restrict__ Gbuf,
+                                                              double* __restrict__ cov_diag, double* __restrict__ cov_off, int NS,
+                                                              RaggedArgs rg = RaggedArgs{}) {
+    constexpr int RING = PB + 1, NW = RING * (RING + 1) / 2, BB = NU * NU, COLD = RING * BB;
+    constexpr int NPF = (COLD + COV_THREADS - 1) / COV_THREADS;
+    constexpr int TPB = (NU / 4) * (NU / 4);                 // 49 tiles of a block
+    constexpr int LTT = (NU / 4) * (NU / 4 + 1) / 2;         // 28 tiles of its lower triangle
+    static_assert(PB >= 3 && PB <= 4 && TPB * PB <= COV_THREADS && LTT * PB <= COV_THREADS, "one tile job per thread");
+    __shared__ double Wn[NW * BLK];
+    __shared__ double Gs[RING * BLK];
+    __shared__ double Ps[PB * BLK];
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x;
+    int N = NS;
+    if constexpr (RAGGED) N = rg.seq[b].y;
+    if (!cov_seq_ok(st, b)) return;                          // uniform: the outputs of such a sequence stay zero
+    const double* Gb = Gbuf + (size_t)b * NS * COLD;
+    double* cd = cov_diag + (size_t)b * NS * BB;
+    double* co = cov_off ? cov_off + (size_t)b * NS * (size_t)(PB * BB) : nullptr;
+
+    for (int t = tid; t < NW * BLK; t += COV_THREADS) Wn[t] = 0.0;      // frames past the end: Sigma = 0
+    double pf[NPF];
+    auto fetch = [&](int n) {                                // (unconditional loads at a clamped index)
+        const double* g = Gb + (size_t)n * COLD;
+#pragma unroll
+        for (int j = 0; j < NPF; j++) { const int e = tid + COV_THREADS * j; pf[j] = g[e < COLD ? e : COLD - 1]; }
+    };
+    fetch(N - 1);
+    // this thread's jobs
+    const int ja_i = 1 + tid / TPB, ja_t = tid % TPB, ja_r = 4 * (ja_t / (NU / 4)), ja_c = 4 * (ja_t % (NU / 4));
+    const bool ja_on = tid < TPB * PB;
+    const int jb_k = 1 + tid / LTT, jb_t = tid % LTT;
+    int jb_tr = 0;
+    while ((jb_tr + 1) * (jb_tr + 2) / 2 <= jb_t) jb_tr++;
+    const int jb_r = 4 * jb_tr, jb_c = 4 * (jb_t - jb_tr * (jb_tr + 1) / 2);
+    const bool jb_on = tid < LTT * PB;
+
+    for (int n = N - 1; n >= 0; n--) {
+#pragma unroll
+        for (int j = 0; j < NPF; j++) {
+            const int e = tid + COV_THREADS * j;
+            if (e < COLD) { const int blk = e / BB, r = (e - blk * BB) / NU, c = e % NU; Gs[blk * BLK + r * LDB + c] = pf[j]; }
+        }
+        fetch(n > 0 ? n - 1 : 0);
+        lds_barrier();
+        // ---- off-diagonal blocks: Sigma(n+i,n) = - sum_k Sigma(n+i,n+k) G_k
+        if (ja_on) {
+            double acc[4][4];
+#pragma unroll
+            for (int x = 0; x < 4; x++)
+#pragma unroll
+                for (int y = 0; y < 4; y++) acc[x][y] = 0.0;
+#pragma unroll
+            for (int k = 1; k <= PB; k++) {
+                // Sigma(n+i,n+k) is stored as the block of (larger frame, smaller frame): read as it stands (k <= i) or transposed
+                const bool tr = k > ja_i;
+                const int hi = tr ? k : ja_i, lo = tr ? ja_i : k;
+                const double* A = Wn + blk_slot<RING>(n + hi, n + lo) * BLK + ja_r * (tr ? 1 : LDB);
+                const int sx = tr ? 1 : LDB, sm = tr ? LDB : 1;
+                const double* G = Gs + k * BLK + ja_c;
+#pragma unroll 4
+                for (int m = 0; m < NU; m++) {
+                    double av[4], bv[4];
+#pragma unroll
+                    for (int x = 0; x < 4; x++) av[x] = A[x * sx + m * sm];
+#pragma unroll
+                    for (int y = 0; y < 4; y++) bv[y] = G[m * LDB + y];
+#pragma unroll
+                    for (int x = 0; x < 4; x++)
+#pragma unroll
+                        for (int y = 0; y < 4; y++) acc[x][y] = fma(-av[x], bv[y], acc[x][y]);
+                }
+            }
+            double* O = Wn + blk_slot<RING>(n + ja_i, n) * BLK + ja_r * LDB + ja_c;
+#pragma unroll
+            for (int x = 0; x < 4; x++)
+#pragma unroll
+                for (int y = 0; y < 4; y++) O[x * LDB + y] = acc[x][y];
+            if (co) {
+                double* Og = co + ((size_t)n * PB + (ja_i - 1)) * BB + ja_r * NU + ja_c;
+#pragma unroll
+                for (int x = 0; x < 4; x++)
+#pragma unroll
+                    for (int y = 0; y < 4; y++) Og[x * NU + y] = acc[x][y];
+            }
+        }
+        lds_barrier();
+        // ---- diagonal block, part k: G_k^T Sigma(n+k,n) on the tiles of the lower triangle
+        if (jb_on) {
+            double acc[4][4];
+#pragma unroll
+            for (int x = 0; x < 4; x++)
+#pragma unroll
+                for (int y = 0; y < 4; y++) acc[x][y] = 0.0;
+            const double* G = Gs + jb_k * BLK + jb_r;
+            const double* S = Wn + blk_slot<RING>(n + jb_k, n) * BLK + jb_c;
+#pragma unroll 4
+            for (int m = 0; m < NU; m++) {
+                double av[4], bv[4];
+#pragma unroll
+                for (int x = 0; x < 4; x++) av[x] = G[m * LDB + x];
+#pragma unroll
+                for (int y = 0; y < 4; y++) bv[y] = S[m * LDB + y];
+#pragma unroll
+                for (int x = 0; x < 4; x++)
+#pragma unroll
+                    for (int y = 0; y < 4; y++) acc[x][y] = fma(av[x], bv[y], acc[x][y]);
+            }
+            double* P = Ps + (jb_k - 1) * BLK + jb_r * LDB + jb_c;
+#pragma unroll
+            for (int x = 0; x < 4; x++)
+#pragma unroll
+                for (int y = 0; y < 4; y++) P[x * LDB + y] = acc[x][y];
+        }
+        lds_barrier();
+        // ---- Sigma(n,n) = T^T T - (part 1 + part 2 + ...), from its lower triangle, mirrored
+        {
+            double* D = Wn + blk_slot<RING>(n, n) * BLK;
+            double* Dg = cd + (size_t)n * BB;
+            for (int e = tid; e < BB; e += COV_THREADS) {
+                const int a = e / NU, c = e - a * NU;
+                if (c <= a) {
+                    double s = Ps[a * LDB + c];
+#pragma unroll
+                    for (int k = 1; k < PB; k++) s += Ps[k * BLK + a * LDB + c];
+                    const double v = Gs[a * LDB + c] - s;
+                    D[a * LDB + c] = v; D[c * LDB + a] = v;
+                    Dg[a * NU + c] = v; Dg[c * NU + a] = v;
+                }
+            }
+        }
+        lds_barrier();          // the column is complete; Gs and Ps are free for the next one
+    }
+}
+
+// ---- marker covariance, one wave per frame: cov_pos[l] = P_l Sigma(n,n) P_l^T with P_l = d p_l / d u, the reduced marker columns Dp of
+// k_frame_normal (same tables, same device functions, same order of the terms; the sums into Dp run per item in list order here -- one
+// lane per item -- so no LDS atomics are needed).  State: the current buffer of the sequence, as k_frame_normal left it.
+// dynamic LDS: state | sin / cos | leg sin / cos | trunk R, dR | dynamic vectors | S rows | Dp | Sigma(n,n) | first term of every item (int)
+template <bool RAGGED = false>
+__global__ __launch_bounds__(WAVE) void k_marker_cov(const DevModel* __restrict__ M, const SeqState* __restrict__ st, int N, size_t n_frames,
+                                                     const double* __restrict__ qbuf, const double* __restrict__ cov_diag,
+                                                     double* __restrict__ cov_pos, RaggedArgs rg = RaggedArgs{}) {
+    extern __shared__ double smem[];
+    const int lane = threadIdx.x;
+    const int b = (int)(blockIdx.x / (unsigned)N);
+    if constexpr (RAGGED) {
+        const int2 rs = rg.seq[b];
+        if ((int)(blockIdx.x % (unsigned)N) >= rs.y) return;
+        M += rs.x;
+    }
+    if (!cov_seq_ok(st, b)) return;
+    const size_t f = (size_t)b * N + blockIdx.x % (unsigned)N;
+    const int buf = st[b].cur;
+    const int nq = M->nq, nl = M->nl, L = M->L, nrev = M->nrev, ns = M->ns, svn = M->sv_n, mct = M->mc_total;
+    double* sq = smem;
+    double* sal = sq + nq;
+    double* ssc = sal + nrev;
+    double* ssa = ssc + 6 * nl;
+    double* sR = ssa + 2 * nrev;
+    double* sdyn = sR + 36 * M->n_trunk;
+    double* sSv = sdyn + 3 * svn;
+    double* sDp = sSv + CPE_MAX_SCOL * M->n_srow;
+    double* sSig = sDp + 3 * mct;
+    int* sBeg = reinterpret_cast<int*>(sSig + NU * NU);       // first term of every item of the flat list
+
+    const int4 fw = *reinterpret_cast<const int4*>(M->fn_lane[lane]);
+    const int svl = lane < CPE_MAX_SDYN ? lane : 0;
+    double svv[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) { svv[i][0] = M->sv_vec[svl][i][0]; svv[i][1] = M->sv_vec[svl][i][1]; svv[i][2] = M->sv_vec[svl][i][2]; }
+    const int hj_n = M->hj_n, hk_n = M->hk_n;
+    const int2 hkw = *reinterpret_cast<const int2*>(M->hk_w[lane]);
+    const double* stf = qbuf + (size_t)buf * n_frames * ns + f * ns;
+    for (int t = lane; t < ns; t += WAVE) sq[t] = stf[t];
+    for (int t = lane; t < NU * NU; t += WAVE) sSig[t] = cov_diag[f * (size_t)(NU * NU) + t];
+    wave_lds_sync();
+    wave_sincos(M, sq, ssc, lane);
+    if (lane < nrev) { double s_, c_; sincos(sal[lane], &s_, &c_); ssa[2 * lane] = s_; ssa[2 * lane + 1] = c_; }
+    wave_lds_sync();
+    // hooke joints: phi of the tails in closed form (as k_frame_normal)
+    for (int level = 0; level < 2; level++) {
+        if (lane < hj_n && ((fw.x >> 16) & 1) == level) {
+            const int p = fw.x & 255, c = (fw.x >> 8) & 255;
+            double a[3];
+            rot_ycol(ssc + 6 * p, a);
+            const double st_ = ssc[6 * c + 2], ct = ssc[6 * c + 3], sp = ssc[6 * c + 4], cp = ssc[6 * c + 5];
+            const double num = a[0] * st_ * cp + a[1] * st_ * sp + a[2] * ct;
+            const double den = a[1] * cp - a[0] * sp;
+            const double hyp = sqrt(num * num + den * den);
+            sq[3 + 3 * c] = atan2(num, den);
+            ssc[6 * c] = num / hyp; ssc[6 * c + 1] = den / hyp;
+        }
+        wave_lds_sync();
+    }
+    if (lane < 4 * M->n_trunk) rot_kind(ssc + 6 * fw.y, lane & 3, sR + 9 * lane);
+    for (int t = WAVE + lane; t < 4 * M->n_trunk; t += WAVE) rot_kind(ssc + 6 * M->trunk_link[t >> 2], t & 3, sR + 9 * t);
+    // dynamic body-frame vectors of the leg markers
+    if (lane < svn) {
+        double d0 = 0.0, d1 = 0.0, d2 = 0.0;
+        if ((fw.w & 3) == 0) {
+            const int cnt = (fw.w >> 2) & 3;
+#pragma unroll
+            for (int i = 0; i < 3; i++) {
+                const int r = (fw.w >> (4 + 6 * i)) & 63;
+                const double sa = ssa[2 * r], ca = ssa[2 * r + 1];
+                if (i < cnt) { d0 += ca * svv[i][0] + sa * svv[i][2]; d1 += svv[i][1]; d2 += -sa * svv[i][0] + ca * svv[i][2]; }
+            }
+        } else {
+            const int r = (fw.w >> 4) & 63;
+            const double sa = ssa[2 * r], ca = ssa[2 * r + 1];
+            d0 = -sa * svv[0][0] + ca * svv[0][2]; d2 = -ca * svv[0][0] - sa * svv[0][2];
+        }
+        sdyn[3 * lane] = d0; sdyn[3 * lane + 1] = d1; sdyn[3 * lane + 2] = d2;
+    }
+    wave_lds_sync();
+    // S rows of the hooke joints (tails): d phi_c / d(independent), level by level
+    for (int level = 0; level < 2; level++) {
+        if (lane < hk_n && ((hkw.x >> 16) & 1) == level) {
+            const double* Rp = sR + 36 * (hkw.x & 63); const double* Rc = sR + 36 * ((hkw.x >> 6) & 63);
+            const double y0 = Rp[1], y1 = Rp[4], y2 = Rp[7];
+            const double z0 = Rc[2], z1 = Rc[5], z2 = Rc[8];
+            const double* Dcphi = Rc + 9;
+            const double gphi = y0 * Dcphi[2] + y1 * Dcphi[5] + y2 * Dcphi[8];
+            const int kind = (hkw.x >> 12) & 3, ang = (hkw.x >> 14) & 3;
+            double direct = 0.0;
+            if (kind == 0) { const double* D = Rc + 9 * (1 + ang); direct = y0 * D[2] + y1 * D[5] + y2 * D[8]; }
+            else if (kind == 1) { const double* D = Rp + 9 * (1 + ang); direct = D[1] * z0 + D[4] * z1 + D[7] * z2; }
+            double val = -direct / gphi;
+            const int ch = (hkw.y & 0xFFFF) - 1;
+            if (ch >= 0) {
+                const double* Dpphi = Rp + 9;
+                const double t0 = -(Dpphi[1] * z0 + Dpphi[4] * z1 + Dpphi[7] * z2) / gphi;
+                val += t0 * sSv[ch];
+            }
+            sSv[hkw.y >> 16] = val;
+        }
+        wave_lds_sync();
+    }
+    // reduced marker columns: the terms of one item (marker, column) sit next to each other in M->tl, in item order; a first pass marks where
+    // every item's terms begin, then item t sums its own terms in list order
+    const int ntl = M->tl_n;
+    for (int t = lane; t < mct; t += WAVE) sBeg[t] = ntl;
+    wave_lds_sync();
+    for (int e = lane; e < ntl; e += WAVE) {
+        const int it = M->tl[e].w0 & 1023;
+        if (e == 0 || (M->tl[e - 1].w0 & 1023) != it) sBeg[it] = e;
+    }
+    wave_lds_sync();
+    for (int t = lane; t < mct; t += WAVE) {
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+        for (int e = sBeg[t]; e < ntl; e++) {
+            const int w0 = M->tl[e].w0;
+            if ((w0 & 1023) != t) break;
+            const int si = ((w0 >> 10) & 1023) - 1, vd = ((w0 >> 20) & 1023) - 1, moff = M->tl[e].moff;
+            const double v0 = vd < 0 ? M->tl[e].v[0] : sdyn[3 * vd], v1 = vd < 0 ? M->tl[e].v[1] : sdyn[3 * vd + 1], v2 = vd < 0 ? M->tl[e].v[2] : sdyn[3 * vd + 2];
+            const double z = si < 0 ? 1.0 : sSv[si];
+            double p0 = v0, p1 = v1, p2 = v2;
+            if (moff >= 0) {
+                const double* D = sR + moff;
+                p0 = D[0] * v0 + D[1] * v1 + D[2] * v2; p1 = D[3] * v0 + D[4] * v1 + D[5] * v2; p2 = D[6] * v0 + D[7] * v1 + D[8] * v2;
+            }
+            s0 += z * p0; s1 += z * p1; s2 += z * p2;
+        }
+        sDp[3 * t] = s0; sDp[3 * t + 1] = s1; sDp[3 * t + 2] = s2;
+    }
+    wave_lds_sync();
+    // cov_pos[l][a][c] = sum_i sum_j Dp_i[a] Sigma[col_i][col_j] Dp_j[c] over the marker's columns; lane = (marker, entry of the lower
+    // triangle), the mirror is stored with it
+    for (int t = lane; t < 6 * L; t += WAVE) {
+        const int l = t / 6, e = t - 6 * l;
+        const int a = e < 1 ? 0 : (e < 3 ? 1 : 2), c = e - a * (a + 1) / 2;
+        const int off = M->mcol_off[l], nc = M->mcol_n[l];
+        double s = 0.0;
+        for (int i = 0; i < nc; i++) {
+            const int ci = M->mcol[l][i];
+            double w = 0.0;
+            for (int j = 0; j < nc; j++) w = fma(sSig[ci * NU + M->mcol[l][j]], sDp[3 * (off + j) + c], w);
+            s = fma(sDp[3 * (off + i) + a], w, s);
+        }
+        double* o = cov_pos + (f * (size_t)L + l) * 9;
+        o[3 * a + c] = s; o[3 * c + a] = s;
+    }
+}
+
+// ---- the factor cpe_covariance used, in the plain layout of cpe_eval_lm_step (true diagonal); zero for a sequence without a factor and past
+// a sequence's own frames.  One workgroup per frame.
+template <bool RAGGED = false>
+__global__ __launch_bounds__(COV_THREADS) void k_cov_export(const SeqState* __restrict__ st, const double* __restrict__ Lbuf, double* __restrict__ L,
+                                                            int NS, int cold, RaggedArgs rg = RaggedArgs{}) {
+    const int b = (int)(blockIdx.x / (unsigned)NS), n = (int)(blockIdx.x % (unsigned)NS);
+    int N = NS;
+    if constexpr (RAGGED) N = rg.seq[b].y;
+    const bool ok = n < N && cov_seq_ok(st, b);
+    const size_t col = (size_t)blockIdx.x * (size_t)cold;
+    for (int t = threadIdx.x; t < cold; t += COV_THREADS) {
+        double v = 0.0;
+        if (ok) { v = Lbuf[col + t]; if (t < NU * NU && t / NU == t % NU) v = 1.0 / v; }
+        L[col + t] = v;
+    }
+}

@@ -319,6 +319,9 @@ class CheetahEstimator:
     enable_eom_slack: bool = True
     bound_eom_error: Optional[Tuple[float, float]] = None
     kinetic: Optional[dict] = None          # node forces of the last estimate_kinetics (tau, lam, grf, slack, stance)
+    # estimate_kinematics(uncertainty=True): dict(cov_u [N, 28, 28], u_std [N, 28], positions_cov [N, L, 3, 3], positions_std [N, L, 3], ridge) --
+    # the marginal posterior covariance of every frame's reduced coordinates and marker positions (cpe_covariance); None where it does not exist
+    uncertainty: Optional[dict] = None
 
     def get_objective_cost(self) -> float:
         return float(self.result["stats"][0].cost) if self.result else float("nan")
@@ -572,9 +575,27 @@ def _kin_prepare(est: CheetahEstimator, monocular_constraints: bool, disable_pos
     return q_init, opts, pri
 
 
+def _uncertainty_of(cov: dict, b: int, ridge: float) -> Optional[dict]:
+    """est.uncertainty of sequence b from a covariance_host / covariance_ragged_host result (None where the matrix has no Cholesky factor)"""
+    if cov["seq_status"][b] != abi.OK:
+        return None
+    cu, cp = np.ascontiguousarray(cov["cov_diag"][b]), np.ascontiguousarray(cov["cov_pos"][b])
+    return dict(cov_u=cu, u_std=np.sqrt(np.diagonal(cu, axis1=1, axis2=2)), positions_cov=cp, positions_std=np.sqrt(np.diagonal(cp, axis1=2, axis2=3)),
+                ridge=float(ridge))
+
+
+def _check_uncertainty(est: CheetahEstimator, pri: Optional[abi.Priors], ridge: float) -> None:
+    """uncertainty=True: what is refused before anything is solved"""
+    if est.params.enable_shutter_delay_estimation and est.scene.cam_idx is None:
+        raise NotImplementedError("uncertainty together with shutter-delay estimation: the covariance is that of the kinematic objective without the "
+                                  "shutter displacement (cpe_covariance); the delays would be treated as known")
+    _lib.covariance_supported(pri, ridge)          # raises with the library's reason: negative ridge, motion-prior window above 4
+
+
 def _kin_finish(est: CheetahEstimator, h, res: dict, seconds: float, solver_output: bool, monocular_constraints: bool,
-                out_dir_prefix: Optional[str]) -> bool:
-    """what estimate_kinematics does after the solver call (acinoset_opt.py:619-634): centre of mass, costs, files.  `res` holds ONE sequence."""
+                out_dir_prefix: Optional[str], uncertainty: Optional[Tuple[Optional[dict], float]] = None) -> bool:
+    """what estimate_kinematics does after the solver call (acinoset_opt.py:619-634): centre of mass, costs, files.  `res` holds ONE sequence.
+    uncertainty: None (not asked for), or (est.uncertainty of this sequence or None, ridge): stored, and written as uncertainty.npz beside fte.pickle."""
     params, scene = est.params, est.scene
     N = params.end_frame - params.start_frame
     est.opt_time_s = seconds
@@ -598,7 +619,16 @@ def _kin_finish(est: CheetahEstimator, h, res: dict, seconds: float, solver_outp
         fname = f"fte_kinematic{'_gt' if params.hand_labeled_data else ''}"
         fname = fname if scene.cam_idx is None or monocular_constraints else "fte_kinematic_orig"
         fname = fname if scene.cam_idx is None else f"{fname}_{scene.cam_idx}"    # acinoset_opt.py:626-628
-        est.save(fname, out_dir_prefix=out_dir_prefix)
+        out_dir = est.save(fname, out_dir_prefix=out_dir_prefix)
+        if uncertainty is not None:
+            est.uncertainty = uncertainty[0]
+            if est.uncertainty is None:
+                print(f"uncertainty: none for {est.name}: the Gauss-Newton matrix has no Cholesky factor at ridge {uncertainty[1]:g} "
+                      "(the data leave a coordinate undetermined; a positive uncertainty_ridge regularises it)")
+            else:
+                np.savez(os.path.join(out_dir, "uncertainty.npz"), **est.uncertainty)
+    elif uncertainty is not None:
+        est.uncertainty = None
     return ok
 
 
@@ -606,12 +636,17 @@ def estimate_kinematics(estimator: CheetahEstimator, solver_output: bool = True,
                         disable_pose_prior: bool = False, disable_motion_prior: bool = False,
                         pose_model_num_components: int = 5, motion_model_window_size: int = 4,
                         motion_model_sparse_solution: bool = True, out_dir_prefix: Optional[str] = None,
-                        q_init: Optional[np.ndarray] = None, options: Optional[abi.Options] = None) -> bool:
-    """Same signature as acinoset_opt.estimate_kinematics (acinoset_opt.py:539-547) plus two optional
-    keyword arguments.  Returns True when the solve converged (IPOPT `ok`+`optimal` in the reference)."""
+                        q_init: Optional[np.ndarray] = None, options: Optional[abi.Options] = None, uncertainty: bool = False,
+                        uncertainty_ridge: float = 0.0) -> bool:
+    """Same signature as acinoset_opt.estimate_kinematics (acinoset_opt.py:539-547) plus optional
+    keyword arguments.  Returns True when the solve converged (IPOPT `ok`+`optimal` in the reference).
+    uncertainty=True: after a converged solve the posterior covariance of the estimate (cpe_covariance at the stored q, damping
+    uncertainty_ridge) goes to est.uncertainty and to uncertainty.npz beside fte.pickle; the return value stays that of the solve."""
     est, params, scene, sk = estimator, estimator.params, estimator.scene, estimator.skeleton
     q_init, opts, pri = _kin_prepare(est, monocular_constraints, disable_pose_prior, disable_motion_prior, pose_model_num_components,
                                      motion_model_window_size, motion_model_sparse_solution, q_init, options)
+    if uncertainty:
+        _check_uncertainty(est, pri, uncertainty_ridge)
     h = _lib.Handle(sk, est.cams, opts, pri, device=est.device)
     try:
         t0 = time()
@@ -622,7 +657,12 @@ def estimate_kinematics(estimator: CheetahEstimator, solver_output: bool = True,
         else:
             res = h.solve_host(q_init[None], est.meas[None], est.weight[None])
             est.shutter_delay = None
-        return _kin_finish(est, h, res, time() - t0, solver_output, monocular_constraints, out_dir_prefix)
+        dt = time() - t0
+        unc = None
+        if uncertainty:
+            cov = h.covariance_host(res["q"], est.meas[None], est.weight[None], uncertainty_ridge) if res["stats"][0].status == abi.OK else None
+            unc = (None if cov is None else _uncertainty_of(cov, 0, uncertainty_ridge), uncertainty_ridge)
+        return _kin_finish(est, h, res, dt, solver_output, monocular_constraints, out_dir_prefix, uncertainty=unc)
     finally:
         h.close()
 
@@ -640,7 +680,8 @@ def ragged_group_key(sk: abi.Skeleton, opts: abi.Options, pri: Optional[abi.Prio
 
 def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_output: bool = False, monocular_constraints: bool = False,
                               disable_pose_prior: bool = False, disable_motion_prior: bool = False, out_dir_prefix: Optional[str] = None,
-                              options: Optional[abi.Options] = None, ragged: bool = False) -> List[bool]:
+                              options: Optional[abi.Options] = None, ragged: bool = False, uncertainty: bool = False,
+                              uncertainty_ridge: float = 0.0) -> List[bool]:
     """estimate_kinematics for MANY sequences at once: the loop of run_dataset.py:1145-1196 (`for seq in dataset: init_trajectory; estimate_kinematics`)
     as batched launches.  Sequences that share a skeleton, a camera rig, a length and a frame rate go through ONE solver handle and ONE cpe_solve
     call (B = the group's size: the GPU solves thousands of sequences per second batched, one at a time it is latency-bound at 7 - 30 ms each);
@@ -649,18 +690,23 @@ def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_out
     estimator, in order.
     ragged=True: sequences need only share the skeleton's shape, the batch-level solver options, the priors and the device (ragged_group_key);
     each group is ONE cpe_solve_ragged call over a Handle.multi of its distinct (skeleton, rig, options) models, whatever the lengths.  Every
-    sequence's results are bit-equal to those of ragged=False."""
+    sequence's results are bit-equal to those of ragged=False.
+    uncertainty=True: as in estimate_kinematics, one cpe_covariance (ragged: cpe_covariance_ragged) call per group on the group's handle; every
+    sequence's est.uncertainty and uncertainty.npz are bit-equal to those of its own estimate_kinematics call."""
     ests = list(estimators)
     out: List[Optional[bool]] = [None] * len(ests)
     groups: Dict[tuple, List[int]] = {}
     prepared = {}
     for i, est in enumerate(ests):
         if est.params.enable_shutter_delay_estimation and est.scene.cam_idx is None:
-            out[i] = estimate_kinematics(est, solver_output, monocular_constraints, disable_pose_prior, disable_motion_prior, out_dir_prefix=out_dir_prefix, options=options)
+            out[i] = estimate_kinematics(est, solver_output, monocular_constraints, disable_pose_prior, disable_motion_prior, out_dir_prefix=out_dir_prefix, options=options,
+                                         uncertainty=uncertainty, uncertainty_ridge=uncertainty_ridge)
             continue
         q_init, opts, pri = _kin_prepare(est, monocular_constraints, disable_pose_prior, disable_motion_prior, 5, 4, True, None,
                                          None if options is None else _copy_options(options))
         prepared[i] = (q_init, opts, pri)
+        if uncertainty:
+            _check_uncertainty(est, pri, uncertainty_ridge)
         if ragged:
             key = ragged_group_key(est.skeleton, opts, pri, est.device)
         else:
@@ -669,7 +715,8 @@ def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_out
         groups.setdefault(key, []).append(i)
     if ragged:
         for idx in groups.values():
-            _solve_ragged_group(ests, idx, prepared, out, solver_output, monocular_constraints, out_dir_prefix)
+            _solve_ragged_group(ests, idx, prepared, out, solver_output, monocular_constraints, out_dir_prefix,
+                                uncertainty_ridge if uncertainty else None)
         return [bool(v) for v in out]
     for idx in groups.values():
         e0 = ests[idx[0]]
@@ -679,11 +726,15 @@ def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_out
             t0 = time()
             res = h.solve_host(np.stack([prepared[i][0] for i in idx]), np.stack([ests[i].meas for i in idx]), np.stack([ests[i].weight for i in idx]))
             dt = (time() - t0) / len(idx)                                            # processing_time_s of a sequence: its share of the batched solve
+            cov = None
+            if uncertainty:
+                cov = h.covariance_host(res["q"], np.stack([ests[i].meas for i in idx]), np.stack([ests[i].weight for i in idx]), uncertainty_ridge)
             for b, i in enumerate(idx):
                 one = {k: (v[b:b + 1] if isinstance(v, np.ndarray) else v) for k, v in res.items() if k not in ("stats", "status")}
                 one["stats"] = [res["stats"][b]]; one["status"] = res["stats"][b].status
                 ests[i].shutter_delay = None
-                out[i] = _kin_finish(ests[i], h, one, dt, solver_output, monocular_constraints, out_dir_prefix)
+                unc = None if cov is None else (_uncertainty_of(cov, b, uncertainty_ridge), uncertainty_ridge)
+                out[i] = _kin_finish(ests[i], h, one, dt, solver_output, monocular_constraints, out_dir_prefix, uncertainty=unc)
         finally:
             h.close()
     return [bool(v) for v in out]
@@ -693,7 +744,7 @@ def _model_bytes(est: CheetahEstimator, opts: abi.Options) -> bytes:
     return _struct_bytes(est.skeleton) + b"".join(_struct_bytes(est.cams[c]) for c in range(len(est.cams))) + _struct_bytes(opts)
 
 
-def _solve_ragged_group(ests, idx, prepared, out, solver_output, monocular_constraints, out_dir_prefix) -> None:
+def _solve_ragged_group(ests, idx, prepared, out, solver_output, monocular_constraints, out_dir_prefix, uncertainty_ridge: Optional[float] = None) -> None:
     """estimate_kinematics_batch(ragged=True) for one group: one model per distinct (skeleton, rig, options), one cpe_solve_ragged call, then every
     sequence's centre of mass, costs and files through _kin_finish with a plain handle of its own model (forward kinematics of that skeleton)"""
     models: Dict[bytes, int] = {}
@@ -712,6 +763,9 @@ def _solve_ragged_group(ests, idx, prepared, out, solver_output, monocular_const
         t0 = time()
         res = h.solve_ragged_host([prepared[i][0] for i in idx], [ests[i].meas for i in idx], [ests[i].weight for i in idx], of)
         dt = (time() - t0) / len(idx)                                                # processing_time_s of a sequence: its share of the batched solve
+        cov = None
+        if uncertainty_ridge is not None:                                            # (uncertainty=True) at the stored q of every sequence, same handle
+            cov = h.covariance_ragged_host(res["q"], [ests[i].meas for i in idx], [ests[i].weight for i in idx], of, uncertainty_ridge)
         for b, i in enumerate(idx):
             one = {k: res[k][b][None] for k in ("q", "dq", "ddq", "positions", "meas_err")}
             one["stats"] = [res["stats"][b]]; one["status"] = res["stats"][b].status
@@ -719,7 +773,8 @@ def _solve_ragged_group(ests, idx, prepared, out, solver_output, monocular_const
                 r = reps[of[b]]
                 fk[of[b]] = _lib.Handle(ests[r].skeleton, ests[r].cams, prepared[r][1], None, device=dev)
             ests[i].shutter_delay = None
-            out[i] = _kin_finish(ests[i], fk[of[b]], one, dt, solver_output, monocular_constraints, out_dir_prefix)
+            unc = None if cov is None else (_uncertainty_of(cov, b, uncertainty_ridge), uncertainty_ridge)
+            out[i] = _kin_finish(ests[i], fk[of[b]], one, dt, solver_output, monocular_constraints, out_dir_prefix, uncertainty=unc)
     finally:
         h.close()
         for f in fk.values():

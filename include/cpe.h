@@ -549,6 +549,45 @@ cpe_status cpe_eval_lm_step(cpe_handle* h, const cpe_kinetic_options* kopt, int3
                             const double* weight, const int32_t* stance, double lam, double* g, double* dg, double* L, double* delta, double* state,
                             double* seq);
 
+/* ---- posterior covariance of the kinematic estimate ("What is inverted").  The reference returns one trajectory and no measure
+ * of how well the data determine it (IPOPT's reduced Hessian is never asked for, acinoset_opt.py:611-617).  Here
+ *     Sigma = (H + ridge D)^-1      on its block band,
+ * H = the Gauss-Newton matrix of cpe_solve's objective in the 28 reduced coordinates per frame (measurement, constant-acceleration, bound-penalty,
+ * pose-prior and motion-prior terms) exactly as the first LM pass of cpe_solve assembles it at q, D = max(diag H, floor) with cpe_eval_lm_step's
+ * floors.  Sigma comes from the block Cholesky factor of that pass by selected inversion (Takahashi recurrence); no dense inverse is formed.
+ * Named deviations: (scale) the objective is taken as the negative log posterior as it stands, cost_scale plays no part; (bounds) multipliers are
+ * zero: a bound violated at q contributes its penalty curvature, a bound that is met nothing -- the Laplace approximation of the unbounded posterior;
+ * (robust loss) the curvature is the solver's PSD weight (opts.curvature), so redescended outliers carry no information; (coordinates) the reduced
+ * ones: trunk entries are Euler angles or metres, leg entries the rotation about the body's y axis (cpe_independent_dofs names them).
+ * Kinematic objective only (no physics-based model, no shutter displacement).  Every covariance entry refuses with CPE_BAD_ARG, before the device
+ * is touched and with the reason in cpe_last_error(): ridge < 0 or not finite; a handle whose half-bandwidth is above 4 (motion-prior windows 5, 6). */
+/* the refusals above for a handle that cpe_create would build with `priors` (NULL = none), without a handle: CPE_BAD_ARG, else CPE_NO_DEVICE
+ * where no GPU is visible, else CPE_OK */
+cpe_status cpe_covariance_supported(const cpe_priors* priors, double ridge);
+/* Building block: selected inverse of a block-banded Cholesky factor.  Device pointers.  L [B][N][pb+1][28][28] in cpe_eval_lm_step's layout
+ * (block [n][i] = block (n + i, n) of the lower factor, row-major, true diagonal; blocks with n + i >= N are not read).  cov_diag [B][N][28][28] =
+ * Sigma(n, n), exactly symmetric; cov_off [B][N][pb][28][28] (may be NULL): block [n][i-1] = Sigma(n + i, n), zero where n + i >= N. */
+cpe_status cpe_band_inverse(cpe_handle* h, int32_t B, int32_t N, const double* L, double* cov_diag, double* cov_off);
+/* Sigma at Euler q [B][N][nq]: the launches of a solve's first pass up to the factor (cold start, multipliers zero, as cpe_eval_lm_step) at damping
+ * ridge >= 0, then the sweep.  Device pointers except status.  cov_diag, cov_off as above; cov_pos [B][N][L][3][3] (may be NULL) = P_l Sigma(n,n) P_l^T,
+ * P_l = d marker_l / d u: the covariance of every marker position in metres^2; L (may be NULL) = the factor used, in cpe_band_inverse's layout (cov_diag
+ * and cov_off are bit-equal to cpe_band_inverse of it).  status [B], HOST: CPE_OK, or CPE_NUMERICAL where the evaluation is not finite or the matrix
+ * has no Cholesky factor at that ridge -- all outputs of such a sequence are zero; the damping is never raised silently.  Returns the worst status.
+ * Results are reproducible bit for bit (no atomics in the sweep), and a sequence's outputs do not depend on its batch. */
+cpe_status cpe_covariance(cpe_handle* h, int32_t B, int32_t N, const double* q, const double* meas, const double* weight, double ridge,
+                          double* cov_diag, double* cov_off, double* cov_pos, double* L, cpe_status* status);
+/* the same for sequences of their own length and model, in cpe_solve_ragged's layout (N_max frames, C_max cameras; model, n_frames HOST); every
+ * output past a sequence's frames is 0.0 */
+cpe_status cpe_covariance_ragged(cpe_handle* h, int32_t B, int32_t N_max, const int32_t* model /*[B] host*/, const int32_t* n_frames /*[B] host*/,
+                                 const double* q, const double* meas, const double* weight, double ridge, double* cov_diag, double* cov_off,
+                                 double* cov_pos, double* L, cpe_status* status);
+/* host-pointer twins (stage through HBM) */
+cpe_status cpe_covariance_host(cpe_handle* h, int32_t B, int32_t N, const double* q, const double* meas, const double* weight, double ridge,
+                               double* cov_diag, double* cov_off, double* cov_pos, double* L, cpe_status* status);
+cpe_status cpe_covariance_ragged_host(cpe_handle* h, int32_t B, int32_t N_max, const int32_t* model, const int32_t* n_frames, const double* q,
+                                      const double* meas, const double* weight, double ridge, double* cov_diag, double* cov_off, double* cov_pos,
+                                      double* L, cpe_status* status);
+
 /* forward kinematics only (get_pose_state / get_com, acinoset_misc.py:1581-1659, :722-742); device ptrs */
 cpe_status cpe_forward_kinematics(cpe_handle* h, int32_t B, int32_t N, const double* q,
                                   double* positions /*[B][N][L][3]*/, double* com /*[B][N][3] or NULL*/);
