@@ -113,12 +113,32 @@ __device__ __forceinline__ int wave_project_joints(const DevModel* __restrict__ 
 // grid stride.  Read-only model tables (cameras, Jacobian-slot table, marker-chain table) are staged ONCE
 // per workgroup in LDS, so the per-frame code has no dependent global loads; the next frame's q / meas /
 // neighbour-q are prefetched into registers while the current frame computes and stores.
+// Index arithmetic is kept off the vector pipe.  The wave number is read once as a scalar, so the frame index, n = f mod N (carried along:
+// one division ahead of the loop, one add and conditional subtract per frame) and the frame's base addresses in q / meas / weight / r / J /
+// eps / cost live in scalar registers; every load and store of the loop has the form scalar 64-bit base + 32-bit lane offset (+ immediate).
+// What depends on the lane alone -- camera and marker of its pairs in each projection pass, the G offset of its Jacobian slots -- is worked
+// out ahead of the loop.  The J loop issues the 15 G reads of a camera back to back, then the 30 multiply-adds, then the five stores, which
+// alone are guarded.  None of this changes an operation on r, J or eps or its order (outputs bit-equal to the version before;
+// profiles/r04_resjac_notes.md has the instruction counts and the timing).
 // LDS (doubles): shared  cam[23C] | ident[10] | slot[4S] | chain[4*L*MAXCHAIN] | clen[(L+1)/2]
 //                per wave A[max(6CL, nq+6nl+36nl)] | pos[3L(+1)]   with A = {q, sin/cos, R & dR} later overlaid by G
 // Tables are structure-of-arrays so that consecutive lanes touch consecutive LDS words (no bank conflicts):
 //   slot:  v0[S] v1[S] v2[S] (double) | doff[S] marker[S] (int32; doff = offset of the 3x3 dR in the wave's R block, <0: identity)
 //   chain: v0[K][L] v1[K][L] v2[K][L] (double) | roff[K][L] (int32), K = CPE_MAX_CHAIN, marker index fastest
 #define RJ_MAXPASS 4
+
+// A wave-uniform address as the scalar base of the loads and stores built on it (global_load / global_store with an SGPR pair as base and a
+// 32-bit VGPR offset).  The empty asm only hides the value's origin: otherwise the loop-invariant lane offset is folded into the kernel
+// argument ahead of the loop and the per-frame part is added per lane, in 64-bit vector arithmetic.
+// The pointer is cast to the global address space first, so that what comes out of the asm is still known to be global memory.
+#define RJ_GLOBAL __attribute__((address_space(1)))
+typedef double rj_v2d __attribute__((ext_vector_type(2)));
+template <typename T>
+__device__ __forceinline__ RJ_GLOBAL T* rj_sbase(T* p) {
+    RJ_GLOBAL T* g = (RJ_GLOBAL T*)p;
+    asm("" : "+s"(g));
+    return g;
+}
 
 __host__ __device__ inline int rj_shared_doubles(int C, int L, int S) {
     return 23 * C + 10 + 3 * S + (2 * S + 1) / 2 + 3 * L * CPE_MAX_CHAIN + (L * CPE_MAX_CHAIN + 1) / 2 + (L + 1) / 2;
@@ -135,7 +155,9 @@ __global__ __launch_bounds__(WAVE * NW, (OCC * NW) / 4) void k_resjac(const DevM
                                                       double* __restrict__ J, double* __restrict__ eps,
                                                       double* __restrict__ cost) {
     extern __shared__ double smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    // the wave number is the same in all 64 lanes; saying so keeps the frame index, n = f % N and every per-frame base address in scalar registers
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nq = M->nq, nl = M->nl, L = M->L, C = M->C, S = M->S, CL = C * L;
     double* scam = smem;
     double* sident = scam + 23 * C;
@@ -180,8 +202,24 @@ __global__ __launch_bounds__(WAVE * NW, (OCC * NW) / 4) void k_resjac(const DevM
     __syncthreads();
 
     const cpe_camera* cams = reinterpret_cast<const cpe_camera*>(scam);
-    const long wstride = (long)gridDim.x * NW;
-    long f = (long)blockIdx.x * NW + wave;
+    // what depends on the lane alone is worked out once: camera and marker of the lane's pair in every projection pass (an integer division
+    // by the run-time L each), and the G offset 6 * marker of the lane's Jacobian slots (lanes past the last slot read marker 0 and store nothing)
+    int pcam[NPASS], ppos[NPASS], gofs[5];
+#pragma unroll
+    for (int p = 0; p < NPASS; p++) {
+        const int t = lane + WAVE * p;
+        const int c = t < CL ? t / L : 0;
+        pcam[p] = c; ppos[p] = t < CL ? 3 * (t - c * L) : 0;
+    }
+#pragma unroll
+    for (int i = 0; i < 5; i++) {
+        const int s = lane + WAVE * i;
+        gofs[i] = s < S ? 6 * sli[S + s] : 0;
+    }
+    // F < 2^31 (cpe_eval_resjac checks it) and the grid has at most ceil(F / NW) workgroups, so a frame index and its successor fit 32 bits
+    // unsigned, and the 64-bit element offsets of a frame are each one 32 x 32 -> 64-bit scalar product
+    const unsigned Fu = (unsigned)F, wstride = gridDim.x * NW;
+    unsigned f = blockIdx.x * NW + wave;
 
     // One drain point per frame.  vmcnt counts loads and stores together and the two kinds may retire out of order with
     // respect to each other, so with stores in flight the only safe wait for a load is vmcnt(0) -- which drains every
@@ -190,34 +228,45 @@ __global__ __launch_bounds__(WAVE * NW, (OCC * NW) / 4) void k_resjac(const DevM
     // 1.86 ms + store-only 2.0 ms ~ 3.1 ms measured).  Now a frame issues all its loads at the top, computes everything
     // (projections and G included) without touching them, waits ONCE, and only then issues its 34 stores in one burst;
     // the burst drains while the next frame computes.
-    const double2* meas2 = reinterpret_cast<const double2*>(meas);
+    const rj_v2d* meas2 = reinterpret_cast<const rj_v2d*>(meas);
+    // n = f % N is carried along: one division here, then n += wstride % N with a conditional subtraction per frame (n, dn < N < 2^31: the sum fits 32 bits)
+    unsigned n = (unsigned)(f % N);
+    const unsigned dn = (unsigned)(wstride % N);
+    const unsigned ulane = lane;        // per-lane offsets inside a frame fit 32 bits; the frame bases below are 64-bit scalars
     double qreg = 0.0;
-    if (f < F && lane < nq) qreg = q[f * nq + lane];
+    if (f < Fu && lane < nq) qreg = rj_sbase(q + (unsigned long)f * (unsigned)nq)[ulane];
     __builtin_amdgcn_s_waitcnt(0x0F70);     // vmcnt(0) before the loop: its header then carries no pending load on either edge
 
-    while (f < F) {
+    while (f < Fu) {
         // Two waves share a SIMD: the one in its dependent chain (rotations, chain walk, projections) goes first at issue, the one in its store
         // burst (independent G reads, products and stores) fills the gaps -- measured -3.0 % against equal priorities, the reverse +0.7 % (60 launches each, interleaved in one process)
         __builtin_amdgcn_s_setprio(2);
         if (lane < nq) sq[lane] = qreg;
-        const long fn = f + wstride;
-        const bool has_prev = (int)(f % N) >= 3;
+        const unsigned fn = f + wstride;
+        // element offsets of the frame in q / eps, in meas / weight / r (pairs) and in J (double2)
+        const unsigned long fq = (unsigned long)f * (unsigned)nq, fcl = (unsigned long)f * (unsigned)CL, fj = (unsigned long)f * (unsigned)(C * S);
+        const bool has_prev = n >= 3u;
         double qn = 0.0, qp1 = 0.0, qp2 = 0.0, qp3 = 0.0;
-        double2 mz[NPASS];
+        rj_v2d mz[NPASS];
         double wz[NPASS];
         if (lane < nq) {
-            const double* qf = q + f * nq + lane;
-            if (fn < F) qn = q[fn * nq + lane];
-            if (has_prev) { qp1 = qf[-nq]; qp2 = qf[-2 * nq]; qp3 = qf[-3 * nq]; }
+            if (fn < Fu) qn = rj_sbase(q + (unsigned long)fn * (unsigned)nq)[ulane];
+            if (has_prev) { qp1 = rj_sbase(q + (fq - nq))[ulane]; qp2 = rj_sbase(q + (fq - 2 * nq))[ulane]; qp3 = rj_sbase(q + (fq - 3 * nq))[ulane]; }
         }
+        RJ_GLOBAL const rj_v2d* measf = rj_sbase(meas2 + fcl);
+        RJ_GLOBAL const double* weightf = WANT_COST ? rj_sbase(weight + fcl) : nullptr;
 #pragma unroll
         for (int p = 0; p < NPASS; p++) {
             const int t = lane + WAVE * p;
-            mz[p] = make_double2(0.0, 0.0); wz[p] = 0.0;
-            if (t < CL) { mz[p] = meas2[f * CL + t]; if (WANT_COST) wz[p] = weight[f * CL + t]; }
+            mz[p] = rj_v2d{0.0, 0.0}; wz[p] = 0.0;
+            if (t < CL) { mz[p] = measf[ulane + WAVE * p]; if (WANT_COST) wz[p] = weightf[ulane + WAVE * p]; }
         }
         wave_lds_sync();
-        wave_sincos(M, sq, ssc, lane);
+        if (lane < 3 * nl) {            // wave_sincos with the link count the kernel already holds
+            double sn, cs;
+            sincos(sq[3 + lane], &sn, &cs);
+            ssc[2 * lane] = sn; ssc[2 * lane + 1] = cs;
+        }
         wave_lds_sync();
         for (int t = lane; t < 4 * nl; t += WAVE) rot_kind(ssc + 6 * (t >> 2), t & 3, sR + 9 * t);
         wave_lds_sync();
@@ -246,16 +295,14 @@ __global__ __launch_bounds__(WAVE * NW, (OCC * NW) / 4) void k_resjac(const DevM
         }
         // d p / d q of my Jacobian slots (slot s = lane + 64 i) stay in registers
         double dp0[5], dp1[5], dp2[5];
-        int mk[5];
 #pragma unroll
         for (int i = 0; i < 5; i++) {
             const int s = lane + WAVE * i;
-            dp0[i] = dp1[i] = dp2[i] = 0.0; mk[i] = 0;
+            dp0[i] = dp1[i] = dp2[i] = 0.0;
             if (s < S) {
                 const int doff = sli[s];
                 const double v0 = slv[s], v1 = slv[S + s], v2 = slv[2 * S + s];
                 const double* D = doff < 0 ? sident : sR + doff;
-                mk[i] = sli[S + s];
                 dp0[i] = D[0] * v0 + D[1] * v1 + D[2] * v2;
                 dp1[i] = D[3] * v0 + D[4] * v1 + D[5] * v2;
                 dp2[i] = D[6] * v0 + D[7] * v1 + D[8] * v2;
@@ -264,8 +311,7 @@ __global__ __launch_bounds__(WAVE * NW, (OCC * NW) / 4) void k_resjac(const DevM
         wave_lds_sync();        // R, sincos, q are dead from here: G may overlay them
 
         // project every (camera, marker) pair: (u, v) stay in registers, d(u,v)/dp goes to LDS; nothing is stored yet
-        const long pair0 = f * CL;
-        double2* Jf = reinterpret_cast<double2*>(J) + f * (long)(C * S);
+        RJ_GLOBAL rj_v2d* rf = rj_sbase(reinterpret_cast<rj_v2d*>(r) + fcl);
         double fc = 0.0;
         double2 uv[NPASS];
 #pragma unroll
@@ -274,9 +320,9 @@ __global__ __launch_bounds__(WAVE * NW, (OCC * NW) / 4) void k_resjac(const DevM
             const int t = lane + WAVE * p;
             uv[p] = make_double2(0.0, 0.0);
             if (t < CL) {
-                const int c = t / L, l = t - c * L;
+                const double* pl = spos + ppos[p];
                 double u, v, G[6];
-                project_point(cams[c], spos[3 * l], spos[3 * l + 1], spos[3 * l + 2], u, v, G);      // (the staged form, 210 instead of 225 VGPRs, measured 0.8 % slower here: no occupancy step in reach)
+                project_point(cams[pcam[p]], pl[0], pl[1], pl[2], u, v, G);      // (the staged form, 210 instead of 225 VGPRs, measured 0.8 % slower here: no occupancy step in reach)
                 uv[p] = make_double2(u, v);
                 double2* Gd = reinterpret_cast<double2*>(sG + 6 * t);
                 Gd[0] = make_double2(G[0], G[1]); Gd[1] = make_double2(G[2], G[3]); Gd[2] = make_double2(G[4], G[5]);
@@ -294,29 +340,40 @@ __global__ __launch_bounds__(WAVE * NW, (OCC * NW) / 4) void k_resjac(const DevM
             const int t = lane + WAVE * p;
             if (t < CL) {
                 const double e0 = uv[p].x - mz[p].x, e1 = uv[p].y - mz[p].y;
-                reinterpret_cast<double2*>(r)[pair0 + t] = make_double2(e0, e1);
+                rf[ulane + WAVE * p] = rj_v2d{e0, e1};
                 if (WANT_COST) {
-                    const double w = cams[t / L].mult * wz[p];
+                    const double w = cams[pcam[p]].mult * wz[p];
                     fc += robust_loss(w * e0, la, lb, lc, 0, false).rho + robust_loss(w * e1, la, lb, lc, 0, false).rho;
                 }
             }
         }
-        // J[c][s][0..1] = G_{c,marker(s)} . dp_s : 16-byte streaming stores, consecutive lanes -> consecutive slots
+        // J[c][s][0..1] = G_{c,marker(s)} . dp_s : 16-byte streaming stores, consecutive lanes -> consecutive slots.  Per camera: the G reads
+        // of all five slots first (unconditional: a lane without a slot reads marker 0), then the products, then the stores, which alone are
+        // guarded -- full rounds of 64 slots by a scalar test, the tail round per lane.  The row base advances on the scalar side.
+        const int nfull = S >> 6;
         for (int c = 0; c < C; c++) {
+            const double* Gc = sG + 6 * c * L;
+            RJ_GLOBAL rj_v2d* Jc = rj_sbase(reinterpret_cast<rj_v2d*>(J) + (fj + (unsigned)(c * S)));
+            double2 g0[5], g1[5], g2[5];
 #pragma unroll
             for (int i = 0; i < 5; i++) {
-                const int s = lane + WAVE * i;
-                if (s < S) {
-                    const double2* G = reinterpret_cast<const double2*>(sG + 6 * (c * L + mk[i]));
-                    const double2 g0 = G[0], g1 = G[1], g2 = G[2];
-                    typedef double v2d __attribute__((ext_vector_type(2)));
-                    v2d val;
-                    val.x = g0.x * dp0[i] + g0.y * dp1[i] + g1.x * dp2[i];
-                    val.y = g1.y * dp0[i] + g2.x * dp1[i] + g2.y * dp2[i];
+                const double2* G = reinterpret_cast<const double2*>(Gc + gofs[i]);
+                g0[i] = G[0]; g1[i] = G[1]; g2[i] = G[2];
+            }
+            rj_v2d val[5];
+#pragma unroll
+            for (int i = 0; i < 5; i++) {
+                val[i].x = g0[i].x * dp0[i] + g0[i].y * dp1[i] + g1[i].x * dp2[i];
+                val[i].y = g1[i].y * dp0[i] + g2[i].x * dp1[i] + g2[i].y * dp2[i];
+                asm volatile("" : "+v"(val[i]));        // the products stay here, ahead of the guards: sunk into them, each would wait for its G reads on its own
+            }
+#pragma unroll
+            for (int i = 0; i < 5; i++) {
+                if (i < nfull || lane + WAVE * i < S) {
 #ifdef CPE_RJ_NOSTORE       // diagnostic build only (profiles/r01_resjac_ablation.md): J computed, not stored -- the compute floor of the box
-                    if (val.x == 1.2345e300) Jf[c * S + s] = make_double2(val.x, val.y);
+                    if (val[i].x == 1.2345e300) Jc[ulane + WAVE * i] = val[i];
 #else
-                    __builtin_nontemporal_store(val, reinterpret_cast<v2d*>(&Jf[c * S + s]));
+                    __builtin_nontemporal_store(val[i], &Jc[ulane + WAVE * i]);
 #endif
                 }
             }
@@ -329,10 +386,12 @@ __global__ __launch_bounds__(WAVE * NW, (OCC * NW) / 4) void k_resjac(const DevM
         if (lane < nq) {
             double e = 0.0;
             if (has_prev) e = (qreg - 3.0 * qp1 + 3.0 * qp2 - qp3) * ih2;
-            eps[f * nq + lane] = e;
+            rj_sbase(eps + fq)[ulane] = e;
         }
         qreg = qn;
         f = fn;
+        n += dn;
+        if (n >= (unsigned)N) n -= (unsigned)N;
         wave_lds_sync();        // G region is rewritten as q / sincos / R by the next frame
     }
 }
