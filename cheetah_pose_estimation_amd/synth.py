@@ -106,7 +106,7 @@ def legs_from_alpha(sk: abi.Skeleton, q: np.ndarray, alpha: np.ndarray) -> np.nd
     for r, (c, B) in enumerate(leg_layout(sk)):
         RB = rot_zyx(q[..., 3 + 3 * B:6 + 3 * B])
         ca, sa = np.cos(alpha[..., r]), np.sin(alpha[..., r])
-        Ry = np.zeros(alpha.shape[:-1] + (3, 3))
+        Ry = np.zeros(alpha.shape[:-1] + (3, 3), dtype=ca.dtype)      # keep alpha's dtype
         Ry[..., 0, 0] = ca; Ry[..., 0, 2] = sa; Ry[..., 1, 1] = 1.0; Ry[..., 2, 0] = -sa; Ry[..., 2, 2] = ca
         Rc = RB @ Ry
         q[..., 3 + 3 * c + 1] = np.arcsin(np.clip(-Rc[..., 2, 0], -1, 1))

@@ -198,6 +198,21 @@ def test_physics_model(oracle, gpu_handle_factory, lam):
     assert np.all(G["seq"][:, 4] > 0.0) and not G["seq"][:, 1].any()               # the physics cost, no constant-acceleration model
 
 
+def test_curvature_mode_1(oracle, gpu_handle_factory):
+    """opts.curvature = 1 (the curvature weight max(rho'', 0)) on both sides, with residuals in all four pieces of the loss: the band, its
+    factor and the step differ from mode 0's wherever rho'' < rho' / s"""
+    import frame_compare as FC
+    c = FC.loss_inputs(1, n_frames=8)
+    sk, cams, opts = c["sk"], c["cams"], c["opts"]
+    assert opts.curvature == 1
+    pieces = FC.reference(oracle, sk, cams, opts, None, *FC.flat(c))["conditions"]["pieces"]
+    assert min(pieces) >= 0.05, pieces
+    h = gpu_handle_factory(sk, cams, opts)
+    G1 = _compare(oracle, h, sk, cams, opts, None, c["q"], c["meas"], c["weight"], 1e-1, "curvature 1")
+    G0 = gpu_handle_factory(sk, cams, FC.with_curvature(opts, 0)).eval_lm_step_host(c["q"], c["meas"], c["weight"], 1e-1)
+    assert _equal(G0["g"], G1["g"]) and not _equal(G0["L"], G1["L"])                # the option reaches the kernel
+
+
 def test_failed_sequence_inside_a_batch(oracle, gpu_handle_factory):
     """a NaN in q of one sequence: status CPE_NUMERICAL and no step for it; its neighbours bit-equal to their own B = 1 calls"""
     sk, cams = _phantom25()

@@ -105,6 +105,41 @@ def test_priors_batch_is_bit_equal_to_solo_solves(which):
     _assert_padding_zero(out, seqs, models)
 
 
+def test_per_model_options_reach_the_kernels(oracle):
+    """three models of one shape that differ in loss knots, bound_penalty and camera multipliers (include/cpe.h: these may differ per model), with
+    outliers and a start outside an angle range: every sequence bit-equal to its solo solve on a handle of its own model, and a model-1
+    sequence solved with model 0's options ends elsewhere"""
+    sk = skeleton.build_skeleton("phantom", 24)
+    models = []
+    for knots, kappa, mult in (((3.0, 10.0, 20.0), 1e4, (1.0,) * 6), ((2.0, 6.0, 15.0), 3e3, (1.0, 1.0, 0.6, 0.6, 1.0, 0.8)),
+                               ((1e6, 2e6, 3e6), 1e4, (0.9,) * 6)):
+        cams = synth.make_cameras(6, seed=100)
+        for c in range(6):
+            cams[c].mult = mult[c]
+        opts = abi.default_options()
+        opts.loss_a, opts.loss_b, opts.loss_c = knots
+        opts.bound_penalty = kappa
+        models.append((sk, cams, opts, False))
+    seqs = []
+    for b, (m, n) in enumerate(((0, 9), (1, 7), (2, 9), (1, 5), (0, 8))):
+        d = synth.make_batch(sk, models[m][1], B=1, N=n, seed=80 + b)                 # (10 % of the measurements are outliers)
+        seqs.append((m, d["q_init"][0].copy(), d["meas"][0], d["weight"][0]))
+    i_roll = next(i for i in range(sk.n_bounds) if sk.bound_a[i] == skeleton.dof("base", skeleton.PHI) and sk.bound_b[i] < 0)
+    seqs[1][1][:, skeleton.dof("base", skeleton.PHI)] = sk.bound_up[i_roll] + 0.3     # the start of a model-1 sequence violates a bound
+    m1, q1, me1, we1 = seqs[1]
+    assert oracle.objective(sk, models[1][1], models[1][2], None, q1, me1, we1)[3][4] > 0.0
+    assert len(seqs) == 5 and max(s[1].shape[0] for s in seqs) == 9
+    out = _ragged(models, seqs)
+    refs = _alone(models, seqs)
+    for b in range(len(seqs)):
+        _assert_bit_equal(out, b, refs[b])
+    _assert_padding_zero(out, seqs, models)
+    wrong = _alone(models, [(0, q1, me1, we1)])[0]                                    # the same sequence with model 0's knots, penalty and multipliers
+    own, other = refs[1]["stats"][0].cost, wrong["stats"][0].cost
+    assert out["stats"][1].cost == own and own != other and out["stats"][1].cost != other
+    assert refs[1]["q"][0].tobytes() != wrong["q"][0].tobytes()
+
+
 def test_short_sequences_next_to_a_long_one():
     # the degenerate band cases (no motion term below 4 frames, partial windows below 8) in one batch with N = 57
     models = _models()
