@@ -107,7 +107,7 @@ def load():
     lib.cpe_solve_kinetic_tracked_ragged.argtypes = [vp, ko_p, vp, C.c_int32, C.c_int32, ip, ip] + [vp] * 17 + [C.POINTER(abi.Stats), C.POINTER(abi.KineticStats)]
     lib.cpe_solve_kinetic_tracked_ragged_host.argtypes = lib.cpe_solve_kinetic_tracked_ragged.argtypes
     lib.cpe_eval_normal_tracked.argtypes = [vp, vp, C.c_int32, C.c_int32] + [vp] * 7
-    for name in abi.COVARIANCE_ENTRIES:
+    for name in (*abi.COVARIANCE_ENTRIES, *abi.KINETIC_COVARIANCE_ENTRIES):
         getattr(lib, name).argtypes = abi.covariance_argtypes(name)
     _LIB = lib
     return lib
@@ -814,6 +814,41 @@ class Handle:
         res = {k: (None if v is None else [np.ascontiguousarray(v[b, :lens[b]]) for b in range(B)]) for k, v in out.items()}
         res.update(status=st, seq_status=list(seq)[:B], padded=out)
         return res
+
+    # ---- posterior covariance of the physics-based estimate (include/cpe.h, cpe_covariance_kinetic) ------------------------------------
+    def covariance_kinetic(self, kopt, q, meas, weight, stance, ridge, cov_diag, cov_off=None, cov_pos=None, cov_f=None, f=None, meta=None, L=None,
+                           grf_fixed=None, tau_box=None, grf_box=None):
+        """cpe_covariance_kinetic on device tensors (stance, meta int32; the outputs as in covariance_kinetic_host, each but cov_diag may be None).
+        Returns (status, [status of every sequence])."""
+        B, N = q.shape[0], q.shape[1]
+        seq = (C.c_int32 * max(B, 1))()
+        st = self._call(self.lib.cpe_covariance_kinetic, "cpe_covariance_kinetic", C.byref(kopt) if kopt is not None else None, B, N, _ptr(q),
+                        _ptr(meas), _ptr(weight), _ptr(stance), _ptr(grf_fixed), _ptr(tau_box), _ptr(grf_box), float(ridge), _ptr(cov_diag),
+                        _ptr(cov_off), _ptr(cov_pos), _ptr(cov_f), _ptr(f), _ptr(meta), _ptr(L), seq, allow=(abi.OK, abi.NUMERICAL))
+        return st, list(seq)[:B]
+
+    def covariance_kinetic_host(self, q, meas, weight, stance, kopt, ridge=0.0, grf_fixed=None, tau_box=None, grf_box=None, want_L=False):
+        """cpe_covariance_kinetic_host: numpy in, dict of numpy arrays out -- cov_diag [B, N, 28, 28], cov_off [B, N, 3, 28, 28], cov_pos
+        [B, N, L, 3, 3] as covariance_host; cov_f [B, N, 64, 64] the covariance of every node's free forces in the compact order of meta
+        [B, N, 65] = (count, indices into f's layout tau | lambda | (z, x, y) per foot, ...), f [B, N, 64]; L with want_L; status, seq_status.
+        grf_fixed / tau_box / grf_box (at most one) in solve_kinetic_host's layouts."""
+        f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+        q, meas, weight, grf_fixed, tau_box, grf_box = (f64(a) for a in (q, meas, weight, grf_fixed, tau_box, grf_box))
+        stance = None if stance is None else np.ascontiguousarray(stance, dtype=np.int32)
+        B, N = q.shape[:2]
+        out = self._covariance_outputs(B, N, True, True, want_L)
+        out.update(cov_f=np.empty((B, N, 64, 64)), f=np.empty((B, N, 64)), meta=np.empty((B, N, 65), dtype=np.int32))
+        seq = (C.c_int32 * max(B, 1))()
+        st = self.lib.cpe_covariance_kinetic_host(self._h, C.byref(kopt) if kopt is not None else None, B, N, _ptr(q), _ptr(meas), _ptr(weight),
+                                                  None if stance is None else stance.ctypes.data, _ptr(grf_fixed), _ptr(tau_box), _ptr(grf_box),
+                                                  float(ridge), _ptr(out["cov_diag"]), _ptr(out["cov_off"]), _ptr(out["cov_pos"]), _ptr(out["cov_f"]),
+                                                  _ptr(out["f"]), out["meta"].ctypes.data,
+                                                  _ptr(out["L"]), seq)
+        _check(st, "cpe_covariance_kinetic_host", allow=(abi.OK, abi.NUMERICAL))
+        if not want_L:
+            del out["L"]
+        out.update(status=st, seq_status=list(seq)[:B])
+        return out
 
     # ---- host-pointer conveniences (numpy in, numpy out; PCIe-inclusive) -------------------------------
     def eval_resjac_host(self, q, meas, weight, want_cost=True):

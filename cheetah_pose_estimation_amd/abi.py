@@ -163,7 +163,8 @@ def default_options(fps: float = 120.0) -> Options:
 
 
 # ---- posterior covariance (include/cpe.h, cpe_covariance): argument lists of the entry points, mirrored for _lib.load().  "h" handle,
-# "i" int32, "d" double, "p" pointer to double, "ip" pointer to int32 (host), "pr" pointer to Priors
+# "i" int32, "d" double, "p" pointer to double (or to int32 on the device), "ip" pointer to int32 (host), "pr" pointer to Priors, "ko" pointer to
+# KineticOptions
 COVARIANCE_ENTRIES = {
     "cpe_covariance_supported": ("pr", "d"),
     "cpe_band_inverse": ("h", "i", "i", "p", "p", "p"),
@@ -172,10 +173,17 @@ COVARIANCE_ENTRIES = {
     "cpe_covariance_ragged": ("h", "i", "i", "ip", "ip", "p", "p", "p", "d", "p", "p", "p", "p", "ip"),
     "cpe_covariance_ragged_host": ("h", "i", "i", "ip", "ip", "p", "p", "p", "d", "p", "p", "p", "p", "ip"),
 }
+# the physics-based twin (cpe_covariance_kinetic): h, ko, B, N | q, meas, weight, stance, grf_fixed, tau_box, grf_box | ridge | cov_diag, cov_off,
+# cov_pos, cov_f, f, meta, L | status
+KINETIC_COVARIANCE_ENTRIES = {
+    "cpe_covariance_kinetic": ("h", "ko", "i", "i") + ("p",) * 7 + ("d",) + ("p",) * 7 + ("ip",),
+    "cpe_covariance_kinetic_host": ("h", "ko", "i", "i") + ("p",) * 7 + ("d",) + ("p",) * 7 + ("ip",),
+}
 COVARIANCE_MAX_PB = 4        # largest half-bandwidth (frames) the covariance sweep supports: motion-prior windows 5 and 6 are refused
 
 
 def covariance_argtypes(name: str) -> list:
     """ctypes argument list of a covariance entry point"""
-    kinds = {"h": C.c_void_p, "i": C.c_int32, "d": C.c_double, "p": C.c_void_p, "ip": C.POINTER(C.c_int32), "pr": C.POINTER(Priors)}
-    return [kinds[k] for k in COVARIANCE_ENTRIES[name]]
+    kinds = {"h": C.c_void_p, "i": C.c_int32, "d": C.c_double, "p": C.c_void_p, "ip": C.POINTER(C.c_int32), "pr": C.POINTER(Priors),
+             "ko": C.POINTER(KineticOptions)}
+    return [kinds[k] for k in {**COVARIANCE_ENTRIES, **KINETIC_COVARIANCE_ENTRIES}[name]]

@@ -494,7 +494,8 @@ static cpe_status create_impl(cpe_handle* h, const cpe_skeleton* skel, const cpe
         const void* ks[] = {(const void*)&k_resjac<true, 4, 3, 2>, (const void*)&k_resjac<false, 4, 3, 2>,
                             (const void*)&k_resjac<true, 4, 4, 2>, (const void*)&k_resjac<false, 4, 4, 2>,
                             (const void*)&k_dyn_eval<>, (const void*)&k_dyn_assemble<>, (const void*)&k_dyn_schur<>, (const void*)&k_dyn_jac<>,
-                            (const void*)&k_dyn_eval<true>, (const void*)&k_dyn_assemble<true>, (const void*)&k_dyn_schur<true>, (const void*)&k_dyn_jac<true>};
+                            (const void*)&k_dyn_eval<true>, (const void*)&k_dyn_assemble<true>, (const void*)&k_dyn_schur<true>, (const void*)&k_dyn_jac<true>,
+                            (const void*)&k_force_cov};
         for (const void* k : ks) {         // all of the CU's 160 KiB that the kernel's static LDS leaves (k_dyn_schur<*> holds a word of its own)
             hipFuncAttributes fa;
             HIPCHK(hipFuncGetAttributes(&fa, k));
@@ -1568,9 +1569,10 @@ static void launch_dyn_pieces(cpe_handle* h, int N, int first, size_t Fw, const 
 // One iteration of the physics-based solve: per-frame terms and physics terms of the evaluated buffer, accept / reject (new damping), elimination
 // of the node forces at that damping for the CURRENT iterate, band system, factor + solve + next trial.  RAGGED: with the table rg (N = nmax).
 // xt: x* of every frame (the 3D kinematic cost, k_frame_tracked in place of k_frame_normal), or null (reprojections).
+// back = false (cpe_covariance_kinetic): stop after k_lm_step<3, 2> -- the factor is in Lbuf and every factored sequence has back_pending = 1.
 template <bool RAGGED>
 static void kin_iterate(cpe_handle* h, const LmParams& prm, int N, size_t Fw, size_t ldsn, const double* meas, const double* weight, const int32_t* stance,
-                        const double* xt, RaggedArgs rg, int first, const int* act, const int* n_act, int slots) {
+                        const double* xt, RaggedArgs rg, int first, const int* act, const int* n_act, int slots, bool back = true) {
     const unsigned gf = (unsigned)((size_t)slots * N);
     const bool plain = h->gmm_k == 0;
     prof_begin(h, 0);
@@ -1597,6 +1599,7 @@ static void kin_iterate(cpe_handle* h, const LmParams& prm, int N, size_t Fw, si
     hipLaunchKernelGGL((k_lm_step<3, 2, RAGGED>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gk, h->Bk, h->costbuf,
                        h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hk, act, n_act, 1, nullptr, h->dgbuf, nullptr, 0, rg);
     prof_end(h);
+    if (!back) return;
     prof_begin(h, 7);
     hipLaunchKernelGGL((k_lm_back<3, RAGGED>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf, h->gtbuf, h->dgbuf, act, n_act, rg);
     prof_end(h);
@@ -2175,6 +2178,136 @@ cpe_status cpe_covariance_ragged_host(cpe_handle* h, int32_t B, int32_t N_max, c
                                       double* L, cpe_status* status) {
     if (!model || !n_frames) return fail(CPE_BAD_ARG, "null argument");
     return covariance_host_impl(h, B, N_max, model, n_frames, q, meas, weight, ridge, cov_diag, cov_off, cov_pos, L, status);
+}
+
+// ---- posterior covariance of the physics-based estimate (include/cpe.h, cpe_covariance_kinetic; kernel in cpe_force_cov.hip.inc) -------------
+static cpe_status cov_kinetic_check(const char* who, const cpe_handle* h, const cpe_kinetic_options* opt, const int32_t* stance, const double* grf_fixed,
+                                    const double* tau_box, const double* grf_box, double ridge) {
+    if (cpe_status s = cov_check(who, -1, ridge); s != CPE_OK) return s;
+    if (!opt) return fail(CPE_BAD_ARG, std::string(who) + ": null kinetic options");
+    if (!stance) return fail(CPE_BAD_ARG, std::string(who) + ": null stance");
+    if ((grf_fixed != nullptr) + (tau_box != nullptr) + (grf_box != nullptr) > 1)
+        return fail(CPE_BAD_ARG, std::string(who) + ": at most one of grf_fixed, tau_box, grf_box");
+    if (h && h->pb != 3)
+        return fail(CPE_BAD_ARG, std::string(who) + ": half-bandwidth " + std::to_string(h->pb) + ": the physics-based model runs on the half-bandwidth-3 solver");
+    return CPE_OK;
+}
+
+cpe_status cpe_covariance_kinetic(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q, const double* meas,
+                                  const double* weight, const int32_t* stance, const double* grf_fixed, const double* tau_box, const double* grf_box,
+                                  double ridge, double* cov_diag, double* cov_off, double* cov_pos, double* cov_f, double* f, int32_t* meta, double* L,
+                                  cpe_status* status) {
+    const char* who = "cpe_covariance_kinetic";
+    if (cpe_status s = cov_kinetic_check(who, h, opt, stance, grf_fixed, tau_box, grf_box, ridge); s != CPE_OK) return s;
+    if (!h || !q || !meas || !weight || !cov_diag || !status) return fail(CPE_BAD_ARG, "null argument");
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    HIPCHK(hipSetDevice(h->device));
+    cpe_status s = ensure_ws(h, B, N);                     // the workspaces first: build_kin records pointers into them
+    if (s != CPE_OK) return s;
+    if ((s = ensure_kws(h, B, N)) != CPE_OK || (s = ensure_cov(h, F)) != CPE_OK) return s;
+    if ((s = build_kin(h, opt, grf_fixed, tau_box, grf_box)) != CPE_OK) return s;
+    if ((s = state_reset(h, B, N, q)) != CPE_OK || (s = kin_state_reset(h, F, tau_box != nullptr)) != CPE_OK) return s;
+    const DevModel& m = h->hm;
+    const size_t BB = (size_t)CPE_NX * CPE_NX, w = sizeof(double), LC = 4 * BB, FF = (size_t)KIN_LS * KIN_LS;
+    // k_force_cov reads the off-diagonal blocks of the band whether the caller wants them or not; one flag per sequence behind them
+    DevBuf off_own, bad_buf;
+    if (!cov_off) { HIPCHK(off_own.alloc(F * 3 * BB)); cov_off = off_own.p; }
+    HIPCHK(bad_buf.alloc(((size_t)B + 1) / 2));
+    int* bad = reinterpret_cast<int*>(bad_buf.p);
+    HIPCHK(hipMemsetAsync(bad, 0, sizeof(int) * B, h->stream));
+    // a sequence without a factor has all outputs zero, and so have the nodes 0 and 1 in cov_f, f and meta
+    HIPCHK(hipMemsetAsync(cov_diag, 0, w * F * BB, h->stream));
+    HIPCHK(hipMemsetAsync(cov_off, 0, w * F * 3 * BB, h->stream));
+    if (cov_pos) HIPCHK(hipMemsetAsync(cov_pos, 0, w * F * m.L * 9, h->stream));
+    if (cov_f) HIPCHK(hipMemsetAsync(cov_f, 0, w * F * FF, h->stream));
+    if (f) HIPCHK(hipMemsetAsync(f, 0, w * F * KIN_LS, h->stream));
+    if (meta) HIPCHK(hipMemsetAsync(meta, 0, sizeof(int32_t) * F * (KIN_LS + 1), h->stream));
+    // the launches of the physics solve's first pass up to the band factor, multipliers zero, at damping ridge in place of opts.lambda0
+    LmParams prm = lm_params(h, B, N);
+    prm.lambda0 = ridge;
+    kin_iterate<false>(h, prm, N, F, lds_normal(m, h->gmm_k, h->gmm_dim), meas, weight, stance, nullptr, RaggedArgs{}, 1, nullptr, nullptr, B, false);
+    cov_launch(h, B, N, h->st, h->Lbuf, 1, cov_diag, cov_off, nullptr);
+    // (without cov_f the kernel still decides whether every node's force matrix has a factor: the status does not depend on what is asked for)
+    hipLaunchKernelGGL(k_force_cov, dim3((unsigned)F), dim3(KIN_THREADS), sizeof(double) * FC_DOUBLES, h->stream, h->dk, h->st, N, F, h->pieces, h->pmeta,
+                       h->fbuf, h->kmu, stance, cov_diag, cov_off, cov_f, f, meta, bad);
+    if (cov_pos) {
+        const size_t ldsm = lds_normal_all(h) + w * BB + sizeof(int) * (size_t)(CPE_MAX_MARKERS * CPE_MAX_MCOL);
+        hipLaunchKernelGGL(k_marker_cov<>, dim3((unsigned)F), dim3(WAVE), ldsm, h->stream, h->dm, h->st, N, F, h->qbuf, cov_diag, cov_pos, RaggedArgs{});
+    }
+    if (L) hipLaunchKernelGGL(k_cov_export<>, dim3((unsigned)F), dim3(COV_THREADS), 0, h->stream, h->st, h->Lbuf, L, N, (int)LC, RaggedArgs{});
+    HIPCHK(hipGetLastError());
+    std::vector<SeqState> hs((size_t)B);
+    std::vector<int> hbad((size_t)B);
+    HIPCHK(hipMemcpyAsync(hs.data(), h->st, sizeof(SeqState) * B, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(hbad.data(), bad, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    cpe_status worst = CPE_OK;
+    for (int b = 0; b < B; b++) {
+        const bool band_ok = hs[b].status == 0 && hs[b].back_pending == 1;
+        status[b] = band_ok && !hbad[b] ? CPE_OK : CPE_NUMERICAL;
+        if (status[b] > worst) worst = status[b];
+        if (band_ok && hbad[b]) {                           // a node's force matrix has no factor: what the band kernels wrote goes too
+            const size_t o = (size_t)b * N;
+            HIPCHK(hipMemsetAsync(cov_diag + o * BB, 0, w * N * BB, h->stream));
+            if (!off_own.p) HIPCHK(hipMemsetAsync(cov_off + o * 3 * BB, 0, w * N * 3 * BB, h->stream));
+            if (cov_pos) HIPCHK(hipMemsetAsync(cov_pos + o * m.L * 9, 0, w * N * m.L * 9, h->stream));
+            if (cov_f) HIPCHK(hipMemsetAsync(cov_f + o * FF, 0, w * N * FF, h->stream));
+            if (f) HIPCHK(hipMemsetAsync(f + o * KIN_LS, 0, w * N * KIN_LS, h->stream));
+            if (meta) HIPCHK(hipMemsetAsync(meta + o * (KIN_LS + 1), 0, sizeof(int32_t) * N * (KIN_LS + 1), h->stream));
+            if (L) HIPCHK(hipMemsetAsync(L + o * LC, 0, w * N * LC, h->stream));
+        }
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));                // (the buffers of this call are freed on return)
+    return worst;
+}
+
+// host-pointer twin (stages through HBM)
+cpe_status cpe_covariance_kinetic_host(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q, const double* meas,
+                                       const double* weight, const int32_t* stance, const double* grf_fixed, const double* tau_box,
+                                       const double* grf_box, double ridge, double* cov_diag, double* cov_off, double* cov_pos, double* cov_f, double* f,
+                                       int32_t* meta, double* L, cpe_status* status) {
+    const char* who = "cpe_covariance_kinetic_host";
+    if (cpe_status s = cov_kinetic_check(who, h, opt, stance, grf_fixed, tau_box, grf_box, ridge); s != CPE_OK) return s;
+    if (!h || !q || !meas || !weight || !cov_diag || !status) return fail(CPE_BAD_ARG, "null argument");
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    const DevModel& m = h->hm;
+    HIPCHK(hipSetDevice(h->device));
+    const int nf = opt->dyn.n_feet, nmot = opt->dyn.n_motors;
+    const size_t nm = F * cams_max(h) * m.L, BB = (size_t)CPE_NX * CPE_NX, w = sizeof(double), FF = (size_t)KIN_LS * KIN_LS;
+    const double* var = grf_fixed ? grf_fixed : (tau_box ? tau_box : grf_box);
+    const size_t nvar = grf_fixed ? F * nf * 3 : (tau_box ? F * nmot * 2 : (grf_box ? F * nf * 6 : 0));
+    DevBuf dq_, dm_, dw_, ds_, dv_, od, oo, op, oc, of, ome, ol;
+    HIPCHK(dq_.alloc(F * m.nq)); HIPCHK(dm_.alloc(nm * 2)); HIPCHK(dw_.alloc(nm)); HIPCHK(ds_.alloc((F * nf + 1) / 2)); HIPCHK(od.alloc(F * BB));
+    if (var) HIPCHK(dv_.alloc(nvar));
+    if (cov_off) HIPCHK(oo.alloc(F * 3 * BB));
+    if (cov_pos) HIPCHK(op.alloc(F * m.L * 9));
+    if (cov_f) HIPCHK(oc.alloc(F * FF));
+    if (f) HIPCHK(of.alloc(F * KIN_LS));
+    if (meta) HIPCHK(ome.alloc((F * (KIN_LS + 1) + 1) / 2));
+    if (L) HIPCHK(ol.alloc(F * 4 * BB));
+    HIPCHK(hipMemcpyAsync(dq_.p, q, w * F * m.nq, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(dm_.p, meas, w * nm * 2, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(dw_.p, weight, w * nm, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(ds_.p, stance, sizeof(int32_t) * F * nf, hipMemcpyHostToDevice, h->stream));
+    if (var) HIPCHK(hipMemcpyAsync(dv_.p, var, w * nvar, hipMemcpyHostToDevice, h->stream));
+    int32_t* dmeta = meta ? reinterpret_cast<int32_t*>(ome.p) : nullptr;
+    const cpe_status s = cpe_covariance_kinetic(h, opt, B, N, dq_.p, dm_.p, dw_.p, reinterpret_cast<const int32_t*>(ds_.p), grf_fixed ? dv_.p : nullptr,
+                                                tau_box ? dv_.p : nullptr, grf_box ? dv_.p : nullptr, ridge, od.p, cov_off ? oo.p : nullptr,
+                                                cov_pos ? op.p : nullptr, cov_f ? oc.p : nullptr, f ? of.p : nullptr, dmeta, L ? ol.p : nullptr, status);
+    if (s < 0) return s;
+    HIPCHK(hipMemcpyAsync(cov_diag, od.p, w * F * BB, hipMemcpyDeviceToHost, h->stream));
+    if (cov_off) HIPCHK(hipMemcpyAsync(cov_off, oo.p, w * F * 3 * BB, hipMemcpyDeviceToHost, h->stream));
+    if (cov_pos) HIPCHK(hipMemcpyAsync(cov_pos, op.p, w * F * m.L * 9, hipMemcpyDeviceToHost, h->stream));
+    if (cov_f) HIPCHK(hipMemcpyAsync(cov_f, oc.p, w * F * FF, hipMemcpyDeviceToHost, h->stream));
+    if (f) HIPCHK(hipMemcpyAsync(f, of.p, w * F * KIN_LS, hipMemcpyDeviceToHost, h->stream));
+    if (meta) HIPCHK(hipMemcpyAsync(meta, dmeta, sizeof(int32_t) * F * (KIN_LS + 1), hipMemcpyDeviceToHost, h->stream));
+    if (L) HIPCHK(hipMemcpyAsync(L, ol.p, w * F * 4 * BB, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return s;
 }
 
 #ifdef CPE_LM_STAMPS

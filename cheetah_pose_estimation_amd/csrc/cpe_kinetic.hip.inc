@@ -1104,6 +1104,37 @@ __global__ __launch_bounds__(KIN_THREADS, 2) void k_dyn_assemble(const DevModel*
 }
 
 
+// The node's force matrix as the elimination takes it, with H_uf riding along (k_dyn_schur, k_force_cov), into Mx [na + 84][KIN_MS] by the whole
+// workgroup: rows < na the damped H_ff (lower triangle) -- diagonal times 1 + lam_f, lam_f = lambda * lm_force_damping, plus the wall term -- and
+// rows na + u the row u of H_uf.  f_: the node's frame, fo: its frame in the current buffer.  Ends with a barrier.
+__device__ __forceinline__ void kin_force_matrix(const DevKin* __restrict__ K, const SeqState& Sq, size_t f_, size_t fo, int na, const double* __restrict__ Hfu,
+                                                 const double* __restrict__ Hff, const double* __restrict__ fbuf, const double* __restrict__ kmu,
+                                                 const int32_t* __restrict__ stance, double* Mx, int tid) {
+    const double lamf = Sq.lambda * K->o.lm_force_damping;
+    for (int a = tid >> 4; a < na; a += 16) for (int c = tid & 15; c <= a; c += 16) { const double v = Hff[a * KIN_LS + c]; Mx[a * KIN_MS + c] = a == c ? v + lamf * v : v; }
+    for (int t = tid; t < na * KIN_NC3; t += KIN_THREADS) { const int a = t / KIN_NC3, u = t - a * KIN_NC3; Mx[(na + u) * KIN_MS + a] = Hfu[t]; }
+    __syncthreads();
+    // walls: Hessian of a log barrier on the INACTIVE force inequalities of the stance feet, lambda * kb * 2 w c c^T / gap^2 (one thread per foot block entry)
+    if (K->o.lm_wall_damping > 0.0 && !K->grf_fix && tid < 9 * K->nf) {
+        const int kf = tid / 9, u = (tid - 9 * kf) / 3, v = tid - 9 * kf - 3 * u, fo0 = K->nm + K->nc;
+        if (stance[f_ * K->nf + kf]) {
+            int a = fo0;
+            for (int k2 = 0; k2 < kf; k2++) if (stance[f_ * K->nf + k2]) a += 3;
+            const double* F = fbuf + fo * KIN_LS + fo0 + 3 * kf; const double* mu = kmu + f_ * (4 * KIN_MU) + kf * KIN_MU;
+            double add = 0.0;
+            for (int j = 0; j < 10; j++) {
+                double c3[3], d; kin_force_con(K->o, j, c3, &d, K->grf_box ? K->grf_box + (f_ * K->nf + kf) * 6 : nullptr);
+                const double g = c3[0] * F[0] + c3[1] * F[1] + c3[2] * F[2] - d;
+                if (mu[j] + K->o.kappa_force * g > 0.0) continue;               // active: its curvature is in H_ff already
+                const double gap = fmax(-g, 1e-3);
+                add += Sq.lambda * K->o.lm_wall_damping * 2.0 * K->o.w_slack / (gap * gap) * c3[u] * c3[v];
+            }
+            if (v <= u) Mx[(a + u) * KIN_MS + a + v] += add;
+        }
+    }
+    __syncthreads();
+}
+
 // --------------------------------------------------------------------------------------------------
 // k_dyn_schur: per node of the CURRENT iterate, S = H_uu - H_uf (H_ff + lam_f diag H_ff)^-1 H_fu with lam_f = lambda * lm_force_damping
 // (trust region in force space), written as the six lower 28 x 28 blocks [n,n] [n,n-1] [n,n-2] [n-1,n-1] [n-1,n-2] [n-2,n-2].
@@ -1135,29 +1166,7 @@ __global__ __launch_bounds__(KIN_THREADS) void k_dyn_schur(const DevKin* __restr
     // LDS: Mx [na + 84][KIN_MS]: rows < na the damped H_ff (lower triangle), rows na + u the row u of H_uf; after na elimination steps on the columns
     // < na those rows hold Y^T = H_uf L^-T and the blocks are H_uu - Y^T Y
     double* Mx = smem; double* dg = Mx + (KIN_NA_MAX + KIN_NC3) * KIN_MS;
-    const double lamf = Sq.lambda * K->o.lm_force_damping;
-    for (int a = tid >> 4; a < na; a += 16) for (int c = tid & 15; c <= a; c += 16) { const double v = Hff[a * KIN_LS + c]; Mx[a * KIN_MS + c] = a == c ? v + lamf * v : v; }
-    for (int t = tid; t < na * KIN_NC3; t += KIN_THREADS) { const int a = t / KIN_NC3, u = t - a * KIN_NC3; Mx[(na + u) * KIN_MS + a] = Hfu[t]; }
-    __syncthreads();
-    // walls: Hessian of a log barrier on the INACTIVE force inequalities of the stance feet, lambda * kb * 2 w c c^T / gap^2 (one thread per foot block entry)
-    if (K->o.lm_wall_damping > 0.0 && !K->grf_fix && tid < 9 * K->nf) {
-        const int kf = tid / 9, u = (tid - 9 * kf) / 3, v = tid - 9 * kf - 3 * u, fo0 = K->nm + K->nc;
-        if (stance[f_ * K->nf + kf]) {
-            int a = fo0;
-            for (int k2 = 0; k2 < kf; k2++) if (stance[f_ * K->nf + k2]) a += 3;
-            const double* F = fbuf + fo * KIN_LS + fo0 + 3 * kf; const double* mu = kmu + f_ * (4 * KIN_MU) + kf * KIN_MU;
-            double add = 0.0;
-            for (int j = 0; j < 10; j++) {
-                double c3[3], d; kin_force_con(K->o, j, c3, &d, K->grf_box ? K->grf_box + (f_ * K->nf + kf) * 6 : nullptr);
-                const double g = c3[0] * F[0] + c3[1] * F[1] + c3[2] * F[2] - d;
-                if (mu[j] + K->o.kappa_force * g > 0.0) continue;               // active: its curvature is in H_ff already
-                const double gap = fmax(-g, 1e-3);
-                add += Sq.lambda * K->o.lm_wall_damping * 2.0 * K->o.w_slack / (gap * gap) * c3[u] * c3[v];
-            }
-            if (v <= u) Mx[(a + u) * KIN_MS + a + v] += add;
-        }
-    }
-    __syncthreads();
+    kin_force_matrix(K, Sq, f_, fo, na, Hfu, Hff, fbuf, kmu, stance, Mx, tid);
     // blocks: (fa, fb) with fb >= fa (frame n - fa is the ROW frame: later in time), element [i][j] = S[fa nu + i][fb nu + j]; 4 x 4 register tiles,
     // the diagonal blocks by their lower triangle and mirrored: 3 x 28 + 3 x 49 = 231 tiles, one per thread.  The tile of H_uu is requested before
     // the factorisation (its latency hides behind it).

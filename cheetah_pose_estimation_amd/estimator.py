@@ -321,6 +321,8 @@ class CheetahEstimator:
     kinetic: Optional[dict] = None          # node forces of the last estimate_kinetics (tau, lam, grf, slack, stance)
     # estimate_kinematics(uncertainty=True): dict(cov_u [N, 28, 28], u_std [N, 28], positions_cov [N, L, 3, 3], positions_std [N, L, 3], ridge) --
     # the marginal posterior covariance of every frame's reduced coordinates and marker positions (cpe_covariance); None where it does not exist
+    # estimate_kinetics / estimate_grf(uncertainty=True): the same fields from cpe_covariance_kinetic plus tau_std [N, n_motors], lambda_std [N, 26],
+    # grf_std [N, 4, 3] (net z, x, y per foot) and tau_cov [N, n_motors, n_motors]; 0.0 where a force is not an unknown of that node
     uncertainty: Optional[dict] = None
 
     def get_objective_cost(self) -> float:
@@ -590,6 +592,63 @@ def _check_uncertainty(est: CheetahEstimator, pri: Optional[abi.Priors], ridge: 
         raise NotImplementedError("uncertainty together with shutter-delay estimation: the covariance is that of the kinematic objective without the "
                                   "shutter displacement (cpe_covariance); the delays would be treated as known")
     _lib.covariance_supported(pri, ridge)          # raises with the library's reason: negative ridge, motion-prior window above 4
+
+
+def force_uncertainty(cov_f: np.ndarray, meta: np.ndarray, n_motors: int, n_con: int, n_feet: int) -> dict:
+    """cov_f [N, 64, 64] and meta [N, 65] of cpe_covariance_kinetic -> standard deviations in the layout of the node forces f = tau | lambda |
+    (z, x, y) per foot: tau_std [N, n_motors], lambda_std [N, n_con], grf_std [N, n_feet, 3], and tau_cov [N, n_motors, n_motors].  meta[n] = (count,
+    the indices into f of the node's free forces, in cov_f's order); an entry is 0.0 where a force is not an unknown of the node."""
+    N, nlat = cov_f.shape[0], n_motors + n_con + 3 * n_feet
+    std = np.zeros((N, nlat))
+    tau_cov = np.zeros((N, n_motors, n_motors))
+    for n in range(N):
+        na = int(meta[n, 0])
+        idx = np.asarray(meta[n, 1:1 + na], dtype=np.int64)
+        std[n, idx] = np.sqrt(np.diagonal(cov_f[n])[:na])
+        t = np.nonzero(idx < n_motors)[0]
+        tau_cov[n][np.ix_(idx[t], idx[t])] = cov_f[n][np.ix_(t, t)]
+    return dict(tau_std=np.ascontiguousarray(std[:, :n_motors]), lambda_std=np.ascontiguousarray(std[:, n_motors:n_motors + n_con]),
+                grf_std=np.ascontiguousarray(std[:, n_motors + n_con:].reshape(N, n_feet, 3)), tau_cov=tau_cov)
+
+
+@dataclass
+class KineticUncertainty:
+    """what estimate_kinetics / estimate_grf(uncertainty=True) computed after the solver call: the fields of est.uncertainty, or why there are none
+    (both None: the solve did not converge, nothing was asked of the library)"""
+    fields: Optional[dict] = None
+    reason: Optional[str] = None
+
+
+def _kinetic_uncertainty(h, ko: abi.KineticOptions, res: dict, meas: np.ndarray, weight: np.ndarray, stance: np.ndarray, ridge: float,
+                         grf_fixed=None, tau_box=None, grf_box=None) -> KineticUncertainty:
+    """cpe_covariance_kinetic at the solution res["q"] of a converged physics-based solve, with the solve's own stance, options and variant arrays"""
+    if res["stats"][0].status != abi.OK:
+        return KineticUncertainty()
+    one = lambda a: None if a is None else a[None]
+    cov = h.covariance_kinetic_host(res["q"], meas[None], weight[None], stance[None], ko, ridge, grf_fixed=one(grf_fixed), tau_box=one(tau_box),
+                                    grf_box=one(grf_box))
+    if cov["seq_status"][0] != abi.OK:
+        return KineticUncertainty(reason=f"uncertainty: the evaluation at the solution is not finite, or the reduced band or a node's force matrix has no "
+                                         f"Cholesky factor at ridge {ridge:g} (the data leave a coordinate or a force undetermined; a positive "
+                                         "uncertainty_ridge regularises it)")
+    unc = _uncertainty_of(cov, 0, ridge)
+    unc.update(force_uncertainty(cov["cov_f"][0], cov["meta"][0], res["tau"].shape[-1], res["lam"].shape[-1], res["grf"].shape[-2]))
+    return KineticUncertainty(fields=unc)
+
+
+def _store_kinetic_uncertainty(est: CheetahEstimator, unc: Optional[KineticUncertainty], ok: bool, out_dir: Optional[str]) -> None:
+    """after the solve's own files (unc None: not asked for, nothing changes): est.uncertainty and, for a solve that is `ok`, uncertainty.npz beside
+    fte.pickle -- or the library's reason raised"""
+    if unc is None:
+        return
+    est.uncertainty = None
+    if not ok:
+        return
+    if unc.reason is not None:
+        raise _lib.CpeError(unc.reason)
+    if unc.fields is not None:
+        est.uncertainty = unc.fields
+        np.savez(os.path.join(out_dir, "uncertainty.npz"), **unc.fields)
 
 
 def _kin_finish(est: CheetahEstimator, h, res: dict, seconds: float, solver_output: bool, monocular_constraints: bool,
@@ -960,7 +1019,7 @@ def estimate_kinetics(estimator: CheetahEstimator, init_torques: bool = True, au
                       no_slip: bool = True, joint_estimation: bool = False, fix_grf: bool = True, ground_constraint: bool = False,
                       disable_pose_prior: bool = False, disable_motion_prior: bool = False, plot: bool = False, out_fname: str = "fte",
                       out_dir_prefix: Optional[str] = None, options: Optional[abi.Options] = None,
-                      kinetic_options: Optional[abi.KineticOptions] = None) -> bool:
+                      kinetic_options: Optional[abi.KineticOptions] = None, uncertainty: bool = False, uncertainty_ridge: float = 0.0) -> bool:
     """Same signature and meaning as acinoset_opt.estimate_kinetics (acinoset_opt.py:693-708) for the branch its drivers run for the
     physics-based reconstruction (`joint_estimation=True`, run_dataset.py:1198-1229): torques, joint constraint forces, ground-reaction
     forces and the trajectory are estimated together, warm-started from the kinematic solution on disk, with the contact windows of
@@ -972,10 +1031,19 @@ def estimate_kinetics(estimator: CheetahEstimator, init_torques: bool = True, au
     within `bound_value(profile, 0.2)`; cpe_solve_kinetic_force_box): net z in [0.8, 1.2] x profile, net x / y from the boxes of the two opposite
     polygon sides (a side is non-negative), friction polyhedron kept; feet outside the profile's contact carry no force (the reference would let
     them take up to 0.2 body weights: its box around zero).  The whole NLP runs on the GPU.  `init_torques` has no effect here: the torques are
-    minimised out exactly at every evaluation, so they need no starting value."""
+    minimised out exactly at every evaluation, so they need no starting value.
+    uncertainty=True: after a successful solve the posterior covariance of the estimate AND of its node forces (cpe_covariance_kinetic at the stored
+    q with the solve's stance, options and force profile, damping uncertainty_ridge) goes to est.uncertainty and to uncertainty.npz beside fte.pickle:
+    estimate_kinematics' fields plus tau_std, lambda_std, grf_std, tau_cov (force_uncertainty).  A sequence without a factor raises CpeError after the
+    solve's own files are written.  Not with use_2d_reprojections=False (the covariance of the 3D kinematic cost is not built)."""
+    if uncertainty and not use_2d_reprojections:
+        raise NotImplementedError("uncertainty together with use_2d_reprojections=False: cpe_covariance_kinetic takes the reprojection cost; the covariance "
+                                  "of the 3D kinematic cost (cpe_solve_kinetic_tracked) is not built")
     prep = _kinetic_prepare(estimator, auto, use_2d_reprojections, init_prev_kinematic_solution, synthesised_grf, no_slip, joint_estimation, fix_grf,
                             ground_constraint, disable_pose_prior, disable_motion_prior, out_dir_prefix, options, kinetic_options)
     est = estimator
+    if uncertainty:
+        _lib.covariance_supported(prep["pri"], uncertainty_ridge)          # raises with the library's reason (negative or non-finite ridge)
     h = _lib.Handle(prep["skeleton"], est.cams, prep["opts"], prep["pri"], device=est.device)
     try:
         t0 = time()
@@ -986,7 +1054,9 @@ def estimate_kinetics(estimator: CheetahEstimator, init_torques: bool = True, au
         else:
             res = h.solve_kinetic_host(prep["ko"], prep["q_init"][None], est.meas[None], est.weight[None], prep["stance"][None],
                                        grf_fixed=None if gfx is None else gfx[None], grf_box=None if gbx is None else gbx[None])
-        return _kinetic_finish(est, h, res, time() - t0, prep, solver_output, out_fname, out_dir_prefix)
+        dt = time() - t0
+        unc = _kinetic_uncertainty(h, prep["ko"], res, est.meas, est.weight, prep["stance"], uncertainty_ridge, grf_fixed=gfx, grf_box=gbx) if uncertainty else None
+        return _kinetic_finish(est, h, res, dt, prep, solver_output, out_fname, out_dir_prefix, uncertainty=unc)
     finally:
         h.close()
 
@@ -1098,8 +1168,9 @@ def _kinetic_prepare(est: CheetahEstimator, auto: bool, use_2d_reprojections: bo
 
 
 def _kinetic_finish(est: CheetahEstimator, h, res: dict, seconds: float, prep: dict, solver_output: bool, out_fname: str,
-                    out_dir_prefix: Optional[str]) -> bool:
-    """what estimate_kinetics does after the solver call: centre of mass, costs, `ok`, files.  `res` holds ONE sequence; h: a handle of its model."""
+                    out_dir_prefix: Optional[str], uncertainty: Optional[KineticUncertainty] = None) -> bool:
+    """what estimate_kinetics does after the solver call: centre of mass, costs, `ok`, files.  `res` holds ONE sequence; h: a handle of its model.
+    uncertainty: what _kinetic_uncertainty returned, or None (not asked for); stored after the solve's own files (_store_kinetic_uncertainty)."""
     params, scene = est.params, est.scene
     N, q_init, stance, ko = prep["N"], prep["q_init"], prep["stance"], prep["ko"]
     est.opt_time_s = seconds
@@ -1124,10 +1195,12 @@ def _kinetic_finish(est: CheetahEstimator, h, res: dict, seconds: float, prep: d
               f"max |slack_eom| {ks.max_slack:.3e} (box [{ko.slack_lo}, {ko.slack_hi}]), max |rows 0-2| / Mg {ks.max_base_rows:.3e}, max violated inequality {ks.max_violation:.3e}\n"
               f"RMSE base: {base_err:.4f}\nRMSE links: {rel_err:.4f}")
     ok = st.status == abi.OK and bool((res["slack"][0] >= ko.slack_lo - 1e-4).all() and (res["slack"][0] <= ko.slack_hi + 1e-4).all())
+    out_dir = None
     if scene.cam_idx is not None or ok:                                              # acinoset_opt.py:948-954
         dname = f"fte_kinetic{'_gt' if params.hand_labeled_data else ''}"
         dname = dname if scene.cam_idx is None else f"{dname}_{scene.cam_idx}"
-        est.save(dname, fname=out_fname, out_dir_prefix=out_dir_prefix)
+        out_dir = est.save(dname, fname=out_fname, out_dir_prefix=out_dir_prefix)
+    _store_kinetic_uncertainty(est, uncertainty, ok, out_dir)
     return ok
 
 
@@ -1256,7 +1329,8 @@ def bound_value(val, slack_percentage: float) -> np.ndarray:
 
 
 def estimate_grf(estimator: CheetahEstimator, solver_output: bool = True, out_dir_prefix: Optional[str] = None,
-                 options: Optional[abi.Options] = None, kinetic_options: Optional[abi.KineticOptions] = None) -> bool:
+                 options: Optional[abi.Options] = None, kinetic_options: Optional[abi.KineticOptions] = None, uncertainty: bool = False,
+                 uncertainty_ridge: float = 0.0) -> bool:
     """Same signature and meaning as the module-level acinoset_opt.estimate_grf (acinoset_opt.py:966-1048), the last stage of the kinetic-dataset
     pipeline (run_dataset.py:1125-1138): the physics-based model is solved again from the stored `fte_kinetic/fte.pickle` -- trajectory as the
     starting point, every torque within 10 % of its stored value (`Tc.bounds = bound_value(init_tau, 0.1)`, :995-1003) -- with the ground-reaction
@@ -1266,7 +1340,8 @@ def estimate_grf(estimator: CheetahEstimator, solver_output: bool = True, out_di
     Contact pattern: the reference takes the non-zero entries of `get_grf_profile(..., synthetic_data=False)`, i.e. the frames of each foot's FIRST
     window in `metadata.json` (frames 0 .. N-2) at which the resampled plate signal is non-zero; with a per-frame CSV twin `grf/data.csv` of that
     table (the reference ships `grf/data.h5` at 3.5 kHz, which needs PyTables and a resampling step that are not reproduced here) the same rule is
-    applied to it, otherwise the window alone decides (a loaded plate never reads exactly zero)."""
+    applied to it, otherwise the window alone decides (a loaded plate never reads exactly zero).
+    uncertainty=True: as in estimate_kinetics, with the torque boxes of this solve; uncertainty.npz goes beside fte_grf/fte.pickle."""
     est, params, scene, sk = estimator, estimator.params, estimator.scene, estimator.skeleton
     assert params.kinetic_dataset, "Cannot determine GRF on a dataset other than the kinetic dataset from Penny Hudson and Co."
     if est.kinematic_model:
@@ -1309,11 +1384,16 @@ def estimate_grf(estimator: CheetahEstimator, solver_output: bool = True, out_di
     if est.bound_eom_error is not None:
         ko.slack_lo, ko.slack_hi = float(est.bound_eom_error[0]), float(est.bound_eom_error[1])      # make_pyomo_model(bound_eom_error=...), acinoset_opt.py:510-514
     skk = skeleton.without_motion_model(sk)
+    if uncertainty:
+        _lib.covariance_supported(None, uncertainty_ridge)                 # raises with the library's reason (negative or non-finite ridge)
     h = _lib.Handle(skk, est.cams, opts, None, device=est.device)
+    unc = None
     try:
         t0 = time()
         res = h.solve_kinetic_host(ko, q_init[None], est.meas[None], est.weight[None], stance[None], tau_box=tau_box[None])
         est.opt_time_s = time() - t0
+        if uncertainty:
+            unc = _kinetic_uncertainty(h, ko, res, est.meas, est.weight, stance, uncertainty_ridge, tau_box=tau_box)
         import torch
         dev = torch.device("cuda", est.device)
         qd = torch.tensor(res["q"], device=dev)
@@ -1336,6 +1416,8 @@ def estimate_grf(estimator: CheetahEstimator, solver_output: bool = True, out_di
               f"max |slack_eom| {ks.max_slack:.3e} (box [{ko.slack_lo}, {ko.slack_hi}]), max violated inequality {ks.max_violation:.3e}\n"
               f"RMSE base: {base_err:.4f}\nRMSE links: {rel_err:.4f}")
     ok = st.status == abi.OK and bool((res["slack"][0] >= ko.slack_lo - 1e-4).all() and (res["slack"][0] <= ko.slack_hi + 1e-4).all())
+    out_dir = None
     if ok:
-        est.save("fte_grf", fname="fte", out_dir_prefix=out_dir_prefix)              # acinoset_opt.py:1045-1046
+        out_dir = est.save("fte_grf", fname="fte", out_dir_prefix=out_dir_prefix)    # acinoset_opt.py:1045-1046
+    _store_kinetic_uncertainty(est, unc, ok, out_dir)
     return ok

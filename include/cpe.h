@@ -559,7 +559,7 @@ cpe_status cpe_eval_lm_step(cpe_handle* h, const cpe_kinetic_options* kopt, int3
  * zero: a bound violated at q contributes its penalty curvature, a bound that is met nothing -- the Laplace approximation of the unbounded posterior;
  * (robust loss) the curvature is the solver's PSD weight (opts.curvature), so redescended outliers carry no information; (coordinates) the reduced
  * ones: trunk entries are Euler angles or metres, leg entries the rotation about the body's y axis (cpe_independent_dofs names them).
- * Kinematic objective only (no physics-based model, no shutter displacement).  Every covariance entry refuses with CPE_BAD_ARG, before the device
+ * cpe_covariance* take the kinematic objective (no shutter displacement); cpe_covariance_kinetic below the physics-based one.  Every covariance entry refuses with CPE_BAD_ARG, before the device
  * is touched and with the reason in cpe_last_error(): ridge < 0 or not finite; a handle whose half-bandwidth is above 4 (motion-prior windows 5, 6). */
 /* the refusals above for a handle that cpe_create would build with `priors` (NULL = none), without a handle: CPE_BAD_ARG, else CPE_NO_DEVICE
  * where no GPU is visible, else CPE_OK */
@@ -587,6 +587,41 @@ cpe_status cpe_covariance_host(cpe_handle* h, int32_t B, int32_t N, const double
 cpe_status cpe_covariance_ragged_host(cpe_handle* h, int32_t B, int32_t N_max, const int32_t* model, const int32_t* n_frames, const double* q,
                                       const double* meas, const double* weight, double ridge, double* cov_diag, double* cov_off, double* cov_pos,
                                       double* L, cpe_status* status);
+
+/* ---- posterior covariance of the physics-based estimate: coordinates, and the node forces (torques, joint constraint forces, net foot forces)
+ * the solve infers ("What is inverted").  Runs the launches of the first pass of cpe_solve_kinetic at Euler q -- cold start, multipliers
+ * zero, node forces minimised from a cold start, as cpe_eval_kinetic_system / cpe_eval_lm_step -- at damping `ridge` in place of opts.lambda0, up to
+ * and including the band factor (no back substitution, no trial iterate).  Then
+ *     Sigma = (H + ridge D)^-1      on its block band (pb = 3),
+ * H = the reduced band of that pass (the Schur complement of the joint Gauss-Newton matrix over coordinates and node forces), D its Marquardt diagonal
+ * with cpe_eval_lm_step's floors; and, because the band is that Schur complement, the Laplace covariance of the forces of node n is local and exact:
+ *     cov_f(n) = M_n^-1 + S_n W_n S_n^T,   S_n = M_n^-1 H_fu(n),
+ * W_n = the 84 x 84 covariance of the coordinates of the frames (n, n-1, n-2), all of it inside the band, M_n = the node's force matrix as the pass
+ * eliminated it.  At ridge = 0 M_n is the plain H_ff of cpe_eval_kinetic_nodes.  At ridge > 0 the forces are eliminated at that damping too
+ * (k_dyn_schur reads the sequence's lambda): M_n = H_ff + ridge lm_force_damping diag H_ff + the wall term ridge lm_wall_damping 2 w_slack c c^T / gap^2
+ * of every inactive force inequality of a stance foot.
+ * Named deviations: those of cpe_covariance (scale, bounds / multipliers zero, robust-loss curvature, reduced coordinates); a force whose inequality
+ * row is active at the cold-start minimiser carries that row's penalty curvature in H_ff; a prescribed (grf_fixed) or absent (swing foot) force is not
+ * an unknown and has no entry.
+ * Device pointers except status.  grf_fixed / tau_box / grf_box: at most one non-NULL, as cpe_eval_kinetic_system.  cov_diag, cov_off, cov_pos, L,
+ * status as cpe_covariance (cov_diag and cov_off are bit-equal to cpe_band_inverse of L).  cov_f [B][N][64][64]: the covariance of node n's free forces
+ * in the compact order of meta[n] -- the row order of Hff in cpe_eval_kinetic_nodes -- exactly symmetric, zero past the count and for the nodes 0, 1.
+ * f [B][N][64] and meta int32 [B][N][65] = (count na, the na indices into f's layout tau | lambda | (z, x, y) per foot, zeros, Newton iterations of the
+ * node's force solve in the last word): those of the evaluation.  cov_off, cov_pos, cov_f, f, meta, L may be NULL.
+ * status[b] is CPE_NUMERICAL, and every output of that sequence zero, where the evaluation is not finite or the band or any node's M_n has no Cholesky
+ * factor; the damping is never raised silently.  Results are reproducible bit for bit (no atomics), and a sequence's outputs do not depend on its batch.
+ * Refused with CPE_BAD_ARG before the device is touched, the reason in cpe_last_error(): ridge < 0 or not finite; a handle whose half-bandwidth is not 3
+ * (motion-prior windows above 3); NULL opt or stance; more than one of grf_fixed, tau_box, grf_box.  Not built: ragged batches, the 3D kinematic cost
+ * (cpe_solve_kinetic_tracked*), the shutter displacement. */
+cpe_status cpe_covariance_kinetic(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q, const double* meas,
+                                  const double* weight, const int32_t* stance, const double* grf_fixed, const double* tau_box, const double* grf_box,
+                                  double ridge, double* cov_diag, double* cov_off, double* cov_pos, double* cov_f, double* f, int32_t* meta, double* L,
+                                  cpe_status* status);
+/* host-pointer twin (stages through HBM) */
+cpe_status cpe_covariance_kinetic_host(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q, const double* meas,
+                                       const double* weight, const int32_t* stance, const double* grf_fixed, const double* tau_box,
+                                       const double* grf_box, double ridge, double* cov_diag, double* cov_off, double* cov_pos, double* cov_f, double* f,
+                                       int32_t* meta, double* L, cpe_status* status);
 
 /* forward kinematics only (get_pose_state / get_com, acinoset_misc.py:1581-1659, :722-742); device ptrs */
 cpe_status cpe_forward_kinematics(cpe_handle* h, int32_t B, int32_t N, const double* q,
