@@ -2052,10 +2052,12 @@ __global__ __launch_bounds__(WAVE) void k_grf(const DevModel* __restrict__ M, cp
             const double yc = __shfl(y, gbase + c, WAVE);
             for (int r = 0; r < 6; r++) r6[r] -= Ag[r * nv + c] * yc;
         }
-        if (valid && c_ < 6) {
-            const double rr = c_ == 0 ? r6[0] : c_ == 1 ? r6[1] : c_ == 2 ? r6[2] : c_ == 3 ? r6[3] : c_ == 4 ? r6[4] : r6[5];
-            residual[f * 6 + c_] = rr;
-        }
+        // lane c_ of the frame stores row c_; one foot leaves only five lanes per frame, so lane 0 stores row 5 as well
+        if (valid)
+            for (int r = c_; r < 6; r += nv) {
+                const double rr = r == 0 ? r6[0] : r == 1 ? r6[1] : r == 2 ? r6[2] : r == 3 ? r6[3] : r == 4 ? r6[4] : r6[5];
+                residual[f * 6 + r] = rr;
+            }
     }
 }
 

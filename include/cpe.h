@@ -277,10 +277,14 @@ cpe_status cpe_solve_ragged_host(cpe_handle* h, int32_t B, int32_t N_max, const 
  * D = [+x, +y, -x, -y], for the feet flagged in contact:  minimise |rows - B| subject to 0 <= GRF <= force_max and
  * friction_ratio * GRFz >= sum_k GRFxy_k per foot (acinoset_opt.py:183-192).  Forces are in body weights (M g).
  * The reference hands each frame to IPOPT; the least-squares problem is convex but not strictly (opposing friction
- * components, three or more feet), so IPOPT's answer is one point of a face of minimisers.  Here the face is resolved
- * by the minimum-norm minimiser (Tikhonov term `regularisation`), computed by FISTA with exact projections, a fixed
- * `iterations` count, identically in oracle and HIP.  Only the root link's inertia enters rows 0-5 (all other
- * orientations are independent coordinates). */
+ * components, three or more feet), so IPOPT's answer is one point of a face of minimisers.  Here the Tikhonov term
+ * `regularisation` singles out one minimiser (the minimum-norm point of that face in the limit) and a fixed `iterations`
+ * count of FISTA with exact projections moves towards it, identically in oracle and HIP.  The fixed count does not reach
+ * it: after the default 2000 iterations the objective (8.0e-10) and the net wrench, hence `residual` (1.5e-6), are
+ * determined, while the split of the force over the null space of the force matrix is a feasible near-minimum-norm point
+ * up to 1.35e-2 body weights from that minimiser (measured against a KKT-certified minimiser, DESIGN.md row a13,
+ * tests/test_dynamics_compare.py).  Only the root link's inertia enters rows 0-5 (all other orientations are
+ * independent coordinates). */
 typedef struct cpe_grf_options {
     double root_inertia[3];   /* principal moments of the root link about its body axes (cheetah: cylinder along x)   */
     double friction_ratio;    /* 1.3 (acinoset_opt.py:190)                                                            */
