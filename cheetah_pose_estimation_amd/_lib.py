@@ -52,63 +52,11 @@ def load():
     if os.path.exists(tl):
         C.CDLL(tl, mode=C.RTLD_GLOBAL)
     lib = C.CDLL(LIB_PATH)
+    for name in abi.ENTRIES:
+        getattr(lib, name).argtypes = abi.argtypes(name)
     lib.cpe_last_error.restype = C.c_char_p
     lib.cpe_stream.restype = C.c_void_p
-    lib.cpe_stream.argtypes = [C.c_void_p]
-    lib.cpe_create.argtypes = [C.POINTER(abi.Skeleton), C.POINTER(abi.Camera), C.c_int32, C.POINTER(abi.Options),
-                               C.POINTER(abi.Priors), C.c_int32, C.POINTER(C.c_void_p)]
-    lib.cpe_destroy.argtypes = [C.c_void_p]
-    lib.cpe_synchronize.argtypes = [C.c_void_p]
-    lib.cpe_stream_wait.argtypes = [C.c_void_p, C.c_void_p]
-    lib.cpe_stream_signal.argtypes = [C.c_void_p, C.c_void_p]
-    lib.cpe_profile_enable.argtypes = [C.c_void_p, C.c_int32]
-    lib.cpe_profile_get.argtypes = [C.c_void_p, dp, C.POINTER(C.c_int64)]
-    lib.cpe_jacobian_slots.argtypes = [C.c_void_p]
-    lib.cpe_jacobian_layout.argtypes = [C.c_void_p, ip, ip]
-    lib.cpe_num_independent.argtypes = [C.c_void_p]
-    lib.cpe_independent_dofs.argtypes = [C.c_void_p, ip]
-    vp = C.c_void_p
-    lib.cpe_eval_resjac.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
-    lib.cpe_eval_resjac_host.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
-    lib.cpe_project_joints.argtypes = [vp, C.c_int32, C.c_int32, vp]
-    lib.cpe_forward_kinematics.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp]
-    lib.cpe_marker_velocities.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp]
-    lib.cpe_reproject.argtypes = [vp, C.c_int32, C.c_int32, vp, vp]
-    lib.cpe_triangulate.argtypes = [vp, C.c_int32, vp, vp, vp, vp, C.c_double, vp]
-    lib.cpe_tensorise_dlc.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_double, vp, vp]
-    lib.cpe_eval_normal.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.cpe_solve.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(abi.Stats)]
-    lib.cpe_solve_shutter.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_double, C.c_int32, C.c_double, vp, vp, vp, vp, vp, vp,
-                                      C.POINTER(abi.Stats), C.POINTER(C.c_int32)]
-    lib.cpe_solve_host.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(abi.Stats)]
-    lib.cpe_create_multi.argtypes = [C.c_int32, C.POINTER(abi.Skeleton), C.POINTER(abi.Camera), ip, C.POINTER(abi.Options), C.POINTER(abi.Priors),
-                                     C.c_int32, C.POINTER(C.c_void_p)]
-    lib.cpe_solve_ragged.argtypes = [vp, C.c_int32, C.c_int32, ip, ip, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(abi.Stats)]
-    lib.cpe_solve_ragged_host.argtypes = [vp, C.c_int32, C.c_int32, ip, ip, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(abi.Stats)]
-    lib.cpe_eom_rows.argtypes = [vp, C.POINTER(abi.EomOptions), C.c_int32, C.c_int32, vp, vp, vp, vp]
-    lib.cpe_eom_residual.argtypes = [vp, C.POINTER(abi.DynOptions), C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
-    lib.cpe_grf_fit.argtypes = [vp, C.POINTER(abi.GrfOptions), C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
-    lib.cpe_default_kinetic_options.argtypes = [C.POINTER(abi.KineticOptions), C.c_double, C.c_int32]
-    lib.cpe_default_kinetic_options.restype = None
-    lib.cpe_solve_kinetic.argtypes = [vp, C.POINTER(abi.KineticOptions), C.c_int32, C.c_int32] + [vp] * 13 + [C.POINTER(abi.Stats), C.POINTER(abi.KineticStats)]
-    lib.cpe_solve_kinetic_fixed.argtypes = [vp, C.POINTER(abi.KineticOptions), C.c_int32, C.c_int32] + [vp] * 14 + [C.POINTER(abi.Stats), C.POINTER(abi.KineticStats)]
-    lib.cpe_solve_kinetic_force_box.argtypes = [vp, C.POINTER(abi.KineticOptions), C.c_int32, C.c_int32] + [vp] * 14 + [C.POINTER(abi.Stats), C.POINTER(abi.KineticStats)]
-    lib.cpe_solve_kinetic_bounded.argtypes = [vp, C.POINTER(abi.KineticOptions), C.c_int32, C.c_int32] + [vp] * 14 + [C.POINTER(abi.Stats), C.POINTER(abi.KineticStats)]
-    lib.cpe_solve_kinetic_ragged.argtypes = [vp, C.POINTER(abi.KineticOptions), C.c_int32, C.c_int32, ip, ip] + [vp] * 16 + [C.POINTER(abi.Stats), C.POINTER(abi.KineticStats)]
-    lib.cpe_solve_kinetic_ragged_host.argtypes = [vp, C.POINTER(abi.KineticOptions), C.c_int32, C.c_int32, ip, ip] + [vp] * 16 + [C.POINTER(abi.Stats), C.POINTER(abi.KineticStats)]
-    lib.cpe_eval_kinetic_nodes.argtypes = [vp, C.POINTER(abi.KineticOptions), C.c_int32, C.c_int32] + [vp] * 11
-    lib.cpe_eval_kinetic_system.argtypes = [vp, C.POINTER(abi.KineticOptions), C.c_int32, C.c_int32] + [vp] * 17
-    lib.cpe_eval_lm_step.argtypes = [vp, C.POINTER(abi.KineticOptions), C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_double] + [vp] * 6
-    lib.cpe_default_track_weights.argtypes = [vp]
-    lib.cpe_default_track_weights.restype = None
-    ko_p = C.POINTER(abi.KineticOptions)
-    lib.cpe_solve_kinetic_tracked.argtypes = [vp, ko_p, vp, C.c_int32, C.c_int32] + [vp] * 17 + [C.POINTER(abi.Stats), C.POINTER(abi.KineticStats)]
-    lib.cpe_solve_kinetic_tracked_host.argtypes = lib.cpe_solve_kinetic_tracked.argtypes
-    lib.cpe_solve_kinetic_tracked_ragged.argtypes = [vp, ko_p, vp, C.c_int32, C.c_int32, ip, ip] + [vp] * 17 + [C.POINTER(abi.Stats), C.POINTER(abi.KineticStats)]
-    lib.cpe_solve_kinetic_tracked_ragged_host.argtypes = lib.cpe_solve_kinetic_tracked_ragged.argtypes
-    lib.cpe_eval_normal_tracked.argtypes = [vp, vp, C.c_int32, C.c_int32] + [vp] * 7
-    for name in (*abi.COVARIANCE_ENTRIES, *abi.KINETIC_COVARIANCE_ENTRIES):
-        getattr(lib, name).argtypes = abi.covariance_argtypes(name)
+    lib.cpe_default_kinetic_options.restype = lib.cpe_default_track_weights.restype = None
     _LIB = lib
     return lib
 
@@ -166,23 +114,35 @@ def _pad(arrs, n_max: int, tail) -> np.ndarray:
 
 KINETIC_INPUTS = ("q_init", "meas", "weight", "stance", "force")
 KINETIC_OUTPUTS = ("q", "dq", "ddq", "positions", "meas_err", "tau", "lam", "grf", "slack")
+FORCE_VARIANTS = ("grf_fixed", "tau_box", "grf_box")
+CAMS = "cameras"     # in a per-frame shape: the camera count -- of the sequence's model where shapes are checked, the handle's largest where arrays are padded
 
 
-def pad_kinetic(q_init_list, meas_list, weight_list, stance_list, force_list=None, n_cams_max: Optional[int] = None) -> dict:
+def _force_variant(who: str, grf_fixed, tau_box, grf_box, message: Optional[str] = None):
+    """(name, array) of the one force array given -- the variant of a physics-based solve -- or (None, None); more than one is a ValueError"""
+    given = [(k, a) for k, a in zip(FORCE_VARIANTS, (grf_fixed, tau_box, grf_box)) if a is not None]
+    if len(given) > 1:
+        raise ValueError(message or f"{who}: at most one of grf_fixed, tau_box, grf_box")
+    return given[0] if given else (None, None)
+
+
+def pad_kinetic(q_init_list, meas_list=None, weight_list=None, stance_list=None, force_list=None, n_cams_max: Optional[int] = None,
+                q_target_list=None) -> dict:
     """The inputs of cpe_solve_kinetic_ragged_host from per-sequence arrays: q_init [N_b, nq], meas [N_b, C_b, L, 2], weight [N_b, C_b, L],
     stance [N_b, n_feet], force (grf_fixed / tau_box / grf_box of the sequence, or None) -> zero-padded [B, N_max, ...] arrays (C_max cameras,
-    n_cams_max or the largest C_b).  Pure numpy."""
+    n_cams_max or the largest C_b).  An absent list gives None; q_target [N_b, nq] is padded as q_init is and listed only when given.  Pure numpy."""
     lens = [int(np.shape(q)[0]) for q in q_init_list]
     nmax = max(lens) if lens else 0
-    cm = n_cams_max if n_cams_max is not None else max(int(np.shape(m)[1]) for m in meas_list)
-    L = int(np.shape(meas_list[0])[2])
-    out = dict(lens=lens, q_init=_pad([np.asarray(q, np.float64) for q in q_init_list], nmax, np.shape(q_init_list[0])[1:]),
-               meas=_pad([np.asarray(m, np.float64) for m in meas_list], nmax, (cm, L, 2)),
-               weight=_pad([np.asarray(w, np.float64) for w in weight_list], nmax, (cm, L)),
-               stance=_pad([np.asarray(x, np.int32) for x in stance_list], nmax, np.shape(stance_list[0])[1:]).astype(np.int32),
-               force=None)
-    if force_list is not None:
-        out["force"] = _pad([np.asarray(f, np.float64) for f in force_list], nmax, np.shape(force_list[0])[1:])
+
+    def pad(arrs, tail=None, dtype=np.float64):
+        return None if arrs is None else _pad([np.asarray(a, dtype) for a in arrs], nmax, np.shape(arrs[0])[1:] if tail is None else tail)
+    out = dict(lens=lens, q_init=pad(q_init_list), meas=None, weight=None, stance=pad(stance_list, dtype=np.int32), force=pad(force_list))
+    if meas_list is not None:
+        cm = n_cams_max if n_cams_max is not None else max(int(np.shape(m)[1]) for m in meas_list)
+        L = int(np.shape(meas_list[0])[2])
+        out.update(meas=pad(meas_list, (cm, L, 2)), weight=pad(weight_list, (cm, L)))
+    if q_target_list is not None:
+        out["q_target"] = pad(q_target_list, np.shape(q_init_list[0])[1:])
     return out
 
 
@@ -192,19 +152,9 @@ def pad_kinetic_tracked(q_init_list, q_target_list, stance_list, meas_list=None,
     the result's meas and weight are None).  Pure numpy."""
     if (meas_list is None) != (weight_list is None):
         raise ValueError("pad_kinetic_tracked: meas and weight are given together or not at all")
-    lens = [int(np.shape(q)[0]) for q in q_init_list]
-    if [int(np.shape(t)[0]) for t in q_target_list] != lens:
+    if [int(np.shape(t)[0]) for t in q_target_list] != [int(np.shape(q)[0]) for q in q_init_list]:
         raise ValueError("pad_kinetic_tracked: every q_target has its q_init's frames")
-    if meas_list is not None:
-        out = pad_kinetic(q_init_list, meas_list, weight_list, stance_list, force_list, n_cams_max=n_cams_max)
-    else:
-        nmax = max(lens) if lens else 0
-        out = dict(lens=lens, q_init=_pad([np.asarray(q, np.float64) for q in q_init_list], nmax, np.shape(q_init_list[0])[1:]), meas=None, weight=None,
-                   stance=_pad([np.asarray(x, np.int32) for x in stance_list], nmax, np.shape(stance_list[0])[1:]).astype(np.int32), force=None)
-        if force_list is not None:
-            out["force"] = _pad([np.asarray(f, np.float64) for f in force_list], nmax, np.shape(force_list[0])[1:])
-    out["q_target"] = _pad([np.asarray(t, np.float64) for t in q_target_list], out["q_init"].shape[1], np.shape(q_init_list[0])[1:])
-    return out
+    return pad_kinetic(q_init_list, meas_list, weight_list, stance_list, force_list, n_cams_max, q_target_list)
 
 
 def track_weights(track_w, rows: int) -> np.ndarray:
@@ -219,15 +169,10 @@ def track_weights(track_w, rows: int) -> np.ndarray:
 
 
 def unpad_kinetic(padded: dict, lens, n_cams) -> dict:
-    """The per-sequence outputs of a padded cpe_solve_kinetic_ragged_host result: every array of KINETIC_OUTPUTS in `padded` [B, N_max, ...] ->
-    list of [N_b, ...] (meas_err also cut to the sequence's n_cams[b] cameras).  Pure numpy."""
-    out = {}
-    for k in KINETIC_OUTPUTS:
-        if k not in padded:
-            continue
-        a = padded[k]
-        out[k] = [np.ascontiguousarray(a[b, :lens[b], :n_cams[b]] if k == "meas_err" else a[b, :lens[b]]) for b in range(len(lens))]
-    return out
+    """The per-sequence outputs of a padded ragged result: every array of `padded` [B, N_max, ...] -> list of [N_b, ...] (meas_err also cut to
+    the sequence's n_cams[b] cameras); an output that is None stays None.  Pure numpy."""
+    cut = lambda k, a, b: a[b, :lens[b], :n_cams[b]] if k == "meas_err" else a[b, :lens[b]]
+    return {k: None if a is None else [np.ascontiguousarray(cut(k, a, b)) for b in range(len(lens))] for k, a in padded.items()}
 
 
 def _ptr(t):
@@ -241,25 +186,22 @@ def _ptr(t):
     return t.data_ptr()
 
 
+def _force_slots(variant, array) -> list:
+    """the grf_fixed, tau_box, grf_box pointer arguments of a host entry: `array` in its variant's place, null in the others"""
+    return [_ptr(array) if variant == k else None for k in FORCE_VARIANTS]
+
+
 class Handle:
     """One solver instance = one skeleton + one camera rig + options, bound to one GPU and one HIP stream.
     Stands where the reference builds its Pyomo model (acinoset_opt.py:459-525)."""
 
     def __init__(self, sk: abi.Skeleton, cams, opts: abi.Options = None, priors: abi.Priors = None, device: int = 0):
         self.lib = load()
-        self.sk, self.cams, self.n_cams = sk, cams, len(cams)
-        self.opts = opts if opts is not None else abi.default_options()
+        opts = opts if opts is not None else abi.default_options()
         self._h = C.c_void_p()
-        st = self.lib.cpe_create(C.byref(sk), cams, self.n_cams, C.byref(self.opts),
-                                 C.byref(priors) if priors is not None else None, device, C.byref(self._h))
-        if st == abi.NO_DEVICE:
-            raise CpeError("no HIP device visible: the solve path has no CPU fallback (" + self.lib.cpe_last_error().decode() + ")")
-        _check(st, "cpe_create")
-        self.device = device
-        self.pb = max(3, priors.lr_window) if priors is not None else 3     # half-bandwidth of the solver's band in frames
-        self.S = self.lib.cpe_jacobian_slots(self._h)
-        self.nu = self.lib.cpe_num_independent(self._h)
-        self.nq, self.L = sk.nq, sk.n_markers
+        st = self.lib.cpe_create(C.byref(sk), cams, len(cams), C.byref(opts), C.byref(priors) if priors is not None else None, device,
+                                 C.byref(self._h))
+        self._created(st, "cpe_create", sk, cams, opts, [len(cams)], priors, device)
 
     @classmethod
     def multi(cls, skels, cams_list, opts_list=None, priors: abi.Priors = None, device: int = 0) -> "Handle":
@@ -280,17 +222,22 @@ class Handle:
         self.lib = load()
         self._h = C.c_void_p()
         st = self.lib.cpe_create_multi(n, sks, cams, ncam, ops, C.byref(priors) if priors is not None else None, device, C.byref(self._h))
+        self._created(st, "cpe_create_multi", skels[0], cams_list[0], opts_list[0], list(ncam), priors, device)
+        return self
+
+    def _created(self, st, what, sk, cams, opts, model_n_cams, priors, device):
+        """the tail of both constructors: refuse a failed create, then what the methods read -- the first model's skeleton, cameras and options,
+        the camera count of every model and the largest of them"""
         if st == abi.NO_DEVICE:
             raise CpeError("no HIP device visible: the solve path has no CPU fallback (" + self.lib.cpe_last_error().decode() + ")")
-        _check(st, "cpe_create_multi")
-        self.sk, self.cams, self.n_cams, self.opts = skels[0], cams_list[0], max(len(cl) for cl in cams_list), opts_list[0]
-        self.model_n_cams = [len(cl) for cl in cams_list]
+        _check(st, what)
+        self.sk, self.cams, self.opts = sk, cams, opts
+        self.model_n_cams, self.n_cams = model_n_cams, max(model_n_cams)
         self.device = device
         self.pb = max(3, priors.lr_window) if priors is not None else 3     # half-bandwidth of the solver's band in frames
         self.S = self.lib.cpe_jacobian_slots(self._h)
         self.nu = self.lib.cpe_num_independent(self._h)
-        self.nq, self.L = skels[0].nq, skels[0].n_markers
-        return self
+        self.nq, self.L = sk.nq, sk.n_markers
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -501,12 +448,13 @@ class Handle:
         (lower, upper) bound of every torque, grf_box [B, N, n_feet, 3, 2] = (lower, upper) of the net (z, x, y) foot forces); returns (status, [Stats], [KineticStats])"""
         B, N = q_init.shape[0], q_init.shape[1]
         stats = (abi.Stats * max(B, 1))(); ks = (abi.KineticStats * max(B, 1))()
-        if sum(a is not None for a in (grf_fixed, tau_box, grf_box)) > 1:
-            raise ValueError("prescribed foot forces, torque boxes and force boxes are separate entry points")
-        fn = self.lib.cpe_solve_kinetic_bounded if tau_box is not None else (self.lib.cpe_solve_kinetic_force_box if grf_box is not None else self.lib.cpe_solve_kinetic_fixed)
-        st = self._call(fn, "cpe_solve_kinetic", C.byref(kopts), B, N, _ptr(q_init), _ptr(meas), _ptr(weight), _ptr(stance),
-                        _ptr(tau_box if tau_box is not None else (grf_box if grf_box is not None else grf_fixed)), _ptr(q), _ptr(dq), _ptr(ddq),
-                        _ptr(positions), _ptr(meas_err), _ptr(tau), _ptr(lam), _ptr(grf), _ptr(slack), stats, ks, allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
+        variant, force = _force_variant("solve_kinetic", grf_fixed, tau_box, grf_box,
+                                        "prescribed foot forces, torque boxes and force boxes are separate entry points")
+        fn = {"tau_box": self.lib.cpe_solve_kinetic_bounded, "grf_box": self.lib.cpe_solve_kinetic_force_box}.get(
+            variant, self.lib.cpe_solve_kinetic_fixed)
+        st = self._call(fn, "cpe_solve_kinetic", C.byref(kopts), B, N, _ptr(q_init), _ptr(meas), _ptr(weight), _ptr(stance), _ptr(force), _ptr(q), _ptr(dq),
+                        _ptr(ddq), _ptr(positions), _ptr(meas_err), _ptr(tau), _ptr(lam), _ptr(grf), _ptr(slack), stats, ks,
+                        allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
         return st, list(stats)[:B], list(ks)[:B]
 
     def n_constraint_rows(self):
@@ -514,22 +462,26 @@ class Handle:
 
     def solve_kinetic_host(self, kopts, q_init, meas, weight, stance, grf_fixed=None, tau_box=None, grf_box=None):
         """numpy in, numpy out (staged through HBM with torch)"""
-        T, E = self._to_device, self._empty
+        T = self._to_device
         qi, me, we, stn = T(q_init), T(meas), T(weight), T(stance, np.int32)
         gfx, tbx, gbx = (None if a is None else T(a) for a in (grf_fixed, tau_box, grf_box))
         B, N = qi.shape[0], qi.shape[1]
-        nm, nf, nc = kopts.dyn.n_motors, kopts.dyn.n_feet, self.n_constraint_rows()
-        q, dq, ddq = E(B, N, self.nq), E(B, N, self.nq), E(B, N, self.nq)
-        pos, err = E(B, N, self.L, 3), E(B, N, self.n_cams, self.L, 2)
-        tau, lam, grf, slack = E(B, N, nm), E(B, N, nc), E(B, N, nf, 5), E(B, N, self.nq)
-        st, stats, ks = self.solve_kinetic(kopts, qi, me, we, stn, q, dq, ddq, pos, err, tau, lam, grf, slack, grf_fixed=gfx, tau_box=tbx, grf_box=gbx)
+        out = self._solve_outputs(B, N, kopts, alloc=lambda shape: self._empty(*shape))
+        st, stats, ks = self.solve_kinetic(kopts, qi, me, we, stn, *[out[k] for k in KINETIC_OUTPUTS], grf_fixed=gfx, tau_box=tbx, grf_box=gbx)
         self.synchronize()
-        c = lambda t: t.cpu().numpy()
-        return dict(status=st, q=c(q), dq=c(dq), ddq=c(ddq), positions=c(pos), meas_err=c(err), tau=c(tau), lam=c(lam), grf=c(grf), slack=c(slack),
-                    stats=stats, kstats=ks)
+        return dict(status=st, **{k: t.cpu().numpy() for k, t in out.items()}, stats=stats, kstats=ks)
+
+    def _solve_outputs(self, B, N, kopts=None, meas_err=True, alloc=np.empty) -> dict:
+        """The outputs of a solve, [B, N, ...] each, unwritten, keyed as KINETIC_OUTPUTS: the kinematic solve's five, and with kinetic options the
+        physics-based solve's nine; meas_err is None where it is not wanted"""
+        nq, L = self.nq, self.L
+        tails = dict(q=(nq,), dq=(nq,), ddq=(nq,), positions=(L, 3), meas_err=(self.n_cams, L, 2))
+        if kopts is not None:
+            tails.update(tau=(kopts.dyn.n_motors,), lam=(self.n_constraint_rows(),), grf=(kopts.dyn.n_feet, 5), slack=(nq,))
+        return {k: alloc((B, N) + t) if meas_err or k != "meas_err" else None for k, t in tails.items()}
 
     def _kinetic_options_array(self, kopts_list):
-        n = len(getattr(self, "model_n_cams", [self.n_cams]))
+        n = len(self.model_n_cams)
         kl = list(kopts_list)
         if len(kl) != n:
             raise ValueError(f"solve_kinetic_ragged: one kinetic options struct per model of the handle ({n}), got {len(kl)}")
@@ -540,8 +492,7 @@ class Handle:
         """cpe_solve_kinetic_ragged on device tensors laid out for N_max = q_init.shape[1] frames and C_max cameras; kopts_list: one
         KineticOptions per model of the handle; model / n_frames: int sequences (one per sequence); at most one of grf_fixed / tau_box / grf_box
         (the variant of the whole batch).  Returns (status, [Stats], [KineticStats])."""
-        if sum(a is not None for a in (grf_fixed, tau_box, grf_box)) > 1:
-            raise ValueError("solve_kinetic_ragged: at most one of grf_fixed, tau_box, grf_box")
+        _force_variant("solve_kinetic_ragged", grf_fixed, tau_box, grf_box)
         ko = self._kinetic_options_array(kopts_list)
         B, N = q_init.shape[0], q_init.shape[1]
         if len(model) != B or len(n_frames) != B:
@@ -560,53 +511,60 @@ class Handle:
         grf_fixed / tau_box / grf_box, each a list of one array per sequence ([N_b, n_feet, 3] / [N_b, n_motors, 2] / [N_b, n_feet, 3, 2]).
         Pads, solves, unpads: returns dict(status, q, dq, ddq, positions, meas_err, tau, lam, grf, slack = lists of per-sequence arrays, stats,
         kstats = lists, padded = the padded outputs)."""
-        B = len(q_init_list)
-        models = [0] * B if model_list is None else [int(m) for m in model_list]
-        ncams = getattr(self, "model_n_cams", [self.n_cams])
-        given = [a for a in (grf_fixed, tau_box, grf_box) if a is not None]
-        if len(given) > 1:
-            raise ValueError("solve_kinetic_ragged_host: at most one of grf_fixed, tau_box, grf_box")
-        force = given[0] if given else None
-        if len(meas_list) != B or len(weight_list) != B or len(stance_list) != B or len(models) != B or (force is not None and len(force) != B):
-            raise ValueError("solve_kinetic_ragged_host: one q_init, meas, weight, stance, model (and force array) per sequence")
-        if len(kopts_list) != len(ncams):
-            raise ValueError(f"solve_kinetic_ragged_host: one kinetic options struct per model of the handle ({len(ncams)}), got {len(kopts_list)}")
-        if any(m < 0 or m >= len(ncams) for m in models):
-            raise ValueError("solve_kinetic_ragged_host: model index out of range")
-        L, nq = self.L, self.nq
-        d0 = kopts_list[0].dyn
-        nf, nm, nc = int(d0.n_feet), int(d0.n_motors), self.n_constraint_rows()
-        ftail = None if force is None else ((nf, 3) if grf_fixed is not None else ((nm, 2) if tau_box is not None else (nf, 3, 2)))
-        for b in range(B):
-            n, c = int(np.shape(q_init_list[b])[0]), ncams[models[b]]
-            if np.shape(q_init_list[b]) != (n, nq) or np.shape(meas_list[b]) != (n, c, L, 2) or np.shape(weight_list[b]) != (n, c, L) \
-                    or np.shape(stance_list[b]) != (n, nf) or (force is not None and np.shape(force[b]) != (n,) + ftail):
-                raise ValueError(f"solve_kinetic_ragged_host: sequence {b} does not have the shapes of its model ({n} frames, {c} cameras)")
-        p = pad_kinetic(q_init_list, meas_list, weight_list, stance_list, force, n_cams_max=self.n_cams)
-        lens, Nm, Cm = p["lens"], p["q_init"].shape[1], self.n_cams
-        E = np.empty
-        out = dict(q=E((B, Nm, nq)), dq=E((B, Nm, nq)), ddq=E((B, Nm, nq)), positions=E((B, Nm, L, 3)), meas_err=E((B, Nm, Cm, L, 2)),
-                   tau=E((B, Nm, nm)), lam=E((B, Nm, nc)), grf=E((B, Nm, nf, 5)), slack=E((B, Nm, nq)))
+        who = "solve_kinetic_ragged_host"
+        variant, force = _force_variant(who, grf_fixed, tau_box, grf_box)
+        p = self._ragged_batch(who, "one q_init, meas, weight, stance, model (and force array)", model_list, kopts_list, variant,
+                               q_init=q_init_list, meas=meas_list, weight=weight_list, stance=stance_list, force=force)
+        B, Nm = p["q_init"].shape[:2]
+        out = self._solve_outputs(B, Nm, kopts_list[0])
         stats = (abi.Stats * max(B, 1))(); ks = (abi.KineticStats * max(B, 1))()
-        mo, nfr = (C.c_int32 * max(B, 1))(*models), (C.c_int32 * max(B, 1))(*lens)
         ko = self._kinetic_options_array(kopts_list)
-        fx = p["force"]
-        st = self.lib.cpe_solve_kinetic_ragged_host(self._h, ko, B, Nm, mo, nfr, _ptr(p["q_init"]), _ptr(p["meas"]), _ptr(p["weight"]),
-                                                    p["stance"].ctypes.data, _ptr(fx) if grf_fixed is not None else None,
-                                                    _ptr(fx) if tau_box is not None else None, _ptr(fx) if grf_box is not None else None,
+        st = self.lib.cpe_solve_kinetic_ragged_host(self._h, ko, B, Nm, p["model_arr"], p["len_arr"], _ptr(p["q_init"]), _ptr(p["meas"]), _ptr(p["weight"]),
+                                                    p["stance"].ctypes.data, *_force_slots(variant, p["force"]),
                                                     *[_ptr(out[k]) for k in KINETIC_OUTPUTS], stats, ks)
         _check(st, "cpe_solve_kinetic_ragged_host", allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
-        res = unpad_kinetic(out, lens, [ncams[m] for m in models])
+        res = unpad_kinetic(out, p["lens"], p["cams"])
         res.update(status=st, stats=list(stats)[:B], kstats=list(ks)[:B], padded=out)
         return res
+
+    def _ragged_batch(self, who, each, model_list, kopts_list=None, variant=None, **lists) -> dict:
+        """The checks and the padding that every ragged *_host method starts with.  lists: the per-sequence arrays under pad_kinetic's names
+        (q_init gives the lengths; None = absent); each: how the error names them; kopts_list / variant: the kinetic options of the models and
+        the name of the force array, for the physics-based solves.  Raises ValueError, in this order, for: not one array per sequence, not one
+        kinetic options struct per model, a model index out of range, a sequence without the shapes of its model.  Returns pad_kinetic's dict
+        (pad_kinetic_tracked's with a q_target) plus models, cams (the camera count of every sequence) and the c_int32 arrays model_arr,
+        len_arr."""
+        B = len(lists["q_init"])
+        models = [0] * B if model_list is None else [int(m) for m in model_list]
+        ncams = self.model_n_cams
+        # weight is looked at with meas only: alone, it is for pad_kinetic_tracked to refuse
+        seen = {k: v for k, v in lists.items() if v is not None and (k != "weight" or lists.get("meas") is not None)}
+        if any(len(v) != B for v in seen.values()) or len(models) != B or ("meas" in seen and "weight" not in seen):
+            raise ValueError(f"{who}: {each} per sequence")
+        if kopts_list is not None and len(kopts_list) != len(ncams):
+            raise ValueError(f"{who}: one kinetic options struct per model of the handle ({len(ncams)}), got {len(kopts_list)}")
+        if any(m < 0 or m >= len(ncams) for m in models):
+            raise ValueError(f"{who}: model index out of range")
+        nq, L = self.nq, self.L
+        tails = dict(q_init=(nq,), q_target=(nq,), meas=(CAMS, L, 2), weight=(CAMS, L))
+        if kopts_list is not None:
+            nf, nm = int(kopts_list[0].dyn.n_feet), int(kopts_list[0].dyn.n_motors)
+            tails.update(stance=(nf,), force=dict(grf_fixed=(nf, 3), tau_box=(nm, 2), grf_box=(nf, 3, 2)).get(variant))
+        for b in range(B):
+            n, c = int(np.shape(lists["q_init"][b])[0]), ncams[models[b]]
+            if any(np.shape(v[b]) != (n,) + tuple(c if t == CAMS else t for t in tails[k]) for k, v in seen.items()):
+                raise ValueError(f"{who}: sequence {b} does not have the shapes of its model ({n} frames, {c} cameras)")
+        pad = pad_kinetic_tracked if "q_target" in lists else pad_kinetic
+        p = pad(n_cams_max=self.n_cams, **{k + "_list": v for k, v in lists.items()})
+        p.update(models=models, cams=[ncams[m] for m in models], model_arr=(C.c_int32 * max(B, 1))(*models), len_arr=(C.c_int32 * max(B, 1))(*p["lens"]))
+        return p
 
     # ---- physics-based solve with the 3D kinematic cost (estimate_kinetics(use_2d_reprojections=False); include/cpe.h) ----------------------
     def solve_kinetic_tracked(self, kopts, q_init, q_target, stance, q, dq, ddq, positions, meas=None, weight=None, meas_err=None, tau=None, lam=None,
                               grf=None, slack=None, grf_fixed=None, tau_box=None, grf_box=None, track_w=None):
         """cpe_solve_kinetic_tracked on device tensors (q_target [B, N, nq]; meas / weight may be None together, meas_err is then not written);
         track_w: None (the reference's weights) or NX numbers (host).  Returns (status, [Stats], [KineticStats])"""
-        if sum(a is not None for a in (grf_fixed, tau_box, grf_box)) > 1:
-            raise ValueError("solve_kinetic_tracked: at most one of grf_fixed, tau_box, grf_box")
+        _force_variant("solve_kinetic_tracked", grf_fixed, tau_box, grf_box)
         B, N = q_init.shape[0], q_init.shape[1]
         w = track_weights(track_w, 1)
         stats = (abi.Stats * max(B, 1))(); ks = (abi.KineticStats * max(B, 1))()
@@ -618,27 +576,20 @@ class Handle:
     def solve_kinetic_tracked_host(self, kopts, q_init, q_target, stance, meas=None, weight=None, grf_fixed=None, tau_box=None, grf_box=None,
                                    track_w=None):
         """cpe_solve_kinetic_tracked_host: numpy in, numpy out -- solve_kinetic_host's dict (meas_err None when meas is None)"""
-        if sum(a is not None for a in (grf_fixed, tau_box, grf_box)) > 1:
-            raise ValueError("solve_kinetic_tracked_host: at most one of grf_fixed, tau_box, grf_box")
+        variant, force = _force_variant("solve_kinetic_tracked_host", grf_fixed, tau_box, grf_box)
         if (meas is None) != (weight is None):
             raise ValueError("solve_kinetic_tracked_host: meas and weight are given together or not at all")
         f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
-        qi, qt, me, we = f64(q_init), f64(q_target), f64(meas), f64(weight)
+        qi, qt, me, we, fx = f64(q_init), f64(q_target), f64(meas), f64(weight), f64(force)
         stn = np.ascontiguousarray(stance, dtype=np.int32)
-        fx = f64(grf_fixed if grf_fixed is not None else (tau_box if tau_box is not None else grf_box))
         B, N = qi.shape[0], qi.shape[1]
         if qt.shape != qi.shape:
             raise ValueError("solve_kinetic_tracked_host: q_target has q_init's shape")
-        nm, nf, nc = kopts.dyn.n_motors, kopts.dyn.n_feet, self.n_constraint_rows()
-        E = np.empty
-        out = dict(q=E((B, N, self.nq)), dq=E((B, N, self.nq)), ddq=E((B, N, self.nq)), positions=E((B, N, self.L, 3)),
-                   meas_err=None if me is None else E((B, N, self.n_cams, self.L, 2)), tau=E((B, N, nm)), lam=E((B, N, nc)), grf=E((B, N, nf, 5)),
-                   slack=E((B, N, self.nq)))
+        out = self._solve_outputs(B, N, kopts, meas_err=me is not None)
         w = track_weights(track_w, 1)
         stats = (abi.Stats * max(B, 1))(); ks = (abi.KineticStats * max(B, 1))()
         st = self.lib.cpe_solve_kinetic_tracked_host(self._h, C.byref(kopts), w.ctypes.data, B, N, _ptr(qi), _ptr(qt), _ptr(me), _ptr(we), stn.ctypes.data,
-                                                     _ptr(fx) if grf_fixed is not None else None, _ptr(fx) if tau_box is not None else None,
-                                                     _ptr(fx) if grf_box is not None else None, *[_ptr(out[k]) for k in KINETIC_OUTPUTS], stats, ks)
+                                                     *_force_slots(variant, fx), *[_ptr(out[k]) for k in KINETIC_OUTPUTS], stats, ks)
         _check(st, "cpe_solve_kinetic_tracked_host", allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
         out.update(status=st, stats=list(stats)[:B], kstats=list(ks)[:B])
         return out
@@ -648,49 +599,20 @@ class Handle:
         """cpe_solve_kinetic_tracked_ragged_host over sequences of their own length and model (solve_kinetic_ragged_host's arguments and result,
         plus q_target [N_b, nq] per sequence; meas_list / weight_list may be None together, meas_err is then None); track_w: None, NX numbers
         for every model, or [n_models, NX]"""
-        B = len(q_init_list)
-        models = [0] * B if model_list is None else [int(m) for m in model_list]
-        ncams = getattr(self, "model_n_cams", [self.n_cams])
-        given = [a for a in (grf_fixed, tau_box, grf_box) if a is not None]
-        if len(given) > 1:
-            raise ValueError("solve_kinetic_tracked_ragged_host: at most one of grf_fixed, tau_box, grf_box")
-        force = given[0] if given else None
-        if len(q_target_list) != B or len(stance_list) != B or len(models) != B or (force is not None and len(force) != B) \
-                or (meas_list is not None and (len(meas_list) != B or weight_list is None or len(weight_list) != B)):
-            raise ValueError("solve_kinetic_tracked_ragged_host: one q_init, q_target, stance, model (and meas, weight, force array) per sequence")
-        if len(kopts_list) != len(ncams):
-            raise ValueError(f"solve_kinetic_tracked_ragged_host: one kinetic options struct per model of the handle ({len(ncams)}), got {len(kopts_list)}")
-        if any(m < 0 or m >= len(ncams) for m in models):
-            raise ValueError("solve_kinetic_tracked_ragged_host: model index out of range")
-        L, nq = self.L, self.nq
-        d0 = kopts_list[0].dyn
-        nf, nm, nc = int(d0.n_feet), int(d0.n_motors), self.n_constraint_rows()
-        ftail = None if force is None else ((nf, 3) if grf_fixed is not None else ((nm, 2) if tau_box is not None else (nf, 3, 2)))
-        for b in range(B):
-            n, c = int(np.shape(q_init_list[b])[0]), ncams[models[b]]
-            if np.shape(q_init_list[b]) != (n, nq) or np.shape(q_target_list[b]) != (n, nq) or np.shape(stance_list[b]) != (n, nf) \
-                    or (meas_list is not None and (np.shape(meas_list[b]) != (n, c, L, 2) or np.shape(weight_list[b]) != (n, c, L))) \
-                    or (force is not None and np.shape(force[b]) != (n,) + ftail):
-                raise ValueError(f"solve_kinetic_tracked_ragged_host: sequence {b} does not have the shapes of its model ({n} frames, {c} cameras)")
-        p = pad_kinetic_tracked(q_init_list, q_target_list, stance_list, meas_list, weight_list, force, n_cams_max=self.n_cams)
-        lens, Nm, Cm = p["lens"], p["q_init"].shape[1], self.n_cams
-        E = np.empty
-        out = dict(q=E((B, Nm, nq)), dq=E((B, Nm, nq)), ddq=E((B, Nm, nq)), positions=E((B, Nm, L, 3)),
-                   meas_err=None if meas_list is None else E((B, Nm, Cm, L, 2)), tau=E((B, Nm, nm)), lam=E((B, Nm, nc)), grf=E((B, Nm, nf, 5)),
-                   slack=E((B, Nm, nq)))
+        who = "solve_kinetic_tracked_ragged_host"
+        variant, force = _force_variant(who, grf_fixed, tau_box, grf_box)
+        p = self._ragged_batch(who, "one q_init, q_target, stance, model (and meas, weight, force array)", model_list, kopts_list, variant,
+                               q_init=q_init_list, q_target=q_target_list, stance=stance_list, meas=meas_list, weight=weight_list, force=force)
+        B, Nm = p["q_init"].shape[:2]
+        out = self._solve_outputs(B, Nm, kopts_list[0], meas_err=meas_list is not None)
         stats = (abi.Stats * max(B, 1))(); ks = (abi.KineticStats * max(B, 1))()
-        mo, nfr = (C.c_int32 * max(B, 1))(*models), (C.c_int32 * max(B, 1))(*lens)
         ko = self._kinetic_options_array(kopts_list)
-        w = track_weights(track_w, len(ncams))
-        fx = p["force"]
-        st = self.lib.cpe_solve_kinetic_tracked_ragged_host(self._h, ko, w.ctypes.data, B, Nm, mo, nfr, _ptr(p["q_init"]), _ptr(p["q_target"]),
-                                                            _ptr(p["meas"]), _ptr(p["weight"]), p["stance"].ctypes.data,
-                                                            _ptr(fx) if grf_fixed is not None else None, _ptr(fx) if tau_box is not None else None,
-                                                            _ptr(fx) if grf_box is not None else None, *[_ptr(out[k]) for k in KINETIC_OUTPUTS], stats, ks)
+        w = track_weights(track_w, len(self.model_n_cams))
+        st = self.lib.cpe_solve_kinetic_tracked_ragged_host(self._h, ko, w.ctypes.data, B, Nm, p["model_arr"], p["len_arr"], _ptr(p["q_init"]),
+                                                            _ptr(p["q_target"]), _ptr(p["meas"]), _ptr(p["weight"]), p["stance"].ctypes.data,
+                                                            *_force_slots(variant, p["force"]), *[_ptr(out[k]) for k in KINETIC_OUTPUTS], stats, ks)
         _check(st, "cpe_solve_kinetic_tracked_ragged_host", allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
-        res = unpad_kinetic({k: v for k, v in out.items() if v is not None}, lens, [ncams[m] for m in models])
-        if meas_list is None:
-            res["meas_err"] = None
+        res = unpad_kinetic(out, p["lens"], p["cams"])
         res.update(status=st, stats=list(stats)[:B], kstats=list(ks)[:B], padded=out)
         return res
 
@@ -790,28 +712,14 @@ class Handle:
     def covariance_ragged_host(self, q_list, meas_list, weight_list, model_list=None, ridge=0.0, want_off=True, want_pos=True, want_L=False):
         """cpe_covariance_ragged_host over sequences of their own length and model (solve_ragged_host's arguments): pads, runs, unpads.  Returns
         dict(cov_diag, cov_off, cov_pos, L = lists of per-sequence arrays [N_b, ...] or None, status, seq_status, padded = the padded outputs)."""
-        B = len(q_list)
-        models = [0] * B if model_list is None else [int(m) for m in model_list]
-        ncams = getattr(self, "model_n_cams", [self.n_cams])
-        if len(meas_list) != B or len(weight_list) != B or len(models) != B:
-            raise ValueError("covariance_ragged_host: one q, meas, weight and model per sequence")
-        if any(m < 0 or m >= len(ncams) for m in models):
-            raise ValueError("covariance_ragged_host: model index out of range")
-        lens = [int(np.shape(q)[0]) for q in q_list]
-        Nm, Cm, L, nq = max(lens), self.n_cams, self.L, self.nq
-        qi = np.zeros((B, Nm, nq)); me = np.zeros((B, Nm, Cm, L, 2)); we = np.zeros((B, Nm, Cm, L))
-        for b in range(B):
-            n, c = lens[b], ncams[models[b]]
-            if np.shape(meas_list[b]) != (n, c, L, 2) or np.shape(weight_list[b]) != (n, c, L) or np.shape(q_list[b]) != (n, nq):
-                raise ValueError(f"covariance_ragged_host: sequence {b} does not have the shapes of its model ({n} frames, {c} cameras)")
-            qi[b, :n], me[b, :n, :c], we[b, :n, :c] = q_list[b], meas_list[b], weight_list[b]
+        p = self._ragged_batch("covariance_ragged_host", "one q, meas, weight and model", model_list, q_init=q_list, meas=meas_list, weight=weight_list)
+        B, Nm = p["q_init"].shape[:2]
         out = self._covariance_outputs(B, Nm, want_off, want_pos, want_L)
         seq = (C.c_int32 * max(B, 1))()
-        mo, nf = (C.c_int32 * max(B, 1))(*models), (C.c_int32 * max(B, 1))(*lens)
-        st = self.lib.cpe_covariance_ragged_host(self._h, B, Nm, mo, nf, _ptr(qi), _ptr(me), _ptr(we), float(ridge), _ptr(out["cov_diag"]),
-                                                 _ptr(out["cov_off"]), _ptr(out["cov_pos"]), _ptr(out["L"]), seq)
+        st = self.lib.cpe_covariance_ragged_host(self._h, B, Nm, p["model_arr"], p["len_arr"], _ptr(p["q_init"]), _ptr(p["meas"]), _ptr(p["weight"]),
+                                                 float(ridge), _ptr(out["cov_diag"]), _ptr(out["cov_off"]), _ptr(out["cov_pos"]), _ptr(out["L"]), seq)
         _check(st, "cpe_covariance_ragged_host", allow=(abi.OK, abi.NUMERICAL))
-        res = {k: (None if v is None else [np.ascontiguousarray(v[b, :lens[b]]) for b in range(B)]) for k, v in out.items()}
+        res = unpad_kinetic(out, p["lens"], p["cams"])
         res.update(status=st, seq_status=list(seq)[:B], padded=out)
         return res
 
@@ -865,40 +773,22 @@ class Handle:
         q_init = np.ascontiguousarray(q_init, dtype=np.float64); meas = np.ascontiguousarray(meas, dtype=np.float64)
         weight = np.ascontiguousarray(weight, dtype=np.float64)
         B, N = q_init.shape[:2]
-        q = np.empty_like(q_init); dq = np.empty_like(q_init); ddq = np.empty_like(q_init)
-        pos = np.empty((B, N, self.L, 3)); me = np.empty((B, N, self.n_cams, self.L, 2))
+        out = self._solve_outputs(B, N)
         stats = (abi.Stats * max(B, 1))()
-        st = self.lib.cpe_solve_host(self._h, B, N, _ptr(q_init), _ptr(meas), _ptr(weight), _ptr(q), _ptr(dq), _ptr(ddq),
-                                     _ptr(pos), _ptr(me), stats)
+        st = self.lib.cpe_solve_host(self._h, B, N, _ptr(q_init), _ptr(meas), _ptr(weight), *[_ptr(a) for a in out.values()], stats)
         _check(st, "cpe_solve_host", allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
-        return dict(status=st, q=q, dq=dq, ddq=ddq, positions=pos, meas_err=me, stats=list(stats)[:B])
+        return dict(status=st, **out, stats=list(stats)[:B])
 
     def solve_ragged_host(self, q_init_list, meas_list, weight_list, model_list=None):
         """cpe_solve_ragged_host over sequences of their own length and model: q_init [N_b, nq], meas [N_b, C_m, L, 2], weight [N_b, C_m, L]
         per sequence (C_m = the camera count of its model, model_list[b]; None = model 0 for all).  Pads, solves, unpads: returns dict(status,
         q, dq, ddq, positions, meas_err = lists of per-sequence arrays of the sequence's own shapes, stats = list of Stats)."""
-        B = len(q_init_list)
-        models = [0] * B if model_list is None else [int(m) for m in model_list]
-        ncams = getattr(self, "model_n_cams", [self.n_cams])
-        if len(meas_list) != B or len(weight_list) != B or len(models) != B:
-            raise ValueError("solve_ragged_host: one q_init, meas, weight and model per sequence")
-        if any(m < 0 or m >= len(ncams) for m in models):
-            raise ValueError("solve_ragged_host: model index out of range")
-        lens = [int(np.shape(q)[0]) for q in q_init_list]
-        Nm, Cm, L, nq = max(lens), self.n_cams, self.L, self.nq
-        qi = np.zeros((B, Nm, nq)); me = np.zeros((B, Nm, Cm, L, 2)); we = np.zeros((B, Nm, Cm, L))
-        for b in range(B):
-            n, c = lens[b], ncams[models[b]]
-            if np.shape(meas_list[b]) != (n, c, L, 2) or np.shape(weight_list[b]) != (n, c, L) or np.shape(q_init_list[b]) != (n, nq):
-                raise ValueError(f"solve_ragged_host: sequence {b} does not have the shapes of its model ({n} frames, {c} cameras)")
-            qi[b, :n], me[b, :n, :c], we[b, :n, :c] = q_init_list[b], meas_list[b], weight_list[b]
-        q, dq, ddq = np.empty_like(qi), np.empty_like(qi), np.empty_like(qi)
-        pos, err = np.empty((B, Nm, L, 3)), np.empty((B, Nm, Cm, L, 2))
+        p = self._ragged_batch("solve_ragged_host", "one q_init, meas, weight and model", model_list, q_init=q_init_list, meas=meas_list,
+                               weight=weight_list)
+        B, Nm = p["q_init"].shape[:2]
+        out = self._solve_outputs(B, Nm)
         stats = (abi.Stats * max(B, 1))()
-        mo, nf = (C.c_int32 * max(B, 1))(*models), (C.c_int32 * max(B, 1))(*lens)
-        st = self.lib.cpe_solve_ragged_host(self._h, B, Nm, mo, nf, _ptr(qi), _ptr(me), _ptr(we), _ptr(q), _ptr(dq), _ptr(ddq), _ptr(pos), _ptr(err), stats)
+        st = self.lib.cpe_solve_ragged_host(self._h, B, Nm, p["model_arr"], p["len_arr"], _ptr(p["q_init"]), _ptr(p["meas"]), _ptr(p["weight"]),
+                                            *[_ptr(a) for a in out.values()], stats)
         _check(st, "cpe_solve_ragged_host", allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
-        cut = lambda a, b, c=None: np.ascontiguousarray(a[b, :lens[b]] if c is None else a[b, :lens[b], :c])
-        return dict(status=st, q=[cut(q, b) for b in range(B)], dq=[cut(dq, b) for b in range(B)], ddq=[cut(ddq, b) for b in range(B)],
-                    positions=[cut(pos, b) for b in range(B)], meas_err=[cut(err, b, ncams[models[b]]) for b in range(B)],
-                    stats=list(stats)[:B], padded=dict(q=q, dq=dq, ddq=ddq, positions=pos, meas_err=err))
+        return dict(status=st, **unpad_kinetic(out, p["lens"], p["cams"]), stats=list(stats)[:B], padded=out)

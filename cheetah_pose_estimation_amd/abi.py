@@ -162,28 +162,97 @@ def default_options(fps: float = 120.0) -> Options:
     return o
 
 
-# ---- posterior covariance (include/cpe.h, cpe_covariance): argument lists of the entry points, mirrored for _lib.load().  "h" handle,
-# "i" int32, "d" double, "p" pointer to double (or to int32 on the device), "ip" pointer to int32 (host), "pr" pointer to Priors, "ko" pointer to
-# KineticOptions
+# ---- argument lists of every entry point of include/cpe.h, mirrored for _lib.load() (tests/test_covariance_host.py holds them against the
+# header's prototypes).  "h" handle, "i" int32, "d" double, "p" pointer to double (or to int32 on the device, or a stream), "ip" / "dp" / "lp"
+# pointer to int32 / double / int64 (host), "hp" pointer to a handle, and a pointer to a struct: "sk" Skeleton, "cam" Camera, "op" Options, "pr"
+# Priors, "st" Stats, "go" GrfOptions, "eo" EomOptions, "do" DynOptions, "ko" KineticOptions, "ks" KineticStats
+_BN = ("h", "i", "i")                      # handle, B, N
+_RAGGED = ("ip", "ip")                     # model, n_frames
+_SOLVE = ("p",) * 8                        # q_init, meas, weight | q, dq, ddq, positions, meas_err
+_KIN_BN = ("h", "ko", "i", "i")            # handle, kinetic options, B, N
+_KIN_IN = ("p",) * 4                       # q_init, meas, weight, stance
+_KIN_FORCES = ("p",) * 3                   # grf_fixed, tau_box, grf_box
+_KIN_OUT = ("p",) * 9 + ("st", "ks")       # q, dq, ddq, positions, meas_err, tau, lambda, grf, slack | stats, kstats
+_TRACKED_BN = ("h", "ko", "p", "i", "i")   # handle, kinetic options, track_w, B, N
+_TRACKED_IN = ("p",) * 5                   # q_init, q_target, meas, weight, stance
+_COV = ("p", "p", "p", "d", "p", "p", "p", "p", "ip")      # q, meas, weight | ridge | cov_diag, cov_off, cov_pos, L | status
 COVARIANCE_ENTRIES = {
     "cpe_covariance_supported": ("pr", "d"),
-    "cpe_band_inverse": ("h", "i", "i", "p", "p", "p"),
-    "cpe_covariance": ("h", "i", "i", "p", "p", "p", "d", "p", "p", "p", "p", "ip"),
-    "cpe_covariance_host": ("h", "i", "i", "p", "p", "p", "d", "p", "p", "p", "p", "ip"),
-    "cpe_covariance_ragged": ("h", "i", "i", "ip", "ip", "p", "p", "p", "d", "p", "p", "p", "p", "ip"),
-    "cpe_covariance_ragged_host": ("h", "i", "i", "ip", "ip", "p", "p", "p", "d", "p", "p", "p", "p", "ip"),
+    "cpe_band_inverse": _BN + ("p", "p", "p"),
+    "cpe_covariance": _BN + _COV,
+    "cpe_covariance_host": _BN + _COV,
+    "cpe_covariance_ragged": _BN + _RAGGED + _COV,
+    "cpe_covariance_ragged_host": _BN + _RAGGED + _COV,
 }
 # the physics-based twin (cpe_covariance_kinetic): h, ko, B, N | q, meas, weight, stance, grf_fixed, tau_box, grf_box | ridge | cov_diag, cov_off,
 # cov_pos, cov_f, f, meta, L | status
 KINETIC_COVARIANCE_ENTRIES = {
-    "cpe_covariance_kinetic": ("h", "ko", "i", "i") + ("p",) * 7 + ("d",) + ("p",) * 7 + ("ip",),
-    "cpe_covariance_kinetic_host": ("h", "ko", "i", "i") + ("p",) * 7 + ("d",) + ("p",) * 7 + ("ip",),
+    "cpe_covariance_kinetic": _KIN_BN + ("p",) * 7 + ("d",) + ("p",) * 7 + ("ip",),
+    "cpe_covariance_kinetic_host": _KIN_BN + ("p",) * 7 + ("d",) + ("p",) * 7 + ("ip",),
 }
 COVARIANCE_MAX_PB = 4        # largest half-bandwidth (frames) the covariance sweep supports: motion-prior windows 5 and 6 are refused
+ENTRIES = {
+    "cpe_create": ("sk", "cam", "i", "op", "pr", "i", "hp"),
+    "cpe_create_multi": ("i", "sk", "cam", "ip", "op", "pr", "i", "hp"),
+    "cpe_destroy": ("h",),
+    "cpe_last_error": (),
+    "cpe_default_options": ("op",),
+    "cpe_stream": ("h",),
+    "cpe_synchronize": ("h",),
+    "cpe_stream_wait": ("h", "p"),
+    "cpe_stream_signal": ("h", "p"),
+    "cpe_profile_enable": ("h", "i"),
+    "cpe_profile_get": ("h", "dp", "lp"),
+    "cpe_jacobian_slots": ("h",),
+    "cpe_jacobian_layout": ("h", "ip", "ip"),
+    "cpe_num_independent": ("h",),
+    "cpe_independent_dofs": ("h", "ip"),
+    "cpe_eval_resjac": _BN + ("p",) * 7,                       # q, meas, weight | r, J, eps, cost
+    "cpe_eval_resjac_host": _BN + ("p",) * 7,
+    "cpe_project_joints": _BN + ("p",),
+    "cpe_forward_kinematics": _BN + ("p", "p", "p"),
+    "cpe_marker_velocities": _BN + ("p", "p", "p"),
+    "cpe_reproject": _BN + ("p", "p"),
+    "cpe_triangulate": ("h", "i", "p", "p", "p", "p", "d", "p"),
+    # N, n_slots, slot, table, rows, parts, first_row | part_of_marker, inv_sigma, thresh | meas, weight
+    "cpe_tensorise_dlc": ("h", "i", "i", "i", "p", "i", "i", "i", "p", "p", "d", "p", "p"),
+    "cpe_eval_normal": _BN + ("p",) * 8,                       # q, meas, weight | g, Bm, cost, gam, q_out
+    "cpe_solve": _BN + _SOLVE + ("st",),
+    "cpe_solve_host": _BN + _SOLVE + ("st",),
+    "cpe_solve_ragged": _BN + _RAGGED + _SOLVE + ("st",),
+    "cpe_solve_ragged_host": _BN + _RAGGED + _SOLVE + ("st",),
+    # q_init, meas, weight | tau_bound, max_rounds, tol_tau | q, dq, ddq, positions, meas_err, tau | stats, rounds
+    "cpe_solve_shutter": _BN + ("p", "p", "p", "d", "i", "d") + ("p",) * 6 + ("st", "ip"),
+    "cpe_grf_fit": ("h", "go", "i", "i") + ("p",) * 7,          # q, dq, ddq, contact | grfz, grfxy, residual
+    "cpe_eom_rows": ("h", "eo", "i", "i") + ("p",) * 4,         # q, dq, ddq | rows
+    "cpe_eom_residual": ("h", "do", "i", "i") + ("p",) * 7,     # q, dq, ddq, tau, lambda, grf | residual
+    "cpe_default_kinetic_options": ("ko", "d", "i"),
+    "cpe_solve_kinetic": _KIN_BN + _KIN_IN + _KIN_OUT,
+    "cpe_solve_kinetic_fixed": _KIN_BN + _KIN_IN + ("p",) + _KIN_OUT,
+    "cpe_solve_kinetic_bounded": _KIN_BN + _KIN_IN + ("p",) + _KIN_OUT,
+    "cpe_solve_kinetic_force_box": _KIN_BN + _KIN_IN + ("p",) + _KIN_OUT,
+    "cpe_solve_kinetic_ragged": _KIN_BN + _RAGGED + _KIN_IN + _KIN_FORCES + _KIN_OUT,
+    "cpe_solve_kinetic_ragged_host": _KIN_BN + _RAGGED + _KIN_IN + _KIN_FORCES + _KIN_OUT,
+    "cpe_default_track_weights": ("p",),
+    "cpe_solve_kinetic_tracked": _TRACKED_BN + _TRACKED_IN + _KIN_FORCES + _KIN_OUT,
+    "cpe_solve_kinetic_tracked_host": _TRACKED_BN + _TRACKED_IN + _KIN_FORCES + _KIN_OUT,
+    "cpe_solve_kinetic_tracked_ragged": _TRACKED_BN + _RAGGED + _TRACKED_IN + _KIN_FORCES + _KIN_OUT,
+    "cpe_solve_kinetic_tracked_ragged_host": _TRACKED_BN + _RAGGED + _TRACKED_IN + _KIN_FORCES + _KIN_OUT,
+    "cpe_eval_normal_tracked": ("h", "p", "i", "i") + ("p",) * 7,      # track_w | B, N | q, q_target | g, Bm, cost, gam, q_out
+    "cpe_eval_kinetic_nodes": _KIN_BN + _KIN_IN + ("p",) * 7,          # f, stat, g, Huu, Hfu, Hff, meta
+    "cpe_eval_kinetic_system": _KIN_BN + _KIN_IN + _KIN_FORCES + ("p",) * 10,     # the same, then gk, Bk, Hk
+    "cpe_eval_lm_step": _KIN_BN + _KIN_IN + ("d",) + ("p",) * 6,       # lam | g, dg, L, delta, state, seq
+    **COVARIANCE_ENTRIES, **KINETIC_COVARIANCE_ENTRIES,
+}
 
 
-def covariance_argtypes(name: str) -> list:
-    """ctypes argument list of a covariance entry point"""
-    kinds = {"h": C.c_void_p, "i": C.c_int32, "d": C.c_double, "p": C.c_void_p, "ip": C.POINTER(C.c_int32), "pr": C.POINTER(Priors),
-             "ko": C.POINTER(KineticOptions)}
-    return [kinds[k] for k in {**COVARIANCE_ENTRIES, **KINETIC_COVARIANCE_ENTRIES}[name]]
+def argtypes(name: str) -> list:
+    """ctypes argument list of an entry point"""
+    ptr = C.POINTER
+    kinds = {"h": C.c_void_p, "i": C.c_int32, "d": C.c_double, "p": C.c_void_p, "ip": ptr(C.c_int32), "dp": ptr(C.c_double), "lp": ptr(C.c_int64),
+             "hp": ptr(C.c_void_p), "sk": ptr(Skeleton), "cam": ptr(Camera), "op": ptr(Options), "pr": ptr(Priors), "st": ptr(Stats),
+             "go": ptr(GrfOptions), "eo": ptr(EomOptions), "do": ptr(DynOptions), "ko": ptr(KineticOptions), "ks": ptr(KineticStats)}
+    return [kinds[k] for k in ENTRIES[name]]
+
+
+covariance_argtypes = argtypes

@@ -78,6 +78,42 @@ struct DevBuf {
     hipError_t alloc(size_t n) { return hipMalloc(&p, sizeof(double) * (n ? n : 1)); }
 };
 
+// The device side of a host-pointer twin.  Every staged array is named once, with its element type and count: in() uploads it, out() remembers
+// the download that fetch() enqueues.  The first HIP error sticks in `err` (checked once after the staging and once by fetch's caller) and makes
+// the later calls do nothing; the memory is freed on destruction.
+struct Staging {
+    struct Download { void* host; const void* dev; size_t bytes; };
+    hipStream_t stream;
+    hipError_t err = hipSuccess;
+    std::vector<void*> bufs;
+    std::vector<Download> downloads;
+    explicit Staging(hipStream_t s) : stream(s) {}
+    Staging(const Staging&) = delete;
+    ~Staging() { for (void* p : bufs) (void)hipFree(p); }
+    template <class T> T* alloc(size_t n) {
+        void* p = nullptr;
+        if (err == hipSuccess && (err = hipMalloc(&p, sizeof(T) * (n ? n : 1))) == hipSuccess) bufs.push_back(p);
+        return static_cast<T*>(p);
+    }
+    template <class T> T* in(const T* host, size_t n) {          // a null host pointer stays null
+        T* d = host ? alloc<T>(n) : nullptr;
+        if (d) err = hipMemcpyAsync(d, host, sizeof(T) * n, hipMemcpyHostToDevice, stream);
+        return d;
+    }
+    // the device entry gets its buffer also where the caller does not want the array back (host null: nothing to download)
+    template <class T> T* out(T* host, size_t n) {
+        T* d = alloc<T>(n);
+        if (d && host) downloads.push_back({host, d, sizeof(T) * n});
+        return d;
+    }
+    template <class T> T* out_opt(T* host, size_t n) { return host ? out(host, n) : nullptr; }   // for outputs the device entry takes as null
+    hipError_t fetch() {                                          // the downloads, then the one drain of the stream
+        for (const Download& d : downloads)
+            if (err == hipSuccess) err = hipMemcpyAsync(d.host, d.dev, d.bytes, hipMemcpyDeviceToHost, stream);
+        return err == hipSuccess ? (err = hipStreamSynchronize(stream)) : err;
+    }
+};
+
 // A workspace buffer is allocated through ws_alloc, which records the member's address: ws_free walks that record, so every buffer
 // is named once.
 template <class T>
@@ -2148,23 +2184,15 @@ static cpe_status covariance_host_impl(cpe_handle* h, int32_t B, int32_t N, cons
     if (F == 0) return CPE_OK;
     const DevModel& m = h->hm;
     HIPCHK(hipSetDevice(h->device));
-    const size_t nm = F * cams_max(h) * m.L, BB = (size_t)CPE_NX * CPE_NX, w = sizeof(double);
-    DevBuf dq_, dm_, dw_, od, oo, op, ol;
-    HIPCHK(dq_.alloc(F * m.nq)); HIPCHK(dm_.alloc(nm * 2)); HIPCHK(dw_.alloc(nm)); HIPCHK(od.alloc(F * BB));
-    if (cov_off) HIPCHK(oo.alloc(F * h->pb * BB));
-    if (cov_pos) HIPCHK(op.alloc(F * m.L * 9));
-    if (L) HIPCHK(ol.alloc(F * (h->pb + 1) * BB));
-    HIPCHK(hipMemcpyAsync(dq_.p, q, w * F * m.nq, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(dm_.p, meas, w * nm * 2, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(dw_.p, weight, w * nm, hipMemcpyHostToDevice, h->stream));
-    const cpe_status s = covariance_impl(h, B, N, model, n_frames, dq_.p, dm_.p, dw_.p, ridge, od.p, cov_off ? oo.p : nullptr, cov_pos ? op.p : nullptr,
-                                         L ? ol.p : nullptr, status);
+    const size_t nm = F * cams_max(h) * m.L, BB = (size_t)CPE_NX * CPE_NX;
+    Staging st(h->stream);
+    const double *dq = st.in(q, F * m.nq), *dmeas = st.in(meas, nm * 2), *dweight = st.in(weight, nm);
+    double *od = st.out(cov_diag, F * BB), *oo = st.out_opt(cov_off, F * h->pb * BB), *op = st.out_opt(cov_pos, F * m.L * 9);
+    double* ol = st.out_opt(L, F * (h->pb + 1) * BB);
+    HIPCHK(st.err);
+    const cpe_status s = covariance_impl(h, B, N, model, n_frames, dq, dmeas, dweight, ridge, od, oo, op, ol, status);
     if (s < 0) return s;
-    HIPCHK(hipMemcpyAsync(cov_diag, od.p, w * F * BB, hipMemcpyDeviceToHost, h->stream));
-    if (cov_off) HIPCHK(hipMemcpyAsync(cov_off, oo.p, w * F * h->pb * BB, hipMemcpyDeviceToHost, h->stream));
-    if (cov_pos) HIPCHK(hipMemcpyAsync(cov_pos, op.p, w * F * m.L * 9, hipMemcpyDeviceToHost, h->stream));
-    if (L) HIPCHK(hipMemcpyAsync(L, ol.p, w * F * (h->pb + 1) * BB, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(st.fetch());
     return s;
 }
 
@@ -2277,36 +2305,21 @@ cpe_status cpe_covariance_kinetic_host(cpe_handle* h, const cpe_kinetic_options*
     const DevModel& m = h->hm;
     HIPCHK(hipSetDevice(h->device));
     const int nf = opt->dyn.n_feet, nmot = opt->dyn.n_motors;
-    const size_t nm = F * cams_max(h) * m.L, BB = (size_t)CPE_NX * CPE_NX, w = sizeof(double), FF = (size_t)KIN_LS * KIN_LS;
+    const size_t nm = F * cams_max(h) * m.L, BB = (size_t)CPE_NX * CPE_NX, FF = (size_t)KIN_LS * KIN_LS;
     const double* var = grf_fixed ? grf_fixed : (tau_box ? tau_box : grf_box);
     const size_t nvar = grf_fixed ? F * nf * 3 : (tau_box ? F * nmot * 2 : (grf_box ? F * nf * 6 : 0));
-    DevBuf dq_, dm_, dw_, ds_, dv_, od, oo, op, oc, of, ome, ol;
-    HIPCHK(dq_.alloc(F * m.nq)); HIPCHK(dm_.alloc(nm * 2)); HIPCHK(dw_.alloc(nm)); HIPCHK(ds_.alloc((F * nf + 1) / 2)); HIPCHK(od.alloc(F * BB));
-    if (var) HIPCHK(dv_.alloc(nvar));
-    if (cov_off) HIPCHK(oo.alloc(F * 3 * BB));
-    if (cov_pos) HIPCHK(op.alloc(F * m.L * 9));
-    if (cov_f) HIPCHK(oc.alloc(F * FF));
-    if (f) HIPCHK(of.alloc(F * KIN_LS));
-    if (meta) HIPCHK(ome.alloc((F * (KIN_LS + 1) + 1) / 2));
-    if (L) HIPCHK(ol.alloc(F * 4 * BB));
-    HIPCHK(hipMemcpyAsync(dq_.p, q, w * F * m.nq, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(dm_.p, meas, w * nm * 2, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(dw_.p, weight, w * nm, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(ds_.p, stance, sizeof(int32_t) * F * nf, hipMemcpyHostToDevice, h->stream));
-    if (var) HIPCHK(hipMemcpyAsync(dv_.p, var, w * nvar, hipMemcpyHostToDevice, h->stream));
-    int32_t* dmeta = meta ? reinterpret_cast<int32_t*>(ome.p) : nullptr;
-    const cpe_status s = cpe_covariance_kinetic(h, opt, B, N, dq_.p, dm_.p, dw_.p, reinterpret_cast<const int32_t*>(ds_.p), grf_fixed ? dv_.p : nullptr,
-                                                tau_box ? dv_.p : nullptr, grf_box ? dv_.p : nullptr, ridge, od.p, cov_off ? oo.p : nullptr,
-                                                cov_pos ? op.p : nullptr, cov_f ? oc.p : nullptr, f ? of.p : nullptr, dmeta, L ? ol.p : nullptr, status);
+    Staging st(h->stream);
+    const double *dq = st.in(q, F * m.nq), *dmeas = st.in(meas, nm * 2), *dweight = st.in(weight, nm);
+    const int32_t* dstance = st.in(stance, F * nf);
+    const double* dvar = st.in(var, nvar);
+    double *od = st.out(cov_diag, F * BB), *oo = st.out_opt(cov_off, F * 3 * BB), *op = st.out_opt(cov_pos, F * m.L * 9);
+    double *oc = st.out_opt(cov_f, F * FF), *of = st.out_opt(f, F * KIN_LS), *ol = st.out_opt(L, F * 4 * BB);
+    int32_t* ometa = st.out_opt(meta, F * (KIN_LS + 1));
+    HIPCHK(st.err);
+    const cpe_status s = cpe_covariance_kinetic(h, opt, B, N, dq, dmeas, dweight, dstance, grf_fixed ? dvar : nullptr, tau_box ? dvar : nullptr,
+                                                grf_box ? dvar : nullptr, ridge, od, oo, op, oc, of, ometa, ol, status);
     if (s < 0) return s;
-    HIPCHK(hipMemcpyAsync(cov_diag, od.p, w * F * BB, hipMemcpyDeviceToHost, h->stream));
-    if (cov_off) HIPCHK(hipMemcpyAsync(cov_off, oo.p, w * F * 3 * BB, hipMemcpyDeviceToHost, h->stream));
-    if (cov_pos) HIPCHK(hipMemcpyAsync(cov_pos, op.p, w * F * m.L * 9, hipMemcpyDeviceToHost, h->stream));
-    if (cov_f) HIPCHK(hipMemcpyAsync(cov_f, oc.p, w * F * FF, hipMemcpyDeviceToHost, h->stream));
-    if (f) HIPCHK(hipMemcpyAsync(f, of.p, w * F * KIN_LS, hipMemcpyDeviceToHost, h->stream));
-    if (meta) HIPCHK(hipMemcpyAsync(meta, dmeta, sizeof(int32_t) * F * (KIN_LS + 1), hipMemcpyDeviceToHost, h->stream));
-    if (L) HIPCHK(hipMemcpyAsync(L, ol.p, w * F * 4 * BB, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(st.fetch());
     return s;
 }
 
@@ -2352,76 +2365,54 @@ cpe_status cpe_eval_resjac_host(cpe_handle* h, int32_t B, int32_t N, const doubl
     if (F == 0) return CPE_OK;
     const DevModel& m = h->hm;
     HIPCHK(hipSetDevice(h->device));
-    DevBuf dq_, dm_, dw_, dr_, dJ_, de_, dc_;
     const size_t nm = F * m.C * m.L;
-    HIPCHK(dq_.alloc(F * m.nq)); HIPCHK(dm_.alloc(nm * 2)); HIPCHK(dw_.alloc(nm)); HIPCHK(dr_.alloc(nm * 2));
-    HIPCHK(dJ_.alloc(F * m.C * m.S * 2)); HIPCHK(de_.alloc(F * m.nq)); HIPCHK(dc_.alloc(F));
-    HIPCHK(hipMemcpyAsync(dq_.p, q, sizeof(double) * F * m.nq, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(dm_.p, meas, sizeof(double) * nm * 2, hipMemcpyHostToDevice, h->stream));
-    if (weight) HIPCHK(hipMemcpyAsync(dw_.p, weight, sizeof(double) * nm, hipMemcpyHostToDevice, h->stream));
-    cpe_status s = cpe_eval_resjac(h, B, N, dq_.p, dm_.p, weight ? dw_.p : nullptr, dr_.p, dJ_.p, de_.p, (cost && weight) ? dc_.p : nullptr);
+    Staging st(h->stream);
+    const double *dq = st.in(q, F * m.nq), *dmeas = st.in(meas, nm * 2), *dweight = st.in(weight, nm);
+    double *dr = st.out(r, nm * 2), *dJ = st.out(J, F * m.C * m.S * 2), *deps = st.out(eps, F * m.nq);
+    double* dcost = st.out_opt(weight ? cost : nullptr, F);       // the cost needs the weights
+    HIPCHK(st.err);
+    cpe_status s = cpe_eval_resjac(h, B, N, dq, dmeas, dweight, dr, dJ, deps, dcost);
     if (s != CPE_OK) return s;
-    HIPCHK(hipMemcpyAsync(r, dr_.p, sizeof(double) * nm * 2, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(J, dJ_.p, sizeof(double) * F * m.C * m.S * 2, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(eps, de_.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
-    if (cost && weight) HIPCHK(hipMemcpyAsync(cost, dc_.p, sizeof(double) * F, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(st.fetch());
     return CPE_OK;
 }
 
-cpe_status cpe_solve_ragged_host(cpe_handle* h, int32_t B, int32_t N_max, const int32_t* model, const int32_t* n_frames, const double* q_init,
-                                 const double* meas, const double* weight, double* q, double* dq, double* ddq, double* positions, double* meas_err,
-                                 cpe_stats* stats) {
-    if (!h || !model || !n_frames || !q_init || !meas || !weight || !q) return fail(CPE_BAD_ARG, "null argument");
+// host-pointer twins of cpe_solve (model == null) and cpe_solve_ragged: stage through HBM
+static cpe_status solve_host_impl(cpe_handle* h, int32_t B, int32_t N, const int32_t* model, const int32_t* n_frames, const double* q_init,
+                                  const double* meas, const double* weight, double* q, double* dq, double* ddq, double* positions, double* meas_err,
+                                  cpe_stats* stats) {
+    if (!h || !q_init || !meas || !weight || !q) return fail(CPE_BAD_ARG, "null argument");
     size_t F;
-    if (cpe_status s = frames(B, N_max, &F); s != CPE_OK) return s;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
     if (F == 0) return CPE_OK;
     std::vector<int2> seq;
-    if (cpe_status s = ragged_table(h, B, N_max, model, n_frames, seq); s != CPE_OK) return s;
+    if (model)
+        if (cpe_status s = ragged_table(h, B, N, model, n_frames, seq); s != CPE_OK) return s;
     const DevModel& m = h->hm;
     HIPCHK(hipSetDevice(h->device));
-    const size_t nm = F * cams_max(h) * m.L;
-    DevBuf di, dm_, dw_, oq, odq, oddq, op, ome;
-    HIPCHK(di.alloc(F * m.nq)); HIPCHK(dm_.alloc(nm * 2)); HIPCHK(dw_.alloc(nm)); HIPCHK(oq.alloc(F * m.nq));
-    HIPCHK(odq.alloc(F * m.nq)); HIPCHK(oddq.alloc(F * m.nq)); HIPCHK(op.alloc(F * m.L * 3)); HIPCHK(ome.alloc(nm * 2));
-    HIPCHK(hipMemcpyAsync(di.p, q_init, sizeof(double) * F * m.nq, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(dm_.p, meas, sizeof(double) * nm * 2, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(dw_.p, weight, sizeof(double) * nm, hipMemcpyHostToDevice, h->stream));
-    cpe_status s = cpe_solve_ragged(h, B, N_max, model, n_frames, di.p, dm_.p, dw_.p, oq.p, odq.p, oddq.p, op.p, ome.p, stats);
+    const size_t nm = F * (model ? cams_max(h) : m.C) * m.L;
+    Staging st(h->stream);
+    const double *di = st.in(q_init, F * m.nq), *dmeas = st.in(meas, nm * 2), *dweight = st.in(weight, nm);
+    double *oq = st.out(q, F * m.nq), *odq = st.out(dq, F * m.nq), *oddq = st.out(ddq, F * m.nq);
+    double *op = st.out(positions, F * m.L * 3), *ome = st.out(meas_err, nm * 2);
+    HIPCHK(st.err);
+    cpe_status s = model ? cpe_solve_ragged(h, B, N, model, n_frames, di, dmeas, dweight, oq, odq, oddq, op, ome, stats)
+                         : cpe_solve(h, B, N, di, dmeas, dweight, oq, odq, oddq, op, ome, stats);
     if (s < 0) return s;
-    HIPCHK(hipMemcpyAsync(q, oq.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
-    if (dq) HIPCHK(hipMemcpyAsync(dq, odq.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
-    if (ddq) HIPCHK(hipMemcpyAsync(ddq, oddq.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
-    if (positions) HIPCHK(hipMemcpyAsync(positions, op.p, sizeof(double) * F * m.L * 3, hipMemcpyDeviceToHost, h->stream));
-    if (meas_err) HIPCHK(hipMemcpyAsync(meas_err, ome.p, sizeof(double) * nm * 2, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(st.fetch());
     return s;
 }
 
 cpe_status cpe_solve_host(cpe_handle* h, int32_t B, int32_t N, const double* q_init, const double* meas, const double* weight,
                           double* q, double* dq, double* ddq, double* positions, double* meas_err, cpe_stats* stats) {
-    if (!h || !q_init || !meas || !weight || !q) return fail(CPE_BAD_ARG, "null argument");
-    size_t F;
-    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
-    if (F == 0) return CPE_OK;
-    const DevModel& m = h->hm;
-    HIPCHK(hipSetDevice(h->device));
-    const size_t nm = F * m.C * m.L;
-    DevBuf di, dm_, dw_, oq, odq, oddq, op, ome;
-    HIPCHK(di.alloc(F * m.nq)); HIPCHK(dm_.alloc(nm * 2)); HIPCHK(dw_.alloc(nm)); HIPCHK(oq.alloc(F * m.nq));
-    HIPCHK(odq.alloc(F * m.nq)); HIPCHK(oddq.alloc(F * m.nq)); HIPCHK(op.alloc(F * m.L * 3)); HIPCHK(ome.alloc(nm * 2));
-    HIPCHK(hipMemcpyAsync(di.p, q_init, sizeof(double) * F * m.nq, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(dm_.p, meas, sizeof(double) * nm * 2, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(dw_.p, weight, sizeof(double) * nm, hipMemcpyHostToDevice, h->stream));
-    cpe_status s = cpe_solve(h, B, N, di.p, dm_.p, dw_.p, oq.p, odq.p, oddq.p, op.p, ome.p, stats);
-    if (s < 0) return s;
-    HIPCHK(hipMemcpyAsync(q, oq.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
-    if (dq) HIPCHK(hipMemcpyAsync(dq, odq.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
-    if (ddq) HIPCHK(hipMemcpyAsync(ddq, oddq.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
-    if (positions) HIPCHK(hipMemcpyAsync(positions, op.p, sizeof(double) * F * m.L * 3, hipMemcpyDeviceToHost, h->stream));
-    if (meas_err) HIPCHK(hipMemcpyAsync(meas_err, ome.p, sizeof(double) * nm * 2, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return s;
+    return solve_host_impl(h, B, N, nullptr, nullptr, q_init, meas, weight, q, dq, ddq, positions, meas_err, stats);
+}
+
+cpe_status cpe_solve_ragged_host(cpe_handle* h, int32_t B, int32_t N_max, const int32_t* model, const int32_t* n_frames, const double* q_init,
+                                 const double* meas, const double* weight, double* q, double* dq, double* ddq, double* positions, double* meas_err,
+                                 cpe_stats* stats) {
+    if (!model || !n_frames) return fail(CPE_BAD_ARG, "null argument");
+    return solve_host_impl(h, B, N_max, model, n_frames, q_init, meas, weight, q, dq, ddq, positions, meas_err, stats);
 }
 
 // joint equalities of a model: two rows per revolute joint, one per Hooke joint (the node forces lambda, build_kin_entry)
@@ -2429,6 +2420,16 @@ static int n_con(const DevModel& m) {
     int n = 0;
     for (int j = 0; j < m.nj; j++) n += m.joint_kind[j] == CPE_JOINT_REVOLUTE_Y ? 2 : 1;
     return n;
+}
+
+// What the physics-based solve twins size their staging by: the counts every model shares (refused here when out of range, and checked again by
+// the solve) and the one optional force array (at most one of the three is given: the callers have checked) with its element count over F frames
+struct ForceStage { size_t nf, nmo; const double* fx; size_t n_fx; };
+static cpe_status force_stage(const cpe_dyn_options& d, size_t F, const double* grf_fixed, const double* tau_box, const double* grf_box, ForceStage& fs) {
+    if (d.n_feet < 1 || d.n_feet > 4 || d.n_motors < 0 || d.n_motors > CPE_MAX_MOTORS) return fail(CPE_BAD_ARG, "kinetic options: feet / motors out of range");
+    const size_t nf = (size_t)d.n_feet, nmo = (size_t)d.n_motors;
+    fs = {nf, nmo, grf_fixed ? grf_fixed : (tau_box ? tau_box : grf_box), grf_fixed ? F * nf * 3 : (tau_box ? F * nmo * 2 : (grf_box ? F * nf * 6 : 0))};
+    return CPE_OK;
 }
 
 cpe_status cpe_solve_kinetic_ragged_host(cpe_handle* h, const cpe_kinetic_options* opts, int32_t B, int32_t N_max, const int32_t* model, const int32_t* n_frames,
@@ -2441,37 +2442,23 @@ cpe_status cpe_solve_kinetic_ragged_host(cpe_handle* h, const cpe_kinetic_option
     size_t F;
     if (cpe_status s = frames(B, N_max, &F); s != CPE_OK) return s;
     if (F == 0) return CPE_OK;
-    const cpe_dyn_options& d = opts[0].dyn;       // (the staging sizes: the counts every model shares, checked again by the solve)
-    if (d.n_feet < 1 || d.n_feet > 4 || d.n_motors < 0 || d.n_motors > CPE_MAX_MOTORS) return fail(CPE_BAD_ARG, "kinetic options: feet / motors out of range");
+    ForceStage fs;
+    if (cpe_status s = force_stage(opts[0].dyn, F, grf_fixed, tau_box, grf_box, fs); s != CPE_OK) return s;
     const DevModel& m = h->hm;
-    const size_t nf = (size_t)d.n_feet, nmo = (size_t)d.n_motors, nc = (size_t)n_con(m), nm = F * cams_max(h) * m.L;
+    const size_t nf = fs.nf, nmo = fs.nmo, nc = (size_t)n_con(m), nm = F * cams_max(h) * m.L;
     HIPCHK(hipSetDevice(h->device));
-    DevBuf di, dm_, dw_, dst, dfx, oq, odq, oddq, op, ome, ot, ol, og, osl;
-    const size_t n_fx = grf_fixed ? F * nf * 3 : (tau_box ? F * nmo * 2 : (grf_box ? F * nf * 6 : 0));
-    const double* fx = grf_fixed ? grf_fixed : (tau_box ? tau_box : grf_box);
-    HIPCHK(di.alloc(F * m.nq)); HIPCHK(dm_.alloc(nm * 2)); HIPCHK(dw_.alloc(nm)); HIPCHK(dst.alloc((F * nf + 1) / 2)); HIPCHK(dfx.alloc(n_fx));
-    HIPCHK(oq.alloc(F * m.nq)); HIPCHK(odq.alloc(F * m.nq)); HIPCHK(oddq.alloc(F * m.nq)); HIPCHK(op.alloc(F * m.L * 3)); HIPCHK(ome.alloc(nm * 2));
-    HIPCHK(ot.alloc(F * nmo)); HIPCHK(ol.alloc(F * nc)); HIPCHK(og.alloc(F * nf * 5)); HIPCHK(osl.alloc(F * m.nq));
-    int32_t* dstance = reinterpret_cast<int32_t*>(dst.p);
-    HIPCHK(hipMemcpyAsync(di.p, q_init, sizeof(double) * F * m.nq, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(dm_.p, meas, sizeof(double) * nm * 2, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(dw_.p, weight, sizeof(double) * nm, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(dstance, stance, sizeof(int32_t) * F * nf, hipMemcpyHostToDevice, h->stream));
-    if (fx) HIPCHK(hipMemcpyAsync(dfx.p, fx, sizeof(double) * n_fx, hipMemcpyHostToDevice, h->stream));
-    cpe_status s = cpe_solve_kinetic_ragged(h, opts, B, N_max, model, n_frames, di.p, dm_.p, dw_.p, dstance, grf_fixed ? dfx.p : nullptr,
-                                            tau_box ? dfx.p : nullptr, grf_box ? dfx.p : nullptr, oq.p, odq.p, oddq.p, op.p, ome.p, ot.p, ol.p, og.p, osl.p,
-                                            stats, kstats);
+    Staging st(h->stream);
+    const double *di = st.in(q_init, F * m.nq), *dmeas = st.in(meas, nm * 2), *dweight = st.in(weight, nm);
+    const int32_t* dstance = st.in(stance, F * nf);
+    const double* dfx = st.in(fs.fx, fs.n_fx);
+    double *oq = st.out(q, F * m.nq), *odq = st.out(dq, F * m.nq), *oddq = st.out(ddq, F * m.nq);
+    double *op = st.out(positions, F * m.L * 3), *ome = st.out(meas_err, nm * 2);
+    double *ot = st.out(tau, F * nmo), *ol = st.out(lambda, F * nc), *og = st.out(grf, F * nf * 5), *osl = st.out(slack, F * m.nq);
+    HIPCHK(st.err);
+    cpe_status s = cpe_solve_kinetic_ragged(h, opts, B, N_max, model, n_frames, di, dmeas, dweight, dstance, grf_fixed ? dfx : nullptr,
+                                            tau_box ? dfx : nullptr, grf_box ? dfx : nullptr, oq, odq, oddq, op, ome, ot, ol, og, osl, stats, kstats);
     if (s < 0) return s;
-    HIPCHK(hipMemcpyAsync(q, oq.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
-    if (dq) HIPCHK(hipMemcpyAsync(dq, odq.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
-    if (ddq) HIPCHK(hipMemcpyAsync(ddq, oddq.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
-    if (positions) HIPCHK(hipMemcpyAsync(positions, op.p, sizeof(double) * F * m.L * 3, hipMemcpyDeviceToHost, h->stream));
-    if (meas_err) HIPCHK(hipMemcpyAsync(meas_err, ome.p, sizeof(double) * nm * 2, hipMemcpyDeviceToHost, h->stream));
-    if (tau) HIPCHK(hipMemcpyAsync(tau, ot.p, sizeof(double) * F * nmo, hipMemcpyDeviceToHost, h->stream));
-    if (lambda) HIPCHK(hipMemcpyAsync(lambda, ol.p, sizeof(double) * F * nc, hipMemcpyDeviceToHost, h->stream));
-    if (grf) HIPCHK(hipMemcpyAsync(grf, og.p, sizeof(double) * F * nf * 5, hipMemcpyDeviceToHost, h->stream));
-    if (slack) HIPCHK(hipMemcpyAsync(slack, osl.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(st.fetch());
     return s;
 }
 
@@ -2491,45 +2478,26 @@ static cpe_status kinetic_tracked_host(cpe_handle* h, const cpe_kinetic_options*
     size_t F;
     if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
     if (F == 0) return CPE_OK;
-    const cpe_dyn_options& d = opts[0].dyn;
-    if (d.n_feet < 1 || d.n_feet > 4 || d.n_motors < 0 || d.n_motors > CPE_MAX_MOTORS) return fail(CPE_BAD_ARG, "kinetic options: feet / motors out of range");
+    ForceStage fs;
+    if (cpe_status s = force_stage(opts[0].dyn, F, grf_fixed, tau_box, grf_box, fs); s != CPE_OK) return s;
     const DevModel& m = h->hm;
     if (cpe_status s = check_target(q_target, B, N, m.nq, n_frames); s != CPE_OK) return s;
-    const size_t nf = (size_t)d.n_feet, nmo = (size_t)d.n_motors, nc = (size_t)n_con(m), nm = meas ? F * (model ? cams_max(h) : m.C) * m.L : 0;
+    const size_t nf = fs.nf, nmo = fs.nmo, nc = (size_t)n_con(m), nm = F * (model ? cams_max(h) : m.C) * m.L;
     HIPCHK(hipSetDevice(h->device));
-    DevBuf di, dt, dm_, dw_, dst, dfx, oq, odq, oddq, op, ome, ot, ol, og, osl;
-    const size_t n_fx = grf_fixed ? F * nf * 3 : (tau_box ? F * nmo * 2 : (grf_box ? F * nf * 6 : 0));
-    const double* fx = grf_fixed ? grf_fixed : (tau_box ? tau_box : grf_box);
-    HIPCHK(di.alloc(F * m.nq)); HIPCHK(dt.alloc(F * m.nq)); HIPCHK(dm_.alloc(nm * 2)); HIPCHK(dw_.alloc(nm)); HIPCHK(dst.alloc((F * nf + 1) / 2));
-    HIPCHK(dfx.alloc(n_fx)); HIPCHK(oq.alloc(F * m.nq)); HIPCHK(odq.alloc(F * m.nq)); HIPCHK(oddq.alloc(F * m.nq)); HIPCHK(op.alloc(F * m.L * 3));
-    HIPCHK(ome.alloc(nm * 2)); HIPCHK(ot.alloc(F * nmo)); HIPCHK(ol.alloc(F * nc)); HIPCHK(og.alloc(F * nf * 5)); HIPCHK(osl.alloc(F * m.nq));
-    int32_t* dstance = reinterpret_cast<int32_t*>(dst.p);
-    HIPCHK(hipMemcpyAsync(di.p, q_init, sizeof(double) * F * m.nq, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(dt.p, q_target, sizeof(double) * F * m.nq, hipMemcpyHostToDevice, h->stream));
-    if (meas) {
-        HIPCHK(hipMemcpyAsync(dm_.p, meas, sizeof(double) * nm * 2, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(dw_.p, weight, sizeof(double) * nm, hipMemcpyHostToDevice, h->stream));
-    }
-    HIPCHK(hipMemcpyAsync(dstance, stance, sizeof(int32_t) * F * nf, hipMemcpyHostToDevice, h->stream));
-    if (fx) HIPCHK(hipMemcpyAsync(dfx.p, fx, sizeof(double) * n_fx, hipMemcpyHostToDevice, h->stream));
-    const double *dmp = meas ? dm_.p : nullptr, *dwp = meas ? dw_.p : nullptr;
-    double* omp = meas ? ome.p : nullptr;
-    const double *gf = grf_fixed ? dfx.p : nullptr, *tb = tau_box ? dfx.p : nullptr, *gb = grf_box ? dfx.p : nullptr;
+    Staging st(h->stream);
+    const double *di = st.in(q_init, F * m.nq), *dt = st.in(q_target, F * m.nq), *dmeas = st.in(meas, nm * 2), *dweight = st.in(weight, nm);
+    const int32_t* dstance = st.in(stance, F * nf);
+    const double* dfx = st.in(fs.fx, fs.n_fx);
+    double *oq = st.out(q, F * m.nq), *odq = st.out(dq, F * m.nq), *oddq = st.out(ddq, F * m.nq), *op = st.out(positions, F * m.L * 3);
+    double* ome = meas ? st.out(meas_err, nm * 2) : nullptr;          // without measurements there are no reprojection errors
+    double *ot = st.out(tau, F * nmo), *ol = st.out(lambda, F * nc), *og = st.out(grf, F * nf * 5), *osl = st.out(slack, F * m.nq);
+    HIPCHK(st.err);
     // the target is checked here, on the host copy the caller handed in: the device entries' own copy back is skipped
-    const TrackIn tr{track_w, model ? n_models(h) : 1, dt.p, true};
-    cpe_status s = solve_kinetic_impl(h, opts, B, N, model, n_frames, di.p, dmp, dwp, dstance, gf, tb, gb, oq.p, odq.p, oddq.p, op.p, omp, ot.p, ol.p, og.p,
-                                      osl.p, stats, kstats, &tr);
+    const TrackIn tr{track_w, model ? n_models(h) : 1, dt, true};
+    cpe_status s = solve_kinetic_impl(h, opts, B, N, model, n_frames, di, dmeas, dweight, dstance, grf_fixed ? dfx : nullptr, tau_box ? dfx : nullptr,
+                                      grf_box ? dfx : nullptr, oq, odq, oddq, op, ome, ot, ol, og, osl, stats, kstats, &tr);
     if (s < 0) return s;
-    HIPCHK(hipMemcpyAsync(q, oq.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
-    if (dq) HIPCHK(hipMemcpyAsync(dq, odq.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
-    if (ddq) HIPCHK(hipMemcpyAsync(ddq, oddq.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
-    if (positions) HIPCHK(hipMemcpyAsync(positions, op.p, sizeof(double) * F * m.L * 3, hipMemcpyDeviceToHost, h->stream));
-    if (meas_err && meas) HIPCHK(hipMemcpyAsync(meas_err, ome.p, sizeof(double) * nm * 2, hipMemcpyDeviceToHost, h->stream));
-    if (tau) HIPCHK(hipMemcpyAsync(tau, ot.p, sizeof(double) * F * nmo, hipMemcpyDeviceToHost, h->stream));
-    if (lambda) HIPCHK(hipMemcpyAsync(lambda, ol.p, sizeof(double) * F * nc, hipMemcpyDeviceToHost, h->stream));
-    if (grf) HIPCHK(hipMemcpyAsync(grf, og.p, sizeof(double) * F * nf * 5, hipMemcpyDeviceToHost, h->stream));
-    if (slack) HIPCHK(hipMemcpyAsync(slack, osl.p, sizeof(double) * F * m.nq, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(st.fetch());
     return s;
 }
 

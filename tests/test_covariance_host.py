@@ -21,14 +21,19 @@ def lib():
     return _lib.load()
 
 
+def _prototypes():
+    """{name: [argument declarations]} of every function declared in include/cpe.h"""
+    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
+    found = re.findall(r"\b(?:cpe_status|int32_t|void\*?|const char\*)\s+(cpe_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", text)
+    return {name: [" ".join(a.split()) for a in args.split(",") if a.split() and a.split() != ["void"]] for name, args in found}
+
+
 def _prototype(name):
     """argument kinds of a prototype in include/cpe.h, in abi.COVARIANCE_ENTRIES' letters"""
-    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
-    m = re.search(r"cpe_status\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-    assert m, f"{name} is not declared in include/cpe.h"
+    protos = _prototypes()
+    assert name in protos, f"{name} is not declared in include/cpe.h"
     kinds = []
-    for arg in m.group(1).split(","):
-        a = " ".join(arg.split())
+    for a in protos[name]:
         if "cpe_handle*" in a:
             kinds.append("h")
         elif "cpe_priors*" in a:
@@ -44,6 +49,43 @@ def _prototype(name):
         else:
             raise AssertionError((name, a))
     return tuple(kinds)
+
+
+STRUCTS = {"cpe_skeleton": abi.Skeleton, "cpe_camera": abi.Camera, "cpe_options": abi.Options, "cpe_priors": abi.Priors, "cpe_stats": abi.Stats,
+           "cpe_grf_options": abi.GrfOptions, "cpe_eom_options": abi.EomOptions, "cpe_dyn_options": abi.DynOptions,
+           "cpe_kinetic_options": abi.KineticOptions, "cpe_kinetic_stats": abi.KineticStats}
+SCALARS = {"int32_t": C.c_int32, "cpe_status": C.c_int32, "int64_t": C.c_int64, "double": C.c_double}
+
+
+def _ctypes_of(decl):
+    """the ctypes types that may stand for one declared argument: a scalar is its own type; a pointer to a struct is a pointer to the struct's
+    mirror; a pointer to numbers is a typed pointer or, where device memory may stand behind it, c_void_p; a handle or a stream is c_void_p"""
+    m = re.fullmatch(r"(?:const )?(\w+)(\*{0,2}) \w+(\[\w*\])?", decl)
+    assert m, decl
+    base, stars = m.group(1), len(m.group(2)) + (1 if m.group(3) else 0)
+    if base == "cpe_handle":
+        return {1: [C.c_void_p], 2: [C.POINTER(C.c_void_p)]}[stars]
+    if base == "void":
+        assert stars == 1, decl
+        return [C.c_void_p]
+    if base in STRUCTS:
+        assert stars == 1, decl
+        return [C.POINTER(STRUCTS[base])]
+    return [SCALARS[base]] if stars == 0 else [C.POINTER(SCALARS[base]), C.c_void_p]
+
+
+def test_every_prototype_has_its_argument_list(lib):
+    """abi.ENTRIES names every function include/cpe.h declares and nothing else, and the argtypes _lib.load() sets from it have every prototype's
+    length and, argument by argument, its kind: a miscounted list fails here instead of handing C shifted arguments"""
+    protos = _prototypes()
+    assert len(protos) >= 56 and set(protos) == set(abi.ENTRIES)
+    for name, decls in protos.items():
+        argtypes = getattr(lib, name).argtypes
+        assert argtypes is not None and len(argtypes) == len(decls), (name, len(argtypes or ()), len(decls))
+        assert list(argtypes) == abi.argtypes(name), name
+        for i, (t, decl) in enumerate(zip(argtypes, decls)):
+            assert t in _ctypes_of(decl), (name, i, decl, t)
+    assert lib.cpe_last_error.restype is C.c_char_p and lib.cpe_stream.restype is C.c_void_p
 
 
 def test_symbols_and_ctypes_mirror(lib):
