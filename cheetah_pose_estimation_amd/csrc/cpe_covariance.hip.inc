@@ -224,7 +224,7 @@ __global__ __launch_bounds__(COV_THREADS, 1) void k_lm_selinv(const SeqState* __
 }
 
 // ---- marker covariance, one wave per frame: cov_pos[l] = P_l Sigma(n,n) P_l^T with P_l = d p_l / d u, the reduced marker columns Dp of
-// k_frame_normal (same tables, same device functions, same order of the terms; the sums into Dp run per item in list order here -- one
+// k_frame_normal (same tables, same state phases, same order of the terms; the sums into Dp run per item in list order here -- one
 // lane per item -- so no LDS atomics are needed).  State: the current buffer of the sequence, as k_frame_normal left it.
 // dynamic LDS: state | sin / cos | leg sin / cos | trunk R, dR | dynamic vectors | S rows | Dp | Sigma(n,n) | first term of every item (int)
 template <bool RAGGED = false>
@@ -233,14 +233,12 @@ __global__ __launch_bounds__(WAVE) void k_marker_cov(const DevModel* __restrict_
                                                      double* __restrict__ cov_pos, RaggedArgs rg = RaggedArgs{}) {
     extern __shared__ double smem[];
     const int lane = threadIdx.x;
-    const int b = (int)(blockIdx.x / (unsigned)N);
-    if constexpr (RAGGED) {
-        const int2 rs = rg.seq[b];
-        if ((int)(blockIdx.x % (unsigned)N) >= rs.y) return;
-        M += rs.x;
-    }
+    FrameSlot fs;
+    if (!frame_slot<RAGGED>(N, nullptr, nullptr, rg, fs)) return;
+    M += fs.model;
+    const int b = fs.b;
     if (!cov_seq_ok(st, b)) return;
-    const size_t f = (size_t)b * N + blockIdx.x % (unsigned)N;
+    const size_t f = (size_t)b * N + fs.n;
     const int buf = st[b].cur;
     const int nq = M->nq, nl = M->nl, L = M->L, nrev = M->nrev, ns = M->ns, svn = M->sv_n, mct = M->mc_total;
     double* sq = smem;
@@ -265,68 +263,14 @@ __global__ __launch_bounds__(WAVE) void k_marker_cov(const DevModel* __restrict_
     for (int t = lane; t < ns; t += WAVE) sq[t] = stf[t];
     for (int t = lane; t < NU * NU; t += WAVE) sSig[t] = cov_diag[f * (size_t)(NU * NU) + t];
     wave_lds_sync();
-    wave_sincos(M, sq, ssc, lane);
-    if (lane < nrev) { double s_, c_; sincos(sal[lane], &s_, &c_); ssa[2 * lane] = s_; ssa[2 * lane + 1] = c_; }
+    // ---- the state phases (cpe_kernels.hip); the legs' Euler angles are not rebuilt: the state holds them
+    wave_state_sincos(M, sq, sal, ssc, ssa, nrev, lane);
     wave_lds_sync();
-    // hooke joints: phi of the tails in closed form (as k_frame_normal)
-    for (int level = 0; level < 2; level++) {
-        if (lane < hj_n && ((fw.x >> 16) & 1) == level) {
-            const int p = fw.x & 255, c = (fw.x >> 8) & 255;
-            double a[3];
-            rot_ycol(ssc + 6 * p, a);
-            const double st_ = ssc[6 * c + 2], ct = ssc[6 * c + 3], sp = ssc[6 * c + 4], cp = ssc[6 * c + 5];
-            const double num = a[0] * st_ * cp + a[1] * st_ * sp + a[2] * ct;
-            const double den = a[1] * cp - a[0] * sp;
-            const double hyp = sqrt(num * num + den * den);
-            sq[3 + 3 * c] = atan2(num, den);
-            ssc[6 * c] = num / hyp; ssc[6 * c + 1] = den / hyp;
-        }
-        wave_lds_sync();
-    }
-    if (lane < 4 * M->n_trunk) rot_kind(ssc + 6 * fw.y, lane & 3, sR + 9 * lane);
-    for (int t = WAVE + lane; t < 4 * M->n_trunk; t += WAVE) rot_kind(ssc + 6 * M->trunk_link[t >> 2], t & 3, sR + 9 * t);
-    // dynamic body-frame vectors of the leg markers
-    if (lane < svn) {
-        double d0 = 0.0, d1 = 0.0, d2 = 0.0;
-        if ((fw.w & 3) == 0) {
-            const int cnt = (fw.w >> 2) & 3;
-#pragma unroll
-            for (int i = 0; i < 3; i++) {
-                const int r = (fw.w >> (4 + 6 * i)) & 63;
-                const double sa = ssa[2 * r], ca = ssa[2 * r + 1];
-                if (i < cnt) { d0 += ca * svv[i][0] + sa * svv[i][2]; d1 += svv[i][1]; d2 += -sa * svv[i][0] + ca * svv[i][2]; }
-            }
-        } else {
-            const int r = (fw.w >> 4) & 63;
-            const double sa = ssa[2 * r], ca = ssa[2 * r + 1];
-            d0 = -sa * svv[0][0] + ca * svv[0][2]; d2 = -ca * svv[0][0] - sa * svv[0][2];
-        }
-        sdyn[3 * lane] = d0; sdyn[3 * lane + 1] = d1; sdyn[3 * lane + 2] = d2;
-    }
+    wave_tail_roll(sq, ssc, hj_n, fw.x, lane);
+    wave_trunk_rotations(M, ssc, sR, fw.y, lane);
+    wave_leg_vectors(ssa, sdyn, svn, fw.w, svv, lane);
     wave_lds_sync();
-    // S rows of the hooke joints (tails): d phi_c / d(independent), level by level
-    for (int level = 0; level < 2; level++) {
-        if (lane < hk_n && ((hkw.x >> 16) & 1) == level) {
-            const double* Rp = sR + 36 * (hkw.x & 63); const double* Rc = sR + 36 * ((hkw.x >> 6) & 63);
-            const double y0 = Rp[1], y1 = Rp[4], y2 = Rp[7];
-            const double z0 = Rc[2], z1 = Rc[5], z2 = Rc[8];
-            const double* Dcphi = Rc + 9;
-            const double gphi = y0 * Dcphi[2] + y1 * Dcphi[5] + y2 * Dcphi[8];
-            const int kind = (hkw.x >> 12) & 3, ang = (hkw.x >> 14) & 3;
-            double direct = 0.0;
-            if (kind == 0) { const double* D = Rc + 9 * (1 + ang); direct = y0 * D[2] + y1 * D[5] + y2 * D[8]; }
-            else if (kind == 1) { const double* D = Rp + 9 * (1 + ang); direct = D[1] * z0 + D[4] * z1 + D[7] * z2; }
-            double val = -direct / gphi;
-            const int ch = (hkw.y & 0xFFFF) - 1;
-            if (ch >= 0) {
-                const double* Dpphi = Rp + 9;
-                const double t0 = -(Dpphi[1] * z0 + Dpphi[4] * z1 + Dpphi[7] * z2) / gphi;
-                val += t0 * sSv[ch];
-            }
-            sSv[hkw.y >> 16] = val;
-        }
-        wave_lds_sync();
-    }
+    wave_hooke_srows(sR, sSv, hk_n, hkw, lane);
     // reduced marker columns: the terms of one item (marker, column) sit next to each other in M->tl, in item order; a first pass marks where
     // every item's terms begin, then item t sums its own terms in list order
     const int ntl = M->tl_n;

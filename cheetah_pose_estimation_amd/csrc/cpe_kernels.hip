@@ -64,6 +64,17 @@ __device__ __forceinline__ void slot_dp(const DevModel* __restrict__ M, const do
     }
 }
 
+// roll of a hooke child in closed form: the phi at which the child's z axis is normal to the parent's y axis a (rot_ycol of the parent), from
+// the sin / cos of the child's theta (st, ct) and psi (sp, cp).  Returns phi and its sin / cos.  The callers form a themselves: with rot_ycol
+// in here the compiler contracts num's sum from another term in k_frame_normal, and the state's last bit moves.
+__device__ __forceinline__ void hooke_roll(const double* a, double st, double ct, double sp, double cp, double& phi, double& sphi, double& cphi) {
+    const double num = a[0] * st * cp + a[1] * st * sp + a[2] * ct;
+    const double den = a[1] * cp - a[0] * sp;
+    const double hyp = sqrt(num * num + den * den);
+    phi = atan2(num, den);
+    sphi = num / hyp; cphi = den / hyp;
+}
+
 // closed-form solution of the joint equalities for the dependent angles (branch
 // child.y = +parent.y reached from the reference's initial guess, acinoset_opt.py:574-583).
 // Updates sq and ssc in place; returns non-zero in every lane if some revolute child sits in the gimbal
@@ -92,18 +103,100 @@ __device__ __forceinline__ int wave_project_joints(const DevModel* __restrict__ 
                     ssc[6 * c + 4] = s; ssc[6 * c + 5] = co;
                 } else {
                     rot_ycol(ssc + 6 * p, a);
-                    const double sp = ssc[6 * c + 4], cp = ssc[6 * c + 5];
-                    const double num = a[0] * st * cp + a[1] * st * sp + a[2] * ct;
-                    const double den = a[1] * cp - a[0] * sp;
-                    const double hyp = sqrt(num * num + den * den);
-                    sq[3 + 3 * c] = atan2(num, den);
-                    ssc[6 * c] = num / hyp; ssc[6 * c + 1] = den / hyp;
+                    double phi, sphi, cphi;
+                    hooke_roll(a, st, ct, ssc[6 * c + 4], ssc[6 * c + 5], phi, sphi, cphi);
+                    sq[3 + 3 * c] = phi;
+                    ssc[6 * c] = sphi; ssc[6 * c + 1] = cphi;
                 }
             }
         }
         wave_lds_sync();
     }
     return __any(clamped);
+}
+
+// --------------------------------------------------------------------------------------------------
+// State phases of the solver's per-frame kernels (k_frame_normal, k_frame_tracked, k_marker_cov): what each of them rebuilds from the state
+// (q, alpha) before its own work, in this order.  The helpers read no model table: the caller loads its lane's packed words (DevModel::fn_lane
+// = fw, hk_w, sv_vec; cpe_model.h) where its prefetches belong and passes them in.  (wave_leg_state, the legs' Euler angles, is in cpe_solver.hip.inc.)
+
+// sin / cos of the state: the link angles -> ssc (wave_sincos), the leg angles alpha -> ssa[2 r + {0,1}]
+__device__ __forceinline__ void wave_state_sincos(const DevModel* __restrict__ M, const double* sq, const double* sal, double* ssc, double* ssa,
+                                                  int nrev, int lane) {
+    wave_sincos(M, sq, ssc, lane);
+    if (lane < nrev) { double s_, c_; sincos(sal[lane], &s_, &c_); ssa[2 * lane] = s_; ssa[2 * lane + 1] = c_; }
+}
+
+// hooke joints: phi of the tails in closed form, one joint per lane from its word fwx (parent | child << 8 | level << 16), level by level:
+// a level-1 joint hangs on a link whose own roll is set at level 0
+__device__ __forceinline__ void wave_tail_roll(double* sq, double* ssc, int hj_n, int fwx, int lane) {
+    for (int level = 0; level < 2; level++) {
+        if (lane < hj_n && ((fwx >> 16) & 1) == level) {
+            const int p = fwx & 255, c = (fwx >> 8) & 255;
+            double a[3], phi, sphi, cphi;
+            rot_ycol(ssc + 6 * p, a);
+            hooke_roll(a, ssc[6 * c + 2], ssc[6 * c + 3], ssc[6 * c + 4], ssc[6 * c + 5], phi, sphi, cphi);
+            sq[3 + 3 * c] = phi;
+            ssc[6 * c] = sphi; ssc[6 * c + 1] = cphi;
+        }
+        wave_lds_sync();
+    }
+}
+
+// R and dR/d(phi,theta,psi) of the TRUNK links only (leg links are body rotations) -> sR[9 * (4 * trunk slot + kind)]; fwy = the trunk link
+// of the lane's block
+__device__ __forceinline__ void wave_trunk_rotations(const DevModel* __restrict__ M, const double* ssc, double* sR, int fwy, int lane) {
+    if (lane < 4 * M->n_trunk) rot_kind(ssc + 6 * fwy, lane & 3, sR + 9 * lane);
+    for (int t = WAVE + lane; t < 4 * M->n_trunk; t += WAVE) rot_kind(ssc + 6 * M->trunk_link[t >> 2], t & 3, sR + 9 * t);     // more than 16 trunk links
+}
+
+// dynamic body-frame vector `lane` of the leg markers -> sdyn[3 lane]: sum_i Ry(alpha_r_i) v_i, or dRy/dalpha(alpha_r_0) v_0, from the lane's
+// word fww (kind | count << 2 | r_0..2 << 4, 10, 16) and its vectors svv
+__device__ __forceinline__ void wave_leg_vectors(const double* ssa, double* sdyn, int svn, int fww, const double (&svv)[3][3], int lane) {
+    if (lane < svn) {                                      // sv_n <= CPE_MAX_SDYN < 64
+        double d0 = 0.0, d1 = 0.0, d2 = 0.0;
+        if ((fww & 3) == 0) {
+            const int cnt = (fww >> 2) & 3;
+#pragma unroll
+            for (int i = 0; i < 3; i++) {
+                const int r = (fww >> (4 + 6 * i)) & 63;
+                const double sa = ssa[2 * r], ca = ssa[2 * r + 1];
+                if (i < cnt) { d0 += ca * svv[i][0] + sa * svv[i][2]; d1 += svv[i][1]; d2 += -sa * svv[i][0] + ca * svv[i][2]; }
+            }
+        } else {
+            const int r = (fww >> 4) & 63;
+            const double sa = ssa[2 * r], ca = ssa[2 * r + 1];
+            d0 = -sa * svv[0][0] + ca * svv[0][2]; d2 = -ca * svv[0][0] - sa * svv[0][2];
+        }
+        sdyn[3 * lane] = d0; sdyn[3 * lane + 1] = d1; sdyn[3 * lane + 2] = d2;
+    }
+}
+
+// S rows of the hooke joints (tails): d phi_c / d(independent) -> sSv, level by level; one host-resolved item per lane, hkw (cpe_model.h).
+// A level-1 item (the parent's own roll is dependent) adds d phi_c / d phi_parent times the parent's level-0 entry of that column.
+__device__ __forceinline__ void wave_hooke_srows(const double* sR, double* sSv, int hk_n, int2 hkw, int lane) {
+    for (int level = 0; level < 2; level++) {
+        if (lane < hk_n && ((hkw.x >> 16) & 1) == level) {
+            const double* Rp = sR + 36 * (hkw.x & 63); const double* Rc = sR + 36 * ((hkw.x >> 6) & 63);
+            const double y0 = Rp[1], y1 = Rp[4], y2 = Rp[7];
+            const double z0 = Rc[2], z1 = Rc[5], z2 = Rc[8];
+            const double* Dcphi = Rc + 9;
+            const double gphi = y0 * Dcphi[2] + y1 * Dcphi[5] + y2 * Dcphi[8];
+            const int kind = (hkw.x >> 12) & 3, ang = (hkw.x >> 14) & 3;
+            double direct = 0.0;
+            if (kind == 0) { const double* D = Rc + 9 * (1 + ang); direct = y0 * D[2] + y1 * D[5] + y2 * D[8]; }
+            else if (kind == 1) { const double* D = Rp + 9 * (1 + ang); direct = D[1] * z0 + D[4] * z1 + D[7] * z2; }
+            double val = -direct / gphi;
+            const int ch = (hkw.y & 0xFFFF) - 1;
+            if (ch >= 0) {
+                const double* Dpphi = Rp + 9;
+                const double t0 = -(Dpphi[1] * z0 + Dpphi[4] * z1 + Dpphi[7] * z2) / gphi;
+                val += t0 * sSv[ch];
+            }
+            sSv[hkw.y >> 16] = val;
+        }
+        wave_lds_sync();
+    }
 }
 
 // --------------------------------------------------------------------------------------------------

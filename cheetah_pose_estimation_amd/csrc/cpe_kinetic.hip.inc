@@ -1221,15 +1221,11 @@ __global__ __launch_bounds__(KIN_THREADS) void k_dyn_gather(const SeqState* __re
                                                             const double* __restrict__ Bbuf, const double* __restrict__ Tbuf, const double* __restrict__ gT,
                                                             double* __restrict__ gk, double* __restrict__ Bk, double* __restrict__ Hk,
                                                             const int* __restrict__ act, const int* __restrict__ n_act, RaggedArgs rg = RaggedArgs{}) {
-    if (n_act && (int)(blockIdx.x / (unsigned)N) >= *n_act) return;
+    FrameSlot fs;
+    if (!frame_slot<RAGGED>(N, act, n_act, rg, fs)) return;
     const int tid = threadIdx.x;
-    const int b = act ? act[blockIdx.x / (unsigned)N] : (int)(blockIdx.x / (unsigned)N), m = (int)(blockIdx.x % (unsigned)N);
+    const int b = fs.b, m = fs.n, NL = fs.len;           // N: the buffers' frames per sequence, NL: this sequence's length (nodes m + 1, m + 2 inside it)
     const size_t f_ = (size_t)b * N + m;
-    int NL = N;                                          // N: the buffers' frames per sequence, NL: this sequence's length (nodes m + 1, m + 2 inside it)
-    if constexpr (RAGGED) {
-        NL = rg.seq[b].y;
-        if (m >= NL) return;
-    }
     const SeqState Sq = st[b];
     if (Sq.status != 0 || Sq.al_pending) return;
     const size_t fo = (size_t)Sq.cur * n_frames + f_;
@@ -1264,13 +1260,12 @@ __global__ void k_dyn_outputs(const DevKin* __restrict__ K, const SeqState* __re
                               const double* __restrict__ Abuf, const double* __restrict__ dummy, double* __restrict__ tau, double* __restrict__ lam,
                               double* __restrict__ grf, RaggedArgs rg = RaggedArgs{} /* RAGGED: frames past a sequence's own are written as zeros */) {
     const size_t f_ = blockIdx.x;
-    const int b = (int)(f_ / (size_t)N), n = (int)(f_ - (size_t)b * N), t = threadIdx.x;
+    FrameSlot fs;
+    const bool own = frame_slot<RAGGED>(N, nullptr, nullptr, rg, fs);
+    K += fs.model;                                         // (the counts nm, nc, nf are the same in every model of the handle)
+    const int b = fs.b, n = fs.n, t = threadIdx.x;
     const double* f = fbuf + ((size_t)st[b].cur * n_frames + f_) * KIN_LS;
-    bool on = n >= 2;
-    if constexpr (RAGGED) {                                // (the counts nm, nc, nf are the same in every model of the handle)
-        const int2 rs = rg.seq[b];
-        K += rs.x; on = on && n < rs.y;
-    }
+    const bool on = n >= 2 && own;
     if (tau && t < K->nm) tau[f_ * K->nm + t] = on ? f[t] : 0.0;
     if (lam && t < K->nc) lam[f_ * K->nc + t] = on ? f[K->nm + t] : 0.0;
     if (grf && t < K->nf) {

@@ -51,6 +51,35 @@ struct LmParams {
 // kinematic solve take it as a compile-time form (RAGGED = true, launched with the table); their plain forms never read it.
 struct RaggedArgs { const int2* seq; int nmax; int cstride; };
 
+// The slot of a per-frame workgroup: workgroup blockIdx.x of a launch over N frames per sequence works on frame n of sequence b -- frame
+// f = b N + n of the buffers -- which solves device model `model` (an offset the caller adds to its per-model tables: M += s.model) over its
+// first `len` frames.
+struct FrameSlot { int b, n, model, len; };
+// act / n_act: the sequences of this launch and how many of them are in use (a device word), or null = all.  False: the workgroup has nothing
+// to do -- past the active list, or RAGGED and past the sequence's own length (the slot is filled all the same).  Plain form: model 0, len N,
+// both compile-time.  The status of the sequence is the caller's to test.
+template <bool RAGGED>
+__device__ __forceinline__ bool frame_slot(int N, const int* __restrict__ act, const int* __restrict__ n_act, const RaggedArgs& rg, FrameSlot& s) {
+    const unsigned i = blockIdx.x / (unsigned)N;
+    if (n_act && (int)i >= *n_act) return false;
+    s.b = act ? act[i] : (int)i;
+    s.n = (int)(blockIdx.x % (unsigned)N);
+    s.model = 0; s.len = N;
+    if constexpr (RAGGED) {
+        const int2 rs = rg.seq[s.b];
+        s.model = rs.x; s.len = rs.y;
+        if (s.n >= rs.y) return false;
+    }
+    return true;
+}
+// the same for a kernel over all frames that is not told N: the ragged form has it in rg.nmax, the plain form needs no slot (model 0)
+template <bool RAGGED>
+__device__ __forceinline__ bool frame_slot_flat(const RaggedArgs& rg, FrameSlot& s) {
+    if constexpr (RAGGED) return frame_slot<true>(rg.nmax, nullptr, nullptr, rg, s);
+    s = FrameSlot{0, 0, 0, 0};
+    return true;
+}
+
 #define COST_STRIDE 8   // per-frame cost record: meas, bound(AL), pose, clamped, max bound violation, autoregressive prior
 
 // --------------------------------------------------------------------------------------------------
@@ -91,29 +120,42 @@ __device__ __forceinline__ void leg_euler(const double* RB, const double* scB, d
     gam[3] = cphic * sfB * ctB - sphic * (ca * cfB * ctB - sa * stB);
 }
 
+// State phase (after the trunk rotations, cpe_kernels.hip): Euler triple of leg link `lane` -> sq, and its constant Gamma row of the cost
+// pitch theta_B + alpha_c, d / d (alpha_c, phi_B, theta_B, psi_B) = (1, 0, 1, 0), -> sgam.  fwz = body | child << 8 | body's trunk slot << 16
+__device__ __forceinline__ void wave_leg_state(double* sq, const double* ssc, const double* ssa, const double* sR, double* sgam, int nrev,
+                                               int fwz, int lane) {
+    if (lane < nrev) {
+        const int Bk = fwz & 255, c = (fwz >> 8) & 255;
+        double e[3];
+        double gtrue[GAM_STRIDE];
+        leg_euler(sR + 36 * (fwz >> 16), ssc + 6 * Bk, ssa[2 * lane], ssa[2 * lane + 1], sq[3 + 3 * Bk + 2], e, gtrue);
+        sq[3 + 3 * c] = e[0]; sq[3 + 3 * c + 1] = e[1]; sq[3 + 3 * c + 2] = e[2];
+        sgam[GAM_STRIDE * lane] = 1.0; sgam[GAM_STRIDE * lane + 1] = 0.0; sgam[GAM_STRIDE * lane + 2] = 1.0; sgam[GAM_STRIDE * lane + 3] = 0.0;
+    }
+}
+
+// the inverse, for a state built from an Euler q: alpha = rotation of R_B^T R_c about y, from the Euler triples of the body and of the leg link
+__device__ __forceinline__ double leg_alpha(const double* qb, const double* qc) {
+    double scb[6], scc[6], RB[9], RC[9];
+    for (int a = 0; a < 3; a++) { sincos(qb[a], &scb[2 * a], &scb[2 * a + 1]); sincos(qc[a], &scc[2 * a], &scc[2 * a + 1]); }
+    rot_kind(scb, 0, RB); rot_kind(scc, 0, RC);
+    const double m00 = RB[0] * RC[0] + RB[3] * RC[3] + RB[6] * RC[6], m02 = RB[0] * RC[2] + RB[3] * RC[5] + RB[6] * RC[8];
+    return atan2(m02, m00);
+}
+
 // --------------------------------------------------------------------------------------------------
-// initial state from an Euler q: alpha_r = rotation of R_B^T R_c about y.  One wave per frame.
+// initial state from an Euler q: alpha_r = leg_alpha.  One wave per frame.
 template <bool RAGGED = false>
 __global__ __launch_bounds__(WAVE) void k_state_init(const DevModel* __restrict__ M, const double* __restrict__ q, double* __restrict__ state,
                                                     RaggedArgs rg = RaggedArgs{}) {
     const int lane = threadIdx.x;
     const size_t f = blockIdx.x;
-    if constexpr (RAGGED) {                                // padding frames stay unset: nothing reads them
-        const int2 rs = rg.seq[f / (unsigned)rg.nmax];
-        if ((int)(f % (unsigned)rg.nmax) >= rs.y) return;
-        M += rs.x;
-    }
+    FrameSlot s;
+    if (!frame_slot_flat<RAGGED>(rg, s)) return;           // padding frames stay unset: nothing reads them
+    M += s.model;
     const int nq = M->nq, ns = M->ns;
     if (lane < nq) state[f * ns + lane] = q[f * nq + lane];
-    if (lane < M->nrev) {
-        const double* qb = q + f * nq + 3 + 3 * M->rev_body[lane];
-        const double* qc = q + f * nq + 3 + 3 * M->rev_child[lane];
-        double scb[6], scc[6], RB[9], RC[9];
-        for (int a = 0; a < 3; a++) { sincos(qb[a], &scb[2 * a], &scb[2 * a + 1]); sincos(qc[a], &scc[2 * a], &scc[2 * a + 1]); }
-        rot_kind(scb, 0, RB); rot_kind(scc, 0, RC);
-        const double m00 = RB[0] * RC[0] + RB[3] * RC[3] + RB[6] * RC[6], m02 = RB[0] * RC[2] + RB[3] * RC[5] + RB[6] * RC[8];
-        state[f * ns + nq + lane] = atan2(m02, m00);
-    }
+    if (lane < M->nrev) state[f * ns + nq + lane] = leg_alpha(q + f * nq + 3 + 3 * M->rev_body[lane], q + f * nq + 3 + 3 * M->rev_child[lane]);
 }
 
 // --------------------------------------------------------------------------------------------------
@@ -146,14 +188,11 @@ __global__ __launch_bounds__(WAVE) void k_frame_normal(const DevModel* __restric
                                                        RaggedArgs rg = RaggedArgs{} /* RAGGED: N = nmax, no shutter delay */) {
     extern __shared__ double smem[];
     const int lane = threadIdx.x;
-    if (n_act && (int)(blockIdx.x / (unsigned)N) >= *n_act) return;
-    const int b = act ? act[blockIdx.x / (unsigned)N] : (int)(blockIdx.x / (unsigned)N);
-    if constexpr (RAGGED) {                              // frames past the sequence's own length leave at once
-        const int2 rs = rg.seq[b];
-        if ((int)(blockIdx.x % (unsigned)N) >= rs.y) return;
-        M += rs.x;
-    }
-    const size_t f = (size_t)b * N + blockIdx.x % (unsigned)N;
+    FrameSlot fs;
+    if (!frame_slot<RAGGED>(N, act, n_act, rg, fs)) return;
+    M += fs.model;
+    const int b = fs.b;
+    const size_t f = (size_t)b * N + fs.n;
     const SeqState S = st[b];
     if (S.status != 0) return;
     const int pend = S.al_pending;                       // multiplier update: re-evaluate the CURRENT iterate
@@ -195,55 +234,14 @@ __global__ __launch_bounds__(WAVE) void k_frame_normal(const DevModel* __restric
     for (int t = lane; t < ns; t += WAVE) sq[t] = stf[t];  // q and alpha are contiguous in LDS too (sal = sq + nq); ns may exceed 64
     for (int t = lane; t < 9 * L; t += WAVE) sMv[t] = 0.0;
     wave_lds_sync();
-    wave_sincos(M, sq, ssc, lane);
-    if (lane < nrev) { double s_, c_; sincos(sal[lane], &s_, &c_); ssa[2 * lane] = s_; ssa[2 * lane + 1] = c_; }
+    // ---- the state phases (cpe_kernels.hip)
+    wave_state_sincos(M, sq, sal, ssc, ssa, nrev, lane);
     wave_lds_sync();
-    // hooke joints: phi of the tails in closed form (the hooke branch of wave_project_joints, cpe_kernels.hip, from the lane's packed word)
-    for (int level = 0; level < 2; level++) {
-        if (lane < hj_n && ((fw.x >> 16) & 1) == level) {
-            const int p = fw.x & 255, c = (fw.x >> 8) & 255;
-            double a[3];
-            rot_ycol(ssc + 6 * p, a);
-            const double st = ssc[6 * c + 2], ct = ssc[6 * c + 3], sp = ssc[6 * c + 4], cp = ssc[6 * c + 5];
-            const double num = a[0] * st * cp + a[1] * st * sp + a[2] * ct;
-            const double den = a[1] * cp - a[0] * sp;
-            const double hyp = sqrt(num * num + den * den);
-            sq[3 + 3 * c] = atan2(num, den);
-            ssc[6 * c] = num / hyp; ssc[6 * c + 1] = den / hyp;
-        }
-        wave_lds_sync();
-    }
-    // R and dR of the trunk links only (leg links are body rotations)
-    if (lane < 4 * M->n_trunk) rot_kind(ssc + 6 * fw.y, lane & 3, sR + 9 * lane);
-    for (int t = WAVE + lane; t < 4 * M->n_trunk; t += WAVE) rot_kind(ssc + 6 * M->trunk_link[t >> 2], t & 3, sR + 9 * t);     // more than 16 trunk links
+    wave_tail_roll(sq, ssc, hj_n, fw.x, lane);
+    wave_trunk_rotations(M, ssc, sR, fw.y, lane);
     wave_lds_sync();
-    // leg Euler angles + Gamma rows; dynamic body-frame vectors of the leg markers
-    if (lane < nrev) {
-        const int Bk = fw.z & 255, c = (fw.z >> 8) & 255;
-        double e[3];
-        double gtrue[GAM_STRIDE];
-        leg_euler(sR + 36 * (fw.z >> 16), ssc + 6 * Bk, ssa[2 * lane], ssa[2 * lane + 1], sq[3 + 3 * Bk + 2], e, gtrue);
-        sq[3 + 3 * c] = e[0]; sq[3 + 3 * c + 1] = e[1]; sq[3 + 3 * c + 2] = e[2];
-        // d (cost pitch) / d (alpha_c, phi_B, theta_B, psi_B): theta_B + alpha_c
-        sgam[GAM_STRIDE * lane] = 1.0; sgam[GAM_STRIDE * lane + 1] = 0.0; sgam[GAM_STRIDE * lane + 2] = 1.0; sgam[GAM_STRIDE * lane + 3] = 0.0;
-    }
-    if (lane < svn) {                                      // sv_n <= CPE_MAX_SDYN < 64
-        double d0 = 0.0, d1 = 0.0, d2 = 0.0;
-        if ((fw.w & 3) == 0) {
-            const int cnt = (fw.w >> 2) & 3;
-#pragma unroll
-            for (int i = 0; i < 3; i++) {
-                const int r = (fw.w >> (4 + 6 * i)) & 63;
-                const double sa = ssa[2 * r], ca = ssa[2 * r + 1];
-                if (i < cnt) { d0 += ca * svv[i][0] + sa * svv[i][2]; d1 += svv[i][1]; d2 += -sa * svv[i][0] + ca * svv[i][2]; }
-            }
-        } else {
-            const int r = (fw.w >> 4) & 63;
-            const double sa = ssa[2 * r], ca = ssa[2 * r + 1];
-            d0 = -sa * svv[0][0] + ca * svv[0][2]; d2 = -ca * svv[0][0] - sa * svv[0][2];
-        }
-        sdyn[3 * lane] = d0; sdyn[3 * lane + 1] = d1; sdyn[3 * lane + 2] = d2;
-    }
+    wave_leg_state(sq, ssc, ssa, sR, sgam, nrev, fw.z, lane);
+    wave_leg_vectors(ssa, sdyn, svn, fw.w, svv, lane);
     wave_lds_sync();
     if (lane < nq) stf[lane] = sq[lane];                  // Euler part of the state, consistent with the joint equalities
     if (lane < GAM_STRIDE * nrev) gambuf[((size_t)buf * n_frames + f) * (GAM_STRIDE * nrev) + lane] = sgam[lane];
@@ -255,29 +253,7 @@ __global__ __launch_bounds__(WAVE) void k_frame_normal(const DevModel* __restric
     for (int k = 0; k < CPE_MAX_CHAIN; k++) { pco[k] = M->pc_off[lm_][k]; pcv[k][0] = M->pc_vec[lm_][k][0]; pcv[k][1] = M->pc_vec[lm_][k][1]; pcv[k][2] = M->pc_vec[lm_][k][2]; }
     const int pwid = M->pw_id[lm_], pwo = M->pw_off[lm_];
     FSTAMP(0);
-    // ---- S rows of the hooke joints (tails): d phi_c / d(independent), level by level; one host-resolved item per lane (cpe_model.h)
-    for (int level = 0; level < 2; level++) {
-        if (lane < hk_n && ((hkw.x >> 16) & 1) == level) {
-            const double* Rp = sR + 36 * (hkw.x & 63); const double* Rc = sR + 36 * ((hkw.x >> 6) & 63);
-            const double y0 = Rp[1], y1 = Rp[4], y2 = Rp[7];
-            const double z0 = Rc[2], z1 = Rc[5], z2 = Rc[8];
-            const double* Dcphi = Rc + 9;
-            const double gphi = y0 * Dcphi[2] + y1 * Dcphi[5] + y2 * Dcphi[8];
-            const int kind = (hkw.x >> 12) & 3, ang = (hkw.x >> 14) & 3;
-            double direct = 0.0;
-            if (kind == 0) { const double* D = Rc + 9 * (1 + ang); direct = y0 * D[2] + y1 * D[5] + y2 * D[8]; }
-            else if (kind == 1) { const double* D = Rp + 9 * (1 + ang); direct = D[1] * z0 + D[4] * z1 + D[7] * z2; }
-            double val = -direct / gphi;
-            const int ch = (hkw.y & 0xFFFF) - 1;
-            if (ch >= 0) {
-                const double* Dpphi = Rp + 9;
-                const double t0 = -(Dpphi[1] * z0 + Dpphi[4] * z1 + Dpphi[7] * z2) / gphi;
-                val += t0 * sSv[ch];
-            }
-            sSv[hkw.y >> 16] = val;
-        }
-        wave_lds_sync();
-    }
+    wave_hooke_srows(sR, sSv, hk_n, hkw, lane);
 
     FSTAMP(1);
     // ---- marker positions: x + sum_trunk R_k v_k + R_B w(alpha)
@@ -358,7 +334,7 @@ __global__ __launch_bounds__(WAVE) void k_frame_normal(const DevModel* __restric
     if (PLAIN)                                            // structural zeros of H: no lane's gather list writes them
         for (int t = lane; t < nu * nu; t += WAVE) if (!((M->h_covered[t >> 5] >> (t & 31)) & 1u)) Bo[t] = 0.0;
     // shutter-delay scratch behind everything else: shift[C][3] | coef[C][3] (alpha, beta, gamma) | rc[C][3] | Mc[C][6] | M1[L][6] | M2[6]
-    const int nloc = (int)(blockIdx.x % (unsigned)N);
+    const int nloc = fs.n;
     const bool shut = sh.tau != nullptr && nloc >= 2;
     double* sSh = sDp + 3 * mct + ((pri && pri->p.gmm_k > 0) ? CPE_NX + pri->p.gmm_k * pri->p.gmm_dim + CPE_MAX_GMM + CPE_NX : 0);
     double* sCo = sSh + 3 * C; double* sRc = sCo + 3 * C; double* sMc = sRc + 3 * C; double* sM1 = sMc + 6 * C; double* sM2 = sM1 + 6 * L;
@@ -657,20 +633,16 @@ __global__ __launch_bounds__(WAVE) void k_lr_band(const DevModel* __restrict__ M
                                                   const DevPriors* __restrict__ pri, int nk, double* __restrict__ gbuf, double* __restrict__ Bbuf,
                                                   double* __restrict__ Hlr, double* __restrict__ costbuf, const int* __restrict__ act,
                                                   const int* __restrict__ n_act, RaggedArgs rg = RaggedArgs{}) {
-    if (n_act && (int)(blockIdx.x / (unsigned)N) >= *n_act) return;
+    FrameSlot fs;
+    if (!frame_slot<RAGGED>(N, act, n_act, rg, fs)) return;
     __shared__ double sx[(2 * CPE_MAX_WINDOW + 1) * CPE_NX];
     __shared__ double ssl[(CPE_MAX_WINDOW + 1) * CPE_NX];
     __shared__ double sgx[CPE_NX];
     __shared__ double sgu[CPE_NX];
     const int lane = threadIdx.x;
-    const int b = act ? act[blockIdx.x / (unsigned)N] : (int)(blockIdx.x / (unsigned)N), a = (int)(blockIdx.x % (unsigned)N);
+    const int b = fs.b, a = fs.n, NL = fs.len;           // N: the buffers' frames per sequence, NL: this sequence's length
     const size_t f = (size_t)b * N + a;
-    int NL = N;                                          // N: the buffers' frames per sequence, NL: this sequence's length
-    if constexpr (RAGGED) {
-        const int2 rs = rg.seq[b];
-        if (a >= rs.y) return;
-        M += rs.x; NL = rs.y;
-    }
+    M += fs.model;
     const SeqState S = st[b];
     if (S.status != 0) return;
     const int buf = (which || S.al_pending) ? S.cur : 1 - S.cur;
@@ -2220,11 +2192,10 @@ __global__ __launch_bounds__(WAVE) void k_finalize(const DevModel* __restrict__ 
                                                    RaggedArgs rg = RaggedArgs{} /* RAGGED: N = nmax; frames and cameras past a sequence's own are written as zeros */) {
     extern __shared__ double smem[];
     const int lane = threadIdx.x;
-    int NL = N;                                          // N: the buffers' frames per sequence, NL: this sequence's length
-    if constexpr (RAGGED) {
-        const int2 rs = rg.seq[blockIdx.x / (unsigned)N];
-        M += rs.x; NL = rs.y;
-    }
+    FrameSlot fs;
+    const bool own = frame_slot<RAGGED>(N, nullptr, nullptr, rg, fs);     // false: a frame past the sequence's own length
+    M += fs.model;
+    const int NL = fs.len;                               // N: the buffers' frames per sequence, NL: this sequence's length
     const int nq = M->nq, nl = M->nl, L = M->L, C = M->C;
     const int cst = RAGGED ? rg.cstride : C;             // cameras per frame of meas / meas_err
     double* sq = smem;
@@ -2233,9 +2204,9 @@ __global__ __launch_bounds__(WAVE) void k_finalize(const DevModel* __restrict__ 
     double* spos = sR + 36 * nl;
     double* scam = spos + 3 * L;
     const size_t f = blockIdx.x;
-    const int b = (int)(f / (size_t)N), n = (int)(f - (size_t)b * N);
+    const int b = fs.b, n = fs.n;
     const int ns = M->ns;                                                                  // state stride (Euler q + leg angles)
-    if (RAGGED && n >= NL) {
+    if (!own) {
         for (int t = lane; t < nq; t += WAVE) { q[f * nq + t] = 0.0; if (dq && ddq) { dq[f * nq + t] = 0.0; ddq[f * nq + t] = 0.0; } }
         if (positions) for (int t = lane; t < 3 * L; t += WAVE) positions[f * (size_t)(3 * L) + t] = 0.0;
         if (meas_err) for (int t = lane; t < 2 * cst * L; t += WAVE) meas_err[f * (size_t)(2 * cst * L) + t] = 0.0;

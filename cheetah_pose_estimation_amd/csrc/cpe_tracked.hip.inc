@@ -12,30 +12,19 @@ struct DevTrack {
     double H[CPE_NX * CPE_NX];          // 2 X^T diag(w) X, row-major
 };
 
-// x* of every frame from an Euler target q [F][nq]: the state (q, alpha) as k_state_init builds it (alpha = rotation of R_B^T R_c about y),
-// then the relative angles on the cost view.  One wave per frame; RAGGED: padding frames leave at once (nothing reads them).
+// x* of every frame from an Euler target q [F][nq]: the state (q, alpha = leg_alpha) of k_state_init, then the relative angles on the cost view.  One wave per frame; RAGGED: padding frames leave at once (nothing reads them).
 template <bool RAGGED = false>
 __global__ __launch_bounds__(WAVE) void k_track_target(const DevModel* __restrict__ M, const double* __restrict__ q, double* __restrict__ xt,
                                                       RaggedArgs rg = RaggedArgs{}) {
     __shared__ double ss[CPE_MAX_NQ + LM_MAX_REV];
     const int lane = threadIdx.x;
     const size_t f = blockIdx.x;
-    if constexpr (RAGGED) {
-        const int2 rs = rg.seq[f / (unsigned)rg.nmax];
-        if ((int)(f % (unsigned)rg.nmax) >= rs.y) return;
-        M += rs.x;
-    }
+    FrameSlot s;
+    if (!frame_slot_flat<RAGGED>(rg, s)) return;
+    M += s.model;
     const int nq = M->nq;
     if (lane < nq) ss[lane] = q[f * nq + lane];
-    if (lane < M->nrev) {
-        const double* qb = q + f * nq + 3 + 3 * M->rev_body[lane];
-        const double* qc = q + f * nq + 3 + 3 * M->rev_child[lane];
-        double scb[6], scc[6], RB[9], RC[9];
-        for (int a = 0; a < 3; a++) { sincos(qb[a], &scb[2 * a], &scb[2 * a + 1]); sincos(qc[a], &scc[2 * a], &scc[2 * a + 1]); }
-        rot_kind(scb, 0, RB); rot_kind(scc, 0, RC);
-        const double m00 = RB[0] * RC[0] + RB[3] * RC[3] + RB[6] * RC[6], m02 = RB[0] * RC[2] + RB[3] * RC[5] + RB[6] * RC[8];
-        ss[nq + lane] = atan2(m02, m00);
-    }
+    if (lane < M->nrev) ss[nq + lane] = leg_alpha(q + f * nq + 3 + 3 * M->rev_body[lane], q + f * nq + 3 + 3 * M->rev_child[lane]);
     wave_lds_sync();
     if (lane < M->nu) {
         const int r = M->rel_ref_u[lane];
@@ -55,14 +44,11 @@ __global__ __launch_bounds__(WAVE) void k_frame_tracked(const DevModel* __restri
                                                         const int* __restrict__ act, const int* __restrict__ n_act, RaggedArgs rg = RaggedArgs{}) {
     extern __shared__ double smem[];
     const int lane = threadIdx.x;
-    if (n_act && (int)(blockIdx.x / (unsigned)N) >= *n_act) return;
-    const int b = act ? act[blockIdx.x / (unsigned)N] : (int)(blockIdx.x / (unsigned)N);
-    if constexpr (RAGGED) {
-        const int2 rs = rg.seq[b];
-        if ((int)(blockIdx.x % (unsigned)N) >= rs.y) return;
-        M += rs.x; T += rs.x;
-    }
-    const size_t f = (size_t)b * N + blockIdx.x % (unsigned)N;
+    FrameSlot fs;
+    if (!frame_slot<RAGGED>(N, act, n_act, rg, fs)) return;
+    M += fs.model; T += fs.model;
+    const int b = fs.b;
+    const size_t f = (size_t)b * N + fs.n;
     const SeqState S = st[b];
     if (S.status != 0) return;
     const int pend = S.al_pending;                       // multiplier update: re-evaluate the CURRENT iterate
@@ -86,34 +72,13 @@ __global__ __launch_bounds__(WAVE) void k_frame_tracked(const DevModel* __restri
     double2 pf_mu = make_double2(0.0, 0.0);
     if (nbnd > 0) pf_mu = reinterpret_cast<const double2*>(mu)[f * (size_t)nbnd + (lane < nbnd ? lane : nbnd - 1)];
     wave_lds_sync();
-    wave_sincos(M, sq, ssc, lane);
-    if (lane < nrev) { double s_, c_; sincos(sal[lane], &s_, &c_); ssa[2 * lane] = s_; ssa[2 * lane + 1] = c_; }
+    // ---- the state phases (cpe_kernels.hip): no marker is read, so no leg vectors and no S rows
+    wave_state_sincos(M, sq, sal, ssc, ssa, nrev, lane);
     wave_lds_sync();
-    // hooke joints: phi of the tails in closed form (as k_frame_normal)
-    for (int level = 0; level < 2; level++) {
-        if (lane < M->hj_n && ((fw.x >> 16) & 1) == level) {
-            const int p = fw.x & 255, c = (fw.x >> 8) & 255;
-            double a[3];
-            rot_ycol(ssc + 6 * p, a);
-            const double st_ = ssc[6 * c + 2], ct = ssc[6 * c + 3], sp = ssc[6 * c + 4], cp = ssc[6 * c + 5];
-            const double num = a[0] * st_ * cp + a[1] * st_ * sp + a[2] * ct;
-            const double den = a[1] * cp - a[0] * sp;
-            const double hyp = sqrt(num * num + den * den);
-            sq[3 + 3 * c] = atan2(num, den);
-            ssc[6 * c] = num / hyp; ssc[6 * c + 1] = den / hyp;
-        }
-        wave_lds_sync();
-    }
-    if (lane < 4 * M->n_trunk) rot_kind(ssc + 6 * fw.y, lane & 3, sR + 9 * lane);
-    for (int t = WAVE + lane; t < 4 * M->n_trunk; t += WAVE) rot_kind(ssc + 6 * M->trunk_link[t >> 2], t & 3, sR + 9 * t);
+    wave_tail_roll(sq, ssc, M->hj_n, fw.x, lane);
+    wave_trunk_rotations(M, ssc, sR, fw.y, lane);
     wave_lds_sync();
-    if (lane < nrev) {                                    // leg Euler angles (principal triple) + Gamma rows of the cost pitch
-        const int Bk = fw.z & 255, c = (fw.z >> 8) & 255;
-        double e[3], gtrue[GAM_STRIDE];
-        leg_euler(sR + 36 * (fw.z >> 16), ssc + 6 * Bk, ssa[2 * lane], ssa[2 * lane + 1], sq[3 + 3 * Bk + 2], e, gtrue);
-        sq[3 + 3 * c] = e[0]; sq[3 + 3 * c + 1] = e[1]; sq[3 + 3 * c + 2] = e[2];
-        sgam[GAM_STRIDE * lane] = 1.0; sgam[GAM_STRIDE * lane + 1] = 0.0; sgam[GAM_STRIDE * lane + 2] = 1.0; sgam[GAM_STRIDE * lane + 3] = 0.0;
-    }
+    wave_leg_state(sq, ssc, ssa, sR, sgam, nrev, fw.z, lane);
     // ---- the tracked term: x on the cost view reads independent coordinates only (trunk Euler angles, alpha), none of those written above
     double ft = 0.0;
     if (lane < nu) {
