@@ -666,6 +666,35 @@ class Handle:
         res["seq"] = seq
         return res
 
+    SHUTTER_STEP_OUTPUTS = ("g", "Bm", "cost", "gx", "rcb", "g_total", "step", "meas_err")
+
+    def _shutter_step_shapes(self, B, N):
+        Cn, L = self.n_cams, self.L
+        return dict(g=(B, N, 28), Bm=(B, N, 28, 28), cost=(B, N, 3), gx=(B, N, 6), rcb=(B, N, Cn, 9), g_total=(B, N, 28), step=(B, Cn),
+                    meas_err=(B, N, Cn, L, 2))
+
+    def eval_shutter_step(self, q, meas, weight, tau, lam, seq, **out):
+        """cpe_eval_shutter_step on device tensors (tau [B, C]; seq: numpy [B, 8]); out: any of SHUTTER_STEP_OUTPUTS, the others are not asked for"""
+        assert set(out) <= set(self.SHUTTER_STEP_OUTPUTS)
+        self._call(self.lib.cpe_eval_shutter_step, "cpe_eval_shutter_step", q.shape[0], q.shape[1], _ptr(q), _ptr(meas), _ptr(weight), _ptr(tau),
+                   float(lam), *[_ptr(out.get(k)) for k in self.SHUTTER_STEP_OUTPUTS], _ptr(seq))
+
+    def eval_shutter_step_host(self, q, meas, weight, tau, lam):
+        """cpe_eval_shutter_step_host: the first pass of a round of the shutter-delay estimation from Euler q at the delays tau [B, C] and damping
+        lam.  numpy in, dict of numpy arrays out: g, g_total [B, N, 28], Bm [B, N, 28, 28], cost [B, N, 3], gx [B, N, 6], rcb [B, N, C, 9],
+        step [B, C], meas_err [B, N, C, L, 2], seq [B, 8] (as eval_lm_step_host)"""
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        q, meas, weight, tau = f64(q), f64(meas), f64(weight), f64(tau)
+        B, N = q.shape[:2]
+        if tau.shape != (B, self.n_cams):
+            raise CpeError("eval_shutter_step_host: one delay per sequence and camera")
+        out = {k: np.full(s, np.nan) for k, s in self._shutter_step_shapes(B, N).items()}
+        seq = np.zeros((B, 8))
+        _check(self.lib.cpe_eval_shutter_step_host(self._h, B, N, _ptr(q), _ptr(meas), _ptr(weight), _ptr(tau), float(lam),
+                                                   *[_ptr(out[k]) for k in self.SHUTTER_STEP_OUTPUTS], _ptr(seq)), "cpe_eval_shutter_step_host")
+        out["seq"] = seq
+        return out
+
     # ---- posterior covariance of the kinematic estimate (include/cpe.h, cpe_covariance) -----------------------------------------------
     def band_inverse(self, L, cov_diag, cov_off=None):
         """cpe_band_inverse on device tensors: L [B, N, pb + 1, 28, 28] (eval_lm_step_host's layout) -> cov_diag [B, N, 28, 28], cov_off

@@ -242,6 +242,9 @@ ENTRIES = {
     "cpe_eval_kinetic_nodes": _KIN_BN + _KIN_IN + ("p",) * 7,          # f, stat, g, Huu, Hfu, Hff, meta
     "cpe_eval_kinetic_system": _KIN_BN + _KIN_IN + _KIN_FORCES + ("p",) * 10,     # the same, then gk, Bk, Hk
     "cpe_eval_lm_step": _KIN_BN + _KIN_IN + ("d",) + ("p",) * 6,       # lam | g, dg, L, delta, state, seq
+    # q, meas, weight, tau | lam | g, Bm, cost, gx, rcb, g_total, step, meas_err, seq
+    "cpe_eval_shutter_step": _BN + ("p",) * 4 + ("d",) + ("p",) * 9,
+    "cpe_eval_shutter_step_host": _BN + ("p",) * 4 + ("d",) + ("p",) * 9,
     **COVARIANCE_ENTRIES, **KINETIC_COVARIANCE_ENTRIES,
 }
 

@@ -1966,19 +1966,12 @@ cpe_status cpe_eval_kinetic_system(cpe_handle* h, const cpe_kinetic_options* opt
     return CPE_OK;
 }
 
-// Diagnostic (include/cpe.h): the first LM iteration of a solve from Euler q at damping lam -- the launches of the first pass of cpe_solve
-// (lm_iterate) or, with kopt, of cpe_solve_kinetic (kin_iterate) -- and what k_lm_step / k_lm_back leave behind, in plain layouts.
-cpe_status cpe_eval_lm_step(cpe_handle* h, const cpe_kinetic_options* kopt, int32_t B, int32_t N, const double* q, const double* meas,
-                            const double* weight, const int32_t* stance, double lam, double* g, double* dg, double* L, double* delta, double* state,
-                            double* seq) {
-    if (!h || !q || !meas || !weight || !seq) return fail(CPE_BAD_ARG, "null argument");
-    if ((kopt == nullptr) != (stance == nullptr)) return fail(CPE_BAD_ARG, "cpe_eval_lm_step: stance is given with the kinetic options, and only then");
-    if (!(lam > 0.0) || !std::isfinite(lam)) return fail(CPE_BAD_ARG, "cpe_eval_lm_step: the damping must be positive and finite");
-    size_t F;
-    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
-    if (F == 0) return CPE_OK;
-    if (kopt && h->pb != 3) return fail(CPE_BAD_ARG, "the physics-based model runs on the half-bandwidth-3 solver");
-    HIPCHK(hipSetDevice(h->device));
+// The first pass of a solve from Euler q at damping lam, for the diagnostics below: cold start, what a sequence without a step leaves defined as
+// zero, then the launches of lm_iterate (sh: the shutter-delay buffers, all null = off) or, with kopt, of kin_iterate.  The stream is drained; hs
+// receives the sequence states, step[b] whether sequence b made a step, seq [B][8] (host) the cost terms, predicted decrease, max |delta| and status.
+static cpe_status lm_first_pass(cpe_handle* h, const cpe_kinetic_options* kopt, int B, int N, const double* q, const double* meas, const double* weight,
+                                const int32_t* stance, double lam, ShutterArgs sh, std::vector<SeqState>& hs, std::vector<char>& step, double* seq) {
+    const size_t F = (size_t)B * N;
     cpe_status s = ensure_ws(h, B, N);                     // the workspaces first: build_kin records pointers into them
     if (s != CPE_OK) return s;
     if (kopt) {
@@ -1998,15 +1991,15 @@ cpe_status cpe_eval_lm_step(cpe_handle* h, const cpe_kinetic_options* kopt, int3
     HIPCHK(hipMemcpyAsync(h->qbuf + F * ns, h->qbuf, w * F * ns, hipMemcpyDeviceToDevice, h->stream));
     LmParams prm = lm_params(h, B, N);
     prm.lambda0 = lam;                                     // the accept stage of the first pass sets S.lambda from it
-    const size_t ldsn = lds_normal(m, h->gmm_k, h->gmm_dim);
+    const size_t ldsn = lds_normal(m, h->gmm_k, h->gmm_dim, sh.tau != nullptr);
     if (kopt) kin_iterate<false>(h, prm, N, F, ldsn, meas, weight, stance, nullptr, RaggedArgs{}, 1, nullptr, nullptr, B);
-    else lm_iterate(h, prm, N, F, ldsn, meas, weight, ShutterArgs{nullptr, nullptr, nullptr}, nullptr, 1, nullptr, nullptr, B);
+    else lm_iterate(h, prm, N, F, ldsn, meas, weight, sh, nullptr, 1, nullptr, nullptr, B);
     HIPCHK(hipGetLastError());
-    std::vector<SeqState> hs((size_t)B);
+    hs.resize((size_t)B);
     HIPCHK(hipMemcpyAsync(hs.data(), h->st, sizeof(SeqState) * B, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     // a step was made where the evaluation is finite (status 0) and the factor exists: a failed factorisation multiplies the damping by 10
-    std::vector<char> step((size_t)B);
+    step.resize((size_t)B);
     for (int b = 0; b < B; b++) {
         const SeqState& S = hs[b];
         step[b] = S.status == 0 && S.lambda == lam;
@@ -2020,6 +2013,27 @@ cpe_status cpe_eval_lm_step(cpe_handle* h, const cpe_kinetic_options* kopt, int3
             HIPCHK(hipMemsetAsync(h->Lbuf + (size_t)b * N * LC, 0, w * N * LC, h->stream));
         }
     }
+    return CPE_OK;
+}
+
+// Diagnostic (include/cpe.h): the first LM iteration of a solve from Euler q at damping lam -- the launches of the first pass of cpe_solve
+// (lm_iterate) or, with kopt, of cpe_solve_kinetic (kin_iterate) -- and what k_lm_step / k_lm_back leave behind, in plain layouts.
+cpe_status cpe_eval_lm_step(cpe_handle* h, const cpe_kinetic_options* kopt, int32_t B, int32_t N, const double* q, const double* meas,
+                            const double* weight, const int32_t* stance, double lam, double* g, double* dg, double* L, double* delta, double* state,
+                            double* seq) {
+    if (!h || !q || !meas || !weight || !seq) return fail(CPE_BAD_ARG, "null argument");
+    if ((kopt == nullptr) != (stance == nullptr)) return fail(CPE_BAD_ARG, "cpe_eval_lm_step: stance is given with the kinetic options, and only then");
+    if (!(lam > 0.0) || !std::isfinite(lam)) return fail(CPE_BAD_ARG, "cpe_eval_lm_step: the damping must be positive and finite");
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    if (kopt && h->pb != 3) return fail(CPE_BAD_ARG, "the physics-based model runs on the half-bandwidth-3 solver");
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<SeqState> hs;
+    std::vector<char> step;
+    if (cpe_status s = lm_first_pass(h, kopt, B, N, q, meas, weight, stance, lam, ShutterArgs{nullptr, nullptr, nullptr}, hs, step, seq); s != CPE_OK) return s;
+    const int ns = h->hm.ns;
+    const size_t BB = (size_t)CPE_NX * CPE_NX, w = sizeof(double), LC = (size_t)(h->pb + 1) * BB;
     if (g) HIPCHK(hipMemcpyAsync(g, h->gtbuf, w * F * CPE_NX, hipMemcpyDeviceToDevice, h->stream));
     if (dg) HIPCHK(hipMemcpyAsync(dg, h->dgbuf, w * F * CPE_NX, hipMemcpyDeviceToDevice, h->stream));
     if (delta) HIPCHK(hipMemcpyAsync(delta, h->zbuf, w * F * CPE_NX, hipMemcpyDeviceToDevice, h->stream));
@@ -2042,6 +2056,45 @@ cpe_status cpe_eval_lm_step(cpe_handle* h, const cpe_kinetic_options* kopt, int3
         HIPCHK(hipMemcpyAsync(L, hl.data(), w * F * LC, hipMemcpyHostToDevice, h->stream));
     }
     HIPCHK(hipStreamSynchronize(h->stream));                // (hl is read by the copy above)
+    return CPE_OK;
+}
+
+// Diagnostic (include/cpe.h): the first pass of a round of cpe_solve_shutter from Euler q at the delays tau and damping lam -- lm_iterate with the
+// shutter-delay buffers, k_shutter_step, k_finalize(tau) -- and what they leave behind, in plain layouts.  The first pass does not move
+// st[b].cur: k_shutter_step and k_finalize read the evaluated buffer, and the `cur` half of gx / rcb is what is copied out.
+cpe_status cpe_eval_shutter_step(cpe_handle* h, int32_t B, int32_t N, const double* q, const double* meas, const double* weight, const double* tau,
+                                 double lam, double* g, double* Bm, double* cost, double* gx, double* rcb, double* g_total, double* step,
+                                 double* meas_err, double* seq) {
+    if (!h || !q || !meas || !weight || !tau || !seq) return fail(CPE_BAD_ARG, "null argument");
+    if (!(lam > 0.0) || !std::isfinite(lam)) return fail(CPE_BAD_ARG, "cpe_eval_shutter_step: the damping must be positive and finite");
+    if (n_models(h) > 1) return fail(CPE_BAD_ARG, "cpe_eval_shutter_step: the shutter-delay path has no ragged form (a handle of several models)");
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    HIPCHK(hipSetDevice(h->device));
+    const DevModel& m = h->hm;
+    const int C = m.C, nu = m.nu;
+    DevBuf dgx, drcb, dstep, dq;
+    HIPCHK(dgx.alloc(2 * F * 6)); HIPCHK(drcb.alloc(2 * F * C * 9)); HIPCHK(dstep.alloc((size_t)B * C)); HIPCHK(dq.alloc(F * m.nq));
+    std::vector<SeqState> hs;
+    std::vector<char> made;
+    if (cpe_status s = lm_first_pass(h, nullptr, B, N, q, meas, weight, nullptr, lam, ShutterArgs{tau, dgx.p, drcb.p}, hs, made, seq); s != CPE_OK) return s;
+    hipLaunchKernelGGL(k_shutter_step, dim3(B), dim3(WAVE), 0, h->stream, h->dm, h->st, N, F, h->qbuf, drcb.p, tau, dstep.p);
+    hipLaunchKernelGGL(k_finalize<>, dim3((unsigned)F), dim3(WAVE), lds_fk(m), h->stream, h->dm, h->st, N, F, h->qbuf, meas, dq.p, nullptr, nullptr, nullptr,
+                       meas_err, nullptr, tau);
+    HIPCHK(hipGetLastError());
+    const size_t w = sizeof(double);
+    for (int b = 0; b < B; b++) {                            // the per-frame buffers hold two iterates: [buffer][F][...]
+        const size_t src = (size_t)hs[b].cur * F + (size_t)b * N, dst = (size_t)b * N;
+        if (g) HIPCHK(hipMemcpyAsync(g + dst * nu, h->gbuf + src * nu, w * N * nu, hipMemcpyDeviceToDevice, h->stream));
+        if (Bm) HIPCHK(hipMemcpyAsync(Bm + dst * nu * nu, h->Bbuf + src * nu * nu, w * N * nu * nu, hipMemcpyDeviceToDevice, h->stream));
+        if (cost) HIPCHK(hipMemcpy2DAsync(cost + dst * 3, w * 3, h->costbuf + src * COST_STRIDE, w * COST_STRIDE, w * 3, N, hipMemcpyDeviceToDevice, h->stream));
+        if (gx) HIPCHK(hipMemcpyAsync(gx + dst * 6, dgx.p + src * 6, w * N * 6, hipMemcpyDeviceToDevice, h->stream));
+        if (rcb) HIPCHK(hipMemcpyAsync(rcb + dst * C * 9, drcb.p + src * C * 9, w * N * C * 9, hipMemcpyDeviceToDevice, h->stream));
+    }
+    if (g_total) HIPCHK(hipMemcpyAsync(g_total, h->gtbuf, w * F * CPE_NX, hipMemcpyDeviceToDevice, h->stream));
+    if (step) HIPCHK(hipMemcpyAsync(step, dstep.p, w * B * C, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));                // (the scratch buffers are freed on return)
     return CPE_OK;
 }
 
@@ -2413,6 +2466,29 @@ cpe_status cpe_solve_ragged_host(cpe_handle* h, int32_t B, int32_t N_max, const 
                                  cpe_stats* stats) {
     if (!model || !n_frames) return fail(CPE_BAD_ARG, "null argument");
     return solve_host_impl(h, B, N_max, model, n_frames, q_init, meas, weight, q, dq, ddq, positions, meas_err, stats);
+}
+
+// host-pointer twin of cpe_eval_shutter_step: stage through HBM
+cpe_status cpe_eval_shutter_step_host(cpe_handle* h, int32_t B, int32_t N, const double* q, const double* meas, const double* weight, const double* tau,
+                                      double lam, double* g, double* Bm, double* cost, double* gx, double* rcb, double* g_total, double* step,
+                                      double* meas_err, double* seq) {
+    if (!h || !q || !meas || !weight || !tau || !seq) return fail(CPE_BAD_ARG, "null argument");
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    const DevModel& m = h->hm;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t nm = F * m.C * m.L, BB = (size_t)CPE_NX * CPE_NX;
+    Staging st(h->stream);
+    const double *dq = st.in(q, F * m.nq), *dmeas = st.in(meas, nm * 2), *dweight = st.in(weight, nm), *dtau = st.in(tau, (size_t)B * m.C);
+    double *og = st.out_opt(g, F * CPE_NX), *oB = st.out_opt(Bm, F * BB), *oc = st.out_opt(cost, F * 3), *ox = st.out_opt(gx, F * 6);
+    double *orc = st.out_opt(rcb, F * m.C * 9), *ogt = st.out_opt(g_total, F * CPE_NX), *os = st.out_opt(step, (size_t)B * m.C);
+    double* ome = st.out_opt(meas_err, nm * 2);
+    HIPCHK(st.err);
+    const cpe_status s = cpe_eval_shutter_step(h, B, N, dq, dmeas, dweight, dtau, lam, og, oB, oc, ox, orc, ogt, os, ome, seq);
+    if (s != CPE_OK) return s;
+    HIPCHK(st.fetch());
+    return CPE_OK;
 }
 
 // joint equalities of a model: two rows per revolute joint, one per Hooke joint (the node forces lambda, build_kin_entry)

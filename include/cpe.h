@@ -552,6 +552,30 @@ cpe_status cpe_eval_kinetic_system(cpe_handle* h, const cpe_kinetic_options* opt
 cpe_status cpe_eval_lm_step(cpe_handle* h, const cpe_kinetic_options* kopt, int32_t B, int32_t N, const double* q, const double* meas,
                             const double* weight, const int32_t* stance, double lam, double* g, double* dg, double* L, double* delta, double* state,
                             double* seq);
+/* Diagnostic building block of the shutter-delay estimation, for tests: exactly the first pass of a round of cpe_solve_shutter from Euler q at
+ * the delays tau [B][C] (device; tau[b][0] is the reference camera's and is read like the others) and the damping lam > 0 in place of
+ * opts.lambda0 -- the same launches: the cold start, k_frame_normal in its shutter-delay branch (+ the motion prior's band), k_lm_step with the
+ * collection of the cross-frame gradient parts, k_lm_back; then k_shutter_step and k_finalize with the delays, both at the evaluated iterate
+ * (a first pass accepts nothing).  It stands for the reference's displaced view, acinoset_misc.py:179-183 and :278-288: camera c sees the
+ * markers of frame n >= 2 at p + v_n tau_c + a_n tau_c^2, v and a the backward differences of the base position.  Outputs, device pointers
+ * except seq, each may be NULL except seq:
+ *   g [B][N][28], Bm [B][N][28][28], cost [B][N][3]   k_frame_normal's per-frame terms with the displacement (cpe_eval_normal's layouts); on a
+ *                     handle with a motion prior g and Bm are read after that prior's band kernel has added its per-frame part
+ *   gx [B][N][6]      the parts of frame n's measurement gradient that belong to the base positions of frames n-1 (0..2) and n-2 (3..5)
+ *   rcb [B][N][C][9]  per camera: the gradient of the frame's measurement cost with respect to a displacement of that camera's markers (3), and the
+ *                     upper triangle xx, xy, xz, yy, yz, zz of its Gauss-Newton matrix (6)
+ *   g_total [B][N][28]  k_lm_step's total gradient, gx collected (cpe_eval_lm_step's g)
+ *   step [B][C]       k_shutter_step's Newton step of every delay with the trajectory held fixed; step[b][0] = 0, and 0 for N < 3
+ *   meas_err [B][N][C][L][2]  pixel minus measurement of the displaced view at the evaluated iterate (cpe_solve_shutter's meas_err)
+ *   seq [B][8]        HOST, as cpe_eval_lm_step
+ * CPE_BAD_ARG, the reason in cpe_last_error(): a null required argument, lam <= 0 or not finite, a handle of several models (cpe_create_multi:
+ * the shutter-delay path has no ragged form).  The _host twin takes host pointers throughout and stages through HBM. */
+cpe_status cpe_eval_shutter_step(cpe_handle* h, int32_t B, int32_t N, const double* q, const double* meas, const double* weight, const double* tau,
+                                 double lam, double* g, double* Bm, double* cost, double* gx, double* rcb, double* g_total, double* step,
+                                 double* meas_err, double* seq);
+cpe_status cpe_eval_shutter_step_host(cpe_handle* h, int32_t B, int32_t N, const double* q, const double* meas, const double* weight, const double* tau,
+                                      double lam, double* g, double* Bm, double* cost, double* gx, double* rcb, double* g_total, double* step,
+                                      double* meas_err, double* seq);
 
 /* ---- posterior covariance of the kinematic estimate ("What is inverted").  The reference returns one trajectory and no measure
  * of how well the data determine it (IPOPT's reduced Hessian is never asked for, acinoset_opt.py:611-617).  Here

@@ -170,11 +170,14 @@ def pixel_jacobian(sk, cams, u, fd_h=FD_H):
     up = np.broadcast_to(u[:, None, None, :], (F, nu, 8, nu)).copy()
     for k in range(nu):
         up[:, k, :, k] += steps
-    f = pixels(sk, cams, up)[0]                                                                                 # [F, nu, 8, C, L, 2]
+    return np.moveaxis(stencil_quotient(pixels(sk, cams, up)[0], dt(fd_h)), 1, -1)                               # (f [F, nu, 8, C, L, 2])
+
+
+def stencil_quotient(f, fd_h):
+    """the extrapolated five-point quotient [F, n, ...] of f [F, n, 8, ...], the values at -2, -1, 1, 2 steps of fd_h and then of fd_h / 2"""
     # (differences first: a pixel that does not depend on the coordinate gives exactly 0)
     five = lambda a, hh: (8 * (a[:, :, 2] - a[:, :, 1]) - (a[:, :, 3] - a[:, :, 0])) / (12 * hh)
-    D = (16 * five(f[:, :, 4:], dt(fd_h) / 2) - five(f[:, :, :4], dt(fd_h))) / 15                               # [F, nu, C, L, 2]
-    return np.moveaxis(D, 1, -1)
+    return (16 * five(f[:, :, 4:], fd_h / 2) - five(f[:, :, :4], fd_h)) / 15
 
 
 # ---- the loss --------------------------------------------------------------------------------------------------------------------------
@@ -226,25 +229,29 @@ def _prior_arrays(pr, dt):
     return P, mu, np.array(pr.gmm_logw[:K], dtype=dt)
 
 
-def evaluate(sk, cams, opts, pr, qc, meas, weight, dtype=np.longdouble, fd_h=FD_H, stencil=None):
+def evaluate(sk, cams, opts, pr, qc, meas, weight, dtype=np.longdouble, fd_h=FD_H, stencil=None, view=None):
     """one frame's terms of F frames at consistent Euler qc [F, nq] (meas [F, C, L, 2], weight [F, C, L]), everything in `dtype`: dict(cost [F, 3],
     g, g_scale [F, 28], Bm [F, 28, 28], q [F, nq] = the numpy map's own consistent q, s [F, C, L, 2] weighted residuals (0 where w = 0), w, z,
-    J [F, C, L, 2, 28], v / margin / active of the bounds, g_meas, g_prior)"""
+    J [F, C, L, 2, 28], v / margin / active of the bounds, g_meas, g_prior).  view: None, or (pixels(u) -> (uv, z), jacobian(u, fd_h) -> [F, C,
+    L, 2, >= 28]) of another view of the same frames (shutter_compare's displaced one) in place of pixels() and pixel_jacobian(): the first 28
+    columns of its Jacobian are d / d u, all of them come back as Jx beside the loss weights gw, cw w^2 and their absolute forms"""
     dt = np.dtype(dtype).type
     C = len(cams)
     ind, _, _, _ = tables(sk)
     nu = len(ind)
     u = u_of_q(sk, np.asarray(qc).astype(dtype))
-    uv, z = pixels(sk, cams, u)
+    pix, jac = view if view is not None else ((lambda u_: pixels(sk, cams, u_)), (lambda u_, h_: pixel_jacobian(sk, cams, u_, h_)))
+    uv, z = pix(u)
     if stencil is None or np.dtype(stencil) == np.dtype(dtype):
-        J = pixel_jacobian(sk, cams, u, fd_h)
+        J = jac(u, fd_h)
     else:                                                                            # the stencil alone in another precision, from the same u
-        J = pixel_jacobian(sk, cams, u.astype(stencil), fd_h).astype(dtype)
+        J = jac(u.astype(stencil), fd_h).astype(dtype)
     w = np.array([cams[c].mult for c in range(C)], dtype=dtype)[None, :, None] * np.asarray(weight).astype(dtype)
     on = w != 0
     on2 = on[..., None]
     s = np.where(on2, w[..., None] * (np.where(on2, uv, 0) - np.asarray(meas).astype(dtype)), 0)
-    J = np.where(on2[..., None], J, 0)
+    Jx = np.where(on2[..., None], J, 0)
+    J = Jx[..., :nu]
     a, b, c = dt(opts.loss_a), dt(opts.loss_b), dt(opts.loss_c)
     rho, d1, d2, d1a, d2a = loss(s, a, b, c)
     cw = np.where(on2, curvature_weight(s, d1, d2, int(opts.curvature)), 0)
@@ -295,7 +302,8 @@ def evaluate(sk, cams, opts, pr, qc, meas, weight, dtype=np.longdouble, fd_h=FD_
         g_scale += np.einsum("fk,fki->fi", gam, np.abs(np.einsum("kij,fkj->fki", np.abs(P), np.abs(dx)))) @ np.abs(X)
         Bm += np.einsum("ia,fij,jb->fab", X, np.einsum("fk,kij->fij", gam, P), X)
     return dict(cost=cost, g=g, g_scale=g_scale, Bm=Bm, q=q_of_u(sk, u), s=s, w=w, z=z, J=J, v=v, margin=margin, active=active,
-                g_meas=g_meas, g_prior=g_prior, g_floor=g_floor, B_floor=B_floor, has_prior=pr is not None and pr.gmm_k > 0)
+                g_meas=g_meas, g_prior=g_prior, g_floor=g_floor, B_floor=B_floor, has_prior=pr is not None and pr.gmm_k > 0,
+                u=u, uv=uv, Jx=Jx, gw=gw, gwa=np.where(on2, d1a * np.abs(w[..., None]), 0), cww=cw * w[..., None] ** 2, cwwa=cwa * w[..., None] ** 2)
 
 
 def consistent_q(oracle, sk, q):

@@ -727,6 +727,8 @@ def test_error_behaviour_of_the_abi(sk25, cams6, gpu_handle_factory):
         "cpe_grf_fit": lambda B, N: lib.cpe_grf_fit(h._h, go, B, N, *[p] * 7),
         "cpe_solve": lambda B, N: lib.cpe_solve(h._h, B, N, *[p] * 8, stats),
         "cpe_solve_shutter": lambda B, N: lib.cpe_solve_shutter(h._h, B, N, p, p, p, 1e-3, 4, 1e-6, *[p] * 6, stats, C.byref(rounds)),
+        "cpe_eval_shutter_step": lambda B, N: lib.cpe_eval_shutter_step(h._h, B, N, p, p, p, p, 1e-2, *[p] * 8, hp),
+        "cpe_eval_shutter_step_host": lambda B, N: lib.cpe_eval_shutter_step_host(h._h, B, N, hp, hp, hp, hp, 1e-2, *[hp] * 9),
         "cpe_solve_kinetic": lambda B, N: lib.cpe_solve_kinetic(h._h, ko, B, N, *[p] * 13, stats, kstats),
         "cpe_solve_kinetic_fixed": lambda B, N: lib.cpe_solve_kinetic_fixed(h._h, ko, B, N, *[p] * 14, stats, kstats),
         "cpe_solve_kinetic_force_box": lambda B, N: lib.cpe_solve_kinetic_force_box(h._h, ko, B, N, *[p] * 14, stats, kstats),
