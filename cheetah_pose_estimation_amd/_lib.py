@@ -787,6 +787,49 @@ class Handle:
         out.update(status=st, seq_status=list(seq)[:B])
         return out
 
+    def covariance_kinetic_ragged(self, kopts_list, model, n_frames, q, meas, weight, stance, ridge, cov_diag, cov_off=None, cov_pos=None, cov_f=None,
+                                  f=None, meta=None, L=None, grf_fixed=None, tau_box=None, grf_box=None):
+        """cpe_covariance_kinetic_ragged on device tensors laid out for N_max = q.shape[1] frames and C_max cameras, as solve_kinetic_ragged takes
+        them; kopts_list: one KineticOptions per model of the handle; model / n_frames: int sequences (one per sequence).  The outputs as in
+        covariance_kinetic, zero past every sequence's own frames.  Returns (status, [status of every sequence])."""
+        _force_variant("covariance_kinetic_ragged", grf_fixed, tau_box, grf_box)
+        ko = self._kinetic_options_array(kopts_list)
+        B, N = q.shape[0], q.shape[1]
+        if len(model) != B or len(n_frames) != B:
+            raise ValueError("covariance_kinetic_ragged: one model index and one frame count per sequence")
+        seq = (C.c_int32 * max(B, 1))()
+        mo, nf = (C.c_int32 * max(B, 1))(*[int(m) for m in model]), (C.c_int32 * max(B, 1))(*[int(n) for n in n_frames])
+        st = self._call(self.lib.cpe_covariance_kinetic_ragged, "cpe_covariance_kinetic_ragged", ko, B, N, mo, nf, _ptr(q), _ptr(meas), _ptr(weight),
+                        _ptr(stance), _ptr(grf_fixed), _ptr(tau_box), _ptr(grf_box), float(ridge), _ptr(cov_diag), _ptr(cov_off), _ptr(cov_pos),
+                        _ptr(cov_f), _ptr(f), _ptr(meta), _ptr(L), seq, allow=(abi.OK, abi.NUMERICAL))
+        return st, list(seq)[:B]
+
+    def covariance_kinetic_ragged_host(self, q_list, meas_list, weight_list, stance_list, kopts_list, model_list=None, ridge=0.0, grf_fixed=None,
+                                       tau_box=None, grf_box=None, want_L=False):
+        """cpe_covariance_kinetic_ragged_host over sequences of their own length and model (solve_kinetic_ragged_host's arguments: kopts_list one
+        KineticOptions per model of the handle; grf_fixed / tau_box / grf_box, at most one, a list of one array per sequence): pads, runs, unpads.
+        Returns dict(cov_diag, cov_off, cov_pos, cov_f, f, meta (L with want_L) = lists of per-sequence arrays [N_b, ...] as in
+        covariance_kinetic_host, status, seq_status, padded = the padded outputs)."""
+        who = "covariance_kinetic_ragged_host"
+        variant, force = _force_variant(who, grf_fixed, tau_box, grf_box)
+        p = self._ragged_batch(who, "one q, meas, weight, stance, model (and force array)", model_list, kopts_list, variant,
+                               q_init=q_list, meas=meas_list, weight=weight_list, stance=stance_list, force=force)
+        B, Nm = p["q_init"].shape[:2]
+        out = self._covariance_outputs(B, Nm, True, True, want_L)
+        out.update(cov_f=np.empty((B, Nm, 64, 64)), f=np.empty((B, Nm, 64)), meta=np.empty((B, Nm, 65), dtype=np.int32))
+        if not want_L:
+            del out["L"]
+        seq = (C.c_int32 * max(B, 1))()
+        ko = self._kinetic_options_array(kopts_list)
+        st = self.lib.cpe_covariance_kinetic_ragged_host(self._h, ko, B, Nm, p["model_arr"], p["len_arr"], _ptr(p["q_init"]), _ptr(p["meas"]),
+                                                         _ptr(p["weight"]), p["stance"].ctypes.data, *_force_slots(variant, p["force"]), float(ridge),
+                                                         _ptr(out["cov_diag"]), _ptr(out["cov_off"]), _ptr(out["cov_pos"]), _ptr(out["cov_f"]),
+                                                         _ptr(out["f"]), out["meta"].ctypes.data, _ptr(out.get("L")), seq)
+        _check(st, "cpe_covariance_kinetic_ragged_host", allow=(abi.OK, abi.NUMERICAL))
+        res = unpad_kinetic(out, p["lens"], p["cams"])
+        res.update(status=st, seq_status=list(seq)[:B], padded=out)
+        return res
+
     # ---- host-pointer conveniences (numpy in, numpy out; PCIe-inclusive) -------------------------------
     def eval_resjac_host(self, q, meas, weight, want_cost=True):
         q = np.ascontiguousarray(q, dtype=np.float64); meas = np.ascontiguousarray(meas, dtype=np.float64)

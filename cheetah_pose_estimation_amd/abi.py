@@ -186,9 +186,15 @@ COVARIANCE_ENTRIES = {
 }
 # the physics-based twin (cpe_covariance_kinetic): h, ko, B, N | q, meas, weight, stance, grf_fixed, tau_box, grf_box | ridge | cov_diag, cov_off,
 # cov_pos, cov_f, f, meta, L | status
+_KIN_COV = ("p",) * 7 + ("d",) + ("p",) * 7 + ("ip",)
 KINETIC_COVARIANCE_ENTRIES = {
-    "cpe_covariance_kinetic": _KIN_BN + ("p",) * 7 + ("d",) + ("p",) * 7 + ("ip",),
-    "cpe_covariance_kinetic_host": _KIN_BN + ("p",) * 7 + ("d",) + ("p",) * 7 + ("ip",),
+    "cpe_covariance_kinetic": _KIN_BN + _KIN_COV,
+    "cpe_covariance_kinetic_host": _KIN_BN + _KIN_COV,
+}
+# its ragged pair: ko an array of one KineticOptions per model, N = N_max, then model, n_frames
+KINETIC_COVARIANCE_RAGGED_ENTRIES = {
+    "cpe_covariance_kinetic_ragged": _KIN_BN + _RAGGED + _KIN_COV,
+    "cpe_covariance_kinetic_ragged_host": _KIN_BN + _RAGGED + _KIN_COV,
 }
 COVARIANCE_MAX_PB = 4        # largest half-bandwidth (frames) the covariance sweep supports: motion-prior windows 5 and 6 are refused
 ENTRIES = {
@@ -245,7 +251,7 @@ ENTRIES = {
     # q, meas, weight, tau | lam | g, Bm, cost, gx, rcb, g_total, step, meas_err, seq
     "cpe_eval_shutter_step": _BN + ("p",) * 4 + ("d",) + ("p",) * 9,
     "cpe_eval_shutter_step_host": _BN + ("p",) * 4 + ("d",) + ("p",) * 9,
-    **COVARIANCE_ENTRIES, **KINETIC_COVARIANCE_ENTRIES,
+    **COVARIANCE_ENTRIES, **KINETIC_COVARIANCE_ENTRIES, **KINETIC_COVARIANCE_RAGGED_ENTRIES,
 }
 
 

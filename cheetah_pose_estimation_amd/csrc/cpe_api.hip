@@ -531,7 +531,7 @@ static cpe_status create_impl(cpe_handle* h, const cpe_skeleton* skel, const cpe
                             (const void*)&k_resjac<true, 4, 4, 2>, (const void*)&k_resjac<false, 4, 4, 2>,
                             (const void*)&k_dyn_eval<>, (const void*)&k_dyn_assemble<>, (const void*)&k_dyn_schur<>, (const void*)&k_dyn_jac<>,
                             (const void*)&k_dyn_eval<true>, (const void*)&k_dyn_assemble<true>, (const void*)&k_dyn_schur<true>, (const void*)&k_dyn_jac<true>,
-                            (const void*)&k_force_cov};
+                            (const void*)&k_force_cov<>, (const void*)&k_force_cov<true>};
         for (const void* k : ks) {         // all of the CU's 160 KiB that the kernel's static LDS leaves (k_dyn_schur<*> holds a word of its own)
             hipFuncAttributes fa;
             HIPCHK(hipFuncGetAttributes(&fa, k));
@@ -1507,13 +1507,14 @@ static cpe_status build_kin(cpe_handle* h, const cpe_kinetic_options* opt, const
     return CPE_OK;
 }
 
-// every entry, model k under opts[k] (cpe_solve_kinetic_ragged)
-static cpe_status build_kin_all(cpe_handle* h, const cpe_kinetic_options* opts, const double* grf_fix, const double* tau_box, const double* grf_box) {
+// every entry, model k under opts[k] (cpe_solve_kinetic_ragged, cpe_covariance_kinetic_ragged: `who`, for the reason of a refusal)
+static cpe_status build_kin_all(cpe_handle* h, const cpe_kinetic_options* opts, const double* grf_fix, const double* tau_box, const double* grf_box,
+                                const char* who = "cpe_solve_kinetic_ragged") {
     const int nmod = n_models(h);
     h->hks.resize((size_t)nmod);
     for (int k = 0; k < nmod; k++)
         if (cpe_status s = build_kin_entry(h, h->models.empty() ? h->hm : h->models[(size_t)k], &opts[k], grf_fix, tau_box, grf_box, h->hks[(size_t)k]); s != CPE_OK)
-            return fail(s, std::string("cpe_solve_kinetic_ragged: model ") + std::to_string(k) + ": " + g_err);
+            return fail(s, std::string(who) + ": model " + std::to_string(k) + ": " + g_err);
     h->hk = h->hks[0];
     if (!h->dk) HIPCHK(hipMalloc(&h->dk, sizeof(DevKin) * nmod));
     HIPCHK(hipMemcpyAsync(h->dk, h->hks.data(), sizeof(DevKin) * nmod, hipMemcpyHostToDevice, h->stream));
@@ -2274,22 +2275,39 @@ static cpe_status cov_kinetic_check(const char* who, const cpe_handle* h, const 
     return CPE_OK;
 }
 
-cpe_status cpe_covariance_kinetic(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q, const double* meas,
-                                  const double* weight, const int32_t* stance, const double* grf_fixed, const double* tau_box, const double* grf_box,
-                                  double ridge, double* cov_diag, double* cov_off, double* cov_pos, double* cov_f, double* f, int32_t* meta, double* L,
-                                  cpe_status* status) {
-    const char* who = "cpe_covariance_kinetic";
+// What the ragged pair refuses of its batch, before the device is touched: the (model, frames) table and kinetic options of different shape
+static cpe_status cov_kinetic_batch(const char* who, const cpe_handle* h, const cpe_kinetic_options* opt, int B, int N_max, const int32_t* model,
+                                    const int32_t* n_frames, std::vector<int2>& seq) {
+    if (cpe_status s = ragged_table(h, B, N_max, model, n_frames, seq); s != CPE_OK) return s;
+    for (int k = 1; k < n_models(h); k++)
+        if (const char* field = kinetic_shape_mismatch(opt[0], opt[k]))
+            return fail(CPE_BAD_ARG, std::string(who) + ": kinetic options of model " + std::to_string(k) + " differ from model 0 in " + field);
+    return CPE_OK;
+}
+
+// cpe_covariance_kinetic (model == null: B sequences of N frames of the handle's first model, options opt[0]) and cpe_covariance_kinetic_ragged
+// (model / n_frames: host arrays of the batch, N = N_max, options opt[k] for model k)
+static cpe_status covariance_kinetic_impl(const char* who, cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const int32_t* model,
+                                          const int32_t* n_frames, const double* q, const double* meas, const double* weight, const int32_t* stance,
+                                          const double* grf_fixed, const double* tau_box, const double* grf_box, double ridge, double* cov_diag,
+                                          double* cov_off, double* cov_pos, double* cov_f, double* f, int32_t* meta, double* L, cpe_status* status) {
     if (cpe_status s = cov_kinetic_check(who, h, opt, stance, grf_fixed, tau_box, grf_box, ridge); s != CPE_OK) return s;
     if (!h || !q || !meas || !weight || !cov_diag || !status) return fail(CPE_BAD_ARG, "null argument");
     size_t F;
     if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
     if (F == 0) return CPE_OK;
+    const bool ragged = model != nullptr;
+    std::vector<int2> seq;
+    if (ragged) { if (cpe_status s = cov_kinetic_batch(who, h, opt, B, N, model, n_frames, seq); s != CPE_OK) return s; }
     HIPCHK(hipSetDevice(h->device));
     cpe_status s = ensure_ws(h, B, N);                     // the workspaces first: build_kin records pointers into them
     if (s != CPE_OK) return s;
     if ((s = ensure_kws(h, B, N)) != CPE_OK || (s = ensure_cov(h, F)) != CPE_OK) return s;
-    if ((s = build_kin(h, opt, grf_fixed, tau_box, grf_box)) != CPE_OK) return s;
-    if ((s = state_reset(h, B, N, q)) != CPE_OK || (s = kin_state_reset(h, F, tau_box != nullptr)) != CPE_OK) return s;
+    if ((s = ragged ? build_kin_all(h, opt, grf_fixed, tau_box, grf_box, who) : build_kin(h, opt, grf_fixed, tau_box, grf_box)) != CPE_OK) return s;
+    const RaggedArgs rgv = ragged ? RaggedArgs{h->rseq, N, cams_max(h)} : RaggedArgs{};
+    const RaggedArgs* rg = ragged ? &rgv : nullptr;
+    if (ragged) HIPCHK(hipMemcpyAsync(h->rseq, seq.data(), sizeof(int2) * B, hipMemcpyHostToDevice, h->stream));     // (seq outlives the stream: drained below)
+    if ((s = state_reset(h, B, N, q, rg)) != CPE_OK || (s = kin_state_reset(h, F, tau_box != nullptr)) != CPE_OK) return s;
     const DevModel& m = h->hm;
     const size_t BB = (size_t)CPE_NX * CPE_NX, w = sizeof(double), LC = 4 * BB, FF = (size_t)KIN_LS * KIN_LS;
     // k_force_cov reads the off-diagonal blocks of the band whether the caller wants them or not; one flag per sequence behind them
@@ -2298,7 +2316,7 @@ cpe_status cpe_covariance_kinetic(cpe_handle* h, const cpe_kinetic_options* opt,
     HIPCHK(bad_buf.alloc(((size_t)B + 1) / 2));
     int* bad = reinterpret_cast<int*>(bad_buf.p);
     HIPCHK(hipMemsetAsync(bad, 0, sizeof(int) * B, h->stream));
-    // a sequence without a factor has all outputs zero, and so have the nodes 0 and 1 in cov_f, f and meta
+    // a sequence without a factor has all outputs zero, and so have the nodes 0 and 1 in cov_f, f and meta and every frame past a sequence's own
     HIPCHK(hipMemsetAsync(cov_diag, 0, w * F * BB, h->stream));
     HIPCHK(hipMemsetAsync(cov_off, 0, w * F * 3 * BB, h->stream));
     if (cov_pos) HIPCHK(hipMemsetAsync(cov_pos, 0, w * F * m.L * 9, h->stream));
@@ -2308,16 +2326,23 @@ cpe_status cpe_covariance_kinetic(cpe_handle* h, const cpe_kinetic_options* opt,
     // the launches of the physics solve's first pass up to the band factor, multipliers zero, at damping ridge in place of opts.lambda0
     LmParams prm = lm_params(h, B, N);
     prm.lambda0 = ridge;
-    kin_iterate<false>(h, prm, N, F, lds_normal(m, h->gmm_k, h->gmm_dim), meas, weight, stance, nullptr, RaggedArgs{}, 1, nullptr, nullptr, B, false);
-    cov_launch(h, B, N, h->st, h->Lbuf, 1, cov_diag, cov_off, nullptr);
+    if (ragged) kin_iterate<true>(h, prm, N, F, lds_normal_all(h), meas, weight, stance, nullptr, rgv, 1, nullptr, nullptr, B, false);
+    else kin_iterate<false>(h, prm, N, F, lds_normal(m, h->gmm_k, h->gmm_dim), meas, weight, stance, nullptr, RaggedArgs{}, 1, nullptr, nullptr, B, false);
+    cov_launch(h, B, N, h->st, h->Lbuf, 1, cov_diag, cov_off, rg);
     // (without cov_f the kernel still decides whether every node's force matrix has a factor: the status does not depend on what is asked for)
-    hipLaunchKernelGGL(k_force_cov, dim3((unsigned)F), dim3(KIN_THREADS), sizeof(double) * FC_DOUBLES, h->stream, h->dk, h->st, N, F, h->pieces, h->pmeta,
-                       h->fbuf, h->kmu, stance, cov_diag, cov_off, cov_f, f, meta, bad);
+    if (ragged) hipLaunchKernelGGL(k_force_cov<true>, dim3((unsigned)F), dim3(KIN_THREADS), sizeof(double) * FC_DOUBLES, h->stream, h->dk, h->st, N, F, h->pieces,
+                                   h->pmeta, h->fbuf, h->kmu, stance, cov_diag, cov_off, cov_f, f, meta, bad, rgv);
+    else hipLaunchKernelGGL(k_force_cov<>, dim3((unsigned)F), dim3(KIN_THREADS), sizeof(double) * FC_DOUBLES, h->stream, h->dk, h->st, N, F, h->pieces, h->pmeta,
+                            h->fbuf, h->kmu, stance, cov_diag, cov_off, cov_f, f, meta, bad, RaggedArgs{});
     if (cov_pos) {
         const size_t ldsm = lds_normal_all(h) + w * BB + sizeof(int) * (size_t)(CPE_MAX_MARKERS * CPE_MAX_MCOL);
-        hipLaunchKernelGGL(k_marker_cov<>, dim3((unsigned)F), dim3(WAVE), ldsm, h->stream, h->dm, h->st, N, F, h->qbuf, cov_diag, cov_pos, RaggedArgs{});
+        if (ragged) hipLaunchKernelGGL(k_marker_cov<true>, dim3((unsigned)F), dim3(WAVE), ldsm, h->stream, h->dm, h->st, N, F, h->qbuf, cov_diag, cov_pos, rgv);
+        else hipLaunchKernelGGL(k_marker_cov<>, dim3((unsigned)F), dim3(WAVE), ldsm, h->stream, h->dm, h->st, N, F, h->qbuf, cov_diag, cov_pos, RaggedArgs{});
     }
-    if (L) hipLaunchKernelGGL(k_cov_export<>, dim3((unsigned)F), dim3(COV_THREADS), 0, h->stream, h->st, h->Lbuf, L, N, (int)LC, RaggedArgs{});
+    if (L) {
+        if (ragged) hipLaunchKernelGGL(k_cov_export<true>, dim3((unsigned)F), dim3(COV_THREADS), 0, h->stream, h->st, h->Lbuf, L, N, (int)LC, rgv);
+        else hipLaunchKernelGGL(k_cov_export<>, dim3((unsigned)F), dim3(COV_THREADS), 0, h->stream, h->st, h->Lbuf, L, N, (int)LC, RaggedArgs{});
+    }
     HIPCHK(hipGetLastError());
     std::vector<SeqState> hs((size_t)B);
     std::vector<int> hbad((size_t)B);
@@ -2344,17 +2369,37 @@ cpe_status cpe_covariance_kinetic(cpe_handle* h, const cpe_kinetic_options* opt,
     return worst;
 }
 
-// host-pointer twin (stages through HBM)
-cpe_status cpe_covariance_kinetic_host(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q, const double* meas,
-                                       const double* weight, const int32_t* stance, const double* grf_fixed, const double* tau_box,
-                                       const double* grf_box, double ridge, double* cov_diag, double* cov_off, double* cov_pos, double* cov_f, double* f,
-                                       int32_t* meta, double* L, cpe_status* status) {
-    const char* who = "cpe_covariance_kinetic_host";
+cpe_status cpe_covariance_kinetic(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q, const double* meas,
+                                  const double* weight, const int32_t* stance, const double* grf_fixed, const double* tau_box, const double* grf_box,
+                                  double ridge, double* cov_diag, double* cov_off, double* cov_pos, double* cov_f, double* f, int32_t* meta, double* L,
+                                  cpe_status* status) {
+    return covariance_kinetic_impl("cpe_covariance_kinetic", h, opt, B, N, nullptr, nullptr, q, meas, weight, stance, grf_fixed, tau_box, grf_box, ridge,
+                                   cov_diag, cov_off, cov_pos, cov_f, f, meta, L, status);
+}
+
+cpe_status cpe_covariance_kinetic_ragged(cpe_handle* h, const cpe_kinetic_options* opts, int32_t B, int32_t N_max, const int32_t* model,
+                                         const int32_t* n_frames, const double* q, const double* meas, const double* weight, const int32_t* stance,
+                                         const double* grf_fixed, const double* tau_box, const double* grf_box, double ridge, double* cov_diag,
+                                         double* cov_off, double* cov_pos, double* cov_f, double* f, int32_t* meta, double* L, cpe_status* status) {
+    if (!model || !n_frames) return fail(CPE_BAD_ARG, "cpe_covariance_kinetic_ragged: null model / n_frames");
+    return covariance_kinetic_impl("cpe_covariance_kinetic_ragged", h, opts, B, N_max, model, n_frames, q, meas, weight, stance, grf_fixed, tau_box, grf_box,
+                                   ridge, cov_diag, cov_off, cov_pos, cov_f, f, meta, L, status);
+}
+
+// host-pointer twins (stage through HBM): cpe_covariance_kinetic_host (model == null) and cpe_covariance_kinetic_ragged_host
+static cpe_status covariance_kinetic_host_impl(const char* who, cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const int32_t* model,
+                                               const int32_t* n_frames, const double* q, const double* meas, const double* weight, const int32_t* stance,
+                                               const double* grf_fixed, const double* tau_box, const double* grf_box, double ridge, double* cov_diag,
+                                               double* cov_off, double* cov_pos, double* cov_f, double* f, int32_t* meta, double* L, cpe_status* status) {
     if (cpe_status s = cov_kinetic_check(who, h, opt, stance, grf_fixed, tau_box, grf_box, ridge); s != CPE_OK) return s;
     if (!h || !q || !meas || !weight || !cov_diag || !status) return fail(CPE_BAD_ARG, "null argument");
     size_t F;
     if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
     if (F == 0) return CPE_OK;
+    if (model) {            // (refused here too: before anything is staged)
+        std::vector<int2> seq;
+        if (cpe_status s = cov_kinetic_batch(who, h, opt, B, N, model, n_frames, seq); s != CPE_OK) return s;
+    }
     const DevModel& m = h->hm;
     HIPCHK(hipSetDevice(h->device));
     const int nf = opt->dyn.n_feet, nmot = opt->dyn.n_motors;
@@ -2369,11 +2414,29 @@ cpe_status cpe_covariance_kinetic_host(cpe_handle* h, const cpe_kinetic_options*
     double *oc = st.out_opt(cov_f, F * FF), *of = st.out_opt(f, F * KIN_LS), *ol = st.out_opt(L, F * 4 * BB);
     int32_t* ometa = st.out_opt(meta, F * (KIN_LS + 1));
     HIPCHK(st.err);
-    const cpe_status s = cpe_covariance_kinetic(h, opt, B, N, dq, dmeas, dweight, dstance, grf_fixed ? dvar : nullptr, tau_box ? dvar : nullptr,
-                                                grf_box ? dvar : nullptr, ridge, od, oo, op, oc, of, ometa, ol, status);
+    const cpe_status s = covariance_kinetic_impl(model ? "cpe_covariance_kinetic_ragged" : "cpe_covariance_kinetic", h, opt, B, N, model, n_frames, dq, dmeas,
+                                                 dweight, dstance, grf_fixed ? dvar : nullptr, tau_box ? dvar : nullptr, grf_box ? dvar : nullptr, ridge, od,
+                                                 oo, op, oc, of, ometa, ol, status);
     if (s < 0) return s;
     HIPCHK(st.fetch());
     return s;
+}
+
+cpe_status cpe_covariance_kinetic_host(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q, const double* meas,
+                                       const double* weight, const int32_t* stance, const double* grf_fixed, const double* tau_box,
+                                       const double* grf_box, double ridge, double* cov_diag, double* cov_off, double* cov_pos, double* cov_f, double* f,
+                                       int32_t* meta, double* L, cpe_status* status) {
+    return covariance_kinetic_host_impl("cpe_covariance_kinetic_host", h, opt, B, N, nullptr, nullptr, q, meas, weight, stance, grf_fixed, tau_box, grf_box,
+                                        ridge, cov_diag, cov_off, cov_pos, cov_f, f, meta, L, status);
+}
+
+cpe_status cpe_covariance_kinetic_ragged_host(cpe_handle* h, const cpe_kinetic_options* opts, int32_t B, int32_t N_max, const int32_t* model,
+                                              const int32_t* n_frames, const double* q, const double* meas, const double* weight, const int32_t* stance,
+                                              const double* grf_fixed, const double* tau_box, const double* grf_box, double ridge, double* cov_diag,
+                                              double* cov_off, double* cov_pos, double* cov_f, double* f, int32_t* meta, double* L, cpe_status* status) {
+    if (!model || !n_frames) return fail(CPE_BAD_ARG, "cpe_covariance_kinetic_ragged_host: null model / n_frames");
+    return covariance_kinetic_host_impl("cpe_covariance_kinetic_ragged_host", h, opts, B, N_max, model, n_frames, q, meas, weight, stance, grf_fixed, tau_box,
+                                        grf_box, ridge, cov_diag, cov_off, cov_pos, cov_f, f, meta, L, status);
 }
 
 #ifdef CPE_LM_STAMPS

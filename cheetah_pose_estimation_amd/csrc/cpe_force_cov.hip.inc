@@ -32,16 +32,24 @@ __device__ __forceinline__ void fc_lower_tile(int t, int& ti, int& tj) {
 // cov_diag / cov_off: the band of Sigma as k_lm_selinv wrote it (cov_off block [f][k-1] = Sigma(f + k, f), PB = 3).  cov_f [F][KIN_LS][KIN_LS], f_out
 // [F][KIN_LS] and meta_out [F][KIN_LS + 1] (each may be null): the node's forces and (count, indices of its free forces, zeros, Newton iterations).
 // bad [B]: set to 1 where a node's M has no Cholesky factor (the host clears that sequence's outputs).
+// RAGGED (cpe_covariance_kinetic_ragged): N = rg.nmax; sequence b has its own frame count and its own entry of K, by the table rg.
+template <bool RAGGED = false>
 __global__ __launch_bounds__(KIN_THREADS, 1) void k_force_cov(const DevKin* __restrict__ K, const SeqState* __restrict__ st, int N, size_t n_frames,
                                                               const double* __restrict__ pieces, const int* __restrict__ pmeta,
                                                               const double* __restrict__ fbuf, const double* __restrict__ kmu,
                                                               const int32_t* __restrict__ stance, const double* __restrict__ cov_diag,
                                                               const double* __restrict__ cov_off, double* __restrict__ cov_f,
-                                                              double* __restrict__ f_out, int32_t* __restrict__ meta_out, int* __restrict__ bad) {
+                                                              double* __restrict__ f_out, int32_t* __restrict__ meta_out, int* __restrict__ bad,
+                                                              RaggedArgs rg = RaggedArgs{}) {
     extern __shared__ double smem[];
     __shared__ int flag;
     const int tid = threadIdx.x;
     const int b = (int)(blockIdx.x / (unsigned)N), n = (int)(blockIdx.x % (unsigned)N);
+    if constexpr (RAGGED) {
+        const int2 rs = rg.seq[b];
+        if (n >= rs.y) return;                                // a frame past the sequence's own
+        K += rs.x;
+    }
     if (n < 2 || !cov_seq_ok(st, b)) return;                  // uniform; no node, or no factor of the band: the outputs stay zero
     const size_t f_ = (size_t)b * N + n;
     const SeqState Sq = st[b];

@@ -619,6 +619,23 @@ class KineticUncertainty:
     reason: Optional[str] = None
 
 
+def _no_factor_reason(ridge: float, names: Optional[Sequence[str]] = None) -> str:
+    """why a physics-based estimate has no uncertainty (names: the estimators of a batch it holds for)"""
+    who = "" if names is None else f" (no uncertainty for: {', '.join(names)})"
+    return (f"uncertainty: the evaluation at the solution is not finite, or the reduced band or a node's force matrix has no "
+            f"Cholesky factor at ridge {ridge:g} (the data leave a coordinate or a force undetermined; a positive "
+            f"uncertainty_ridge regularises it){who}")
+
+
+def _kinetic_uncertainty_of(cov: dict, b: int, ridge: float, res: dict) -> KineticUncertainty:
+    """sequence b of a covariance_kinetic_host / covariance_kinetic_ragged_host result; res: the solve's result of that ONE sequence"""
+    if cov["seq_status"][b] != abi.OK:
+        return KineticUncertainty(reason=_no_factor_reason(ridge))
+    unc = _uncertainty_of(cov, b, ridge)
+    unc.update(force_uncertainty(cov["cov_f"][b], cov["meta"][b], res["tau"].shape[-1], res["lam"].shape[-1], res["grf"].shape[-2]))
+    return KineticUncertainty(fields=unc)
+
+
 def _kinetic_uncertainty(h, ko: abi.KineticOptions, res: dict, meas: np.ndarray, weight: np.ndarray, stance: np.ndarray, ridge: float,
                          grf_fixed=None, tau_box=None, grf_box=None) -> KineticUncertainty:
     """cpe_covariance_kinetic at the solution res["q"] of a converged physics-based solve, with the solve's own stance, options and variant arrays"""
@@ -627,25 +644,23 @@ def _kinetic_uncertainty(h, ko: abi.KineticOptions, res: dict, meas: np.ndarray,
     one = lambda a: None if a is None else a[None]
     cov = h.covariance_kinetic_host(res["q"], meas[None], weight[None], stance[None], ko, ridge, grf_fixed=one(grf_fixed), tau_box=one(tau_box),
                                     grf_box=one(grf_box))
-    if cov["seq_status"][0] != abi.OK:
-        return KineticUncertainty(reason=f"uncertainty: the evaluation at the solution is not finite, or the reduced band or a node's force matrix has no "
-                                         f"Cholesky factor at ridge {ridge:g} (the data leave a coordinate or a force undetermined; a positive "
-                                         "uncertainty_ridge regularises it)")
-    unc = _uncertainty_of(cov, 0, ridge)
-    unc.update(force_uncertainty(cov["cov_f"][0], cov["meta"][0], res["tau"].shape[-1], res["lam"].shape[-1], res["grf"].shape[-2]))
-    return KineticUncertainty(fields=unc)
+    return _kinetic_uncertainty_of(cov, 0, ridge, res)
 
 
-def _store_kinetic_uncertainty(est: CheetahEstimator, unc: Optional[KineticUncertainty], ok: bool, out_dir: Optional[str]) -> None:
+def _store_kinetic_uncertainty(est: CheetahEstimator, unc: Optional[KineticUncertainty], ok: bool, out_dir: Optional[str],
+                               no_factor: Optional[list] = None) -> None:
     """after the solve's own files (unc None: not asked for, nothing changes): est.uncertainty and, for a solve that is `ok`, uncertainty.npz beside
-    fte.pickle -- or the library's reason raised"""
+    fte.pickle -- or the library's reason raised (no_factor, a list: the estimator is appended to it instead, for the batch to raise once at its end)"""
     if unc is None:
         return
     est.uncertainty = None
     if not ok:
         return
     if unc.reason is not None:
-        raise _lib.CpeError(unc.reason)
+        if no_factor is None:
+            raise _lib.CpeError(unc.reason)
+        no_factor.append(est)
+        return
     if unc.fields is not None:
         est.uncertainty = unc.fields
         np.savez(os.path.join(out_dir, "uncertainty.npz"), **unc.fields)
@@ -1168,9 +1183,10 @@ def _kinetic_prepare(est: CheetahEstimator, auto: bool, use_2d_reprojections: bo
 
 
 def _kinetic_finish(est: CheetahEstimator, h, res: dict, seconds: float, prep: dict, solver_output: bool, out_fname: str,
-                    out_dir_prefix: Optional[str], uncertainty: Optional[KineticUncertainty] = None) -> bool:
+                    out_dir_prefix: Optional[str], uncertainty: Optional[KineticUncertainty] = None, no_factor: Optional[list] = None) -> bool:
     """what estimate_kinetics does after the solver call: centre of mass, costs, `ok`, files.  `res` holds ONE sequence; h: a handle of its model.
-    uncertainty: what _kinetic_uncertainty returned, or None (not asked for); stored after the solve's own files (_store_kinetic_uncertainty)."""
+    uncertainty: what _kinetic_uncertainty returned, or None (not asked for); stored after the solve's own files (_store_kinetic_uncertainty, which
+    no_factor goes to)."""
     params, scene = est.params, est.scene
     N, q_init, stance, ko = prep["N"], prep["q_init"], prep["stance"], prep["ko"]
     est.opt_time_s = seconds
@@ -1200,7 +1216,7 @@ def _kinetic_finish(est: CheetahEstimator, h, res: dict, seconds: float, prep: d
         dname = f"fte_kinetic{'_gt' if params.hand_labeled_data else ''}"
         dname = dname if scene.cam_idx is None else f"{dname}_{scene.cam_idx}"
         out_dir = est.save(dname, fname=out_fname, out_dir_prefix=out_dir_prefix)
-    _store_kinetic_uncertainty(est, uncertainty, ok, out_dir)
+    _store_kinetic_uncertainty(est, uncertainty, ok, out_dir, no_factor)
     return ok
 
 
@@ -1237,14 +1253,22 @@ def estimate_kinetics_batch(estimators: Sequence[CheetahEstimator], init_torques
                             no_slip: bool = True, joint_estimation: bool = False, fix_grf: bool = True, ground_constraint: bool = False,
                             disable_pose_prior: bool = False, disable_motion_prior: bool = False, plot: bool = False, out_fname: str = "fte",
                             out_dir_prefix: Optional[str] = None, options: Optional[abi.Options] = None,
-                            kinetic_options: Optional[abi.KineticOptions] = None, ragged: bool = False) -> List[bool]:
+                            kinetic_options: Optional[abi.KineticOptions] = None, ragged: bool = False, uncertainty: bool = False,
+                            uncertainty_ridge: float = 0.0) -> List[bool]:
     """estimate_kinetics for MANY sequences at once, with its keyword arguments (applied to every sequence).  Each sequence is prepared as
     estimate_kinetics prepares it (the per-frame force fit of the fix_grf=True, synthesised_grf=False branch included, one sequence at a time),
     then solved in a batch, then gets its centre of mass, costs and files exactly as estimate_kinetics writes them; only processing_time_s (its
     share of the batched solve) differs.  All estimators must live on the same device.  Returns one bool per estimator, in order.
     ragged=False: sequences with the same skeleton, rig, length, options, kinetic options, priors, variant and device share ONE solve_kinetic_host
     call.  ragged=True: they need only share kinetic_ragged_group_key; each group is ONE cpe_solve_kinetic_ragged call over a Handle.multi of its
-    distinct (skeleton, rig, options, kinetic options) models, whatever the lengths.  Every sequence's results are bit-equal either way."""
+    distinct (skeleton, rig, options, kinetic options) models, whatever the lengths.  Every sequence's results are bit-equal either way.
+    uncertainty=True: as in estimate_kinetics, from ONE covariance call per group on the group's handle over its converged sequences
+    (covariance_kinetic_host; ragged: covariance_kinetic_ragged_host); every sequence's est.uncertainty and uncertainty.npz are bit-equal to those of
+    its own estimate_kinetics call.  A sequence without a factor does not stop the batch: every sequence is finished and stored first, then ONE
+    CpeError names all of them."""
+    if uncertainty and not use_2d_reprojections:
+        raise NotImplementedError("uncertainty together with use_2d_reprojections=False: cpe_covariance_kinetic takes the reprojection cost; the covariance "
+                                  "of the 3D kinematic cost (cpe_solve_kinetic_tracked) is not built")
     ests = list(estimators)
     out: List[Optional[bool]] = [None] * len(ests)
     groups: Dict[tuple, List[int]] = {}
@@ -1259,13 +1283,36 @@ def estimate_kinetics_batch(estimators: Sequence[CheetahEstimator], init_torques
         else:
             key = (_kinetic_model_bytes(est, p), p["N"], None if p["pri"] is None else _struct_bytes(p["pri"]), p["variant"], est.device, p["tracked"])
         groups.setdefault(key, []).append(i)
+    if uncertainty:                                  # what is refused, before anything is solved
+        for idx in groups.values():
+            _lib.covariance_supported(prepared[idx[0]]["pri"], uncertainty_ridge)
+    no_factor: List[CheetahEstimator] = []
     for idx in groups.values():
-        (_solve_kinetic_ragged_group if ragged else _solve_kinetic_group)(ests, idx, prepared, out, solver_output, out_fname, out_dir_prefix)
+        (_solve_kinetic_ragged_group if ragged else _solve_kinetic_group)(ests, idx, prepared, out, solver_output, out_fname, out_dir_prefix,
+                                                                          uncertainty_ridge if uncertainty else None, no_factor)
+    if no_factor:
+        raise _lib.CpeError(_no_factor_reason(uncertainty_ridge, [f"{e.name} {e.data_path}" for e in no_factor]))
     return [bool(v) for v in out]
 
 
-def _solve_kinetic_group(ests, idx, prepared, out, solver_output, out_fname, out_dir_prefix) -> None:
-    """estimate_kinetics_batch(ragged=False) for one group: one handle, one solve_kinetic_host call with B = the group's size"""
+def _batch_kinetic_uncertainty(res: dict, idx, ridge: Optional[float], covariance) -> Dict[int, KineticUncertainty]:
+    """uncertainty of every sequence of a solved group, keyed by its place b in the group (empty: not asked for).  covariance(conv): ONE
+    covariance call over the places `conv` of the group, those whose solve converged; the others get nothing, as in _kinetic_uncertainty."""
+    if ridge is None:
+        return {}
+    unc = {b: KineticUncertainty() for b in range(len(idx))}
+    conv = [b for b in range(len(idx)) if res["stats"][b].status == abi.OK]
+    if conv:
+        cov = covariance(conv)
+        for k, b in enumerate(conv):
+            unc[b] = _kinetic_uncertainty_of(cov, k, ridge, _kinetic_one(res, b))
+    return unc
+
+
+def _solve_kinetic_group(ests, idx, prepared, out, solver_output, out_fname, out_dir_prefix, uncertainty_ridge: Optional[float] = None,
+                         no_factor: Optional[list] = None) -> None:
+    """estimate_kinetics_batch(ragged=False) for one group: one handle, one solve_kinetic_host call with B = the group's size (and, with
+    uncertainty_ridge, one covariance_kinetic_host call)"""
     e0, p0 = ests[idx[0]], prepared[idx[0]]
     stack = lambda k: None if p0[k] is None else np.stack([prepared[i][k] for i in idx])
     h = _lib.Handle(p0["skeleton"], e0.cams, p0["opts"], p0["pri"], device=e0.device)
@@ -1278,15 +1325,21 @@ def _solve_kinetic_group(ests, idx, prepared, out, solver_output, out_fname, out
         else:
             res = h.solve_kinetic_host(p0["ko"], stack("q_init"), meas, weight, stack("stance"), grf_fixed=stack("grf_fixed"), grf_box=stack("grf_box"))
         dt = (time() - t0) / len(idx)                                                # processing_time_s of a sequence: its share of the batched solve
+        cut = lambda a, conv: None if a is None else a[conv]
+        unc = _batch_kinetic_uncertainty(res, idx, uncertainty_ridge, lambda conv: h.covariance_kinetic_host(
+            res["q"][conv], meas[conv], weight[conv], stack("stance")[conv], p0["ko"], uncertainty_ridge, grf_fixed=cut(stack("grf_fixed"), conv),
+            grf_box=cut(stack("grf_box"), conv)))
         for b, i in enumerate(idx):
-            out[i] = _kinetic_finish(ests[i], h, _kinetic_one(res, b), dt, prepared[i], solver_output, out_fname, out_dir_prefix)
+            out[i] = _kinetic_finish(ests[i], h, _kinetic_one(res, b), dt, prepared[i], solver_output, out_fname, out_dir_prefix, unc.get(b), no_factor)
     finally:
         h.close()
 
 
-def _solve_kinetic_ragged_group(ests, idx, prepared, out, solver_output, out_fname, out_dir_prefix) -> None:
+def _solve_kinetic_ragged_group(ests, idx, prepared, out, solver_output, out_fname, out_dir_prefix, uncertainty_ridge: Optional[float] = None,
+                                no_factor: Optional[list] = None) -> None:
     """estimate_kinetics_batch(ragged=True) for one group: one model per distinct (skeleton, rig, options, kinetic options), one
-    cpe_solve_kinetic_ragged call, then every sequence's centre of mass, costs and files through _kinetic_finish with a plain handle of its model"""
+    cpe_solve_kinetic_ragged call (and, with uncertainty_ridge, one cpe_covariance_kinetic_ragged call on the same handle), then every sequence's
+    centre of mass, costs and files through _kinetic_finish with a plain handle of its model"""
     models: Dict[bytes, int] = {}
     of = [models.setdefault(_kinetic_model_bytes(ests[i], prepared[i]), len(models)) for i in idx]
     first = {}
@@ -1308,11 +1361,16 @@ def _solve_kinetic_ragged_group(ests, idx, prepared, out, solver_output, out_fna
             res = h.solve_kinetic_ragged_host([prepared[i]["ko"] for i in reps], [prepared[i]["q_init"] for i in idx], [ests[i].meas for i in idx],
                                               [ests[i].weight for i in idx], [prepared[i]["stance"] for i in idx], of, **fkw)
         dt = (time() - t0) / len(idx)                                                # processing_time_s of a sequence: its share of the batched solve
+        unc = _batch_kinetic_uncertainty(res, idx, uncertainty_ridge, lambda conv: h.covariance_kinetic_ragged_host(
+            [res["q"][b] for b in conv], [ests[idx[b]].meas for b in conv], [ests[idx[b]].weight for b in conv],
+            [prepared[idx[b]]["stance"] for b in conv], [prepared[i]["ko"] for i in reps], [of[b] for b in conv], uncertainty_ridge,
+            **{k: [v[b] for b in conv] for k, v in fkw.items()}))
         for b, i in enumerate(idx):
             if of[b] not in fk:
                 r = reps[of[b]]
                 fk[of[b]] = _lib.Handle(prepared[r]["skeleton"], ests[r].cams, prepared[r]["opts"], None, device=dev)
-            out[i] = _kinetic_finish(ests[i], fk[of[b]], _kinetic_one(res, b), dt, prepared[i], solver_output, out_fname, out_dir_prefix)
+            out[i] = _kinetic_finish(ests[i], fk[of[b]], _kinetic_one(res, b), dt, prepared[i], solver_output, out_fname, out_dir_prefix, unc.get(b),
+                                     no_factor)
     finally:
         h.close()
         for f in fk.values():

@@ -639,8 +639,8 @@ cpe_status cpe_covariance_ragged_host(cpe_handle* h, int32_t B, int32_t N_max, c
  * status[b] is CPE_NUMERICAL, and every output of that sequence zero, where the evaluation is not finite or the band or any node's M_n has no Cholesky
  * factor; the damping is never raised silently.  Results are reproducible bit for bit (no atomics), and a sequence's outputs do not depend on its batch.
  * Refused with CPE_BAD_ARG before the device is touched, the reason in cpe_last_error(): ridge < 0 or not finite; a handle whose half-bandwidth is not 3
- * (motion-prior windows above 3); NULL opt or stance; more than one of grf_fixed, tau_box, grf_box.  Not built: ragged batches, the 3D kinematic cost
- * (cpe_solve_kinetic_tracked*), the shutter displacement. */
+ * (motion-prior windows above 3); NULL opt or stance; more than one of grf_fixed, tau_box, grf_box.  Not built: the 3D kinematic cost (cpe_solve_kinetic_tracked*),
+ * the shutter displacement. */
 cpe_status cpe_covariance_kinetic(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q, const double* meas,
                                   const double* weight, const int32_t* stance, const double* grf_fixed, const double* tau_box, const double* grf_box,
                                   double ridge, double* cov_diag, double* cov_off, double* cov_pos, double* cov_f, double* f, int32_t* meta, double* L,
@@ -650,6 +650,26 @@ cpe_status cpe_covariance_kinetic_host(cpe_handle* h, const cpe_kinetic_options*
                                        const double* weight, const int32_t* stance, const double* grf_fixed, const double* tau_box,
                                        const double* grf_box, double ridge, double* cov_diag, double* cov_off, double* cov_pos, double* cov_f, double* f,
                                        int32_t* meta, double* L, cpe_status* status);
+/* The same for sequences of their own length, rig and model, in cpe_solve_kinetic_ragged's layout: a handle of cpe_create_multi, opts [n_models] (one
+ * cpe_kinetic_options per model of the handle), model [B] and n_frames [B] HOST arrays, every per-frame array padded to N_max frames (meas / weight
+ * to C_max cameras as well).  For every sequence b the rows [0, n_frames[b]) of cov_diag, cov_off, cov_pos, cov_f, f, meta and L, and status[b], are
+ * bit-equal to cpe_covariance_kinetic of that sequence alone (B = 1, N = n_frames[b]) on a plain handle of its own model; rows past a sequence's
+ * length read 0.  status[b] is CPE_NUMERICAL, and every output of that sequence zero (what the band kernels had written included), where its
+ * evaluation is not finite or its band or one of its nodes' M_n has no Cholesky factor; such a sequence does not disturb a neighbour's bits.  Returns
+ * the worst status.  cov_off == NULL works as in the plain entry.
+ * Refused with CPE_BAD_ARG before the device is touched, the reason in cpe_last_error(): what cpe_covariance_kinetic refuses; NULL model or n_frames;
+ * a model index or frame count out of range; kinetic options of a model that differ from model 0's in a field that fixes the layout of the node
+ * forces (dyn.n_feet, dyn.foot_marker, dyn.n_motors, dyn.motor_first / _second / _axis: the field is named). */
+cpe_status cpe_covariance_kinetic_ragged(cpe_handle* h, const cpe_kinetic_options* opts, int32_t B, int32_t N_max, const int32_t* model /*[B] host*/,
+                                         const int32_t* n_frames /*[B] host*/, const double* q, const double* meas, const double* weight,
+                                         const int32_t* stance, const double* grf_fixed, const double* tau_box, const double* grf_box, double ridge,
+                                         double* cov_diag, double* cov_off, double* cov_pos, double* cov_f, double* f, int32_t* meta, double* L,
+                                         cpe_status* status);
+/* host-pointer twin (stages through HBM) */
+cpe_status cpe_covariance_kinetic_ragged_host(cpe_handle* h, const cpe_kinetic_options* opts, int32_t B, int32_t N_max, const int32_t* model,
+                                              const int32_t* n_frames, const double* q, const double* meas, const double* weight, const int32_t* stance,
+                                              const double* grf_fixed, const double* tau_box, const double* grf_box, double ridge, double* cov_diag,
+                                              double* cov_off, double* cov_pos, double* cov_f, double* f, int32_t* meta, double* L, cpe_status* status);
 
 /* forward kinematics only (get_pose_state / get_com, acinoset_misc.py:1581-1659, :722-742); device ptrs */
 cpe_status cpe_forward_kinematics(cpe_handle* h, int32_t B, int32_t N, const double* q,
