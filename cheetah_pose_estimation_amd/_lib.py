@@ -752,6 +752,63 @@ class Handle:
         res.update(status=st, seq_status=list(seq)[:B], padded=out)
         return res
 
+    # ---- posterior covariance of the rates (include/cpe.h, cpe_rate_covariance) -----------------------------------------------------------
+    def rate_covariance(self, q, cov_diag, cov_off, cov_du=None, cov_ddu=None, cov_vel=None, cov_com=None, cov_com_vel=None, jac_pos=None,
+                        jac_com=None):
+        """cpe_rate_covariance on device tensors: q [B, N, nq], cov_diag [B, N, 28, 28], cov_off [B, N, pb, 28, 28] (a covariance entry's band) ->
+        cov_du, cov_ddu [B, N, 28, 28], cov_vel [B, N, L, 3, 3], cov_com, cov_com_vel [B, N, 3, 3], jac_pos [B, N, L, 3, 28], jac_com [B, N, 3, 28];
+        each may be None, not all"""
+        self._call(self.lib.cpe_rate_covariance, "cpe_rate_covariance", q.shape[0], q.shape[1], _ptr(q), _ptr(cov_diag), _ptr(cov_off), _ptr(cov_du),
+                   _ptr(cov_ddu), _ptr(cov_vel), _ptr(cov_com), _ptr(cov_com_vel), _ptr(jac_pos), _ptr(jac_com))
+
+    def _rate_outputs(self, B, N, want):
+        shapes = dict(cov_du=(28, 28), cov_ddu=(28, 28), cov_vel=(self.L, 3, 3), cov_com=(3, 3), cov_com_vel=(3, 3), jac_pos=(self.L, 3, 28),
+                      jac_com=(3, 28))
+        unknown = set(want) - set(shapes)
+        if unknown:
+            raise ValueError(f"rate covariance: unknown outputs {sorted(unknown)}")
+        return {k: np.empty((B, N) + shapes[k]) if k in want else None for k in abi.RATE_COVARIANCE_OUTPUTS}
+
+    def rate_covariance_host(self, q, cov_diag, cov_off, want=abi.RATE_COVARIANCE_OUTPUTS):
+        """cpe_rate_covariance_host: numpy in, dict of numpy arrays out (the outputs named in `want`, shapes as in rate_covariance())"""
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        q, cov_diag, cov_off = f64(q), f64(cov_diag), f64(cov_off)
+        B, N = q.shape[:2]
+        if cov_diag.shape != (B, N, 28, 28) or cov_off.shape != (B, N, self.pb, 28, 28):
+            raise ValueError(f"rate_covariance_host: cov_diag / cov_off do not have the shapes of q and the handle's half-bandwidth {self.pb}")
+        out = self._rate_outputs(B, N, want)
+        st = self.lib.cpe_rate_covariance_host(self._h, B, N, _ptr(q), _ptr(cov_diag), _ptr(cov_off), *[_ptr(out[k]) for k in abi.RATE_COVARIANCE_OUTPUTS])
+        _check(st, "cpe_rate_covariance_host")
+        return {k: v for k, v in out.items() if v is not None}
+
+    def rate_covariance_ragged_host(self, q_list, cov_diag_list, cov_off_list, model_list=None, want=abi.RATE_COVARIANCE_OUTPUTS):
+        """cpe_rate_covariance_ragged_host over sequences of their own length and model (covariance_ragged_host's q_list and model_list, and its
+        per-sequence cov_diag / cov_off): pads, runs, unpads.  Returns dict(the outputs named in `want` = lists of per-sequence arrays [N_b, ...],
+        padded = the padded outputs)."""
+        B = len(q_list)
+        models = [0] * B if model_list is None else [int(m) for m in model_list]
+        if len(cov_diag_list) != B or len(cov_off_list) != B or len(models) != B:
+            raise ValueError("rate_covariance_ragged_host: one q, cov_diag, cov_off and model per sequence")
+        if any(m < 0 or m >= len(self.model_n_cams) for m in models):
+            raise ValueError("rate_covariance_ragged_host: model index out of range")
+        lens = [int(np.shape(a)[0]) for a in q_list]
+        for b in range(B):
+            if np.shape(q_list[b]) != (lens[b], self.nq) or np.shape(cov_diag_list[b]) != (lens[b], 28, 28) or \
+                    np.shape(cov_off_list[b]) != (lens[b], self.pb, 28, 28):
+                raise ValueError(f"rate_covariance_ragged_host: sequence {b} does not have the shapes of its {lens[b]} frames")
+        Nm = max(lens) if lens else 0
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        q, cd, co = f64(_pad(q_list, Nm, (self.nq,))), f64(_pad(cov_diag_list, Nm, (28, 28))), f64(_pad(cov_off_list, Nm, (self.pb, 28, 28)))
+        out = self._rate_outputs(B, Nm, want)
+        mo, nf = (C.c_int32 * max(B, 1))(*models), (C.c_int32 * max(B, 1))(*lens)
+        st = self.lib.cpe_rate_covariance_ragged_host(self._h, B, Nm, mo, nf, _ptr(q), _ptr(cd), _ptr(co),
+                                                      *[_ptr(out[k]) for k in abi.RATE_COVARIANCE_OUTPUTS])
+        _check(st, "cpe_rate_covariance_ragged_host")
+        out = {k: v for k, v in out.items() if v is not None}
+        res = unpad_kinetic(out, lens, None)
+        res.update(padded=out)
+        return res
+
     # ---- posterior covariance of the physics-based estimate (include/cpe.h, cpe_covariance_kinetic) ------------------------------------
     def covariance_kinetic(self, kopt, q, meas, weight, stance, ridge, cov_diag, cov_off=None, cov_pos=None, cov_f=None, f=None, meta=None, L=None,
                            grf_fixed=None, tau_box=None, grf_box=None):

@@ -196,6 +196,15 @@ KINETIC_COVARIANCE_RAGGED_ENTRIES = {
     "cpe_covariance_kinetic_ragged": _KIN_BN + _RAGGED + _KIN_COV,
     "cpe_covariance_kinetic_ragged_host": _KIN_BN + _RAGGED + _KIN_COV,
 }
+# the rates (cpe_rate_covariance): h, B, N (| model, n_frames) | q, cov_diag, cov_off | cov_du, cov_ddu, cov_vel, cov_com, cov_com_vel, jac_pos, jac_com
+_RATE_COV = ("p",) * 10
+RATE_COVARIANCE_ENTRIES = {
+    "cpe_rate_covariance": _BN + _RATE_COV,
+    "cpe_rate_covariance_host": _BN + _RATE_COV,
+    "cpe_rate_covariance_ragged": _BN + _RAGGED + _RATE_COV,
+    "cpe_rate_covariance_ragged_host": _BN + _RAGGED + _RATE_COV,
+}
+RATE_COVARIANCE_OUTPUTS = ("cov_du", "cov_ddu", "cov_vel", "cov_com", "cov_com_vel", "jac_pos", "jac_com")      # in the order of the arguments
 COVARIANCE_MAX_PB = 4        # largest half-bandwidth (frames) the covariance sweep supports: motion-prior windows 5 and 6 are refused
 ENTRIES = {
     "cpe_create": ("sk", "cam", "i", "op", "pr", "i", "hp"),
@@ -251,7 +260,7 @@ ENTRIES = {
     # q, meas, weight, tau | lam | g, Bm, cost, gx, rcb, g_total, step, meas_err, seq
     "cpe_eval_shutter_step": _BN + ("p",) * 4 + ("d",) + ("p",) * 9,
     "cpe_eval_shutter_step_host": _BN + ("p",) * 4 + ("d",) + ("p",) * 9,
-    **COVARIANCE_ENTRIES, **KINETIC_COVARIANCE_ENTRIES, **KINETIC_COVARIANCE_RAGGED_ENTRIES,
+    **COVARIANCE_ENTRIES, **KINETIC_COVARIANCE_ENTRIES, **KINETIC_COVARIANCE_RAGGED_ENTRIES, **RATE_COVARIANCE_ENTRIES,
 }
 
 

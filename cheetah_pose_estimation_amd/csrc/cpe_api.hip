@@ -69,6 +69,10 @@ struct cpe_handle {
     DevTrack* dtrack = nullptr; std::vector<DevTrack> htrack;
     double* xtgt = nullptr; size_t xtgt_frames = 0;
     double* covG = nullptr; size_t covG_n = 0;     // cpe_covariance / cpe_band_inverse: the sweep's operands T^T T | G_1 .. G_pb of every column
+    // cpe_rate_covariance: the handle's skeletons once more with the link centres as markers (centre-of-mass Jacobian), host and device, in
+    // dm's order -- or why they could not be built; and the Jacobians of a call that does not ask for them
+    std::vector<DevModel> cmodels; DevModel* dmc = nullptr; std::string com_err;
+    double* rateJ = nullptr; size_t rateJ_n = 0;
     int pb = 3;                // half-bandwidth of the normal equations in frames (W with a window-W motion prior, W = 4..6)
 };
 
@@ -135,7 +139,8 @@ static double host_rho0(double a, double b, double c) {
            sc * (a * b - 0.5 * a * a + 0.5 * a * cb);
 }
 
-static cpe_status build_model(const cpe_skeleton* s, const cpe_camera* cams, int C, const cpe_options* o, DevModel& m) {
+// gather = false: without the gather lists of H and g (a model that only serves the reduced marker columns, build_com_model)
+static cpe_status build_model(const cpe_skeleton* s, const cpe_camera* cams, int C, const cpe_options* o, DevModel& m, bool gather = true) {
     memset(&m, 0, sizeof(m));
     if (s->n_links < 1 || s->n_links > CPE_MAX_LINKS || s->n_markers < 1 || s->n_markers > CPE_MAX_MARKERS ||
         s->n_joints < 0 || s->n_joints > CPE_MAX_JOINTS || s->n_bounds < 0 || s->n_bounds > CPE_MAX_BOUNDS ||
@@ -382,7 +387,7 @@ static cpe_status build_model(const cpe_skeleton* s, const cpe_camera* cams, int
                     for (int d = 0; d < 3; d++) T.v[d] = m.ss_vec[sl][d];
                 }
     }
-    {   // gather lists for H and g (see cpe_model.h)
+    if (gather) {   // gather lists for H and g (see cpe_model.h)
         const int nu_ = m.nu;
         std::vector<std::vector<uint32_t>> by_entry(nu_ * nu_);
         for (int l = 0; l < L; l++)
@@ -457,6 +462,23 @@ static cpe_status build_model(const cpe_skeleton* s, const cpe_camera* cams, int
     return CPE_OK;
 }
 
+// The skeleton once more with its link centres as markers -- marker i = the centre of mass of link i -- so that the reduced marker columns of this
+// model are d (link centre) / d u: the centre-of-mass Jacobian is their mass-weighted mean (k_point_jac).  Appends to `out`; a skeleton whose link
+// centres do not fit the marker tables leaves the reason in `err` and `out` empty: only the centre-of-mass outputs of cpe_rate_covariance need it.
+static void build_com_model(const cpe_skeleton* s, const cpe_camera* cams, int C, const cpe_options* o, std::vector<DevModel>& out, std::string& err) {
+    if (!err.empty()) return;
+    cpe_skeleton c = *s;
+    c.n_markers = s->n_links;
+    for (int i = 0; i < s->n_links && i < CPE_MAX_MARKERS; i++) {
+        c.marker_link[i] = i;
+        for (int d = 0; d < 3; d++) c.marker_off[i][d] = s->com[i][d];
+    }
+    const std::string keep = g_err;
+    out.emplace_back();
+    if (build_model(&c, cams, C, o, out.back(), false) != CPE_OK) { err = g_err; out.clear(); }
+    g_err = keep;
+}
+
 // the plain variant of k_frame_normal (no Gaussian-mixture prior, no shutter delay) writes H straight to HBM and needs 6 KB less LDS per wave
 #define FRAME_NORMAL(plain) ((plain) ? k_frame_normal<true> : k_frame_normal<false>)
 #define FRAME_NORMAL_RAGGED(plain) ((plain) ? k_frame_normal<true, true> : k_frame_normal<false, true>)
@@ -520,7 +542,10 @@ static cpe_status create_impl(cpe_handle* h, const cpe_skeleton* skel, const cpe
                               const cpe_priors* priors, bool use_pri, const std::vector<DevModel>* models = nullptr) {
     const int device = h->device;
     if (models) { h->models = *models; h->hm = h->models[0]; }
-    else if (cpe_status s = build_model(skel, cams, n_cams, opts, h->hm); s != CPE_OK) return s;
+    else {
+        if (cpe_status s = build_model(skel, cams, n_cams, opts, h->hm); s != CPE_OK) return s;
+        build_com_model(skel, cams, n_cams, opts, h->cmodels, h->com_err);
+    }
     HIPCHK(hipSetDevice(device));
     {
         hipDeviceProp_t prop;
@@ -546,6 +571,10 @@ static cpe_status create_impl(cpe_handle* h, const cpe_skeleton* skel, const cpe
     HIPCHK(hipMalloc(&h->dm, sizeof(DevModel) * n_models(h)));
     HIPCHK(hipMemcpy(h->dm, h->models.empty() ? &h->hm : h->models.data(), sizeof(DevModel) * n_models(h), hipMemcpyHostToDevice));
     HIPCHK(hipMalloc(&h->flag, sizeof(int)));
+    if (!h->cmodels.empty()) {
+        HIPCHK(hipMalloc(&h->dmc, sizeof(DevModel) * h->cmodels.size()));
+        HIPCHK(hipMemcpy(h->dmc, h->cmodels.data(), sizeof(DevModel) * h->cmodels.size(), hipMemcpyHostToDevice));
+    }
     if (use_pri) {
         if (h->hm.nu != CPE_NX) return fail(CPE_BAD_ARG, "learned priors need the 28 relative angles of the reference's skeleton");
         if (priors->gmm_k > 0 && priors->gmm_dim > h->hm.nu) return fail(CPE_BAD_ARG, "pose prior dimension exceeds the number of relative angles");
@@ -704,6 +733,7 @@ cpe_status cpe_create_multi(int32_t n_models, const cpe_skeleton* skels, const c
     if (device < 0 || device >= ndev) return fail(CPE_BAD_ARG, "device index out of range");
     cpe_handle* h = new cpe_handle();
     h->device = device; h->opts = opts[0];
+    for (int k = 0; k < n_models; k++) build_com_model(&skels[k], cams + (size_t)k * CPE_MAX_CAMS, n_cams[k], &opts[k], h->cmodels, h->com_err);
     const cpe_status s = create_impl(h, &skels[0], cams, n_cams[0], &opts[0], priors, use_pri, &models);
     if (s != CPE_OK) { cpe_destroy(h); return s; }
     *out = h;
@@ -723,6 +753,8 @@ void cpe_destroy(cpe_handle* h) {
     if (h->dtrack) (void)hipFree(h->dtrack);
     if (h->xtgt) (void)hipFree(h->xtgt);
     if (h->covG) (void)hipFree(h->covG);
+    if (h->dmc) (void)hipFree(h->dmc);
+    if (h->rateJ) (void)hipFree(h->rateJ);
     if (h->n_act) (void)hipFree(h->n_act);
     if (h->poll_host) (void)hipHostFree(h->poll_host);
     for (int i = 0; i < 2; i++) if (h->poll_ev[i]) (void)hipEventDestroy(h->poll_ev[i]);
@@ -2260,6 +2292,130 @@ cpe_status cpe_covariance_ragged_host(cpe_handle* h, int32_t B, int32_t N_max, c
                                       double* L, cpe_status* status) {
     if (!model || !n_frames) return fail(CPE_BAD_ARG, "null argument");
     return covariance_host_impl(h, B, N_max, model, n_frames, q, meas, weight, ridge, cov_diag, cov_off, cov_pos, L, status);
+}
+
+// ---- posterior covariance of the rates (include/cpe.h, cpe_rate_covariance; kernels in cpe_rate_cov.hip.inc) --------------------------------
+// What both forms refuse, before the device is touched and in this order -- what needs no handle first: negative sizes, the ragged form's null
+// model / n_frames, a null handle, q, cov_diag or cov_off, all outputs null; then a plain handle or a bad table for the ragged form, and a
+// centre-of-mass output for a skeleton without a link-centre model.  Fills F and, for the ragged form, the table.
+static cpe_status rate_cov_check(const char* who, bool ragged, const cpe_handle* h, int32_t B, int32_t N, const int32_t* model, const int32_t* n_frames,
+                                 bool inputs, bool any_output, bool want_com, size_t* F, std::vector<int2>& seq) {
+    const std::string w = std::string(who) + ": ";
+    if (cpe_status s = frames(B, N, F); s != CPE_OK) return fail(s, w + g_err);
+    if (ragged && (!model || !n_frames)) return fail(CPE_BAD_ARG, w + "null model / n_frames");
+    if (!h || !inputs) return fail(CPE_BAD_ARG, w + "null argument (handle, q, cov_diag and cov_off are required)");
+    if (!any_output) return fail(CPE_BAD_ARG, w + "all outputs are null");
+    if (ragged && h->models.empty()) return fail(CPE_BAD_ARG, w + "a plain handle has no ragged form (create it with cpe_create_multi)");
+    if (ragged) { if (cpe_status s = ragged_table(h, B, N, model, n_frames, seq); s != CPE_OK) return fail(s, w + g_err.substr(g_err.find(": ") + 2)); }     // (its own name in place of cpe_solve_ragged's)
+    if (want_com && h->cmodels.empty())
+        return fail(CPE_BAD_ARG, w + "no centre-of-mass Jacobian for this skeleton (its link centres do not fit the marker tables: " + h->com_err + ")");
+    return CPE_OK;
+}
+
+// cpe_rate_covariance (model == nullptr) and cpe_rate_covariance_ragged
+static cpe_status rate_covariance_impl(const char* who, bool ragged, cpe_handle* h, int32_t B, int32_t N, const int32_t* model, const int32_t* n_frames,
+                                       const double* q, const double* cov_diag, const double* cov_off, double* cov_du, double* cov_ddu,
+                                       double* cov_vel, double* cov_com, double* cov_com_vel, double* jac_pos, double* jac_com) {
+    const bool want_com = cov_com || cov_com_vel || jac_com, want_pos = cov_vel || jac_pos;
+    size_t F;
+    std::vector<int2> seq;
+    if (cpe_status s = rate_cov_check(who, ragged, h, B, N, model, n_frames, q && cov_diag && cov_off, cov_du || cov_ddu || want_com || want_pos, want_com, &F, seq);
+        s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    HIPCHK(hipSetDevice(h->device));
+    cpe_status s = ensure_ws(h, B, N);
+    if (s != CPE_OK) return s;
+    const DevModel& m = h->hm;
+    const size_t BB = (size_t)CPE_NX * CPE_NX, PW = 3 * CPE_NX, wd = sizeof(double);
+    // the Jacobians the caller does not take go to scratch of the handle
+    const size_t need = (want_pos && !jac_pos ? F * m.L * PW : 0) + (want_com && !jac_com ? F * PW : 0);
+    if (need > h->rateJ_n) {
+        if (h->rateJ) { HIPCHK(hipStreamSynchronize(h->stream)); (void)hipFree(h->rateJ); h->rateJ = nullptr; h->rateJ_n = 0; }
+        HIPCHK(hipMalloc(&h->rateJ, wd * need));
+        h->rateJ_n = need;
+    }
+    double* jp = !want_pos ? nullptr : jac_pos ? jac_pos : h->rateJ;
+    double* jc = !want_com ? nullptr : jac_com ? jac_com : h->rateJ + (want_pos && !jac_pos ? F * m.L * PW : 0);
+    const RaggedArgs rgv{h->rseq, N, cams_max(h)};
+    const RaggedArgs* rg = ragged ? &rgv : nullptr;
+    if (ragged) HIPCHK(hipMemcpyAsync(h->rseq, seq.data(), sizeof(int2) * B, hipMemcpyHostToDevice, h->stream));     // (seq outlives the stream: it is drained below)
+    if ((s = state_reset(h, B, N, q, rg)) != CPE_OK) return s;
+    // everything that is defined as zero -- past a sequence's frames, row 0 of the velocities, the short sequences, the columns a point does not
+    // depend on -- is zero from here; the kernels write the rest
+    if (jp) HIPCHK(hipMemsetAsync(jp, 0, wd * F * m.L * PW, h->stream));
+    if (jc) HIPCHK(hipMemsetAsync(jc, 0, wd * F * PW, h->stream));
+    if (cov_du) HIPCHK(hipMemsetAsync(cov_du, 0, wd * F * BB, h->stream));
+    if (cov_ddu) HIPCHK(hipMemsetAsync(cov_ddu, 0, wd * F * BB, h->stream));
+    if (cov_vel) HIPCHK(hipMemsetAsync(cov_vel, 0, wd * F * m.L * 9, h->stream));
+    if (cov_com) HIPCHK(hipMemsetAsync(cov_com, 0, wd * F * 9, h->stream));
+    if (cov_com_vel) HIPCHK(hipMemsetAsync(cov_com_vel, 0, wd * F * 9, h->stream));
+    const unsigned gf = (unsigned)F;
+    if (jp || jc) {
+        const size_t lds = wd * PJ_LDS_DOUBLES;
+        if (rg) hipLaunchKernelGGL(k_point_jac<true>, dim3(gf), dim3(WAVE), lds, h->stream, h->dm, h->dmc, N, h->qbuf, jp, jc, *rg);
+        else hipLaunchKernelGGL(k_point_jac<>, dim3(gf), dim3(WAVE), lds, h->stream, h->dm, h->dmc, N, h->qbuf, jp, jc, RaggedArgs{});
+    }
+    if (cov_du || cov_ddu || cov_vel || cov_com || cov_com_vel) {
+        const size_t lds = wd * (3 * BB + 2 * PW * m.L + 2 * PW);       // (at most 63168 bytes, CPE_MAX_MARKERS = 32)
+        if (rg) hipLaunchKernelGGL(k_rate_cov<true>, dim3(gf), dim3(WAVE), lds, h->stream, h->dm, N, h->pb, cov_diag, cov_off, jp, jc, cov_du, cov_ddu,
+                                   cov_vel, cov_com, cov_com_vel, *rg);
+        else hipLaunchKernelGGL(k_rate_cov<>, dim3(gf), dim3(WAVE), lds, h->stream, h->dm, N, h->pb, cov_diag, cov_off, jp, jc, cov_du, cov_ddu,
+                                cov_vel, cov_com, cov_com_vel, RaggedArgs{});
+    }
+    HIPCHK(hipGetLastError());
+    if (ragged) HIPCHK(hipStreamSynchronize(h->stream));
+    return CPE_OK;
+}
+
+cpe_status cpe_rate_covariance(cpe_handle* h, int32_t B, int32_t N, const double* q, const double* cov_diag, const double* cov_off, double* cov_du,
+                               double* cov_ddu, double* cov_vel, double* cov_com, double* cov_com_vel, double* jac_pos, double* jac_com) {
+    return rate_covariance_impl("cpe_rate_covariance", false, h, B, N, nullptr, nullptr, q, cov_diag, cov_off, cov_du, cov_ddu, cov_vel, cov_com, cov_com_vel,
+                                jac_pos, jac_com);
+}
+
+cpe_status cpe_rate_covariance_ragged(cpe_handle* h, int32_t B, int32_t N_max, const int32_t* model, const int32_t* n_frames, const double* q,
+                                      const double* cov_diag, const double* cov_off, double* cov_du, double* cov_ddu, double* cov_vel,
+                                      double* cov_com, double* cov_com_vel, double* jac_pos, double* jac_com) {
+    return rate_covariance_impl("cpe_rate_covariance_ragged", true, h, B, N_max, model, n_frames, q, cov_diag, cov_off, cov_du, cov_ddu, cov_vel, cov_com,
+                                cov_com_vel, jac_pos, jac_com);
+}
+
+// host-pointer twins (stage through HBM); refused on the host pointers, before anything is staged
+static cpe_status rate_covariance_host_impl(const char* who, bool ragged, cpe_handle* h, int32_t B, int32_t N, const int32_t* model,
+                                            const int32_t* n_frames, const double* q, const double* cov_diag, const double* cov_off, double* cov_du,
+                                            double* cov_ddu, double* cov_vel, double* cov_com, double* cov_com_vel, double* jac_pos, double* jac_com) {
+    size_t F;
+    std::vector<int2> seq;
+    if (cpe_status s = rate_cov_check(who, ragged, h, B, N, model, n_frames, q && cov_diag && cov_off,
+                                      cov_du || cov_ddu || cov_vel || cov_com || cov_com_vel || jac_pos || jac_com, cov_com || cov_com_vel || jac_com, &F, seq);
+        s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    const DevModel& m = h->hm;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t BB = (size_t)CPE_NX * CPE_NX, PW = 3 * CPE_NX;
+    Staging st(h->stream);
+    const double *dq = st.in(q, F * m.nq), *dd = st.in(cov_diag, F * BB), *dof = st.in(cov_off, F * h->pb * BB);
+    double *odu = st.out_opt(cov_du, F * BB), *oddu = st.out_opt(cov_ddu, F * BB), *ov = st.out_opt(cov_vel, F * m.L * 9);
+    double *oc = st.out_opt(cov_com, F * 9), *ocv = st.out_opt(cov_com_vel, F * 9), *ojp = st.out_opt(jac_pos, F * m.L * PW), *ojc = st.out_opt(jac_com, F * PW);
+    HIPCHK(st.err);
+    const cpe_status s = rate_covariance_impl(who, ragged, h, B, N, model, n_frames, dq, dd, dof, odu, oddu, ov, oc, ocv, ojp, ojc);
+    if (s != CPE_OK) return s;
+    HIPCHK(st.fetch());
+    return s;
+}
+
+cpe_status cpe_rate_covariance_host(cpe_handle* h, int32_t B, int32_t N, const double* q, const double* cov_diag, const double* cov_off,
+                                    double* cov_du, double* cov_ddu, double* cov_vel, double* cov_com, double* cov_com_vel, double* jac_pos,
+                                    double* jac_com) {
+    return rate_covariance_host_impl("cpe_rate_covariance_host", false, h, B, N, nullptr, nullptr, q, cov_diag, cov_off, cov_du, cov_ddu, cov_vel, cov_com,
+                                     cov_com_vel, jac_pos, jac_com);
+}
+
+cpe_status cpe_rate_covariance_ragged_host(cpe_handle* h, int32_t B, int32_t N_max, const int32_t* model, const int32_t* n_frames, const double* q,
+                                           const double* cov_diag, const double* cov_off, double* cov_du, double* cov_ddu, double* cov_vel,
+                                           double* cov_com, double* cov_com_vel, double* jac_pos, double* jac_com) {
+    return rate_covariance_host_impl("cpe_rate_covariance_ragged_host", true, h, B, N_max, model, n_frames, q, cov_diag, cov_off, cov_du, cov_ddu, cov_vel,
+                                     cov_com, cov_com_vel, jac_pos, jac_com);
 }
 
 // ---- posterior covariance of the physics-based estimate (include/cpe.h, cpe_covariance_kinetic; kernel in cpe_force_cov.hip.inc) -------------

@@ -323,6 +323,8 @@ class CheetahEstimator:
     # the marginal posterior covariance of every frame's reduced coordinates and marker positions (cpe_covariance); None where it does not exist
     # estimate_kinetics / estimate_grf(uncertainty=True): the same fields from cpe_covariance_kinetic plus tau_std [N, n_motors], lambda_std [N, 26],
     # grf_std [N, 4, 3] (net z, x, y per foot) and tau_cov [N, n_motors, n_motors]; 0.0 where a force is not an unknown of that node
+    # uncertainty_rates=True adds RATE_FIELDS (cpe_rate_covariance): du_std, ddu_std [N, 28], velocities_cov / _std [N, L, 3(, 3)], com_cov / _std
+    # [N, 3(, 3)], and, aligned with com_vel, com_vel_cov / _std [N-1, 3(, 3)] and speed_std [N-1]
     uncertainty: Optional[dict] = None
 
     def get_objective_cost(self) -> float:
@@ -577,13 +579,65 @@ def _kin_prepare(est: CheetahEstimator, monocular_constraints: bool, disable_pos
     return q_init, opts, pri
 
 
+RATE_FIELDS = ("du_std", "ddu_std", "velocities_cov", "velocities_std", "com_cov", "com_std", "com_vel_cov", "com_vel_std", "speed_std")
+_RATE_WANT = ("cov_du", "cov_ddu", "cov_vel", "cov_com", "cov_com_vel")
+
+
+def _check_rates(uncertainty: bool, uncertainty_rates: bool) -> None:
+    """uncertainty_rates=True propagates the covariance uncertainty=True computes: alone it is refused, before anything is looked at"""
+    if uncertainty_rates and not uncertainty:
+        raise ValueError("uncertainty_rates=True needs uncertainty=True: the rates are propagated from the covariance that keyword computes")
+
+
+def _with_rates(h, cov: dict, q, rates: bool, model_list=None) -> dict:
+    """a covariance result with, for uncertainty_rates=True, the rate covariances of the same sequences under "rates": ONE cpe_rate_covariance call
+    on the same handle at the same q with that call's cov_diag and cov_off (model_list: the ragged form, lists per sequence)"""
+    if rates:
+        if isinstance(cov["cov_diag"], list):
+            cov["rates"] = h.rate_covariance_ragged_host(q, cov["cov_diag"], cov["cov_off"], model_list, want=_RATE_WANT)
+        else:
+            cov["rates"] = h.rate_covariance_host(q, cov["cov_diag"], cov["cov_off"], want=_RATE_WANT)
+    return cov
+
+
+def _rate_fields(rates: dict, b: int) -> dict:
+    """the rate fields of est.uncertainty of sequence b, all but speed_std (which needs the centre-of-mass velocity: speed_std_of).  com_vel_cov
+    row k is the library's row k + 1: the velocity between the frames k and k + 1, as com_vel[k]."""
+    std = lambda c, a, b_: np.sqrt(np.diagonal(c, axis1=a, axis2=b_))
+    du, ddu, vel = (np.ascontiguousarray(rates[k][b]) for k in ("cov_du", "cov_ddu", "cov_vel"))
+    com, cv = np.ascontiguousarray(rates["cov_com"][b]), np.ascontiguousarray(rates["cov_com_vel"][b][1:])
+    return dict(du_std=std(du, 1, 2), ddu_std=std(ddu, 1, 2), velocities_cov=vel, velocities_std=std(vel, 2, 3), com_cov=com, com_std=std(com, 1, 2),
+                com_vel_cov=cv, com_vel_std=std(cv, 1, 2))
+
+
+def speed_std_of(com_vel: np.ndarray, com_vel_cov: np.ndarray) -> np.ndarray:
+    """standard deviation of the speed |com_vel| by the delta method: sqrt(v^T C v) / |v|, and 0 where |v| = 0"""
+    v = np.asarray(com_vel, dtype=np.float64)
+    var = np.einsum("ni,nij,nj->n", v, com_vel_cov, v)
+    norm = np.sqrt(np.einsum("ni,ni->n", v, v))
+    out = np.zeros(v.shape[0])
+    nz = norm > 0
+    out[nz] = np.sqrt(np.maximum(var[nz], 0.0)) / norm[nz]
+    return out
+
+
+def _add_speed_std(est) -> None:
+    """est.uncertainty["speed_std"] once est.com_vel is known (uncertainty_rates=True; nothing otherwise)"""
+    if est.uncertainty is not None and "com_vel_cov" in est.uncertainty:
+        est.uncertainty["speed_std"] = speed_std_of(est.com_vel, est.uncertainty["com_vel_cov"])
+
+
 def _uncertainty_of(cov: dict, b: int, ridge: float) -> Optional[dict]:
-    """est.uncertainty of sequence b from a covariance_host / covariance_ragged_host result (None where the matrix has no Cholesky factor)"""
+    """est.uncertainty of sequence b from a covariance_host / covariance_ragged_host result (None where the matrix has no Cholesky factor); with
+    the rate fields where _with_rates added the rate covariances"""
     if cov["seq_status"][b] != abi.OK:
         return None
     cu, cp = np.ascontiguousarray(cov["cov_diag"][b]), np.ascontiguousarray(cov["cov_pos"][b])
-    return dict(cov_u=cu, u_std=np.sqrt(np.diagonal(cu, axis1=1, axis2=2)), positions_cov=cp, positions_std=np.sqrt(np.diagonal(cp, axis1=2, axis2=3)),
-                ridge=float(ridge))
+    unc = dict(cov_u=cu, u_std=np.sqrt(np.diagonal(cu, axis1=1, axis2=2)), positions_cov=cp, positions_std=np.sqrt(np.diagonal(cp, axis1=2, axis2=3)),
+               ridge=float(ridge))
+    if "rates" in cov:
+        unc.update(_rate_fields(cov["rates"], b))
+    return unc
 
 
 def _check_uncertainty(est: CheetahEstimator, pri: Optional[abi.Priors], ridge: float) -> None:
@@ -637,14 +691,14 @@ def _kinetic_uncertainty_of(cov: dict, b: int, ridge: float, res: dict) -> Kinet
 
 
 def _kinetic_uncertainty(h, ko: abi.KineticOptions, res: dict, meas: np.ndarray, weight: np.ndarray, stance: np.ndarray, ridge: float,
-                         grf_fixed=None, tau_box=None, grf_box=None) -> KineticUncertainty:
+                         grf_fixed=None, tau_box=None, grf_box=None, rates: bool = False) -> KineticUncertainty:
     """cpe_covariance_kinetic at the solution res["q"] of a converged physics-based solve, with the solve's own stance, options and variant arrays"""
     if res["stats"][0].status != abi.OK:
         return KineticUncertainty()
     one = lambda a: None if a is None else a[None]
     cov = h.covariance_kinetic_host(res["q"], meas[None], weight[None], stance[None], ko, ridge, grf_fixed=one(grf_fixed), tau_box=one(tau_box),
                                     grf_box=one(grf_box))
-    return _kinetic_uncertainty_of(cov, 0, ridge, res)
+    return _kinetic_uncertainty_of(_with_rates(h, cov, res["q"], rates), 0, ridge, res)
 
 
 def _store_kinetic_uncertainty(est: CheetahEstimator, unc: Optional[KineticUncertainty], ok: bool, out_dir: Optional[str],
@@ -663,7 +717,8 @@ def _store_kinetic_uncertainty(est: CheetahEstimator, unc: Optional[KineticUncer
         return
     if unc.fields is not None:
         est.uncertainty = unc.fields
-        np.savez(os.path.join(out_dir, "uncertainty.npz"), **unc.fields)
+        _add_speed_std(est)
+        np.savez(os.path.join(out_dir, "uncertainty.npz"), **est.uncertainty)
 
 
 def _kin_finish(est: CheetahEstimator, h, res: dict, seconds: float, solver_output: bool, monocular_constraints: bool,
@@ -700,6 +755,7 @@ def _kin_finish(est: CheetahEstimator, h, res: dict, seconds: float, solver_outp
                 print(f"uncertainty: none for {est.name}: the Gauss-Newton matrix has no Cholesky factor at ridge {uncertainty[1]:g} "
                       "(the data leave a coordinate undetermined; a positive uncertainty_ridge regularises it)")
             else:
+                _add_speed_std(est)
                 np.savez(os.path.join(out_dir, "uncertainty.npz"), **est.uncertainty)
     elif uncertainty is not None:
         est.uncertainty = None
@@ -711,11 +767,15 @@ def estimate_kinematics(estimator: CheetahEstimator, solver_output: bool = True,
                         pose_model_num_components: int = 5, motion_model_window_size: int = 4,
                         motion_model_sparse_solution: bool = True, out_dir_prefix: Optional[str] = None,
                         q_init: Optional[np.ndarray] = None, options: Optional[abi.Options] = None, uncertainty: bool = False,
-                        uncertainty_ridge: float = 0.0) -> bool:
+                        uncertainty_ridge: float = 0.0, uncertainty_rates: bool = False) -> bool:
     """Same signature as acinoset_opt.estimate_kinematics (acinoset_opt.py:539-547) plus optional
     keyword arguments.  Returns True when the solve converged (IPOPT `ok`+`optimal` in the reference).
     uncertainty=True: after a converged solve the posterior covariance of the estimate (cpe_covariance at the stored q, damping
-    uncertainty_ridge) goes to est.uncertainty and to uncertainty.npz beside fte.pickle; the return value stays that of the solve."""
+    uncertainty_ridge) goes to est.uncertainty and to uncertainty.npz beside fte.pickle; the return value stays that of the solve.
+    uncertainty_rates=True (with uncertainty=True): also how well the rates are determined (cpe_rate_covariance on that covariance): du_std, ddu_std
+    [N, 28], velocities_cov / _std [N, L, 3(, 3)], com_cov / _std [N, 3(, 3)], com_vel_cov / _std [N-1, 3(, 3)] and speed_std [N-1], both aligned
+    with com_vel (RATE_FIELDS; DESIGN.md 2, "What is propagated")."""
+    _check_rates(uncertainty, uncertainty_rates)
     est, params, scene, sk = estimator, estimator.params, estimator.scene, estimator.skeleton
     q_init, opts, pri = _kin_prepare(est, monocular_constraints, disable_pose_prior, disable_motion_prior, pose_model_num_components,
                                      motion_model_window_size, motion_model_sparse_solution, q_init, options)
@@ -735,6 +795,7 @@ def estimate_kinematics(estimator: CheetahEstimator, solver_output: bool = True,
         unc = None
         if uncertainty:
             cov = h.covariance_host(res["q"], est.meas[None], est.weight[None], uncertainty_ridge) if res["stats"][0].status == abi.OK else None
+            cov = None if cov is None else _with_rates(h, cov, res["q"], uncertainty_rates)
             unc = (None if cov is None else _uncertainty_of(cov, 0, uncertainty_ridge), uncertainty_ridge)
         return _kin_finish(est, h, res, dt, solver_output, monocular_constraints, out_dir_prefix, uncertainty=unc)
     finally:
@@ -755,7 +816,7 @@ def ragged_group_key(sk: abi.Skeleton, opts: abi.Options, pri: Optional[abi.Prio
 def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_output: bool = False, monocular_constraints: bool = False,
                               disable_pose_prior: bool = False, disable_motion_prior: bool = False, out_dir_prefix: Optional[str] = None,
                               options: Optional[abi.Options] = None, ragged: bool = False, uncertainty: bool = False,
-                              uncertainty_ridge: float = 0.0) -> List[bool]:
+                              uncertainty_ridge: float = 0.0, uncertainty_rates: bool = False) -> List[bool]:
     """estimate_kinematics for MANY sequences at once: the loop of run_dataset.py:1145-1196 (`for seq in dataset: init_trajectory; estimate_kinematics`)
     as batched launches.  Sequences that share a skeleton, a camera rig, a length and a frame rate go through ONE solver handle and ONE cpe_solve
     call (B = the group's size: the GPU solves thousands of sequences per second batched, one at a time it is latency-bound at 7 - 30 ms each);
@@ -766,7 +827,9 @@ def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_out
     each group is ONE cpe_solve_ragged call over a Handle.multi of its distinct (skeleton, rig, options) models, whatever the lengths.  Every
     sequence's results are bit-equal to those of ragged=False.
     uncertainty=True: as in estimate_kinematics, one cpe_covariance (ragged: cpe_covariance_ragged) call per group on the group's handle; every
-    sequence's est.uncertainty and uncertainty.npz are bit-equal to those of its own estimate_kinematics call."""
+    sequence's est.uncertainty and uncertainty.npz are bit-equal to those of its own estimate_kinematics call.  uncertainty_rates=True: as in
+    estimate_kinematics, one cpe_rate_covariance (ragged: cpe_rate_covariance_ragged) call after each covariance call, with the same bit-equality."""
+    _check_rates(uncertainty, uncertainty_rates)
     ests = list(estimators)
     out: List[Optional[bool]] = [None] * len(ests)
     groups: Dict[tuple, List[int]] = {}
@@ -774,7 +837,7 @@ def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_out
     for i, est in enumerate(ests):
         if est.params.enable_shutter_delay_estimation and est.scene.cam_idx is None:
             out[i] = estimate_kinematics(est, solver_output, monocular_constraints, disable_pose_prior, disable_motion_prior, out_dir_prefix=out_dir_prefix, options=options,
-                                         uncertainty=uncertainty, uncertainty_ridge=uncertainty_ridge)
+                                         uncertainty=uncertainty, uncertainty_ridge=uncertainty_ridge, uncertainty_rates=uncertainty_rates)
             continue
         q_init, opts, pri = _kin_prepare(est, monocular_constraints, disable_pose_prior, disable_motion_prior, 5, 4, True, None,
                                          None if options is None else _copy_options(options))
@@ -790,7 +853,7 @@ def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_out
     if ragged:
         for idx in groups.values():
             _solve_ragged_group(ests, idx, prepared, out, solver_output, monocular_constraints, out_dir_prefix,
-                                uncertainty_ridge if uncertainty else None)
+                                uncertainty_ridge if uncertainty else None, uncertainty_rates)
         return [bool(v) for v in out]
     for idx in groups.values():
         e0 = ests[idx[0]]
@@ -803,6 +866,7 @@ def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_out
             cov = None
             if uncertainty:
                 cov = h.covariance_host(res["q"], np.stack([ests[i].meas for i in idx]), np.stack([ests[i].weight for i in idx]), uncertainty_ridge)
+                cov = _with_rates(h, cov, res["q"], uncertainty_rates)
             for b, i in enumerate(idx):
                 one = {k: (v[b:b + 1] if isinstance(v, np.ndarray) else v) for k, v in res.items() if k not in ("stats", "status")}
                 one["stats"] = [res["stats"][b]]; one["status"] = res["stats"][b].status
@@ -818,7 +882,8 @@ def _model_bytes(est: CheetahEstimator, opts: abi.Options) -> bytes:
     return _struct_bytes(est.skeleton) + b"".join(_struct_bytes(est.cams[c]) for c in range(len(est.cams))) + _struct_bytes(opts)
 
 
-def _solve_ragged_group(ests, idx, prepared, out, solver_output, monocular_constraints, out_dir_prefix, uncertainty_ridge: Optional[float] = None) -> None:
+def _solve_ragged_group(ests, idx, prepared, out, solver_output, monocular_constraints, out_dir_prefix, uncertainty_ridge: Optional[float] = None,
+                        uncertainty_rates: bool = False) -> None:
     """estimate_kinematics_batch(ragged=True) for one group: one model per distinct (skeleton, rig, options), one cpe_solve_ragged call, then every
     sequence's centre of mass, costs and files through _kin_finish with a plain handle of its own model (forward kinematics of that skeleton)"""
     models: Dict[bytes, int] = {}
@@ -840,6 +905,7 @@ def _solve_ragged_group(ests, idx, prepared, out, solver_output, monocular_const
         cov = None
         if uncertainty_ridge is not None:                                            # (uncertainty=True) at the stored q of every sequence, same handle
             cov = h.covariance_ragged_host(res["q"], [ests[i].meas for i in idx], [ests[i].weight for i in idx], of, uncertainty_ridge)
+            cov = _with_rates(h, cov, res["q"], uncertainty_rates, of)
         for b, i in enumerate(idx):
             one = {k: res[k][b][None] for k in ("q", "dq", "ddq", "positions", "meas_err")}
             one["stats"] = [res["stats"][b]]; one["status"] = res["stats"][b].status
@@ -1034,7 +1100,8 @@ def estimate_kinetics(estimator: CheetahEstimator, init_torques: bool = True, au
                       no_slip: bool = True, joint_estimation: bool = False, fix_grf: bool = True, ground_constraint: bool = False,
                       disable_pose_prior: bool = False, disable_motion_prior: bool = False, plot: bool = False, out_fname: str = "fte",
                       out_dir_prefix: Optional[str] = None, options: Optional[abi.Options] = None,
-                      kinetic_options: Optional[abi.KineticOptions] = None, uncertainty: bool = False, uncertainty_ridge: float = 0.0) -> bool:
+                      kinetic_options: Optional[abi.KineticOptions] = None, uncertainty: bool = False, uncertainty_ridge: float = 0.0,
+                      uncertainty_rates: bool = False) -> bool:
     """Same signature and meaning as acinoset_opt.estimate_kinetics (acinoset_opt.py:693-708) for the branch its drivers run for the
     physics-based reconstruction (`joint_estimation=True`, run_dataset.py:1198-1229): torques, joint constraint forces, ground-reaction
     forces and the trajectory are estimated together, warm-started from the kinematic solution on disk, with the contact windows of
@@ -1050,7 +1117,9 @@ def estimate_kinetics(estimator: CheetahEstimator, init_torques: bool = True, au
     uncertainty=True: after a successful solve the posterior covariance of the estimate AND of its node forces (cpe_covariance_kinetic at the stored
     q with the solve's stance, options and force profile, damping uncertainty_ridge) goes to est.uncertainty and to uncertainty.npz beside fte.pickle:
     estimate_kinematics' fields plus tau_std, lambda_std, grf_std, tau_cov (force_uncertainty).  A sequence without a factor raises CpeError after the
-    solve's own files are written.  Not with use_2d_reprojections=False (the covariance of the 3D kinematic cost is not built)."""
+    solve's own files are written.  Not with use_2d_reprojections=False (the covariance of the 3D kinematic cost is not built).
+    uncertainty_rates=True (with uncertainty=True): the rate fields of estimate_kinematics (RATE_FIELDS), from that covariance."""
+    _check_rates(uncertainty, uncertainty_rates)
     if uncertainty and not use_2d_reprojections:
         raise NotImplementedError("uncertainty together with use_2d_reprojections=False: cpe_covariance_kinetic takes the reprojection cost; the covariance "
                                   "of the 3D kinematic cost (cpe_solve_kinetic_tracked) is not built")
@@ -1070,7 +1139,8 @@ def estimate_kinetics(estimator: CheetahEstimator, init_torques: bool = True, au
             res = h.solve_kinetic_host(prep["ko"], prep["q_init"][None], est.meas[None], est.weight[None], prep["stance"][None],
                                        grf_fixed=None if gfx is None else gfx[None], grf_box=None if gbx is None else gbx[None])
         dt = time() - t0
-        unc = _kinetic_uncertainty(h, prep["ko"], res, est.meas, est.weight, prep["stance"], uncertainty_ridge, grf_fixed=gfx, grf_box=gbx) if uncertainty else None
+        unc = _kinetic_uncertainty(h, prep["ko"], res, est.meas, est.weight, prep["stance"], uncertainty_ridge, grf_fixed=gfx, grf_box=gbx,
+                                   rates=uncertainty_rates) if uncertainty else None
         return _kinetic_finish(est, h, res, dt, prep, solver_output, out_fname, out_dir_prefix, uncertainty=unc)
     finally:
         h.close()
@@ -1254,7 +1324,7 @@ def estimate_kinetics_batch(estimators: Sequence[CheetahEstimator], init_torques
                             disable_pose_prior: bool = False, disable_motion_prior: bool = False, plot: bool = False, out_fname: str = "fte",
                             out_dir_prefix: Optional[str] = None, options: Optional[abi.Options] = None,
                             kinetic_options: Optional[abi.KineticOptions] = None, ragged: bool = False, uncertainty: bool = False,
-                            uncertainty_ridge: float = 0.0) -> List[bool]:
+                            uncertainty_ridge: float = 0.0, uncertainty_rates: bool = False) -> List[bool]:
     """estimate_kinetics for MANY sequences at once, with its keyword arguments (applied to every sequence).  Each sequence is prepared as
     estimate_kinetics prepares it (the per-frame force fit of the fix_grf=True, synthesised_grf=False branch included, one sequence at a time),
     then solved in a batch, then gets its centre of mass, costs and files exactly as estimate_kinetics writes them; only processing_time_s (its
@@ -1265,7 +1335,8 @@ def estimate_kinetics_batch(estimators: Sequence[CheetahEstimator], init_torques
     uncertainty=True: as in estimate_kinetics, from ONE covariance call per group on the group's handle over its converged sequences
     (covariance_kinetic_host; ragged: covariance_kinetic_ragged_host); every sequence's est.uncertainty and uncertainty.npz are bit-equal to those of
     its own estimate_kinetics call.  A sequence without a factor does not stop the batch: every sequence is finished and stored first, then ONE
-    CpeError names all of them."""
+    CpeError names all of them.  uncertainty_rates=True: as in estimate_kinetics, one rate call after each covariance call, same bit-equality."""
+    _check_rates(uncertainty, uncertainty_rates)
     if uncertainty and not use_2d_reprojections:
         raise NotImplementedError("uncertainty together with use_2d_reprojections=False: cpe_covariance_kinetic takes the reprojection cost; the covariance "
                                   "of the 3D kinematic cost (cpe_solve_kinetic_tracked) is not built")
@@ -1289,7 +1360,7 @@ def estimate_kinetics_batch(estimators: Sequence[CheetahEstimator], init_torques
     no_factor: List[CheetahEstimator] = []
     for idx in groups.values():
         (_solve_kinetic_ragged_group if ragged else _solve_kinetic_group)(ests, idx, prepared, out, solver_output, out_fname, out_dir_prefix,
-                                                                          uncertainty_ridge if uncertainty else None, no_factor)
+                                                                          uncertainty_ridge if uncertainty else None, no_factor, uncertainty_rates)
     if no_factor:
         raise _lib.CpeError(_no_factor_reason(uncertainty_ridge, [f"{e.name} {e.data_path}" for e in no_factor]))
     return [bool(v) for v in out]
@@ -1310,7 +1381,7 @@ def _batch_kinetic_uncertainty(res: dict, idx, ridge: Optional[float], covarianc
 
 
 def _solve_kinetic_group(ests, idx, prepared, out, solver_output, out_fname, out_dir_prefix, uncertainty_ridge: Optional[float] = None,
-                         no_factor: Optional[list] = None) -> None:
+                         no_factor: Optional[list] = None, uncertainty_rates: bool = False) -> None:
     """estimate_kinetics_batch(ragged=False) for one group: one handle, one solve_kinetic_host call with B = the group's size (and, with
     uncertainty_ridge, one covariance_kinetic_host call)"""
     e0, p0 = ests[idx[0]], prepared[idx[0]]
@@ -1326,9 +1397,9 @@ def _solve_kinetic_group(ests, idx, prepared, out, solver_output, out_fname, out
             res = h.solve_kinetic_host(p0["ko"], stack("q_init"), meas, weight, stack("stance"), grf_fixed=stack("grf_fixed"), grf_box=stack("grf_box"))
         dt = (time() - t0) / len(idx)                                                # processing_time_s of a sequence: its share of the batched solve
         cut = lambda a, conv: None if a is None else a[conv]
-        unc = _batch_kinetic_uncertainty(res, idx, uncertainty_ridge, lambda conv: h.covariance_kinetic_host(
+        unc = _batch_kinetic_uncertainty(res, idx, uncertainty_ridge, lambda conv: _with_rates(h, h.covariance_kinetic_host(
             res["q"][conv], meas[conv], weight[conv], stack("stance")[conv], p0["ko"], uncertainty_ridge, grf_fixed=cut(stack("grf_fixed"), conv),
-            grf_box=cut(stack("grf_box"), conv)))
+            grf_box=cut(stack("grf_box"), conv)), res["q"][conv], uncertainty_rates))
         for b, i in enumerate(idx):
             out[i] = _kinetic_finish(ests[i], h, _kinetic_one(res, b), dt, prepared[i], solver_output, out_fname, out_dir_prefix, unc.get(b), no_factor)
     finally:
@@ -1336,7 +1407,7 @@ def _solve_kinetic_group(ests, idx, prepared, out, solver_output, out_fname, out
 
 
 def _solve_kinetic_ragged_group(ests, idx, prepared, out, solver_output, out_fname, out_dir_prefix, uncertainty_ridge: Optional[float] = None,
-                                no_factor: Optional[list] = None) -> None:
+                                no_factor: Optional[list] = None, uncertainty_rates: bool = False) -> None:
     """estimate_kinetics_batch(ragged=True) for one group: one model per distinct (skeleton, rig, options, kinetic options), one
     cpe_solve_kinetic_ragged call (and, with uncertainty_ridge, one cpe_covariance_kinetic_ragged call on the same handle), then every sequence's
     centre of mass, costs and files through _kinetic_finish with a plain handle of its model"""
@@ -1361,10 +1432,10 @@ def _solve_kinetic_ragged_group(ests, idx, prepared, out, solver_output, out_fna
             res = h.solve_kinetic_ragged_host([prepared[i]["ko"] for i in reps], [prepared[i]["q_init"] for i in idx], [ests[i].meas for i in idx],
                                               [ests[i].weight for i in idx], [prepared[i]["stance"] for i in idx], of, **fkw)
         dt = (time() - t0) / len(idx)                                                # processing_time_s of a sequence: its share of the batched solve
-        unc = _batch_kinetic_uncertainty(res, idx, uncertainty_ridge, lambda conv: h.covariance_kinetic_ragged_host(
+        unc = _batch_kinetic_uncertainty(res, idx, uncertainty_ridge, lambda conv: _with_rates(h, h.covariance_kinetic_ragged_host(
             [res["q"][b] for b in conv], [ests[idx[b]].meas for b in conv], [ests[idx[b]].weight for b in conv],
             [prepared[idx[b]]["stance"] for b in conv], [prepared[i]["ko"] for i in reps], [of[b] for b in conv], uncertainty_ridge,
-            **{k: [v[b] for b in conv] for k, v in fkw.items()}))
+            **{k: [v[b] for b in conv] for k, v in fkw.items()}), [res["q"][b] for b in conv], uncertainty_rates, [of[b] for b in conv]))
         for b, i in enumerate(idx):
             if of[b] not in fk:
                 r = reps[of[b]]
@@ -1388,7 +1459,7 @@ def bound_value(val, slack_percentage: float) -> np.ndarray:
 
 def estimate_grf(estimator: CheetahEstimator, solver_output: bool = True, out_dir_prefix: Optional[str] = None,
                  options: Optional[abi.Options] = None, kinetic_options: Optional[abi.KineticOptions] = None, uncertainty: bool = False,
-                 uncertainty_ridge: float = 0.0) -> bool:
+                 uncertainty_ridge: float = 0.0, uncertainty_rates: bool = False) -> bool:
     """Same signature and meaning as the module-level acinoset_opt.estimate_grf (acinoset_opt.py:966-1048), the last stage of the kinetic-dataset
     pipeline (run_dataset.py:1125-1138): the physics-based model is solved again from the stored `fte_kinetic/fte.pickle` -- trajectory as the
     starting point, every torque within 10 % of its stored value (`Tc.bounds = bound_value(init_tau, 0.1)`, :995-1003) -- with the ground-reaction
@@ -1399,7 +1470,9 @@ def estimate_grf(estimator: CheetahEstimator, solver_output: bool = True, out_di
     window in `metadata.json` (frames 0 .. N-2) at which the resampled plate signal is non-zero; with a per-frame CSV twin `grf/data.csv` of that
     table (the reference ships `grf/data.h5` at 3.5 kHz, which needs PyTables and a resampling step that are not reproduced here) the same rule is
     applied to it, otherwise the window alone decides (a loaded plate never reads exactly zero).
-    uncertainty=True: as in estimate_kinetics, with the torque boxes of this solve; uncertainty.npz goes beside fte_grf/fte.pickle."""
+    uncertainty=True: as in estimate_kinetics, with the torque boxes of this solve; uncertainty.npz goes beside fte_grf/fte.pickle.
+    uncertainty_rates=True (with uncertainty=True): the rate fields of estimate_kinematics (RATE_FIELDS), from that covariance."""
+    _check_rates(uncertainty, uncertainty_rates)
     est, params, scene, sk = estimator, estimator.params, estimator.scene, estimator.skeleton
     assert params.kinetic_dataset, "Cannot determine GRF on a dataset other than the kinetic dataset from Penny Hudson and Co."
     if est.kinematic_model:
@@ -1451,7 +1524,7 @@ def estimate_grf(estimator: CheetahEstimator, solver_output: bool = True, out_di
         res = h.solve_kinetic_host(ko, q_init[None], est.meas[None], est.weight[None], stance[None], tau_box=tau_box[None])
         est.opt_time_s = time() - t0
         if uncertainty:
-            unc = _kinetic_uncertainty(h, ko, res, est.meas, est.weight, stance, uncertainty_ridge, tau_box=tau_box)
+            unc = _kinetic_uncertainty(h, ko, res, est.meas, est.weight, stance, uncertainty_ridge, tau_box=tau_box, rates=uncertainty_rates)
         import torch
         dev = torch.device("cuda", est.device)
         qd = torch.tensor(res["q"], device=dev)

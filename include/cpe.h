@@ -616,6 +616,45 @@ cpe_status cpe_covariance_ragged_host(cpe_handle* h, int32_t B, int32_t N_max, c
                                       const double* meas, const double* weight, double ridge, double* cov_diag, double* cov_off, double* cov_pos,
                                       double* L, cpe_status* status);
 
+/* ---- posterior covariance of the rates ("What is propagated"): how well the data determine velocities, accelerations and the
+ * centre of mass, from a covariance band the entries above return.  A rate is a fixed linear stencil over at most three consecutive frames, so its
+ * covariance needs Sigma(n,n), Sigma(n+1,n), Sigma(n+2,n) only -- all inside the band.  The entry does not care where Sigma came from
+ * (cpe_covariance*, cpe_covariance_kinetic*, cpe_band_inverse, or a band of the caller's); values are not validated.
+ * Device pointers.  q [B][N][nq]: Euler angles as cpe_covariance takes them (cold start of the state); cov_diag [B][N][28][28] and cov_off
+ * [B][N][pb][28][28] (block [n][i-1] = Sigma(n+i, n), pb = the handle's half-bandwidth): cpe_band_inverse's layout.
+ * With NL the sequence's length, h its model's time step and u_n the 28 reduced coordinates (the gauge of the solve's dq / ddq at the first frames):
+ *   cov_du      [B][N][28][28]   covariance of the reduced velocity: row n >= 1 (u_n - u_{n-1}) / h; row 0 (-2 u_0 + 3 u_1 - u_2) / h if NL >= 3,
+ *                                (u_1 - u_0) / h if NL == 2, zero if NL == 1
+ *   cov_ddu     [B][N][28][28]   covariance of (u_m - 2 u_{m-1} + u_{m-2}) / h^2, m = max(n, 2); zero if NL < 3 (rows 0, 1, 2 are bit-equal)
+ *   cov_vel     [B][N][L][3][3]  first-order covariance of the marker velocity (p_l(u_n) - p_l(u_{n-1})) / h:
+ *                                (P_n S_nn P_n^T + P_{n-1} S_{n-1,n-1} P_{n-1}^T - P_n S_{n,n-1} P_{n-1}^T - (that)^T) / h^2; row 0 is zero
+ *   cov_com     [B][N][3][3]     Pc_n S_nn Pc_n^T, the covariance of the centre of mass in metres^2
+ *   cov_com_vel [B][N][3][3]     the velocity formula with Pc; row 0 is zero, row k + 1 belongs to the velocity between the frames k and k + 1
+ *   jac_pos     [B][N][L][3][28] P_l = d p_l / d u, dense (exactly 0.0 in the columns a marker does not depend on): cpe_covariance's cov_pos is
+ *                                P_l Sigma(n,n) P_l^T of these numbers
+ *   jac_com     [B][N][3][28]    Pc = d com / d u, com as cpe_forward_kinematics returns it: the mass-weighted mean of the link centres' columns
+ * Every output may be NULL, but not all of them.  Every block is symmetric bit for bit; every sum has a fixed order (no atomics): results are
+ * reproducible bit for bit and a sequence's outputs do not depend on its batch.  All outputs are linear in Sigma: a sequence whose band is zero
+ * (cpe_covariance found no factor) gets zero covariances.  du of a trunk coordinate is the rate of the Euler angle cpe_independent_dofs names, du of
+ * a leg coordinate the rate of its rotation about the body's y axis.
+ * Refused with CPE_BAD_ARG before the device is touched, the reason in cpe_last_error(): negative sizes; NULL h, q, cov_diag or cov_off; all
+ * outputs NULL; a centre-of-mass output for a skeleton whose link centres do not fit the marker tables. */
+cpe_status cpe_rate_covariance(cpe_handle* h, int32_t B, int32_t N, const double* q, const double* cov_diag, const double* cov_off, double* cov_du,
+                               double* cov_ddu, double* cov_vel, double* cov_com, double* cov_com_vel, double* jac_pos, double* jac_com);
+/* the same for sequences of their own length and model, in cpe_covariance_ragged's layout (N_max frames; model, n_frames HOST): NL = n_frames[b], h
+ * and the Jacobians those of model[b]; everything past a sequence's frames reads 0.0.  Also refused: NULL model or n_frames, a model index or frame
+ * count out of range, a plain handle (cpe_create). */
+cpe_status cpe_rate_covariance_ragged(cpe_handle* h, int32_t B, int32_t N_max, const int32_t* model /*[B] host*/, const int32_t* n_frames /*[B] host*/,
+                                      const double* q, const double* cov_diag, const double* cov_off, double* cov_du, double* cov_ddu, double* cov_vel,
+                                      double* cov_com, double* cov_com_vel, double* jac_pos, double* jac_com);
+/* host-pointer twins (stage through HBM) */
+cpe_status cpe_rate_covariance_host(cpe_handle* h, int32_t B, int32_t N, const double* q, const double* cov_diag, const double* cov_off,
+                                    double* cov_du, double* cov_ddu, double* cov_vel, double* cov_com, double* cov_com_vel, double* jac_pos,
+                                    double* jac_com);
+cpe_status cpe_rate_covariance_ragged_host(cpe_handle* h, int32_t B, int32_t N_max, const int32_t* model, const int32_t* n_frames, const double* q,
+                                           const double* cov_diag, const double* cov_off, double* cov_du, double* cov_ddu, double* cov_vel,
+                                           double* cov_com, double* cov_com_vel, double* jac_pos, double* jac_com);
+
 /* ---- posterior covariance of the physics-based estimate: coordinates, and the node forces (torques, joint constraint forces, net foot forces)
  * the solve infers ("What is inverted").  Runs the launches of the first pass of cpe_solve_kinetic at Euler q -- cold start, multipliers
  * zero, node forces minimised from a cold start, as cpe_eval_kinetic_system / cpe_eval_lm_step -- at damping `ridge` in place of opts.lambda0, up to
