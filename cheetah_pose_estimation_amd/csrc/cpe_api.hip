@@ -480,8 +480,8 @@ static void build_com_model(const cpe_skeleton* s, const cpe_camera* cams, int C
 }
 
 // the plain variant of k_frame_normal (no Gaussian-mixture prior, no shutter delay) writes H straight to HBM and needs 6 KB less LDS per wave
-#define FRAME_NORMAL(plain) ((plain) ? k_frame_normal<true> : k_frame_normal<false>)
-#define FRAME_NORMAL_RAGGED(plain) ((plain) ? k_frame_normal<true, true> : k_frame_normal<false, true>)
+template <bool RAGGED = false>
+static auto frame_normal(bool plain) { return plain ? k_frame_normal<true, RAGGED> : k_frame_normal<false, RAGGED>; }
 static size_t lds_fk(const DevModel& m) { return sizeof(double) * (m.nq + 6 * m.nl + 36 * m.nl + 3 * m.L + 23 * m.C); }
 static size_t lds_normal(const DevModel& m, int gmm_k = 0, int gmm_dim = 0, bool shutter = false) {
     // g (and, unless the plain variant writes H straight to HBM, H | g) overlay the S rows, which are dead once Dp is built
@@ -495,29 +495,30 @@ static size_t lds_normal(const DevModel& m, int gmm_k = 0, int gmm_dim = 0, bool
     if (shutter) n += 15 * m.C + 6 * m.L + 6;          // shift | coefficients | rc | Mc per camera, M1 per marker, M2
     return sizeof(double) * n;
 }
-// the dynamic LDS a ragged launch needs: the most any of the handle's models needs
-static size_t lds_fk_all(const cpe_handle* h) {
-    size_t n = lds_fk(h->hm);
-    for (const DevModel& m : h->models) n = std::max(n, lds_fk(m));
-    return n;
-}
-static size_t lds_normal_all(const cpe_handle* h) {
-    size_t n = lds_normal(h->hm, h->gmm_k, h->gmm_dim);
-    for (const DevModel& m : h->models) n = std::max(n, lds_normal(m, h->gmm_k, h->gmm_dim));
-    return n;
-}
 // k_frame_tracked (cpe_tracked.hip.inc): state | sin / cos | trunk rotations | Gamma | weighted residual | H | g, then the pose prior's scratch
-#define FRAME_TRACKED(gmm) ((gmm) ? k_frame_tracked<true> : k_frame_tracked<false>)
-#define FRAME_TRACKED_RAGGED(gmm) ((gmm) ? k_frame_tracked<true, true> : k_frame_tracked<false, true>)
+template <bool RAGGED = false>
+static auto frame_tracked(bool gmm) { return gmm ? k_frame_tracked<true, RAGGED> : k_frame_tracked<false, RAGGED>; }
 static size_t lds_tracked(const DevModel& m, int gmm_k, int gmm_dim) {
     size_t n = m.ns + 6 * m.nl + 2 * m.nrev + 36 * m.n_trunk + GAM_STRIDE * m.nrev + m.nu + m.nu * m.nu + m.nu;
     if (gmm_k > 0) n += CPE_NX + gmm_k * gmm_dim + CPE_MAX_GMM + CPE_NX;          // x | P_k (x - mu_k) | log p_k | gradient in x
     return sizeof(double) * n;
 }
-static size_t lds_tracked_all(const cpe_handle* h) {
-    size_t n = lds_tracked(h->hm, h->gmm_k, h->gmm_dim);
-    for (const DevModel& m : h->models) n = std::max(n, lds_tracked(m, h->gmm_k, h->gmm_dim));
+// the dynamic LDS a ragged launch needs: the most any of the handle's models needs
+template <class Fn>
+static size_t lds_all(const cpe_handle* h, Fn&& lds) {
+    size_t n = lds(h->hm);
+    for (const DevModel& m : h->models) n = std::max(n, lds(m));
     return n;
+}
+static size_t lds_normal_all(const cpe_handle* h) { return lds_all(h, [h](const DevModel& m) { return lds_normal(m, h->gmm_k, h->gmm_dim); }); }
+// The dynamic LDS of a launch: with the ragged table rg what every model of the handle fits in (no shutter delay there), without it what the
+// handle's first model needs
+static size_t lds_fk(const cpe_handle* h, const RaggedArgs* rg) { return rg ? lds_all(h, [](const DevModel& m) { return lds_fk(m); }) : lds_fk(h->hm); }
+static size_t lds_normal(const cpe_handle* h, const RaggedArgs* rg, bool shutter = false) {
+    return rg ? lds_normal_all(h) : lds_normal(h->hm, h->gmm_k, h->gmm_dim, shutter);
+}
+static size_t lds_tracked(const cpe_handle* h, const RaggedArgs* rg) {
+    return rg ? lds_all(h, [h](const DevModel& m) { return lds_tracked(m, h->gmm_k, h->gmm_dim); }) : lds_tracked(h->hm, h->gmm_k, h->gmm_dim);
 }
 static int n_models(const cpe_handle* h) { return h->models.empty() ? 1 : (int)h->models.size(); }
 static int cams_max(const cpe_handle* h) {
@@ -1034,12 +1035,31 @@ static cpe_status ensure_ws(cpe_handle* h, int B, int N) {
     return CPE_OK;
 }
 
+// f(std::integral_constant<int, PB>{}) for the handle's half-bandwidth PB = 3..6: k_lm_step and k_lm_back are instantiated per PB
+extern "C++" template <class Fn>
+static void with_pb(int pb, Fn&& f) {
+    switch (pb) {
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    default: f(std::integral_constant<int, 6>{}); break;
+    }
+}
+
+// f(std::true_type{}, *rg) with the ragged table of a call, f(std::false_type{}, RaggedArgs{}) without one (rg null): every kernel that has a
+// ragged form takes the flag as its RAGGED template argument and the table as its last argument, and is launched from inside such an f
+extern "C++" template <class Fn>
+static void with_ragged(const RaggedArgs* rg, Fn&& f) {
+    if (rg) f(std::true_type{}, *rg);
+    else f(std::false_type{}, RaggedArgs{});
+}
+
 // Cold start of every sequence from Euler q (device pointer): state buffer 0 = (q, alpha), sequence states and bound multipliers zero.
 // rg: the ragged table of cpe_solve_ragged (N = nmax), or null
 static cpe_status state_reset(cpe_handle* h, int B, int N, const double* q, const RaggedArgs* rg = nullptr) {
     const size_t F = (size_t)B * N;
-    if (rg) hipLaunchKernelGGL(k_state_init<true>, dim3((unsigned)F), dim3(WAVE), 0, h->stream, h->dm, q, h->qbuf, *rg);
-    else hipLaunchKernelGGL(k_state_init<>, dim3((unsigned)F), dim3(WAVE), 0, h->stream, h->dm, q, h->qbuf);   // Euler q -> (q, alpha)
+    // Euler q -> (q, alpha)
+    with_ragged(rg, [&](auto r, RaggedArgs a) { hipLaunchKernelGGL(k_state_init<decltype(r)::value>, dim3((unsigned)F), dim3(WAVE), 0, h->stream, h->dm, q, h->qbuf, a); });
     HIPCHK(hipMemsetAsync(h->st, 0, sizeof(SeqState) * B, h->stream));
     HIPCHK(hipMemsetAsync(h->mu, 0, sizeof(double) * n_mu(h->hm, F), h->stream));
     return CPE_OK;
@@ -1056,7 +1076,7 @@ cpe_status cpe_eval_normal(cpe_handle* h, int32_t B, int32_t N, const double* q,
     if (s != CPE_OK) return s;
     if ((s = state_reset(h, B, N, q)) != CPE_OK) return s;
     const DevModel& m = h->hm;
-    hipLaunchKernelGGL(FRAME_NORMAL(h->gmm_k == 0), dim3((unsigned)F), dim3(WAVE), lds_normal(m, h->gmm_k, h->gmm_dim), h->stream, h->dm, h->st, N, 1, F, h->qbuf, meas, weight,
+    hipLaunchKernelGGL(frame_normal<>(h->gmm_k == 0), dim3((unsigned)F), dim3(WAVE), lds_normal(h, nullptr), h->stream, h->dm, h->st, N, 1, F, h->qbuf, meas, weight,
                        h->gbuf, h->Bbuf, h->costbuf, h->mu, h->gambuf, h->pri, nullptr, nullptr, ShutterArgs{nullptr, nullptr, nullptr}, RaggedArgs{});
     HIPCHK(hipMemcpyAsync(g, h->gbuf, sizeof(double) * F * m.nu, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(Bm, h->Bbuf, sizeof(double) * F * m.nu * m.nu, hipMemcpyDeviceToDevice, h->stream));
@@ -1120,74 +1140,41 @@ __global__ void k_reset_status(SeqState* __restrict__ st, int B) {
     if (b < B) { st[b].status = 0; st[b].al_pending = 0; }
 }
 
-// f(std::integral_constant<int, PB>{}) for the handle's half-bandwidth PB = 3..6: k_lm_step and k_lm_back are instantiated per PB
-extern "C++" template <class Fn>
-static void with_pb(int pb, Fn&& f) {
-    switch (pb) {
-    case 3: f(std::integral_constant<int, 3>{}); break;
-    case 4: f(std::integral_constant<int, 4>{}); break;
-    case 5: f(std::integral_constant<int, 5>{}); break;
-    default: f(std::integral_constant<int, 6>{}); break;
-    }
-}
-
 // One iteration of the kinematic solve (the LmIterate of lm_run): k_frame_normal (+ k_lr_band) on the evaluated buffer, then k_lm_step and
-// k_lm_back.  sh: shutter-delay buffers (all null = off); rg: the ragged table (N = nmax), or null.  back = false (cpe_covariance): stop after
-// k_lm_step -- the factor is in Lbuf and every factored sequence has back_pending = 1.
+// k_lm_back.  sh: shutter-delay buffers (all null = off); rg: the ragged table (N = nmax), or null.  Precondition: sh is all null whenever rg
+// is given -- the ragged forms have no shutter delay (lm_run refuses the pair; the other callers pass one of the two as null).
+// back = false (cpe_covariance): stop after k_lm_step -- the factor is in Lbuf and every factored sequence has back_pending = 1.
 static void lm_iterate(cpe_handle* h, const LmParams& prm, int N, size_t Fw, size_t ldsn, const double* meas, const double* weight, ShutterArgs sh,
                        const RaggedArgs* rg, int first, const int* act, const int* n_act, int slots, bool back = true) {
     const bool lr = h->lr_window > 0;
     const unsigned gf = (unsigned)((size_t)slots * N);
     const double* hiu = lr ? reinterpret_cast<const double*>(reinterpret_cast<const char*>(h->pri) + offsetof(DevPriors, lr_HIu)) + CPE_NX * CPE_NX : nullptr;
-    if (rg) {      // the same launches in their ragged forms
+    with_ragged(rg, [&](auto r, RaggedArgs a) {
+        constexpr bool R = decltype(r)::value;
         prof_begin(h, 0);
-        hipLaunchKernelGGL(FRAME_NORMAL_RAGGED(h->gmm_k == 0), dim3(gf), dim3(WAVE), ldsn, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, meas, weight,
-                           h->gbuf, h->Bbuf, h->costbuf, h->mu, h->gambuf, h->pri, act, n_act, ShutterArgs{nullptr, nullptr, nullptr}, *rg);
+        hipLaunchKernelGGL(frame_normal<R>(h->gmm_k == 0 && sh.tau == nullptr), dim3(gf), dim3(WAVE), ldsn, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, meas, weight,
+                           h->gbuf, h->Bbuf, h->costbuf, h->mu, h->gambuf, h->pri, act, n_act, sh, a);
         prof_end(h);
         if (lr) {
             prof_begin(h, 1);
-            hipLaunchKernelGGL(k_lr_band<true>, dim3(gf), dim3(WAVE), 0, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, h->gambuf, h->pri, h->pb, h->gbuf,
-                               h->Bbuf, h->Hlr, h->costbuf, act, n_act, *rg);
+            hipLaunchKernelGGL(k_lr_band<R>, dim3(gf), dim3(WAVE), 0, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, h->gambuf, h->pri, h->pb, h->gbuf, h->Bbuf,
+                               h->Hlr, h->costbuf, act, n_act, a);
             prof_end(h);
         }
         prof_begin(h, 2);
         with_pb(h->pb, [&](auto pbc) {
-            hipLaunchKernelGGL((k_lm_step<decltype(pbc)::value, 0, true>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf,
-                               h->gbuf, h->Bbuf, h->costbuf, h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hlr, act, n_act, 2, nullptr, h->dgbuf, hiu, h->lr_window, *rg);
+            hipLaunchKernelGGL((k_lm_step<decltype(pbc)::value, 0, R>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gbuf,
+                               h->Bbuf, h->costbuf, h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hlr, act, n_act, 2, sh.gx, h->dgbuf, hiu, h->lr_window, a);
         });
         prof_end(h);
         if (!back) return;
         prof_begin(h, 7);
         with_pb(h->pb, [&](auto pbc) {
-            hipLaunchKernelGGL((k_lm_back<decltype(pbc)::value, true>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf,
-                               h->zbuf, h->gtbuf, h->dgbuf, act, n_act, *rg);
+            hipLaunchKernelGGL((k_lm_back<decltype(pbc)::value, R>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf,
+                               h->gtbuf, h->dgbuf, act, n_act, a);
         });
         prof_end(h);
-        return;
-    }
-    prof_begin(h, 0);
-    hipLaunchKernelGGL(FRAME_NORMAL(h->gmm_k == 0 && sh.tau == nullptr), dim3(gf), dim3(WAVE), ldsn, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, meas, weight, h->gbuf, h->Bbuf,
-                       h->costbuf, h->mu, h->gambuf, h->pri, act, n_act, sh, RaggedArgs{});
-    prof_end(h);
-    if (lr) {
-        prof_begin(h, 1);
-        hipLaunchKernelGGL(k_lr_band<>, dim3(gf), dim3(WAVE), 0, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, h->gambuf, h->pri, h->pb, h->gbuf, h->Bbuf,
-                           h->Hlr, h->costbuf, act, n_act);
-        prof_end(h);
-    }
-    prof_begin(h, 2);
-    with_pb(h->pb, [&](auto pbc) {
-        hipLaunchKernelGGL((k_lm_step<decltype(pbc)::value, 0>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gbuf,
-                           h->Bbuf, h->costbuf, h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hlr, act, n_act, 2, sh.gx, h->dgbuf, hiu, h->lr_window);
     });
-    prof_end(h);
-    if (!back) return;
-    prof_begin(h, 7);
-    with_pb(h->pb, [&](auto pbc) {
-        hipLaunchKernelGGL((k_lm_back<decltype(pbc)::value>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf,
-                           h->gtbuf, h->dgbuf, act, n_act);
-    });
-    prof_end(h);
 }
 
 // The LM run of cpe_solve on the handle's workspace: cold start from q_init (device pointer) or, with q_init == nullptr, a restart from
@@ -1195,14 +1182,14 @@ static void lm_iterate(cpe_handle* h, const LmParams& prm, int N, size_t Fw, siz
 // rg: the ragged table of cpe_solve_ragged (N = nmax; no shutter delay), or null.
 static cpe_status lm_run(cpe_handle* h, int B, int N, const double* q_init, const double* meas, const double* weight, ShutterArgs sh,
                          const RaggedArgs* rg = nullptr) {
-    const DevModel& m = h->hm;
+    if (rg && (sh.tau || sh.gx || sh.rcb)) return fail(CPE_BAD_ARG, "the ragged solve has no shutter delay");
     const size_t Fw = (size_t)B * N;   // buffers are laid out for exactly this call's F (strides use F)
     if (q_init) {
         const cpe_status s = state_reset(h, B, N, q_init, rg);
         if (s != CPE_OK) return s;
     } else hipLaunchKernelGGL(k_reset_status, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->st, B);
     const LmParams prm = lm_params(h, B, N);
-    const size_t ldsn = rg ? lds_normal_all(h) : lds_normal(m, h->gmm_k, h->gmm_dim, sh.tau != nullptr);
+    const size_t ldsn = lds_normal(h, rg, sh.tau != nullptr);
     return lm_drive(h, B, [&](int first, const int* act, const int* n_act, int slots) {
         lm_iterate(h, prm, N, Fw, ldsn, meas, weight, sh, rg, first, act, n_act, slots);
     });
@@ -1216,10 +1203,10 @@ static cpe_status lm_readback(cpe_handle* h, int B, int N, const double* meas, d
                               const RaggedArgs* rg = nullptr) {
     const size_t F = (size_t)B * N;
     HIPCHK(hipMemsetAsync(h->cmax, 0, sizeof(double) * B, h->stream));
-    if (rg) hipLaunchKernelGGL(k_finalize<true>, dim3((unsigned)F), dim3(WAVE), lds_fk_all(h), h->stream, h->dm, h->st, N, F, h->qbuf, meas, q, dq, ddq,
-                               positions, meas_err, reinterpret_cast<unsigned long long*>(h->cmax), nullptr, *rg);
-    else hipLaunchKernelGGL(k_finalize<>, dim3((unsigned)F), dim3(WAVE), lds_fk(h->hm), h->stream, h->dm, h->st, N, F, h->qbuf, meas, q, dq, ddq, positions, meas_err,
-                            reinterpret_cast<unsigned long long*>(h->cmax), tau);
+    with_ragged(rg, [&](auto r, RaggedArgs a) {
+        hipLaunchKernelGGL(k_finalize<decltype(r)::value>, dim3((unsigned)F), dim3(WAVE), lds_fk(h, rg), h->stream, h->dm, h->st, N, F, h->qbuf, meas, q, dq, ddq,
+                           positions, meas_err, reinterpret_cast<unsigned long long*>(h->cmax), tau, a);
+    });
     if (more) more();
     HIPCHK(hipGetLastError());
     hs.resize(B);
@@ -1270,21 +1257,6 @@ static cpe_status lm_finish(cpe_handle* h, int B, int N, const double* meas, dou
     return seq_stats(h, B, hs, hc, iters_extra, kinematic_costs, stats);
 }
 
-cpe_status cpe_solve(cpe_handle* h, int32_t B, int32_t N, const double* q_init, const double* meas, const double* weight,
-                     double* q, double* dq, double* ddq, double* positions, double* meas_err, cpe_stats* stats) {
-    if (!h || !q_init || !meas || !weight || !q) return fail(CPE_BAD_ARG, "null argument");
-    if ((dq == nullptr) != (ddq == nullptr)) return fail(CPE_BAD_ARG, "dq and ddq must be given together");
-    size_t F;
-    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
-    if (F == 0) return CPE_OK;
-    HIPCHK(hipSetDevice(h->device));
-    cpe_status s = ensure_ws(h, B, N);
-    if (s != CPE_OK) return s;
-    s = lm_run(h, B, N, q_init, meas, weight, ShutterArgs{nullptr, nullptr, nullptr});
-    if (s != CPE_OK) return s;
-    return lm_finish(h, B, N, meas, q, dq, ddq, positions, meas_err, nullptr, stats, nullptr);
-}
-
 // The arguments of cpe_solve_ragged, checked before anything is launched: the (model, frames) table of the batch.
 static cpe_status ragged_table(const cpe_handle* h, int B, int N_max, const int32_t* model, const int32_t* n_frames, std::vector<int2>& seq) {
     seq.resize((size_t)B);
@@ -1298,24 +1270,44 @@ static cpe_status ragged_table(const cpe_handle* h, int B, int N_max, const int3
     return CPE_OK;
 }
 
+// The checked table on the device (h->rseq) and the kernels' view of it.  seq is pageable: the caller drains the stream before seq goes.
+static cpe_status ragged_upload(cpe_handle* h, const std::vector<int2>& seq, int N_max, RaggedArgs& rg) {
+    HIPCHK(hipMemcpyAsync(h->rseq, seq.data(), sizeof(int2) * seq.size(), hipMemcpyHostToDevice, h->stream));
+    rg = RaggedArgs{h->rseq, N_max, cams_max(h)};
+    return CPE_OK;
+}
+
+// cpe_solve (model == nullptr) and cpe_solve_ragged
+static cpe_status solve_impl(cpe_handle* h, int32_t B, int32_t N, const int32_t* model, const int32_t* n_frames, const double* q_init, const double* meas,
+                             const double* weight, double* q, double* dq, double* ddq, double* positions, double* meas_err, cpe_stats* stats) {
+    if (!h || !q_init || !meas || !weight || !q) return fail(CPE_BAD_ARG, "null argument");
+    if ((dq == nullptr) != (ddq == nullptr)) return fail(CPE_BAD_ARG, "dq and ddq must be given together");
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    std::vector<int2> seq;
+    if (model) { if (cpe_status s = ragged_table(h, B, N, model, n_frames, seq); s != CPE_OK) return s; }
+    HIPCHK(hipSetDevice(h->device));
+    cpe_status s = ensure_ws(h, B, N);
+    if (s != CPE_OK) return s;
+    RaggedArgs rgv;
+    if (model && (s = ragged_upload(h, seq, N, rgv)) != CPE_OK) return s;     // (seq outlives the stream: lm_finish drains it)
+    const RaggedArgs* rg = model ? &rgv : nullptr;
+    s = lm_run(h, B, N, q_init, meas, weight, ShutterArgs{nullptr, nullptr, nullptr}, rg);
+    if (s != CPE_OK) return s;
+    return lm_finish(h, B, N, meas, q, dq, ddq, positions, meas_err, nullptr, stats, nullptr, rg);
+}
+
+cpe_status cpe_solve(cpe_handle* h, int32_t B, int32_t N, const double* q_init, const double* meas, const double* weight,
+                     double* q, double* dq, double* ddq, double* positions, double* meas_err, cpe_stats* stats) {
+    return solve_impl(h, B, N, nullptr, nullptr, q_init, meas, weight, q, dq, ddq, positions, meas_err, stats);
+}
+
 cpe_status cpe_solve_ragged(cpe_handle* h, int32_t B, int32_t N_max, const int32_t* model, const int32_t* n_frames, const double* q_init,
                             const double* meas, const double* weight, double* q, double* dq, double* ddq, double* positions, double* meas_err,
                             cpe_stats* stats) {
-    if (!h || !model || !n_frames || !q_init || !meas || !weight || !q) return fail(CPE_BAD_ARG, "null argument");
-    if ((dq == nullptr) != (ddq == nullptr)) return fail(CPE_BAD_ARG, "dq and ddq must be given together");
-    size_t F;
-    if (cpe_status s = frames(B, N_max, &F); s != CPE_OK) return s;
-    if (F == 0) return CPE_OK;
-    std::vector<int2> seq;
-    if (cpe_status s = ragged_table(h, B, N_max, model, n_frames, seq); s != CPE_OK) return s;
-    HIPCHK(hipSetDevice(h->device));
-    cpe_status s = ensure_ws(h, B, N_max);
-    if (s != CPE_OK) return s;
-    HIPCHK(hipMemcpyAsync(h->rseq, seq.data(), sizeof(int2) * B, hipMemcpyHostToDevice, h->stream));     // (seq outlives the stream: lm_finish drains it)
-    const RaggedArgs rg{h->rseq, N_max, cams_max(h)};
-    s = lm_run(h, B, N_max, q_init, meas, weight, ShutterArgs{nullptr, nullptr, nullptr}, &rg);
-    if (s != CPE_OK) return s;
-    return lm_finish(h, B, N_max, meas, q, dq, ddq, positions, meas_err, nullptr, stats, nullptr, &rg);
+    if (!model || !n_frames) return fail(CPE_BAD_ARG, "null argument");
+    return solve_impl(h, B, N_max, model, n_frames, q_init, meas, weight, q, dq, ddq, positions, meas_err, stats);
 }
 
 // ---- shutter-delay estimation (include/cpe.h, cpe_solve_shutter) ------------------------------------------------------------------
@@ -1608,73 +1600,74 @@ static cpe_status kin_state_reset(cpe_handle* h, size_t F, bool torque_box) {
     return CPE_OK;
 }
 
-extern "C++" {     // (the launch templates below; the file's own functions are extern "C")
-
 // one evaluation pass of the physics terms on the evaluated buffer (after k_frame_normal): rows, node forces, cost.
-// RAGGED: the forms of cpe_solve_kinetic_ragged, launched with its table rg (N = nmax)
-template <bool RAGGED = false>
-static void launch_dyn_eval(cpe_handle* h, int N, int first, size_t Fw, const int32_t* stance, const int* act, const int* n_act, int slots, RaggedArgs rg = RaggedArgs{}) {
+// rg: the ragged table (N = nmax), or null -- here and in the two functions below
+static void launch_dyn_eval(cpe_handle* h, int N, int first, size_t Fw, const int32_t* stance, const int* act, const int* n_act, int slots, const RaggedArgs* rg) {
     const unsigned gf = (unsigned)((size_t)slots * N);
     prof_begin(h, 5);
-    hipLaunchKernelGGL(k_dyn_eval<RAGGED>, dim3(gf), dim3(KIN_THREADS), lds_kin_eval(), h->stream, h->dm, h->dk, h->st, N, first, Fw, h->qbuf, stance, h->fbuf, h->kmu,
-                       h->costbuf, h->Jbuf, h->Abuf, h->pieces, h->pmeta, h->dstat, h->slackb, act, n_act, rg);
+    with_ragged(rg, [&](auto r, RaggedArgs a) {
+        hipLaunchKernelGGL(k_dyn_eval<decltype(r)::value>, dim3(gf), dim3(KIN_THREADS), lds_kin_eval(), h->stream, h->dm, h->dk, h->st, N, first, Fw, h->qbuf, stance,
+                           h->fbuf, h->kmu, h->costbuf, h->Jbuf, h->Abuf, h->pieces, h->pmeta, h->dstat, h->slackb, act, n_act, a);
+    });
     prof_end(h);
 }
 // Jacobian and second-order pieces of the CURRENT iterate -- after the accept step, and only for sequences whose iterate is new: a rejected trial
 // costs its evaluation only (a quarter to a third of the iterations of a physics-based solve are rejections)
-template <bool RAGGED = false>
-static void launch_dyn_pieces(cpe_handle* h, int N, int first, size_t Fw, const int* act, const int* n_act, int slots, RaggedArgs rg = RaggedArgs{}) {
+static void launch_dyn_pieces(cpe_handle* h, int N, int first, size_t Fw, const int* act, const int* n_act, int slots, const RaggedArgs* rg) {
     const unsigned gf = (unsigned)((size_t)slots * N);
-    prof_begin(h, 10);
-    hipLaunchKernelGGL(k_dyn_jac<RAGGED>, dim3(gf), dim3(KJ_THREADS), sizeof(double) * KJ_DOUBLES, h->stream, h->dm, h->dk, h->st, N, first, Fw, h->qbuf, h->fbuf, h->Jbuf,
-                       act, n_act, rg);
-    prof_end(h);
-    prof_begin(h, 8);
-    hipLaunchKernelGGL(k_dyn_assemble<RAGGED>, dim3(gf), dim3(KIN_THREADS), lds_kin_assemble(), h->stream, h->dm, h->dk, h->st, N, first, Fw, h->Jbuf, h->Abuf, h->pieces,
-                       h->pmeta, h->gTb, act, n_act, rg);
-    prof_end(h);
+    with_ragged(rg, [&](auto r, RaggedArgs a) {
+        constexpr bool R = decltype(r)::value;
+        prof_begin(h, 10);
+        hipLaunchKernelGGL(k_dyn_jac<R>, dim3(gf), dim3(KJ_THREADS), sizeof(double) * KJ_DOUBLES, h->stream, h->dm, h->dk, h->st, N, first, Fw, h->qbuf, h->fbuf, h->Jbuf,
+                           act, n_act, a);
+        prof_end(h);
+        prof_begin(h, 8);
+        hipLaunchKernelGGL(k_dyn_assemble<R>, dim3(gf), dim3(KIN_THREADS), lds_kin_assemble(), h->stream, h->dm, h->dk, h->st, N, first, Fw, h->Jbuf, h->Abuf, h->pieces,
+                           h->pmeta, h->gTb, act, n_act, a);
+        prof_end(h);
+    });
 }
 
 // One iteration of the physics-based solve: per-frame terms and physics terms of the evaluated buffer, accept / reject (new damping), elimination
-// of the node forces at that damping for the CURRENT iterate, band system, factor + solve + next trial.  RAGGED: with the table rg (N = nmax).
+// of the node forces at that damping for the CURRENT iterate, band system, factor + solve + next trial.
 // xt: x* of every frame (the 3D kinematic cost, k_frame_tracked in place of k_frame_normal), or null (reprojections).
 // back = false (cpe_covariance_kinetic): stop after k_lm_step<3, 2> -- the factor is in Lbuf and every factored sequence has back_pending = 1.
-template <bool RAGGED>
 static void kin_iterate(cpe_handle* h, const LmParams& prm, int N, size_t Fw, size_t ldsn, const double* meas, const double* weight, const int32_t* stance,
-                        const double* xt, RaggedArgs rg, int first, const int* act, const int* n_act, int slots, bool back = true) {
+                        const double* xt, const RaggedArgs* rg, int first, const int* act, const int* n_act, int slots, bool back = true) {
     const unsigned gf = (unsigned)((size_t)slots * N);
     const bool plain = h->gmm_k == 0;
-    prof_begin(h, 0);
-    if (xt) hipLaunchKernelGGL(RAGGED ? FRAME_TRACKED_RAGGED(!plain) : FRAME_TRACKED(!plain), dim3(gf), dim3(WAVE), ldsn, h->stream, h->dm, h->dtrack, h->st, N, first, Fw,
-                               h->qbuf, xt, h->gbuf, h->Bbuf, h->costbuf, h->mu, h->gambuf, h->pri, act, n_act, rg);
-    else hipLaunchKernelGGL(RAGGED ? FRAME_NORMAL_RAGGED(plain) : FRAME_NORMAL(plain), dim3(gf), dim3(WAVE), ldsn, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, meas,
-                            weight, h->gbuf, h->Bbuf, h->costbuf, h->mu, h->gambuf, h->pri, act, n_act, ShutterArgs{nullptr, nullptr, nullptr}, rg);
-    prof_end(h);
-    launch_dyn_eval<RAGGED>(h, N, first, Fw, stance, act, n_act, slots, rg);
-    prof_begin(h, 2);
-    hipLaunchKernelGGL((k_lm_step<3, 1, RAGGED>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gbuf, h->Bbuf, h->costbuf,
-                       h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, nullptr, act, n_act, 2, nullptr, h->dgbuf, nullptr, 0, rg);
-    prof_end(h);
-    launch_dyn_pieces<RAGGED>(h, N, 0, Fw, act, n_act, slots, rg);      // (`which` = 0 also in the first pass: the accept step has just marked every sequence new)
-    prof_begin(h, 9);
-    hipLaunchKernelGGL(k_dyn_schur<RAGGED>, dim3(gf), dim3(KIN_THREADS), lds_kin_schur(), h->stream, h->dk, h->st, N, Fw, h->pieces, h->pmeta, h->fbuf, h->kmu, stance,
-                       h->Tbuf, act, n_act, rg);
-    prof_end(h);
-    prof_begin(h, 6);
-    hipLaunchKernelGGL(k_dyn_gather<RAGGED>, dim3(gf), dim3(KIN_THREADS), 0, h->stream, h->st, N, Fw, h->gbuf, h->Bbuf, h->Tbuf, h->gTb, h->gk, h->Bk, h->Hk, act,
-                       n_act, rg);
-    prof_end(h);
-    prof_begin(h, 2);
-    hipLaunchKernelGGL((k_lm_step<3, 2, RAGGED>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gk, h->Bk, h->costbuf,
-                       h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hk, act, n_act, 1, nullptr, h->dgbuf, nullptr, 0, rg);
-    prof_end(h);
-    if (!back) return;
-    prof_begin(h, 7);
-    hipLaunchKernelGGL((k_lm_back<3, RAGGED>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf, h->gtbuf, h->dgbuf, act, n_act, rg);
-    prof_end(h);
+    with_ragged(rg, [&](auto r, RaggedArgs a) {
+        constexpr bool R = decltype(r)::value;
+        prof_begin(h, 0);
+        if (xt) hipLaunchKernelGGL(frame_tracked<R>(!plain), dim3(gf), dim3(WAVE), ldsn, h->stream, h->dm, h->dtrack, h->st, N, first, Fw, h->qbuf, xt, h->gbuf, h->Bbuf,
+                                   h->costbuf, h->mu, h->gambuf, h->pri, act, n_act, a);
+        else hipLaunchKernelGGL(frame_normal<R>(plain), dim3(gf), dim3(WAVE), ldsn, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, meas, weight, h->gbuf, h->Bbuf,
+                                h->costbuf, h->mu, h->gambuf, h->pri, act, n_act, ShutterArgs{nullptr, nullptr, nullptr}, a);
+        prof_end(h);
+        launch_dyn_eval(h, N, first, Fw, stance, act, n_act, slots, rg);
+        prof_begin(h, 2);
+        hipLaunchKernelGGL((k_lm_step<3, 1, R>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gbuf, h->Bbuf, h->costbuf,
+                           h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, nullptr, act, n_act, 2, nullptr, h->dgbuf, nullptr, 0, a);
+        prof_end(h);
+        launch_dyn_pieces(h, N, 0, Fw, act, n_act, slots, rg);      // (`which` = 0 also in the first pass: the accept step has just marked every sequence new)
+        prof_begin(h, 9);
+        hipLaunchKernelGGL(k_dyn_schur<R>, dim3(gf), dim3(KIN_THREADS), lds_kin_schur(), h->stream, h->dk, h->st, N, Fw, h->pieces, h->pmeta, h->fbuf, h->kmu, stance,
+                           h->Tbuf, act, n_act, a);
+        prof_end(h);
+        prof_begin(h, 6);
+        hipLaunchKernelGGL(k_dyn_gather<R>, dim3(gf), dim3(KIN_THREADS), 0, h->stream, h->st, N, Fw, h->gbuf, h->Bbuf, h->Tbuf, h->gTb, h->gk, h->Bk, h->Hk, act,
+                           n_act, a);
+        prof_end(h);
+        prof_begin(h, 2);
+        hipLaunchKernelGGL((k_lm_step<3, 2, R>), dim3(slots), dim3(LM_THREADS), 0, h->stream, h->dm, h->st, prm, first, h->qbuf, h->gk, h->Bk, h->costbuf,
+                           h->Lbuf, h->zbuf, h->gtbuf, h->gambuf, h->Hk, act, n_act, 1, nullptr, h->dgbuf, nullptr, 0, a);
+        prof_end(h);
+        if (!back) return;
+        prof_begin(h, 7);
+        hipLaunchKernelGGL((k_lm_back<3, R>), dim3(slots), dim3(2 * WAVE), 0, h->stream, h->dm, h->st, prm, h->qbuf, h->Lbuf, h->zbuf, h->gtbuf, h->dgbuf, act, n_act, a);
+        prof_end(h);
+    });
 }
-
-}  // extern "C++"
 
 // ---- 3D kinematic cost (cpe_solve_kinetic_tracked*) ----------------------------------------------------------------------
 void cpe_default_track_weights(double w[CPE_NX]) {
@@ -1749,9 +1742,14 @@ static cpe_status track_target(cpe_handle* h, int B, int N, const double* q_targ
         HIPCHK(hipMalloc(&h->xtgt, sizeof(double) * F * CPE_NX));
         h->xtgt_frames = F;
     }
-    if (rg) hipLaunchKernelGGL(k_track_target<true>, dim3((unsigned)F), dim3(WAVE), 0, h->stream, h->dm, q_target, h->xtgt, *rg);
-    else hipLaunchKernelGGL(k_track_target<>, dim3((unsigned)F), dim3(WAVE), 0, h->stream, h->dm, q_target, h->xtgt, RaggedArgs{});
+    with_ragged(rg, [&](auto r, RaggedArgs a) { hipLaunchKernelGGL(k_track_target<decltype(r)::value>, dim3((unsigned)F), dim3(WAVE), 0, h->stream, h->dm, q_target, h->xtgt, a); });
     HIPCHK(hipGetLastError());
+    return CPE_OK;
+}
+
+// at most one of grf_fixed / tau_box / grf_box is given: refused under the entry's name `who`
+static cpe_status one_force(const std::string& who, const double* grf_fixed, const double* tau_box, const double* grf_box) {
+    if ((grf_fixed != nullptr) + (tau_box != nullptr) + (grf_box != nullptr) > 1) return fail(CPE_BAD_ARG, who + ": at most one of grf_fixed, tau_box, grf_box");
     return CPE_OK;
 }
 
@@ -1799,25 +1797,25 @@ static cpe_status solve_kinetic_impl(cpe_handle* h, const cpe_kinetic_options* o
     if (tr && (s = build_track(h, tr->w, tr->rows)) != CPE_OK) return s;
     const DevModel& m = h->hm;
     const size_t Fw = F;
-    const RaggedArgs rg = ragged ? RaggedArgs{h->rseq, N, cams_max(h)} : RaggedArgs{};
-    if (ragged) HIPCHK(hipMemcpyAsync(h->rseq, seq.data(), sizeof(int2) * B, hipMemcpyHostToDevice, h->stream));     // (seq outlives the stream: drained below)
-    if (tr && (s = track_target(h, B, N, tr->q_target, ragged ? &rg : nullptr, n_frames, tr->checked)) != CPE_OK) return s;
-    if ((s = state_reset(h, B, N, q_init, ragged ? &rg : nullptr)) != CPE_OK || (s = kin_state_reset(h, F, tau_box != nullptr)) != CPE_OK) return s;
+    RaggedArgs rgv;
+    if (ragged && (s = ragged_upload(h, seq, N, rgv)) != CPE_OK) return s;     // (seq outlives the stream: drained below)
+    const RaggedArgs* rg = ragged ? &rgv : nullptr;
+    if (tr && (s = track_target(h, B, N, tr->q_target, rg, n_frames, tr->checked)) != CPE_OK) return s;
+    if ((s = state_reset(h, B, N, q_init, rg)) != CPE_OK || (s = kin_state_reset(h, F, tau_box != nullptr)) != CPE_OK) return s;
     const LmParams prm = lm_params(h, B, N);
-    const size_t ldsn = tr ? (ragged ? lds_tracked_all(h) : lds_tracked(m, h->gmm_k, h->gmm_dim))
-                           : (ragged ? lds_normal_all(h) : lds_normal(m, h->gmm_k, h->gmm_dim));
+    const size_t ldsn = tr ? lds_tracked(h, rg) : lds_normal(h, rg);
     const double* xt = tr ? h->xtgt : nullptr;
     auto iterate = [&](int first, const int* act, const int* n_act, int slots) {
-        if (ragged) kin_iterate<true>(h, prm, N, Fw, ldsn, meas, weight, stance, xt, rg, first, act, n_act, slots);
-        else kin_iterate<false>(h, prm, N, Fw, ldsn, meas, weight, stance, xt, rg, first, act, n_act, slots);
+        kin_iterate(h, prm, N, Fw, ldsn, meas, weight, stance, xt, rg, first, act, n_act, slots);
     };
     if ((s = lm_drive(h, B, iterate)) != CPE_OK) return s;
     std::vector<SeqState> hs;
     std::vector<double> hc;
     s = lm_readback(h, B, N, meas, q, dq, ddq, positions, meas_err, nullptr, [&] {
-        if (ragged) hipLaunchKernelGGL(k_dyn_outputs<true>, dim3((unsigned)F), dim3(64), 0, h->stream, h->dk, h->st, N, Fw, h->fbuf, h->Abuf, nullptr, tau, lambda, grf, rg);
-        else hipLaunchKernelGGL(k_dyn_outputs<>, dim3((unsigned)F), dim3(64), 0, h->stream, h->dk, h->st, N, Fw, h->fbuf, h->Abuf, nullptr, tau, lambda, grf);
-    }, hs, hc, ragged ? &rg : nullptr);
+        with_ragged(rg, [&](auto r, RaggedArgs a) {
+            hipLaunchKernelGGL(k_dyn_outputs<decltype(r)::value>, dim3((unsigned)F), dim3(64), 0, h->stream, h->dk, h->st, N, Fw, h->fbuf, h->Abuf, nullptr, tau, lambda, grf, a);
+        });
+    }, hs, hc, rg);
     if (s != CPE_OK) return s;
     auto len = [&](int b) { return ragged ? n_frames[b] : N; };          // the sequence's own frames
     // slack and the per-node statistics live in the buffer of each sequence's final iterate
@@ -1880,8 +1878,7 @@ cpe_status cpe_solve_kinetic_ragged(cpe_handle* h, const cpe_kinetic_options* op
                                     const double* tau_box, const double* grf_box, double* q, double* dq, double* ddq, double* positions, double* meas_err,
                                     double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats, cpe_kinetic_stats* kstats) {
     if (!h || !opts || !model || !n_frames) return fail(CPE_BAD_ARG, "null argument");
-    if ((grf_fixed != nullptr) + (tau_box != nullptr) + (grf_box != nullptr) > 1)
-        return fail(CPE_BAD_ARG, "cpe_solve_kinetic_ragged: at most one of grf_fixed, tau_box, grf_box");
+    if (cpe_status s = one_force("cpe_solve_kinetic_ragged", grf_fixed, tau_box, grf_box); s != CPE_OK) return s;
     return solve_kinetic_impl(h, opts, B, N_max, model, n_frames, q_init, meas, weight, stance, grf_fixed, tau_box, grf_box, q, dq, ddq, positions, meas_err,
                               tau, lambda, grf, slack, stats, kstats);
 }
@@ -1890,8 +1887,7 @@ cpe_status cpe_solve_kinetic_tracked(cpe_handle* h, const cpe_kinetic_options* o
                                      const double* q_target, const double* meas, const double* weight, const int32_t* stance, const double* grf_fixed,
                                      const double* tau_box, const double* grf_box, double* q, double* dq, double* ddq, double* positions, double* meas_err,
                                      double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats, cpe_kinetic_stats* kstats) {
-    if ((grf_fixed != nullptr) + (tau_box != nullptr) + (grf_box != nullptr) > 1)
-        return fail(CPE_BAD_ARG, "cpe_solve_kinetic_tracked: at most one of grf_fixed, tau_box, grf_box");
+    if (cpe_status s = one_force("cpe_solve_kinetic_tracked", grf_fixed, tau_box, grf_box); s != CPE_OK) return s;
     const TrackIn tr{track_w, 1, q_target, false};
     return solve_kinetic_impl(h, opt, B, N, nullptr, nullptr, q_init, meas, weight, stance, grf_fixed, tau_box, grf_box, q, dq, ddq, positions, meas_err,
                               tau, lambda, grf, slack, stats, kstats, &tr);
@@ -1903,8 +1899,7 @@ cpe_status cpe_solve_kinetic_tracked_ragged(cpe_handle* h, const cpe_kinetic_opt
                                             const double* grf_box, double* q, double* dq, double* ddq, double* positions, double* meas_err, double* tau,
                                             double* lambda, double* grf, double* slack, cpe_stats* stats, cpe_kinetic_stats* kstats) {
     if (!h || !opts || !model || !n_frames) return fail(CPE_BAD_ARG, "null argument");
-    if ((grf_fixed != nullptr) + (tau_box != nullptr) + (grf_box != nullptr) > 1)
-        return fail(CPE_BAD_ARG, "cpe_solve_kinetic_tracked_ragged: at most one of grf_fixed, tau_box, grf_box");
+    if (cpe_status s = one_force("cpe_solve_kinetic_tracked_ragged", grf_fixed, tau_box, grf_box); s != CPE_OK) return s;
     const TrackIn tr{track_w, n_models(h), q_target, false};
     return solve_kinetic_impl(h, opts, B, N_max, model, n_frames, q_init, meas, weight, stance, grf_fixed, tau_box, grf_box, q, dq, ddq, positions, meas_err,
                               tau, lambda, grf, slack, stats, kstats, &tr);
@@ -1924,7 +1919,7 @@ cpe_status cpe_eval_normal_tracked(cpe_handle* h, const double* track_w, int32_t
     if ((s = build_track(h, track_w, 1)) != CPE_OK || (s = track_target(h, B, N, q_target, nullptr, nullptr, false)) != CPE_OK) return s;
     if ((s = state_reset(h, B, N, q)) != CPE_OK) return s;
     const DevModel& m = h->hm;
-    hipLaunchKernelGGL(FRAME_TRACKED(h->gmm_k > 0), dim3((unsigned)F), dim3(WAVE), lds_tracked(m, h->gmm_k, h->gmm_dim), h->stream, h->dm, h->dtrack, h->st, N, 1, F,
+    hipLaunchKernelGGL(frame_tracked<>(h->gmm_k > 0), dim3((unsigned)F), dim3(WAVE), lds_tracked(h, nullptr), h->stream, h->dm, h->dtrack, h->st, N, 1, F,
                        h->qbuf, h->xtgt, h->gbuf, h->Bbuf, h->costbuf, h->mu, h->gambuf, h->pri, nullptr, nullptr, RaggedArgs{});
     HIPCHK(hipMemcpyAsync(g, h->gbuf, sizeof(double) * F * m.nu, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(Bm, h->Bbuf, sizeof(double) * F * m.nu * m.nu, hipMemcpyDeviceToDevice, h->stream));
@@ -1948,8 +1943,7 @@ cpe_status cpe_eval_kinetic_system(cpe_handle* h, const cpe_kinetic_options* opt
                                    const int32_t* stance, const double* grf_fixed, const double* tau_box, const double* grf_box, double* f, double* stat,
                                    double* g, double* Huu, double* Hfu, double* Hff, int32_t* meta, double* gk, double* Bk, double* Hk) {
     if (!h || !opt || !q || !meas || !weight || !stance) return fail(CPE_BAD_ARG, "null argument");
-    if ((grf_fixed != nullptr) + (tau_box != nullptr) + (grf_box != nullptr) > 1)
-        return fail(CPE_BAD_ARG, "cpe_eval_kinetic_system: at most one of grf_fixed, tau_box, grf_box");
+    if (cpe_status s = one_force("cpe_eval_kinetic_system", grf_fixed, tau_box, grf_box); s != CPE_OK) return s;
     size_t F;
     if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
     if (F == 0) return CPE_OK;
@@ -1973,10 +1967,10 @@ cpe_status cpe_eval_kinetic_system(cpe_handle* h, const cpe_kinetic_options* opt
         HIPCHK(hipMemcpyAsync(h->st, hs.data(), sizeof(SeqState) * B, hipMemcpyHostToDevice, h->stream));
     }
     const DevModel& m = h->hm;
-    hipLaunchKernelGGL(FRAME_NORMAL(h->gmm_k == 0), dim3((unsigned)F), dim3(WAVE), lds_normal(m, h->gmm_k, h->gmm_dim), h->stream, h->dm, h->st, N, 1, F, h->qbuf, meas, weight,
+    hipLaunchKernelGGL(frame_normal<>(h->gmm_k == 0), dim3((unsigned)F), dim3(WAVE), lds_normal(h, nullptr), h->stream, h->dm, h->st, N, 1, F, h->qbuf, meas, weight,
                        h->gbuf, h->Bbuf, h->costbuf, h->mu, h->gambuf, h->pri, nullptr, nullptr, ShutterArgs{nullptr, nullptr, nullptr}, RaggedArgs{});
-    launch_dyn_eval<>(h, N, 1, F, stance, nullptr, nullptr, B);
-    launch_dyn_pieces<>(h, N, 1, F, nullptr, nullptr, B);
+    launch_dyn_eval(h, N, 1, F, stance, nullptr, nullptr, B, nullptr);
+    launch_dyn_pieces(h, N, 1, F, nullptr, nullptr, B, nullptr);
     if (band) {
         hipLaunchKernelGGL(k_dyn_schur<>, dim3((unsigned)F), dim3(KIN_THREADS), lds_kin_schur(), h->stream, h->dk, h->st, N, F, h->pieces, h->pmeta, h->fbuf, h->kmu,
                            stance, h->Tbuf, nullptr, nullptr, RaggedArgs{});
@@ -2024,8 +2018,8 @@ static cpe_status lm_first_pass(cpe_handle* h, const cpe_kinetic_options* kopt, 
     HIPCHK(hipMemcpyAsync(h->qbuf + F * ns, h->qbuf, w * F * ns, hipMemcpyDeviceToDevice, h->stream));
     LmParams prm = lm_params(h, B, N);
     prm.lambda0 = lam;                                     // the accept stage of the first pass sets S.lambda from it
-    const size_t ldsn = lds_normal(m, h->gmm_k, h->gmm_dim, sh.tau != nullptr);
-    if (kopt) kin_iterate<false>(h, prm, N, F, ldsn, meas, weight, stance, nullptr, RaggedArgs{}, 1, nullptr, nullptr, B);
+    const size_t ldsn = lds_normal(h, nullptr, sh.tau != nullptr);
+    if (kopt) kin_iterate(h, prm, N, F, ldsn, meas, weight, stance, nullptr, nullptr, 1, nullptr, nullptr, B);
     else lm_iterate(h, prm, N, F, ldsn, meas, weight, sh, nullptr, 1, nullptr, nullptr, B);
     HIPCHK(hipGetLastError());
     hs.resize((size_t)B);
@@ -2154,16 +2148,28 @@ static void cov_launch(cpe_handle* h, int B, int N, const SeqState* st, const do
                        const RaggedArgs* rg) {
     const unsigned gf = (unsigned)((size_t)B * N);
     auto go = [&](auto pbc) {
-        constexpr int PB = decltype(pbc)::value;
-        if (rg) {
-            hipLaunchKernelGGL((k_cov_prep<PB, true>), dim3(gf), dim3(WAVE), 0, h->stream, st, Lsrc, h->covG, N, recip, *rg);
-            hipLaunchKernelGGL((k_lm_selinv<PB, true>), dim3(B), dim3(COV_THREADS), 0, h->stream, st, h->covG, cov_diag, cov_off, N, *rg);
-        } else {
-            hipLaunchKernelGGL((k_cov_prep<PB>), dim3(gf), dim3(WAVE), 0, h->stream, st, Lsrc, h->covG, N, recip, RaggedArgs{});
-            hipLaunchKernelGGL((k_lm_selinv<PB>), dim3(B), dim3(COV_THREADS), 0, h->stream, st, h->covG, cov_diag, cov_off, N, RaggedArgs{});
-        }
+        with_ragged(rg, [&](auto r, RaggedArgs a) {
+            constexpr int PB = decltype(pbc)::value;
+            constexpr bool R = decltype(r)::value;
+            hipLaunchKernelGGL((k_cov_prep<PB, R>), dim3(gf), dim3(WAVE), 0, h->stream, st, Lsrc, h->covG, N, recip, a);
+            hipLaunchKernelGGL((k_lm_selinv<PB, R>), dim3(B), dim3(COV_THREADS), 0, h->stream, st, h->covG, cov_diag, cov_off, N, a);
+        });
     };
     if (h->pb == 3) go(std::integral_constant<int, 3>{}); else go(std::integral_constant<int, 4>{});
+}
+
+// what the covariances of both models add after the sweep: the markers' position covariance (cov_pos, or null) and the factor columns in plain
+// layout (L, or null)
+static void cov_extras(cpe_handle* h, int N, size_t F, const double* cov_diag, double* cov_pos, double* L, const RaggedArgs* rg) {
+    const size_t BB = (size_t)CPE_NX * CPE_NX;
+    // (k_marker_cov's arrays are a subset of k_frame_normal's, plus Sigma(n,n) and one int per (marker, column) item; in both forms it is given
+    // what the largest of the handle's models needs)
+    const size_t ldsm = lds_normal_all(h) + sizeof(double) * BB + sizeof(int) * (size_t)(CPE_MAX_MARKERS * CPE_MAX_MCOL);
+    with_ragged(rg, [&](auto r, RaggedArgs a) {
+        constexpr bool R = decltype(r)::value;
+        if (cov_pos) hipLaunchKernelGGL(k_marker_cov<R>, dim3((unsigned)F), dim3(WAVE), ldsm, h->stream, h->dm, h->st, N, F, h->qbuf, cov_diag, cov_pos, a);
+        if (L) hipLaunchKernelGGL(k_cov_export<R>, dim3((unsigned)F), dim3(COV_THREADS), 0, h->stream, h->st, h->Lbuf, L, N, (int)((h->pb + 1) * BB), a);
+    });
 }
 
 cpe_status cpe_covariance_supported(const cpe_priors* priors, double ridge) {
@@ -2206,13 +2212,12 @@ static cpe_status covariance_impl(cpe_handle* h, int32_t B, int32_t N, const int
     cpe_status s = ensure_ws(h, B, N);
     if (s != CPE_OK) return s;
     if ((s = ensure_cov(h, F)) != CPE_OK) return s;
-    RaggedArgs rgv{h->rseq, N, cams_max(h)};
+    RaggedArgs rgv;
+    if (model && (s = ragged_upload(h, seq, N, rgv)) != CPE_OK) return s;     // (seq outlives the stream: it is drained below)
     const RaggedArgs* rg = model ? &rgv : nullptr;
-    if (model) HIPCHK(hipMemcpyAsync(h->rseq, seq.data(), sizeof(int2) * B, hipMemcpyHostToDevice, h->stream));     // (seq outlives the stream: it is drained below)
     if ((s = state_reset(h, B, N, q, rg)) != CPE_OK) return s;
     const DevModel& m = h->hm;
-    const int RING = h->pb + 1;
-    const size_t BB = (size_t)CPE_NX * CPE_NX, w = sizeof(double), LC = (size_t)RING * BB;
+    const size_t BB = (size_t)CPE_NX * CPE_NX, w = sizeof(double);
     // a sequence without a factor, and every frame past a sequence's own, has all outputs zero
     HIPCHK(hipMemsetAsync(cov_diag, 0, w * F * BB, h->stream));
     if (cov_off) HIPCHK(hipMemsetAsync(cov_off, 0, w * F * h->pb * BB, h->stream));
@@ -2220,19 +2225,9 @@ static cpe_status covariance_impl(cpe_handle* h, int32_t B, int32_t N, const int
     // the launches of a solve's first pass up to the factor, multipliers zero, at damping ridge in place of opts.lambda0
     LmParams prm = lm_params(h, B, N);
     prm.lambda0 = ridge;
-    const size_t ldsn = rg ? lds_normal_all(h) : lds_normal(m, h->gmm_k, h->gmm_dim);
-    lm_iterate(h, prm, N, F, ldsn, meas, weight, ShutterArgs{nullptr, nullptr, nullptr}, rg, 1, nullptr, nullptr, B, false);
+    lm_iterate(h, prm, N, F, lds_normal(h, rg), meas, weight, ShutterArgs{nullptr, nullptr, nullptr}, rg, 1, nullptr, nullptr, B, false);
     cov_launch(h, B, N, h->st, h->Lbuf, 1, cov_diag, cov_off, rg);
-    if (cov_pos) {
-        // (k_marker_cov's arrays are a subset of k_frame_normal's, plus Sigma(n,n) and one int per (marker, column) item)
-        const size_t ldsm = lds_normal_all(h) + w * BB + sizeof(int) * (size_t)(CPE_MAX_MARKERS * CPE_MAX_MCOL);
-        if (rg) hipLaunchKernelGGL(k_marker_cov<true>, dim3((unsigned)F), dim3(WAVE), ldsm, h->stream, h->dm, h->st, N, F, h->qbuf, cov_diag, cov_pos, *rg);
-        else hipLaunchKernelGGL(k_marker_cov<>, dim3((unsigned)F), dim3(WAVE), ldsm, h->stream, h->dm, h->st, N, F, h->qbuf, cov_diag, cov_pos, RaggedArgs{});
-    }
-    if (L) {
-        if (rg) hipLaunchKernelGGL(k_cov_export<true>, dim3((unsigned)F), dim3(COV_THREADS), 0, h->stream, h->st, h->Lbuf, L, N, (int)LC, *rg);
-        else hipLaunchKernelGGL(k_cov_export<>, dim3((unsigned)F), dim3(COV_THREADS), 0, h->stream, h->st, h->Lbuf, L, N, (int)LC, RaggedArgs{});
-    }
+    cov_extras(h, N, F, cov_diag, cov_pos, L, rg);
     HIPCHK(hipGetLastError());
     std::vector<SeqState> hs((size_t)B);
     HIPCHK(hipMemcpyAsync(hs.data(), h->st, sizeof(SeqState) * B, hipMemcpyDeviceToHost, h->stream));
@@ -2336,9 +2331,9 @@ static cpe_status rate_covariance_impl(const char* who, bool ragged, cpe_handle*
     }
     double* jp = !want_pos ? nullptr : jac_pos ? jac_pos : h->rateJ;
     double* jc = !want_com ? nullptr : jac_com ? jac_com : h->rateJ + (want_pos && !jac_pos ? F * m.L * PW : 0);
-    const RaggedArgs rgv{h->rseq, N, cams_max(h)};
+    RaggedArgs rgv;
+    if (ragged && (s = ragged_upload(h, seq, N, rgv)) != CPE_OK) return s;     // (seq outlives the stream: it is drained below)
     const RaggedArgs* rg = ragged ? &rgv : nullptr;
-    if (ragged) HIPCHK(hipMemcpyAsync(h->rseq, seq.data(), sizeof(int2) * B, hipMemcpyHostToDevice, h->stream));     // (seq outlives the stream: it is drained below)
     if ((s = state_reset(h, B, N, q, rg)) != CPE_OK) return s;
     // everything that is defined as zero -- past a sequence's frames, row 0 of the velocities, the short sequences, the columns a point does not
     // depend on -- is zero from here; the kernels write the rest
@@ -2350,18 +2345,15 @@ static cpe_status rate_covariance_impl(const char* who, bool ragged, cpe_handle*
     if (cov_com) HIPCHK(hipMemsetAsync(cov_com, 0, wd * F * 9, h->stream));
     if (cov_com_vel) HIPCHK(hipMemsetAsync(cov_com_vel, 0, wd * F * 9, h->stream));
     const unsigned gf = (unsigned)F;
-    if (jp || jc) {
-        const size_t lds = wd * PJ_LDS_DOUBLES;
-        if (rg) hipLaunchKernelGGL(k_point_jac<true>, dim3(gf), dim3(WAVE), lds, h->stream, h->dm, h->dmc, N, h->qbuf, jp, jc, *rg);
-        else hipLaunchKernelGGL(k_point_jac<>, dim3(gf), dim3(WAVE), lds, h->stream, h->dm, h->dmc, N, h->qbuf, jp, jc, RaggedArgs{});
-    }
-    if (cov_du || cov_ddu || cov_vel || cov_com || cov_com_vel) {
-        const size_t lds = wd * (3 * BB + 2 * PW * m.L + 2 * PW);       // (at most 63168 bytes, CPE_MAX_MARKERS = 32)
-        if (rg) hipLaunchKernelGGL(k_rate_cov<true>, dim3(gf), dim3(WAVE), lds, h->stream, h->dm, N, h->pb, cov_diag, cov_off, jp, jc, cov_du, cov_ddu,
-                                   cov_vel, cov_com, cov_com_vel, *rg);
-        else hipLaunchKernelGGL(k_rate_cov<>, dim3(gf), dim3(WAVE), lds, h->stream, h->dm, N, h->pb, cov_diag, cov_off, jp, jc, cov_du, cov_ddu,
-                                cov_vel, cov_com, cov_com_vel, RaggedArgs{});
-    }
+    with_ragged(rg, [&](auto r, RaggedArgs a) {
+        constexpr bool R = decltype(r)::value;
+        if (jp || jc) hipLaunchKernelGGL(k_point_jac<R>, dim3(gf), dim3(WAVE), wd * PJ_LDS_DOUBLES, h->stream, h->dm, h->dmc, N, h->qbuf, jp, jc, a);
+        if (cov_du || cov_ddu || cov_vel || cov_com || cov_com_vel) {
+            const size_t lds = wd * (3 * BB + 2 * PW * m.L + 2 * PW);       // (at most 63168 bytes, CPE_MAX_MARKERS = 32)
+            hipLaunchKernelGGL(k_rate_cov<R>, dim3(gf), dim3(WAVE), lds, h->stream, h->dm, N, h->pb, cov_diag, cov_off, jp, jc, cov_du, cov_ddu, cov_vel, cov_com,
+                               cov_com_vel, a);
+        }
+    });
     HIPCHK(hipGetLastError());
     if (ragged) HIPCHK(hipStreamSynchronize(h->stream));
     return CPE_OK;
@@ -2424,8 +2416,7 @@ static cpe_status cov_kinetic_check(const char* who, const cpe_handle* h, const 
     if (cpe_status s = cov_check(who, -1, ridge); s != CPE_OK) return s;
     if (!opt) return fail(CPE_BAD_ARG, std::string(who) + ": null kinetic options");
     if (!stance) return fail(CPE_BAD_ARG, std::string(who) + ": null stance");
-    if ((grf_fixed != nullptr) + (tau_box != nullptr) + (grf_box != nullptr) > 1)
-        return fail(CPE_BAD_ARG, std::string(who) + ": at most one of grf_fixed, tau_box, grf_box");
+    if (cpe_status s = one_force(who, grf_fixed, tau_box, grf_box); s != CPE_OK) return s;
     if (h && h->pb != 3)
         return fail(CPE_BAD_ARG, std::string(who) + ": half-bandwidth " + std::to_string(h->pb) + ": the physics-based model runs on the half-bandwidth-3 solver");
     return CPE_OK;
@@ -2460,9 +2451,9 @@ static cpe_status covariance_kinetic_impl(const char* who, cpe_handle* h, const 
     if (s != CPE_OK) return s;
     if ((s = ensure_kws(h, B, N)) != CPE_OK || (s = ensure_cov(h, F)) != CPE_OK) return s;
     if ((s = ragged ? build_kin_all(h, opt, grf_fixed, tau_box, grf_box, who) : build_kin(h, opt, grf_fixed, tau_box, grf_box)) != CPE_OK) return s;
-    const RaggedArgs rgv = ragged ? RaggedArgs{h->rseq, N, cams_max(h)} : RaggedArgs{};
+    RaggedArgs rgv;
+    if (ragged && (s = ragged_upload(h, seq, N, rgv)) != CPE_OK) return s;     // (seq outlives the stream: drained below)
     const RaggedArgs* rg = ragged ? &rgv : nullptr;
-    if (ragged) HIPCHK(hipMemcpyAsync(h->rseq, seq.data(), sizeof(int2) * B, hipMemcpyHostToDevice, h->stream));     // (seq outlives the stream: drained below)
     if ((s = state_reset(h, B, N, q, rg)) != CPE_OK || (s = kin_state_reset(h, F, tau_box != nullptr)) != CPE_OK) return s;
     const DevModel& m = h->hm;
     const size_t BB = (size_t)CPE_NX * CPE_NX, w = sizeof(double), LC = 4 * BB, FF = (size_t)KIN_LS * KIN_LS;
@@ -2482,23 +2473,14 @@ static cpe_status covariance_kinetic_impl(const char* who, cpe_handle* h, const 
     // the launches of the physics solve's first pass up to the band factor, multipliers zero, at damping ridge in place of opts.lambda0
     LmParams prm = lm_params(h, B, N);
     prm.lambda0 = ridge;
-    if (ragged) kin_iterate<true>(h, prm, N, F, lds_normal_all(h), meas, weight, stance, nullptr, rgv, 1, nullptr, nullptr, B, false);
-    else kin_iterate<false>(h, prm, N, F, lds_normal(m, h->gmm_k, h->gmm_dim), meas, weight, stance, nullptr, RaggedArgs{}, 1, nullptr, nullptr, B, false);
+    kin_iterate(h, prm, N, F, lds_normal(h, rg), meas, weight, stance, nullptr, rg, 1, nullptr, nullptr, B, false);
     cov_launch(h, B, N, h->st, h->Lbuf, 1, cov_diag, cov_off, rg);
     // (without cov_f the kernel still decides whether every node's force matrix has a factor: the status does not depend on what is asked for)
-    if (ragged) hipLaunchKernelGGL(k_force_cov<true>, dim3((unsigned)F), dim3(KIN_THREADS), sizeof(double) * FC_DOUBLES, h->stream, h->dk, h->st, N, F, h->pieces,
-                                   h->pmeta, h->fbuf, h->kmu, stance, cov_diag, cov_off, cov_f, f, meta, bad, rgv);
-    else hipLaunchKernelGGL(k_force_cov<>, dim3((unsigned)F), dim3(KIN_THREADS), sizeof(double) * FC_DOUBLES, h->stream, h->dk, h->st, N, F, h->pieces, h->pmeta,
-                            h->fbuf, h->kmu, stance, cov_diag, cov_off, cov_f, f, meta, bad, RaggedArgs{});
-    if (cov_pos) {
-        const size_t ldsm = lds_normal_all(h) + w * BB + sizeof(int) * (size_t)(CPE_MAX_MARKERS * CPE_MAX_MCOL);
-        if (ragged) hipLaunchKernelGGL(k_marker_cov<true>, dim3((unsigned)F), dim3(WAVE), ldsm, h->stream, h->dm, h->st, N, F, h->qbuf, cov_diag, cov_pos, rgv);
-        else hipLaunchKernelGGL(k_marker_cov<>, dim3((unsigned)F), dim3(WAVE), ldsm, h->stream, h->dm, h->st, N, F, h->qbuf, cov_diag, cov_pos, RaggedArgs{});
-    }
-    if (L) {
-        if (ragged) hipLaunchKernelGGL(k_cov_export<true>, dim3((unsigned)F), dim3(COV_THREADS), 0, h->stream, h->st, h->Lbuf, L, N, (int)LC, rgv);
-        else hipLaunchKernelGGL(k_cov_export<>, dim3((unsigned)F), dim3(COV_THREADS), 0, h->stream, h->st, h->Lbuf, L, N, (int)LC, RaggedArgs{});
-    }
+    with_ragged(rg, [&](auto r, RaggedArgs a) {
+        hipLaunchKernelGGL(k_force_cov<decltype(r)::value>, dim3((unsigned)F), dim3(KIN_THREADS), sizeof(double) * FC_DOUBLES, h->stream, h->dk, h->st, N, F, h->pieces,
+                           h->pmeta, h->fbuf, h->kmu, stance, cov_diag, cov_off, cov_f, f, meta, bad, a);
+    });
+    cov_extras(h, N, F, cov_diag, cov_pos, L, rg);
     HIPCHK(hipGetLastError());
     std::vector<SeqState> hs((size_t)B);
     std::vector<int> hbad((size_t)B);
@@ -2668,8 +2650,7 @@ static cpe_status solve_host_impl(cpe_handle* h, int32_t B, int32_t N, const int
     double *oq = st.out(q, F * m.nq), *odq = st.out(dq, F * m.nq), *oddq = st.out(ddq, F * m.nq);
     double *op = st.out(positions, F * m.L * 3), *ome = st.out(meas_err, nm * 2);
     HIPCHK(st.err);
-    cpe_status s = model ? cpe_solve_ragged(h, B, N, model, n_frames, di, dmeas, dweight, oq, odq, oddq, op, ome, stats)
-                         : cpe_solve(h, B, N, di, dmeas, dweight, oq, odq, oddq, op, ome, stats);
+    cpe_status s = solve_impl(h, B, N, model, n_frames, di, dmeas, dweight, oq, odq, oddq, op, ome, stats);
     if (s < 0) return s;
     HIPCHK(st.fetch());
     return s;
@@ -2732,8 +2713,7 @@ cpe_status cpe_solve_kinetic_ragged_host(cpe_handle* h, const cpe_kinetic_option
                                          const double* tau_box, const double* grf_box, double* q, double* dq, double* ddq, double* positions, double* meas_err,
                                          double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats, cpe_kinetic_stats* kstats) {
     if (!h || !opts || !model || !n_frames || !q_init || !meas || !weight || !stance || !q) return fail(CPE_BAD_ARG, "null argument");
-    if ((grf_fixed != nullptr) + (tau_box != nullptr) + (grf_box != nullptr) > 1)
-        return fail(CPE_BAD_ARG, "cpe_solve_kinetic_ragged: at most one of grf_fixed, tau_box, grf_box");
+    if (cpe_status s = one_force("cpe_solve_kinetic_ragged", grf_fixed, tau_box, grf_box); s != CPE_OK) return s;
     size_t F;
     if (cpe_status s = frames(B, N_max, &F); s != CPE_OK) return s;
     if (F == 0) return CPE_OK;
@@ -2768,8 +2748,7 @@ static cpe_status kinetic_tracked_host(cpe_handle* h, const cpe_kinetic_options*
     if (!q_target) return fail(CPE_BAD_ARG, "q_target is null");
     if (meas && !weight) return fail(CPE_BAD_ARG, "meas is given without weight");
     if (weight && !meas) return fail(CPE_BAD_ARG, "weight is given without meas");
-    if ((grf_fixed != nullptr) + (tau_box != nullptr) + (grf_box != nullptr) > 1)
-        return fail(CPE_BAD_ARG, "cpe_solve_kinetic_tracked: at most one of grf_fixed, tau_box, grf_box");
+    if (cpe_status s = one_force("cpe_solve_kinetic_tracked", grf_fixed, tau_box, grf_box); s != CPE_OK) return s;
     size_t F;
     if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
     if (F == 0) return CPE_OK;
