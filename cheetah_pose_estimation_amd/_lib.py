@@ -752,6 +752,37 @@ class Handle:
         res.update(status=st, seq_status=list(seq)[:B], padded=out)
         return res
 
+    # ---- covariance between distant frames (include/cpe.h, cpe_covariance_columns) ---------------------------------------------------------
+    def _column_args(self, who, shape, anchors, n_frames):
+        """B, N, K and the host arrays (anchors [B, K], n_frames [B] or None) of a columns call, from the shape of L"""
+        B, N = int(shape[0]), int(shape[1])
+        an = np.ascontiguousarray(anchors, dtype=np.int32)
+        if an.ndim != 2 or an.shape[0] != B:
+            raise ValueError(f"{who}: anchors must be [B, K] with one row per sequence")
+        nf = None if n_frames is None else np.ascontiguousarray(n_frames, dtype=np.int32)
+        if nf is not None and nf.shape != (B,):
+            raise ValueError(f"{who}: one frame count per sequence")
+        return B, N, an.shape[1], an, nf, an.ctypes.data_as(ip), None if nf is None else nf.ctypes.data_as(ip)
+
+    def covariance_columns(self, L, cov_diag, cov_off, anchors, cols, n_frames=None):
+        """cpe_covariance_columns on device tensors: L [B, N, pb + 1, 28, 28], cov_diag [B, N, 28, 28], cov_off [B, N, pb, 28, 28] (a covariance
+        entry's factor and band); anchors [B, K] and n_frames [B] (or None = all N) on the host -> cols [B, K, N, 28, 28]: block [b, k, n] =
+        Sigma(n, anchors[b, k]) for n <= the anchor, zero elsewhere and for an anchor of -1"""
+        B, N, K, _an, _nf, pa, pn = self._column_args("covariance_columns", L.shape, anchors, n_frames)
+        self._call(self.lib.cpe_covariance_columns, "cpe_covariance_columns", B, N, pn, _ptr(L), _ptr(cov_diag), _ptr(cov_off), K, pa, _ptr(cols))
+
+    def covariance_columns_host(self, L, cov_diag, cov_off, anchors, n_frames=None):
+        """cpe_covariance_columns_host: numpy in, cols [B, K, N, 28, 28] out"""
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        L, cov_diag, cov_off = f64(L), f64(cov_diag), f64(cov_off)
+        B, N, K, _an, _nf, pa, pn = self._column_args("covariance_columns_host", L.shape, anchors, n_frames)
+        if L.shape != (B, N, self.pb + 1, 28, 28) or cov_diag.shape != (B, N, 28, 28) or cov_off.shape != (B, N, self.pb, 28, 28):
+            raise ValueError(f"covariance_columns_host: L / cov_diag / cov_off do not have the shapes of the handle's half-bandwidth {self.pb}")
+        cols = np.empty((B, K, N, 28, 28))
+        _check(self.lib.cpe_covariance_columns_host(self._h, B, N, pn, _ptr(L), _ptr(cov_diag), _ptr(cov_off), K, pa, _ptr(cols)),
+               "cpe_covariance_columns_host")
+        return cols
+
     # ---- posterior covariance of the rates (include/cpe.h, cpe_rate_covariance) -----------------------------------------------------------
     def rate_covariance(self, q, cov_diag, cov_off, cov_du=None, cov_ddu=None, cov_vel=None, cov_com=None, cov_com_vel=None, jac_pos=None,
                         jac_com=None):

@@ -205,6 +205,9 @@ RATE_COVARIANCE_ENTRIES = {
     "cpe_rate_covariance_ragged_host": _BN + _RAGGED + _RATE_COV,
 }
 RATE_COVARIANCE_OUTPUTS = ("cov_du", "cov_ddu", "cov_vel", "cov_com", "cov_com_vel", "jac_pos", "jac_com")      # in the order of the arguments
+# the columns beyond the band (cpe_covariance_columns): h, B, N | n_frames | L, cov_diag, cov_off | K, anchors | cols
+_COLUMNS = _BN + ("ip", "p", "p", "p", "i", "ip", "p")
+COLUMN_COVARIANCE_ENTRIES = ("cpe_covariance_columns", "cpe_covariance_columns_host")
 COVARIANCE_MAX_PB = 4        # largest half-bandwidth (frames) the covariance sweep supports: motion-prior windows 5 and 6 are refused
 ENTRIES = {
     "cpe_create": ("sk", "cam", "i", "op", "pr", "i", "hp"),
@@ -261,6 +264,7 @@ ENTRIES = {
     "cpe_eval_shutter_step": _BN + ("p",) * 4 + ("d",) + ("p",) * 9,
     "cpe_eval_shutter_step_host": _BN + ("p",) * 4 + ("d",) + ("p",) * 9,
     **COVARIANCE_ENTRIES, **KINETIC_COVARIANCE_ENTRIES, **KINETIC_COVARIANCE_RAGGED_ENTRIES, **RATE_COVARIANCE_ENTRIES,
+    **{name: _COLUMNS for name in COLUMN_COVARIANCE_ENTRIES},
 }
 
 

@@ -2289,6 +2289,85 @@ cpe_status cpe_covariance_ragged_host(cpe_handle* h, int32_t B, int32_t N_max, c
     return covariance_host_impl(h, B, N_max, model, n_frames, q, meas, weight, ridge, cov_diag, cov_off, cov_pos, L, status);
 }
 
+// ---- columns of Sigma beyond the band (include/cpe.h, cpe_covariance_columns; k_cov_columns in cpe_covariance.hip.inc) -----------------------
+// What both forms refuse, before the device is touched; fills F and the device's view of the call: tab = one (0, frames) pair per sequence -- zero
+// frames for a sequence without an anchor, whose arrays are then not read -- followed by the B K anchors.
+static cpe_status columns_check(const char* who, const cpe_handle* h, int32_t B, int32_t N, const int32_t* n_frames, bool arrays, int32_t K,
+                                const int32_t* anchors, size_t* F, std::vector<int>& tab) {
+    const std::string w = std::string(who) + ": ";
+    if (!h || !arrays || !anchors) return fail(CPE_BAD_ARG, w + "null argument (only n_frames may be null)");
+    if (cpe_status s = cov_check(who, h->pb, 0.0); s != CPE_OK) return s;
+    if (K < 1) return fail(CPE_BAD_ARG, w + "K must be at least 1");
+    size_t FK;
+    if (cpe_status s = frames(B, N, F); s != CPE_OK) return fail(s, w + g_err);
+    if (cpe_status s = frames((int32_t)*F, K, &FK); s != CPE_OK) return fail(s, w + g_err);
+    tab.assign(2 * (size_t)B + (size_t)B * K, 0);
+    for (int b = 0; b < B; b++) {
+        const int nf = n_frames ? n_frames[b] : N;
+        if (nf < 0 || nf > N) return fail(CPE_BAD_ARG, w + "frame count of sequence " + std::to_string(b) + " outside 0..N");
+        bool any = false;
+        for (int k = 0; k < K; k++) {
+            const int a = anchors[(size_t)b * K + k];
+            if (a < -1 || a >= nf)
+                return fail(CPE_BAD_ARG, w + "anchor " + std::to_string(a) + " of sequence " + std::to_string(b) + " outside -1.." + std::to_string(nf - 1));
+            tab[2 * (size_t)B + (size_t)b * K + k] = a;
+            any = any || a >= 0;
+        }
+        tab[2 * (size_t)b + 1] = any ? nf : 0;
+    }
+    return CPE_OK;
+}
+
+// the device entry after its checks: d_tab = tab on the device
+static cpe_status columns_launch(cpe_handle* h, int32_t B, int32_t N, size_t F, const int* d_tab, const double* L, const double* cov_diag,
+                                 const double* cov_off, int32_t K, double* cols) {
+    if (cpe_status s = ensure_cov(h, F); s != CPE_OK) return s;
+    HIPCHK(hipMemsetAsync(cols, 0, sizeof(double) * F * K * CPE_NX * CPE_NX, h->stream));      // n > a, unused slots, past a sequence's frames
+    const RaggedArgs rg{reinterpret_cast<const int2*>(d_tab), N, 0};
+    const int* d_anchors = d_tab + 2 * (size_t)B;
+    auto go = [&](auto pbc) {
+        constexpr int PB = decltype(pbc)::value;
+        hipLaunchKernelGGL((k_cov_prep<PB, true>), dim3((unsigned)F), dim3(WAVE), 0, h->stream, nullptr, L, h->covG, N, 0, rg);
+        hipLaunchKernelGGL((k_cov_columns<PB>), dim3((unsigned)((size_t)B * K)), dim3(COV_THREADS), 0, h->stream, h->covG, cov_diag, cov_off, d_anchors, cols, N, K);
+    };
+    if (h->pb == 3) go(std::integral_constant<int, 3>{}); else go(std::integral_constant<int, 4>{});
+    HIPCHK(hipGetLastError());
+    return CPE_OK;
+}
+
+cpe_status cpe_covariance_columns(cpe_handle* h, int32_t B, int32_t N, const int32_t* n_frames, const double* L, const double* cov_diag,
+                                  const double* cov_off, int32_t K, const int32_t* anchors, double* cols) {
+    size_t F;
+    std::vector<int> tab;
+    if (cpe_status s = columns_check("cpe_covariance_columns", h, B, N, n_frames, L && cov_diag && cov_off && cols, K, anchors, &F, tab); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    HIPCHK(hipSetDevice(h->device));
+    Staging st(h->stream);
+    const int* d_tab = st.in(tab.data(), tab.size());
+    HIPCHK(st.err);
+    if (cpe_status s = columns_launch(h, B, N, F, d_tab, L, cov_diag, cov_off, K, cols); s != CPE_OK) return s;
+    HIPCHK(hipStreamSynchronize(h->stream));                // (tab is pageable and the staged copy is freed on return)
+    return CPE_OK;
+}
+
+cpe_status cpe_covariance_columns_host(cpe_handle* h, int32_t B, int32_t N, const int32_t* n_frames, const double* L, const double* cov_diag,
+                                       const double* cov_off, int32_t K, const int32_t* anchors, double* cols) {
+    size_t F;
+    std::vector<int> tab;
+    if (cpe_status s = columns_check("cpe_covariance_columns_host", h, B, N, n_frames, L && cov_diag && cov_off && cols, K, anchors, &F, tab); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t BB = (size_t)CPE_NX * CPE_NX;
+    Staging st(h->stream);
+    const int* d_tab = st.in(tab.data(), tab.size());
+    const double *dl = st.in(L, F * (h->pb + 1) * BB), *dd = st.in(cov_diag, F * BB), *dof = st.in(cov_off, F * h->pb * BB);
+    double* oc = st.out(cols, F * K * BB);
+    HIPCHK(st.err);
+    if (cpe_status s = columns_launch(h, B, N, F, d_tab, dl, dd, dof, K, oc); s != CPE_OK) return s;
+    HIPCHK(st.fetch());
+    return CPE_OK;
+}
+
 // ---- posterior covariance of the rates (include/cpe.h, cpe_rate_covariance; kernels in cpe_rate_cov.hip.inc) --------------------------------
 // What both forms refuse, before the device is touched and in this order -- what needs no handle first: negative sizes, the ragged form's null
 // model / n_frames, a null handle, q, cov_diag or cov_off, all outputs null; then a plain handle or a bad table for the ragged form, and a

@@ -5,7 +5,8 @@
 //     Sigma(n,n)   = T_n^T T_n - sum_k G_k^T Sigma(n+k,n)
 // Every Sigma on the right lies inside the band.  Three kernels: k_cov_prep (frame-parallel: T, G, T^T T -- the whole factor is known up
 // front, so the 28-step triangular inverse is not part of the serial chain), k_lm_selinv (the serial sweep, one workgroup per sequence)
-// and k_marker_cov (3x3 covariance of every marker position).  No atomics; every sum has a fixed order.
+// and k_marker_cov (3x3 covariance of every marker position).  No atomics; every sum has a fixed order.  A fourth, k_cov_columns at the end of the
+// file, continues the recurrence past the band: whole columns Sigma(0..a, a) for the covariance between distant frames (cpe_covariance_columns).
 
 #define COV_THREADS 256
 
@@ -331,5 +332,113 @@ __global__ __launch_bounds__(COV_THREADS) void k_cov_export(const SeqState* __re
         double v = 0.0;
         if (ok) { v = Lbuf[col + t]; if (t < NU * NU && t / NU == t % NU) v = 1.0 / v; }
         L[col + t] = v;
+    }
+}
+
+// ---- columns of Sigma beyond the band (include/cpe.h, cpe_covariance_columns; DESIGN.md 2 "What is spanned").  L^T Sigma = L^-1 is lower
+// triangular, so above an anchor frame a the rows of L^T give
+//     Sigma(n,a) = - sum_k G_k(n)^T Sigma(n+k,a)                      k = 1..PB,   n = a-PB-1 .. 0
+// with k_cov_prep's G_k: the sweep's recurrence continued upward, seeded by the band blocks Sigma(a-i,a) = Sigma(a,a-i)^T.  One 256-thread workgroup
+// per (sequence, anchor slot), the rows in series.  LDS: the last PB blocks of the column as a ring over the frame index mod PB, the operands
+// G_1 .. G_PB of the row, and PB partial products; blocks are [28][LDB] doubles.  The operands of row n-1 are requested into registers before row
+// n is computed.  Block products by 4 x 4 register tiles as in k_lm_selinv: 49 PB jobs (tile, k), one per thread, then the thread that stores an
+// element sums its PB parts in the order of k.  No atomics; a column depends on nothing but its own sequence and anchor.  The rows n > a are not
+// written (the caller zeroes the output); the rows a-PB .. a are copies of the band.
+template <int PB>
+__global__ __launch_bounds__(COV_THREADS, 1) void k_cov_columns(const double* __restrict__ Gbuf, const double* __restrict__ cov_diag,
+                                                                const double* __restrict__ cov_off, const int* __restrict__ anchors,
+                                                                double* __restrict__ cols, int NS, int K) {
+    constexpr int RING = PB + 1, BB = NU * NU, COLD = RING * BB, GN = PB * BB;
+    constexpr int NPF = (GN + COV_THREADS - 1) / COV_THREADS;
+    constexpr int TPB = (NU / 4) * (NU / 4);                 // 49 tiles of a block
+    static_assert(PB >= 3 && PB <= 4 && TPB * PB <= COV_THREADS, "one tile job per thread");
+    __shared__ double Xs[PB * BLK];
+    __shared__ double Gs[PB * BLK];
+    __shared__ double Ps[PB * BLK];
+    const int tid = threadIdx.x;
+    const int b = (int)(blockIdx.x / (unsigned)K);
+    const int a = anchors[blockIdx.x];
+    if (a < 0 || a >= NS) return;                            // uniform: an unused slot stays zero
+    const double* Gb = Gbuf + (size_t)b * NS * COLD;
+    const double* cd = cov_diag + (size_t)b * NS * BB;
+    const double* co = cov_off + (size_t)b * NS * (size_t)(PB * BB);
+    double* out = cols + (size_t)blockIdx.x * NS * BB;
+
+    // ---- the rows inside the band: Sigma(a,a), and Sigma(a-i,a) = the transpose of block [a-i][i-1] of cov_off -- into the ring as well
+    for (int e = tid; e < BB; e += COV_THREADS) out[(size_t)a * BB + e] = cd[(size_t)a * BB + e];
+#pragma unroll
+    for (int i = 1; i <= PB; i++) {
+        const int n = a - i;
+        if (n < 0) break;
+        const double* S = co + ((size_t)n * PB + (i - 1)) * BB;
+        double* X = Xs + (n % PB) * BLK;
+        for (int e = tid; e < BB; e += COV_THREADS) {
+            const int r = e / NU, c = e - r * NU;
+            const double v = S[c * NU + r];
+            X[r * LDB + c] = v;
+            out[(size_t)n * BB + e] = v;
+        }
+    }
+    const int n0 = a - PB - 1;
+    if (n0 < 0) return;                                      // uniform
+    double pf[NPF];
+    auto fetch = [&](int n) {                                // G_1 .. G_PB of row n (unconditional loads at a clamped index)
+        const double* g = Gb + (size_t)n * COLD + BB;
+#pragma unroll
+        for (int j = 0; j < NPF; j++) { const int e = tid + COV_THREADS * j; pf[j] = g[e < GN ? e : GN - 1]; }
+    };
+    fetch(n0);
+    const int jk = tid / TPB, jt = tid % TPB, jr = 4 * (jt / (NU / 4)), jc = 4 * (jt % (NU / 4));
+    const bool jon = tid < TPB * PB;
+
+    for (int n = n0; n >= 0; n--) {
+#pragma unroll
+        for (int j = 0; j < NPF; j++) {
+            const int e = tid + COV_THREADS * j;
+            if (e < GN) { const int blk = e / BB, r = (e - blk * BB) / NU, c = e % NU; Gs[blk * BLK + r * LDB + c] = pf[j]; }
+        }
+        fetch(n > 0 ? n - 1 : 0);
+        lds_barrier();          // the operands of this row, and the block the row before it left in the ring
+        // ---- part k: G_k^T Sigma(n+k,a)
+        if (jon) {
+            double acc[4][4];
+#pragma unroll
+            for (int x = 0; x < 4; x++)
+#pragma unroll
+                for (int y = 0; y < 4; y++) acc[x][y] = 0.0;
+            const double* G = Gs + jk * BLK + jr;
+            const double* X = Xs + ((n + 1 + jk) % PB) * BLK + jc;
+#pragma unroll 4
+            for (int m = 0; m < NU; m++) {
+                double av[4], bv[4];
+#pragma unroll
+                for (int x = 0; x < 4; x++) av[x] = G[m * LDB + x];
+#pragma unroll
+                for (int y = 0; y < 4; y++) bv[y] = X[m * LDB + y];
+#pragma unroll
+                for (int x = 0; x < 4; x++)
+#pragma unroll
+                    for (int y = 0; y < 4; y++) acc[x][y] = fma(av[x], bv[y], acc[x][y]);
+            }
+            double* P = Ps + jk * BLK + jr * LDB + jc;
+#pragma unroll
+            for (int x = 0; x < 4; x++)
+#pragma unroll
+                for (int y = 0; y < 4; y++) P[x * LDB + y] = acc[x][y];
+        }
+        lds_barrier();          // the parts are complete, and Sigma(n+PB,a) has been read for the last time: row n takes its place in the ring
+        {
+            double* X = Xs + (n % PB) * BLK;
+            double* Og = out + (size_t)n * BB;
+            for (int e = tid; e < BB; e += COV_THREADS) {
+                const int r = e / NU, c = e - r * NU;
+                double s = Ps[r * LDB + c];
+#pragma unroll
+                for (int k = 1; k < PB; k++) s += Ps[k * BLK + r * LDB + c];
+                X[r * LDB + c] = -s;
+                Og[e] = -s;
+            }
+        }
+        // (no barrier here: the next row's operands go to Gs, which nobody reads any more, and its first barrier orders the ring)
     }
 }

@@ -325,6 +325,8 @@ class CheetahEstimator:
     # grf_std [N, 4, 3] (net z, x, y per foot) and tau_cov [N, n_motors, n_motors]; 0.0 where a force is not an unknown of that node
     # uncertainty_rates=True adds RATE_FIELDS (cpe_rate_covariance): du_std, ddu_std [N, 28], velocities_cov / _std [N, L, 3(, 3)], com_cov / _std
     # [N, 3(, 3)], and, aligned with com_vel, com_vel_cov / _std [N-1, 3(, 3)] and speed_std [N-1]
+    # uncertainty_spans adds SPAN_FIELDS (cpe_covariance_columns, span_uncertainty): per span (first, last) the centre of mass's displacement, distance,
+    # mean velocity and mean speed with covariances / standard deviations, and span_positions_displacement_cov / _std [S, L, 3(, 3)]
     uncertainty: Optional[dict] = None
 
     def get_objective_cost(self) -> float:
@@ -579,6 +581,9 @@ def _kin_prepare(est: CheetahEstimator, monocular_constraints: bool, disable_pos
     return q_init, opts, pri
 
 
+SPAN_FIELDS = ("span_frames", "span_seconds", "span_com_displacement", "span_com_displacement_cov", "span_com_displacement_std", "span_distance",
+               "span_distance_std", "span_mean_velocity", "span_mean_velocity_cov", "span_mean_velocity_std", "span_mean_speed", "span_mean_speed_std",
+               "span_positions_displacement_cov", "span_positions_displacement_std")
 RATE_FIELDS = ("du_std", "ddu_std", "velocities_cov", "velocities_std", "com_cov", "com_std", "com_vel_cov", "com_vel_std", "speed_std")
 _RATE_WANT = ("cov_du", "cov_ddu", "cov_vel", "cov_com", "cov_com_vel")
 
@@ -589,14 +594,89 @@ def _check_rates(uncertainty: bool, uncertainty_rates: bool) -> None:
         raise ValueError("uncertainty_rates=True needs uncertainty=True: the rates are propagated from the covariance that keyword computes")
 
 
-def _with_rates(h, cov: dict, q, rates: bool, model_list=None) -> dict:
+def _check_spans(uncertainty: bool, uncertainty_spans) -> None:
+    """uncertainty_spans propagates the covariance uncertainty=True computes: alone it is refused, before anything is looked at"""
+    if uncertainty_spans is not None and not uncertainty:
+        raise ValueError("uncertainty_spans needs uncertainty=True: the spans are propagated from the covariance that keyword computes")
+
+
+def resolve_spans(uncertainty_spans, n_frames: int) -> Optional[List[Tuple[int, int]]]:
+    """the (first, last) frame pairs of a sequence of n_frames frames that uncertainty_spans asks for: None -> None; True -> the whole sequence,
+    (0, n_frames - 1), and no span at all for a one-frame sequence; else pairs relative to the sequence's first frame, negative values counting
+    from its end, each with 0 <= first < last <= n_frames - 1 (ValueError otherwise)"""
+    if uncertainty_spans is None:
+        return None
+    if uncertainty_spans is True:
+        return [(0, n_frames - 1)] if n_frames >= 2 else []
+    out = []
+    for pair in uncertainty_spans:
+        try:
+            first, last = (int(v) for v in pair)
+        except (TypeError, ValueError):
+            raise ValueError(f"uncertainty_spans: {pair!r} is not a (first, last) pair of frames") from None
+        a, b = (first + n_frames if first < 0 else first), (last + n_frames if last < 0 else last)
+        if not 0 <= a < b <= n_frames - 1:
+            raise ValueError(f"uncertainty_spans: ({first}, {last}) does not satisfy 0 <= first < last <= {n_frames - 1} in a sequence of {n_frames} frames")
+        out.append((a, b))
+    return out
+
+
+def span_uncertainty(columns: np.ndarray, anchors, cov_diag: np.ndarray, jac_com: np.ndarray, jac_pos: np.ndarray, com_pos: np.ndarray, spans,
+                     h: float) -> dict:
+    """SPAN_FIELDS of one sequence: the displacement between two distant frames with its first-order covariance ("What is spanned").
+    columns [K, N, 28, 28] with columns[k][n] = Sigma(n, anchors[k]) for n <= anchors[k] (cpe_covariance_columns; every span's last frame is among
+    the anchors), cov_diag [N, 28, 28] = Sigma(n, n), jac_com [N, 3, 28] and jac_pos [N, L, 3, 28] (cpe_rate_covariance), com_pos [N, 3], spans =
+    resolved (first, last) pairs, h = the time step in seconds.  For a span (a, b) and a point with Jacobians P_a, P_b:
+        cov(p_b - p_a) = P_b S_bb P_b^T + P_a S_aa P_a^T - P_b S(b,a) P_a^T - (that)^T
+    Pure numpy; S = 0 spans give arrays of leading size 0."""
+    spans = np.asarray(spans, dtype=np.int64).reshape(-1, 2)
+    S, L = spans.shape[0], jac_pos.shape[1]
+    slot = {int(a): k for k, a in enumerate(np.asarray(anchors).ravel()) if a >= 0}
+    T = lambda M: np.swapaxes(M, -1, -2)
+    std = lambda c: np.sqrt(np.maximum(np.diagonal(c, axis1=-2, axis2=-1), 0.0))
+
+    def displacement_cov(P, a, b):                           # P [N, ..., 3, 28]
+        Pa, Pb = P[a], P[b]
+        X = Pb @ T(columns[slot[b]][a]) @ T(Pa)              # P_b S(b,a) P_a^T, S(b,a) = S(a,b)^T
+        C = Pb @ cov_diag[b] @ T(Pb) + Pa @ cov_diag[a] @ T(Pa) - X - T(X)
+        return 0.5 * (C + T(C))
+
+    seconds = (spans[:, 1] - spans[:, 0]) * float(h)
+    disp = com_pos[spans[:, 1]] - com_pos[spans[:, 0]]
+    dcov, pcov = np.zeros((S, 3, 3)), np.zeros((S, L, 3, 3))
+    for s, (a, b) in enumerate(spans):
+        dcov[s], pcov[s] = displacement_cov(jac_com, a, b), displacement_cov(jac_pos, a, b)
+    vel, vcov = disp / seconds[:, None], dcov / (seconds ** 2)[:, None, None]
+    dist = np.sqrt(np.einsum("si,si->s", disp, disp))
+    return dict(span_frames=spans, span_seconds=seconds, span_com_displacement=disp, span_com_displacement_cov=dcov, span_com_displacement_std=std(dcov),
+                span_distance=dist, span_distance_std=speed_std_of(disp, dcov), span_mean_velocity=vel, span_mean_velocity_cov=vcov,
+                span_mean_velocity_std=std(vcov), span_mean_speed=dist / seconds, span_mean_speed_std=speed_std_of(vel, vcov),
+                span_positions_displacement_cov=pcov, span_positions_displacement_std=std(pcov))
+
+
+def _with_rates(h, cov: dict, q, rates: bool, model_list=None, spans=None) -> dict:
     """a covariance result with, for uncertainty_rates=True, the rate covariances of the same sequences under "rates": ONE cpe_rate_covariance call
-    on the same handle at the same q with that call's cov_diag and cov_off (model_list: the ragged form, lists per sequence)"""
-    if rates:
-        if isinstance(cov["cov_diag"], list):
-            cov["rates"] = h.rate_covariance_ragged_host(q, cov["cov_diag"], cov["cov_off"], model_list, want=_RATE_WANT)
+    on the same handle at the same q with that call's cov_diag and cov_off (model_list: the ragged form, lists per sequence).
+    spans (uncertainty_spans: the resolved spans of every sequence; the covariance call was made with want_L=True): that rate call also returns the
+    point Jacobians, and ONE cpe_covariance_columns call gives the columns of Sigma above the distinct last frames of every sequence's spans -- no
+    anchor for a sequence without a factor.  Both go under "spans"."""
+    want = (_RATE_WANT if rates else ()) + (("jac_pos", "jac_com") if spans is not None else ())
+    ragged = isinstance(cov["cov_diag"], list)
+    if want:
+        if ragged:
+            r = h.rate_covariance_ragged_host(q, cov["cov_diag"], cov["cov_off"], model_list, want=want)
         else:
-            cov["rates"] = h.rate_covariance_host(q, cov["cov_diag"], cov["cov_off"], want=_RATE_WANT)
+            r = h.rate_covariance_host(q, cov["cov_diag"], cov["cov_off"], want=want)
+        if rates:
+            cov["rates"] = r
+    if spans is not None:
+        lasts = [sorted({b for _, b in sp}) if cov["seq_status"][k] == abi.OK else [] for k, sp in enumerate(spans)]
+        anchors = np.full((len(spans), max(1, max(len(a) for a in lasts))), -1, dtype=np.int32)
+        for k, a in enumerate(lasts):
+            anchors[k, :len(a)] = a
+        src = cov["padded"] if ragged else cov
+        cols = h.covariance_columns_host(src["L"], src["cov_diag"], src["cov_off"], anchors, [len(c) for c in cov["cov_diag"]] if ragged else None)
+        cov["spans"] = dict(columns=cols, anchors=anchors, spans=spans, jac_pos=r["jac_pos"], jac_com=r["jac_com"])
     return cov
 
 
@@ -622,9 +702,14 @@ def speed_std_of(com_vel: np.ndarray, com_vel_cov: np.ndarray) -> np.ndarray:
 
 
 def _add_speed_std(est) -> None:
-    """est.uncertainty["speed_std"] once est.com_vel is known (uncertainty_rates=True; nothing otherwise)"""
+    """est.uncertainty["speed_std"] once est.com_vel is known (uncertainty_rates=True; nothing otherwise), and SPAN_FIELDS once est.com_pos is
+    (uncertainty_spans: from what _uncertainty_of left under "_spans", which goes)"""
     if est.uncertainty is not None and "com_vel_cov" in est.uncertainty:
         est.uncertainty["speed_std"] = speed_std_of(est.com_vel, est.uncertainty["com_vel_cov"])
+    sp = None if est.uncertainty is None else est.uncertainty.pop("_spans", None)
+    if sp is not None:
+        est.uncertainty.update(span_uncertainty(sp["columns"], sp["anchors"], est.uncertainty["cov_u"], sp["jac_com"], sp["jac_pos"], est.com_pos,
+                                                sp["spans"], 1.0 / est.scene.fps))
 
 
 def _uncertainty_of(cov: dict, b: int, ridge: float) -> Optional[dict]:
@@ -637,6 +722,10 @@ def _uncertainty_of(cov: dict, b: int, ridge: float) -> Optional[dict]:
                ridge=float(ridge))
     if "rates" in cov:
         unc.update(_rate_fields(cov["rates"], b))
+    if "spans" in cov:                              # (SPAN_FIELDS need the centre of mass: _add_speed_std)
+        sp = cov["spans"]
+        unc["_spans"] = dict(columns=sp["columns"][b], anchors=sp["anchors"][b], spans=sp["spans"][b], jac_pos=np.ascontiguousarray(sp["jac_pos"][b]),
+                             jac_com=np.ascontiguousarray(sp["jac_com"][b]))
     return unc
 
 
@@ -691,14 +780,14 @@ def _kinetic_uncertainty_of(cov: dict, b: int, ridge: float, res: dict) -> Kinet
 
 
 def _kinetic_uncertainty(h, ko: abi.KineticOptions, res: dict, meas: np.ndarray, weight: np.ndarray, stance: np.ndarray, ridge: float,
-                         grf_fixed=None, tau_box=None, grf_box=None, rates: bool = False) -> KineticUncertainty:
+                         grf_fixed=None, tau_box=None, grf_box=None, rates: bool = False, spans=None) -> KineticUncertainty:
     """cpe_covariance_kinetic at the solution res["q"] of a converged physics-based solve, with the solve's own stance, options and variant arrays"""
     if res["stats"][0].status != abi.OK:
         return KineticUncertainty()
     one = lambda a: None if a is None else a[None]
     cov = h.covariance_kinetic_host(res["q"], meas[None], weight[None], stance[None], ko, ridge, grf_fixed=one(grf_fixed), tau_box=one(tau_box),
-                                    grf_box=one(grf_box))
-    return _kinetic_uncertainty_of(_with_rates(h, cov, res["q"], rates), 0, ridge, res)
+                                    grf_box=one(grf_box), want_L=spans is not None)
+    return _kinetic_uncertainty_of(_with_rates(h, cov, res["q"], rates, spans=None if spans is None else [spans]), 0, ridge, res)
 
 
 def _store_kinetic_uncertainty(est: CheetahEstimator, unc: Optional[KineticUncertainty], ok: bool, out_dir: Optional[str],
@@ -767,16 +856,22 @@ def estimate_kinematics(estimator: CheetahEstimator, solver_output: bool = True,
                         pose_model_num_components: int = 5, motion_model_window_size: int = 4,
                         motion_model_sparse_solution: bool = True, out_dir_prefix: Optional[str] = None,
                         q_init: Optional[np.ndarray] = None, options: Optional[abi.Options] = None, uncertainty: bool = False,
-                        uncertainty_ridge: float = 0.0, uncertainty_rates: bool = False) -> bool:
+                        uncertainty_ridge: float = 0.0, uncertainty_rates: bool = False, uncertainty_spans=None) -> bool:
     """Same signature as acinoset_opt.estimate_kinematics (acinoset_opt.py:539-547) plus optional
     keyword arguments.  Returns True when the solve converged (IPOPT `ok`+`optimal` in the reference).
     uncertainty=True: after a converged solve the posterior covariance of the estimate (cpe_covariance at the stored q, damping
     uncertainty_ridge) goes to est.uncertainty and to uncertainty.npz beside fte.pickle; the return value stays that of the solve.
     uncertainty_rates=True (with uncertainty=True): also how well the rates are determined (cpe_rate_covariance on that covariance): du_std, ddu_std
     [N, 28], velocities_cov / _std [N, L, 3(, 3)], com_cov / _std [N, 3(, 3)], com_vel_cov / _std [N-1, 3(, 3)] and speed_std [N-1], both aligned
-    with com_vel (RATE_FIELDS; DESIGN.md 2, "What is propagated")."""
+    with com_vel (RATE_FIELDS; DESIGN.md 2, "What is propagated").
+    uncertainty_spans (with uncertainty=True): True = the whole sequence, or (first, last) frame pairs relative to the sequence's first frame,
+    negative values counting from its end (resolve_spans).  For every span the displacement of the centre of mass, the distance, the mean velocity
+    and the mean speed with their first-order covariances and standard deviations, and the covariance of every marker's displacement (SPAN_FIELDS,
+    span_uncertainty; DESIGN.md 2, "What is spanned"), from the covariance between the two frames (cpe_covariance_columns)."""
     _check_rates(uncertainty, uncertainty_rates)
+    _check_spans(uncertainty, uncertainty_spans)
     est, params, scene, sk = estimator, estimator.params, estimator.scene, estimator.skeleton
+    spans = resolve_spans(uncertainty_spans, params.end_frame - params.start_frame)
     q_init, opts, pri = _kin_prepare(est, monocular_constraints, disable_pose_prior, disable_motion_prior, pose_model_num_components,
                                      motion_model_window_size, motion_model_sparse_solution, q_init, options)
     if uncertainty:
@@ -794,8 +889,9 @@ def estimate_kinematics(estimator: CheetahEstimator, solver_output: bool = True,
         dt = time() - t0
         unc = None
         if uncertainty:
-            cov = h.covariance_host(res["q"], est.meas[None], est.weight[None], uncertainty_ridge) if res["stats"][0].status == abi.OK else None
-            cov = None if cov is None else _with_rates(h, cov, res["q"], uncertainty_rates)
+            cov = h.covariance_host(res["q"], est.meas[None], est.weight[None], uncertainty_ridge, want_L=spans is not None) \
+                if res["stats"][0].status == abi.OK else None
+            cov = None if cov is None else _with_rates(h, cov, res["q"], uncertainty_rates, spans=None if spans is None else [spans])
             unc = (None if cov is None else _uncertainty_of(cov, 0, uncertainty_ridge), uncertainty_ridge)
         return _kin_finish(est, h, res, dt, solver_output, monocular_constraints, out_dir_prefix, uncertainty=unc)
     finally:
@@ -816,7 +912,7 @@ def ragged_group_key(sk: abi.Skeleton, opts: abi.Options, pri: Optional[abi.Prio
 def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_output: bool = False, monocular_constraints: bool = False,
                               disable_pose_prior: bool = False, disable_motion_prior: bool = False, out_dir_prefix: Optional[str] = None,
                               options: Optional[abi.Options] = None, ragged: bool = False, uncertainty: bool = False,
-                              uncertainty_ridge: float = 0.0, uncertainty_rates: bool = False) -> List[bool]:
+                              uncertainty_ridge: float = 0.0, uncertainty_rates: bool = False, uncertainty_spans=None) -> List[bool]:
     """estimate_kinematics for MANY sequences at once: the loop of run_dataset.py:1145-1196 (`for seq in dataset: init_trajectory; estimate_kinematics`)
     as batched launches.  Sequences that share a skeleton, a camera rig, a length and a frame rate go through ONE solver handle and ONE cpe_solve
     call (B = the group's size: the GPU solves thousands of sequences per second batched, one at a time it is latency-bound at 7 - 30 ms each);
@@ -828,16 +924,21 @@ def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_out
     sequence's results are bit-equal to those of ragged=False.
     uncertainty=True: as in estimate_kinematics, one cpe_covariance (ragged: cpe_covariance_ragged) call per group on the group's handle; every
     sequence's est.uncertainty and uncertainty.npz are bit-equal to those of its own estimate_kinematics call.  uncertainty_rates=True: as in
-    estimate_kinematics, one cpe_rate_covariance (ragged: cpe_rate_covariance_ragged) call after each covariance call, with the same bit-equality."""
+    estimate_kinematics, one cpe_rate_covariance (ragged: cpe_rate_covariance_ragged) call after each covariance call, with the same bit-equality.
+    uncertainty_spans: as in estimate_kinematics, resolved for every sequence; one cpe_covariance_columns call per group, same bit-equality."""
     _check_rates(uncertainty, uncertainty_rates)
+    _check_spans(uncertainty, uncertainty_spans)
     ests = list(estimators)
+    spans = [resolve_spans(uncertainty_spans, e.params.end_frame - e.params.start_frame) for e in ests]      # (a bad pair: before any solve)
+    group_spans = lambda idx: None if uncertainty_spans is None else [spans[i] for i in idx]
     out: List[Optional[bool]] = [None] * len(ests)
     groups: Dict[tuple, List[int]] = {}
     prepared = {}
     for i, est in enumerate(ests):
         if est.params.enable_shutter_delay_estimation and est.scene.cam_idx is None:
             out[i] = estimate_kinematics(est, solver_output, monocular_constraints, disable_pose_prior, disable_motion_prior, out_dir_prefix=out_dir_prefix, options=options,
-                                         uncertainty=uncertainty, uncertainty_ridge=uncertainty_ridge, uncertainty_rates=uncertainty_rates)
+                                         uncertainty=uncertainty, uncertainty_ridge=uncertainty_ridge, uncertainty_rates=uncertainty_rates,
+                                         uncertainty_spans=uncertainty_spans)
             continue
         q_init, opts, pri = _kin_prepare(est, monocular_constraints, disable_pose_prior, disable_motion_prior, 5, 4, True, None,
                                          None if options is None else _copy_options(options))
@@ -853,7 +954,7 @@ def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_out
     if ragged:
         for idx in groups.values():
             _solve_ragged_group(ests, idx, prepared, out, solver_output, monocular_constraints, out_dir_prefix,
-                                uncertainty_ridge if uncertainty else None, uncertainty_rates)
+                                uncertainty_ridge if uncertainty else None, uncertainty_rates, group_spans(idx))
         return [bool(v) for v in out]
     for idx in groups.values():
         e0 = ests[idx[0]]
@@ -865,8 +966,9 @@ def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_out
             dt = (time() - t0) / len(idx)                                            # processing_time_s of a sequence: its share of the batched solve
             cov = None
             if uncertainty:
-                cov = h.covariance_host(res["q"], np.stack([ests[i].meas for i in idx]), np.stack([ests[i].weight for i in idx]), uncertainty_ridge)
-                cov = _with_rates(h, cov, res["q"], uncertainty_rates)
+                cov = h.covariance_host(res["q"], np.stack([ests[i].meas for i in idx]), np.stack([ests[i].weight for i in idx]), uncertainty_ridge,
+                                        want_L=uncertainty_spans is not None)
+                cov = _with_rates(h, cov, res["q"], uncertainty_rates, spans=group_spans(idx))
             for b, i in enumerate(idx):
                 one = {k: (v[b:b + 1] if isinstance(v, np.ndarray) else v) for k, v in res.items() if k not in ("stats", "status")}
                 one["stats"] = [res["stats"][b]]; one["status"] = res["stats"][b].status
@@ -883,7 +985,7 @@ def _model_bytes(est: CheetahEstimator, opts: abi.Options) -> bytes:
 
 
 def _solve_ragged_group(ests, idx, prepared, out, solver_output, monocular_constraints, out_dir_prefix, uncertainty_ridge: Optional[float] = None,
-                        uncertainty_rates: bool = False) -> None:
+                        uncertainty_rates: bool = False, spans=None) -> None:
     """estimate_kinematics_batch(ragged=True) for one group: one model per distinct (skeleton, rig, options), one cpe_solve_ragged call, then every
     sequence's centre of mass, costs and files through _kin_finish with a plain handle of its own model (forward kinematics of that skeleton)"""
     models: Dict[bytes, int] = {}
@@ -904,8 +1006,9 @@ def _solve_ragged_group(ests, idx, prepared, out, solver_output, monocular_const
         dt = (time() - t0) / len(idx)                                                # processing_time_s of a sequence: its share of the batched solve
         cov = None
         if uncertainty_ridge is not None:                                            # (uncertainty=True) at the stored q of every sequence, same handle
-            cov = h.covariance_ragged_host(res["q"], [ests[i].meas for i in idx], [ests[i].weight for i in idx], of, uncertainty_ridge)
-            cov = _with_rates(h, cov, res["q"], uncertainty_rates, of)
+            cov = h.covariance_ragged_host(res["q"], [ests[i].meas for i in idx], [ests[i].weight for i in idx], of, uncertainty_ridge,
+                                           want_L=spans is not None)
+            cov = _with_rates(h, cov, res["q"], uncertainty_rates, of, spans)
         for b, i in enumerate(idx):
             one = {k: res[k][b][None] for k in ("q", "dq", "ddq", "positions", "meas_err")}
             one["stats"] = [res["stats"][b]]; one["status"] = res["stats"][b].status
@@ -1101,7 +1204,7 @@ def estimate_kinetics(estimator: CheetahEstimator, init_torques: bool = True, au
                       disable_pose_prior: bool = False, disable_motion_prior: bool = False, plot: bool = False, out_fname: str = "fte",
                       out_dir_prefix: Optional[str] = None, options: Optional[abi.Options] = None,
                       kinetic_options: Optional[abi.KineticOptions] = None, uncertainty: bool = False, uncertainty_ridge: float = 0.0,
-                      uncertainty_rates: bool = False) -> bool:
+                      uncertainty_rates: bool = False, uncertainty_spans=None) -> bool:
     """Same signature and meaning as acinoset_opt.estimate_kinetics (acinoset_opt.py:693-708) for the branch its drivers run for the
     physics-based reconstruction (`joint_estimation=True`, run_dataset.py:1198-1229): torques, joint constraint forces, ground-reaction
     forces and the trajectory are estimated together, warm-started from the kinematic solution on disk, with the contact windows of
@@ -1118,8 +1221,11 @@ def estimate_kinetics(estimator: CheetahEstimator, init_torques: bool = True, au
     q with the solve's stance, options and force profile, damping uncertainty_ridge) goes to est.uncertainty and to uncertainty.npz beside fte.pickle:
     estimate_kinematics' fields plus tau_std, lambda_std, grf_std, tau_cov (force_uncertainty).  A sequence without a factor raises CpeError after the
     solve's own files are written.  Not with use_2d_reprojections=False (the covariance of the 3D kinematic cost is not built).
-    uncertainty_rates=True (with uncertainty=True): the rate fields of estimate_kinematics (RATE_FIELDS), from that covariance."""
+    uncertainty_rates=True (with uncertainty=True): the rate fields of estimate_kinematics (RATE_FIELDS), from that covariance.
+    uncertainty_spans (with uncertainty=True): the span fields of estimate_kinematics (SPAN_FIELDS), from that covariance."""
     _check_rates(uncertainty, uncertainty_rates)
+    _check_spans(uncertainty, uncertainty_spans)
+    spans = resolve_spans(uncertainty_spans, estimator.params.end_frame - estimator.params.start_frame)
     if uncertainty and not use_2d_reprojections:
         raise NotImplementedError("uncertainty together with use_2d_reprojections=False: cpe_covariance_kinetic takes the reprojection cost; the covariance "
                                   "of the 3D kinematic cost (cpe_solve_kinetic_tracked) is not built")
@@ -1140,7 +1246,7 @@ def estimate_kinetics(estimator: CheetahEstimator, init_torques: bool = True, au
                                        grf_fixed=None if gfx is None else gfx[None], grf_box=None if gbx is None else gbx[None])
         dt = time() - t0
         unc = _kinetic_uncertainty(h, prep["ko"], res, est.meas, est.weight, prep["stance"], uncertainty_ridge, grf_fixed=gfx, grf_box=gbx,
-                                   rates=uncertainty_rates) if uncertainty else None
+                                   rates=uncertainty_rates, spans=spans) if uncertainty else None
         return _kinetic_finish(est, h, res, dt, prep, solver_output, out_fname, out_dir_prefix, uncertainty=unc)
     finally:
         h.close()
@@ -1324,7 +1430,7 @@ def estimate_kinetics_batch(estimators: Sequence[CheetahEstimator], init_torques
                             disable_pose_prior: bool = False, disable_motion_prior: bool = False, plot: bool = False, out_fname: str = "fte",
                             out_dir_prefix: Optional[str] = None, options: Optional[abi.Options] = None,
                             kinetic_options: Optional[abi.KineticOptions] = None, ragged: bool = False, uncertainty: bool = False,
-                            uncertainty_ridge: float = 0.0, uncertainty_rates: bool = False) -> List[bool]:
+                            uncertainty_ridge: float = 0.0, uncertainty_rates: bool = False, uncertainty_spans=None) -> List[bool]:
     """estimate_kinetics for MANY sequences at once, with its keyword arguments (applied to every sequence).  Each sequence is prepared as
     estimate_kinetics prepares it (the per-frame force fit of the fix_grf=True, synthesised_grf=False branch included, one sequence at a time),
     then solved in a batch, then gets its centre of mass, costs and files exactly as estimate_kinetics writes them; only processing_time_s (its
@@ -1335,12 +1441,15 @@ def estimate_kinetics_batch(estimators: Sequence[CheetahEstimator], init_torques
     uncertainty=True: as in estimate_kinetics, from ONE covariance call per group on the group's handle over its converged sequences
     (covariance_kinetic_host; ragged: covariance_kinetic_ragged_host); every sequence's est.uncertainty and uncertainty.npz are bit-equal to those of
     its own estimate_kinetics call.  A sequence without a factor does not stop the batch: every sequence is finished and stored first, then ONE
-    CpeError names all of them.  uncertainty_rates=True: as in estimate_kinetics, one rate call after each covariance call, same bit-equality."""
+    CpeError names all of them.  uncertainty_rates=True: as in estimate_kinetics, one rate call after each covariance call, same bit-equality.
+    uncertainty_spans: as in estimate_kinetics, resolved for every sequence; one cpe_covariance_columns call per group, same bit-equality."""
     _check_rates(uncertainty, uncertainty_rates)
+    _check_spans(uncertainty, uncertainty_spans)
     if uncertainty and not use_2d_reprojections:
         raise NotImplementedError("uncertainty together with use_2d_reprojections=False: cpe_covariance_kinetic takes the reprojection cost; the covariance "
                                   "of the 3D kinematic cost (cpe_solve_kinetic_tracked) is not built")
     ests = list(estimators)
+    spans = [resolve_spans(uncertainty_spans, e.params.end_frame - e.params.start_frame) for e in ests]      # (a bad pair: before any solve)
     out: List[Optional[bool]] = [None] * len(ests)
     groups: Dict[tuple, List[int]] = {}
     prepared = {}
@@ -1360,7 +1469,8 @@ def estimate_kinetics_batch(estimators: Sequence[CheetahEstimator], init_torques
     no_factor: List[CheetahEstimator] = []
     for idx in groups.values():
         (_solve_kinetic_ragged_group if ragged else _solve_kinetic_group)(ests, idx, prepared, out, solver_output, out_fname, out_dir_prefix,
-                                                                          uncertainty_ridge if uncertainty else None, no_factor, uncertainty_rates)
+                                                                          uncertainty_ridge if uncertainty else None, no_factor, uncertainty_rates,
+                                                                          None if uncertainty_spans is None else [spans[i] for i in idx])
     if no_factor:
         raise _lib.CpeError(_no_factor_reason(uncertainty_ridge, [f"{e.name} {e.data_path}" for e in no_factor]))
     return [bool(v) for v in out]
@@ -1381,7 +1491,7 @@ def _batch_kinetic_uncertainty(res: dict, idx, ridge: Optional[float], covarianc
 
 
 def _solve_kinetic_group(ests, idx, prepared, out, solver_output, out_fname, out_dir_prefix, uncertainty_ridge: Optional[float] = None,
-                         no_factor: Optional[list] = None, uncertainty_rates: bool = False) -> None:
+                         no_factor: Optional[list] = None, uncertainty_rates: bool = False, spans=None) -> None:
     """estimate_kinetics_batch(ragged=False) for one group: one handle, one solve_kinetic_host call with B = the group's size (and, with
     uncertainty_ridge, one covariance_kinetic_host call)"""
     e0, p0 = ests[idx[0]], prepared[idx[0]]
@@ -1399,7 +1509,8 @@ def _solve_kinetic_group(ests, idx, prepared, out, solver_output, out_fname, out
         cut = lambda a, conv: None if a is None else a[conv]
         unc = _batch_kinetic_uncertainty(res, idx, uncertainty_ridge, lambda conv: _with_rates(h, h.covariance_kinetic_host(
             res["q"][conv], meas[conv], weight[conv], stack("stance")[conv], p0["ko"], uncertainty_ridge, grf_fixed=cut(stack("grf_fixed"), conv),
-            grf_box=cut(stack("grf_box"), conv)), res["q"][conv], uncertainty_rates))
+            grf_box=cut(stack("grf_box"), conv), want_L=spans is not None), res["q"][conv], uncertainty_rates,
+            spans=None if spans is None else [spans[b] for b in conv]))
         for b, i in enumerate(idx):
             out[i] = _kinetic_finish(ests[i], h, _kinetic_one(res, b), dt, prepared[i], solver_output, out_fname, out_dir_prefix, unc.get(b), no_factor)
     finally:
@@ -1407,7 +1518,7 @@ def _solve_kinetic_group(ests, idx, prepared, out, solver_output, out_fname, out
 
 
 def _solve_kinetic_ragged_group(ests, idx, prepared, out, solver_output, out_fname, out_dir_prefix, uncertainty_ridge: Optional[float] = None,
-                                no_factor: Optional[list] = None, uncertainty_rates: bool = False) -> None:
+                                no_factor: Optional[list] = None, uncertainty_rates: bool = False, spans=None) -> None:
     """estimate_kinetics_batch(ragged=True) for one group: one model per distinct (skeleton, rig, options, kinetic options), one
     cpe_solve_kinetic_ragged call (and, with uncertainty_ridge, one cpe_covariance_kinetic_ragged call on the same handle), then every sequence's
     centre of mass, costs and files through _kinetic_finish with a plain handle of its model"""
@@ -1435,7 +1546,8 @@ def _solve_kinetic_ragged_group(ests, idx, prepared, out, solver_output, out_fna
         unc = _batch_kinetic_uncertainty(res, idx, uncertainty_ridge, lambda conv: _with_rates(h, h.covariance_kinetic_ragged_host(
             [res["q"][b] for b in conv], [ests[idx[b]].meas for b in conv], [ests[idx[b]].weight for b in conv],
             [prepared[idx[b]]["stance"] for b in conv], [prepared[i]["ko"] for i in reps], [of[b] for b in conv], uncertainty_ridge,
-            **{k: [v[b] for b in conv] for k, v in fkw.items()}), [res["q"][b] for b in conv], uncertainty_rates, [of[b] for b in conv]))
+            want_L=spans is not None, **{k: [v[b] for b in conv] for k, v in fkw.items()}), [res["q"][b] for b in conv], uncertainty_rates,
+            [of[b] for b in conv], None if spans is None else [spans[b] for b in conv]))
         for b, i in enumerate(idx):
             if of[b] not in fk:
                 r = reps[of[b]]
@@ -1459,7 +1571,7 @@ def bound_value(val, slack_percentage: float) -> np.ndarray:
 
 def estimate_grf(estimator: CheetahEstimator, solver_output: bool = True, out_dir_prefix: Optional[str] = None,
                  options: Optional[abi.Options] = None, kinetic_options: Optional[abi.KineticOptions] = None, uncertainty: bool = False,
-                 uncertainty_ridge: float = 0.0, uncertainty_rates: bool = False) -> bool:
+                 uncertainty_ridge: float = 0.0, uncertainty_rates: bool = False, uncertainty_spans=None) -> bool:
     """Same signature and meaning as the module-level acinoset_opt.estimate_grf (acinoset_opt.py:966-1048), the last stage of the kinetic-dataset
     pipeline (run_dataset.py:1125-1138): the physics-based model is solved again from the stored `fte_kinetic/fte.pickle` -- trajectory as the
     starting point, every torque within 10 % of its stored value (`Tc.bounds = bound_value(init_tau, 0.1)`, :995-1003) -- with the ground-reaction
@@ -1471,9 +1583,12 @@ def estimate_grf(estimator: CheetahEstimator, solver_output: bool = True, out_di
     table (the reference ships `grf/data.h5` at 3.5 kHz, which needs PyTables and a resampling step that are not reproduced here) the same rule is
     applied to it, otherwise the window alone decides (a loaded plate never reads exactly zero).
     uncertainty=True: as in estimate_kinetics, with the torque boxes of this solve; uncertainty.npz goes beside fte_grf/fte.pickle.
-    uncertainty_rates=True (with uncertainty=True): the rate fields of estimate_kinematics (RATE_FIELDS), from that covariance."""
+    uncertainty_rates=True (with uncertainty=True): the rate fields of estimate_kinematics (RATE_FIELDS), from that covariance.
+    uncertainty_spans (with uncertainty=True): the span fields of estimate_kinematics (SPAN_FIELDS), from that covariance."""
     _check_rates(uncertainty, uncertainty_rates)
+    _check_spans(uncertainty, uncertainty_spans)
     est, params, scene, sk = estimator, estimator.params, estimator.scene, estimator.skeleton
+    spans = resolve_spans(uncertainty_spans, params.end_frame - params.start_frame)
     assert params.kinetic_dataset, "Cannot determine GRF on a dataset other than the kinetic dataset from Penny Hudson and Co."
     if est.kinematic_model:
         raise AssertionError("Dynamic model of the cheetah is required.")
@@ -1524,7 +1639,7 @@ def estimate_grf(estimator: CheetahEstimator, solver_output: bool = True, out_di
         res = h.solve_kinetic_host(ko, q_init[None], est.meas[None], est.weight[None], stance[None], tau_box=tau_box[None])
         est.opt_time_s = time() - t0
         if uncertainty:
-            unc = _kinetic_uncertainty(h, ko, res, est.meas, est.weight, stance, uncertainty_ridge, tau_box=tau_box, rates=uncertainty_rates)
+            unc = _kinetic_uncertainty(h, ko, res, est.meas, est.weight, stance, uncertainty_ridge, tau_box=tau_box, rates=uncertainty_rates, spans=spans)
         import torch
         dev = torch.device("cuda", est.device)
         qd = torch.tensor(res["q"], device=dev)

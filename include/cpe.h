@@ -655,6 +655,25 @@ cpe_status cpe_rate_covariance_ragged_host(cpe_handle* h, int32_t B, int32_t N_m
                                            const double* cov_diag, const double* cov_off, double* cov_du, double* cov_ddu, double* cov_vel,
                                            double* cov_com, double* cov_com_vel, double* jac_pos, double* jac_com);
 
+/* ---- covariance between distant frames ("What is spanned"): the blocks Sigma(n, a) of a whole column above an anchor frame a, far
+ * outside the band -- what the error bar of a displacement, a stride length or a mean speed between two frames needs.  L^T Sigma = L^-1 is lower
+ * triangular, so the sweep's recurrence continues upward: Sigma(n, a) = - sum_{k=1..pb} G_k(n)^T Sigma(n+k, a), G_k(n) = L(n+k, n) L(n, n)^-1, for
+ * n = a-pb-1 .. 0, seeded by the band blocks Sigma(a-i, a) = Sigma(a, a-i)^T -- the back substitution of L^T X = Y on the rows where Y = 0.
+ * Device pointers except n_frames and anchors.  L [B][N][pb+1][28][28], cov_diag [B][N][28][28], cov_off [B][N][pb][28][28]: cpe_band_inverse's
+ * layout, pb = the handle's half-bandwidth, from cpe_covariance*, cpe_covariance_kinetic*, cpe_band_inverse or the caller; values are not validated.
+ * n_frames [B] HOST: the length of every sequence, or NULL = all N.  anchors [B][K] HOST: frame indices, -1 = unused slot.
+ * cols [B][K][N][28][28]: block [b][k][n] = Sigma(n, a), a = anchors[b][k], for n <= a; the rows a-pb .. a are bit-copies of the band blocks
+ * (transposed where needed); exactly 0.0 for n > a, for an unused slot and past a sequence's frames.  A sequence all of whose anchors are -1 is not
+ * read at all: the way to skip a sequence for which cpe_covariance found no factor.  Every sum has a fixed order (no atomics): results are
+ * reproducible bit for bit, and a column depends neither on the batch nor on the other anchors of the call.
+ * Refused with CPE_BAD_ARG before the device is touched, the reason in cpe_last_error(): a NULL argument other than n_frames; K < 1; an anchor
+ * outside [-1, n_frames[b]); a frame count outside [0, N]; a half-bandwidth above 4; negative sizes or more than 2^31 - 1 blocks (B N K). */
+cpe_status cpe_covariance_columns(cpe_handle* h, int32_t B, int32_t N, const int32_t* n_frames /*[B] host, or NULL*/, const double* L,
+                                  const double* cov_diag, const double* cov_off, int32_t K, const int32_t* anchors /*[B][K] host*/, double* cols);
+/* host-pointer twin (stages through HBM) */
+cpe_status cpe_covariance_columns_host(cpe_handle* h, int32_t B, int32_t N, const int32_t* n_frames, const double* L, const double* cov_diag,
+                                       const double* cov_off, int32_t K, const int32_t* anchors, double* cols);
+
 /* ---- posterior covariance of the physics-based estimate: coordinates, and the node forces (torques, joint constraint forces, net foot forces)
  * the solve infers ("What is inverted").  Runs the launches of the first pass of cpe_solve_kinetic at Euler q -- cold start, multipliers
  * zero, node forces minimised from a cold start, as cpe_eval_kinetic_system / cpe_eval_lm_step -- at damping `ridge` in place of opts.lambda0, up to

@@ -3,9 +3,11 @@ LM iteration of the same handle, at the two shapes the benchmark solves: phantom
 one camera + the packaged priors, N = 200, B = 2048 (half-bandwidth 4).  The covariance is taken at the synthetic truth with damping --ridge; the LM
 iteration is cpe_eval_lm_step on the same batch at the same damping.  Prints one JSON line per shape: milliseconds of cpe_covariance with every
 output (best of three, host clock around a call that ends in a synchronise), the same without the marker covariance and with the diagonal
-blocks only, the sequences with a factor, and the milliseconds of the LM iteration.  No threshold; the numbers quoted in DESIGN.md section 4.
+blocks only, the sequences with a factor, and the milliseconds of the LM iteration.  With --columns K also cpe_covariance_columns on that
+covariance's factor and band, K anchors per sequence spread from the last frame down (device pointers, timed the same way).  No threshold; the
+numbers quoted in DESIGN.md sections 4 and 6.
 
-    python tools/time_covariance.py [--batch6 B] [--batch1 B] [--N N] [--ridge R]"""
+    python tools/time_covariance.py [--batch6 B] [--batch1 B] [--N N] [--ridge R] [--columns K]"""
 import argparse
 import json
 import os
@@ -26,6 +28,7 @@ def main():
     ap.add_argument("--batch1", type=int, default=2048, help="sequences of the config-3 shape")
     ap.add_argument("--N", type=int, default=200)
     ap.add_argument("--ridge", type=float, default=1e-6)
+    ap.add_argument("--columns", type=int, default=0, help="also time cpe_covariance_columns with this many anchors per sequence")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     N = args.N
@@ -69,9 +72,25 @@ def main():
             h.synchronize()
             dt = 1e3 * (time.perf_counter() - t0)
             ms_lm = dt if ms_lm is None else min(ms_lm, dt)
+        extra = {}
+        if args.columns > 0:
+            K = args.columns
+            Lf, cols = E(B, N, h.pb + 1, 28, 28), E(B, K, N, 28, 28)
+            h.covariance(q, me, we, args.ridge, cd, cov_off=co, L=Lf); h.synchronize()
+            anchors = np.tile(np.array([N - 1 - (k * N) // K for k in range(K)], dtype=np.int32), (B, 1))
+            ms_cols = None
+            for _ in range(4):                                                                       # (the first call is the warm-up)
+                torch.cuda.synchronize(dev)
+                t0 = time.perf_counter()
+                h.covariance_columns(Lf, cd, co, anchors, cols)
+                h.synchronize()
+                dt = 1e3 * (time.perf_counter() - t0)
+                ms_cols = dt if ms_cols is None else min(ms_cols, dt)
+            extra = dict(column_anchors=anchors[0].tolist(), columns_ms=round(ms_cols, 3))
+            del Lf, cols
         print(json.dumps(dict(shape=label, B=B, N=N, half_bandwidth=h.pb, ridge=args.ridge, sequences_with_factor=int(sum(s == abi.OK for s in seq)),
                               covariance_ms=round(ms_all, 3), without_cov_pos_ms=round(ms_nopos, 3), diagonal_only_ms=round(ms_diag, 3),
-                              lm_iteration_ms=round(ms_lm, 3))), flush=True)
+                              lm_iteration_ms=round(ms_lm, 3), **extra)), flush=True)
         h.close()
         del q, me, we, cd, co, cp
         torch.cuda.empty_cache()
