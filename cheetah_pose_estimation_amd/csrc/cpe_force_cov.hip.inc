@@ -19,17 +19,11 @@
 #define FC_DOUBLES (FC_MX + KIN_LS + FC_ZT + FC_CS)
 #define FC_TA (KIN_NA_MAX / 4)            // 4 x 4 tiles along the forces
 #define FC_TV (KIN_NC3 / 4)               // ... along the coordinates
+#define FC_PB 3                           // half-bandwidth of the band k_lm_step<3, 2> factors
 static_assert(KIN_NA_MAX % 4 == 0 && KIN_NC3 % 4 == 0 && FC_TA * FC_TV <= 2 * KIN_THREADS && FC_TA * FC_TA <= KIN_THREADS, "tiling of k_force_cov");
 static_assert(CPE_NX * KIN_NC3 <= FC_CS && KIN_NA_MAX * KIN_MS <= FC_ZT && KIN_NA_MAX <= KIN_LS, "LDS regions of k_force_cov");
 
-// tile t of the lower triangle, rows first: (ti, tj) with tj <= ti
-__device__ __forceinline__ void fc_lower_tile(int t, int& ti, int& tj) {
-    ti = 0;
-    while ((ti + 1) * (ti + 2) / 2 <= t) ti++;
-    tj = t - ti * (ti + 1) / 2;
-}
-
-// cov_diag / cov_off: the band of Sigma as k_lm_selinv wrote it (cov_off block [f][k-1] = Sigma(f + k, f), PB = 3).  cov_f [F][KIN_LS][KIN_LS], f_out
+// cov_diag / cov_off: the band of Sigma as k_lm_selinv wrote it (band_entry, half-bandwidth FC_PB).  cov_f [F][KIN_LS][KIN_LS], f_out
 // [F][KIN_LS] and meta_out [F][KIN_LS + 1] (each may be null): the node's forces and (count, indices of its free forces, zeros, Newton iterations).
 // bad [B]: set to 1 where a node's M has no Cholesky factor (the host clears that sequence's outputs).
 // RAGGED (cpe_covariance_kinetic_ragged): N = rg.nmax; sequence b has its own frame count and its own entry of K, by the table rg.
@@ -59,7 +53,6 @@ __global__ __launch_bounds__(KIN_THREADS, 1) void k_force_cov(const DevKin* __re
     const double* pc = pieces + fo * (size_t)KIN_PIECE;
     const double* Hfu = pc + KIN_NC3 * KIN_NC3; const double* Hff = Hfu + KIN_LS * KIN_NC3;
     double* Mx = smem; double* dg = Mx + FC_MX; double* Zt = dg + KIN_LS; double* Cs = Zt + FC_ZT;
-    constexpr int BB = CPE_NX * CPE_NX;
 
     if (f_out && tid < KIN_LS) f_out[f_ * KIN_LS + tid] = fbuf[fo * KIN_LS + tid];
     if (meta_out && tid <= KIN_LS) meta_out[f_ * (KIN_LS + 1) + tid] = tid <= na || tid == KIN_LS ? pmeta[fo * (KIN_LS + 1) + tid] : 0;
@@ -78,12 +71,7 @@ __global__ __launch_bounds__(KIN_THREADS, 1) void k_force_cov(const DevKin* __re
     // ---- Z = Y W, W streamed in three panels of 28 rows (the frame n - p); two tiles (4 forces x 4 coordinates) per thread, each the whole
     // sum over u = 0 .. 83 in that order
     double z[2][4][4];
-#pragma unroll
-    for (int s = 0; s < 2; s++)
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-            for (int j = 0; j < 4; j++) z[s][i][j] = 0.0;
+    tile4_zero(z[0]); tile4_zero(z[1]);
     int za[2], zv[2]; bool zon[2];
 #pragma unroll
     for (int s = 0; s < 2; s++) {
@@ -91,34 +79,18 @@ __global__ __launch_bounds__(KIN_THREADS, 1) void k_force_cov(const DevKin* __re
         zon[s] = t < nta * FC_TV;
         za[s] = zon[s] ? 4 * (t / FC_TV) : 0; zv[s] = zon[s] ? 4 * (t % FC_TV) : 0;
     }
+    const double* cd = cov_diag + (size_t)b * N * (CPE_NX * CPE_NX);                  // the sequence's band
+    const double* co = cov_off + (size_t)b * N * (FC_PB * CPE_NX * CPE_NX);
     for (int p = 0; p < 3; p++) {
-        // W[28 p + i][28 q + j] = Sigma(n - p, n - q)[i][j]: the block of (later frame, earlier frame) as it stands, or transposed
+        // W[28 p + i][28 q + j] = Sigma(n - p, n - q)[i][j]
         for (int t = tid; t < CPE_NX * KIN_NC3; t += KIN_THREADS) {
             const int i = t / KIN_NC3, v = t - i * KIN_NC3, q = v / CPE_NX, j = v - q * CPE_NX;
-            double w;
-            if (q == p) w = cov_diag[(f_ - p) * BB + i * CPE_NX + j];
-            else if (p < q) w = cov_off[((f_ - q) * 3 + (q - p - 1)) * BB + i * CPE_NX + j];
-            else w = cov_off[((f_ - p) * 3 + (p - q - 1)) * BB + j * CPE_NX + i];
-            Cs[t] = w;
+            Cs[t] = band_entry(cd, co, FC_PB, n - p, n - q, i, j);
         }
         __syncthreads();
 #pragma unroll
-        for (int s = 0; s < 2; s++) {
-            const double* Y = Yt + (size_t)(CPE_NX * p) * KIN_MS + za[s];
-            const double* W = Cs + zv[s];
-#pragma unroll 4
-            for (int r = 0; r < CPE_NX; r++) {
-                double x[4], y[4];
-#pragma unroll
-                for (int i = 0; i < 4; i++) x[i] = Y[r * KIN_MS + i];
-#pragma unroll
-                for (int j = 0; j < 4; j++) y[j] = W[r * KIN_NC3 + j];
-#pragma unroll
-                for (int i = 0; i < 4; i++)
-#pragma unroll
-                    for (int j = 0; j < 4; j++) z[s][i][j] = fma(x[i], y[j], z[s][i][j]);
-            }
-        }
+        for (int s = 0; s < 2; s++)
+            tile4_fma<false, 4>(z[s], Yt + (size_t)(CPE_NX * p) * KIN_MS + za[s], 1, KIN_MS, Cs + zv[s], KIN_NC3, 0, CPE_NX);
         __syncthreads();
     }
 #pragma unroll
@@ -133,23 +105,13 @@ __global__ __launch_bounds__(KIN_THREADS, 1) void k_force_cov(const DevKin* __re
 
     // ---- C = I + Z Y^T on the tiles of the lower triangle, mirrored (rows and columns past na: zero)
     if (tid < nta * (nta + 1) / 2) {
-        int ti, tj; fc_lower_tile(tid, ti, tj);
+        int ti, tj; lower_tile(tid, ti, tj);
         double c[4][4];
 #pragma unroll
         for (int i = 0; i < 4; i++)
 #pragma unroll
             for (int j = 0; j < 4; j++) c[i][j] = ti == tj && i == j && 4 * ti + i < na ? 1.0 : 0.0;
-        const double* Zp = Zt + 4 * ti; const double* Yp = Yt + 4 * tj;
-#pragma unroll 4
-        for (int v = 0; v < KIN_NC3; v++) {
-            double x[4], y[4];
-#pragma unroll
-            for (int i = 0; i < 4; i++) { x[i] = Zp[v * KIN_MS + i]; y[i] = Yp[v * KIN_MS + i]; }
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-#pragma unroll
-                for (int j = 0; j < 4; j++) c[i][j] = fma(x[i], y[j], c[i][j]);
-        }
+        tile4_fma<false, 4>(c, Zt + 4 * ti, 1, KIN_MS, Yt + 4 * tj, KIN_MS, 0, KIN_NC3);
 #pragma unroll
         for (int i = 0; i < 4; i++)
 #pragma unroll
@@ -177,45 +139,18 @@ __global__ __launch_bounds__(KIN_THREADS, 1) void k_force_cov(const DevKin* __re
     if (tid < nta * nta) {
         const int ti = tid / nta, tj = tid - ti * nta;
         double c[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-            for (int j = 0; j < 4; j++) c[i][j] = 0.0;
-        const double* Cp = Cs + (4 * ti) * KIN_MS; const double* Tp = Ti + 4 * tj;
-        for (int k = 4 * tj; k < na; k++) {
-            double x[4], y[4];
-#pragma unroll
-            for (int i = 0; i < 4; i++) { x[i] = Cp[i * KIN_MS + k]; y[i] = Tp[k * KIN_MS + i]; }
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-#pragma unroll
-                for (int j = 0; j < 4; j++) c[i][j] = fma(x[i], y[j], c[i][j]);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-            for (int j = 0; j < 4; j++) Ps[(4 * ti + i) * KIN_MS + 4 * tj + j] = c[i][j];
+        tile4_zero(c);
+        tile4_fma<false, 0>(c, Cs + (4 * ti) * KIN_MS, KIN_MS, 1, Ti + 4 * tj, KIN_MS, 4 * tj, na);
+        tile4_store(c, Ps + (4 * ti) * KIN_MS + 4 * tj, KIN_MS);
     }
     __syncthreads();
 
     // ---- cov_f = T^T P on the tiles of the lower triangle (T[k][a] = 0 for k < a), stored with the mirror
     if (tid < nta * (nta + 1) / 2) {
-        int ti, tj; fc_lower_tile(tid, ti, tj);
+        int ti, tj; lower_tile(tid, ti, tj);
         double c[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-            for (int j = 0; j < 4; j++) c[i][j] = 0.0;
-        const double* Tp = Ti + 4 * ti; const double* Pp = Ps + 4 * tj;
-        for (int k = 4 * ti; k < na; k++) {
-            double x[4], y[4];
-#pragma unroll
-            for (int i = 0; i < 4; i++) { x[i] = Tp[k * KIN_MS + i]; y[i] = Pp[k * KIN_MS + i]; }
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-#pragma unroll
-                for (int j = 0; j < 4; j++) c[i][j] = fma(x[i], y[j], c[i][j]);
-        }
+        tile4_zero(c);
+        tile4_fma<false, 0>(c, Ti + 4 * ti, 1, KIN_MS, Ps + 4 * tj, KIN_MS, 4 * ti, na);
         double* O = cov_f + f_ * (size_t)(KIN_LS * KIN_LS);
 #pragma unroll
         for (int i = 0; i < 4; i++)

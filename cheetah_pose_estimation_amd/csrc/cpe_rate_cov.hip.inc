@@ -1,7 +1,7 @@
 // cpe_rate_cov.hip.inc -- posterior covariance of the rates (include/cpe.h, cpe_rate_covariance; DESIGN.md 2 "What is propagated").
 // A rate is a fixed linear stencil over at most three consecutive frames, rate = sum_i c_i u_{f_i}, so its covariance is
 //     sum_i sum_j c_i c_j Sigma(f_i, f_j),
-// every block inside the band cpe_band_inverse writes (cov_diag, cov_off; Sigma(a,b) = Sigma(b,a)^T for a < b).  A point p(u) -- a marker, the
+// every block inside the band cpe_band_inverse writes (cov_diag, cov_off: band_entry).  A point p(u) -- a marker, the
 // centre of mass -- moves by P = d p / d u to first order: cov p = P Sigma(n,n) P^T, and the velocity (p(u_n) - p(u_{n-1})) / h has
 //     (P_n S_nn P_n^T + P_{n-1} S_{n-1,n-1} P_{n-1}^T - P_n S_{n,n-1} P_{n-1}^T - (that)^T) / h^2.
 // Two kernels, one wave per frame: k_point_jac (P of every marker and of the centre of mass, dense) and k_rate_cov (the five covariances).
@@ -12,44 +12,6 @@
 #define PJ_ITEMS (CPE_MAX_MARKERS * CPE_MAX_MCOL)
 #define PJ_LDS_DOUBLES (CPE_MAX_NQ + CPE_MAX_JOINTS + 6 * CPE_MAX_LINKS + 2 * CPE_MAX_JOINTS + 36 * CPE_MAX_LINKS + 3 * CPE_MAX_SDYN + \
                         CPE_MAX_SCOL * CPE_MAX_DEP + 3 * PJ_ITEMS + PJ_ITEMS / 2)
-
-// Reduced columns Dp of the points of model X (its markers) at the state whose sin / cos, trunk rotations and S rows are in LDS: the dynamic
-// vectors of X's leg chains, then the terms of every (point, column) item summed in list order, one lane per item -- k_marker_cov's sums.
-__device__ __forceinline__ void wave_point_columns(const DevModel* __restrict__ X, const double* ssa, const double* sR, const double* sSv,
-                                                   double* sdyn, double* sDp, int* sBeg, int lane) {
-    const int svn = X->sv_n, mct = X->mc_total, ntl = X->tl_n;
-    const int fww = X->fn_lane[lane][3];
-    const int svl = lane < CPE_MAX_SDYN ? lane : 0;
-    double svv[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; i++) { svv[i][0] = X->sv_vec[svl][i][0]; svv[i][1] = X->sv_vec[svl][i][1]; svv[i][2] = X->sv_vec[svl][i][2]; }
-    wave_leg_vectors(ssa, sdyn, svn, fww, svv, lane);
-    for (int t = lane; t < mct; t += WAVE) sBeg[t] = ntl;
-    wave_lds_sync();
-    for (int e = lane; e < ntl; e += WAVE) {
-        const int it = X->tl[e].w0 & 1023;
-        if (e == 0 || (X->tl[e - 1].w0 & 1023) != it) sBeg[it] = e;
-    }
-    wave_lds_sync();
-    for (int t = lane; t < mct; t += WAVE) {
-        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-        for (int e = sBeg[t]; e < ntl; e++) {
-            const int w0 = X->tl[e].w0;
-            if ((w0 & 1023) != t) break;
-            const int si = ((w0 >> 10) & 1023) - 1, vd = ((w0 >> 20) & 1023) - 1, moff = X->tl[e].moff;
-            const double v0 = vd < 0 ? X->tl[e].v[0] : sdyn[3 * vd], v1 = vd < 0 ? X->tl[e].v[1] : sdyn[3 * vd + 1], v2 = vd < 0 ? X->tl[e].v[2] : sdyn[3 * vd + 2];
-            const double z = si < 0 ? 1.0 : sSv[si];
-            double p0 = v0, p1 = v1, p2 = v2;
-            if (moff >= 0) {
-                const double* D = sR + moff;
-                p0 = D[0] * v0 + D[1] * v1 + D[2] * v2; p1 = D[3] * v0 + D[4] * v1 + D[5] * v2; p2 = D[6] * v0 + D[7] * v1 + D[8] * v2;
-            }
-            s0 += z * p0; s1 += z * p1; s2 += z * p2;
-        }
-        sDp[3 * t] = s0; sDp[3 * t + 1] = s1; sDp[3 * t + 2] = s2;
-    }
-    wave_lds_sync();
-}
 
 // ---- Jacobians, one wave per frame.  M: the handle's models; Mc: the same skeletons with the link centres as markers (marker i = centre of mass
 // of link i).  State: buffer 0 of the workspace as k_state_init wrote it.  jac_pos [F][L][3][28] and jac_com [F][3][28] arrive zeroed: only the
@@ -116,29 +78,28 @@ __global__ __launch_bounds__(WAVE) void k_point_jac(const DevModel* __restrict__
 
 // ---- stencils.  velocity row n of a sequence of NL frames: (u_n - u_{n-1}) / h; row 0 repeats k_finalize's gauge, (-2 u_0 + 3 u_1 - u_2) / h
 // (NL >= 3), (u_1 - u_0) / h (NL == 2), nothing (NL == 1).  acceleration row n: (u_m - 2 u_{m-1} + u_{m-2}) / h^2 at m = max(n, 2), nothing
-// for NL < 3.  Frames ascending; a coefficient is k / h or k / (h h) with k a small integer.
-struct RateStencil { int m; int f[3]; double c[3]; };
+// for NL < 3.  The m frames are consecutive, f0 .. f0 + m - 1; a coefficient is k / h or k / (h h) with k a small integer.
+struct RateStencil { int m; int f0; double c[3]; };
 __device__ __forceinline__ RateStencil velocity_stencil(int NL, int n, double h) {
     RateStencil s;
-    s.m = 0; s.f[0] = s.f[1] = s.f[2] = 0; s.c[0] = s.c[1] = s.c[2] = 0.0;
-    if (n >= 1) { s.m = 2; s.f[0] = n - 1; s.f[1] = n; s.c[0] = -1.0 / h; s.c[1] = 1.0 / h; }
-    else if (NL >= 3) { s.m = 3; s.f[0] = 0; s.f[1] = 1; s.f[2] = 2; s.c[0] = -2.0 / h; s.c[1] = 3.0 / h; s.c[2] = -1.0 / h; }
-    else if (NL == 2) { s.m = 2; s.f[0] = 0; s.f[1] = 1; s.c[0] = -1.0 / h; s.c[1] = 1.0 / h; }
+    s.m = 0; s.f0 = 0; s.c[0] = s.c[1] = s.c[2] = 0.0;
+    if (n >= 1) { s.m = 2; s.f0 = n - 1; s.c[0] = -1.0 / h; s.c[1] = 1.0 / h; }
+    else if (NL >= 3) { s.m = 3; s.c[0] = -2.0 / h; s.c[1] = 3.0 / h; s.c[2] = -1.0 / h; }
+    else if (NL == 2) { s.m = 2; s.c[0] = -1.0 / h; s.c[1] = 1.0 / h; }
     return s;
 }
 __device__ __forceinline__ RateStencil acceleration_stencil(int NL, int n, double h) {
     RateStencil s;
-    s.m = 0; s.f[0] = s.f[1] = s.f[2] = 0; s.c[0] = s.c[1] = s.c[2] = 0.0;
+    s.m = 0; s.f0 = 0; s.c[0] = s.c[1] = s.c[2] = 0.0;
     if (NL >= 3) {
-        const int m = n > 2 ? n : 2;
         const double h2 = h * h;
-        s.m = 3; s.f[0] = m - 2; s.f[1] = m - 1; s.f[2] = m; s.c[0] = 1.0 / h2; s.c[1] = -2.0 / h2; s.c[2] = 1.0 / h2;
+        s.m = 3; s.f0 = (n > 2 ? n : 2) - 2; s.c[0] = 1.0 / h2; s.c[1] = -2.0 / h2; s.c[2] = 1.0 / h2;
     }
     return s;
 }
 
-// out [28][28] = sum_i sum_j (c_i c_j) Sigma(f_i, f_j), i outer, j inner, straight from the band in HBM (every entry is read once or twice);
-// cd / co: the sequence's cov_diag / cov_off.  Lower triangle, mirrored.
+// out [28][28] = sum_i sum_j (c_i c_j) Sigma(f_i, f_j), i outer, j inner, straight from the band in HBM (band_entry; every entry is read once or
+// twice).  Lower triangle, mirrored.
 __device__ __forceinline__ void wave_stencil_cov(const RateStencil& s, const double* __restrict__ cd, const double* __restrict__ co, int pb,
                                                  double* __restrict__ out, int lane) {
     constexpr int BB = NU * NU;
@@ -151,12 +112,7 @@ __device__ __forceinline__ void wave_stencil_cov(const RateStencil& s, const dou
 #pragma unroll
             for (int j = 0; j < 3; j++) {
                 if (i >= s.m || j >= s.m) continue;
-                const int fi = s.f[i], fj = s.f[j];
-                double v;
-                if (i == j) v = cd[(size_t)fi * BB + a * NU + c];
-                else if (i > j) v = co[((size_t)fj * pb + (fi - fj - 1)) * BB + a * NU + c];
-                else v = co[((size_t)fi * pb + (fj - fi - 1)) * BB + c * NU + a];
-                acc = fma(s.c[i] * s.c[j], v, acc);
+                acc = fma(s.c[i] * s.c[j], band_entry(cd, co, pb, s.f0 + i, s.f0 + j, a, c), acc);
             }
         out[a * NU + c] = acc; out[c * NU + a] = acc;
     }
@@ -206,8 +162,9 @@ __global__ __launch_bounds__(WAVE) void k_rate_cov(const DevModel* __restrict__ 
     double* sQc = sPc + PW;            // Pc_{n-1}
     const bool vel = n >= 1;           // uniform
     for (int t = lane; t < BB; t += WAVE) {
-        sA[t] = cd[(size_t)n * BB + t];
-        if (vel) { sB[t] = cd[(size_t)(n - 1) * BB + t]; sX[t] = co[(size_t)(n - 1) * pb * BB + t]; }
+        const int r = t / NU, c = t - r * NU;
+        sA[t] = band_entry(cd, co, pb, n, n, r, c);
+        if (vel) { sB[t] = band_entry(cd, co, pb, n - 1, n - 1, r, c); sX[t] = band_entry(cd, co, pb, n, n - 1, r, c); }
     }
     if (cov_vel && vel)
         for (int t = lane; t < PW * L; t += WAVE) { sP[t] = jp[f * (size_t)(PW * L) + t]; sQ[t] = jp[(f - 1) * (size_t)(PW * L) + t]; }
@@ -218,8 +175,8 @@ __global__ __launch_bounds__(WAVE) void k_rate_cov(const DevModel* __restrict__ 
     // lane = (point, entry of the lower triangle); the mirror is stored with it
     if (cov_vel && vel)
         for (int t = lane; t < 6 * L; t += WAVE) {
-            const int l = t / 6, e = t - 6 * l;
-            const int a = e < 1 ? 0 : (e < 3 ? 1 : 2), c = e - a * (a + 1) / 2;
+            const int l = t / 6;
+            int a, c; lower_entry3(t - 6 * l, a, c);
             const int32_t* cols = M->mcol[l];
             const int nc = M->mcol_n[l];
             const double *Pa = sP + (l * 3 + a) * NU, *Pc = sP + (l * 3 + c) * NU, *Qa = sQ + (l * 3 + a) * NU, *Qc = sQ + (l * 3 + c) * NU;
@@ -230,8 +187,7 @@ __global__ __launch_bounds__(WAVE) void k_rate_cov(const DevModel* __restrict__ 
             o[3 * a + c] = v; o[3 * c + a] = v;
         }
     if (lane < 6) {
-        const int e = lane;
-        const int a = e < 1 ? 0 : (e < 3 ? 1 : 2), c = e - a * (a + 1) / 2;
+        int a, c; lower_entry3(lane, a, c);
         const double *Pa = sPc + a * NU, *Pc = sPc + c * NU, *Qa = sQc + a * NU, *Qc = sQc + c * NU;
         if (cov_com || (cov_com_vel && vel)) {
             const double t1 = quad_form(sA, Pa, Pc, nullptr, NU);

@@ -4,10 +4,11 @@ one camera + the packaged priors, N = 200, B = 2048 (half-bandwidth 4).  The cov
 iteration is cpe_eval_lm_step on the same batch at the same damping.  Prints one JSON line per shape: milliseconds of cpe_covariance with every
 output (best of three, host clock around a call that ends in a synchronise), the same without the marker covariance and with the diagonal
 blocks only, the sequences with a factor, and the milliseconds of the LM iteration.  With --columns K also cpe_covariance_columns on that
-covariance's factor and band, K anchors per sequence spread from the last frame down (device pointers, timed the same way).  No threshold; the
-numbers quoted in DESIGN.md sections 4 and 6.
+covariance's factor and band, K anchors per sequence spread from the last frame down (device pointers, timed the same way).  With --rates also
+cpe_rate_covariance with all seven outputs on the band just computed (k_point_jac and k_rate_cov; device pointers, timed the same way).  No
+threshold; the numbers quoted in DESIGN.md sections 4 and 6.
 
-    python tools/time_covariance.py [--batch6 B] [--batch1 B] [--N N] [--ridge R] [--columns K]"""
+    python tools/time_covariance.py [--batch6 B] [--batch1 B] [--N N] [--ridge R] [--columns K] [--rates]"""
 import argparse
 import json
 import os
@@ -29,6 +30,7 @@ def main():
     ap.add_argument("--N", type=int, default=200)
     ap.add_argument("--ridge", type=float, default=1e-6)
     ap.add_argument("--columns", type=int, default=0, help="also time cpe_covariance_columns with this many anchors per sequence")
+    ap.add_argument("--rates", action="store_true", help="also time cpe_rate_covariance with all seven outputs")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     N = args.N
@@ -88,6 +90,21 @@ def main():
                 ms_cols = dt if ms_cols is None else min(ms_cols, dt)
             extra = dict(column_anchors=anchors[0].tolist(), columns_ms=round(ms_cols, 3))
             del Lf, cols
+        if args.rates:
+            L = sk.n_markers
+            h.covariance(q, me, we, args.ridge, cd, cov_off=co); h.synchronize()                     # the band the rates are taken on
+            outs = dict(cov_du=E(B, N, 28, 28), cov_ddu=E(B, N, 28, 28), cov_vel=E(B, N, L, 3, 3), cov_com=E(B, N, 3, 3), cov_com_vel=E(B, N, 3, 3),
+                        jac_pos=E(B, N, L, 3, 28), jac_com=E(B, N, 3, 28))
+            ms_rates = None
+            for _ in range(4):                                                                       # (the first call is the warm-up)
+                torch.cuda.synchronize(dev)
+                t0 = time.perf_counter()
+                h.rate_covariance(q, cd, co, **outs)
+                h.synchronize()
+                dt = 1e3 * (time.perf_counter() - t0)
+                ms_rates = dt if ms_rates is None else min(ms_rates, dt)
+            extra.update(rates_ms=round(ms_rates, 3))
+            del outs
         print(json.dumps(dict(shape=label, B=B, N=N, half_bandwidth=h.pb, ridge=args.ridge, sequences_with_factor=int(sum(s == abi.OK for s in seq)),
                               covariance_ms=round(ms_all, 3), without_cov_pos_ms=round(ms_nopos, 3), diagonal_only_ms=round(ms_diag, 3),
                               lm_iteration_ms=round(ms_lm, 3), **extra)), flush=True)
