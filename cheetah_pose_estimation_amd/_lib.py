@@ -157,6 +157,17 @@ def pad_kinetic_tracked(q_init_list, q_target_list, stance_list, meas_list=None,
     return pad_kinetic(q_init_list, meas_list, weight_list, stance_list, force_list, n_cams_max, q_target_list)
 
 
+def pad_track_W(track_W_list, lens=None) -> np.ndarray:
+    """The track_W of cpe_solve_kinetic_tracked_weighted_ragged_host from per-sequence arrays [N_b, NX, NX]: zero-padded [B, N_max, NX, NX] float64
+    (lens: the frame counts they must have, e.g. pad_kinetic_tracked's; None = their own).  Pure numpy."""
+    arrs = [np.asarray(w, dtype=np.float64) for w in track_W_list]
+    if any(w.ndim != 3 or w.shape[1:] != (abi.NX, abi.NX) for w in arrs):
+        raise ValueError(f"pad_track_W: every track_W is [N_b, {abi.NX}, {abi.NX}]")
+    if lens is not None and [w.shape[0] for w in arrs] != [int(n) for n in lens]:
+        raise ValueError("pad_track_W: every track_W has its q_init's frames")
+    return _pad(arrs, max([w.shape[0] for w in arrs], default=0), (abi.NX, abi.NX))
+
+
 def track_weights(track_w, rows: int) -> np.ndarray:
     """[rows, NX] float64 weights of the 3D kinematic cost: None = the reference's (abi.default_track_weights) for every row, one NX vector =
     the same for every row, or one row per model"""
@@ -616,8 +627,110 @@ class Handle:
         res.update(status=st, stats=list(stats)[:B], kstats=list(ks)[:B], padded=out)
         return res
 
-    def eval_normal_tracked(self, q, q_target, g, Bm, cost, track_w=None, gam=None, q_out=None):
-        """cpe_eval_normal_tracked on device tensors: the per-frame terms of the tracked solve (T_n, bounds, pose prior) at Euler q"""
+    # ---- the 3D kinematic cost with the kinematic posterior as its weights (estimate_kinetics(track_weights="posterior"); include/cpe.h) --------
+    def track_precision(self, cov_diag, W, scale=1.0, model=None, n_frames=None):
+        """cpe_track_precision on device tensors: W [B, N, NX, NX] = (scale / 2) (X Sigma X^T)^-1 of every frame's block of cov_diag [B, N, NX, NX];
+        model / n_frames: int sequences of a ragged batch (frames past a sequence's own are not written), or None.  A block without a Cholesky
+        factor raises CpeError naming the sequence and the frame (its W is zero, the others are written)."""
+        B, N = cov_diag.shape[0], cov_diag.shape[1]
+        if (model is None) != (n_frames is None):
+            raise ValueError("track_precision: model and n_frames are given together or not at all")
+        mo = nf = None
+        if model is not None:
+            if len(model) != B or len(n_frames) != B:
+                raise ValueError("track_precision: one model index and one frame count per sequence")
+            mo, nf = (C.c_int32 * max(B, 1))(*[int(m) for m in model]), (C.c_int32 * max(B, 1))(*[int(n) for n in n_frames])
+        self._call(self.lib.cpe_track_precision, "cpe_track_precision", B, N, mo, nf, _ptr(cov_diag), float(scale), _ptr(W))
+
+    def track_precision_host(self, cov_diag, scale=1.0, model_list=None):
+        """cpe_track_precision_host: cov_diag [B, N, NX, NX] numpy -> W [B, N, NX, NX]; or, for sequences of their own length (and model,
+        model_list; None = model 0), a list of [N_b, NX, NX] -> a list of W [N_b, NX, NX] from ONE call.  Raises CpeError as track_precision."""
+        ragged = isinstance(cov_diag, (list, tuple))
+        if ragged:
+            lens = [int(np.shape(c)[0]) for c in cov_diag]
+            models = [0] * len(lens) if model_list is None else [int(m) for m in model_list]
+            if len(models) != len(lens):
+                raise ValueError("track_precision_host: one model index per sequence")
+            cd = pad_track_W(cov_diag)
+            mo, nf = (C.c_int32 * max(len(lens), 1))(*models), (C.c_int32 * max(len(lens), 1))(*lens)
+        else:
+            cd = np.ascontiguousarray(cov_diag, dtype=np.float64)
+            if cd.ndim != 4 or cd.shape[2:] != (abi.NX, abi.NX):
+                raise ValueError(f"track_precision_host: cov_diag is [B, N, {abi.NX}, {abi.NX}]")
+            mo = nf = None
+        W = np.zeros_like(cd)
+        st = self.lib.cpe_track_precision_host(self._h, cd.shape[0], cd.shape[1], mo, nf, _ptr(cd), float(scale), _ptr(W))
+        _check(st, "cpe_track_precision_host")
+        return [np.ascontiguousarray(W[b, :n]) for b, n in enumerate(lens)] if ragged else W
+
+    def solve_kinetic_tracked_weighted(self, kopts, track_W, q_init, q_target, stance, q, dq, ddq, positions, meas=None, weight=None, meas_err=None,
+                                       tau=None, lam=None, grf=None, slack=None, grf_fixed=None, tau_box=None, grf_box=None):
+        """cpe_solve_kinetic_tracked_weighted on device tensors: solve_kinetic_tracked with track_W [B, N, NX, NX] (symmetric, positive
+        semi-definite: the caller's contract) in place of track_w.  Returns (status, [Stats], [KineticStats])"""
+        _force_variant("solve_kinetic_tracked_weighted", grf_fixed, tau_box, grf_box)
+        B, N = q_init.shape[0], q_init.shape[1]
+        stats = (abi.Stats * max(B, 1))(); ks = (abi.KineticStats * max(B, 1))()
+        st = self._call(self.lib.cpe_solve_kinetic_tracked_weighted, "cpe_solve_kinetic_tracked_weighted", C.byref(kopts), _ptr(track_W), B, N, _ptr(q_init),
+                        _ptr(q_target), _ptr(meas), _ptr(weight), _ptr(stance), _ptr(grf_fixed), _ptr(tau_box), _ptr(grf_box), _ptr(q), _ptr(dq), _ptr(ddq),
+                        _ptr(positions), _ptr(meas_err), _ptr(tau), _ptr(lam), _ptr(grf), _ptr(slack), stats, ks, allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
+        return st, list(stats)[:B], list(ks)[:B]
+
+    def solve_kinetic_tracked_weighted_host(self, kopts, track_W, q_init, q_target, stance, meas=None, weight=None, grf_fixed=None, tau_box=None,
+                                            grf_box=None):
+        """cpe_solve_kinetic_tracked_weighted_host: numpy in, numpy out -- solve_kinetic_tracked_host's arguments and dict with track_W
+        [B, N, NX, NX] in place of track_w"""
+        who = "solve_kinetic_tracked_weighted_host"
+        variant, force = _force_variant(who, grf_fixed, tau_box, grf_box)
+        if (meas is None) != (weight is None):
+            raise ValueError(f"{who}: meas and weight are given together or not at all")
+        f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+        qi, qt, me, we, fx, W = f64(q_init), f64(q_target), f64(meas), f64(weight), f64(force), f64(track_W)
+        stn = np.ascontiguousarray(stance, dtype=np.int32)
+        B, N = qi.shape[0], qi.shape[1]
+        if qt is not None and qt.shape != qi.shape:
+            raise ValueError(f"{who}: q_target has q_init's shape")
+        if W is not None and W.shape != (B, N, abi.NX, abi.NX):
+            raise ValueError(f"{who}: track_W is [B, N, {abi.NX}, {abi.NX}]")
+        out = self._solve_outputs(B, N, kopts, meas_err=me is not None)
+        stats = (abi.Stats * max(B, 1))(); ks = (abi.KineticStats * max(B, 1))()
+        st = self.lib.cpe_solve_kinetic_tracked_weighted_host(self._h, C.byref(kopts), _ptr(W), B, N, _ptr(qi), _ptr(qt), _ptr(me), _ptr(we), stn.ctypes.data,
+                                                              *_force_slots(variant, fx), *[_ptr(out[k]) for k in KINETIC_OUTPUTS], stats, ks)
+        _check(st, "cpe_solve_kinetic_tracked_weighted_host", allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
+        out.update(status=st, stats=list(stats)[:B], kstats=list(ks)[:B])
+        return out
+
+    def solve_kinetic_tracked_weighted_ragged_host(self, kopts_list, track_W_list, q_init_list, q_target_list, stance_list, meas_list=None,
+                                                   weight_list=None, model_list=None, grf_fixed=None, tau_box=None, grf_box=None):
+        """cpe_solve_kinetic_tracked_weighted_ragged_host: solve_kinetic_tracked_ragged_host's arguments and result with one track_W
+        [N_b, NX, NX] per sequence in place of track_w"""
+        who = "solve_kinetic_tracked_weighted_ragged_host"
+        variant, force = _force_variant(who, grf_fixed, tau_box, grf_box)
+        p = self._ragged_batch(who, "one q_init, q_target, track_W, stance, model (and meas, weight, force array)", model_list, kopts_list, variant,
+                               q_init=q_init_list, q_target=q_target_list, stance=stance_list, meas=meas_list, weight=weight_list, force=force)
+        if len(track_W_list) != len(p["lens"]):
+            raise ValueError(f"{who}: one q_init, q_target, track_W, stance, model (and meas, weight, force array) per sequence")
+        W = pad_track_W(track_W_list, p["lens"])
+        B, Nm = p["q_init"].shape[:2]
+        out = self._solve_outputs(B, Nm, kopts_list[0], meas_err=meas_list is not None)
+        stats = (abi.Stats * max(B, 1))(); ks = (abi.KineticStats * max(B, 1))()
+        ko = self._kinetic_options_array(kopts_list)
+        st = self.lib.cpe_solve_kinetic_tracked_weighted_ragged_host(self._h, ko, _ptr(W), B, Nm, p["model_arr"], p["len_arr"], _ptr(p["q_init"]),
+                                                                     _ptr(p["q_target"]), _ptr(p["meas"]), _ptr(p["weight"]), p["stance"].ctypes.data,
+                                                                     *_force_slots(variant, p["force"]), *[_ptr(out[k]) for k in KINETIC_OUTPUTS], stats, ks)
+        _check(st, "cpe_solve_kinetic_tracked_weighted_ragged_host", allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
+        res = unpad_kinetic(out, p["lens"], p["cams"])
+        res.update(status=st, stats=list(stats)[:B], kstats=list(ks)[:B], padded=out)
+        return res
+
+    def eval_normal_tracked(self, q, q_target, g, Bm, cost, track_w=None, gam=None, q_out=None, track_W=None):
+        """cpe_eval_normal_tracked on device tensors: the per-frame terms of the tracked solve (T_n, bounds, pose prior) at Euler q; track_W
+        [B, N, NX, NX] (device tensor): the full-weight form instead (cpe_eval_normal_tracked_weighted; not together with track_w)"""
+        if track_W is not None:
+            if track_w is not None:
+                raise ValueError("eval_normal_tracked: track_w or track_W, not both")
+            self._call(self.lib.cpe_eval_normal_tracked_weighted, "cpe_eval_normal_tracked_weighted", _ptr(track_W), q.shape[0], q.shape[1], _ptr(q),
+                       _ptr(q_target), _ptr(g), _ptr(Bm), _ptr(cost), _ptr(gam), _ptr(q_out))
+            return
         w = track_weights(track_w, 1)
         self._call(self.lib.cpe_eval_normal_tracked, "cpe_eval_normal_tracked", w.ctypes.data, q.shape[0], q.shape[1], _ptr(q), _ptr(q_target), _ptr(g),
                    _ptr(Bm), _ptr(cost), _ptr(gam), _ptr(q_out))

@@ -257,6 +257,14 @@ ENTRIES = {
     "cpe_solve_kinetic_tracked_ragged": _TRACKED_BN + _RAGGED + _TRACKED_IN + _KIN_FORCES + _KIN_OUT,
     "cpe_solve_kinetic_tracked_ragged_host": _TRACKED_BN + _RAGGED + _TRACKED_IN + _KIN_FORCES + _KIN_OUT,
     "cpe_eval_normal_tracked": ("h", "p", "i", "i") + ("p",) * 7,      # track_w | B, N | q, q_target | g, Bm, cost, gam, q_out
+    # the full-weight form: track_W [B, N, NX, NX] in track_w's place; cpe_track_precision: B, N | model, n_frames | cov_diag | scale | W
+    "cpe_track_precision": _BN + _RAGGED + ("p", "d", "p"),
+    "cpe_track_precision_host": _BN + _RAGGED + ("p", "d", "p"),
+    "cpe_solve_kinetic_tracked_weighted": _TRACKED_BN + _TRACKED_IN + _KIN_FORCES + _KIN_OUT,
+    "cpe_solve_kinetic_tracked_weighted_host": _TRACKED_BN + _TRACKED_IN + _KIN_FORCES + _KIN_OUT,
+    "cpe_solve_kinetic_tracked_weighted_ragged": _TRACKED_BN + _RAGGED + _TRACKED_IN + _KIN_FORCES + _KIN_OUT,
+    "cpe_solve_kinetic_tracked_weighted_ragged_host": _TRACKED_BN + _RAGGED + _TRACKED_IN + _KIN_FORCES + _KIN_OUT,
+    "cpe_eval_normal_tracked_weighted": ("h", "p", "i", "i") + ("p",) * 7,
     "cpe_eval_kinetic_nodes": _KIN_BN + _KIN_IN + ("p",) * 7,          # f, stat, g, Huu, Hfu, Hff, meta
     "cpe_eval_kinetic_system": _KIN_BN + _KIN_IN + _KIN_FORCES + ("p",) * 10,     # the same, then gk, Bk, Hk
     "cpe_eval_lm_step": _KIN_BN + _KIN_IN + ("d",) + ("p",) * 6,       # lam | g, dg, L, delta, state, seq

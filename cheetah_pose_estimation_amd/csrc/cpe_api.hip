@@ -68,6 +68,7 @@ struct cpe_handle {
     // 3D kinematic cost of the physics-based solve (cpe_solve_kinetic_tracked*): per-model tables, their host copies, x* of every frame
     DevTrack* dtrack = nullptr; std::vector<DevTrack> htrack;
     double* xtgt = nullptr; size_t xtgt_frames = 0;
+    double* trackH = nullptr; size_t trackH_frames = 0;      // the full-weight form: 2 X^T W_n X of every frame (k_track_block)
     double* covG = nullptr; size_t covG_n = 0;     // cpe_covariance / cpe_band_inverse: the sweep's operands T^T T | G_1 .. G_pb of every column
     // cpe_rate_covariance: the handle's skeletons once more with the link centres as markers (centre-of-mass Jacobian), host and device, in
     // dm's order -- or why they could not be built; and the Jacobians of a call that does not ask for them
@@ -497,7 +498,10 @@ static size_t lds_normal(const DevModel& m, int gmm_k = 0, int gmm_dim = 0, bool
 }
 // k_frame_tracked (cpe_tracked.hip.inc): state | sin / cos | trunk rotations | Gamma | weighted residual | H | g, then the pose prior's scratch
 template <bool RAGGED = false>
-static auto frame_tracked(bool gmm) { return gmm ? k_frame_tracked<true, RAGGED> : k_frame_tracked<false, RAGGED>; }
+static auto frame_tracked(bool gmm, bool full = false) {
+    if (full) return gmm ? k_frame_tracked<true, RAGGED, true> : k_frame_tracked<false, RAGGED, true>;
+    return gmm ? k_frame_tracked<true, RAGGED> : k_frame_tracked<false, RAGGED>;
+}
 static size_t lds_tracked(const DevModel& m, int gmm_k, int gmm_dim) {
     size_t n = m.ns + 6 * m.nl + 2 * m.nrev + 36 * m.n_trunk + GAM_STRIDE * m.nrev + m.nu + m.nu * m.nu + m.nu;
     if (gmm_k > 0) n += CPE_NX + gmm_k * gmm_dim + CPE_MAX_GMM + CPE_NX;          // x | P_k (x - mu_k) | log p_k | gradient in x
@@ -752,6 +756,7 @@ void cpe_destroy(cpe_handle* h) {
     if (h->dyn) (void)hipFree(h->dyn);
     if (h->dk) (void)hipFree(h->dk);
     if (h->dtrack) (void)hipFree(h->dtrack);
+    if (h->trackH) (void)hipFree(h->trackH);
     if (h->xtgt) (void)hipFree(h->xtgt);
     if (h->covG) (void)hipFree(h->covG);
     if (h->dmc) (void)hipFree(h->dmc);
@@ -1630,17 +1635,19 @@ static void launch_dyn_pieces(cpe_handle* h, int N, int first, size_t Fw, const 
 
 // One iteration of the physics-based solve: per-frame terms and physics terms of the evaluated buffer, accept / reject (new damping), elimination
 // of the node forces at that damping for the CURRENT iterate, band system, factor + solve + next trial.
-// xt: x* of every frame (the 3D kinematic cost, k_frame_tracked in place of k_frame_normal), or null (reprojections).
+// xt: x* of every frame (the 3D kinematic cost, k_frame_tracked in place of k_frame_normal), or null (reprojections); tw: its full-weight
+// form's per-frame arrays (W non-null), or nulls.
 // back = false (cpe_covariance_kinetic): stop after k_lm_step<3, 2> -- the factor is in Lbuf and every factored sequence has back_pending = 1.
 static void kin_iterate(cpe_handle* h, const LmParams& prm, int N, size_t Fw, size_t ldsn, const double* meas, const double* weight, const int32_t* stance,
-                        const double* xt, const RaggedArgs* rg, int first, const int* act, const int* n_act, int slots, bool back = true) {
+                        const double* xt, const RaggedArgs* rg, int first, const int* act, const int* n_act, int slots, bool back = true,
+                        TrackFull tw = TrackFull{}) {
     const unsigned gf = (unsigned)((size_t)slots * N);
     const bool plain = h->gmm_k == 0;
     with_ragged(rg, [&](auto r, RaggedArgs a) {
         constexpr bool R = decltype(r)::value;
         prof_begin(h, 0);
-        if (xt) hipLaunchKernelGGL(frame_tracked<R>(!plain), dim3(gf), dim3(WAVE), ldsn, h->stream, h->dm, h->dtrack, h->st, N, first, Fw, h->qbuf, xt, h->gbuf, h->Bbuf,
-                                   h->costbuf, h->mu, h->gambuf, h->pri, act, n_act, a);
+        if (xt) hipLaunchKernelGGL(frame_tracked<R>(!plain, tw.W != nullptr), dim3(gf), dim3(WAVE), ldsn, h->stream, h->dm, h->dtrack, h->st, N, first, Fw, h->qbuf, xt,
+                                   h->gbuf, h->Bbuf, h->costbuf, h->mu, h->gambuf, h->pri, act, n_act, a, tw);
         else hipLaunchKernelGGL(frame_normal<R>(plain), dim3(gf), dim3(WAVE), ldsn, h->stream, h->dm, h->st, N, first, Fw, h->qbuf, meas, weight, h->gbuf, h->Bbuf,
                                 h->costbuf, h->mu, h->gambuf, h->pri, act, n_act, ShutterArgs{nullptr, nullptr, nullptr}, a);
         prof_end(h);
@@ -1679,8 +1686,11 @@ void cpe_default_track_weights(double w[CPE_NX]) {
 }
 
 // The tables of the tracked cost for every model of the handle: weights w (rows of CPE_NX; model k takes row min(k, rows - 1)), X^T and
-// 2 X^T diag(w) X with X = dx/du of the cost view (the construction of DevPriors::Xc).  Refuses negative or non-finite weights.
+// 2 X^T diag(w) X with X = dx/du of the cost view (the construction of DevPriors::Xc).  Refuses negative or non-finite weights.  w null (the
+// full-weight form, which reads X^T only): weights zero.
 static cpe_status build_track(cpe_handle* h, const double* w, int rows) {
+    static const double zero[CPE_NX] = {};
+    if (!w) { w = zero; rows = 1; }
     for (int i = 0; i < rows * CPE_NX; i++)
         if (!std::isfinite(w[i]) || w[i] < 0.0)
             return fail(CPE_BAD_ARG, "track_w: weights must be finite and non-negative (row " + std::to_string(i / CPE_NX) + ", entry " + std::to_string(i % CPE_NX) + ")");
@@ -1754,7 +1764,41 @@ static cpe_status one_force(const std::string& who, const double* grf_fixed, con
 }
 
 // what the tracked entries add to solve_kinetic_impl: weights (rows of CPE_NX) and the Euler target (device pointer)
-struct TrackIn { const double* w; int rows; const double* q_target; bool checked; };   // checked: q_target checked on the host
+// full (cpe_solve_kinetic_tracked_weighted*): W [B][N][28][28] (device pointer) in place of w
+struct TrackIn { const double* w; int rows; const double* q_target; bool checked; bool full; const double* W; };   // checked: q_target checked on the host
+
+// the per-frame blocks 2 X^T W X of the full-weight form into h->trackH (after build_track); rg: the ragged table (N = nmax), or null
+static cpe_status track_blocks(cpe_handle* h, int B, int N, const double* W, const RaggedArgs* rg) {
+    const size_t F = (size_t)B * N;
+    if (F > h->trackH_frames) {
+        if (h->trackH) (void)hipFree(h->trackH);
+        h->trackH = nullptr; h->trackH_frames = 0;
+        HIPCHK(hipMalloc(&h->trackH, sizeof(double) * F * CPE_NX * CPE_NX));
+        h->trackH_frames = F;
+    }
+    with_ragged(rg, [&](auto r, RaggedArgs a) { hipLaunchKernelGGL(k_track_block<decltype(r)::value>, dim3((unsigned)F), dim3(WAVE), 0, h->stream, h->dtrack, W, h->trackH, N, a); });
+    HIPCHK(hipGetLastError());
+    return CPE_OK;
+}
+
+// CPE_BAD_ARG unless every W_n of the sequences' own frames (host pointer [B][N][28][28]; lens: the frame counts, or null) is finite and bit-symmetric
+// with a non-negative diagonal.  (Positive semi-definiteness is not checked: the caller's contract.)
+static cpe_status check_track_W(const double* W, int B, int N, const int32_t* lens) {
+    constexpr size_t BB = (size_t)CPE_NX * CPE_NX;
+    for (int b = 0; b < B; b++)
+        for (int n = 0; n < (lens ? lens[b] : N); n++) {
+            const double* w = W + ((size_t)b * N + n) * BB;
+            const std::string where = " (sequence " + std::to_string(b) + ", frame " + std::to_string(n) + ")";
+            for (int i = 0; i < CPE_NX; i++)
+                for (int j = 0; j <= i; j++) {
+                    if (!std::isfinite(w[i * CPE_NX + j]) || !std::isfinite(w[j * CPE_NX + i])) return fail(CPE_BAD_ARG, "track_W: non-finite entry" + where);
+                    if (w[i * CPE_NX + j] != w[j * CPE_NX + i]) return fail(CPE_BAD_ARG, "track_W: not symmetric" + where);
+                }
+            for (int i = 0; i < CPE_NX; i++)
+                if (w[i * CPE_NX + i] < 0.0) return fail(CPE_BAD_ARG, "track_W: negative diagonal entry" + where);
+        }
+    return CPE_OK;
+}
 
 // The physics-based solve of every entry point: cpe_solve_kinetic* (model == null: B sequences of N frames of the handle's first model, options
 // opt[0]) and cpe_solve_kinetic_ragged (model / n_frames: host arrays of the batch, N = N_max, options opt[k] for model k).  At most one of
@@ -1768,7 +1812,7 @@ static cpe_status solve_kinetic_impl(cpe_handle* h, const cpe_kinetic_options* o
     if (!h || !opt || !q_init || !stance || !q) return fail(CPE_BAD_ARG, "null argument");
     if (!tr && (!meas || !weight)) return fail(CPE_BAD_ARG, "null argument");
     if (tr) {
-        if (!tr->w) return fail(CPE_BAD_ARG, "track_w is null");
+        if (tr->full ? !tr->W : !tr->w) return fail(CPE_BAD_ARG, tr->full ? "track_W is null" : "track_w is null");
         if (!tr->q_target) return fail(CPE_BAD_ARG, "q_target is null");
         if (meas && !weight) return fail(CPE_BAD_ARG, "meas is given without weight");
         if (weight && !meas) return fail(CPE_BAD_ARG, "weight is given without meas");
@@ -1794,19 +1838,21 @@ static cpe_status solve_kinetic_impl(cpe_handle* h, const cpe_kinetic_options* o
     if (s != CPE_OK) return s;
     s = ragged ? build_kin_all(h, opt, grf_fixed, tau_box, grf_box) : build_kin(h, opt, grf_fixed, tau_box, grf_box);
     if (s != CPE_OK) return s;
-    if (tr && (s = build_track(h, tr->w, tr->rows)) != CPE_OK) return s;
+    if (tr && (s = build_track(h, tr->full ? nullptr : tr->w, tr->rows)) != CPE_OK) return s;
     const DevModel& m = h->hm;
     const size_t Fw = F;
     RaggedArgs rgv;
     if (ragged && (s = ragged_upload(h, seq, N, rgv)) != CPE_OK) return s;     // (seq outlives the stream: drained below)
     const RaggedArgs* rg = ragged ? &rgv : nullptr;
     if (tr && (s = track_target(h, B, N, tr->q_target, rg, n_frames, tr->checked)) != CPE_OK) return s;
+    if (tr && tr->full && (s = track_blocks(h, B, N, tr->W, rg)) != CPE_OK) return s;
+    const TrackFull tw = tr && tr->full ? TrackFull{tr->W, h->trackH} : TrackFull{};
     if ((s = state_reset(h, B, N, q_init, rg)) != CPE_OK || (s = kin_state_reset(h, F, tau_box != nullptr)) != CPE_OK) return s;
     const LmParams prm = lm_params(h, B, N);
     const size_t ldsn = tr ? lds_tracked(h, rg) : lds_normal(h, rg);
     const double* xt = tr ? h->xtgt : nullptr;
     auto iterate = [&](int first, const int* act, const int* n_act, int slots) {
-        kin_iterate(h, prm, N, Fw, ldsn, meas, weight, stance, xt, rg, first, act, n_act, slots);
+        kin_iterate(h, prm, N, Fw, ldsn, meas, weight, stance, xt, rg, first, act, n_act, slots, true, tw);
     };
     if ((s = lm_drive(h, B, iterate)) != CPE_OK) return s;
     std::vector<SeqState> hs;
@@ -1905,10 +1951,107 @@ cpe_status cpe_solve_kinetic_tracked_ragged(cpe_handle* h, const cpe_kinetic_opt
                               tau, lambda, grf, slack, stats, kstats, &tr);
 }
 
+cpe_status cpe_solve_kinetic_tracked_weighted(cpe_handle* h, const cpe_kinetic_options* opt, const double* track_W, int32_t B, int32_t N,
+                                              const double* q_init, const double* q_target, const double* meas, const double* weight, const int32_t* stance,
+                                              const double* grf_fixed, const double* tau_box, const double* grf_box, double* q, double* dq, double* ddq,
+                                              double* positions, double* meas_err, double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats,
+                                              cpe_kinetic_stats* kstats) {
+    if (cpe_status s = one_force("cpe_solve_kinetic_tracked_weighted", grf_fixed, tau_box, grf_box); s != CPE_OK) return s;
+    const TrackIn tr{nullptr, 1, q_target, false, true, track_W};
+    return solve_kinetic_impl(h, opt, B, N, nullptr, nullptr, q_init, meas, weight, stance, grf_fixed, tau_box, grf_box, q, dq, ddq, positions, meas_err,
+                              tau, lambda, grf, slack, stats, kstats, &tr);
+}
+
+cpe_status cpe_solve_kinetic_tracked_weighted_ragged(cpe_handle* h, const cpe_kinetic_options* opts, const double* track_W, int32_t B, int32_t N_max,
+                                                     const int32_t* model, const int32_t* n_frames, const double* q_init, const double* q_target,
+                                                     const double* meas, const double* weight, const int32_t* stance, const double* grf_fixed,
+                                                     const double* tau_box, const double* grf_box, double* q, double* dq, double* ddq, double* positions,
+                                                     double* meas_err, double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats,
+                                                     cpe_kinetic_stats* kstats) {
+    if (!h || !opts || !model || !n_frames) return fail(CPE_BAD_ARG, "null argument");
+    if (cpe_status s = one_force("cpe_solve_kinetic_tracked_weighted_ragged", grf_fixed, tau_box, grf_box); s != CPE_OK) return s;
+    const TrackIn tr{nullptr, 1, q_target, false, true, track_W};
+    return solve_kinetic_impl(h, opts, B, N_max, model, n_frames, q_init, meas, weight, stance, grf_fixed, tau_box, grf_box, q, dq, ddq, positions, meas_err,
+                              tau, lambda, grf, slack, stats, kstats, &tr);
+}
+
+// W_n = (scale / 2) (X Sigma_nn X^T)^-1 of every frame (k_track_precision); model / n_frames: host arrays of a ragged batch (N = N_max), or null
+cpe_status cpe_track_precision(cpe_handle* h, int32_t B, int32_t N, const int32_t* model, const int32_t* n_frames, const double* cov_diag, double scale,
+                               double* W) {
+    if (!h) return fail(CPE_BAD_ARG, "null argument");
+    if (!cov_diag) return fail(CPE_BAD_ARG, "cov_diag is null");
+    if (!W) return fail(CPE_BAD_ARG, "W is null");
+    if (!std::isfinite(scale) || !(scale > 0.0)) return fail(CPE_BAD_ARG, "scale must be finite and > 0");
+    if ((model == nullptr) != (n_frames == nullptr)) return fail(CPE_BAD_ARG, "model and n_frames are given together");
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    std::vector<int2> seq;
+    if (model)
+        if (cpe_status s = ragged_table(h, B, N, model, n_frames, seq); s != CPE_OK) return s;
+    HIPCHK(hipSetDevice(h->device));
+    cpe_status s = ensure_ws(h, B, N);
+    if (s != CPE_OK || (s = build_track(h, nullptr, 1)) != CPE_OK) return s;
+    RaggedArgs rgv;
+    if (model && (s = ragged_upload(h, seq, N, rgv)) != CPE_OK) return s;
+    Staging st(h->stream);
+    int* bad = st.alloc<int>(F);
+    HIPCHK(st.err);
+    if (model) HIPCHK(hipMemsetAsync(bad, 0, sizeof(int) * F, h->stream));        // (padding frames are not visited)
+    with_ragged(model ? &rgv : nullptr, [&](auto r, RaggedArgs a) {
+        hipLaunchKernelGGL(k_track_precision<decltype(r)::value>, dim3((unsigned)F), dim3(WAVE), 0, h->stream, h->dtrack, cov_diag, scale, W, bad, N, a);
+    });
+    HIPCHK(hipGetLastError());
+    std::vector<int> hbad(F);
+    HIPCHK(hipMemcpyAsync(hbad.data(), bad, sizeof(int) * F, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (size_t f = 0; f < F; f++)
+        if (hbad[f])
+            return fail(CPE_NUMERICAL, "cpe_track_precision: the covariance block of sequence " + std::to_string(f / (size_t)N) + ", frame " +
+                                           std::to_string(f % (size_t)N) + " has no Cholesky factor (its W is zero)");
+    return CPE_OK;
+}
+
+cpe_status cpe_track_precision_host(cpe_handle* h, int32_t B, int32_t N, const int32_t* model, const int32_t* n_frames, const double* cov_diag,
+                                    double scale, double* W) {
+    if (!h) return fail(CPE_BAD_ARG, "null argument");
+    if (!cov_diag) return fail(CPE_BAD_ARG, "cov_diag is null");
+    if (!W) return fail(CPE_BAD_ARG, "W is null");
+    size_t F;
+    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t BB = (size_t)CPE_NX * CPE_NX;
+    Staging st(h->stream);
+    const double* dc = st.in(cov_diag, F * BB);
+    double* ow = st.out(W, F * BB);
+    HIPCHK(st.err);
+    if (model) HIPCHK(hipMemsetAsync(ow, 0, sizeof(double) * F * BB, h->stream));   // the padding frames
+    const cpe_status s = cpe_track_precision(h, B, N, model, n_frames, dc, scale, ow);
+    if (s < 0) return s;
+    HIPCHK(st.fetch());
+    return s;
+}
+
+// cpe_eval_normal_tracked (track_w) and cpe_eval_normal_tracked_weighted (track_W, device [B][N][28][28]): exactly one of the two is given
+static cpe_status eval_normal_tracked_impl(cpe_handle* h, const double* track_w, const double* track_W, int32_t B, int32_t N, const double* q,
+                                           const double* q_target, double* g, double* Bm, double* cost, double* gam, double* q_out);
+
 cpe_status cpe_eval_normal_tracked(cpe_handle* h, const double* track_w, int32_t B, int32_t N, const double* q, const double* q_target, double* g,
                                    double* Bm, double* cost, double* gam, double* q_out) {
+    if (h && q && g && Bm && cost && !track_w) return fail(CPE_BAD_ARG, "track_w is null");
+    return eval_normal_tracked_impl(h, track_w, nullptr, B, N, q, q_target, g, Bm, cost, gam, q_out);
+}
+
+cpe_status cpe_eval_normal_tracked_weighted(cpe_handle* h, const double* track_W, int32_t B, int32_t N, const double* q, const double* q_target, double* g,
+                                            double* Bm, double* cost, double* gam, double* q_out) {
+    if (h && q && g && Bm && cost && !track_W) return fail(CPE_BAD_ARG, "track_W is null");
+    return eval_normal_tracked_impl(h, nullptr, track_W, B, N, q, q_target, g, Bm, cost, gam, q_out);
+}
+
+static cpe_status eval_normal_tracked_impl(cpe_handle* h, const double* track_w, const double* track_W, int32_t B, int32_t N, const double* q,
+                                           const double* q_target, double* g, double* Bm, double* cost, double* gam, double* q_out) {
     if (!h || !q || !g || !Bm || !cost) return fail(CPE_BAD_ARG, "null argument");
-    if (!track_w) return fail(CPE_BAD_ARG, "track_w is null");
     if (!q_target) return fail(CPE_BAD_ARG, "q_target is null");
     size_t F;
     if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
@@ -1917,10 +2060,12 @@ cpe_status cpe_eval_normal_tracked(cpe_handle* h, const double* track_w, int32_t
     cpe_status s = ensure_ws(h, B, N);
     if (s != CPE_OK) return s;
     if ((s = build_track(h, track_w, 1)) != CPE_OK || (s = track_target(h, B, N, q_target, nullptr, nullptr, false)) != CPE_OK) return s;
+    if (track_W && (s = track_blocks(h, B, N, track_W, nullptr)) != CPE_OK) return s;
     if ((s = state_reset(h, B, N, q)) != CPE_OK) return s;
     const DevModel& m = h->hm;
-    hipLaunchKernelGGL(frame_tracked<>(h->gmm_k > 0), dim3((unsigned)F), dim3(WAVE), lds_tracked(h, nullptr), h->stream, h->dm, h->dtrack, h->st, N, 1, F,
-                       h->qbuf, h->xtgt, h->gbuf, h->Bbuf, h->costbuf, h->mu, h->gambuf, h->pri, nullptr, nullptr, RaggedArgs{});
+    hipLaunchKernelGGL(frame_tracked<>(h->gmm_k > 0, track_W != nullptr), dim3((unsigned)F), dim3(WAVE), lds_tracked(h, nullptr), h->stream, h->dm, h->dtrack, h->st,
+                       N, 1, F, h->qbuf, h->xtgt, h->gbuf, h->Bbuf, h->costbuf, h->mu, h->gambuf, h->pri, nullptr, nullptr, RaggedArgs{},
+                       track_W ? TrackFull{track_W, h->trackH} : TrackFull{});
     HIPCHK(hipMemcpyAsync(g, h->gbuf, sizeof(double) * F * m.nu, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(Bm, h->Bbuf, sizeof(double) * F * m.nu * m.nu, hipMemcpyDeviceToDevice, h->stream));
     hipLaunchKernelGGL(k_gather_normal, dim3((unsigned)F), dim3(128), 0, h->stream, h->dm, F, h->qbuf, h->costbuf, h->gambuf, cost, gam, q_out);
@@ -2817,13 +2962,14 @@ cpe_status cpe_solve_kinetic_ragged_host(cpe_handle* h, const cpe_kinetic_option
 }
 
 // host-pointer twins of cpe_solve_kinetic_tracked (model == null) and cpe_solve_kinetic_tracked_ragged: stage through HBM
+// track_W non-null: the full-weight form ([B][N][28][28], host; checked here), track_w is then not read
 static cpe_status kinetic_tracked_host(cpe_handle* h, const cpe_kinetic_options* opts, const double* track_w, int32_t B, int32_t N, const int32_t* model,
                                        const int32_t* n_frames, const double* q_init, const double* q_target, const double* meas, const double* weight,
                                        const int32_t* stance, const double* grf_fixed, const double* tau_box, const double* grf_box, double* q, double* dq,
                                        double* ddq, double* positions, double* meas_err, double* tau, double* lambda, double* grf, double* slack,
-                                       cpe_stats* stats, cpe_kinetic_stats* kstats) {
+                                       cpe_stats* stats, cpe_kinetic_stats* kstats, const double* track_W = nullptr, bool full = false) {
     if (!h || !opts || !q_init || !stance || !q) return fail(CPE_BAD_ARG, "null argument");
-    if (!track_w) return fail(CPE_BAD_ARG, "track_w is null");
+    if (full ? !track_W : !track_w) return fail(CPE_BAD_ARG, full ? "track_W is null" : "track_w is null");
     if (!q_target) return fail(CPE_BAD_ARG, "q_target is null");
     if (meas && !weight) return fail(CPE_BAD_ARG, "meas is given without weight");
     if (weight && !meas) return fail(CPE_BAD_ARG, "weight is given without meas");
@@ -2835,10 +2981,13 @@ static cpe_status kinetic_tracked_host(cpe_handle* h, const cpe_kinetic_options*
     if (cpe_status s = force_stage(opts[0].dyn, F, grf_fixed, tau_box, grf_box, fs); s != CPE_OK) return s;
     const DevModel& m = h->hm;
     if (cpe_status s = check_target(q_target, B, N, m.nq, n_frames); s != CPE_OK) return s;
+    if (full)
+        if (cpe_status s = check_track_W(track_W, B, N, n_frames); s != CPE_OK) return s;
     const size_t nf = fs.nf, nmo = fs.nmo, nc = (size_t)n_con(m), nm = F * (model ? cams_max(h) : m.C) * m.L;
     HIPCHK(hipSetDevice(h->device));
     Staging st(h->stream);
     const double *di = st.in(q_init, F * m.nq), *dt = st.in(q_target, F * m.nq), *dmeas = st.in(meas, nm * 2), *dweight = st.in(weight, nm);
+    const double* dW = st.in(full ? track_W : nullptr, F * CPE_NX * CPE_NX);
     const int32_t* dstance = st.in(stance, F * nf);
     const double* dfx = st.in(fs.fx, fs.n_fx);
     double *oq = st.out(q, F * m.nq), *odq = st.out(dq, F * m.nq), *oddq = st.out(ddq, F * m.nq), *op = st.out(positions, F * m.L * 3);
@@ -2846,7 +2995,7 @@ static cpe_status kinetic_tracked_host(cpe_handle* h, const cpe_kinetic_options*
     double *ot = st.out(tau, F * nmo), *ol = st.out(lambda, F * nc), *og = st.out(grf, F * nf * 5), *osl = st.out(slack, F * m.nq);
     HIPCHK(st.err);
     // the target is checked here, on the host copy the caller handed in: the device entries' own copy back is skipped
-    const TrackIn tr{track_w, model ? n_models(h) : 1, dt, true};
+    const TrackIn tr{track_w, model ? n_models(h) : 1, dt, true, full, dW};
     cpe_status s = solve_kinetic_impl(h, opts, B, N, model, n_frames, di, dmeas, dweight, dstance, grf_fixed ? dfx : nullptr, tau_box ? dfx : nullptr,
                                       grf_box ? dfx : nullptr, oq, odq, oddq, op, ome, ot, ol, og, osl, stats, kstats, &tr);
     if (s < 0) return s;
@@ -2872,6 +3021,26 @@ cpe_status cpe_solve_kinetic_tracked_ragged_host(cpe_handle* h, const cpe_kineti
     if (!model || !n_frames) return fail(CPE_BAD_ARG, "null argument");
     return kinetic_tracked_host(h, opts, track_w, B, N_max, model, n_frames, q_init, q_target, meas, weight, stance, grf_fixed, tau_box, grf_box, q, dq, ddq,
                                 positions, meas_err, tau, lambda, grf, slack, stats, kstats);
+}
+
+cpe_status cpe_solve_kinetic_tracked_weighted_host(cpe_handle* h, const cpe_kinetic_options* opt, const double* track_W, int32_t B, int32_t N,
+                                                   const double* q_init, const double* q_target, const double* meas, const double* weight,
+                                                   const int32_t* stance, const double* grf_fixed, const double* tau_box, const double* grf_box, double* q,
+                                                   double* dq, double* ddq, double* positions, double* meas_err, double* tau, double* lambda, double* grf,
+                                                   double* slack, cpe_stats* stats, cpe_kinetic_stats* kstats) {
+    return kinetic_tracked_host(h, opt, nullptr, B, N, nullptr, nullptr, q_init, q_target, meas, weight, stance, grf_fixed, tau_box, grf_box, q, dq, ddq,
+                                positions, meas_err, tau, lambda, grf, slack, stats, kstats, track_W, true);
+}
+
+cpe_status cpe_solve_kinetic_tracked_weighted_ragged_host(cpe_handle* h, const cpe_kinetic_options* opts, const double* track_W, int32_t B, int32_t N_max,
+                                                          const int32_t* model, const int32_t* n_frames, const double* q_init, const double* q_target,
+                                                          const double* meas, const double* weight, const int32_t* stance, const double* grf_fixed,
+                                                          const double* tau_box, const double* grf_box, double* q, double* dq, double* ddq,
+                                                          double* positions, double* meas_err, double* tau, double* lambda, double* grf, double* slack,
+                                                          cpe_stats* stats, cpe_kinetic_stats* kstats) {
+    if (!model || !n_frames) return fail(CPE_BAD_ARG, "null argument");
+    return kinetic_tracked_host(h, opts, nullptr, B, N_max, model, n_frames, q_init, q_target, meas, weight, stance, grf_fixed, tau_box, grf_box, q, dq, ddq,
+                                positions, meas_err, tau, lambda, grf, slack, stats, kstats, track_W, true);
 }
 
 }  // extern "C"

@@ -133,6 +133,37 @@ __device__ __forceinline__ void wave_point_columns(const DevModel* __restrict__ 
     wave_lds_sync();
 }
 
+// T = L^-1 of the lower-triangular block sL [28][28] (row-major; sr[k] = 1 / L[k][k]) by forward substitution, one column per lane: lanes 0..27
+// and 28..55 both hold columns 0..27 in t (each half takes every second row of the products that follow), lanes 56..63 shadow columns 0..7 and
+// store nothing.  T goes to sT, row-major; ends with a wave_lds_sync.
+__device__ __forceinline__ void wave_tri_inverse(const double* sL, const double* sr, double* sT, double (&t)[NU], int lane) {
+    const int c = lane % NU, hh = lane / NU;
+#pragma unroll
+    for (int i = 0; i < NU; i++) {
+        double s = i == c ? 1.0 : 0.0;
+#pragma unroll
+        for (int k = 0; k < i; k++) s = fma(-sL[i * NU + k], t[k], s);
+        t[i] = s * sr[i];
+    }
+    if (hh == 0) {
+#pragma unroll
+        for (int k = 0; k < NU; k++) sT[k * NU + c] = t[k];
+    }
+    wave_lds_sync();
+}
+// (T^T T)[a][c] = sum_k T[k][a] T[k][c] after wave_tri_inverse, lanes 0..55: the same products in the same order for [a][c] and [c][a] --
+// bit-symmetric.  O: the block [28][28], row-major; SCALED: every entry times `scale` (symmetric still).
+template <bool SCALED>
+__device__ __forceinline__ void wave_ttt(const double* sT, const double (&t)[NU], double* O, double scale, int lane) {
+    const int c = lane % NU, hh = lane / NU;
+    for (int a = hh; a < NU; a += 2) {
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < NU; k++) s = fma(sT[k * NU + a], t[k], s);
+        O[a * NU + c] = SCALED ? scale * s : s;
+    }
+}
+
 // ---- pre-pass, one wave per frame.  Column n of the factor: block 0 = L(n,n), block i = L(n+i,n), [row * 28 + col].  `recip` != 0: the
 // diagonal of block 0 holds 1 / L[k][k] (Lbuf as k_lm_step writes it), else L[k][k] itself (the plain layout of cpe_eval_lm_step).  Both
 // forms go through the same arithmetic, r = 1 / d with d the true diagonal, so a factor exported by cpe_covariance and handed back to
@@ -160,30 +191,11 @@ __global__ __launch_bounds__(WAVE) void k_cov_prep(const SeqState* __restrict__ 
         sr[lane] = 1.0 / d;
     }
     wave_lds_sync();
-    // T = L00^-1 by forward substitution, one column per lane: lanes 0..27 and 28..55 both hold columns 0..27 (each half takes every
-    // second row of the products below), lanes 56..63 shadow columns 0..7 and store nothing
-    const int c = lane % NU, hh = lane / NU;
     double t[NU];
-#pragma unroll
-    for (int i = 0; i < NU; i++) {
-        double s = i == c ? 1.0 : 0.0;
-#pragma unroll
-        for (int k = 0; k < i; k++) s = fma(-sL[i * NU + k], t[k], s);
-        t[i] = s * sr[i];
-    }
-    if (hh == 0) {
-#pragma unroll
-        for (int k = 0; k < NU; k++) sT[k * NU + c] = t[k];
-    }
-    wave_lds_sync();
+    wave_tri_inverse(sL, sr, sT, t, lane);
+    const int c = lane % NU, hh = lane / NU;
     if (hh < 2) {
-        // (T^T T)[a][c] = sum_k T[k][a] T[k][c]: the same products in the same order for [a][c] and [c][a] -- bit-symmetric
-        for (int a = hh; a < NU; a += 2) {
-            double s = 0.0;
-#pragma unroll
-            for (int k = 0; k < NU; k++) s = fma(sT[k * NU + a], t[k], s);
-            Gc[a * NU + c] = s;
-        }
+        wave_ttt<false>(sT, t, Gc, 1.0, lane);
 #pragma unroll
         for (int i = 1; i <= PB; i++) {
             const double* Li = sL + i * BB;

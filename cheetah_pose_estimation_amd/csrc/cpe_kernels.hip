@@ -721,7 +721,7 @@ __global__ __launch_bounds__(WAVE) void k_project(const DevModel* __restrict__ M
 #include "cpe_solver.hip.inc"
 #include "cpe_kinetic.hip.inc"
 #include "cpe_kinetic_jac.hip.inc"
-#include "cpe_tracked.hip.inc"
 #include "cpe_covariance.hip.inc"
+#include "cpe_tracked.hip.inc"
 #include "cpe_rate_cov.hip.inc"
 #include "cpe_force_cov.hip.inc"

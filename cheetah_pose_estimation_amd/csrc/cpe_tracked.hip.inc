@@ -1,9 +1,12 @@
-// cpe_tracked.hip.inc -- the 3D kinematic cost of the physics-based solve (included by cpe_kernels.hip after the solver kernels).
+// cpe_tracked.hip.inc -- the 3D kinematic cost of the physics-based solve (included by cpe_kernels.hip after the solver and covariance kernels).
 //
 // estimate_kinetics(use_2d_reprojections=False) (acinoset_opt.py:908-913, acinoset_misc.py:531-590) replaces the reprojection cost by
 //     T_n = sum_{p in x} w_p (x_p(u_n) - x*_{n,p})^2
 // over the 28 relative angles x on the cost view (leg pitch = theta_B + alpha, DESIGN.md 2).  x = X u with a constant X of the model, so the
 // gradient 2 X^T W (x - x*) and the block 2 X^T W X are exact and the block is a constant of (model, weights): DevTrack.  DESIGN.md 2b.
+// The full-weight form (cpe_solve_kinetic_tracked_weighted*) tracks frame n with its own symmetric 28 x 28 matrix,
+//     T_n = (x_n - x*_n)^T W_n (x_n - x*_n),
+// W_n = (scale / 2) (X Sigma_nn X^T)^-1 from the kinematic posterior (k_track_precision), block 2 X^T W_n X once per solve (k_track_block).
 
 // per model: weights, X^T and 2 X^T W X (built by the host, cpe_api.hip build_track)
 struct DevTrack {
@@ -11,6 +14,109 @@ struct DevTrack {
     double Xt[CPE_NX][CPE_NX];          // Xt[j][k] = d x_k / d u_j
     double H[CPE_NX * CPE_NX];          // 2 X^T diag(w) X, row-major
 };
+
+// the full-weight form's per-frame arrays: W [F][28][28] (the caller's) and the blocks 2 X^T W X [F][28 * 28] (k_track_block); null in the plain form
+struct TrackFull { const double* W; const double* H; };
+
+// W_n = (scale / 2) (X Sigma_nn X^T)^-1 of every frame from the u-space blocks cov_diag [F][28][28] of cpe_covariance: C = X Sigma X^T (lower
+// triangle), its Cholesky factor in place, T = L^-1 and T^T T by the helpers of k_cov_prep (bit-symmetric).  A block without a factor -- a pivot
+// that is not positive and finite -- gives W = 0 and bad[f] = 1 (else 0).  One wave per frame, every sum in a fixed order, no atomics; RAGGED:
+// padding frames leave at once.
+template <bool RAGGED = false>
+__global__ __launch_bounds__(WAVE) void k_track_precision(const DevTrack* __restrict__ T, const double* __restrict__ cov_diag, double scale,
+                                                         double* __restrict__ W, int* __restrict__ bad, int NS, RaggedArgs rg = RaggedArgs{}) {
+    constexpr int BB = NU * NU;
+    __shared__ double sA[BB];            // Sigma, then C and its factor
+    __shared__ double sY[BB];            // Sigma X^T, then T
+    __shared__ double sr[NU];
+    __shared__ int sbad;
+    const int lane = threadIdx.x;
+    FrameSlot fs;
+    if (!frame_slot<RAGGED>(NS, nullptr, nullptr, rg, fs)) return;
+    T += fs.model;
+    const size_t f = blockIdx.x;
+    const double* Sg = cov_diag + f * BB;
+    double* Wo = W + f * BB;
+    for (int t = lane; t < BB; t += WAVE) sA[t] = Sg[t];
+    if (lane == 0) sbad = 0;
+    wave_lds_sync();
+    // Y[a][j] = sum_b Sigma[a][b] X[j][b]
+    for (int t = lane; t < BB; t += WAVE) {
+        const int a = t / NU, j = t - a * NU;
+        double s = 0.0;
+        for (int b = 0; b < NU; b++) s = fma(sA[a * NU + b], T->Xt[b][j], s);
+        sY[t] = s;
+    }
+    wave_lds_sync();
+    // C[i][j] = sum_a X[i][a] Y[a][j], j <= i (the upper triangle is never read)
+    for (int t = lane; t < BB; t += WAVE) {
+        const int i = t / NU, j = t - i * NU;
+        if (j > i) continue;
+        double s = 0.0;
+        for (int a = 0; a < NU; a++) s = fma(T->Xt[a][i], sY[a * NU + j], s);
+        sA[t] = s;
+    }
+    wave_lds_sync();
+    // Cholesky, right-looking, in place: column k scaled by 1 / L[k][k], then the trailing lower triangle updated
+    for (int k = 0; k < NU; k++) {
+        const double d = sA[k * NU + k];
+        if (!(d > 0.0) || isinf(d)) { if (lane == 0) sbad = 1; break; }        // uniform
+        const double l = sqrt(d), il = 1.0 / l;
+        wave_lds_sync();                                     // every lane has read the pivot
+        if (lane == 0) { sA[k * NU + k] = l; sr[k] = il; }
+        if (lane > k && lane < NU) sA[lane * NU + k] *= il;
+        wave_lds_sync();
+        const int m = NU - 1 - k;                            // trailing rows k+1 .. 27
+        for (int e = lane; e < m * m; e += WAVE) {
+            const int i = k + 1 + e / m, j = k + 1 + e % m;
+            if (j <= i) sA[i * NU + j] = fma(-sA[i * NU + k], sA[j * NU + k], sA[i * NU + j]);
+        }
+        wave_lds_sync();
+    }
+    wave_lds_sync();
+    if (sbad) {                                              // uniform
+        for (int t = lane; t < BB; t += WAVE) Wo[t] = 0.0;
+        if (lane == 0) bad[f] = 1;
+        return;
+    }
+    if (lane == 0) bad[f] = 0;
+    double t[NU];
+    wave_tri_inverse(sA, sr, sY, t, lane);
+    if (lane < 2 * NU) wave_ttt<true>(sY, t, Wo, 0.5 * scale, lane);
+}
+
+// H_n = 2 X^T W_n X of every frame, [F][28 * 28] row-major, from W [F][28][28]: the lower triangle is computed and mirrored, so the block is
+// exactly symmetric.  Once per solve (the block is a constant of it); one wave per frame, fixed order, no atomics.
+template <bool RAGGED = false>
+__global__ __launch_bounds__(WAVE) void k_track_block(const DevTrack* __restrict__ T, const double* __restrict__ W, double* __restrict__ H, int NS,
+                                                     RaggedArgs rg = RaggedArgs{}) {
+    constexpr int BB = NU * NU;
+    __shared__ double sW[BB];
+    __shared__ double sY[BB];
+    const int lane = threadIdx.x;
+    FrameSlot fs;
+    if (!frame_slot<RAGGED>(NS, nullptr, nullptr, rg, fs)) return;
+    T += fs.model;
+    const size_t f = blockIdx.x;
+    for (int t = lane; t < BB; t += WAVE) sW[t] = W[f * BB + t];
+    wave_lds_sync();
+    // Y[p][j] = sum_q W[p][q] X[q][j]
+    for (int t = lane; t < BB; t += WAVE) {
+        const int p = t / NU, j = t - p * NU;
+        double s = 0.0;
+        for (int q = 0; q < NU; q++) s = fma(sW[p * NU + q], T->Xt[j][q], s);
+        sY[t] = s;
+    }
+    wave_lds_sync();
+    double* Ho = H + f * BB;
+    for (int t = lane; t < BB; t += WAVE) {
+        const int i = t / NU, j = t - i * NU;
+        if (j > i) continue;
+        double s = 0.0;
+        for (int p = 0; p < NU; p++) s = fma(T->Xt[i][p], sY[p * NU + j], s);
+        Ho[i * NU + j] = 2.0 * s; Ho[j * NU + i] = 2.0 * s;
+    }
+}
 
 // x* of every frame from an Euler target q [F][nq]: the state (q, alpha = leg_alpha) of k_state_init, then the relative angles on the cost view.  One wave per frame; RAGGED: padding frames leave at once (nothing reads them).
 template <bool RAGGED = false>
@@ -36,12 +142,15 @@ __global__ __launch_bounds__(WAVE) void k_track_target(const DevModel* __restric
 // Kept: the state made consistent with the joint equalities (tails' roll, legs' Euler angles: the physics terms read them), Gamma, the
 // angle-bound AL terms and the pose prior (GMM).  Added: T_n to g, to the diagonal block and to cost slot 0.  One wave per frame.
 // dynamic LDS (doubles): q | al [ns] | sc[6 nl] | sa[2 nrev] | R[36 n_trunk] | gam[4 nrev] | res[nu] | H[nu nu] | g[nu] | GMM scratch
-template <bool GMM, bool RAGGED = false>
+// FULLW: the full-weight form -- r = 2 W_n d with W_n read row by row from global memory (W_n is symmetric: lane p sums W[k][p] d[k] over the
+// rows k, so every load is contiguous across the lanes), T_n = d . r / 2, the block from tw.H; the LDS is the plain form's.
+template <bool GMM, bool RAGGED = false, bool FULLW = false>
 __global__ __launch_bounds__(WAVE) void k_frame_tracked(const DevModel* __restrict__ M, const DevTrack* __restrict__ T, const SeqState* __restrict__ st,
                                                         int N, int which, size_t n_frames, double* __restrict__ qbuf, const double* __restrict__ xt,
                                                         double* __restrict__ gbuf, double* __restrict__ Bbuf, double* __restrict__ costbuf,
                                                         double* __restrict__ mu, double* __restrict__ gambuf, const DevPriors* __restrict__ pri,
-                                                        const int* __restrict__ act, const int* __restrict__ n_act, RaggedArgs rg = RaggedArgs{}) {
+                                                        const int* __restrict__ act, const int* __restrict__ n_act, RaggedArgs rg = RaggedArgs{},
+                                                        TrackFull tw = TrackFull{}) {
     extern __shared__ double smem[];
     const int lane = threadIdx.x;
     FrameSlot fs;
@@ -84,11 +193,30 @@ __global__ __launch_bounds__(WAVE) void k_frame_tracked(const DevModel* __restri
     if (lane < nu) {
         const int r = M->rel_ref_u[lane];
         const double d = M->rel_sign_u[lane] * (cost_coord(M, sq, lane) - (r >= 0 ? cost_coord(M, sq, r) : 0.0)) - xtg;
-        const double w = T->w[lane];
-        ft = w * d * d;
-        sres[lane] = 2.0 * w * d;
+        if constexpr (FULLW) sres[lane] = d;
+        else {
+            const double w = T->w[lane];
+            ft = w * d * d;
+            sres[lane] = 2.0 * w * d;
+        }
     }
-    for (int t = lane; t < nu * nu; t += WAVE) sH[t] = T->H[t];
+    if constexpr (FULLW) {
+        const double* Hn = tw.H + f * (size_t)(NU * NU);
+        for (int t = lane; t < nu * nu; t += WAVE) sH[t] = Hn[t];
+        wave_lds_sync();
+        double r = 0.0;
+        if (lane < nu) {
+            const double* Wn = tw.W + f * (size_t)(NU * NU) + lane;
+#pragma unroll 4
+            for (int k = 0; k < nu; k++) r += Wn[k * NU] * sres[k];
+            r *= 2.0;
+            ft = 0.5 * sres[lane] * r;
+        }
+        wave_lds_sync();
+        if (lane < nu) sres[lane] = r;
+    } else {
+        for (int t = lane; t < nu * nu; t += WAVE) sH[t] = T->H[t];
+    }
     wave_lds_sync();
     if (lane < nq) stf[lane] = sq[lane];                  // Euler part of the state, consistent with the joint equalities
     if (lane < GAM_STRIDE * nrev) gambuf[((size_t)buf * n_frames + f) * (GAM_STRIDE * nrev) + lane] = sgam[lane];

@@ -1204,7 +1204,7 @@ def estimate_kinetics(estimator: CheetahEstimator, init_torques: bool = True, au
                       disable_pose_prior: bool = False, disable_motion_prior: bool = False, plot: bool = False, out_fname: str = "fte",
                       out_dir_prefix: Optional[str] = None, options: Optional[abi.Options] = None,
                       kinetic_options: Optional[abi.KineticOptions] = None, uncertainty: bool = False, uncertainty_ridge: float = 0.0,
-                      uncertainty_rates: bool = False, uncertainty_spans=None) -> bool:
+                      uncertainty_rates: bool = False, uncertainty_spans=None, track_weights: str = "reference", track_scale: float = 1.0) -> bool:
     """Same signature and meaning as acinoset_opt.estimate_kinetics (acinoset_opt.py:693-708) for the branch its drivers run for the
     physics-based reconstruction (`joint_estimation=True`, run_dataset.py:1198-1229): torques, joint constraint forces, ground-reaction
     forces and the trajectory are estimated together, warm-started from the kinematic solution on disk, with the contact windows of
@@ -1222,15 +1222,21 @@ def estimate_kinetics(estimator: CheetahEstimator, init_torques: bool = True, au
     estimate_kinematics' fields plus tau_std, lambda_std, grf_std, tau_cov (force_uncertainty).  A sequence without a factor raises CpeError after the
     solve's own files are written.  Not with use_2d_reprojections=False (the covariance of the 3D kinematic cost is not built).
     uncertainty_rates=True (with uncertainty=True): the rate fields of estimate_kinematics (RATE_FIELDS), from that covariance.
-    uncertainty_spans (with uncertainty=True): the span fields of estimate_kinematics (SPAN_FIELDS), from that covariance."""
+    uncertainty_spans (with uncertainty=True): the span fields of estimate_kinematics (SPAN_FIELDS), from that covariance.
+    track_weights (use_2d_reprojections=False): "reference" = the reference's 28 constants; "posterior" = frame n is tracked with its own matrix
+    W_n = (track_scale / 2) (X Sigma_nn X^T)^-1 from cov_u of the uncertainty.npz that estimate_kinematics(uncertainty=True) wrote beside the
+    kinematic result (one cpe_track_precision call, then cpe_solve_kinetic_tracked_weighted; DESIGN.md 2b has the approximation and what
+    track_scale is for).  "posterior" with use_2d_reprojections=True, or any other string, is a ValueError."""
     _check_rates(uncertainty, uncertainty_rates)
     _check_spans(uncertainty, uncertainty_spans)
+    _check_track_weights(track_weights, track_scale, use_2d_reprojections)
     spans = resolve_spans(uncertainty_spans, estimator.params.end_frame - estimator.params.start_frame)
     if uncertainty and not use_2d_reprojections:
         raise NotImplementedError("uncertainty together with use_2d_reprojections=False: cpe_covariance_kinetic takes the reprojection cost; the covariance "
                                   "of the 3D kinematic cost (cpe_solve_kinetic_tracked) is not built")
     prep = _kinetic_prepare(estimator, auto, use_2d_reprojections, init_prev_kinematic_solution, synthesised_grf, no_slip, joint_estimation, fix_grf,
-                            ground_constraint, disable_pose_prior, disable_motion_prior, out_dir_prefix, options, kinetic_options)
+                            ground_constraint, disable_pose_prior, disable_motion_prior, out_dir_prefix, options, kinetic_options,
+                            track_weights=track_weights, track_scale=track_scale)
     est = estimator
     if uncertainty:
         _lib.covariance_supported(prep["pri"], uncertainty_ridge)          # raises with the library's reason (negative or non-finite ridge)
@@ -1238,7 +1244,12 @@ def estimate_kinetics(estimator: CheetahEstimator, init_torques: bool = True, au
     try:
         t0 = time()
         gfx, gbx = prep["grf_fixed"], prep["grf_box"]
-        if prep["tracked"]:
+        if prep["weighted"]:
+            W = h.track_precision_host(prep["cov_u"][None], prep["track_scale"])
+            res = h.solve_kinetic_tracked_weighted_host(prep["ko"], W, prep["q_init"][None], prep["q_target"][None], prep["stance"][None], est.meas[None],
+                                                        est.weight[None], grf_fixed=None if gfx is None else gfx[None],
+                                                        grf_box=None if gbx is None else gbx[None])
+        elif prep["tracked"]:
             res = h.solve_kinetic_tracked_host(prep["ko"], prep["q_init"][None], prep["q_target"][None], prep["stance"][None], est.meas[None],
                                                est.weight[None], grf_fixed=None if gfx is None else gfx[None], grf_box=None if gbx is None else gbx[None])
         else:
@@ -1259,6 +1270,32 @@ def kinematic_result_path(data_dir: str, cam_idx: Optional[int], init_prev_kinem
     return os.path.join(data_dir, f"fte_kinematic_{cam_idx}" if mono else "fte_kinematic", "fte.pickle")
 
 
+TRACK_WEIGHTS = ("reference", "posterior")
+
+
+def _check_track_weights(track_weights: str, track_scale: float, use_2d_reprojections: bool) -> None:
+    """what the track_weights / track_scale keywords refuse, before anything is looked at"""
+    if track_weights not in TRACK_WEIGHTS:
+        raise ValueError(f"track_weights={track_weights!r}: expected one of {TRACK_WEIGHTS}")
+    if track_weights == "posterior" and use_2d_reprojections:
+        raise ValueError('track_weights="posterior" weights the 3D kinematic cost: it requires use_2d_reprojections=False')
+    if not (np.isfinite(track_scale) and track_scale > 0.0):
+        raise ValueError(f"track_scale={track_scale!r}: expected a finite number > 0")
+
+
+def load_posterior_blocks(kinematic_pickle: str, n_frames: int) -> np.ndarray:
+    """cov_u [n_frames, 28, 28] of the uncertainty.npz beside a kinematic result: the blocks track_weights="posterior" turns into weights"""
+    path = os.path.join(os.path.dirname(kinematic_pickle), "uncertainty.npz")
+    if not os.path.exists(path):
+        raise FileNotFoundError(f'{path}: track_weights="posterior" reads the posterior covariance of the kinematic estimate; '
+                                "estimate_kinematics(uncertainty=True) writes it beside its fte.pickle")
+    with np.load(path) as z:
+        cov_u = np.ascontiguousarray(z["cov_u"], dtype=np.float64)
+    if cov_u.ndim != 3 or cov_u.shape[1:] != (abi.NX, abi.NX) or cov_u.shape[0] < n_frames:
+        raise ValueError(f"{path}: cov_u has shape {cov_u.shape}, expected [at least {n_frames}, {abi.NX}, {abi.NX}]")
+    return np.ascontiguousarray(cov_u[:n_frames])
+
+
 def tracked_motion_options(ko: abi.KineticOptions, fps: float) -> abi.KineticOptions:
     """the motion energy of the 3D kinematic cost (acinoset_opt.py:913, :919-920): 1e-2 x torque in place of the marker smoothing, weighted
     0.1 fps^-2 -> w_torque = 1 + 1e-3 fps^-2, w_smooth = 0 (in place; returns ko)"""
@@ -1268,8 +1305,10 @@ def tracked_motion_options(ko: abi.KineticOptions, fps: float) -> abi.KineticOpt
 
 def _kinetic_prepare(est: CheetahEstimator, auto: bool, use_2d_reprojections: bool, init_prev_kinematic_solution: bool, synthesised_grf: bool,
                      no_slip: bool, joint_estimation: bool, fix_grf: bool, ground_constraint: bool, disable_pose_prior: bool, disable_motion_prior: bool,
-                     out_dir_prefix: Optional[str], options: Optional[abi.Options], kinetic_options: Optional[abi.KineticOptions]) -> dict:
-    """what estimate_kinetics sets up before the solver call: initial guess, contacts, stance, the force profile or its boxes, options, priors"""
+                     out_dir_prefix: Optional[str], options: Optional[abi.Options], kinetic_options: Optional[abi.KineticOptions],
+                     track_weights: str = "reference", track_scale: float = 1.0) -> dict:
+    """what estimate_kinetics sets up before the solver call: initial guess, contacts, stance, the force profile or its boxes, options, priors;
+    with track_weights="posterior" also cov_u [N, 28, 28] of the kinematic estimate (weighted = True)"""
     params, scene, sk = est.params, est.scene, est.skeleton
     if est.kinematic_model:
         raise AssertionError("Dynamic model of the cheetah is required.")          # the reference asserts hasattr(model, 'eom_f')
@@ -1279,7 +1318,8 @@ def _kinetic_prepare(est: CheetahEstimator, auto: bool, use_2d_reprojections: bo
     if params.enable_shutter_delay_estimation and scene.cam_idx is None:
         raise NotImplementedError("shutter delays are estimated by estimate_kinematics only (cpe_solve_shutter); not inside the physics-based model")
     data_dir = params.data_dir if out_dir_prefix is None else os.path.join(out_dir_prefix, est.data_path)
-    fte = load_result_pickle(kinematic_result_path(data_dir, scene.cam_idx, init_prev_kinematic_solution))
+    kin_path = kinematic_result_path(data_dir, scene.cam_idx, init_prev_kinematic_solution)
+    fte = load_result_pickle(kin_path)
     est.com_vel, est.com_pos = fte["com_vel"], fte["com_pos"]
     N = params.end_frame - params.start_frame
     if init_prev_kinematic_solution:
@@ -1348,6 +1388,8 @@ def _kinetic_prepare(est: CheetahEstimator, auto: bool, use_2d_reprojections: bo
     if not use_2d_reprojections:                                                     # the 3D kinematic cost (acinoset_opt.py:911-913): the target is
         q_target = np.ascontiguousarray(fte["q"][:N], dtype=np.float64)              # init_q, the stored kinematic solution (:739-744)
         tracked_motion_options(ko, scene.fps)
+    weighted = q_target is not None and track_weights == "posterior"
+    cov_u = load_posterior_blocks(kin_path, N) if weighted else None
     if disable_motion_prior:
         ko.w_torque, ko.w_smooth = 0.0, 0.0                                          # acinoset_opt.py:918-920
     if est.bound_eom_error is not None:
@@ -1355,7 +1397,7 @@ def _kinetic_prepare(est: CheetahEstimator, auto: bool, use_2d_reprojections: bo
     skk = skeleton.without_motion_model(sk)              # the physics-based cost has no constant-acceleration term (acinoset_opt.py:905-921)
     variant = "fixed" if grf_fixed is not None else ("force_box" if grf_box is not None else "free")
     return dict(q_init=q_init, stance=stance, grf_fixed=grf_fixed, grf_box=grf_box, pri=pri, opts=opts, ko=ko, skeleton=skk, N=N, variant=variant,
-                q_target=q_target, tracked=q_target is not None)
+                q_target=q_target, tracked=q_target is not None, weighted=weighted, cov_u=cov_u, track_scale=float(track_scale))
 
 
 def _kinetic_finish(est: CheetahEstimator, h, res: dict, seconds: float, prep: dict, solver_output: bool, out_fname: str,
@@ -1404,13 +1446,15 @@ def _copy_kinetic_options(o: abi.KineticOptions) -> abi.KineticOptions:
 
 
 def kinetic_ragged_group_key(sk: abi.Skeleton, opts: abi.Options, ko: abi.KineticOptions, pri: Optional[abi.Priors], variant: str, device: int,
-                             tracked: bool = False) -> tuple:
+                             tracked: bool = False, track_weights: str = "reference") -> tuple:
     """What sequences must share to go through one cpe_solve_kinetic_ragged call (Handle.multi): the skeleton's shape, the solver options the LM
     driver reads per batch, the kinetic option fields that fix every node's unknowns and rows (_lib.kinetic_shape_signature), the priors, the
     variant (free, prescribed or boxed foot forces), the device and the mode (2D reprojections, or the 3D kinematic cost: tracked = True,
-    cpe_solve_kinetic_tracked_ragged).  Rig, length, frame rate, masses and the other kinetic options may differ."""
+    cpe_solve_kinetic_tracked_ragged; with track_weights = "posterior" its full-weight form, cpe_solve_kinetic_tracked_weighted_ragged).  Rig,
+    length, frame rate, masses and the other kinetic options may differ."""
+    mode = "2d" if not tracked else ("tracked" if track_weights == "reference" else "tracked-" + track_weights)
     return (_lib.shape_signature(sk), _lib.shared_options_signature(opts), _lib.kinetic_shape_signature(ko), None if pri is None else _struct_bytes(pri),
-            variant, device, "tracked" if tracked else "2d")
+            variant, device, mode)
 
 
 def _kinetic_model_bytes(est: CheetahEstimator, prep: dict) -> bytes:
@@ -1430,7 +1474,8 @@ def estimate_kinetics_batch(estimators: Sequence[CheetahEstimator], init_torques
                             disable_pose_prior: bool = False, disable_motion_prior: bool = False, plot: bool = False, out_fname: str = "fte",
                             out_dir_prefix: Optional[str] = None, options: Optional[abi.Options] = None,
                             kinetic_options: Optional[abi.KineticOptions] = None, ragged: bool = False, uncertainty: bool = False,
-                            uncertainty_ridge: float = 0.0, uncertainty_rates: bool = False, uncertainty_spans=None) -> List[bool]:
+                            uncertainty_ridge: float = 0.0, uncertainty_rates: bool = False, uncertainty_spans=None,
+                            track_weights: str = "reference", track_scale: float = 1.0) -> List[bool]:
     """estimate_kinetics for MANY sequences at once, with its keyword arguments (applied to every sequence).  Each sequence is prepared as
     estimate_kinetics prepares it (the per-frame force fit of the fix_grf=True, synthesised_grf=False branch included, one sequence at a time),
     then solved in a batch, then gets its centre of mass, costs and files exactly as estimate_kinetics writes them; only processing_time_s (its
@@ -1442,9 +1487,11 @@ def estimate_kinetics_batch(estimators: Sequence[CheetahEstimator], init_torques
     (covariance_kinetic_host; ragged: covariance_kinetic_ragged_host); every sequence's est.uncertainty and uncertainty.npz are bit-equal to those of
     its own estimate_kinetics call.  A sequence without a factor does not stop the batch: every sequence is finished and stored first, then ONE
     CpeError names all of them.  uncertainty_rates=True: as in estimate_kinetics, one rate call after each covariance call, same bit-equality.
-    uncertainty_spans: as in estimate_kinetics, resolved for every sequence; one cpe_covariance_columns call per group, same bit-equality."""
+    uncertainty_spans: as in estimate_kinetics, resolved for every sequence; one cpe_covariance_columns call per group, same bit-equality.
+    track_weights / track_scale: as in estimate_kinetics; "posterior" makes ONE cpe_track_precision call per group on the group's handle."""
     _check_rates(uncertainty, uncertainty_rates)
     _check_spans(uncertainty, uncertainty_spans)
+    _check_track_weights(track_weights, track_scale, use_2d_reprojections)
     if uncertainty and not use_2d_reprojections:
         raise NotImplementedError("uncertainty together with use_2d_reprojections=False: cpe_covariance_kinetic takes the reprojection cost; the covariance "
                                   "of the 3D kinematic cost (cpe_solve_kinetic_tracked) is not built")
@@ -1456,12 +1503,15 @@ def estimate_kinetics_batch(estimators: Sequence[CheetahEstimator], init_torques
     for i, est in enumerate(ests):
         p = _kinetic_prepare(est, auto, use_2d_reprojections, init_prev_kinematic_solution, synthesised_grf, no_slip, joint_estimation, fix_grf,
                              ground_constraint, disable_pose_prior, disable_motion_prior, out_dir_prefix,
-                             None if options is None else _copy_options(options), None if kinetic_options is None else _copy_kinetic_options(kinetic_options))
+                             None if options is None else _copy_options(options), None if kinetic_options is None else _copy_kinetic_options(kinetic_options),
+                             track_weights=track_weights, track_scale=track_scale)
         prepared[i] = p
         if ragged:
-            key = kinetic_ragged_group_key(p["skeleton"], p["opts"], p["ko"], p["pri"], p["variant"], est.device, tracked=p["tracked"])
+            key = kinetic_ragged_group_key(p["skeleton"], p["opts"], p["ko"], p["pri"], p["variant"], est.device, tracked=p["tracked"],
+                                           track_weights=track_weights)
         else:
-            key = (_kinetic_model_bytes(est, p), p["N"], None if p["pri"] is None else _struct_bytes(p["pri"]), p["variant"], est.device, p["tracked"])
+            key = (_kinetic_model_bytes(est, p), p["N"], None if p["pri"] is None else _struct_bytes(p["pri"]), p["variant"], est.device, p["tracked"],
+                   p["weighted"])
         groups.setdefault(key, []).append(i)
     if uncertainty:                                  # what is refused, before anything is solved
         for idx in groups.values():
@@ -1500,7 +1550,11 @@ def _solve_kinetic_group(ests, idx, prepared, out, solver_output, out_fname, out
     try:
         t0 = time()
         meas, weight = np.stack([ests[i].meas for i in idx]), np.stack([ests[i].weight for i in idx])
-        if p0["tracked"]:
+        if p0["weighted"]:
+            W = h.track_precision_host(stack("cov_u"), p0["track_scale"])
+            res = h.solve_kinetic_tracked_weighted_host(p0["ko"], W, stack("q_init"), stack("q_target"), stack("stance"), meas, weight,
+                                                        grf_fixed=stack("grf_fixed"), grf_box=stack("grf_box"))
+        elif p0["tracked"]:
             res = h.solve_kinetic_tracked_host(p0["ko"], stack("q_init"), stack("q_target"), stack("stance"), meas, weight, grf_fixed=stack("grf_fixed"),
                                                grf_box=stack("grf_box"))
         else:
@@ -1535,7 +1589,12 @@ def _solve_kinetic_ragged_group(ests, idx, prepared, out, solver_output, out_fna
         force = "grf_fixed" if p0["variant"] == "fixed" else ("grf_box" if p0["variant"] == "force_box" else None)
         t0 = time()
         fkw = {} if force is None else {force: [prepared[i][force] for i in idx]}
-        if p0["tracked"]:
+        if p0["weighted"]:
+            W = h.track_precision_host([prepared[i]["cov_u"] for i in idx], p0["track_scale"], model_list=of)
+            res = h.solve_kinetic_tracked_weighted_ragged_host([prepared[i]["ko"] for i in reps], W, [prepared[i]["q_init"] for i in idx],
+                                                               [prepared[i]["q_target"] for i in idx], [prepared[i]["stance"] for i in idx],
+                                                               [ests[i].meas for i in idx], [ests[i].weight for i in idx], of, **fkw)
+        elif p0["tracked"]:
             res = h.solve_kinetic_tracked_ragged_host([prepared[i]["ko"] for i in reps], [prepared[i]["q_init"] for i in idx],
                                                       [prepared[i]["q_target"] for i in idx], [prepared[i]["stance"] for i in idx],
                                                       [ests[i].meas for i in idx], [ests[i].weight for i in idx], of, **fkw)

@@ -512,6 +512,53 @@ cpe_status cpe_solve_kinetic_tracked_ragged_host(cpe_handle* h, const cpe_kineti
 cpe_status cpe_eval_normal_tracked(cpe_handle* h, const double* track_w, int32_t B, int32_t N, const double* q, const double* q_target, double* g,
                                    double* Bm, double* cost, double* gam, double* q_out);
 
+/* ---- the 3D kinematic cost with the kinematic posterior as its weights (estimate_kinetics(track_weights="posterior")).  Frame n
+ * is tracked with its own symmetric matrix,
+ *     T_n = (x_n - x*_n)^T W_n (x_n - x*_n),        W_n = (scale / 2) (X Sigma_nn X^T)^-1,        X = dx/du of the cost view,
+ * the per-frame Laplace surrogate of the reprojection cost: Sigma_nn is the frame's block of cpe_covariance's cov_diag.  The marginal block
+ * ignores the posterior's correlation between frames, so the motion model's information is counted in every frame it touched: `scale` is the
+ * caller's handle on that.
+ * cpe_track_precision: cov_diag, W [B][N][CPE_NX][CPE_NX] (device pointers; _host: host pointers), scale finite and > 0; model / n_frames [B]
+ * (HOST) as cpe_solve_ragged's with N = N_max, or both NULL (B sequences of N frames of the first model).  W_n is bit-symmetric.  A block
+ * without a Cholesky factor (a pivot that is not positive and finite) gets W_n = 0 and the call returns CPE_NUMERICAL, cpe_last_error() naming
+ * the first such sequence and frame; the other frames are written.  Frames past a sequence's own are not written (_host: they come back zero).
+ * NULL cov_diag or W, or a bad scale: CPE_BAD_ARG, cpe_last_error() naming the argument. */
+cpe_status cpe_track_precision(cpe_handle* h, int32_t B, int32_t N, const int32_t* model /*[B] host or NULL*/, const int32_t* n_frames /*[B] host or NULL*/,
+                               const double* cov_diag, double scale, double* W);
+cpe_status cpe_track_precision_host(cpe_handle* h, int32_t B, int32_t N, const int32_t* model, const int32_t* n_frames, const double* cov_diag,
+                                    double scale, double* W);
+/* cpe_solve_kinetic_tracked* with track_W [B][N][CPE_NX][CPE_NX] (x-space; a device pointer, a host pointer in the _host forms) in place of
+ * track_w; every other argument, layout, output and the ragged contract are theirs, and cpe_stats.cost_meas reports sum_n T_n.  Every W_n must
+ * be symmetric and positive semi-definite: positive semi-definiteness is the caller's contract and is not checked (an indefinite W_n gives an
+ * indefinite Gauss-Newton block).  Refused with CPE_BAD_ARG before anything is launched, cpe_last_error() naming the argument: NULL track_W or
+ * q_target, meas without weight (or weight without meas), a non-finite entry of q_target; and, in the _host forms only (the device forms do not
+ * copy 6 KB per frame back), within a sequence's own frames a non-finite entry of track_W, a negative diagonal entry, or W[i][j] != W[j][i]. */
+cpe_status cpe_solve_kinetic_tracked_weighted(cpe_handle* h, const cpe_kinetic_options* opt, const double* track_W, int32_t B, int32_t N,
+                                              const double* q_init, const double* q_target, const double* meas, const double* weight, const int32_t* stance,
+                                              const double* grf_fixed, const double* tau_box, const double* grf_box, double* q, double* dq, double* ddq,
+                                              double* positions, double* meas_err, double* tau, double* lambda, double* grf, double* slack, cpe_stats* stats,
+                                              cpe_kinetic_stats* kstats);
+cpe_status cpe_solve_kinetic_tracked_weighted_host(cpe_handle* h, const cpe_kinetic_options* opt, const double* track_W, int32_t B, int32_t N,
+                                                   const double* q_init, const double* q_target, const double* meas, const double* weight,
+                                                   const int32_t* stance, const double* grf_fixed, const double* tau_box, const double* grf_box, double* q,
+                                                   double* dq, double* ddq, double* positions, double* meas_err, double* tau, double* lambda, double* grf,
+                                                   double* slack, cpe_stats* stats, cpe_kinetic_stats* kstats);
+cpe_status cpe_solve_kinetic_tracked_weighted_ragged(cpe_handle* h, const cpe_kinetic_options* opts, const double* track_W, int32_t B, int32_t N_max,
+                                                     const int32_t* model /*[B] host*/, const int32_t* n_frames /*[B] host*/, const double* q_init,
+                                                     const double* q_target, const double* meas, const double* weight, const int32_t* stance,
+                                                     const double* grf_fixed, const double* tau_box, const double* grf_box, double* q, double* dq, double* ddq,
+                                                     double* positions, double* meas_err, double* tau, double* lambda, double* grf, double* slack,
+                                                     cpe_stats* stats, cpe_kinetic_stats* kstats);
+cpe_status cpe_solve_kinetic_tracked_weighted_ragged_host(cpe_handle* h, const cpe_kinetic_options* opts, const double* track_W, int32_t B, int32_t N_max,
+                                                          const int32_t* model, const int32_t* n_frames, const double* q_init, const double* q_target,
+                                                          const double* meas, const double* weight, const int32_t* stance, const double* grf_fixed,
+                                                          const double* tau_box, const double* grf_box, double* q, double* dq, double* ddq,
+                                                          double* positions, double* meas_err, double* tau, double* lambda, double* grf, double* slack,
+                                                          cpe_stats* stats, cpe_kinetic_stats* kstats);
+/* cpe_eval_normal_tracked with track_W [B][N][CPE_NX][CPE_NX] (device pointer) in place of track_w */
+cpe_status cpe_eval_normal_tracked_weighted(cpe_handle* h, const double* track_W, int32_t B, int32_t N, const double* q, const double* q_target, double* g,
+                                            double* Bm, double* cost, double* gam, double* q_out);
+
 /* diagnostic building block of cpe_solve_kinetic (as cpe_eval_normal is of cpe_solve): ONE evaluation of the physics terms of every node at
  * Euler q, multipliers zero, forces from a cold start -- what ASL hands IPOPT per node for the constraints of make_pyomo_model(include_eom_slack=True)
  * (acinoset_opt.py:510-514) after the node forces are minimised out.  Device pointers, each may be NULL: f [B][N][64] node forces (tau | lambda |

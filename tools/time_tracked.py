@@ -1,6 +1,8 @@
 """Developer tool (not part of the product or the tests): times the physics-based solve at config 4's shape -- phantom, six cameras, gallop, N = 200,
 B sequences, free foot forces -- with the 2D reprojection cost (cpe_solve_kinetic) and with the 3D kinematic cost (cpe_solve_kinetic_tracked,
-estimate_kinetics(use_2d_reprojections=False)), from the same start, the tracked solve's target being the start itself.  Prints one JSON line per
+estimate_kinetics(use_2d_reprojections=False)) and with its full-weight form (cpe_solve_kinetic_tracked_weighted, track_weights="posterior":
+W from one cpe_track_precision call on synthetic covariance blocks, standard deviations over two decades), from the same start, the tracked
+solves' target being the start itself.  Prints one JSON line per
 mode: solves/s of the timed solve and the per-kernel milliseconds per launch of the handle's HIP-event profile of the untimed warm-up solve (slot
 k_frame_normal holds k_frame_tracked in the tracked mode).  The numbers quoted in DESIGN.md section 4.
 
@@ -42,13 +44,22 @@ def main():
     out = dict(q=E(B, N, 54), dq=E(B, N, 54), ddq=E(B, N, 54), positions=E(B, N, 24, 3), meas_err=E(B, N, 6, 24, 2), tau=E(B, N, nm),
                lam=E(B, N, nc), grf=E(B, N, nf, 5), slack=E(B, N, 54))
     ko = abi.default_kinetic_options(skeleton.dyn_options("phantom"), 120.0)
-    for mode in ("2d", "tracked"):
-        if mode == "tracked":
+    rng = np.random.default_rng(7)
+    A = rng.standard_normal((8, N, 28, 28)) / np.sqrt(28.0)
+    s = 10.0 ** rng.uniform(-2.0, 0.0, (8, N, 28))
+    S = A @ np.swapaxes(A, -1, -2) + 0.5 * np.eye(28)
+    cov = torch.tensor(rep(s[..., :, None] * (0.5 * (S + np.swapaxes(S, -1, -2))) * s[..., None, :]), device=dev)
+    W = E(B, N, 28, 28)
+    h.track_precision(cov, W)
+    for mode in ("2d", "tracked", "weighted"):
+        if mode != "2d":
             ko.w_torque, ko.w_smooth = 1.0 + 1e-3 / 120.0 ** 2, 0.0
         run = (lambda: h.solve_kinetic(ko, T["q_init"], T["meas"], T["weight"], T["stance"], out["q"], out["dq"], out["ddq"], out["positions"],
                                        out["meas_err"], out["tau"], out["lam"], out["grf"], out["slack"])) if mode == "2d" else \
               (lambda: h.solve_kinetic_tracked(ko, T["q_init"], T["q_init"], T["stance"], out["q"], out["dq"], out["ddq"], out["positions"],
-                                               tau=out["tau"], lam=out["lam"], grf=out["grf"], slack=out["slack"]))
+                                               tau=out["tau"], lam=out["lam"], grf=out["grf"], slack=out["slack"])) if mode == "tracked" else \
+              (lambda: h.solve_kinetic_tracked_weighted(ko, W, T["q_init"], T["q_init"], T["stance"], out["q"], out["dq"], out["ddq"], out["positions"],
+                                                        tau=out["tau"], lam=out["lam"], grf=out["grf"], slack=out["slack"]))
         h.profile(True)
         run(); h.synchronize()
         prof = h.profile_totals()
