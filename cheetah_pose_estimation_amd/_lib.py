@@ -198,8 +198,18 @@ def _ptr(t):
 
 
 def _force_slots(variant, array) -> list:
-    """the grf_fixed, tau_box, grf_box pointer arguments of a host entry: `array` in its variant's place, null in the others"""
+    """the grf_fixed, tau_box, grf_box pointer arguments of an entry: `array` in its variant's place, null in the others"""
     return [_ptr(array) if variant == k else None for k in FORCE_VARIANTS]
+
+
+def _f64(a, optional: bool = False):
+    """a as a C-contiguous float64 array; optional: None stays None (an argument the entry may take as null)"""
+    return None if optional and a is None else np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _int32s(B: int, values=()):
+    """the c_int32 array of a call over B sequences: their model indices or frame counts, or (no values) room for their statuses"""
+    return (C.c_int32 * max(B, 1))(*[int(v) for v in values])
 
 
 class Handle:
@@ -403,7 +413,7 @@ class Handle:
         (one per sequence).  Returns (status, [Stats])."""
         B, N = q_init.shape[0], q_init.shape[1]
         stats = (abi.Stats * max(B, 1))()
-        mo, nf = (C.c_int32 * max(B, 1))(*[int(m) for m in model]), (C.c_int32 * max(B, 1))(*[int(n) for n in n_frames])
+        mo, nf = _int32s(B, model), _int32s(B, n_frames)
         st = self._call(self.lib.cpe_solve_ragged, "cpe_solve_ragged", B, N, mo, nf, _ptr(q_init), _ptr(meas), _ptr(weight), _ptr(q), _ptr(dq),
                         _ptr(ddq), _ptr(positions), _ptr(meas_err), stats, allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
         return st, list(stats)[:B]
@@ -457,15 +467,26 @@ class Handle:
     def solve_kinetic(self, kopts, q_init, meas, weight, stance, q, dq, ddq, positions, meas_err, tau=None, lam=None, grf=None, slack=None, grf_fixed=None, tau_box=None, grf_box=None):
         """device tensors (stance int32 [B, N, n_feet]; at most one of: grf_fixed [B, N, n_feet, 3] = prescribed net foot forces, tau_box [B, N, n_motors, 2] =
         (lower, upper) bound of every torque, grf_box [B, N, n_feet, 3, 2] = (lower, upper) of the net (z, x, y) foot forces); returns (status, [Stats], [KineticStats])"""
-        B, N = q_init.shape[0], q_init.shape[1]
-        stats = (abi.Stats * max(B, 1))(); ks = (abi.KineticStats * max(B, 1))()
         variant, force = _force_variant("solve_kinetic", grf_fixed, tau_box, grf_box,
                                         "prescribed foot forces, torque boxes and force boxes are separate entry points")
-        fn = {"tau_box": self.lib.cpe_solve_kinetic_bounded, "grf_box": self.lib.cpe_solve_kinetic_force_box}.get(
-            variant, self.lib.cpe_solve_kinetic_fixed)
-        st = self._call(fn, "cpe_solve_kinetic", C.byref(kopts), B, N, _ptr(q_init), _ptr(meas), _ptr(weight), _ptr(stance), _ptr(force), _ptr(q), _ptr(dq),
-                        _ptr(ddq), _ptr(positions), _ptr(meas_err), _ptr(tau), _ptr(lam), _ptr(grf), _ptr(slack), stats, ks,
-                        allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
+        entry = {"tau_box": "cpe_solve_kinetic_bounded", "grf_box": "cpe_solve_kinetic_force_box"}.get(variant, "cpe_solve_kinetic_fixed")
+        return self._solve_kinetic_entry(entry, C.byref(kopts), (), (), [q_init, meas, weight], stance, [_ptr(force)],
+                                         [q, dq, ddq, positions, meas_err, tau, lam, grf, slack], what="cpe_solve_kinetic")
+
+    def _solve_kinetic_entry(self, entry, ko, track, ragged, arrays, stance, forces, outputs, what=None):
+        """The one argument list of the physics-based solves, whatever the entry (all ten wrappers end here): ko (the kinetic options by
+        reference, or the array of a ragged entry), track (nothing, or for the 3D kinematic cost the one array track_w / track_W: held here, so
+        that it outlives the call), B, N, ragged (model, n_frames, or nothing), arrays (q_init, [q_target], meas, weight), stance, forces (the
+        entry's force slots, as pointers), the nine outputs in KINETIC_OUTPUTS' order, stats.  A *_host entry takes host pointers and is called
+        directly; any other takes device tensors and goes through _call (stream bracketing; `what` names it in an error, default the entry).
+        Returns (status, [Stats], [KineticStats]); raises CpeError unless the status is OK, MAX_ITER or NUMERICAL."""
+        host = entry.endswith("_host")
+        B, N = arrays[0].shape[0], arrays[0].shape[1]
+        stats = (abi.Stats * max(B, 1))(); ks = (abi.KineticStats * max(B, 1))()
+        args = [ko, *[_ptr(t) for t in track], B, N, *ragged, *[_ptr(a) for a in arrays], stance.ctypes.data if host else _ptr(stance), *forces,
+                *[_ptr(a) for a in outputs], stats, ks]
+        fn, allow = getattr(self.lib, entry), (abi.OK, abi.MAX_ITER, abi.NUMERICAL)
+        st = _check(fn(self._h, *args), entry, allow) if host else self._call(fn, what or entry, *args, allow=allow)
         return st, list(stats)[:B], list(ks)[:B]
 
     def n_constraint_rows(self):
@@ -503,17 +524,13 @@ class Handle:
         """cpe_solve_kinetic_ragged on device tensors laid out for N_max = q_init.shape[1] frames and C_max cameras; kopts_list: one
         KineticOptions per model of the handle; model / n_frames: int sequences (one per sequence); at most one of grf_fixed / tau_box / grf_box
         (the variant of the whole batch).  Returns (status, [Stats], [KineticStats])."""
-        _force_variant("solve_kinetic_ragged", grf_fixed, tau_box, grf_box)
+        forces = _force_slots(*_force_variant("solve_kinetic_ragged", grf_fixed, tau_box, grf_box))
         ko = self._kinetic_options_array(kopts_list)
-        B, N = q_init.shape[0], q_init.shape[1]
+        B = q_init.shape[0]
         if len(model) != B or len(n_frames) != B:
             raise ValueError("solve_kinetic_ragged: one model index and one frame count per sequence")
-        stats = (abi.Stats * max(B, 1))(); ks = (abi.KineticStats * max(B, 1))()
-        mo, nf = (C.c_int32 * max(B, 1))(*[int(m) for m in model]), (C.c_int32 * max(B, 1))(*[int(n) for n in n_frames])
-        st = self._call(self.lib.cpe_solve_kinetic_ragged, "cpe_solve_kinetic_ragged", ko, B, N, mo, nf, _ptr(q_init), _ptr(meas), _ptr(weight),
-                        _ptr(stance), _ptr(grf_fixed), _ptr(tau_box), _ptr(grf_box), _ptr(q), _ptr(dq), _ptr(ddq), _ptr(positions), _ptr(meas_err),
-                        _ptr(tau), _ptr(lam), _ptr(grf), _ptr(slack), stats, ks, allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
-        return st, list(stats)[:B], list(ks)[:B]
+        return self._solve_kinetic_entry("cpe_solve_kinetic_ragged", ko, (), [_int32s(B, model), _int32s(B, n_frames)], [q_init, meas, weight], stance, forces,
+                                         [q, dq, ddq, positions, meas_err, tau, lam, grf, slack])
 
     def solve_kinetic_ragged_host(self, kopts_list, q_init_list, meas_list, weight_list, stance_list, model_list=None, grf_fixed=None, tau_box=None,
                                   grf_box=None):
@@ -522,20 +539,30 @@ class Handle:
         grf_fixed / tau_box / grf_box, each a list of one array per sequence ([N_b, n_feet, 3] / [N_b, n_motors, 2] / [N_b, n_feet, 3, 2]).
         Pads, solves, unpads: returns dict(status, q, dq, ddq, positions, meas_err, tau, lam, grf, slack = lists of per-sequence arrays, stats,
         kstats = lists, padded = the padded outputs)."""
-        who = "solve_kinetic_ragged_host"
-        variant, force = _force_variant(who, grf_fixed, tau_box, grf_box)
-        p = self._ragged_batch(who, "one q_init, meas, weight, stance, model (and force array)", model_list, kopts_list, variant,
-                               q_init=q_init_list, meas=meas_list, weight=weight_list, stance=stance_list, force=force)
-        B, Nm = p["q_init"].shape[:2]
-        out = self._solve_outputs(B, Nm, kopts_list[0])
-        stats = (abi.Stats * max(B, 1))(); ks = (abi.KineticStats * max(B, 1))()
-        ko = self._kinetic_options_array(kopts_list)
-        st = self.lib.cpe_solve_kinetic_ragged_host(self._h, ko, B, Nm, p["model_arr"], p["len_arr"], _ptr(p["q_init"]), _ptr(p["meas"]), _ptr(p["weight"]),
-                                                    p["stance"].ctypes.data, *_force_slots(variant, p["force"]),
-                                                    *[_ptr(out[k]) for k in KINETIC_OUTPUTS], stats, ks)
-        _check(st, "cpe_solve_kinetic_ragged_host", allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
+        return self._solve_kinetic_ragged_host("cpe_solve_kinetic_ragged_host", "one q_init, meas, weight, stance, model (and force array)", kopts_list,
+                                               model_list, (grf_fixed, tau_box, grf_box), q_init=q_init_list, meas=meas_list, weight=weight_list,
+                                               stance=stance_list)
+
+    def _solve_kinetic_host_entry(self, entry, kopts, ko, track, ragged, p, variant):
+        """What every pointer-host form of the physics-based solve ends with.  p: its converted (ragged: padded) inputs under pad_kinetic's names,
+        a q_target only for the 3D kinematic cost; kopts: the options that size the outputs; ko, track, ragged: as _solve_kinetic_entry takes them.
+        Allocates the outputs (no meas_err without meas) and calls.  Returns them, [B, N, ...] each, and dict(status, stats, kstats)."""
+        B, N = p["q_init"].shape[:2]
+        out = self._solve_outputs(B, N, kopts, meas_err=p["meas"] is not None)
+        st, stats, ks = self._solve_kinetic_entry(entry, ko, track, ragged, [p[k] for k in ("q_init", "q_target", "meas", "weight") if k in p], p["stance"],
+                                                  _force_slots(variant, p["force"]), [out[k] for k in KINETIC_OUTPUTS])
+        return out, dict(status=st, stats=stats, kstats=ks)
+
+    def _solve_kinetic_ragged_host(self, entry, each, kopts_list, model_list, forces, track=None, **lists):
+        """The three ragged pointer-host forms: force variant, _ragged_batch's checks and padding of `lists` (each: how its error names them), the
+        entry, unpadding.  track(p): the track_w / track_W array of an entry of the 3D kinematic cost, made from the padded batch p."""
+        who = entry[len("cpe_"):]
+        variant, force = _force_variant(who, *forces)
+        p = self._ragged_batch(who, each, model_list, kopts_list, variant, **lists, force=force)
+        ko, track = self._kinetic_options_array(kopts_list), [] if track is None else [track(p)]
+        out, tail = self._solve_kinetic_host_entry(entry, kopts_list[0], ko, track, [p["model_arr"], p["len_arr"]], p, variant)
         res = unpad_kinetic(out, p["lens"], p["cams"])
-        res.update(status=st, stats=list(stats)[:B], kstats=list(ks)[:B], padded=out)
+        res.update(tail, padded=out)
         return res
 
     def _ragged_batch(self, who, each, model_list, kopts_list=None, variant=None, **lists) -> dict:
@@ -567,7 +594,7 @@ class Handle:
                 raise ValueError(f"{who}: sequence {b} does not have the shapes of its model ({n} frames, {c} cameras)")
         pad = pad_kinetic_tracked if "q_target" in lists else pad_kinetic
         p = pad(n_cams_max=self.n_cams, **{k + "_list": v for k, v in lists.items()})
-        p.update(models=models, cams=[ncams[m] for m in models], model_arr=(C.c_int32 * max(B, 1))(*models), len_arr=(C.c_int32 * max(B, 1))(*p["lens"]))
+        p.update(models=models, cams=[ncams[m] for m in models], model_arr=_int32s(B, models), len_arr=_int32s(B, p["lens"]))
         return p
 
     # ---- physics-based solve with the 3D kinematic cost (estimate_kinetics(use_2d_reprojections=False); include/cpe.h) ----------------------
@@ -575,57 +602,40 @@ class Handle:
                               grf=None, slack=None, grf_fixed=None, tau_box=None, grf_box=None, track_w=None):
         """cpe_solve_kinetic_tracked on device tensors (q_target [B, N, nq]; meas / weight may be None together, meas_err is then not written);
         track_w: None (the reference's weights) or NX numbers (host).  Returns (status, [Stats], [KineticStats])"""
-        _force_variant("solve_kinetic_tracked", grf_fixed, tau_box, grf_box)
-        B, N = q_init.shape[0], q_init.shape[1]
-        w = track_weights(track_w, 1)
-        stats = (abi.Stats * max(B, 1))(); ks = (abi.KineticStats * max(B, 1))()
-        st = self._call(self.lib.cpe_solve_kinetic_tracked, "cpe_solve_kinetic_tracked", C.byref(kopts), w.ctypes.data, B, N, _ptr(q_init), _ptr(q_target),
-                        _ptr(meas), _ptr(weight), _ptr(stance), _ptr(grf_fixed), _ptr(tau_box), _ptr(grf_box), _ptr(q), _ptr(dq), _ptr(ddq),
-                        _ptr(positions), _ptr(meas_err), _ptr(tau), _ptr(lam), _ptr(grf), _ptr(slack), stats, ks, allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
-        return st, list(stats)[:B], list(ks)[:B]
+        forces = _force_slots(*_force_variant("solve_kinetic_tracked", grf_fixed, tau_box, grf_box))
+        return self._solve_kinetic_entry("cpe_solve_kinetic_tracked", C.byref(kopts), [track_weights(track_w, 1)], (),
+                                         [q_init, q_target, meas, weight], stance, forces, [q, dq, ddq, positions, meas_err, tau, lam, grf, slack])
+
+    def _solve_kinetic_tracked_host(self, entry, kopts, track, q_init, q_target, stance, meas, weight, forces):
+        """The two plain pointer-host forms of the 3D kinematic cost: force variant, meas and weight together, conversion, q_target's shape, then
+        track(p) -> the entry's track_w / track_W array with its own checks made, the entry, solve_kinetic_host's dict.  A null q_init fails
+        here; a null q_target goes to the library, which refuses it."""
+        who = entry[len("cpe_"):]
+        variant, force = _force_variant(who, *forces)
+        if (meas is None) != (weight is None):
+            raise ValueError(f"{who}: meas and weight are given together or not at all")
+        p = {k: _f64(a, optional=True) for k, a in (("q_init", q_init), ("q_target", q_target), ("meas", meas), ("weight", weight), ("force", force))}
+        p["stance"] = np.ascontiguousarray(stance, dtype=np.int32)
+        if p["q_target"] is not None and p["q_target"].shape != p["q_init"].shape:
+            raise ValueError(f"{who}: q_target has q_init's shape")
+        out, tail = self._solve_kinetic_host_entry(entry, kopts, C.byref(kopts), [track(p)], (), p, variant)
+        out.update(tail)
+        return out
 
     def solve_kinetic_tracked_host(self, kopts, q_init, q_target, stance, meas=None, weight=None, grf_fixed=None, tau_box=None, grf_box=None,
                                    track_w=None):
         """cpe_solve_kinetic_tracked_host: numpy in, numpy out -- solve_kinetic_host's dict (meas_err None when meas is None)"""
-        variant, force = _force_variant("solve_kinetic_tracked_host", grf_fixed, tau_box, grf_box)
-        if (meas is None) != (weight is None):
-            raise ValueError("solve_kinetic_tracked_host: meas and weight are given together or not at all")
-        f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
-        qi, qt, me, we, fx = f64(q_init), f64(q_target), f64(meas), f64(weight), f64(force)
-        stn = np.ascontiguousarray(stance, dtype=np.int32)
-        B, N = qi.shape[0], qi.shape[1]
-        if qt.shape != qi.shape:
-            raise ValueError("solve_kinetic_tracked_host: q_target has q_init's shape")
-        out = self._solve_outputs(B, N, kopts, meas_err=me is not None)
-        w = track_weights(track_w, 1)
-        stats = (abi.Stats * max(B, 1))(); ks = (abi.KineticStats * max(B, 1))()
-        st = self.lib.cpe_solve_kinetic_tracked_host(self._h, C.byref(kopts), w.ctypes.data, B, N, _ptr(qi), _ptr(qt), _ptr(me), _ptr(we), stn.ctypes.data,
-                                                     *_force_slots(variant, fx), *[_ptr(out[k]) for k in KINETIC_OUTPUTS], stats, ks)
-        _check(st, "cpe_solve_kinetic_tracked_host", allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
-        out.update(status=st, stats=list(stats)[:B], kstats=list(ks)[:B])
-        return out
+        return self._solve_kinetic_tracked_host("cpe_solve_kinetic_tracked_host", kopts, lambda p: track_weights(track_w, 1), q_init, q_target, stance,
+                                                meas, weight, (grf_fixed, tau_box, grf_box))
 
     def solve_kinetic_tracked_ragged_host(self, kopts_list, q_init_list, q_target_list, stance_list, meas_list=None, weight_list=None, model_list=None,
                                           grf_fixed=None, tau_box=None, grf_box=None, track_w=None):
         """cpe_solve_kinetic_tracked_ragged_host over sequences of their own length and model (solve_kinetic_ragged_host's arguments and result,
         plus q_target [N_b, nq] per sequence; meas_list / weight_list may be None together, meas_err is then None); track_w: None, NX numbers
         for every model, or [n_models, NX]"""
-        who = "solve_kinetic_tracked_ragged_host"
-        variant, force = _force_variant(who, grf_fixed, tau_box, grf_box)
-        p = self._ragged_batch(who, "one q_init, q_target, stance, model (and meas, weight, force array)", model_list, kopts_list, variant,
-                               q_init=q_init_list, q_target=q_target_list, stance=stance_list, meas=meas_list, weight=weight_list, force=force)
-        B, Nm = p["q_init"].shape[:2]
-        out = self._solve_outputs(B, Nm, kopts_list[0], meas_err=meas_list is not None)
-        stats = (abi.Stats * max(B, 1))(); ks = (abi.KineticStats * max(B, 1))()
-        ko = self._kinetic_options_array(kopts_list)
-        w = track_weights(track_w, len(self.model_n_cams))
-        st = self.lib.cpe_solve_kinetic_tracked_ragged_host(self._h, ko, w.ctypes.data, B, Nm, p["model_arr"], p["len_arr"], _ptr(p["q_init"]),
-                                                            _ptr(p["q_target"]), _ptr(p["meas"]), _ptr(p["weight"]), p["stance"].ctypes.data,
-                                                            *_force_slots(variant, p["force"]), *[_ptr(out[k]) for k in KINETIC_OUTPUTS], stats, ks)
-        _check(st, "cpe_solve_kinetic_tracked_ragged_host", allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
-        res = unpad_kinetic(out, p["lens"], p["cams"])
-        res.update(status=st, stats=list(stats)[:B], kstats=list(ks)[:B], padded=out)
-        return res
+        return self._solve_kinetic_ragged_host("cpe_solve_kinetic_tracked_ragged_host", "one q_init, q_target, stance, model (and meas, weight, force array)",
+                                               kopts_list, model_list, (grf_fixed, tau_box, grf_box), lambda p: track_weights(track_w, len(self.model_n_cams)),
+                                               q_init=q_init_list, q_target=q_target_list, stance=stance_list, meas=meas_list, weight=weight_list)
 
     # ---- the 3D kinematic cost with the kinematic posterior as its weights (estimate_kinetics(track_weights="posterior"); include/cpe.h) --------
     def track_precision(self, cov_diag, W, scale=1.0, model=None, n_frames=None):
@@ -639,7 +649,7 @@ class Handle:
         if model is not None:
             if len(model) != B or len(n_frames) != B:
                 raise ValueError("track_precision: one model index and one frame count per sequence")
-            mo, nf = (C.c_int32 * max(B, 1))(*[int(m) for m in model]), (C.c_int32 * max(B, 1))(*[int(n) for n in n_frames])
+            mo, nf = _int32s(B, model), _int32s(B, n_frames)
         self._call(self.lib.cpe_track_precision, "cpe_track_precision", B, N, mo, nf, _ptr(cov_diag), float(scale), _ptr(W))
 
     def track_precision_host(self, cov_diag, scale=1.0, model_list=None):
@@ -652,9 +662,9 @@ class Handle:
             if len(models) != len(lens):
                 raise ValueError("track_precision_host: one model index per sequence")
             cd = pad_track_W(cov_diag)
-            mo, nf = (C.c_int32 * max(len(lens), 1))(*models), (C.c_int32 * max(len(lens), 1))(*lens)
+            mo, nf = _int32s(len(lens), models), _int32s(len(lens), lens)
         else:
-            cd = np.ascontiguousarray(cov_diag, dtype=np.float64)
+            cd = _f64(cov_diag)
             if cd.ndim != 4 or cd.shape[2:] != (abi.NX, abi.NX):
                 raise ValueError(f"track_precision_host: cov_diag is [B, N, {abi.NX}, {abi.NX}]")
             mo = nf = None
@@ -667,60 +677,36 @@ class Handle:
                                        tau=None, lam=None, grf=None, slack=None, grf_fixed=None, tau_box=None, grf_box=None):
         """cpe_solve_kinetic_tracked_weighted on device tensors: solve_kinetic_tracked with track_W [B, N, NX, NX] (symmetric, positive
         semi-definite: the caller's contract) in place of track_w.  Returns (status, [Stats], [KineticStats])"""
-        _force_variant("solve_kinetic_tracked_weighted", grf_fixed, tau_box, grf_box)
-        B, N = q_init.shape[0], q_init.shape[1]
-        stats = (abi.Stats * max(B, 1))(); ks = (abi.KineticStats * max(B, 1))()
-        st = self._call(self.lib.cpe_solve_kinetic_tracked_weighted, "cpe_solve_kinetic_tracked_weighted", C.byref(kopts), _ptr(track_W), B, N, _ptr(q_init),
-                        _ptr(q_target), _ptr(meas), _ptr(weight), _ptr(stance), _ptr(grf_fixed), _ptr(tau_box), _ptr(grf_box), _ptr(q), _ptr(dq), _ptr(ddq),
-                        _ptr(positions), _ptr(meas_err), _ptr(tau), _ptr(lam), _ptr(grf), _ptr(slack), stats, ks, allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
-        return st, list(stats)[:B], list(ks)[:B]
+        forces = _force_slots(*_force_variant("solve_kinetic_tracked_weighted", grf_fixed, tau_box, grf_box))
+        return self._solve_kinetic_entry("cpe_solve_kinetic_tracked_weighted", C.byref(kopts), [track_W], (), [q_init, q_target, meas, weight], stance,
+                                         forces, [q, dq, ddq, positions, meas_err, tau, lam, grf, slack])
 
     def solve_kinetic_tracked_weighted_host(self, kopts, track_W, q_init, q_target, stance, meas=None, weight=None, grf_fixed=None, tau_box=None,
                                             grf_box=None):
         """cpe_solve_kinetic_tracked_weighted_host: numpy in, numpy out -- solve_kinetic_tracked_host's arguments and dict with track_W
         [B, N, NX, NX] in place of track_w"""
         who = "solve_kinetic_tracked_weighted_host"
-        variant, force = _force_variant(who, grf_fixed, tau_box, grf_box)
-        if (meas is None) != (weight is None):
-            raise ValueError(f"{who}: meas and weight are given together or not at all")
-        f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
-        qi, qt, me, we, fx, W = f64(q_init), f64(q_target), f64(meas), f64(weight), f64(force), f64(track_W)
-        stn = np.ascontiguousarray(stance, dtype=np.int32)
-        B, N = qi.shape[0], qi.shape[1]
-        if qt is not None and qt.shape != qi.shape:
-            raise ValueError(f"{who}: q_target has q_init's shape")
-        if W is not None and W.shape != (B, N, abi.NX, abi.NX):
-            raise ValueError(f"{who}: track_W is [B, N, {abi.NX}, {abi.NX}]")
-        out = self._solve_outputs(B, N, kopts, meas_err=me is not None)
-        stats = (abi.Stats * max(B, 1))(); ks = (abi.KineticStats * max(B, 1))()
-        st = self.lib.cpe_solve_kinetic_tracked_weighted_host(self._h, C.byref(kopts), _ptr(W), B, N, _ptr(qi), _ptr(qt), _ptr(me), _ptr(we), stn.ctypes.data,
-                                                              *_force_slots(variant, fx), *[_ptr(out[k]) for k in KINETIC_OUTPUTS], stats, ks)
-        _check(st, "cpe_solve_kinetic_tracked_weighted_host", allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
-        out.update(status=st, stats=list(stats)[:B], kstats=list(ks)[:B])
-        return out
+
+        def track(p):
+            W = _f64(track_W, optional=True)
+            if W is not None and W.shape != p["q_init"].shape[:2] + (abi.NX, abi.NX):
+                raise ValueError(f"{who}: track_W is [B, N, {abi.NX}, {abi.NX}]")
+            return W
+        return self._solve_kinetic_tracked_host("cpe_" + who, kopts, track, q_init, q_target, stance, meas, weight,
+                                                (grf_fixed, tau_box, grf_box))
 
     def solve_kinetic_tracked_weighted_ragged_host(self, kopts_list, track_W_list, q_init_list, q_target_list, stance_list, meas_list=None,
                                                    weight_list=None, model_list=None, grf_fixed=None, tau_box=None, grf_box=None):
         """cpe_solve_kinetic_tracked_weighted_ragged_host: solve_kinetic_tracked_ragged_host's arguments and result with one track_W
         [N_b, NX, NX] per sequence in place of track_w"""
-        who = "solve_kinetic_tracked_weighted_ragged_host"
-        variant, force = _force_variant(who, grf_fixed, tau_box, grf_box)
-        p = self._ragged_batch(who, "one q_init, q_target, track_W, stance, model (and meas, weight, force array)", model_list, kopts_list, variant,
-                               q_init=q_init_list, q_target=q_target_list, stance=stance_list, meas=meas_list, weight=weight_list, force=force)
-        if len(track_W_list) != len(p["lens"]):
-            raise ValueError(f"{who}: one q_init, q_target, track_W, stance, model (and meas, weight, force array) per sequence")
-        W = pad_track_W(track_W_list, p["lens"])
-        B, Nm = p["q_init"].shape[:2]
-        out = self._solve_outputs(B, Nm, kopts_list[0], meas_err=meas_list is not None)
-        stats = (abi.Stats * max(B, 1))(); ks = (abi.KineticStats * max(B, 1))()
-        ko = self._kinetic_options_array(kopts_list)
-        st = self.lib.cpe_solve_kinetic_tracked_weighted_ragged_host(self._h, ko, _ptr(W), B, Nm, p["model_arr"], p["len_arr"], _ptr(p["q_init"]),
-                                                                     _ptr(p["q_target"]), _ptr(p["meas"]), _ptr(p["weight"]), p["stance"].ctypes.data,
-                                                                     *_force_slots(variant, p["force"]), *[_ptr(out[k]) for k in KINETIC_OUTPUTS], stats, ks)
-        _check(st, "cpe_solve_kinetic_tracked_weighted_ragged_host", allow=(abi.OK, abi.MAX_ITER, abi.NUMERICAL))
-        res = unpad_kinetic(out, p["lens"], p["cams"])
-        res.update(status=st, stats=list(stats)[:B], kstats=list(ks)[:B], padded=out)
-        return res
+        who, each = "solve_kinetic_tracked_weighted_ragged_host", "one q_init, q_target, track_W, stance, model (and meas, weight, force array)"
+
+        def track(p):                                   # after _ragged_batch: the count, then the frames of every track_W
+            if len(track_W_list) != len(p["lens"]):
+                raise ValueError(f"{who}: {each} per sequence")
+            return pad_track_W(track_W_list, p["lens"])
+        return self._solve_kinetic_ragged_host("cpe_" + who, each, kopts_list, model_list, (grf_fixed, tau_box, grf_box),
+                                               track, q_init=q_init_list, q_target=q_target_list, stance=stance_list, meas=meas_list, weight=weight_list)
 
     def eval_normal_tracked(self, q, q_target, g, Bm, cost, track_w=None, gam=None, q_out=None, track_W=None):
         """cpe_eval_normal_tracked on device tensors: the per-frame terms of the tracked solve (T_n, bounds, pose prior) at Euler q; track_W
@@ -796,8 +782,7 @@ class Handle:
         """cpe_eval_shutter_step_host: the first pass of a round of the shutter-delay estimation from Euler q at the delays tau [B, C] and damping
         lam.  numpy in, dict of numpy arrays out: g, g_total [B, N, 28], Bm [B, N, 28, 28], cost [B, N, 3], gx [B, N, 6], rcb [B, N, C, 9],
         step [B, C], meas_err [B, N, C, L, 2], seq [B, 8] (as eval_lm_step_host)"""
-        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-        q, meas, weight, tau = f64(q), f64(meas), f64(weight), f64(tau)
+        q, meas, weight, tau = _f64(q), _f64(meas), _f64(weight), _f64(tau)
         B, N = q.shape[:2]
         if tau.shape != (B, self.n_cams):
             raise CpeError("eval_shutter_step_host: one delay per sequence and camera")
@@ -828,7 +813,7 @@ class Handle:
         [B, N, pb, 28, 28], cov_pos [B, N, L, 3, 3], L [B, N, pb + 1, 28, 28] (each of the last three may be None).  Returns (status, [status of
         every sequence]): abi.OK, or abi.NUMERICAL where the matrix has no Cholesky factor (that sequence's outputs are zero)."""
         B, N = q.shape[0], q.shape[1]
-        seq = (C.c_int32 * max(B, 1))()
+        seq = _int32s(B)
         st = self._call(self.lib.cpe_covariance, "cpe_covariance", B, N, _ptr(q), _ptr(meas), _ptr(weight), float(ridge), _ptr(cov_diag), _ptr(cov_off),
                         _ptr(cov_pos), _ptr(L), seq, allow=(abi.OK, abi.NUMERICAL))
         return st, list(seq)[:B]
@@ -840,11 +825,10 @@ class Handle:
 
     def covariance_host(self, q, meas, weight, ridge=0.0, want_off=True, want_pos=True, want_L=False):
         """cpe_covariance_host: numpy in, dict of numpy arrays out (cov_diag, cov_off, cov_pos, L as in covariance(); status, seq_status)"""
-        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-        q, meas, weight = f64(q), f64(meas), f64(weight)
+        q, meas, weight = _f64(q), _f64(meas), _f64(weight)
         B, N = q.shape[:2]
         out = self._covariance_outputs(B, N, want_off, want_pos, want_L)
-        seq = (C.c_int32 * max(B, 1))()
+        seq = _int32s(B)
         st = self.lib.cpe_covariance_host(self._h, B, N, _ptr(q), _ptr(meas), _ptr(weight), float(ridge), _ptr(out["cov_diag"]), _ptr(out["cov_off"]),
                                           _ptr(out["cov_pos"]), _ptr(out["L"]), seq)
         _check(st, "cpe_covariance_host", allow=(abi.OK, abi.NUMERICAL))
@@ -857,7 +841,7 @@ class Handle:
         p = self._ragged_batch("covariance_ragged_host", "one q, meas, weight and model", model_list, q_init=q_list, meas=meas_list, weight=weight_list)
         B, Nm = p["q_init"].shape[:2]
         out = self._covariance_outputs(B, Nm, want_off, want_pos, want_L)
-        seq = (C.c_int32 * max(B, 1))()
+        seq = _int32s(B)
         st = self.lib.cpe_covariance_ragged_host(self._h, B, Nm, p["model_arr"], p["len_arr"], _ptr(p["q_init"]), _ptr(p["meas"]), _ptr(p["weight"]),
                                                  float(ridge), _ptr(out["cov_diag"]), _ptr(out["cov_off"]), _ptr(out["cov_pos"]), _ptr(out["L"]), seq)
         _check(st, "cpe_covariance_ragged_host", allow=(abi.OK, abi.NUMERICAL))
@@ -886,8 +870,7 @@ class Handle:
 
     def covariance_columns_host(self, L, cov_diag, cov_off, anchors, n_frames=None):
         """cpe_covariance_columns_host: numpy in, cols [B, K, N, 28, 28] out"""
-        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-        L, cov_diag, cov_off = f64(L), f64(cov_diag), f64(cov_off)
+        L, cov_diag, cov_off = _f64(L), _f64(cov_diag), _f64(cov_off)
         B, N, K, _an, _nf, pa, pn = self._column_args("covariance_columns_host", L.shape, anchors, n_frames)
         if L.shape != (B, N, self.pb + 1, 28, 28) or cov_diag.shape != (B, N, 28, 28) or cov_off.shape != (B, N, self.pb, 28, 28):
             raise ValueError(f"covariance_columns_host: L / cov_diag / cov_off do not have the shapes of the handle's half-bandwidth {self.pb}")
@@ -915,8 +898,7 @@ class Handle:
 
     def rate_covariance_host(self, q, cov_diag, cov_off, want=abi.RATE_COVARIANCE_OUTPUTS):
         """cpe_rate_covariance_host: numpy in, dict of numpy arrays out (the outputs named in `want`, shapes as in rate_covariance())"""
-        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-        q, cov_diag, cov_off = f64(q), f64(cov_diag), f64(cov_off)
+        q, cov_diag, cov_off = _f64(q), _f64(cov_diag), _f64(cov_off)
         B, N = q.shape[:2]
         if cov_diag.shape != (B, N, 28, 28) or cov_off.shape != (B, N, self.pb, 28, 28):
             raise ValueError(f"rate_covariance_host: cov_diag / cov_off do not have the shapes of q and the handle's half-bandwidth {self.pb}")
@@ -941,10 +923,9 @@ class Handle:
                     np.shape(cov_off_list[b]) != (lens[b], self.pb, 28, 28):
                 raise ValueError(f"rate_covariance_ragged_host: sequence {b} does not have the shapes of its {lens[b]} frames")
         Nm = max(lens) if lens else 0
-        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-        q, cd, co = f64(_pad(q_list, Nm, (self.nq,))), f64(_pad(cov_diag_list, Nm, (28, 28))), f64(_pad(cov_off_list, Nm, (self.pb, 28, 28)))
+        q, cd, co = _f64(_pad(q_list, Nm, (self.nq,))), _f64(_pad(cov_diag_list, Nm, (28, 28))), _f64(_pad(cov_off_list, Nm, (self.pb, 28, 28)))
         out = self._rate_outputs(B, Nm, want)
-        mo, nf = (C.c_int32 * max(B, 1))(*models), (C.c_int32 * max(B, 1))(*lens)
+        mo, nf = _int32s(B, models), _int32s(B, lens)
         st = self.lib.cpe_rate_covariance_ragged_host(self._h, B, Nm, mo, nf, _ptr(q), _ptr(cd), _ptr(co),
                                                       *[_ptr(out[k]) for k in abi.RATE_COVARIANCE_OUTPUTS])
         _check(st, "cpe_rate_covariance_ragged_host")
@@ -959,7 +940,7 @@ class Handle:
         """cpe_covariance_kinetic on device tensors (stance, meta int32; the outputs as in covariance_kinetic_host, each but cov_diag may be None).
         Returns (status, [status of every sequence])."""
         B, N = q.shape[0], q.shape[1]
-        seq = (C.c_int32 * max(B, 1))()
+        seq = _int32s(B)
         st = self._call(self.lib.cpe_covariance_kinetic, "cpe_covariance_kinetic", C.byref(kopt) if kopt is not None else None, B, N, _ptr(q),
                         _ptr(meas), _ptr(weight), _ptr(stance), _ptr(grf_fixed), _ptr(tau_box), _ptr(grf_box), float(ridge), _ptr(cov_diag),
                         _ptr(cov_off), _ptr(cov_pos), _ptr(cov_f), _ptr(f), _ptr(meta), _ptr(L), seq, allow=(abi.OK, abi.NUMERICAL))
@@ -970,13 +951,12 @@ class Handle:
         [B, N, L, 3, 3] as covariance_host; cov_f [B, N, 64, 64] the covariance of every node's free forces in the compact order of meta
         [B, N, 65] = (count, indices into f's layout tau | lambda | (z, x, y) per foot, ...), f [B, N, 64]; L with want_L; status, seq_status.
         grf_fixed / tau_box / grf_box (at most one) in solve_kinetic_host's layouts."""
-        f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
-        q, meas, weight, grf_fixed, tau_box, grf_box = (f64(a) for a in (q, meas, weight, grf_fixed, tau_box, grf_box))
+        q, meas, weight, grf_fixed, tau_box, grf_box = (_f64(a, optional=True) for a in (q, meas, weight, grf_fixed, tau_box, grf_box))
         stance = None if stance is None else np.ascontiguousarray(stance, dtype=np.int32)
         B, N = q.shape[:2]
         out = self._covariance_outputs(B, N, True, True, want_L)
         out.update(cov_f=np.empty((B, N, 64, 64)), f=np.empty((B, N, 64)), meta=np.empty((B, N, 65), dtype=np.int32))
-        seq = (C.c_int32 * max(B, 1))()
+        seq = _int32s(B)
         st = self.lib.cpe_covariance_kinetic_host(self._h, C.byref(kopt) if kopt is not None else None, B, N, _ptr(q), _ptr(meas), _ptr(weight),
                                                   None if stance is None else stance.ctypes.data, _ptr(grf_fixed), _ptr(tau_box), _ptr(grf_box),
                                                   float(ridge), _ptr(out["cov_diag"]), _ptr(out["cov_off"]), _ptr(out["cov_pos"]), _ptr(out["cov_f"]),
@@ -998,8 +978,8 @@ class Handle:
         B, N = q.shape[0], q.shape[1]
         if len(model) != B or len(n_frames) != B:
             raise ValueError("covariance_kinetic_ragged: one model index and one frame count per sequence")
-        seq = (C.c_int32 * max(B, 1))()
-        mo, nf = (C.c_int32 * max(B, 1))(*[int(m) for m in model]), (C.c_int32 * max(B, 1))(*[int(n) for n in n_frames])
+        seq = _int32s(B)
+        mo, nf = _int32s(B, model), _int32s(B, n_frames)
         st = self._call(self.lib.cpe_covariance_kinetic_ragged, "cpe_covariance_kinetic_ragged", ko, B, N, mo, nf, _ptr(q), _ptr(meas), _ptr(weight),
                         _ptr(stance), _ptr(grf_fixed), _ptr(tau_box), _ptr(grf_box), float(ridge), _ptr(cov_diag), _ptr(cov_off), _ptr(cov_pos),
                         _ptr(cov_f), _ptr(f), _ptr(meta), _ptr(L), seq, allow=(abi.OK, abi.NUMERICAL))
@@ -1020,7 +1000,7 @@ class Handle:
         out.update(cov_f=np.empty((B, Nm, 64, 64)), f=np.empty((B, Nm, 64)), meta=np.empty((B, Nm, 65), dtype=np.int32))
         if not want_L:
             del out["L"]
-        seq = (C.c_int32 * max(B, 1))()
+        seq = _int32s(B)
         ko = self._kinetic_options_array(kopts_list)
         st = self.lib.cpe_covariance_kinetic_ragged_host(self._h, ko, B, Nm, p["model_arr"], p["len_arr"], _ptr(p["q_init"]), _ptr(p["meas"]),
                                                          _ptr(p["weight"]), p["stance"].ctypes.data, *_force_slots(variant, p["force"]), float(ridge),
@@ -1033,8 +1013,7 @@ class Handle:
 
     # ---- host-pointer conveniences (numpy in, numpy out; PCIe-inclusive) -------------------------------
     def eval_resjac_host(self, q, meas, weight, want_cost=True):
-        q = np.ascontiguousarray(q, dtype=np.float64); meas = np.ascontiguousarray(meas, dtype=np.float64)
-        weight = np.ascontiguousarray(weight, dtype=np.float64)
+        q, meas, weight = _f64(q), _f64(meas), _f64(weight)
         B, N = q.shape[:2]
         r = np.empty((B, N, self.n_cams, self.L, 2)); J = np.empty((B, N, self.n_cams, self.S, 2))
         eps = np.empty((B, N, self.nq)); cost = np.empty((B, N)) if want_cost else None
@@ -1043,8 +1022,7 @@ class Handle:
         return r, J, eps, cost
 
     def solve_host(self, q_init, meas, weight):
-        q_init = np.ascontiguousarray(q_init, dtype=np.float64); meas = np.ascontiguousarray(meas, dtype=np.float64)
-        weight = np.ascontiguousarray(weight, dtype=np.float64)
+        q_init, meas, weight = _f64(q_init), _f64(meas), _f64(weight)
         B, N = q_init.shape[:2]
         out = self._solve_outputs(B, N)
         stats = (abi.Stats * max(B, 1))()

@@ -1243,21 +1243,10 @@ def estimate_kinetics(estimator: CheetahEstimator, init_torques: bool = True, au
     h = _lib.Handle(prep["skeleton"], est.cams, prep["opts"], prep["pri"], device=est.device)
     try:
         t0 = time()
-        gfx, gbx = prep["grf_fixed"], prep["grf_box"]
-        if prep["weighted"]:
-            W = h.track_precision_host(prep["cov_u"][None], prep["track_scale"])
-            res = h.solve_kinetic_tracked_weighted_host(prep["ko"], W, prep["q_init"][None], prep["q_target"][None], prep["stance"][None], est.meas[None],
-                                                        est.weight[None], grf_fixed=None if gfx is None else gfx[None],
-                                                        grf_box=None if gbx is None else gbx[None])
-        elif prep["tracked"]:
-            res = h.solve_kinetic_tracked_host(prep["ko"], prep["q_init"][None], prep["q_target"][None], prep["stance"][None], est.meas[None],
-                                               est.weight[None], grf_fixed=None if gfx is None else gfx[None], grf_box=None if gbx is None else gbx[None])
-        else:
-            res = h.solve_kinetic_host(prep["ko"], prep["q_init"][None], est.meas[None], est.weight[None], prep["stance"][None],
-                                       grf_fixed=None if gfx is None else gfx[None], grf_box=None if gbx is None else gbx[None])
+        res = _kinetic_solve(h, [prep], [est])                                       # the plain batch of one sequence
         dt = time() - t0
-        unc = _kinetic_uncertainty(h, prep["ko"], res, est.meas, est.weight, prep["stance"], uncertainty_ridge, grf_fixed=gfx, grf_box=gbx,
-                                   rates=uncertainty_rates, spans=spans) if uncertainty else None
+        unc = _kinetic_uncertainty(h, prep["ko"], res, est.meas, est.weight, prep["stance"], uncertainty_ridge, grf_fixed=prep["grf_fixed"],
+                                   grf_box=prep["grf_box"], rates=uncertainty_rates, spans=spans) if uncertainty else None
         return _kinetic_finish(est, h, res, dt, prep, solver_output, out_fname, out_dir_prefix, uncertainty=unc)
     finally:
         h.close()
@@ -1438,6 +1427,26 @@ def _kinetic_finish(est: CheetahEstimator, h, res: dict, seconds: float, prep: d
     return ok
 
 
+def _kinetic_solve(h, preps, ests, of=None) -> dict:
+    """THE solver call of estimate_kinetics and estimate_kinetics_batch, in the mode the sequences were prepared for: 2D reprojections, the 3D
+    kinematic cost (tracked) or its full-weight form (weighted: one cpe_track_precision call first).  preps / ests: the _kinetic_prepare dict
+    and the estimator of every sequence, all of one mode and variant.  of = None: a plain batch on a handle of their one model (one length; the
+    arrays are stacked to [B, N, ...]).  of = the model index of every sequence on a Handle.multi: a ragged batch (lists of per-sequence arrays;
+    the kinetic options of model k are those of its first sequence).  Returns the result of the *_host / *_ragged_host method."""
+    p0 = preps[0]
+    gather = (lambda v: None if v[0] is None else np.stack(v)) if of is None else (lambda v: None if v[0] is None else list(v))
+    a = {k: gather([p[k] for p in preps]) for k in ("q_init", "q_target", "stance", "cov_u", "grf_fixed", "grf_box")}
+    meas, weight = gather([e.meas for e in ests]), gather([e.weight for e in ests])
+    ko, form, kw = (p0["ko"], "_host", {}) if of is None else ([preps[of.index(k)]["ko"] for k in range(max(of) + 1)], "_ragged_host", dict(model_list=of))
+    force = dict(grf_fixed=a["grf_fixed"], grf_box=a["grf_box"])
+    if p0["weighted"]:
+        W = h.track_precision_host(a["cov_u"], p0["track_scale"], **kw)
+        return getattr(h, "solve_kinetic_tracked_weighted" + form)(ko, W, a["q_init"], a["q_target"], a["stance"], meas, weight, **kw, **force)
+    if p0["tracked"]:
+        return getattr(h, "solve_kinetic_tracked" + form)(ko, a["q_init"], a["q_target"], a["stance"], meas, weight, **kw, **force)
+    return getattr(h, "solve_kinetic" + form)(ko, a["q_init"], meas, weight, a["stance"], **kw, **force)
+
+
 def _copy_kinetic_options(o: abi.KineticOptions) -> abi.KineticOptions:
     import ctypes as _C
     c = abi.KineticOptions()
@@ -1549,22 +1558,13 @@ def _solve_kinetic_group(ests, idx, prepared, out, solver_output, out_fname, out
     h = _lib.Handle(p0["skeleton"], e0.cams, p0["opts"], p0["pri"], device=e0.device)
     try:
         t0 = time()
-        meas, weight = np.stack([ests[i].meas for i in idx]), np.stack([ests[i].weight for i in idx])
-        if p0["weighted"]:
-            W = h.track_precision_host(stack("cov_u"), p0["track_scale"])
-            res = h.solve_kinetic_tracked_weighted_host(p0["ko"], W, stack("q_init"), stack("q_target"), stack("stance"), meas, weight,
-                                                        grf_fixed=stack("grf_fixed"), grf_box=stack("grf_box"))
-        elif p0["tracked"]:
-            res = h.solve_kinetic_tracked_host(p0["ko"], stack("q_init"), stack("q_target"), stack("stance"), meas, weight, grf_fixed=stack("grf_fixed"),
-                                               grf_box=stack("grf_box"))
-        else:
-            res = h.solve_kinetic_host(p0["ko"], stack("q_init"), meas, weight, stack("stance"), grf_fixed=stack("grf_fixed"), grf_box=stack("grf_box"))
+        res = _kinetic_solve(h, [prepared[i] for i in idx], [ests[i] for i in idx])
         dt = (time() - t0) / len(idx)                                                # processing_time_s of a sequence: its share of the batched solve
         cut = lambda a, conv: None if a is None else a[conv]
         unc = _batch_kinetic_uncertainty(res, idx, uncertainty_ridge, lambda conv: _with_rates(h, h.covariance_kinetic_host(
-            res["q"][conv], meas[conv], weight[conv], stack("stance")[conv], p0["ko"], uncertainty_ridge, grf_fixed=cut(stack("grf_fixed"), conv),
-            grf_box=cut(stack("grf_box"), conv), want_L=spans is not None), res["q"][conv], uncertainty_rates,
-            spans=None if spans is None else [spans[b] for b in conv]))
+            res["q"][conv], np.stack([ests[idx[b]].meas for b in conv]), np.stack([ests[idx[b]].weight for b in conv]), stack("stance")[conv], p0["ko"],
+            uncertainty_ridge, grf_fixed=cut(stack("grf_fixed"), conv), grf_box=cut(stack("grf_box"), conv), want_L=spans is not None),
+            res["q"][conv], uncertainty_rates, spans=None if spans is None else [spans[b] for b in conv]))
         for b, i in enumerate(idx):
             out[i] = _kinetic_finish(ests[i], h, _kinetic_one(res, b), dt, prepared[i], solver_output, out_fname, out_dir_prefix, unc.get(b), no_factor)
     finally:
@@ -1589,18 +1589,7 @@ def _solve_kinetic_ragged_group(ests, idx, prepared, out, solver_output, out_fna
         force = "grf_fixed" if p0["variant"] == "fixed" else ("grf_box" if p0["variant"] == "force_box" else None)
         t0 = time()
         fkw = {} if force is None else {force: [prepared[i][force] for i in idx]}
-        if p0["weighted"]:
-            W = h.track_precision_host([prepared[i]["cov_u"] for i in idx], p0["track_scale"], model_list=of)
-            res = h.solve_kinetic_tracked_weighted_ragged_host([prepared[i]["ko"] for i in reps], W, [prepared[i]["q_init"] for i in idx],
-                                                               [prepared[i]["q_target"] for i in idx], [prepared[i]["stance"] for i in idx],
-                                                               [ests[i].meas for i in idx], [ests[i].weight for i in idx], of, **fkw)
-        elif p0["tracked"]:
-            res = h.solve_kinetic_tracked_ragged_host([prepared[i]["ko"] for i in reps], [prepared[i]["q_init"] for i in idx],
-                                                      [prepared[i]["q_target"] for i in idx], [prepared[i]["stance"] for i in idx],
-                                                      [ests[i].meas for i in idx], [ests[i].weight for i in idx], of, **fkw)
-        else:
-            res = h.solve_kinetic_ragged_host([prepared[i]["ko"] for i in reps], [prepared[i]["q_init"] for i in idx], [ests[i].meas for i in idx],
-                                              [ests[i].weight for i in idx], [prepared[i]["stance"] for i in idx], of, **fkw)
+        res = _kinetic_solve(h, [prepared[i] for i in idx], [ests[i] for i in idx], of)
         dt = (time() - t0) / len(idx)                                                # processing_time_s of a sequence: its share of the batched solve
         unc = _batch_kinetic_uncertainty(res, idx, uncertainty_ridge, lambda conv: _with_rates(h, h.covariance_kinetic_ragged_host(
             [res["q"][b] for b in conv], [ests[idx[b]].meas for b in conv], [ests[idx[b]].weight for b in conv],

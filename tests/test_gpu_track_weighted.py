@@ -357,6 +357,18 @@ def test_estimate_kinetics_with_posterior_weights_end_to_end(tmp_path):
     for k in d["tau"]:
         assert np.array_equal(d3["tau"][k], d["tau"][k]), k
     assert est3.costs == est2.costs
+    # the batch entry, plain (one group of one sequence): every array of the pickle
+    est6 = mk()
+    assert E.estimate_kinetics_batch([est6], out_fname="fte_post_plain_batch", ragged=False, track_weights="posterior", track_scale=scale, **kw) == [True]
+    d6 = E.load_result_pickle(os.path.join(out_dir, "fte_post_plain_batch.pickle"))
+    assert set(d6) == set(d) and {"q", "dq", "ddq", "positions", "meas_err", "x", "dx", "ddx", "com_pos", "com_vel", "tau"} <= set(d)
+    for k, v in d.items():
+        if isinstance(v, (np.ndarray, list)):
+            assert np.array_equal(np.asarray(d6[k]), np.asarray(v)), k
+    assert set(d6["tau"]) == set(d["tau"])
+    for k in d["tau"]:
+        assert np.array_equal(d6["tau"][k], d["tau"][k]), k
+    assert est6.costs == est2.costs
     # default arguments: the reference's weights, as before
     est4, est5 = mk(), mk()
     assert E.estimate_kinetics(est4, out_fname="fte_default", **kw) is True

@@ -312,3 +312,15 @@ def test_estimate_kinetics_without_2d_reprojections_end_to_end(tmp_path):
     for k in d["tau"]:
         assert np.array_equal(d3["tau"][k], d["tau"][k]), k
     assert est3.costs == est2.costs
+    # the batch entry, plain (one group of one sequence): every array of the pickle
+    est4 = mk()
+    assert E.estimate_kinetics_batch([est4], out_fname="fte_plain_batch", ragged=False, **kw) == [True]
+    d4 = E.load_result_pickle(os.path.join(out_dir, "fte_plain_batch.pickle"))
+    assert set(d4) == set(d) and {"q", "dq", "ddq", "positions", "meas_err", "x", "dx", "ddx", "com_pos", "com_vel", "tau"} <= set(d)
+    for k, v in d.items():
+        if isinstance(v, (np.ndarray, list)):
+            assert np.array_equal(np.asarray(d4[k]), np.asarray(v)), k
+    assert set(d4["tau"]) == set(d["tau"])
+    for k in d["tau"]:
+        assert np.array_equal(d4["tau"][k], d["tau"][k]), k
+    assert est4.costs == est2.costs
