@@ -793,6 +793,19 @@ class Handle:
         out["seq"] = seq
         return out
 
+    def eval_active_list(self, status, window):
+        """cpe_eval_active_list: k_build_act on B = len(status) sequences with these status words (0 = running) -> (act, n_act): act is the
+        whole int32 array of window + 64 entries as the kernel left it (-1 where it wrote nothing), n_act the length of the list"""
+        st = np.ascontiguousarray(status, dtype=np.int32)
+        if st.ndim != 1:
+            raise ValueError("eval_active_list: status is one word per sequence")
+        window = int(window)
+        act = np.zeros(max(window, 0) + 64, dtype=np.int32)
+        n_act = C.c_int32(0)
+        _check(self.lib.cpe_eval_active_list(self._h, st.shape[0], window, st.ctypes.data_as(ip), act.ctypes.data_as(ip), C.byref(n_act)),
+               "cpe_eval_active_list")
+        return act, n_act.value
+
     # ---- posterior covariance of the kinematic estimate (include/cpe.h, cpe_covariance) -----------------------------------------------
     def band_inverse(self, L, cov_diag, cov_off=None):
         """cpe_band_inverse on device tensors: L [B, N, pb + 1, 28, 28] (eval_lm_step_host's layout) -> cov_diag [B, N, 28, 28], cov_off

@@ -271,6 +271,7 @@ ENTRIES = {
     # q, meas, weight, tau | lam | g, Bm, cost, gx, rcb, g_total, step, meas_err, seq
     "cpe_eval_shutter_step": _BN + ("p",) * 4 + ("d",) + ("p",) * 9,
     "cpe_eval_shutter_step_host": _BN + ("p",) * 4 + ("d",) + ("p",) * 9,
+    "cpe_eval_active_list": ("h", "i", "i", "ip", "ip", "ip"),         # B, window | status | act, n_act (host)
     **COVARIANCE_ENTRIES, **KINETIC_COVARIANCE_ENTRIES, **KINETIC_COVARIANCE_RAGGED_ENTRIES, **RATE_COVARIANCE_ENTRIES,
     **{name: _COLUMNS for name in COLUMN_COVARIANCE_ENTRIES},
 }

@@ -1101,6 +1101,11 @@ static LmParams lm_params(const cpe_handle* h, int B, int N) {
 // for `slots` sequences; workgroups past *n_act leave at once.
 using LmIterate = std::function<void(int first, const int* act, const int* n_act, int slots)>;
 
+// The one launch of k_build_act (one workgroup of 256 threads): lm_drive before every iteration, cpe_eval_active_list on its scratch arrays.
+static void launch_build_act(hipStream_t stream, const SeqState* st, int B, int window, int* act, int* n_act) {
+    hipLaunchKernelGGL(k_build_act, dim3(1), dim3(256), 0, stream, st, B, window, act, n_act);
+}
+
 // The LM loop of both models on the handle's workspace, from the first pass over every sequence to the last sequence's end.
 // Active window: k_lm_step runs one workgroup per sequence and its duration is the sequential depth of ONE sequence,
 // whatever the grid (3.3 ms for <= 256 workgroups, 4.4 ms for 512 = 2 per CU), so the launches are kept exactly full: before
@@ -1120,7 +1125,7 @@ static cpe_status lm_drive(cpe_handle* h, int B, const LmIterate& iterate) {
     for (long it = 0; it < max_rounds; it += POLL) {
         for (int k = 0; k < POLL; k++) {
             prof_begin(h, 3);
-            hipLaunchKernelGGL(k_build_act, dim3(1), dim3(256), 0, h->stream, h->st, B, window, h->act, h->n_act);
+            launch_build_act(h->stream, h->st, B, window, h->act, h->n_act);
             prof_end(h);
             iterate(0, h->act, h->n_act, window);
         }
@@ -2228,6 +2233,35 @@ cpe_status cpe_eval_lm_step(cpe_handle* h, const cpe_kinetic_options* kopt, int3
         HIPCHK(hipMemcpyAsync(L, hl.data(), w * F * LC, hipMemcpyHostToDevice, h->stream));
     }
     HIPCHK(hipStreamSynchronize(h->stream));                // (hl is read by the copy above)
+    return CPE_OK;
+}
+
+// Diagnostic (include/cpe.h): k_build_act alone, through lm_drive's launch statement, on a scratch state array that holds the given status words
+// and zeros elsewhere.  act has ACT_GUARD entries past `window`, all filled with -1 first: what the kernel leaves of them is what the caller sees.
+cpe_status cpe_eval_active_list(cpe_handle* h, int32_t B, int32_t window, const int32_t* status, int32_t* act, int32_t* n_act) {
+    constexpr int ACT_GUARD = 64;
+    if (!h) return fail(CPE_BAD_ARG, "cpe_eval_active_list: h is null");
+    if (!status) return fail(CPE_BAD_ARG, "cpe_eval_active_list: status is null");
+    if (!act) return fail(CPE_BAD_ARG, "cpe_eval_active_list: act is null");
+    if (!n_act) return fail(CPE_BAD_ARG, "cpe_eval_active_list: n_act is null");
+    if (B < 1) return fail(CPE_BAD_ARG, "cpe_eval_active_list: B = " + std::to_string(B) + " (at least 1)");
+    if (window < 1) return fail(CPE_BAD_ARG, "cpe_eval_active_list: window = " + std::to_string(window) + " (at least 1)");
+    if (window > 0x7fffffff - ACT_GUARD) return fail(CPE_BAD_ARG, "cpe_eval_active_list: window = " + std::to_string(window) + " is too large");
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<SeqState> hs((size_t)B);
+    memset(hs.data(), 0, sizeof(SeqState) * hs.size());
+    for (int b = 0; b < B; b++) hs[b].status = status[b];
+    const size_t n_out = (size_t)window + ACT_GUARD;
+    Staging sg(h->stream);
+    SeqState* dst = sg.in(hs.data(), hs.size());
+    int32_t* dact = sg.out(act, n_out);
+    int32_t* dn = sg.out(n_act, 1);
+    if (sg.err != hipSuccess) return fail(CPE_HIP_ERROR, std::string("cpe_eval_active_list: ") + hipGetErrorString(sg.err));
+    HIPCHK(hipMemsetAsync(dact, 0xff, sizeof(int32_t) * n_out, h->stream));          // every byte 0xff: -1 in every entry
+    HIPCHK(hipMemsetAsync(dn, 0xff, sizeof(int32_t), h->stream));
+    launch_build_act(h->stream, dst, B, window, dact, dn);
+    HIPCHK(hipGetLastError());
+    if (sg.fetch() != hipSuccess) return fail(CPE_HIP_ERROR, std::string("cpe_eval_active_list: ") + hipGetErrorString(sg.err));   // (drains the stream)
     return CPE_OK;
 }
 

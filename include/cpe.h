@@ -623,6 +623,17 @@ cpe_status cpe_eval_shutter_step(cpe_handle* h, int32_t B, int32_t N, const doub
 cpe_status cpe_eval_shutter_step_host(cpe_handle* h, int32_t B, int32_t N, const double* q, const double* meas, const double* weight, const double* tau,
                                       double lam, double* g, double* Bm, double* cost, double* gx, double* rcb, double* g_total, double* step,
                                       double* meas_err, double* seq);
+/* Diagnostic building block of every solve, for tests: the launch window.  After its first pass a solve lists, before every iteration and on the
+ * device, the first `window` sequences that are still running (k_build_act), and every kernel of the iteration works on that list.  This entry
+ * runs that one launch, through the launch statement of the solves, on a scratch state array of B sequences whose status words are status[b]
+ * (0 = running, anything else = finished) and whose other fields are zero.  HOST pointers.  Outputs:
+ *   act [window + 64]  the indices of the first min(count, window) running sequences in ascending order; every entry after them, the 64 past
+ *                     `window` included, reads -1 (the entry fills the array with -1 before the launch: the kernel writes nothing else)
+ *   n_act              min(count, window), count = the number of running sequences
+ * window > B is allowed (no solve passes it): the list is then every running sequence.  The entry allocates its own buffers, leaves the handle's
+ * solver workspace alone and drains the stream before it returns.  CPE_BAD_ARG, with the argument's name in cpe_last_error(): a null h, status,
+ * act or n_act; B < 1; window < 1. */
+cpe_status cpe_eval_active_list(cpe_handle* h, int32_t B, int32_t window, const int32_t* status, int32_t* act, int32_t* n_act);
 
 /* ---- posterior covariance of the kinematic estimate ("What is inverted").  The reference returns one trajectory and no measure
  * of how well the data determine it (IPOPT's reduced Hessian is never asked for, acinoset_opt.py:611-617).  Here
