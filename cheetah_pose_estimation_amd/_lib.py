@@ -892,6 +892,77 @@ class Handle:
                "cpe_covariance_columns_host")
         return cols
 
+    # ---- draws from the posterior (include/cpe.h, cpe_band_sample / cpe_posterior_samples) -------------------------------------------------
+    def _sample_args(self, who, L_shape, z_shape, n_frames):
+        """B, N, S and the host array n_frames [B] (or None = all N) of a band_sample call, from the shapes of L and z"""
+        B, N = int(L_shape[0]), int(L_shape[1])
+        if tuple(L_shape) != (B, N, self.pb + 1, 28, 28) or len(z_shape) != 4 or (z_shape[0], z_shape[2], z_shape[3]) != (B, N, 28):
+            raise ValueError(f"{who}: L is [B, N, {self.pb + 1}, 28, 28] (the handle's half-bandwidth is {self.pb}) and z [B, S, N, 28]")
+        nf = None if n_frames is None else np.ascontiguousarray(n_frames, dtype=np.int32)
+        if nf is not None and nf.shape != (B,):
+            raise ValueError(f"{who}: one frame count per sequence")
+        return B, N, int(z_shape[1]), nf, None if nf is None else nf.ctypes.data_as(ip)
+
+    def band_sample(self, L, z, du, n_frames=None):
+        """cpe_band_sample on device tensors: L [B, N, pb + 1, 28, 28] (a covariance entry's factor), z [B, S, N, 28] -> du [B, S, N, 28], the
+        solutions of L^T du = z: with z ~ N(0, I) draws from N(0, Sigma).  n_frames [B] on the host (or None = all N): du is zero past a
+        sequence's frames, and a sequence of 0 frames is not read"""
+        B, N, S, _nf, pn = self._sample_args("band_sample", L.shape, z.shape, n_frames)
+        self._call(self.lib.cpe_band_sample, "cpe_band_sample", B, N, pn, _ptr(L), S, _ptr(z), _ptr(du))
+
+    def band_sample_host(self, L, z, n_frames=None):
+        """cpe_band_sample_host: numpy in, du [B, S, N, 28] out"""
+        L, z = _f64(L), _f64(z)
+        B, N, S, _nf, pn = self._sample_args("band_sample_host", L.shape, z.shape, n_frames)
+        du = np.empty((B, S, N, 28))
+        _check(self.lib.cpe_band_sample_host(self._h, B, N, pn, _ptr(L), S, _ptr(z), _ptr(du)), "cpe_band_sample_host")
+        return du
+
+    def posterior_samples(self, q, du, q_s, positions_s=None, model=None, n_frames=None):
+        """cpe_posterior_samples on device tensors: q [B, N, nq] (the estimate), du [B, S, N, 28] (band_sample's) -> q_s [B, S, N, nq], the poses
+        of the samples (they satisfy the joint equalities), and positions_s [B, S, N, L, 3] (or None).  model / n_frames: int sequences of a
+        ragged batch (everything past a sequence's frames is zero), or None"""
+        B, N, S = q.shape[0], q.shape[1], du.shape[1]
+        if (model is None) != (n_frames is None):
+            raise ValueError("posterior_samples: model and n_frames are given together or not at all")
+        mo = nf = None
+        if model is not None:
+            if len(model) != B or len(n_frames) != B:
+                raise ValueError("posterior_samples: one model index and one frame count per sequence")
+            mo, nf = _int32s(B, model), _int32s(B, n_frames)
+        self._call(self.lib.cpe_posterior_samples, "cpe_posterior_samples", B, N, mo, nf, _ptr(q), S, _ptr(du), _ptr(q_s), _ptr(positions_s))
+
+    def posterior_samples_host(self, q, du, model_list=None, want_positions=True):
+        """cpe_posterior_samples_host: q [B, N, nq], du [B, S, N, 28] numpy -> dict(q [B, S, N, nq], positions [B, S, N, L, 3] or None); or, for
+        sequences of their own length (and model, model_list; None = model 0), lists of q [N_b, nq] and du [S, N_b, 28] -> lists of
+        [S, N_b, ...] from ONE call"""
+        ragged = isinstance(q, (list, tuple))
+        if ragged:
+            lens = [int(np.shape(a)[0]) for a in q]
+            B, Nm = len(lens), max(lens) if lens else 0
+            models = [0] * B if model_list is None else [int(m) for m in model_list]
+            S = int(np.shape(du[0])[0]) if B else 1
+            if len(du) != B or len(models) != B or any(np.shape(du[b]) != (S, lens[b], 28) or np.shape(q[b]) != (lens[b], self.nq) for b in range(B)):
+                raise ValueError("posterior_samples_host: one q [N_b, nq], du [S, N_b, 28] and model per sequence, the same S for all")
+            qp = _f64(_pad(q, Nm, (self.nq,)))
+            dp_ = np.zeros((B, S, Nm, 28))
+            for b in range(B):
+                dp_[b, :, :lens[b]] = du[b]
+            mo, nf = _int32s(B, models), _int32s(B, lens)
+        else:
+            qp, dp_ = _f64(q), _f64(du)
+            if qp.ndim != 3 or dp_.ndim != 4 or (dp_.shape[0], dp_.shape[2], dp_.shape[3]) != (qp.shape[0], qp.shape[1], 28) or qp.shape[2] != self.nq:
+                raise ValueError("posterior_samples_host: q is [B, N, nq] and du [B, S, N, 28]")
+            B, Nm, S = qp.shape[0], qp.shape[1], dp_.shape[1]
+            mo = nf = None
+        q_s = np.empty((B, S, Nm, self.nq))
+        pos = np.empty((B, S, Nm, self.L, 3)) if want_positions else None
+        _check(self.lib.cpe_posterior_samples_host(self._h, B, Nm, mo, nf, _ptr(qp), S, _ptr(dp_), _ptr(q_s), _ptr(pos)), "cpe_posterior_samples_host")
+        if not ragged:
+            return dict(q=q_s, positions=pos)
+        cut = lambda a: None if a is None else [np.ascontiguousarray(a[b, :, :n]) for b, n in enumerate(lens)]
+        return dict(q=cut(q_s), positions=cut(pos), padded=dict(q=q_s, positions=pos))
+
     # ---- posterior covariance of the rates (include/cpe.h, cpe_rate_covariance) -----------------------------------------------------------
     def rate_covariance(self, q, cov_diag, cov_off, cov_du=None, cov_ddu=None, cov_vel=None, cov_com=None, cov_com_vel=None, jac_pos=None,
                         jac_com=None):

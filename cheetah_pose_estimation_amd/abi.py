@@ -208,6 +208,16 @@ RATE_COVARIANCE_OUTPUTS = ("cov_du", "cov_ddu", "cov_vel", "cov_com", "cov_com_v
 # the columns beyond the band (cpe_covariance_columns): h, B, N | n_frames | L, cov_diag, cov_off | K, anchors | cols
 _COLUMNS = _BN + ("ip", "p", "p", "p", "i", "ip", "p")
 COLUMN_COVARIANCE_ENTRIES = ("cpe_covariance_columns", "cpe_covariance_columns_host")
+# draws from the posterior (cpe_band_sample: h, B, N | n_frames | L | S | z | du; cpe_posterior_samples: h, B, N | model, n_frames | q | S | du |
+# q_s, positions_s)
+_BAND_SAMPLE = _BN + ("ip", "p", "i", "p", "p")
+_POSTERIOR_SAMPLES = _BN + _RAGGED + ("p", "i", "p", "p", "p")
+SAMPLE_ENTRIES = {
+    "cpe_band_sample": _BAND_SAMPLE,
+    "cpe_band_sample_host": _BAND_SAMPLE,
+    "cpe_posterior_samples": _POSTERIOR_SAMPLES,
+    "cpe_posterior_samples_host": _POSTERIOR_SAMPLES,
+}
 COVARIANCE_MAX_PB = 4        # largest half-bandwidth (frames) the covariance sweep supports: motion-prior windows 5 and 6 are refused
 ENTRIES = {
     "cpe_create": ("sk", "cam", "i", "op", "pr", "i", "hp"),
@@ -273,7 +283,7 @@ ENTRIES = {
     "cpe_eval_shutter_step_host": _BN + ("p",) * 4 + ("d",) + ("p",) * 9,
     "cpe_eval_active_list": ("h", "i", "i", "ip", "ip", "ip"),         # B, window | status | act, n_act (host)
     **COVARIANCE_ENTRIES, **KINETIC_COVARIANCE_ENTRIES, **KINETIC_COVARIANCE_RAGGED_ENTRIES, **RATE_COVARIANCE_ENTRIES,
-    **{name: _COLUMNS for name in COLUMN_COVARIANCE_ENTRIES},
+    **{name: _COLUMNS for name in COLUMN_COVARIANCE_ENTRIES}, **SAMPLE_ENTRIES,
 }
 
 

@@ -2547,6 +2547,142 @@ cpe_status cpe_covariance_columns_host(cpe_handle* h, int32_t B, int32_t N, cons
     return CPE_OK;
 }
 
+// ---- draws from the posterior (include/cpe.h, cpe_band_sample / cpe_posterior_samples; kernels in cpe_sample.hip.inc) ------------------------
+// What both forms of a sampling entry refuse about its sizes, before the device is touched and before anything that needs a handle: fills
+// F = B N and FS = B N S, the sample frames (one launch grid of them at most).
+static cpe_status sample_sizes(const std::string& w, int32_t B, int32_t N, int32_t S, size_t* F, size_t* FS) {
+    if (S < 1) return fail(CPE_BAD_ARG, w + "S must be at least 1");
+    if (cpe_status s = frames(B, N, F); s != CPE_OK) return fail(s, w + g_err);
+    if (cpe_status s = frames((int32_t)*F, S, FS); s != CPE_OK) return fail(s, w + g_err);
+    return CPE_OK;
+}
+
+// cpe_band_sample's refusals, columns_check's where they apply; lens = the frame count of every sequence (n_frames, or N)
+static cpe_status band_sample_check(const char* who, const cpe_handle* h, int32_t B, int32_t N, const int32_t* n_frames, bool arrays, int32_t S, size_t* F,
+                                    size_t* FS, std::vector<int>& lens) {
+    const std::string w = std::string(who) + ": ";
+    if (cpe_status s = sample_sizes(w, B, N, S, F, FS); s != CPE_OK) return s;
+    lens.assign((size_t)B, N);
+    for (int b = 0; n_frames && b < B; b++) {
+        if (n_frames[b] < 0 || n_frames[b] > N) return fail(CPE_BAD_ARG, w + "frame count of sequence " + std::to_string(b) + " outside 0..N");
+        lens[(size_t)b] = n_frames[b];
+    }
+    if (!h || !arrays) return fail(CPE_BAD_ARG, w + "null argument (only n_frames may be null)");
+    return cov_check(who, h->pb, 0.0);
+}
+
+// the device entry after its checks: d_len = the frame counts on the device, or null (all N)
+static cpe_status band_sample_launch(cpe_handle* h, int32_t B, int32_t N, size_t FS, const int* d_len, const double* L, int32_t S, const double* z,
+                                     double* du) {
+    HIPCHK(hipMemsetAsync(du, 0, sizeof(double) * FS * CPE_NX, h->stream));       // past a sequence's frames, and a sequence of no frames
+    const unsigned grid = (unsigned)((size_t)B * ((S + WAVE - 1) / WAVE));
+    if (h->pb == 3) hipLaunchKernelGGL((k_band_sample<3>), dim3(grid), dim3(2 * WAVE), 0, h->stream, L, z, du, d_len, N, S);
+    else hipLaunchKernelGGL((k_band_sample<4>), dim3(grid), dim3(2 * WAVE), 0, h->stream, L, z, du, d_len, N, S);
+    HIPCHK(hipGetLastError());
+    return CPE_OK;
+}
+
+cpe_status cpe_band_sample(cpe_handle* h, int32_t B, int32_t N, const int32_t* n_frames, const double* L, int32_t S, const double* z, double* du) {
+    size_t F, FS;
+    std::vector<int> lens;
+    if (cpe_status s = band_sample_check("cpe_band_sample", h, B, N, n_frames, L && z && du, S, &F, &FS, lens); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    HIPCHK(hipSetDevice(h->device));
+    Staging st(h->stream);
+    const int* d_len = n_frames ? st.in(lens.data(), lens.size()) : nullptr;
+    HIPCHK(st.err);
+    if (cpe_status s = band_sample_launch(h, B, N, FS, d_len, L, S, z, du); s != CPE_OK) return s;
+    if (n_frames) HIPCHK(hipStreamSynchronize(h->stream));          // (lens is pageable and the staged copy is freed on return)
+    return CPE_OK;
+}
+
+cpe_status cpe_band_sample_host(cpe_handle* h, int32_t B, int32_t N, const int32_t* n_frames, const double* L, int32_t S, const double* z, double* du) {
+    size_t F, FS;
+    std::vector<int> lens;
+    if (cpe_status s = band_sample_check("cpe_band_sample_host", h, B, N, n_frames, L && z && du, S, &F, &FS, lens); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    HIPCHK(hipSetDevice(h->device));
+    Staging st(h->stream);
+    const int* d_len = n_frames ? st.in(lens.data(), lens.size()) : nullptr;
+    const double *dl = st.in(L, F * (h->pb + 1) * CPE_NX * CPE_NX), *dz = st.in(z, FS * CPE_NX);
+    double* od = st.out(du, FS * CPE_NX);
+    HIPCHK(st.err);
+    if (cpe_status s = band_sample_launch(h, B, N, FS, d_len, dl, S, dz, od); s != CPE_OK) return s;
+    HIPCHK(st.fetch());
+    return CPE_OK;
+}
+
+// cpe_posterior_samples' refusals; seq = the ragged table (model given), else empty
+static cpe_status posterior_samples_check(const char* who, const cpe_handle* h, int32_t B, int32_t N, const int32_t* model, const int32_t* n_frames,
+                                          bool arrays, int32_t S, size_t* F, size_t* FS, std::vector<int2>& seq) {
+    const std::string w = std::string(who) + ": ";
+    if (cpe_status s = sample_sizes(w, B, N, S, F, FS); s != CPE_OK) return s;
+    if ((model == nullptr) != (n_frames == nullptr)) return fail(CPE_BAD_ARG, w + "model and n_frames are given together");
+    if (!h || !arrays) return fail(CPE_BAD_ARG, w + "null argument (handle, q, du and q_s are required)");
+    if (model) { if (cpe_status s = ragged_table(h, B, N, model, n_frames, seq); s != CPE_OK) return fail(s, w + g_err.substr(g_err.find(": ") + 2)); }
+    return CPE_OK;
+}
+
+// the device entry after its checks.  The samples are B S sequences of N frames to k_finalize: their states in a scratch array of that shape, their
+// sequence states zero (buffer 0), and -- ragged -- the table with every sequence's row S times.
+static cpe_status posterior_samples_launch(cpe_handle* h, int32_t B, int32_t N, size_t FS, const std::vector<int2>& seq, const double* q,
+                                           int32_t S, const double* du, double* q_s, double* positions_s) {
+    const bool ragged = !seq.empty();
+    cpe_status s = ensure_ws(h, B, N);
+    if (s != CPE_OK) return s;
+    RaggedArgs rgv;
+    if (ragged && (s = ragged_upload(h, seq, N, rgv)) != CPE_OK) return s;
+    if ((s = state_reset(h, B, N, q, ragged ? &rgv : nullptr)) != CPE_OK) return s;
+    const size_t BS = (size_t)B * S;
+    std::vector<int2> seqs;
+    if (ragged) { seqs.resize(BS); for (size_t i = 0; i < BS; i++) seqs[i] = seq[i / (size_t)S]; }
+    Staging st(h->stream);
+    double* sstate = st.alloc<double>(FS * h->hm.ns);
+    SeqState* sst = st.alloc<SeqState>(BS);
+    const int2* d_seqs = ragged ? st.in(seqs.data(), seqs.size()) : nullptr;
+    HIPCHK(st.err);
+    HIPCHK(hipMemsetAsync(sst, 0, sizeof(SeqState) * BS, h->stream));
+    if (ragged) HIPCHK(hipMemsetAsync(sstate, 0, sizeof(double) * FS * h->hm.ns, h->stream));      // (the padding frames: never read, kept defined)
+    const RaggedArgs rgs{d_seqs, N, cams_max(h)};
+    const RaggedArgs* rg = ragged ? &rgv : nullptr;
+    with_ragged(rg, [&](auto r, RaggedArgs a) {
+        constexpr bool R = decltype(r)::value;
+        hipLaunchKernelGGL(k_sample_state<R>, dim3((unsigned)FS), dim3(WAVE), 0, h->stream, h->dm, h->qbuf, du, sstate, N, S, a);
+        hipLaunchKernelGGL(k_finalize<R>, dim3((unsigned)FS), dim3(WAVE), lds_fk(h, rg), h->stream, h->dm, sst, N, FS, sstate, nullptr, q_s, nullptr, nullptr,
+                           positions_s, nullptr, nullptr, nullptr, R ? rgs : a);
+    });
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));                // (the scratch arrays are freed on return; seq and seqs are pageable)
+    return CPE_OK;
+}
+
+cpe_status cpe_posterior_samples(cpe_handle* h, int32_t B, int32_t N, const int32_t* model, const int32_t* n_frames, const double* q, int32_t S,
+                                 const double* du, double* q_s, double* positions_s) {
+    size_t F, FS;
+    std::vector<int2> seq;
+    if (cpe_status s = posterior_samples_check("cpe_posterior_samples", h, B, N, model, n_frames, q && du && q_s, S, &F, &FS, seq); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    HIPCHK(hipSetDevice(h->device));
+    return posterior_samples_launch(h, B, N, FS, seq, q, S, du, q_s, positions_s);
+}
+
+cpe_status cpe_posterior_samples_host(cpe_handle* h, int32_t B, int32_t N, const int32_t* model, const int32_t* n_frames, const double* q, int32_t S,
+                                      const double* du, double* q_s, double* positions_s) {
+    size_t F, FS;
+    std::vector<int2> seq;
+    if (cpe_status s = posterior_samples_check("cpe_posterior_samples_host", h, B, N, model, n_frames, q && du && q_s, S, &F, &FS, seq); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    const DevModel& m = h->hm;
+    HIPCHK(hipSetDevice(h->device));
+    Staging st(h->stream);
+    const double *dq = st.in(q, F * m.nq), *dd = st.in(du, FS * CPE_NX);
+    double *oq = st.out(q_s, FS * m.nq), *op = st.out_opt(positions_s, FS * m.L * 3);
+    HIPCHK(st.err);
+    if (cpe_status s = posterior_samples_launch(h, B, N, FS, seq, dq, S, dd, oq, op); s != CPE_OK) return s;
+    HIPCHK(st.fetch());
+    return CPE_OK;
+}
+
 // ---- posterior covariance of the rates (include/cpe.h, cpe_rate_covariance; kernels in cpe_rate_cov.hip.inc) --------------------------------
 // What both forms refuse, before the device is touched and in this order -- what needs no handle first: negative sizes, the ragged form's null
 // model / n_frames, a null handle, q, cov_diag or cov_off, all outputs null; then a plain handle or a bad table for the ragged form, and a

@@ -328,6 +328,10 @@ class CheetahEstimator:
     # uncertainty_spans adds SPAN_FIELDS (cpe_covariance_columns, span_uncertainty): per span (first, last) the centre of mass's displacement, distance,
     # mean velocity and mean speed with covariances / standard deviations, and span_positions_displacement_cov / _std [S, L, 3(, 3)]
     uncertainty: Optional[dict] = None
+    # estimate_kinematics(uncertainty=True, uncertainty_samples=K): SAMPLE_FIELDS, K trajectories drawn from the posterior (cpe_band_sample,
+    # cpe_posterior_samples): du [K, N, 28], q [K, N, nq], x [K, N, 28], positions [K, N, L, 3], com_pos [K, N, 3], seed, ridge; None where not
+    # asked for or where the covariance has no factor
+    samples: Optional[dict] = None
 
     def get_objective_cost(self) -> float:
         return float(self.result["stats"][0].cost) if self.result else float("nan")
@@ -600,6 +604,71 @@ def _check_spans(uncertainty: bool, uncertainty_spans) -> None:
         raise ValueError("uncertainty_spans needs uncertainty=True: the spans are propagated from the covariance that keyword computes")
 
 
+SAMPLE_FIELDS = ("seed", "ridge", "du", "q", "x", "positions", "com_pos")
+
+
+def _check_samples(uncertainty: bool, uncertainty_samples: int) -> None:
+    """uncertainty_samples draws from the covariance uncertainty=True computes: alone it is refused, as is a negative count, before anything is
+    looked at"""
+    if uncertainty_samples < 0:
+        raise ValueError(f"uncertainty_samples must be >= 0, not {uncertainty_samples}")
+    if uncertainty_samples and not uncertainty:
+        raise ValueError("uncertainty_samples needs uncertainty=True: the samples are drawn from the covariance that keyword computes")
+
+
+def sample_normals(seed: int, K: int, N: int) -> np.ndarray:
+    """z [K, N, 28] of K samples of a sequence of N frames: a function of (seed, K, N) alone, so a sequence's samples do not depend on the call
+    (single, batch, ragged batch) that draws them"""
+    return np.random.default_rng(seed).standard_normal((K, N, abi.NX))
+
+
+def _with_samples(h, cov: dict, q, K: int, seed: int, model_list=None) -> dict:
+    """a covariance result (made with want_L=True) with, for uncertainty_samples=K > 0, K draws of every sequence under "samples": ONE
+    cpe_band_sample call on the factor the covariance call returned -- no second factorisation; a sequence without a factor takes no part (frame
+    count 0) -- and ONE cpe_posterior_samples call at the same q (model_list: the ragged form, lists per sequence)."""
+    if K <= 0:
+        return cov
+    ragged = isinstance(cov["cov_diag"], list)
+    L = cov["padded"]["L"] if ragged else cov["L"]
+    B, Nm = L.shape[:2]
+    lens = [len(c) for c in cov["cov_diag"]] if ragged else [Nm] * B
+    z = np.zeros((B, K, Nm, abi.NX))
+    for b, n in enumerate(lens):
+        z[b, :, :n] = sample_normals(seed, K, n)
+    du = h.band_sample_host(L, z, [n if cov["seq_status"][b] == abi.OK else 0 for b, n in enumerate(lens)])
+    if ragged:
+        ps = h.posterior_samples_host(list(q), [np.ascontiguousarray(du[b, :, :n]) for b, n in enumerate(lens)], model_list)
+    else:
+        ps = h.posterior_samples_host(q, du)
+    cov["samples"] = dict(du=du, lens=lens, q=ps["q"], positions=ps["positions"], seed=int(seed))
+    return cov
+
+
+def _samples_of(cov: Optional[dict], b: int, ridge: float) -> Optional[dict]:
+    """the sample fields of sequence b that the library computed (du, q, positions; seed, ridge), or None: not asked for, or no factor"""
+    if cov is None or "samples" not in cov or cov["seq_status"][b] != abi.OK:
+        return None
+    sm = cov["samples"]
+    return dict(seed=np.int64(sm["seed"]), ridge=float(ridge), du=np.ascontiguousarray(sm["du"][b, :, :sm["lens"][b]]),
+                q=np.ascontiguousarray(sm["q"][b]), positions=np.ascontiguousarray(sm["positions"][b]))
+
+
+def _store_samples(est, h, samples: Optional[dict], out_dir: str) -> None:
+    """est.samples = SAMPLE_FIELDS of this sequence (h: a handle of its model) and samples.npz beside uncertainty.npz; None: no samples, no file"""
+    est.samples = None
+    if samples is None:
+        return
+    import torch
+    q = samples["q"]
+    dev = torch.device("cuda", est.device)
+    pos = torch.empty(q.shape[:2] + (est.skeleton.n_markers, 3), dtype=torch.float64, device=dev)
+    com = torch.empty(q.shape[:2] + (3,), dtype=torch.float64, device=dev)
+    h.forward_kinematics(torch.tensor(q, device=dev), pos, com); h.synchronize()
+    est.samples = dict(samples, x=est.relative_angles(q), com_pos=com.cpu().numpy())
+    assert set(est.samples) == set(SAMPLE_FIELDS)
+    np.savez(os.path.join(out_dir, "samples.npz"), **est.samples)
+
+
 def resolve_spans(uncertainty_spans, n_frames: int) -> Optional[List[Tuple[int, int]]]:
     """the (first, last) frame pairs of a sequence of n_frames frames that uncertainty_spans asks for: None -> None; True -> the whole sequence,
     (0, n_frames - 1), and no span at all for a one-frame sequence; else pairs relative to the sequence's first frame, negative values counting
@@ -811,9 +880,11 @@ def _store_kinetic_uncertainty(est: CheetahEstimator, unc: Optional[KineticUncer
 
 
 def _kin_finish(est: CheetahEstimator, h, res: dict, seconds: float, solver_output: bool, monocular_constraints: bool,
-                out_dir_prefix: Optional[str], uncertainty: Optional[Tuple[Optional[dict], float]] = None) -> bool:
+                out_dir_prefix: Optional[str], uncertainty: Optional[Tuple[Optional[dict], float]] = None, samples: Optional[dict] = None) -> bool:
     """what estimate_kinematics does after the solver call (acinoset_opt.py:619-634): centre of mass, costs, files.  `res` holds ONE sequence.
-    uncertainty: None (not asked for), or (est.uncertainty of this sequence or None, ridge): stored, and written as uncertainty.npz beside fte.pickle."""
+    uncertainty: None (not asked for), or (est.uncertainty of this sequence or None, ridge): stored, and written as uncertainty.npz beside fte.pickle.
+    samples: what _samples_of returned for this sequence (uncertainty_samples; None: none): completed, stored and written as samples.npz."""
+    est.samples = None
     params, scene = est.params, est.scene
     N = params.end_frame - params.start_frame
     est.opt_time_s = seconds
@@ -846,6 +917,7 @@ def _kin_finish(est: CheetahEstimator, h, res: dict, seconds: float, solver_outp
             else:
                 _add_speed_std(est)
                 np.savez(os.path.join(out_dir, "uncertainty.npz"), **est.uncertainty)
+                _store_samples(est, h, samples, out_dir)
     elif uncertainty is not None:
         est.uncertainty = None
     return ok
@@ -856,7 +928,8 @@ def estimate_kinematics(estimator: CheetahEstimator, solver_output: bool = True,
                         pose_model_num_components: int = 5, motion_model_window_size: int = 4,
                         motion_model_sparse_solution: bool = True, out_dir_prefix: Optional[str] = None,
                         q_init: Optional[np.ndarray] = None, options: Optional[abi.Options] = None, uncertainty: bool = False,
-                        uncertainty_ridge: float = 0.0, uncertainty_rates: bool = False, uncertainty_spans=None) -> bool:
+                        uncertainty_ridge: float = 0.0, uncertainty_rates: bool = False, uncertainty_spans=None, uncertainty_samples: int = 0,
+                        uncertainty_seed: int = 0) -> bool:
     """Same signature as acinoset_opt.estimate_kinematics (acinoset_opt.py:539-547) plus optional
     keyword arguments.  Returns True when the solve converged (IPOPT `ok`+`optimal` in the reference).
     uncertainty=True: after a converged solve the posterior covariance of the estimate (cpe_covariance at the stored q, damping
@@ -867,7 +940,13 @@ def estimate_kinematics(estimator: CheetahEstimator, solver_output: bool = True,
     uncertainty_spans (with uncertainty=True): True = the whole sequence, or (first, last) frame pairs relative to the sequence's first frame,
     negative values counting from its end (resolve_spans).  For every span the displacement of the centre of mass, the distance, the mean velocity
     and the mean speed with their first-order covariances and standard deviations, and the covariance of every marker's displacement (SPAN_FIELDS,
-    span_uncertainty; DESIGN.md 2, "What is spanned"), from the covariance between the two frames (cpe_covariance_columns)."""
+    span_uncertainty; DESIGN.md 2, "What is spanned"), from the covariance between the two frames (cpe_covariance_columns).
+    uncertainty_samples=K > 0 (with uncertainty=True): K whole trajectories drawn from that posterior ("What is sampled"), for the
+    error bar of any quantity computed from a trajectory: du = L^-T z with z = sample_normals(uncertainty_seed, K, N) and the covariance call's own
+    factor L (cpe_band_sample), then the poses (cpe_posterior_samples).  They go to est.samples and to samples.npz beside uncertainty.npz
+    (SAMPLE_FIELDS: seed, ridge, du [K, N, 28], q [K, N, nq], x = relative_angles(q), positions [K, N, L, 3], com_pos [K, N, 3]); est.uncertainty
+    and uncertainty.npz do not change.  Without a factor: est.samples = None and no file."""
+    _check_samples(uncertainty, uncertainty_samples)
     _check_rates(uncertainty, uncertainty_rates)
     _check_spans(uncertainty, uncertainty_spans)
     est, params, scene, sk = estimator, estimator.params, estimator.scene, estimator.skeleton
@@ -889,11 +968,13 @@ def estimate_kinematics(estimator: CheetahEstimator, solver_output: bool = True,
         dt = time() - t0
         unc = None
         if uncertainty:
-            cov = h.covariance_host(res["q"], est.meas[None], est.weight[None], uncertainty_ridge, want_L=spans is not None) \
+            cov = h.covariance_host(res["q"], est.meas[None], est.weight[None], uncertainty_ridge, want_L=spans is not None or uncertainty_samples > 0) \
                 if res["stats"][0].status == abi.OK else None
             cov = None if cov is None else _with_rates(h, cov, res["q"], uncertainty_rates, spans=None if spans is None else [spans])
+            cov = None if cov is None else _with_samples(h, cov, res["q"], uncertainty_samples, uncertainty_seed)
             unc = (None if cov is None else _uncertainty_of(cov, 0, uncertainty_ridge), uncertainty_ridge)
-        return _kin_finish(est, h, res, dt, solver_output, monocular_constraints, out_dir_prefix, uncertainty=unc)
+        return _kin_finish(est, h, res, dt, solver_output, monocular_constraints, out_dir_prefix, uncertainty=unc,
+                           samples=_samples_of(cov if uncertainty else None, 0, uncertainty_ridge))
     finally:
         h.close()
 
@@ -912,7 +993,8 @@ def ragged_group_key(sk: abi.Skeleton, opts: abi.Options, pri: Optional[abi.Prio
 def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_output: bool = False, monocular_constraints: bool = False,
                               disable_pose_prior: bool = False, disable_motion_prior: bool = False, out_dir_prefix: Optional[str] = None,
                               options: Optional[abi.Options] = None, ragged: bool = False, uncertainty: bool = False,
-                              uncertainty_ridge: float = 0.0, uncertainty_rates: bool = False, uncertainty_spans=None) -> List[bool]:
+                              uncertainty_ridge: float = 0.0, uncertainty_rates: bool = False, uncertainty_spans=None, uncertainty_samples: int = 0,
+                              uncertainty_seed: int = 0) -> List[bool]:
     """estimate_kinematics for MANY sequences at once: the loop of run_dataset.py:1145-1196 (`for seq in dataset: init_trajectory; estimate_kinematics`)
     as batched launches.  Sequences that share a skeleton, a camera rig, a length and a frame rate go through ONE solver handle and ONE cpe_solve
     call (B = the group's size: the GPU solves thousands of sequences per second batched, one at a time it is latency-bound at 7 - 30 ms each);
@@ -925,7 +1007,10 @@ def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_out
     uncertainty=True: as in estimate_kinematics, one cpe_covariance (ragged: cpe_covariance_ragged) call per group on the group's handle; every
     sequence's est.uncertainty and uncertainty.npz are bit-equal to those of its own estimate_kinematics call.  uncertainty_rates=True: as in
     estimate_kinematics, one cpe_rate_covariance (ragged: cpe_rate_covariance_ragged) call after each covariance call, with the same bit-equality.
-    uncertainty_spans: as in estimate_kinematics, resolved for every sequence; one cpe_covariance_columns call per group, same bit-equality."""
+    uncertainty_spans: as in estimate_kinematics, resolved for every sequence; one cpe_covariance_columns call per group, same bit-equality.
+    uncertainty_samples, uncertainty_seed: as in estimate_kinematics, every sequence with the z of its own call (sample_normals); one cpe_band_sample
+    and one cpe_posterior_samples call per group, same bit-equality of est.samples and samples.npz."""
+    _check_samples(uncertainty, uncertainty_samples)
     _check_rates(uncertainty, uncertainty_rates)
     _check_spans(uncertainty, uncertainty_spans)
     ests = list(estimators)
@@ -938,7 +1023,7 @@ def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_out
         if est.params.enable_shutter_delay_estimation and est.scene.cam_idx is None:
             out[i] = estimate_kinematics(est, solver_output, monocular_constraints, disable_pose_prior, disable_motion_prior, out_dir_prefix=out_dir_prefix, options=options,
                                          uncertainty=uncertainty, uncertainty_ridge=uncertainty_ridge, uncertainty_rates=uncertainty_rates,
-                                         uncertainty_spans=uncertainty_spans)
+                                         uncertainty_spans=uncertainty_spans, uncertainty_samples=uncertainty_samples, uncertainty_seed=uncertainty_seed)
             continue
         q_init, opts, pri = _kin_prepare(est, monocular_constraints, disable_pose_prior, disable_motion_prior, 5, 4, True, None,
                                          None if options is None else _copy_options(options))
@@ -954,7 +1039,7 @@ def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_out
     if ragged:
         for idx in groups.values():
             _solve_ragged_group(ests, idx, prepared, out, solver_output, monocular_constraints, out_dir_prefix,
-                                uncertainty_ridge if uncertainty else None, uncertainty_rates, group_spans(idx))
+                                uncertainty_ridge if uncertainty else None, uncertainty_rates, group_spans(idx), (uncertainty_samples, uncertainty_seed))
         return [bool(v) for v in out]
     for idx in groups.values():
         e0 = ests[idx[0]]
@@ -967,14 +1052,16 @@ def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_out
             cov = None
             if uncertainty:
                 cov = h.covariance_host(res["q"], np.stack([ests[i].meas for i in idx]), np.stack([ests[i].weight for i in idx]), uncertainty_ridge,
-                                        want_L=uncertainty_spans is not None)
+                                        want_L=uncertainty_spans is not None or uncertainty_samples > 0)
                 cov = _with_rates(h, cov, res["q"], uncertainty_rates, spans=group_spans(idx))
+                cov = _with_samples(h, cov, res["q"], uncertainty_samples, uncertainty_seed)
             for b, i in enumerate(idx):
                 one = {k: (v[b:b + 1] if isinstance(v, np.ndarray) else v) for k, v in res.items() if k not in ("stats", "status")}
                 one["stats"] = [res["stats"][b]]; one["status"] = res["stats"][b].status
                 ests[i].shutter_delay = None
                 unc = None if cov is None else (_uncertainty_of(cov, b, uncertainty_ridge), uncertainty_ridge)
-                out[i] = _kin_finish(ests[i], h, one, dt, solver_output, monocular_constraints, out_dir_prefix, uncertainty=unc)
+                out[i] = _kin_finish(ests[i], h, one, dt, solver_output, monocular_constraints, out_dir_prefix, uncertainty=unc,
+                                     samples=_samples_of(cov, b, uncertainty_ridge))
         finally:
             h.close()
     return [bool(v) for v in out]
@@ -985,9 +1072,10 @@ def _model_bytes(est: CheetahEstimator, opts: abi.Options) -> bytes:
 
 
 def _solve_ragged_group(ests, idx, prepared, out, solver_output, monocular_constraints, out_dir_prefix, uncertainty_ridge: Optional[float] = None,
-                        uncertainty_rates: bool = False, spans=None) -> None:
+                        uncertainty_rates: bool = False, spans=None, samples: Tuple[int, int] = (0, 0)) -> None:
     """estimate_kinematics_batch(ragged=True) for one group: one model per distinct (skeleton, rig, options), one cpe_solve_ragged call, then every
-    sequence's centre of mass, costs and files through _kin_finish with a plain handle of its own model (forward kinematics of that skeleton)"""
+    sequence's centre of mass, costs and files through _kin_finish with a plain handle of its own model (forward kinematics of that skeleton).
+    samples: (uncertainty_samples, uncertainty_seed)"""
     models: Dict[bytes, int] = {}
     of = []
     for i in idx:
@@ -1007,8 +1095,9 @@ def _solve_ragged_group(ests, idx, prepared, out, solver_output, monocular_const
         cov = None
         if uncertainty_ridge is not None:                                            # (uncertainty=True) at the stored q of every sequence, same handle
             cov = h.covariance_ragged_host(res["q"], [ests[i].meas for i in idx], [ests[i].weight for i in idx], of, uncertainty_ridge,
-                                           want_L=spans is not None)
+                                           want_L=spans is not None or samples[0] > 0)
             cov = _with_rates(h, cov, res["q"], uncertainty_rates, of, spans)
+            cov = _with_samples(h, cov, res["q"], samples[0], samples[1], of)
         for b, i in enumerate(idx):
             one = {k: res[k][b][None] for k in ("q", "dq", "ddq", "positions", "meas_err")}
             one["stats"] = [res["stats"][b]]; one["status"] = res["stats"][b].status
@@ -1017,7 +1106,8 @@ def _solve_ragged_group(ests, idx, prepared, out, solver_output, monocular_const
                 fk[of[b]] = _lib.Handle(ests[r].skeleton, ests[r].cams, prepared[r][1], None, device=dev)
             ests[i].shutter_delay = None
             unc = None if cov is None else (_uncertainty_of(cov, b, uncertainty_ridge), uncertainty_ridge)
-            out[i] = _kin_finish(ests[i], fk[of[b]], one, dt, solver_output, monocular_constraints, out_dir_prefix, uncertainty=unc)
+            out[i] = _kin_finish(ests[i], fk[of[b]], one, dt, solver_output, monocular_constraints, out_dir_prefix, uncertainty=unc,
+                                 samples=_samples_of(cov, b, uncertainty_ridge))
     finally:
         h.close()
         for f in fk.values():

@@ -732,6 +732,41 @@ cpe_status cpe_covariance_columns(cpe_handle* h, int32_t B, int32_t N, const int
 cpe_status cpe_covariance_columns_host(cpe_handle* h, int32_t B, int32_t N, const int32_t* n_frames, const double* L, const double* cov_diag,
                                        const double* cov_off, int32_t K, const int32_t* anchors, double* cols);
 
+/* ---- draws from the posterior of the kinematic estimate ("What is sampled"): whole trajectories, for the error bar of any quantity a
+ * caller computes from a trajectory -- also one that is no smooth function of a few neighbouring frames and has no Jacobian here (a joint-angle range
+ * over a stride, the foot height at touch-down, a detected contact window).  With z ~ N(0, I) the solution of L^T du = z has covariance
+ * L^-T L^-1 = Sigma: the full matrix, not only its band.
+ * cpe_band_sample, the building block (pure linear algebra): for every sequence b and sample s, newest frame first (NL the sequence's length),
+ *     du_n = L(n,n)^-T (z_n - sum_{i=1..pb} L(n+i,n)^T du_{n+i}),        n = NL-1 .. 0,   blocks with n + i >= NL are not used.
+ * Device pointers except n_frames.  L [B][N][pb+1][28][28]: cpe_band_inverse's layout with the true diagonal, pb = the handle's half-bandwidth, from
+ * cpe_covariance*, cpe_covariance_kinetic*, cpe_eval_lm_step or the caller; values are not validated.  z, du [B][S][N][28]: sample s of sequence b is
+ * one contiguous trajectory.  n_frames [B] HOST: the length of every sequence, or NULL = all N.  du is exactly 0.0 past a sequence's frames; a
+ * sequence with n_frames[b] == 0 is not read at all (neither L nor z): the way to skip a sequence for which cpe_covariance found no factor.  The
+ * reciprocals of the diagonal are formed as the covariance sweep forms them (r = 1 / d).  Every sum has a fixed order (no atomics): results are
+ * reproducible bit for bit, and the result of a sample depends neither on S, nor on its slot s, nor on the batch.
+ * Refused with CPE_BAD_ARG before the device is touched, the reason in cpe_last_error(): S < 1; negative sizes or more than 2^31 - 1 sample frames
+ * (B N S); a frame count outside [0, N]; a NULL argument other than n_frames; a half-bandwidth above 4. */
+cpe_status cpe_band_sample(cpe_handle* h, int32_t B, int32_t N, const int32_t* n_frames /*[B] host, or NULL*/, const double* L, int32_t S,
+                           const double* z, double* du);
+/* host-pointer twin (stages through HBM) */
+cpe_status cpe_band_sample_host(cpe_handle* h, int32_t B, int32_t N, const int32_t* n_frames, const double* L, int32_t S, const double* z, double* du);
+/* cpe_posterior_samples: the poses of S draws.  Device pointers except model and n_frames.  q [B][N][nq]: the estimate, Euler angles as
+ * cpe_covariance takes them; du [B][S][N][28]: cpe_band_sample's output (or any step in the reduced coordinates).  Sample s of sequence b is the
+ * cold-start state of q (leg angles about the body's y axis, as every solve starts) with du added to the entries of the reduced coordinates --
+ * exactly the update with which an LM step writes its trial iterate -- made consistent with the joint equalities and turned into Euler angles and
+ * marker positions by the code of the solve's own outputs: q_s [B][S][N][nq] (required) satisfies the joint equalities as cpe_solve's q does, and
+ * positions_s [B][S][N][L][3] (may be NULL) are its marker positions.  Angle bounds are not enforced (they are not part of the Laplace
+ * approximation, see cpe_covariance).  All samples with du == 0 of a sequence come back with the same bits.
+ * model, n_frames [B] HOST: both NULL, or both given = sequences of their own length and model in cpe_covariance_ragged's layout (N = N_max) on a
+ * handle of cpe_create_multi; everything past a sequence's frames is then 0.0, and a sequence's samples are bit-equal to those of its own plain call.
+ * Refused with CPE_BAD_ARG before the device is touched, the reason in cpe_last_error(): S < 1; negative sizes or more than 2^31 - 1 sample frames;
+ * model without n_frames or the reverse; NULL h, q, du or q_s; a model index or frame count out of range. */
+cpe_status cpe_posterior_samples(cpe_handle* h, int32_t B, int32_t N, const int32_t* model /*[B] host, or NULL*/, const int32_t* n_frames /*[B] host, or NULL*/,
+                                 const double* q, int32_t S, const double* du, double* q_s, double* positions_s);
+/* host-pointer twin (stages through HBM) */
+cpe_status cpe_posterior_samples_host(cpe_handle* h, int32_t B, int32_t N, const int32_t* model, const int32_t* n_frames, const double* q, int32_t S,
+                                      const double* du, double* q_s, double* positions_s);
+
 /* ---- posterior covariance of the physics-based estimate: coordinates, and the node forces (torques, joint constraint forces, net foot forces)
  * the solve infers ("What is inverted").  Runs the launches of the first pass of cpe_solve_kinetic at Euler q -- cold start, multipliers
  * zero, node forces minimised from a cold start, as cpe_eval_kinetic_system / cpe_eval_lm_step -- at damping `ridge` in place of opts.lambda0, up to
