@@ -1095,6 +1095,86 @@ class Handle:
         res.update(status=st, seq_status=list(seq)[:B], padded=out)
         return res
 
+    # ---- draws of the node forces of the physics-based estimate (include/cpe.h, cpe_force_samples) -----------------------------------------
+    def force_samples(self, kopt, q, meas, weight, stance, ridge, du, f_s, zeta=None, f=None, meta=None, grf_fixed=None, tau_box=None, grf_box=None):
+        """cpe_force_samples on device tensors: du [B, S, N, 28] (band_sample's on the factor covariance_kinetic returns, or any step), zeta
+        [B, S, N, 64] (standard normals in the compact order of meta; None = zeros: the conditional mean) -> f_s [B, S, N, 64] in f's layout
+        tau | lambda | (z, x, y) per foot; f [B, N, 64], meta int32 [B, N, 65] as covariance_kinetic (each may be None).
+        Returns (status, [status of every sequence])."""
+        B, N, S = q.shape[0], q.shape[1], du.shape[1]
+        seq = _int32s(B)
+        st = self._call(self.lib.cpe_force_samples, "cpe_force_samples", C.byref(kopt) if kopt is not None else None, B, N, _ptr(q), _ptr(meas),
+                        _ptr(weight), _ptr(stance), _ptr(grf_fixed), _ptr(tau_box), _ptr(grf_box), float(ridge), S, _ptr(du), _ptr(zeta), _ptr(f_s),
+                        _ptr(f), _ptr(meta), seq, allow=(abi.OK, abi.NUMERICAL))
+        return st, list(seq)[:B]
+
+    def force_samples_host(self, q, meas, weight, stance, kopt, du, zeta=None, ridge=0.0, grf_fixed=None, tau_box=None, grf_box=None):
+        """cpe_force_samples_host: numpy in (du [B, S, N, 28], zeta [B, S, N, 64] or None), dict of numpy arrays out -- f_s [B, S, N, 64], f
+        [B, N, 64], meta [B, N, 65] (as covariance_kinetic_host's), status, seq_status"""
+        q, meas, weight, grf_fixed, tau_box, grf_box, zeta = (_f64(a, optional=True) for a in (q, meas, weight, grf_fixed, tau_box, grf_box, zeta))
+        stance = None if stance is None else np.ascontiguousarray(stance, dtype=np.int32)
+        du = _f64(du)
+        B, N = q.shape[:2]
+        if du.ndim != 4 or (du.shape[0], du.shape[2], du.shape[3]) != (B, N, 28) or (zeta is not None and zeta.shape != du.shape[:3] + (64,)):
+            raise ValueError("force_samples_host: du is [B, S, N, 28] and zeta [B, S, N, 64] (or None)")
+        S = du.shape[1]
+        out = dict(f_s=np.empty((B, S, N, 64)), f=np.empty((B, N, 64)), meta=np.empty((B, N, 65), dtype=np.int32))
+        seq = _int32s(B)
+        st = self.lib.cpe_force_samples_host(self._h, C.byref(kopt) if kopt is not None else None, B, N, _ptr(q), _ptr(meas), _ptr(weight),
+                                             None if stance is None else stance.ctypes.data, _ptr(grf_fixed), _ptr(tau_box), _ptr(grf_box),
+                                             float(ridge), S, _ptr(du), _ptr(zeta), _ptr(out["f_s"]), _ptr(out["f"]), out["meta"].ctypes.data, seq)
+        _check(st, "cpe_force_samples_host", allow=(abi.OK, abi.NUMERICAL))
+        out.update(status=st, seq_status=list(seq)[:B])
+        return out
+
+    def force_samples_ragged(self, kopts_list, model, n_frames, q, meas, weight, stance, ridge, du, f_s, zeta=None, f=None, meta=None, grf_fixed=None,
+                             tau_box=None, grf_box=None):
+        """cpe_force_samples_ragged on device tensors laid out for N_max = q.shape[1] frames and C_max cameras, as covariance_kinetic_ragged takes
+        them; the outputs as in force_samples, zero past every sequence's own frames.  Returns (status, [status of every sequence])."""
+        _force_variant("force_samples_ragged", grf_fixed, tau_box, grf_box)
+        ko = self._kinetic_options_array(kopts_list)
+        B, N, S = q.shape[0], q.shape[1], du.shape[1]
+        if len(model) != B or len(n_frames) != B:
+            raise ValueError("force_samples_ragged: one model index and one frame count per sequence")
+        seq = _int32s(B)
+        mo, nf = _int32s(B, model), _int32s(B, n_frames)
+        st = self._call(self.lib.cpe_force_samples_ragged, "cpe_force_samples_ragged", ko, B, N, mo, nf, _ptr(q), _ptr(meas), _ptr(weight),
+                        _ptr(stance), _ptr(grf_fixed), _ptr(tau_box), _ptr(grf_box), float(ridge), S, _ptr(du), _ptr(zeta), _ptr(f_s), _ptr(f),
+                        _ptr(meta), seq, allow=(abi.OK, abi.NUMERICAL))
+        return st, list(seq)[:B]
+
+    def force_samples_ragged_host(self, q_list, meas_list, weight_list, stance_list, kopts_list, du_list, zeta_list=None, model_list=None, ridge=0.0,
+                                  grf_fixed=None, tau_box=None, grf_box=None):
+        """cpe_force_samples_ragged_host over sequences of their own length and model (covariance_kinetic_ragged_host's arguments, then du_list:
+        one [S, N_b, 28] per sequence, the same S for all, and zeta_list: one [S, N_b, 64] per sequence, or None): pads, runs, unpads.  Returns
+        dict(f_s = list of [S, N_b, 64], f, meta = lists of [N_b, ...], status, seq_status, padded = the padded outputs)."""
+        who = "force_samples_ragged_host"
+        variant, force = _force_variant(who, grf_fixed, tau_box, grf_box)
+        p = self._ragged_batch(who, "one q, meas, weight, stance, model (and force array)", model_list, kopts_list, variant,
+                               q_init=q_list, meas=meas_list, weight=weight_list, stance=stance_list, force=force)
+        B, Nm = p["q_init"].shape[:2]
+        lens = p["lens"]
+        S = int(np.shape(du_list[0])[0]) if B else 1
+        if len(du_list) != B or any(np.shape(du_list[b]) != (S, lens[b], 28) for b in range(B)) or \
+                (zeta_list is not None and (len(zeta_list) != B or any(np.shape(zeta_list[b]) != (S, lens[b], 64) for b in range(B)))):
+            raise ValueError(f"{who}: one du [S, N_b, 28] (and zeta [S, N_b, 64]) per sequence, the same S for all")
+        du = np.zeros((B, S, Nm, 28))
+        zeta = None if zeta_list is None else np.zeros((B, S, Nm, 64))
+        for b in range(B):
+            du[b, :, :lens[b]] = du_list[b]
+            if zeta is not None:
+                zeta[b, :, :lens[b]] = zeta_list[b]
+        out = dict(f_s=np.empty((B, S, Nm, 64)), f=np.empty((B, Nm, 64)), meta=np.empty((B, Nm, 65), dtype=np.int32))
+        seq = _int32s(B)
+        ko = self._kinetic_options_array(kopts_list)
+        st = self.lib.cpe_force_samples_ragged_host(self._h, ko, B, Nm, p["model_arr"], p["len_arr"], _ptr(p["q_init"]), _ptr(p["meas"]),
+                                                    _ptr(p["weight"]), p["stance"].ctypes.data, *_force_slots(variant, p["force"]), float(ridge), S,
+                                                    _ptr(du), _ptr(zeta), _ptr(out["f_s"]), _ptr(out["f"]), out["meta"].ctypes.data, seq)
+        _check(st, who, allow=(abi.OK, abi.NUMERICAL))
+        res = unpad_kinetic(dict(f=out["f"], meta=out["meta"]), lens, p["cams"])
+        res.update(f_s=[np.ascontiguousarray(out["f_s"][b, :, :n]) for b, n in enumerate(lens)], status=st, seq_status=list(seq)[:B], padded=out)
+        return res
+
     # ---- host-pointer conveniences (numpy in, numpy out; PCIe-inclusive) -------------------------------
     def eval_resjac_host(self, q, meas, weight, want_cost=True):
         q, meas, weight = _f64(q), _f64(meas), _f64(weight)

@@ -218,6 +218,15 @@ SAMPLE_ENTRIES = {
     "cpe_posterior_samples": _POSTERIOR_SAMPLES,
     "cpe_posterior_samples_host": _POSTERIOR_SAMPLES,
 }
+# draws of the node forces (cpe_force_samples): h, ko, B, N (| model, n_frames) | q, meas, weight, stance, grf_fixed, tau_box, grf_box | ridge | S |
+# du, zeta | f_s, f, meta | status
+_FORCE_SAMPLES = ("p",) * 7 + ("d", "i") + ("p",) * 5 + ("ip",)
+FORCE_SAMPLE_ENTRIES = {
+    "cpe_force_samples": _KIN_BN + _FORCE_SAMPLES,
+    "cpe_force_samples_host": _KIN_BN + _FORCE_SAMPLES,
+    "cpe_force_samples_ragged": _KIN_BN + _RAGGED + _FORCE_SAMPLES,
+    "cpe_force_samples_ragged_host": _KIN_BN + _RAGGED + _FORCE_SAMPLES,
+}
 COVARIANCE_MAX_PB = 4        # largest half-bandwidth (frames) the covariance sweep supports: motion-prior windows 5 and 6 are refused
 ENTRIES = {
     "cpe_create": ("sk", "cam", "i", "op", "pr", "i", "hp"),
@@ -283,7 +292,7 @@ ENTRIES = {
     "cpe_eval_shutter_step_host": _BN + ("p",) * 4 + ("d",) + ("p",) * 9,
     "cpe_eval_active_list": ("h", "i", "i", "ip", "ip", "ip"),         # B, window | status | act, n_act (host)
     **COVARIANCE_ENTRIES, **KINETIC_COVARIANCE_ENTRIES, **KINETIC_COVARIANCE_RAGGED_ENTRIES, **RATE_COVARIANCE_ENTRIES,
-    **{name: _COLUMNS for name in COLUMN_COVARIANCE_ENTRIES}, **SAMPLE_ENTRIES,
+    **{name: _COLUMNS for name in COLUMN_COVARIANCE_ENTRIES}, **SAMPLE_ENTRIES, **FORCE_SAMPLE_ENTRIES,
 }
 
 

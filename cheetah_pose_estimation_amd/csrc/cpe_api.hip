@@ -561,7 +561,7 @@ static cpe_status create_impl(cpe_handle* h, const cpe_skeleton* skel, const cpe
                             (const void*)&k_resjac<true, 4, 4, 2>, (const void*)&k_resjac<false, 4, 4, 2>,
                             (const void*)&k_dyn_eval<>, (const void*)&k_dyn_assemble<>, (const void*)&k_dyn_schur<>, (const void*)&k_dyn_jac<>,
                             (const void*)&k_dyn_eval<true>, (const void*)&k_dyn_assemble<true>, (const void*)&k_dyn_schur<true>, (const void*)&k_dyn_jac<true>,
-                            (const void*)&k_force_cov<>, (const void*)&k_force_cov<true>};
+                            (const void*)&k_force_cov<>, (const void*)&k_force_cov<true>, (const void*)&k_force_sample<>, (const void*)&k_force_sample<true>};
         for (const void* k : ks) {         // all of the CU's 160 KiB that the kernel's static LDS leaves (k_dyn_schur<*> holds a word of its own)
             hipFuncAttributes fa;
             HIPCHK(hipFuncGetAttributes(&fa, k));
@@ -2826,37 +2826,88 @@ static cpe_status cov_kinetic_batch(const char* who, const cpe_handle* h, const 
     return CPE_OK;
 }
 
+// What both forms of cpe_covariance_kinetic* refuse, in this order: cov_kinetic_check's, a null handle or array (`arrays`: the entry's required
+// ones), the sizes, the ragged batch.  Fills F (0: nothing to do) and, for the ragged form, the table.  (force_samples_check runs the same pieces
+// with its sample sizes ahead of what needs a handle.)
+static cpe_status kin_cov_args(const char* who, const cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const int32_t* model,
+                               const int32_t* n_frames, bool arrays, const int32_t* stance, const double* grf_fixed, const double* tau_box,
+                               const double* grf_box, double ridge, size_t* F, std::vector<int2>& seq) {
+    if (cpe_status s = cov_kinetic_check(who, h, opt, stance, grf_fixed, tau_box, grf_box, ridge); s != CPE_OK) return s;
+    if (!h || !arrays) return fail(CPE_BAD_ARG, "null argument");
+    if (cpe_status s = frames(B, N, F); s != CPE_OK) return s;
+    if (*F == 0 || !model) return CPE_OK;
+    return cov_kinetic_batch(who, h, opt, B, N, model, n_frames, seq);
+}
+
+// The first pass both entries run at Euler q: workspaces, model tables, cold-start state, one flag per sequence for the node kernel (kin_cov_setup),
+// then the launches of the physics solve's first pass up to the band factor, multipliers zero, at damping ridge in place of opts.lambda0
+// (kin_cov_pass); after the entry's own kernels, the status of every sequence (kin_cov_status).
+struct KinCovPass {
+    RaggedArgs rgv;
+    const RaggedArgs* rg = nullptr;
+    DevBuf bad_buf;
+    int* bad = nullptr;                // [B]: a node's force matrix has no Cholesky factor
+};
+static cpe_status kin_cov_setup(const char* who, cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, size_t F, const std::vector<int2>& seq,
+                                const double* q, const double* grf_fixed, const double* tau_box, const double* grf_box, KinCovPass& kp) {
+    const bool ragged = !seq.empty();
+    cpe_status s = ensure_ws(h, B, N);                     // the workspaces first: build_kin records pointers into them
+    if (s != CPE_OK) return s;
+    if ((s = ensure_kws(h, B, N)) != CPE_OK || (s = ensure_cov(h, F)) != CPE_OK) return s;
+    if ((s = ragged ? build_kin_all(h, opt, grf_fixed, tau_box, grf_box, who) : build_kin(h, opt, grf_fixed, tau_box, grf_box)) != CPE_OK) return s;
+    if (ragged && (s = ragged_upload(h, seq, N, kp.rgv)) != CPE_OK) return s;     // (seq outlives the stream: drained by kin_cov_status)
+    kp.rg = ragged ? &kp.rgv : nullptr;
+    if ((s = state_reset(h, B, N, q, kp.rg)) != CPE_OK || (s = kin_state_reset(h, F, tau_box != nullptr)) != CPE_OK) return s;
+    HIPCHK(kp.bad_buf.alloc(((size_t)B + 1) / 2));
+    kp.bad = reinterpret_cast<int*>(kp.bad_buf.p);
+    HIPCHK(hipMemsetAsync(kp.bad, 0, sizeof(int) * B, h->stream));
+    return CPE_OK;
+}
+static void kin_cov_pass(cpe_handle* h, int32_t B, int32_t N, size_t F, const double* meas, const double* weight, const int32_t* stance, double ridge,
+                         const KinCovPass& kp) {
+    LmParams prm = lm_params(h, B, N);
+    prm.lambda0 = ridge;
+    kin_iterate(h, prm, N, F, lds_normal(h, kp.rg), meas, weight, stance, nullptr, kp.rg, 1, nullptr, nullptr, B, false);
+}
+// drains the stream; status[b], the worst of them, and wipe[b] = the band of sequence b has a factor but one of its nodes has none: what the
+// kernels wrote for it is to be cleared by the entry (a sequence without a band factor has been written by no kernel)
+static cpe_status kin_cov_status(cpe_handle* h, int32_t B, const KinCovPass& kp, cpe_status* status, std::vector<char>& wipe, cpe_status* worst) {
+    std::vector<SeqState> hs((size_t)B);
+    std::vector<int> hbad((size_t)B);
+    HIPCHK(hipMemcpyAsync(hs.data(), h->st, sizeof(SeqState) * B, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(hbad.data(), kp.bad, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    wipe.assign((size_t)B, 0);
+    *worst = CPE_OK;
+    for (int b = 0; b < B; b++) {
+        const bool band_ok = hs[b].status == 0 && hs[b].back_pending == 1;
+        status[b] = band_ok && !hbad[b] ? CPE_OK : CPE_NUMERICAL;
+        if (status[b] > *worst) *worst = status[b];
+        wipe[(size_t)b] = band_ok && hbad[b];
+    }
+    return CPE_OK;
+}
+
 // cpe_covariance_kinetic (model == null: B sequences of N frames of the handle's first model, options opt[0]) and cpe_covariance_kinetic_ragged
 // (model / n_frames: host arrays of the batch, N = N_max, options opt[k] for model k)
 static cpe_status covariance_kinetic_impl(const char* who, cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const int32_t* model,
                                           const int32_t* n_frames, const double* q, const double* meas, const double* weight, const int32_t* stance,
                                           const double* grf_fixed, const double* tau_box, const double* grf_box, double ridge, double* cov_diag,
                                           double* cov_off, double* cov_pos, double* cov_f, double* f, int32_t* meta, double* L, cpe_status* status) {
-    if (cpe_status s = cov_kinetic_check(who, h, opt, stance, grf_fixed, tau_box, grf_box, ridge); s != CPE_OK) return s;
-    if (!h || !q || !meas || !weight || !cov_diag || !status) return fail(CPE_BAD_ARG, "null argument");
     size_t F;
-    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
-    if (F == 0) return CPE_OK;
-    const bool ragged = model != nullptr;
     std::vector<int2> seq;
-    if (ragged) { if (cpe_status s = cov_kinetic_batch(who, h, opt, B, N, model, n_frames, seq); s != CPE_OK) return s; }
+    if (cpe_status s = kin_cov_args(who, h, opt, B, N, model, n_frames, q && meas && weight && cov_diag && status, stance, grf_fixed, tau_box, grf_box, ridge, &F, seq);
+        s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
     HIPCHK(hipSetDevice(h->device));
-    cpe_status s = ensure_ws(h, B, N);                     // the workspaces first: build_kin records pointers into them
-    if (s != CPE_OK) return s;
-    if ((s = ensure_kws(h, B, N)) != CPE_OK || (s = ensure_cov(h, F)) != CPE_OK) return s;
-    if ((s = ragged ? build_kin_all(h, opt, grf_fixed, tau_box, grf_box, who) : build_kin(h, opt, grf_fixed, tau_box, grf_box)) != CPE_OK) return s;
-    RaggedArgs rgv;
-    if (ragged && (s = ragged_upload(h, seq, N, rgv)) != CPE_OK) return s;     // (seq outlives the stream: drained below)
-    const RaggedArgs* rg = ragged ? &rgv : nullptr;
-    if ((s = state_reset(h, B, N, q, rg)) != CPE_OK || (s = kin_state_reset(h, F, tau_box != nullptr)) != CPE_OK) return s;
+    KinCovPass kp;
+    if (cpe_status s = kin_cov_setup(who, h, opt, B, N, F, seq, q, grf_fixed, tau_box, grf_box, kp); s != CPE_OK) return s;
+    const RaggedArgs* rg = kp.rg;
     const DevModel& m = h->hm;
     const size_t BB = (size_t)CPE_NX * CPE_NX, w = sizeof(double), LC = 4 * BB, FF = (size_t)KIN_LS * KIN_LS;
-    // k_force_cov reads the off-diagonal blocks of the band whether the caller wants them or not; one flag per sequence behind them
-    DevBuf off_own, bad_buf;
+    // k_force_cov reads the off-diagonal blocks of the band whether the caller wants them or not
+    DevBuf off_own;
     if (!cov_off) { HIPCHK(off_own.alloc(F * 3 * BB)); cov_off = off_own.p; }
-    HIPCHK(bad_buf.alloc(((size_t)B + 1) / 2));
-    int* bad = reinterpret_cast<int*>(bad_buf.p);
-    HIPCHK(hipMemsetAsync(bad, 0, sizeof(int) * B, h->stream));
     // a sequence without a factor has all outputs zero, and so have the nodes 0 and 1 in cov_f, f and meta and every frame past a sequence's own
     HIPCHK(hipMemsetAsync(cov_diag, 0, w * F * BB, h->stream));
     HIPCHK(hipMemsetAsync(cov_off, 0, w * F * 3 * BB, h->stream));
@@ -2864,29 +2915,20 @@ static cpe_status covariance_kinetic_impl(const char* who, cpe_handle* h, const 
     if (cov_f) HIPCHK(hipMemsetAsync(cov_f, 0, w * F * FF, h->stream));
     if (f) HIPCHK(hipMemsetAsync(f, 0, w * F * KIN_LS, h->stream));
     if (meta) HIPCHK(hipMemsetAsync(meta, 0, sizeof(int32_t) * F * (KIN_LS + 1), h->stream));
-    // the launches of the physics solve's first pass up to the band factor, multipliers zero, at damping ridge in place of opts.lambda0
-    LmParams prm = lm_params(h, B, N);
-    prm.lambda0 = ridge;
-    kin_iterate(h, prm, N, F, lds_normal(h, rg), meas, weight, stance, nullptr, rg, 1, nullptr, nullptr, B, false);
+    kin_cov_pass(h, B, N, F, meas, weight, stance, ridge, kp);
     cov_launch(h, B, N, h->st, h->Lbuf, 1, cov_diag, cov_off, rg);
     // (without cov_f the kernel still decides whether every node's force matrix has a factor: the status does not depend on what is asked for)
     with_ragged(rg, [&](auto r, RaggedArgs a) {
         hipLaunchKernelGGL(k_force_cov<decltype(r)::value>, dim3((unsigned)F), dim3(KIN_THREADS), sizeof(double) * FC_DOUBLES, h->stream, h->dk, h->st, N, F, h->pieces,
-                           h->pmeta, h->fbuf, h->kmu, stance, cov_diag, cov_off, cov_f, f, meta, bad, a);
+                           h->pmeta, h->fbuf, h->kmu, stance, cov_diag, cov_off, cov_f, f, meta, kp.bad, a);
     });
     cov_extras(h, N, F, cov_diag, cov_pos, L, rg);
     HIPCHK(hipGetLastError());
-    std::vector<SeqState> hs((size_t)B);
-    std::vector<int> hbad((size_t)B);
-    HIPCHK(hipMemcpyAsync(hs.data(), h->st, sizeof(SeqState) * B, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(hbad.data(), bad, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    cpe_status worst = CPE_OK;
+    std::vector<char> wipe;
+    cpe_status worst;
+    if (cpe_status s = kin_cov_status(h, B, kp, status, wipe, &worst); s != CPE_OK) return s;
     for (int b = 0; b < B; b++) {
-        const bool band_ok = hs[b].status == 0 && hs[b].back_pending == 1;
-        status[b] = band_ok && !hbad[b] ? CPE_OK : CPE_NUMERICAL;
-        if (status[b] > worst) worst = status[b];
-        if (band_ok && hbad[b]) {                           // a node's force matrix has no factor: what the band kernels wrote goes too
+        if (wipe[(size_t)b]) {                              // a node's force matrix has no factor: what the band kernels wrote goes too
             const size_t o = (size_t)b * N;
             HIPCHK(hipMemsetAsync(cov_diag + o * BB, 0, w * N * BB, h->stream));
             if (!off_own.p) HIPCHK(hipMemsetAsync(cov_off + o * 3 * BB, 0, w * N * 3 * BB, h->stream));
@@ -2923,15 +2965,11 @@ static cpe_status covariance_kinetic_host_impl(const char* who, cpe_handle* h, c
                                                const int32_t* n_frames, const double* q, const double* meas, const double* weight, const int32_t* stance,
                                                const double* grf_fixed, const double* tau_box, const double* grf_box, double ridge, double* cov_diag,
                                                double* cov_off, double* cov_pos, double* cov_f, double* f, int32_t* meta, double* L, cpe_status* status) {
-    if (cpe_status s = cov_kinetic_check(who, h, opt, stance, grf_fixed, tau_box, grf_box, ridge); s != CPE_OK) return s;
-    if (!h || !q || !meas || !weight || !cov_diag || !status) return fail(CPE_BAD_ARG, "null argument");
     size_t F;
-    if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
+    std::vector<int2> seq;  // (refused here too: before anything is staged)
+    if (cpe_status s = kin_cov_args(who, h, opt, B, N, model, n_frames, q && meas && weight && cov_diag && status, stance, grf_fixed, tau_box, grf_box, ridge, &F, seq);
+        s != CPE_OK) return s;
     if (F == 0) return CPE_OK;
-    if (model) {            // (refused here too: before anything is staged)
-        std::vector<int2> seq;
-        if (cpe_status s = cov_kinetic_batch(who, h, opt, B, N, model, n_frames, seq); s != CPE_OK) return s;
-    }
     const DevModel& m = h->hm;
     HIPCHK(hipSetDevice(h->device));
     const int nf = opt->dyn.n_feet, nmot = opt->dyn.n_motors;
@@ -2969,6 +3007,124 @@ cpe_status cpe_covariance_kinetic_ragged_host(cpe_handle* h, const cpe_kinetic_o
     if (!model || !n_frames) return fail(CPE_BAD_ARG, "cpe_covariance_kinetic_ragged_host: null model / n_frames");
     return covariance_kinetic_host_impl("cpe_covariance_kinetic_ragged_host", h, opts, B, N_max, model, n_frames, q, meas, weight, stance, grf_fixed, tau_box,
                                         grf_box, ridge, cov_diag, cov_off, cov_pos, cov_f, f, meta, L, status);
+}
+
+// ---- draws of the node forces of the physics-based estimate (include/cpe.h, cpe_force_samples; kernel in cpe_force_sample.hip.inc) -----------
+// What both forms refuse, before the device is touched: cpe_covariance_kinetic's refusals, a null du or f_s, S < 1, too many sample frames.
+// Fills F = B N, FS = B N S and, for the ragged form, the table.
+static cpe_status force_samples_check(const char* who, const cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const int32_t* model,
+                                      const int32_t* n_frames, bool arrays, const int32_t* stance, const double* grf_fixed, const double* tau_box,
+                                      const double* grf_box, double ridge, int32_t S, const double* du, const double* f_s, size_t* F, size_t* FS,
+                                      std::vector<int2>& seq) {
+    if (cpe_status s = cov_kinetic_check(who, h, opt, stance, grf_fixed, tau_box, grf_box, ridge); s != CPE_OK) return s;
+    if (!du || !f_s) return fail(CPE_BAD_ARG, std::string(who) + ": null du / f_s");
+    if (cpe_status s = sample_sizes(std::string(who) + ": ", B, N, S, F, FS); s != CPE_OK) return s;
+    if (!h || !arrays) return fail(CPE_BAD_ARG, "null argument");                  // (what needs a handle last)
+    if (*F == 0 || !model) return CPE_OK;
+    return cov_kinetic_batch(who, h, opt, B, N, model, n_frames, seq);
+}
+
+// cpe_force_samples (model == null) and cpe_force_samples_ragged: the first pass of covariance_kinetic_impl, then k_force_sample on its pieces
+static cpe_status force_samples_impl(const char* who, cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const int32_t* model,
+                                     const int32_t* n_frames, const double* q, const double* meas, const double* weight, const int32_t* stance,
+                                     const double* grf_fixed, const double* tau_box, const double* grf_box, double ridge, int32_t S, const double* du,
+                                     const double* zeta, double* f_s, double* f, int32_t* meta, cpe_status* status) {
+    size_t F, FS;
+    std::vector<int2> seq;
+    if (cpe_status s = force_samples_check(who, h, opt, B, N, model, n_frames, q && meas && weight && status, stance, grf_fixed, tau_box, grf_box, ridge, S, du,
+                                           f_s, &F, &FS, seq); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    HIPCHK(hipSetDevice(h->device));
+    KinCovPass kp;
+    if (cpe_status s = kin_cov_setup(who, h, opt, B, N, F, seq, q, grf_fixed, tau_box, grf_box, kp); s != CPE_OK) return s;
+    const size_t w = sizeof(double);
+    // a sequence without a factor has all outputs zero, and so have the nodes 0 and 1 and every frame past a sequence's own
+    HIPCHK(hipMemsetAsync(f_s, 0, w * FS * KIN_LS, h->stream));
+    if (f) HIPCHK(hipMemsetAsync(f, 0, w * F * KIN_LS, h->stream));
+    if (meta) HIPCHK(hipMemsetAsync(meta, 0, sizeof(int32_t) * F * (KIN_LS + 1), h->stream));
+    kin_cov_pass(h, B, N, F, meas, weight, stance, ridge, kp);
+    with_ragged(kp.rg, [&](auto r, RaggedArgs a) {
+        hipLaunchKernelGGL(k_force_sample<decltype(r)::value>, dim3((unsigned)F), dim3(KIN_THREADS), sizeof(double) * FS_DOUBLES, h->stream, h->dk, h->st, N, F,
+                           h->pieces, h->pmeta, h->fbuf, h->kmu, stance, S, du, zeta, f_s, f, meta, kp.bad, a);
+    });
+    HIPCHK(hipGetLastError());
+    std::vector<char> wipe;
+    cpe_status worst;
+    if (cpe_status s = kin_cov_status(h, B, kp, status, wipe, &worst); s != CPE_OK) return s;
+    for (int b = 0; b < B; b++) {
+        if (wipe[(size_t)b]) {                              // a node's force matrix has no factor: what the other nodes wrote goes
+            const size_t o = (size_t)b * N;
+            HIPCHK(hipMemsetAsync(f_s + o * S * KIN_LS, 0, w * N * S * KIN_LS, h->stream));
+            if (f) HIPCHK(hipMemsetAsync(f + o * KIN_LS, 0, w * N * KIN_LS, h->stream));
+            if (meta) HIPCHK(hipMemsetAsync(meta + o * (KIN_LS + 1), 0, sizeof(int32_t) * N * (KIN_LS + 1), h->stream));
+        }
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));                // (the buffers of this call are freed on return)
+    return worst;
+}
+
+cpe_status cpe_force_samples(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q, const double* meas, const double* weight,
+                             const int32_t* stance, const double* grf_fixed, const double* tau_box, const double* grf_box, double ridge, int32_t S,
+                             const double* du, const double* zeta, double* f_s, double* f, int32_t* meta, cpe_status* status) {
+    return force_samples_impl("cpe_force_samples", h, opt, B, N, nullptr, nullptr, q, meas, weight, stance, grf_fixed, tau_box, grf_box, ridge, S, du, zeta, f_s,
+                              f, meta, status);
+}
+
+cpe_status cpe_force_samples_ragged(cpe_handle* h, const cpe_kinetic_options* opts, int32_t B, int32_t N_max, const int32_t* model, const int32_t* n_frames,
+                                    const double* q, const double* meas, const double* weight, const int32_t* stance, const double* grf_fixed,
+                                    const double* tau_box, const double* grf_box, double ridge, int32_t S, const double* du, const double* zeta, double* f_s,
+                                    double* f, int32_t* meta, cpe_status* status) {
+    if (!model || !n_frames) return fail(CPE_BAD_ARG, "cpe_force_samples_ragged: null model / n_frames");
+    return force_samples_impl("cpe_force_samples_ragged", h, opts, B, N_max, model, n_frames, q, meas, weight, stance, grf_fixed, tau_box, grf_box, ridge, S, du,
+                              zeta, f_s, f, meta, status);
+}
+
+// host-pointer twins (stage through HBM): cpe_force_samples_host (model == null) and cpe_force_samples_ragged_host
+static cpe_status force_samples_host_impl(const char* who, cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const int32_t* model,
+                                          const int32_t* n_frames, const double* q, const double* meas, const double* weight, const int32_t* stance,
+                                          const double* grf_fixed, const double* tau_box, const double* grf_box, double ridge, int32_t S, const double* du,
+                                          const double* zeta, double* f_s, double* f, int32_t* meta, cpe_status* status) {
+    size_t F, FS;
+    std::vector<int2> seq;  // (refused here too: before anything is staged)
+    if (cpe_status s = force_samples_check(who, h, opt, B, N, model, n_frames, q && meas && weight && status, stance, grf_fixed, tau_box, grf_box, ridge, S, du,
+                                           f_s, &F, &FS, seq); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    const DevModel& m = h->hm;
+    HIPCHK(hipSetDevice(h->device));
+    const int nf = opt->dyn.n_feet, nmot = opt->dyn.n_motors;
+    const size_t nm = F * cams_max(h) * m.L;
+    const double* var = grf_fixed ? grf_fixed : (tau_box ? tau_box : grf_box);
+    const size_t nvar = grf_fixed ? F * nf * 3 : (tau_box ? F * nmot * 2 : (grf_box ? F * nf * 6 : 0));
+    Staging st(h->stream);
+    const double *dq = st.in(q, F * m.nq), *dmeas = st.in(meas, nm * 2), *dweight = st.in(weight, nm);
+    const int32_t* dstance = st.in(stance, F * nf);
+    const double* dvar = st.in(var, nvar);
+    const double *ddu = st.in(du, FS * CPE_NX), *dzeta = st.in(zeta, FS * KIN_LS);
+    double *os = st.out(f_s, FS * KIN_LS), *of = st.out_opt(f, F * KIN_LS);
+    int32_t* ometa = st.out_opt(meta, F * (KIN_LS + 1));
+    HIPCHK(st.err);
+    const cpe_status s = force_samples_impl(model ? "cpe_force_samples_ragged" : "cpe_force_samples", h, opt, B, N, model, n_frames, dq, dmeas, dweight, dstance,
+                                            grf_fixed ? dvar : nullptr, tau_box ? dvar : nullptr, grf_box ? dvar : nullptr, ridge, S, ddu, dzeta, os, of, ometa,
+                                            status);
+    if (s < 0) return s;
+    HIPCHK(st.fetch());
+    return s;
+}
+
+cpe_status cpe_force_samples_host(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q, const double* meas,
+                                  const double* weight, const int32_t* stance, const double* grf_fixed, const double* tau_box, const double* grf_box,
+                                  double ridge, int32_t S, const double* du, const double* zeta, double* f_s, double* f, int32_t* meta, cpe_status* status) {
+    return force_samples_host_impl("cpe_force_samples_host", h, opt, B, N, nullptr, nullptr, q, meas, weight, stance, grf_fixed, tau_box, grf_box, ridge, S, du,
+                                   zeta, f_s, f, meta, status);
+}
+
+cpe_status cpe_force_samples_ragged_host(cpe_handle* h, const cpe_kinetic_options* opts, int32_t B, int32_t N_max, const int32_t* model,
+                                         const int32_t* n_frames, const double* q, const double* meas, const double* weight, const int32_t* stance,
+                                         const double* grf_fixed, const double* tau_box, const double* grf_box, double ridge, int32_t S, const double* du,
+                                         const double* zeta, double* f_s, double* f, int32_t* meta, cpe_status* status) {
+    if (!model || !n_frames) return fail(CPE_BAD_ARG, "cpe_force_samples_ragged_host: null model / n_frames");
+    return force_samples_host_impl("cpe_force_samples_ragged_host", h, opts, B, N_max, model, n_frames, q, meas, weight, stance, grf_fixed, tau_box, grf_box,
+                                   ridge, S, du, zeta, f_s, f, meta, status);
 }
 
 #ifdef CPE_LM_STAMPS

@@ -622,6 +622,45 @@ def sample_normals(seed: int, K: int, N: int) -> np.ndarray:
     return np.random.default_rng(seed).standard_normal((K, N, abi.NX))
 
 
+# estimate_kinetics / estimate_grf(uncertainty=True, uncertainty_samples=K): SAMPLE_FIELDS plus the node forces of every draw (cpe_force_samples)
+# in the layouts of tau_std, lambda_std and grf_std -- tau [K, N, n_motors], lam [K, N, n_con], grf_net [K, N, n_feet, 3] (z, x, y) -- and the
+# forces the draws are centred on, tau_mean, lam_mean, grf_net_mean: those of the covariance call's evaluation (cold start at the stored q,
+# multipliers zero), not the solve's own
+KINETIC_SAMPLE_FIELDS = SAMPLE_FIELDS + ("tau", "lam", "grf_net", "tau_mean", "lam_mean", "grf_net_mean")
+
+
+def sample_force_normals(seed: int, K: int, N: int) -> np.ndarray:
+    """zeta [K, N, 64] of K samples of the node forces of a sequence of N frames: a function of (seed, K, N) alone, as sample_normals, and a
+    stream of its own (z stays sample_normals(seed, K, N): the du of a physics draw follows the kinematic rule)"""
+    return np.random.default_rng([seed, 1]).standard_normal((K, N, 64))
+
+
+def _with_force_samples(cov: dict, K: int, seed: int, call) -> dict:
+    """a kinetic covariance result that _with_samples has completed with, for uncertainty_samples=K > 0, the node forces of the same draws under
+    "samples": ONE cpe_force_samples call per group.  call(du [B, K, Nm, 28], zeta [B, K, Nm, 64], lens) makes it with the covariance call's own
+    arguments and returns its padded outputs (f_s [B, K, Nm, 64], f [B, Nm, 64])."""
+    if K <= 0:
+        return cov
+    sm = cov["samples"]
+    B, _, Nm = sm["du"].shape[:3]
+    zeta = np.zeros((B, K, Nm, 64))
+    for b, n in enumerate(sm["lens"]):
+        zeta[b, :, :n] = sample_force_normals(seed, K, n)
+    fs = call(sm["du"], zeta, sm["lens"])
+    sm.update(f_s=fs["f_s"], f=fs["f"])
+    return cov
+
+
+def force_sample_fields(f_s: np.ndarray, f: np.ndarray, n_motors: int, n_con: int, n_feet: int) -> dict:
+    """f_s [K, N, 64] and f [N, 64] of cpe_force_samples in the layout tau | lambda | (z, x, y) per foot -> the force fields of
+    KINETIC_SAMPLE_FIELDS"""
+    a, b = n_motors, n_motors + n_con
+    cut = lambda v: (np.ascontiguousarray(v[..., :a]), np.ascontiguousarray(v[..., a:b]),
+                     np.ascontiguousarray(v[..., b:b + 3 * n_feet].reshape(v.shape[:-1] + (n_feet, 3))))
+    (tau, lam, grf), (tau_m, lam_m, grf_m) = cut(f_s), cut(f)
+    return dict(tau=tau, lam=lam, grf_net=grf, tau_mean=tau_m, lam_mean=lam_m, grf_net_mean=grf_m)
+
+
 def _with_samples(h, cov: dict, q, K: int, seed: int, model_list=None) -> dict:
     """a covariance result (made with want_L=True) with, for uncertainty_samples=K > 0, K draws of every sequence under "samples": ONE
     cpe_band_sample call on the factor the covariance call returned -- no second factorisation; a sequence without a factor takes no part (frame
@@ -653,19 +692,27 @@ def _samples_of(cov: Optional[dict], b: int, ridge: float) -> Optional[dict]:
                 q=np.ascontiguousarray(sm["q"][b]), positions=np.ascontiguousarray(sm["positions"][b]))
 
 
-def _store_samples(est, h, samples: Optional[dict], out_dir: str) -> None:
-    """est.samples = SAMPLE_FIELDS of this sequence (h: a handle of its model) and samples.npz beside uncertainty.npz; None: no samples, no file"""
-    est.samples = None
-    if samples is None:
-        return
+def _complete_samples(est, h, samples: Optional[dict]) -> Optional[dict]:
+    """the sample fields of this sequence with those computed from q (h: a handle of its model): x and com_pos; None stays None"""
+    if samples is None or "x" in samples:
+        return samples
     import torch
     q = samples["q"]
     dev = torch.device("cuda", est.device)
     pos = torch.empty(q.shape[:2] + (est.skeleton.n_markers, 3), dtype=torch.float64, device=dev)
     com = torch.empty(q.shape[:2] + (3,), dtype=torch.float64, device=dev)
     h.forward_kinematics(torch.tensor(q, device=dev), pos, com); h.synchronize()
-    est.samples = dict(samples, x=est.relative_angles(q), com_pos=com.cpu().numpy())
-    assert set(est.samples) == set(SAMPLE_FIELDS)
+    return dict(samples, x=est.relative_angles(q), com_pos=com.cpu().numpy())
+
+
+def _store_samples(est, h, samples: Optional[dict], out_dir: str, fields=SAMPLE_FIELDS) -> None:
+    """est.samples = `fields` of this sequence (h: a handle of its model, or None for samples _complete_samples has seen) and samples.npz beside
+    uncertainty.npz; None: no samples, no file"""
+    est.samples = None
+    if samples is None:
+        return
+    est.samples = _complete_samples(est, h, samples)
+    assert set(est.samples) == set(fields)
     np.savez(os.path.join(out_dir, "samples.npz"), **est.samples)
 
 
@@ -829,6 +876,7 @@ class KineticUncertainty:
     (both None: the solve did not converge, nothing was asked of the library)"""
     fields: Optional[dict] = None
     reason: Optional[str] = None
+    samples: Optional[dict] = None          # uncertainty_samples: KINETIC_SAMPLE_FIELDS of the sequence but x and com_pos (_complete_samples)
 
 
 def _no_factor_reason(ridge: float, names: Optional[Sequence[str]] = None) -> str:
@@ -844,28 +892,42 @@ def _kinetic_uncertainty_of(cov: dict, b: int, ridge: float, res: dict) -> Kinet
     if cov["seq_status"][b] != abi.OK:
         return KineticUncertainty(reason=_no_factor_reason(ridge))
     unc = _uncertainty_of(cov, b, ridge)
-    unc.update(force_uncertainty(cov["cov_f"][b], cov["meta"][b], res["tau"].shape[-1], res["lam"].shape[-1], res["grf"].shape[-2]))
-    return KineticUncertainty(fields=unc)
+    counts = res["tau"].shape[-1], res["lam"].shape[-1], res["grf"].shape[-2]
+    unc.update(force_uncertainty(cov["cov_f"][b], cov["meta"][b], *counts))
+    sm = _samples_of(cov, b, ridge)
+    if sm is not None:
+        n = cov["samples"]["lens"][b]
+        sm.update(force_sample_fields(cov["samples"]["f_s"][b, :, :n], cov["samples"]["f"][b, :n], *counts))
+    return KineticUncertainty(fields=unc, samples=sm)
 
 
 def _kinetic_uncertainty(h, ko: abi.KineticOptions, res: dict, meas: np.ndarray, weight: np.ndarray, stance: np.ndarray, ridge: float,
-                         grf_fixed=None, tau_box=None, grf_box=None, rates: bool = False, spans=None) -> KineticUncertainty:
-    """cpe_covariance_kinetic at the solution res["q"] of a converged physics-based solve, with the solve's own stance, options and variant arrays"""
+                         grf_fixed=None, tau_box=None, grf_box=None, rates: bool = False, spans=None,
+                         samples: Tuple[int, int] = (0, 0)) -> KineticUncertainty:
+    """cpe_covariance_kinetic at the solution res["q"] of a converged physics-based solve, with the solve's own stance, options and variant arrays;
+    samples = (uncertainty_samples, uncertainty_seed): the draws of _with_samples and, with the same arguments, their node forces"""
     if res["stats"][0].status != abi.OK:
         return KineticUncertainty()
     one = lambda a: None if a is None else a[None]
-    cov = h.covariance_kinetic_host(res["q"], meas[None], weight[None], stance[None], ko, ridge, grf_fixed=one(grf_fixed), tau_box=one(tau_box),
-                                    grf_box=one(grf_box), want_L=spans is not None)
-    return _kinetic_uncertainty_of(_with_rates(h, cov, res["q"], rates, spans=None if spans is None else [spans]), 0, ridge, res)
+    force = dict(grf_fixed=one(grf_fixed), tau_box=one(tau_box), grf_box=one(grf_box))
+    cov = h.covariance_kinetic_host(res["q"], meas[None], weight[None], stance[None], ko, ridge, want_L=spans is not None or samples[0] > 0, **force)
+    cov = _with_rates(h, cov, res["q"], rates, spans=None if spans is None else [spans])
+    cov = _with_samples(h, cov, res["q"], samples[0], samples[1])
+    cov = _with_force_samples(cov, samples[0], samples[1], lambda du, zeta, lens: h.force_samples_host(
+        res["q"], meas[None], weight[None], stance[None], ko, du, zeta, ridge, **force))
+    return _kinetic_uncertainty_of(cov, 0, ridge, res)
 
 
 def _store_kinetic_uncertainty(est: CheetahEstimator, unc: Optional[KineticUncertainty], ok: bool, out_dir: Optional[str],
-                               no_factor: Optional[list] = None) -> None:
+                               no_factor: Optional[list] = None, h=None) -> None:
     """after the solve's own files (unc None: not asked for, nothing changes): est.uncertainty and, for a solve that is `ok`, uncertainty.npz beside
-    fte.pickle -- or the library's reason raised (no_factor, a list: the estimator is appended to it instead, for the batch to raise once at its end)"""
+    fte.pickle -- or the library's reason raised (no_factor, a list: the estimator is appended to it instead, for the batch to raise once at its end).
+    unc.samples (uncertainty_samples): est.samples and samples.npz beside it; h: a handle of the sequence's model, or None where _complete_samples
+    has seen them."""
     if unc is None:
         return
     est.uncertainty = None
+    est.samples = None
     if not ok:
         return
     if unc.reason is not None:
@@ -877,6 +939,7 @@ def _store_kinetic_uncertainty(est: CheetahEstimator, unc: Optional[KineticUncer
         est.uncertainty = unc.fields
         _add_speed_std(est)
         np.savez(os.path.join(out_dir, "uncertainty.npz"), **est.uncertainty)
+        _store_samples(est, h, unc.samples, out_dir, KINETIC_SAMPLE_FIELDS)
 
 
 def _kin_finish(est: CheetahEstimator, h, res: dict, seconds: float, solver_output: bool, monocular_constraints: bool,
@@ -1294,7 +1357,8 @@ def estimate_kinetics(estimator: CheetahEstimator, init_torques: bool = True, au
                       disable_pose_prior: bool = False, disable_motion_prior: bool = False, plot: bool = False, out_fname: str = "fte",
                       out_dir_prefix: Optional[str] = None, options: Optional[abi.Options] = None,
                       kinetic_options: Optional[abi.KineticOptions] = None, uncertainty: bool = False, uncertainty_ridge: float = 0.0,
-                      uncertainty_rates: bool = False, uncertainty_spans=None, track_weights: str = "reference", track_scale: float = 1.0) -> bool:
+                      uncertainty_rates: bool = False, uncertainty_spans=None, track_weights: str = "reference", track_scale: float = 1.0,
+                      uncertainty_samples: int = 0, uncertainty_seed: int = 0) -> bool:
     """Same signature and meaning as acinoset_opt.estimate_kinetics (acinoset_opt.py:693-708) for the branch its drivers run for the
     physics-based reconstruction (`joint_estimation=True`, run_dataset.py:1198-1229): torques, joint constraint forces, ground-reaction
     forces and the trajectory are estimated together, warm-started from the kinematic solution on disk, with the contact windows of
@@ -1313,10 +1377,18 @@ def estimate_kinetics(estimator: CheetahEstimator, init_torques: bool = True, au
     solve's own files are written.  Not with use_2d_reprojections=False (the covariance of the 3D kinematic cost is not built).
     uncertainty_rates=True (with uncertainty=True): the rate fields of estimate_kinematics (RATE_FIELDS), from that covariance.
     uncertainty_spans (with uncertainty=True): the span fields of estimate_kinematics (SPAN_FIELDS), from that covariance.
+    uncertainty_samples=K > 0 (with uncertainty=True): K draws from the JOINT posterior of coordinates and node forces ("What is
+    sampled (forces)"), for the error bar of anything computed from forces of several frames or from forces and poses -- an impulse, a peak force,
+    joint power.  du = L^-T z as in estimate_kinematics (z = sample_normals(uncertainty_seed, K, N), the covariance call's own factor), the poses,
+    then ONE cpe_force_samples call with zeta = sample_force_normals(uncertainty_seed, K, N).  est.samples and samples.npz beside uncertainty.npz
+    hold KINETIC_SAMPLE_FIELDS: estimate_kinematics' fields plus tau [K, N, n_motors], lam [K, N, n_con], grf_net [K, N, n_feet, 3] (z, x, y) and
+    tau_mean, lam_mean, grf_net_mean, the forces the draws are centred on -- the covariance call's cold-start evaluation at the stored q with
+    multipliers zero, not fte.pickle's forces.  est.uncertainty and uncertainty.npz do not change.
     track_weights (use_2d_reprojections=False): "reference" = the reference's 28 constants; "posterior" = frame n is tracked with its own matrix
     W_n = (track_scale / 2) (X Sigma_nn X^T)^-1 from cov_u of the uncertainty.npz that estimate_kinematics(uncertainty=True) wrote beside the
     kinematic result (one cpe_track_precision call, then cpe_solve_kinetic_tracked_weighted; DESIGN.md 2b has the approximation and what
     track_scale is for).  "posterior" with use_2d_reprojections=True, or any other string, is a ValueError."""
+    _check_samples(uncertainty, uncertainty_samples)
     _check_rates(uncertainty, uncertainty_rates)
     _check_spans(uncertainty, uncertainty_spans)
     _check_track_weights(track_weights, track_scale, use_2d_reprojections)
@@ -1336,7 +1408,8 @@ def estimate_kinetics(estimator: CheetahEstimator, init_torques: bool = True, au
         res = _kinetic_solve(h, [prep], [est])                                       # the plain batch of one sequence
         dt = time() - t0
         unc = _kinetic_uncertainty(h, prep["ko"], res, est.meas, est.weight, prep["stance"], uncertainty_ridge, grf_fixed=prep["grf_fixed"],
-                                   grf_box=prep["grf_box"], rates=uncertainty_rates, spans=spans) if uncertainty else None
+                                   grf_box=prep["grf_box"], rates=uncertainty_rates, spans=spans,
+                                   samples=(uncertainty_samples, uncertainty_seed)) if uncertainty else None
         return _kinetic_finish(est, h, res, dt, prep, solver_output, out_fname, out_dir_prefix, uncertainty=unc)
     finally:
         h.close()
@@ -1513,7 +1586,7 @@ def _kinetic_finish(est: CheetahEstimator, h, res: dict, seconds: float, prep: d
         dname = f"fte_kinetic{'_gt' if params.hand_labeled_data else ''}"
         dname = dname if scene.cam_idx is None else f"{dname}_{scene.cam_idx}"
         out_dir = est.save(dname, fname=out_fname, out_dir_prefix=out_dir_prefix)
-    _store_kinetic_uncertainty(est, uncertainty, ok, out_dir, no_factor)
+    _store_kinetic_uncertainty(est, uncertainty, ok, out_dir, no_factor, h)
     return ok
 
 
@@ -1574,7 +1647,8 @@ def estimate_kinetics_batch(estimators: Sequence[CheetahEstimator], init_torques
                             out_dir_prefix: Optional[str] = None, options: Optional[abi.Options] = None,
                             kinetic_options: Optional[abi.KineticOptions] = None, ragged: bool = False, uncertainty: bool = False,
                             uncertainty_ridge: float = 0.0, uncertainty_rates: bool = False, uncertainty_spans=None,
-                            track_weights: str = "reference", track_scale: float = 1.0) -> List[bool]:
+                            track_weights: str = "reference", track_scale: float = 1.0, uncertainty_samples: int = 0,
+                            uncertainty_seed: int = 0) -> List[bool]:
     """estimate_kinetics for MANY sequences at once, with its keyword arguments (applied to every sequence).  Each sequence is prepared as
     estimate_kinetics prepares it (the per-frame force fit of the fix_grf=True, synthesised_grf=False branch included, one sequence at a time),
     then solved in a batch, then gets its centre of mass, costs and files exactly as estimate_kinetics writes them; only processing_time_s (its
@@ -1587,7 +1661,11 @@ def estimate_kinetics_batch(estimators: Sequence[CheetahEstimator], init_torques
     its own estimate_kinetics call.  A sequence without a factor does not stop the batch: every sequence is finished and stored first, then ONE
     CpeError names all of them.  uncertainty_rates=True: as in estimate_kinetics, one rate call after each covariance call, same bit-equality.
     uncertainty_spans: as in estimate_kinetics, resolved for every sequence; one cpe_covariance_columns call per group, same bit-equality.
+    uncertainty_samples, uncertainty_seed: as in estimate_kinetics, every sequence with the z and zeta of its own call; one cpe_band_sample, one
+    cpe_posterior_samples and one cpe_force_samples (ragged: cpe_force_samples_ragged) call per group, same bit-equality of est.samples and
+    samples.npz.
     track_weights / track_scale: as in estimate_kinetics; "posterior" makes ONE cpe_track_precision call per group on the group's handle."""
+    _check_samples(uncertainty, uncertainty_samples)
     _check_rates(uncertainty, uncertainty_rates)
     _check_spans(uncertainty, uncertainty_spans)
     _check_track_weights(track_weights, track_scale, use_2d_reprojections)
@@ -1619,7 +1697,8 @@ def estimate_kinetics_batch(estimators: Sequence[CheetahEstimator], init_torques
     for idx in groups.values():
         (_solve_kinetic_ragged_group if ragged else _solve_kinetic_group)(ests, idx, prepared, out, solver_output, out_fname, out_dir_prefix,
                                                                           uncertainty_ridge if uncertainty else None, no_factor, uncertainty_rates,
-                                                                          None if uncertainty_spans is None else [spans[i] for i in idx])
+                                                                          None if uncertainty_spans is None else [spans[i] for i in idx],
+                                                                          (uncertainty_samples, uncertainty_seed))
     if no_factor:
         raise _lib.CpeError(_no_factor_reason(uncertainty_ridge, [f"{e.name} {e.data_path}" for e in no_factor]))
     return [bool(v) for v in out]
@@ -1640,9 +1719,9 @@ def _batch_kinetic_uncertainty(res: dict, idx, ridge: Optional[float], covarianc
 
 
 def _solve_kinetic_group(ests, idx, prepared, out, solver_output, out_fname, out_dir_prefix, uncertainty_ridge: Optional[float] = None,
-                         no_factor: Optional[list] = None, uncertainty_rates: bool = False, spans=None) -> None:
+                         no_factor: Optional[list] = None, uncertainty_rates: bool = False, spans=None, samples: Tuple[int, int] = (0, 0)) -> None:
     """estimate_kinetics_batch(ragged=False) for one group: one handle, one solve_kinetic_host call with B = the group's size (and, with
-    uncertainty_ridge, one covariance_kinetic_host call)"""
+    uncertainty_ridge, one covariance_kinetic_host call; with samples = (uncertainty_samples, uncertainty_seed) the draws and their forces)"""
     e0, p0 = ests[idx[0]], prepared[idx[0]]
     stack = lambda k: None if p0[k] is None else np.stack([prepared[i][k] for i in idx])
     h = _lib.Handle(p0["skeleton"], e0.cams, p0["opts"], p0["pri"], device=e0.device)
@@ -1651,10 +1730,16 @@ def _solve_kinetic_group(ests, idx, prepared, out, solver_output, out_fname, out
         res = _kinetic_solve(h, [prepared[i] for i in idx], [ests[i] for i in idx])
         dt = (time() - t0) / len(idx)                                                # processing_time_s of a sequence: its share of the batched solve
         cut = lambda a, conv: None if a is None else a[conv]
-        unc = _batch_kinetic_uncertainty(res, idx, uncertainty_ridge, lambda conv: _with_rates(h, h.covariance_kinetic_host(
-            res["q"][conv], np.stack([ests[idx[b]].meas for b in conv]), np.stack([ests[idx[b]].weight for b in conv]), stack("stance")[conv], p0["ko"],
-            uncertainty_ridge, grf_fixed=cut(stack("grf_fixed"), conv), grf_box=cut(stack("grf_box"), conv), want_L=spans is not None),
-            res["q"][conv], uncertainty_rates, spans=None if spans is None else [spans[b] for b in conv]))
+
+        def covariance(conv):
+            a = (res["q"][conv], np.stack([ests[idx[b]].meas for b in conv]), np.stack([ests[idx[b]].weight for b in conv]), stack("stance")[conv], p0["ko"])
+            force = dict(grf_fixed=cut(stack("grf_fixed"), conv), grf_box=cut(stack("grf_box"), conv))
+            cov = h.covariance_kinetic_host(*a, uncertainty_ridge, want_L=spans is not None or samples[0] > 0, **force)
+            cov = _with_rates(h, cov, a[0], uncertainty_rates, spans=None if spans is None else [spans[b] for b in conv])
+            cov = _with_samples(h, cov, a[0], samples[0], samples[1])
+            return _with_force_samples(cov, samples[0], samples[1], lambda du, zeta, lens: h.force_samples_host(*a, du, zeta, uncertainty_ridge, **force))
+
+        unc = _batch_kinetic_uncertainty(res, idx, uncertainty_ridge, covariance)
         for b, i in enumerate(idx):
             out[i] = _kinetic_finish(ests[i], h, _kinetic_one(res, b), dt, prepared[i], solver_output, out_fname, out_dir_prefix, unc.get(b), no_factor)
     finally:
@@ -1662,7 +1747,8 @@ def _solve_kinetic_group(ests, idx, prepared, out, solver_output, out_fname, out
 
 
 def _solve_kinetic_ragged_group(ests, idx, prepared, out, solver_output, out_fname, out_dir_prefix, uncertainty_ridge: Optional[float] = None,
-                                no_factor: Optional[list] = None, uncertainty_rates: bool = False, spans=None) -> None:
+                                no_factor: Optional[list] = None, uncertainty_rates: bool = False, spans=None,
+                                samples: Tuple[int, int] = (0, 0)) -> None:
     """estimate_kinetics_batch(ragged=True) for one group: one model per distinct (skeleton, rig, options, kinetic options), one
     cpe_solve_kinetic_ragged call (and, with uncertainty_ridge, one cpe_covariance_kinetic_ragged call on the same handle), then every sequence's
     centre of mass, costs and files through _kinetic_finish with a plain handle of its model"""
@@ -1681,11 +1767,18 @@ def _solve_kinetic_ragged_group(ests, idx, prepared, out, solver_output, out_fna
         fkw = {} if force is None else {force: [prepared[i][force] for i in idx]}
         res = _kinetic_solve(h, [prepared[i] for i in idx], [ests[i] for i in idx], of)
         dt = (time() - t0) / len(idx)                                                # processing_time_s of a sequence: its share of the batched solve
-        unc = _batch_kinetic_uncertainty(res, idx, uncertainty_ridge, lambda conv: _with_rates(h, h.covariance_kinetic_ragged_host(
-            [res["q"][b] for b in conv], [ests[idx[b]].meas for b in conv], [ests[idx[b]].weight for b in conv],
-            [prepared[idx[b]]["stance"] for b in conv], [prepared[i]["ko"] for i in reps], [of[b] for b in conv], uncertainty_ridge,
-            want_L=spans is not None, **{k: [v[b] for b in conv] for k, v in fkw.items()}), [res["q"][b] for b in conv], uncertainty_rates,
-            [of[b] for b in conv], None if spans is None else [spans[b] for b in conv]))
+        def covariance(conv):
+            a = ([res["q"][b] for b in conv], [ests[idx[b]].meas for b in conv], [ests[idx[b]].weight for b in conv],
+                 [prepared[idx[b]]["stance"] for b in conv], [prepared[i]["ko"] for i in reps])
+            ofc, force = [of[b] for b in conv], {k: [v[b] for b in conv] for k, v in fkw.items()}
+            cov = h.covariance_kinetic_ragged_host(*a, ofc, uncertainty_ridge, want_L=spans is not None or samples[0] > 0, **force)
+            cov = _with_rates(h, cov, a[0], uncertainty_rates, ofc, None if spans is None else [spans[b] for b in conv])
+            cov = _with_samples(h, cov, a[0], samples[0], samples[1], ofc)
+            cuts = lambda v, lens: [np.ascontiguousarray(v[b, :, :n]) for b, n in enumerate(lens)]
+            return _with_force_samples(cov, samples[0], samples[1], lambda du, zeta, lens: h.force_samples_ragged_host(
+                *a, cuts(du, lens), cuts(zeta, lens), ofc, uncertainty_ridge, **force)["padded"])
+
+        unc = _batch_kinetic_uncertainty(res, idx, uncertainty_ridge, covariance)
         for b, i in enumerate(idx):
             if of[b] not in fk:
                 r = reps[of[b]]
@@ -1709,7 +1802,8 @@ def bound_value(val, slack_percentage: float) -> np.ndarray:
 
 def estimate_grf(estimator: CheetahEstimator, solver_output: bool = True, out_dir_prefix: Optional[str] = None,
                  options: Optional[abi.Options] = None, kinetic_options: Optional[abi.KineticOptions] = None, uncertainty: bool = False,
-                 uncertainty_ridge: float = 0.0, uncertainty_rates: bool = False, uncertainty_spans=None) -> bool:
+                 uncertainty_ridge: float = 0.0, uncertainty_rates: bool = False, uncertainty_spans=None, uncertainty_samples: int = 0,
+                 uncertainty_seed: int = 0) -> bool:
     """Same signature and meaning as the module-level acinoset_opt.estimate_grf (acinoset_opt.py:966-1048), the last stage of the kinetic-dataset
     pipeline (run_dataset.py:1125-1138): the physics-based model is solved again from the stored `fte_kinetic/fte.pickle` -- trajectory as the
     starting point, every torque within 10 % of its stored value (`Tc.bounds = bound_value(init_tau, 0.1)`, :995-1003) -- with the ground-reaction
@@ -1722,7 +1816,10 @@ def estimate_grf(estimator: CheetahEstimator, solver_output: bool = True, out_di
     applied to it, otherwise the window alone decides (a loaded plate never reads exactly zero).
     uncertainty=True: as in estimate_kinetics, with the torque boxes of this solve; uncertainty.npz goes beside fte_grf/fte.pickle.
     uncertainty_rates=True (with uncertainty=True): the rate fields of estimate_kinematics (RATE_FIELDS), from that covariance.
-    uncertainty_spans (with uncertainty=True): the span fields of estimate_kinematics (SPAN_FIELDS), from that covariance."""
+    uncertainty_spans (with uncertainty=True): the span fields of estimate_kinematics (SPAN_FIELDS), from that covariance.
+    uncertainty_samples, uncertainty_seed (with uncertainty=True): as in estimate_kinetics (KINETIC_SAMPLE_FIELDS), with the torque boxes of this
+    solve; samples.npz goes beside uncertainty.npz."""
+    _check_samples(uncertainty, uncertainty_samples)
     _check_rates(uncertainty, uncertainty_rates)
     _check_spans(uncertainty, uncertainty_spans)
     est, params, scene, sk = estimator, estimator.params, estimator.scene, estimator.skeleton
@@ -1777,7 +1874,9 @@ def estimate_grf(estimator: CheetahEstimator, solver_output: bool = True, out_di
         res = h.solve_kinetic_host(ko, q_init[None], est.meas[None], est.weight[None], stance[None], tau_box=tau_box[None])
         est.opt_time_s = time() - t0
         if uncertainty:
-            unc = _kinetic_uncertainty(h, ko, res, est.meas, est.weight, stance, uncertainty_ridge, tau_box=tau_box, rates=uncertainty_rates, spans=spans)
+            unc = _kinetic_uncertainty(h, ko, res, est.meas, est.weight, stance, uncertainty_ridge, tau_box=tau_box, rates=uncertainty_rates, spans=spans,
+                                       samples=(uncertainty_samples, uncertainty_seed))
+            unc.samples = _complete_samples(est, h, unc.samples)
         import torch
         dev = torch.device("cuda", est.device)
         qd = torch.tensor(res["q"], device=dev)

@@ -822,6 +822,56 @@ cpe_status cpe_covariance_kinetic_ragged_host(cpe_handle* h, const cpe_kinetic_o
                                               const double* grf_fixed, const double* tau_box, const double* grf_box, double ridge, double* cov_diag,
                                               double* cov_off, double* cov_pos, double* cov_f, double* f, int32_t* meta, double* L, cpe_status* status);
 
+/* ---- draws of the node forces of the physics-based estimate ("What is sampled (forces)"): whole trajectories of torques, joint
+ * constraint forces and net foot forces JOINTLY with the coordinates, for the error bar of any quantity computed from them -- the impulse of a stance,
+ * a peak force and its frame, joint power and work, a duty factor from a force threshold -- which need the covariance between the forces of different
+ * frames and between forces and coordinates, not only cov_f(n).  The band cpe_covariance_kinetic factors (A = L L^T) is the Schur complement of the
+ * joint Gauss-Newton matrix over (coordinates, node forces).  Ordered as (forces of every node, coordinates) that joint matrix has the lower factor
+ *     G = [[ blockdiag(C_n), 0 ], [ H_uf C_n^-T, L ]],        M_n = C_n C_n^T  (the node's force matrix as eliminated),
+ * so G^T (df, du) = (zeta, z) with z, zeta ~ N(0, I) is a draw of the joint Laplace posterior:
+ *     L^T du = z                                        (cpe_band_sample on the L cpe_covariance_kinetic returns)
+ *     df_n = C_n^-T (zeta_n - Y_n w_n),   Y_n = C_n^-1 H_fu(n),   w_n = (du_n, du_{n-1}, du_{n-2}),   n >= 2      (this entry)
+ * with cov(df_n) = M_n^-1 + S_n W_n S_n^T = cov_f(n) exactly, cov(df_n, du) = -S_n Sigma(w_n, .), and for n != m cov(df_n, df_m) =
+ * S_n Sigma(w_n, w_m) S_m^T -- blocks of Sigma at any distance, which only sampling reaches without a dense inverse.
+ * The entry is stateless: it runs the first pass of cpe_covariance_kinetic itself (cold start at Euler q, multipliers zero, damping `ridge`, up to and
+ * including the band factor), then one kernel over the nodes.  That pass is deterministic: f, meta and status[b] are bit-equal to
+ * cpe_covariance_kinetic's for the same inputs, and M_n is the matrix behind its cov_f.
+ * Device pointers except status.  q, meas, weight, stance, grf_fixed / tau_box / grf_box, ridge: as cpe_covariance_kinetic.  du [B][S][N][28]:
+ * cpe_band_sample's output, or any step in the reduced coordinates.  zeta [B][S][N][64]: standard normals in the compact order of meta[n]; entries past
+ * the node's count are not read; NULL = zeros, which gives the conditional mean f - S_n w_n.  f_s [B][S][N][64], f's layout tau | lambda | (z, x, y)
+ * per foot: f + df on the node's unknowns; a force that is no unknown of the node keeps f's value; the nodes 0, 1 and the frames past a sequence's
+ * own are exactly 0.0.  f [B][N][64], meta int32 [B][N][65]: as cpe_covariance_kinetic, may be NULL.  status [B], HOST: CPE_NUMERICAL under
+ * cpe_covariance_kinetic's conditions (the evaluation is not finite, or the band or a node's M_n has no Cholesky factor) -- all outputs of that
+ * sequence are zero.  Returns the worst status.  Every sum has a fixed order (no atomics): a sample's forces are bit-equal whatever S, its slot s and
+ * the batch.
+ * Named deviations -- a draw is NOT: (linear) re-minimised: the forces are the linearisation about the evaluation, not the minimiser at the sampled
+ * pose; (inequalities) feasible: the friction polyhedron, Fz >= 0.01 and the torque / force boxes are not enforced, a row active at the evaluation
+ * contributes its penalty curvature, an inactive one nothing; (centre) centred on anything but the evaluation's f -- the cold-start evaluation at q
+ * with multipliers zero, not a converged solve's forces; (ridge) as wide as the posterior at ridge > 0: M_n and the band are both damped, the draws
+ * are narrower; plus those of cpe_covariance_kinetic.
+ * Refused with CPE_BAD_ARG before the device is touched, the reason in cpe_last_error(): what cpe_covariance_kinetic refuses; S < 1; negative sizes
+ * or more than 2^31 - 1 sample frames (B N S); NULL du or f_s. */
+cpe_status cpe_force_samples(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q, const double* meas,
+                             const double* weight, const int32_t* stance, const double* grf_fixed, const double* tau_box, const double* grf_box,
+                             double ridge, int32_t S, const double* du, const double* zeta, double* f_s, double* f, int32_t* meta, cpe_status* status);
+/* host-pointer twin (stages through HBM) */
+cpe_status cpe_force_samples_host(cpe_handle* h, const cpe_kinetic_options* opt, int32_t B, int32_t N, const double* q, const double* meas,
+                                  const double* weight, const int32_t* stance, const double* grf_fixed, const double* tau_box, const double* grf_box,
+                                  double ridge, int32_t S, const double* du, const double* zeta, double* f_s, double* f, int32_t* meta,
+                                  cpe_status* status);
+/* The same for sequences of their own length, rig and model, in cpe_covariance_kinetic_ragged's layout (du, zeta, f_s padded to N_max frames): every
+ * sequence's rows are bit-equal to its own plain call, rows past its length read 0, and a sequence that is CPE_NUMERICAL does not disturb a
+ * neighbour's bits.  Also refused: what cpe_covariance_kinetic_ragged refuses. */
+cpe_status cpe_force_samples_ragged(cpe_handle* h, const cpe_kinetic_options* opts, int32_t B, int32_t N_max, const int32_t* model /*[B] host*/,
+                                    const int32_t* n_frames /*[B] host*/, const double* q, const double* meas, const double* weight,
+                                    const int32_t* stance, const double* grf_fixed, const double* tau_box, const double* grf_box, double ridge,
+                                    int32_t S, const double* du, const double* zeta, double* f_s, double* f, int32_t* meta, cpe_status* status);
+/* host-pointer twin (stages through HBM) */
+cpe_status cpe_force_samples_ragged_host(cpe_handle* h, const cpe_kinetic_options* opts, int32_t B, int32_t N_max, const int32_t* model,
+                                         const int32_t* n_frames, const double* q, const double* meas, const double* weight, const int32_t* stance,
+                                         const double* grf_fixed, const double* tau_box, const double* grf_box, double ridge, int32_t S,
+                                         const double* du, const double* zeta, double* f_s, double* f, int32_t* meta, cpe_status* status);
+
 /* forward kinematics only (get_pose_state / get_com, acinoset_misc.py:1581-1659, :722-742); device ptrs */
 cpe_status cpe_forward_kinematics(cpe_handle* h, int32_t B, int32_t N, const double* q,
                                   double* positions /*[B][N][L][3]*/, double* com /*[B][N][3] or NULL*/);
