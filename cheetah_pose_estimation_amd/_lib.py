@@ -963,6 +963,58 @@ class Handle:
         cut = lambda a: None if a is None else [np.ascontiguousarray(a[b, :, :n]) for b, n in enumerate(lens)]
         return dict(q=cut(q_s), positions=cut(pos), padded=dict(q=q_s, positions=pos))
 
+    # ---- the reduced system of the length calibration (include/cpe.h, cpe_scale_system) ---------------------------------------------------
+    def _scale_tables(self, who, d_attach, d_marker_off):
+        """G and the host tables d_attach [M, G, n_links, 3], d_marker_off [M, G, n_markers, 3] (M = the handle's models; a table of one model
+        may come without the leading axis)"""
+        da, dm = _f64(d_attach), _f64(d_marker_off)
+        M = len(self.model_n_cams)
+        if da.ndim == 3 and dm.ndim == 3 and M == 1:
+            da, dm = da[None], dm[None]
+        G = da.shape[1] if da.ndim == 4 else -1
+        if da.shape != (M, G, self.sk.n_links, 3) or dm.shape != (M, G, self.L, 3):
+            raise ValueError(f"{who}: d_attach is [{M}, G, {self.sk.n_links}, 3] and d_marker_off [{M}, G, {self.L}, 3]")
+        return G, np.ascontiguousarray(da), np.ascontiguousarray(dm)
+
+    def scale_system(self, q, meas, weight, d_attach, d_marker_off, A, b, A_red, b_red, cost, ridge=0.0, model=None, n_frames=None):
+        """cpe_scale_system on device tensors: the Gauss-Newton system of G segment-length scales at Euler q [B, N, nq], poses eliminated through
+        the band factor of (H + ridge D).  d_attach, d_marker_off: numpy (skeleton.length_derivatives).  A, A_red [B, G, G], b, b_red [B, G],
+        cost [B] device tensors.  Returns (status, [status of every sequence]) as covariance() does."""
+        B, N = q.shape[0], q.shape[1]
+        G, da, dm = self._scale_tables("scale_system", d_attach, d_marker_off)
+        if (model is None) != (n_frames is None):
+            raise ValueError("scale_system: model and n_frames are given together or not at all")
+        mo = nf = None
+        if model is not None:
+            if len(model) != B or len(n_frames) != B:
+                raise ValueError("scale_system: one model index and one frame count per sequence")
+            mo, nf = _int32s(B, model), _int32s(B, n_frames)
+        for name, t, shape in (("A", A, (B, G, G)), ("b", b, (B, G)), ("A_red", A_red, (B, G, G)), ("b_red", b_red, (B, G)), ("cost", cost, (B,))):
+            if t is None or tuple(t.shape) != shape or t.element_size() != 8 or not t.dtype.is_floating_point or not t.is_contiguous():
+                raise ValueError(f"scale_system: {name} is a contiguous float64 tensor of shape {shape}")
+        seq = _int32s(B)
+        st = self._call(self.lib.cpe_scale_system, "cpe_scale_system", B, N, mo, nf, _ptr(q), _ptr(meas), _ptr(weight), float(ridge), G, _ptr(da),
+                        _ptr(dm), _ptr(A), _ptr(b), _ptr(A_red), _ptr(b_red), _ptr(cost), seq, allow=(abi.OK, abi.NUMERICAL))
+        return st, list(seq)[:B]
+
+    def scale_system_host(self, q, meas, weight, d_attach, d_marker_off, ridge=0.0, model_list=None):
+        """cpe_scale_system_host: q [B, N, nq], meas, weight numpy -> dict(A, A_red [B, G, G], b, b_red [B, G], cost [B], status, seq_status); or,
+        for sequences of their own length and model (lists, as covariance_ragged_host takes them; model_list None = model 0), ONE ragged call"""
+        if isinstance(q, (list, tuple)):
+            p = self._ragged_batch("scale_system_host", "one q, meas, weight and model", model_list, q_init=q, meas=meas, weight=weight)
+            qp, mp, wp, mo, nf = p["q_init"], p["meas"], p["weight"], p["model_arr"], p["len_arr"]
+        else:
+            qp, mp, wp, mo, nf = _f64(q), _f64(meas), _f64(weight), None, None
+        B, N = qp.shape[:2]
+        G, da, dm = self._scale_tables("scale_system_host", d_attach, d_marker_off)
+        out = dict(A=np.empty((B, G, G)), b=np.empty((B, G)), A_red=np.empty((B, G, G)), b_red=np.empty((B, G)), cost=np.empty(B))
+        seq = _int32s(B)
+        st = self.lib.cpe_scale_system_host(self._h, B, N, mo, nf, _ptr(qp), _ptr(mp), _ptr(wp), float(ridge), G, _ptr(da), _ptr(dm), _ptr(out["A"]),
+                                            _ptr(out["b"]), _ptr(out["A_red"]), _ptr(out["b_red"]), _ptr(out["cost"]), seq)
+        _check(st, "cpe_scale_system_host", allow=(abi.OK, abi.NUMERICAL))
+        out.update(status=st, seq_status=list(seq)[:B])
+        return out
+
     # ---- posterior covariance of the rates (include/cpe.h, cpe_rate_covariance) -----------------------------------------------------------
     def rate_covariance(self, q, cov_diag, cov_off, cov_du=None, cov_ddu=None, cov_vel=None, cov_com=None, cov_com_vel=None, jac_pos=None,
                         jac_com=None):

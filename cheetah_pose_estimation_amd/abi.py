@@ -227,6 +227,14 @@ FORCE_SAMPLE_ENTRIES = {
     "cpe_force_samples_ragged": _KIN_BN + _RAGGED + _FORCE_SAMPLES,
     "cpe_force_samples_ragged_host": _KIN_BN + _RAGGED + _FORCE_SAMPLES,
 }
+# the reduced system of the length calibration (cpe_scale_system): h, B, N | model, n_frames | q, meas, weight | ridge | G | d_attach, d_marker_off
+# (host) | A, b, A_red, b_red, cost | status
+MAX_SCALES = 16
+_SCALE_SYSTEM = _BN + _RAGGED + ("p", "p", "p", "d", "i", "p", "p") + ("p",) * 5 + ("ip",)
+SCALE_ENTRIES = {
+    "cpe_scale_system": _SCALE_SYSTEM,
+    "cpe_scale_system_host": _SCALE_SYSTEM,
+}
 COVARIANCE_MAX_PB = 4        # largest half-bandwidth (frames) the covariance sweep supports: motion-prior windows 5 and 6 are refused
 ENTRIES = {
     "cpe_create": ("sk", "cam", "i", "op", "pr", "i", "hp"),
@@ -293,6 +301,7 @@ ENTRIES = {
     "cpe_eval_active_list": ("h", "i", "i", "ip", "ip", "ip"),         # B, window | status | act, n_act (host)
     **COVARIANCE_ENTRIES, **KINETIC_COVARIANCE_ENTRIES, **KINETIC_COVARIANCE_RAGGED_ENTRIES, **RATE_COVARIANCE_ENTRIES,
     **{name: _COLUMNS for name in COLUMN_COVARIANCE_ENTRIES}, **SAMPLE_ENTRIES, **FORCE_SAMPLE_ENTRIES,
+    **SCALE_ENTRIES,
 }
 
 

@@ -140,6 +140,16 @@ static double host_rho0(double a, double b, double c) {
            sc * (a * b - 0.5 * a * a + 0.5 * a * cb);
 }
 
+// The chain vectors of one marker (DevModel::chain_vec) from the root down: in the frame of link chain_link[i], where the next link of the chain
+// attaches, and for the last link the marker's offset.  Linear in (attach, marker_off): given the derivatives of the two tables by a length
+// scale, the same loop returns the derivatives of the chain vectors (cpe_scale_system).
+static void chain_vectors(const int32_t* chain_link, int n, const double (*attach)[3], const double* marker_off, double (*vec)[3]) {
+    for (int i = 0; i < n; i++) {
+        const double* v = i == n - 1 ? marker_off : attach[chain_link[i + 1]];
+        for (int d = 0; d < 3; d++) vec[i][d] = v[d];
+    }
+}
+
 // gather = false: without the gather lists of H and g (a model that only serves the reduced marker columns, build_com_model)
 static cpe_status build_model(const cpe_skeleton* s, const cpe_camera* cams, int C, const cpe_options* o, DevModel& m, bool gather = true) {
     memset(&m, 0, sizeof(m));
@@ -281,12 +291,8 @@ static cpe_status build_model(const cpe_skeleton* s, const cpe_camera* cams, int
         while (k >= 0) { chain[n++] = k; k = s->parent[k]; }
         if (n > CPE_MAX_CHAIN) return fail(CPE_BAD_ARG, "marker chain too long");
         m.chain_len[l] = n;
-        for (int i = 0; i < n; i++) {
-            const int link = chain[n - 1 - i];
-            m.chain_link[l][i] = link;
-            const double* v = i == n - 1 ? s->marker_off[l] : s->attach[chain[n - 2 - i]];
-            for (int d = 0; d < 3; d++) m.chain_vec[l][i][d] = v[d];
-        }
+        for (int i = 0; i < n; i++) m.chain_link[l][i] = chain[n - 1 - i];
+        chain_vectors(m.chain_link[l], n, s->attach, s->marker_off[l], m.chain_vec[l]);
         m.slot_off[l] = S;
         if (S + 3 + 3 * n > CPE_MAX_SLOTS) return fail(CPE_BAD_ARG, "too many Jacobian slots");
         for (int d = 0; d < 3; d++) { m.slot_marker[S] = l; m.slot_dof[S] = d; m.slot_cpos[S] = -1; m.slot_ang[S] = 0; S++; }
@@ -2681,6 +2687,133 @@ cpe_status cpe_posterior_samples_host(cpe_handle* h, int32_t B, int32_t N, const
     if (cpe_status s = posterior_samples_launch(h, B, N, FS, seq, dq, S, dd, oq, op); s != CPE_OK) return s;
     HIPCHK(st.fetch());
     return CPE_OK;
+}
+
+// ---- the reduced system of the segment-length calibration (include/cpe.h, cpe_scale_system; kernels in cpe_scale.hip.inc) -------------------
+// dynamic LDS of k_scale_cross for model m and G scales (the carve of the kernel, in its order)
+static size_t lds_scale(const DevModel& m, int G) {
+    const size_t d = m.ns + 6 * m.nl + 2 * m.nrev + 36 * m.n_trunk + 3 * m.sv_n + CPE_MAX_SCOL * m.n_srow + 3 * m.mc_total + 3 * m.L + CAMW * m.C +
+                     9 * m.L + 9 * m.nl + 2 * (size_t)(3 * m.L * G);
+    return sizeof(double) * d + sizeof(int) * (size_t)(m.L * CPE_NX + m.mc_total);
+}
+// No model build_model accepts needs more than the 64 KB a launch may ask for without an attribute: the carve at every table's limit (leg links
+// LM_MAX_REV, all links in the trunk, CPE_MAX_SDYN dynamic vectors, CPE_MAX_DEP hooke rows, CPE_MAX_MARKERS x CPE_MAX_MCOL marker columns,
+// CPE_MAX_CAMS cameras, CPE_MAX_SCALES scales) is 57 304 B
+static_assert(sizeof(double) * (CPE_MAX_NQ + LM_MAX_REV + 6 * CPE_MAX_LINKS + 2 * LM_MAX_REV + 36 * CPE_MAX_LINKS + 3 * CPE_MAX_SDYN + CPE_MAX_SCOL * CPE_MAX_DEP +
+                                3 * CPE_MAX_MARKERS * CPE_MAX_MCOL + 3 * CPE_MAX_MARKERS + CAMW * CPE_MAX_CAMS + 9 * CPE_MAX_MARKERS + 9 * CPE_MAX_LINKS +
+                                2 * 3 * CPE_MAX_MARKERS * CPE_MAX_SCALES) +
+                  sizeof(int) * (CPE_MAX_MARKERS * CPE_NX + CPE_MAX_MARKERS * CPE_MAX_MCOL) <= 65536, "k_scale_cross: dynamic LDS within the default limit");
+
+// What both forms refuse, before the device is touched and in this order -- what needs no handle first: G outside 1..CPE_MAX_SCALES, a negative
+// or non-finite ridge, negative sizes, model without n_frames or the reverse, a frame count outside 1..N, a null handle or array; then a
+// half-bandwidth above 4 and a model index out of range.  Fills F and, for the ragged form, the table.
+static cpe_status scale_check(const char* who, const cpe_handle* h, int32_t B, int32_t N, const int32_t* model, const int32_t* n_frames, bool arrays,
+                              double ridge, int32_t G, size_t* F, std::vector<int2>& seq) {
+    const std::string w = std::string(who) + ": ";
+    if (G < 1 || G > CPE_MAX_SCALES) return fail(CPE_BAD_ARG, w + "G = " + std::to_string(G) + " outside 1.." + std::to_string(CPE_MAX_SCALES));
+    if (cpe_status s = cov_check(who, -1, ridge); s != CPE_OK) return s;
+    if (cpe_status s = frames(B, N, F); s != CPE_OK) return fail(s, w + g_err);
+    if ((model == nullptr) != (n_frames == nullptr)) return fail(CPE_BAD_ARG, w + "model and n_frames are given together");
+    for (int b = 0; n_frames && b < B; b++)
+        if (n_frames[b] < 1 || n_frames[b] > N) return fail(CPE_BAD_ARG, w + "frame count of sequence " + std::to_string(b) + " outside 1..N");
+    if (!h || !arrays) return fail(CPE_BAD_ARG, w + "null argument (only model and n_frames may be null)");
+    if (cpe_status s = cov_check(who, h->pb, ridge); s != CPE_OK) return s;
+    if (model) { if (cpe_status s = ragged_table(h, B, N, model, n_frames, seq); s != CPE_OK) return fail(s, w + g_err.substr(g_err.find(": ") + 2)); }
+    return CPE_OK;
+}
+
+// the device entry after its checks: q .. cost are device pointers, d_attach / d_marker_off / status host
+static cpe_status scale_launch(cpe_handle* h, int32_t B, int32_t N, size_t F, const std::vector<int2>& seq, const double* q, const double* meas,
+                               const double* weight, double ridge, int32_t G, const double* d_attach, const double* d_marker_off, double* A,
+                               double* bvec, double* A_red, double* b_red, double* cost, cpe_status* status) {
+    const bool ragged = !seq.empty();
+    const int nm = n_models(h), L = h->hm.L, nl = h->hm.nl;
+    size_t lds = 0;
+    for (int k = 0; k < nm; k++) lds = std::max(lds, lds_scale(h->models.empty() ? h->hm : h->models[k], G));
+    cpe_status s = ensure_ws(h, B, N);
+    if (s != CPE_OK) return s;
+    RaggedArgs rgv;
+    if (ragged && (s = ragged_upload(h, seq, N, rgv)) != CPE_OK) return s;
+    const RaggedArgs* rg = ragged ? &rgv : nullptr;
+    if ((s = state_reset(h, B, N, q, rg)) != CPE_OK) return s;
+    // d chain_vec / d s_g of every model, by the loop that builds chain_vec
+    const size_t per = (size_t)L * CPE_MAX_CHAIN * 3;
+    std::vector<double> dcv((size_t)nm * G * per, 0.0);
+    for (int k = 0; k < nm; k++) {
+        const DevModel& m = h->models.empty() ? h->hm : h->models[k];
+        for (int g = 0; g < G; g++) {
+            const double(*att)[3] = reinterpret_cast<const double(*)[3]>(d_attach + ((size_t)k * G + g) * nl * 3);
+            const double* off = d_marker_off + ((size_t)k * G + g) * L * 3;
+            for (int l = 0; l < L; l++)
+                chain_vectors(m.chain_link[l], m.chain_len[l], att, off + 3 * l, reinterpret_cast<double(*)[3]>(&dcv[((size_t)k * G + g) * per + (size_t)l * CPE_MAX_CHAIN * 3]));
+        }
+    }
+    const int SC = scale_record(G);
+    Staging sc(h->stream);
+    const double* d_dcv = sc.in(dcv.data(), dcv.size());
+    double* rec = sc.alloc<double>(F * SC);
+    HIPCHK(sc.err);
+    const size_t w = sizeof(double);
+    // a sequence without a factor has all outputs zero
+    HIPCHK(hipMemsetAsync(A, 0, w * B * G * G, h->stream));
+    HIPCHK(hipMemsetAsync(A_red, 0, w * B * G * G, h->stream));
+    HIPCHK(hipMemsetAsync(bvec, 0, w * B * G, h->stream));
+    HIPCHK(hipMemsetAsync(b_red, 0, w * B * G, h->stream));
+    HIPCHK(hipMemsetAsync(cost, 0, w * B, h->stream));
+    // the first pass of cpe_covariance: the factor in Lbuf, the gradient in gtbuf
+    LmParams prm = lm_params(h, B, N);
+    prm.lambda0 = ridge;
+    lm_iterate(h, prm, N, F, lds_normal(h, rg), meas, weight, ShutterArgs{nullptr, nullptr, nullptr}, rg, 1, nullptr, nullptr, B, false);
+    with_ragged(rg, [&](auto r, RaggedArgs a) {
+        constexpr bool R = decltype(r)::value;
+        hipLaunchKernelGGL(k_scale_cross<R>, dim3((unsigned)F), dim3(WAVE), lds, h->stream, h->dm, h->st, N, F, h->qbuf, meas, weight, d_dcv, G, rec, a);
+        if (h->pb == 3) hipLaunchKernelGGL((k_band_forward<3, R>), dim3(B), dim3(WAVE), 0, h->stream, h->st, h->Lbuf, h->gtbuf, h->costbuf, rec, N, F, G, A, bvec, A_red, b_red, cost, a);
+        else hipLaunchKernelGGL((k_band_forward<4, R>), dim3(B), dim3(WAVE), 0, h->stream, h->st, h->Lbuf, h->gtbuf, h->costbuf, rec, N, F, G, A, bvec, A_red, b_red, cost, a);
+    });
+    HIPCHK(hipGetLastError());
+    std::vector<SeqState> hs((size_t)B);
+    HIPCHK(hipMemcpyAsync(hs.data(), h->st, sizeof(SeqState) * B, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));                // (the scratch arrays are freed on return; seq and dcv are pageable)
+    cpe_status worst = CPE_OK;
+    for (int b = 0; b < B; b++) {
+        status[b] = hs[b].status == 0 && hs[b].back_pending == 1 ? CPE_OK : CPE_NUMERICAL;
+        if (status[b] > worst) worst = status[b];
+    }
+    return worst;
+}
+
+cpe_status cpe_scale_system(cpe_handle* h, int32_t B, int32_t N, const int32_t* model, const int32_t* n_frames, const double* q, const double* meas,
+                            const double* weight, double ridge, int32_t G, const double* d_attach, const double* d_marker_off, double* A, double* b,
+                            double* A_red, double* b_red, double* cost, cpe_status* status) {
+    size_t F;
+    std::vector<int2> seq;
+    const bool arrays = q && meas && weight && d_attach && d_marker_off && A && b && A_red && b_red && cost && status;
+    if (cpe_status s = scale_check("cpe_scale_system", h, B, N, model, n_frames, arrays, ridge, G, &F, seq); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    HIPCHK(hipSetDevice(h->device));
+    return scale_launch(h, B, N, F, seq, q, meas, weight, ridge, G, d_attach, d_marker_off, A, b, A_red, b_red, cost, status);
+}
+
+cpe_status cpe_scale_system_host(cpe_handle* h, int32_t B, int32_t N, const int32_t* model, const int32_t* n_frames, const double* q,
+                                 const double* meas, const double* weight, double ridge, int32_t G, const double* d_attach,
+                                 const double* d_marker_off, double* A, double* b, double* A_red, double* b_red, double* cost, cpe_status* status) {
+    size_t F;
+    std::vector<int2> seq;
+    const bool arrays = q && meas && weight && d_attach && d_marker_off && A && b && A_red && b_red && cost && status;
+    if (cpe_status s = scale_check("cpe_scale_system_host", h, B, N, model, n_frames, arrays, ridge, G, &F, seq); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    const DevModel& m = h->hm;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t nmeas = F * cams_max(h) * m.L;
+    Staging st(h->stream);
+    const double *dq = st.in(q, F * m.nq), *dmeas = st.in(meas, nmeas * 2), *dweight = st.in(weight, nmeas);
+    double *oA = st.out(A, (size_t)B * G * G), *ob = st.out(b, (size_t)B * G), *oAr = st.out(A_red, (size_t)B * G * G), *obr = st.out(b_red, (size_t)B * G),
+           *oc = st.out(cost, (size_t)B);
+    HIPCHK(st.err);
+    const cpe_status s = scale_launch(h, B, N, F, seq, dq, dmeas, dweight, ridge, G, d_attach, d_marker_off, oA, ob, oAr, obr, oc, status);
+    if (s < 0) return s;
+    HIPCHK(st.fetch());
+    return s;
 }
 
 // ---- posterior covariance of the rates (include/cpe.h, cpe_rate_covariance; kernels in cpe_rate_cov.hip.inc) --------------------------------

@@ -332,6 +332,15 @@ class CheetahEstimator:
     # cpe_posterior_samples): du [K, N, 28], q [K, N, nq], x [K, N, 28], positions [K, N, L, 3], com_pos [K, N, 3], seed, ridge; None where not
     # asked for or where the covariance has no factor
     samples: Optional[dict] = None
+    # calibrate_lengths / estimate_kinematics(estimate_lengths=True): the scale of every segment group of length_groups (skeleton.LENGTH_GROUPS'
+    # form), the covariance of the scales (the inverse of the reduced system + prior), and the model name the skeleton was built from; None: the
+    # parameter file's lengths.  The later stages build their inertia and mass tables with these scales.
+    length_scale: Optional[np.ndarray] = None
+    length_scale_cov: Optional[np.ndarray] = None
+    length_groups: Optional[tuple] = None
+    # how that fit ended: dict(converged, rounds, prior_sigma, ridge, objective).  converged False: the loop stopped at max_rounds or found no
+    # descent step; the scales are then the last iterate, not a minimiser (a warning is issued, and skeleton_scale.json says so)
+    length_calibration: Optional[dict] = None
 
     def get_objective_cost(self) -> float:
         return float(self.result["stats"][0].cost) if self.result else float("nan")
@@ -368,7 +377,7 @@ class CheetahEstimator:
                 lo, hi = max(a - start_frame, 0), min(b - start_frame, N)
                 if hi > lo:
                     flags[lo:hi, i] = 1
-        gopt = skeleton.grf_options(self.name)                                # load_params falls back to the generic animal
+        gopt = skeleton.grf_options(self.name, **_length_kw(self))            # load_params falls back to the generic animal
         h = _lib.Handle(sk, self.cams, device=self.device)
         try:
             gz, gxy, res = h.grf_fit_host(gopt, fte["q"][None, :N], fte["dq"][None, :N], fte["ddq"][None, :N], flags[None])
@@ -394,7 +403,7 @@ class CheetahEstimator:
         sk, res, kin = self.skeleton, self.result, self.kinetic
         q, dq, ddq = res["q"][0], res["dq"][0], res["ddq"][0]
         N = q.shape[0]
-        p = skeleton.load_params(self.name)
+        p = skeleton.load_params(self.name, **_length_kw(self))
         groups = dict(skeleton.motor_groups())
         links = []
         for i, name in enumerate(skeleton.LINKS):
@@ -972,6 +981,8 @@ def _kin_finish(est: CheetahEstimator, h, res: dict, seconds: float, solver_outp
         fname = fname if scene.cam_idx is None or monocular_constraints else "fte_kinematic_orig"
         fname = fname if scene.cam_idx is None else f"{fname}_{scene.cam_idx}"    # acinoset_opt.py:626-628
         out_dir = est.save(fname, out_dir_prefix=out_dir_prefix)
+        if est.length_scale is not None:
+            write_skeleton_scale(est, out_dir)
         if uncertainty is not None:
             est.uncertainty = uncertainty[0]
             if est.uncertainty is None:
@@ -986,13 +997,184 @@ def _kin_finish(est: CheetahEstimator, h, res: dict, seconds: float, solver_outp
     return ok
 
 
+def _length_kw(est) -> dict:
+    """the length_scale / groups keywords of skeleton.load_params, grf_options, eom_options, dyn_options for an estimator: empty (today's tables)
+    unless its lengths were calibrated"""
+    ls = getattr(est, "length_scale", None)
+    return {} if ls is None else dict(length_scale=ls, groups=est.length_groups)
+
+
+LENGTH_STEP_CAP = 0.05          # largest change of a scale in one round
+LENGTH_HALVINGS = 8             # how often a step is halved while the total objective rises
+
+
+def calibrate_loop(solve, system, n_groups: int, prior_sigma: Optional[float] = 0.1, s0=None, tol: float = 1e-6, max_rounds: int = 30,
+                   log=None) -> dict:
+    """The length calibration over two callables ("What is calibrated"), the same loop for the GPU and for a CPU reference:
+        solve(s, state)  -> (J, state')   the pose solves at scales s, warm-started from `state` (None: cold); J = the objective they reached,
+                                          summed over the sequences (solver cost / cost_scale)
+        system(s, state) -> (A_red, b_red) summed over the sequences: the Gauss-Newton system of the scales with the poses eliminated, at state
+    Minimises T(s) = J(s, q*(s)) + |s - 1|^2 / (2 sigma^2) (prior_sigma None: no prior) by reduced Gauss-Newton steps
+    ds = -(A_red + P)^-1 (b_red + P (s - 1)), P = I / sigma^2, each capped at LENGTH_STEP_CAP per scale and halved while T rises; stops when
+    max |ds| < tol.  Returns dict(s, cov = (A_red + P)^-1 at the last system, objective = T, rounds, converged, state, history = [(T, max |ds|)])."""
+    G = int(n_groups)
+    s = np.ones(G) if s0 is None else np.array(s0, dtype=np.float64)
+    if s.shape != (G,):
+        raise ValueError(f"calibrate_loop: one initial scale per group ({G})")
+    P = np.zeros((G, G)) if prior_sigma is None else np.eye(G) / float(prior_sigma) ** 2
+    total = lambda J, sv: float(J) + 0.5 * float((sv - 1.0) @ P @ (sv - 1.0))
+    J, state = solve(s, None)
+    T = total(J, s)
+    history, converged, rounds, cov = [], False, 0, None
+    for rounds in range(1, max_rounds + 1):
+        A_red, b_red = system(s, state)
+        Hs = np.asarray(A_red, dtype=np.float64) + P
+        cov = np.linalg.inv(Hs)
+        ds = -np.linalg.solve(Hs, np.asarray(b_red, dtype=np.float64) + P @ (s - 1.0))
+        big = np.abs(ds).max()
+        if big > LENGTH_STEP_CAP:
+            ds *= LENGTH_STEP_CAP / big
+        history.append((T, float(np.abs(ds).max())))
+        if log:
+            log(f"length calibration round {rounds}: objective {T:.9g}, max |ds| {np.abs(ds).max():.3e}")
+        if np.abs(ds).max() < tol:
+            converged = True
+            break
+        for _ in range(LENGTH_HALVINGS + 1):
+            J_try, state_try = solve(s + ds, state)
+            T_try = total(J_try, s + ds)
+            if T_try <= T:
+                break
+            ds = 0.5 * ds
+        else:                                                # no step along ds lowers the objective: s is as good as this model gets
+            converged = np.abs(ds).max() < tol
+            break
+        s, state, T = s + ds, state_try, T_try
+    return dict(s=s, cov=cov, objective=T, rounds=rounds, converged=converged, state=state, history=history)
+
+
+def calibrate_lengths(estimators: Sequence[CheetahEstimator], groups=skeleton.LENGTH_GROUPS, prior_sigma: Optional[float] = 0.1,
+                      length_scale_init=None, tol: float = 1e-6, max_rounds: int = 30, monocular_constraints: bool = False,
+                      disable_pose_prior: bool = False, disable_motion_prior: bool = False, options: Optional[abi.Options] = None,
+                      ridge: float = 0.0, q_init: Optional[Sequence[np.ndarray]] = None, solver_output: bool = False,
+                      pose_model_num_components: int = 5, motion_model_window_size: int = 4, motion_model_sparse_solution: bool = True) -> dict:
+    """Fit the segment lengths of ONE animal to the data of its sequences: one scale per group of `groups` (skeleton.LENGTH_GROUPS' form), shared by
+    all estimators (they must name the same animal and dataset kind).  calibrate_loop with, per round, one ragged batch pose solve on the
+    skeleton build_skeleton(length_scale=s) -- warm-started from the previous round's poses -- and one cpe_scale_system call (damping `ridge`);
+    A_red and b_red are summed in list order.  prior_sigma: standard deviation of the Gaussian prior s ~ N(1, sigma^2) on every scale, a
+    modelling default for the individual variation of limb lengths (None: no prior -- refused for one camera, where scale and depth cannot be
+    told apart, unless a sequence of the animal has more cameras).  q_init: the first round's initial poses per estimator (None: the
+    reference's initial guess).  pose_model_num_components, motion_model_window_size, motion_model_sparse_solution: the priors of a monocular
+    run, as estimate_kinematics takes them.
+    Sets est.length_scale, est.length_scale_cov, est.length_groups, est.length_calibration (converged, rounds, prior_sigma, ridge, objective) and
+    replaces est.skeleton on every estimator; returns calibrate_loop's dict with `q` = the last poses per estimator.  A loop that did not
+    converge (max_rounds reached, or no descent step) leaves its last iterate all the same, says so in length_calibration and warns."""
+    ests = list(estimators)
+    if not ests:
+        raise ValueError("calibrate_lengths: no estimator")
+    _check_lengths(ests, prior_sigma)
+    e0 = ests[0]
+    if any(e.name != e0.name or e.params.kinetic_dataset != e0.params.kinetic_dataset or e.device != e0.device for e in ests):
+        raise ValueError("calibrate_lengths: the estimators of one call share the animal, the dataset kind and the device")
+    if prior_sigma is not None and not prior_sigma > 0:
+        raise ValueError("calibrate_lengths: prior_sigma must be positive")
+    groups = tuple((str(n), tuple(l)) for n, l in groups)
+    G = len(groups)
+    if not 1 <= G <= abi.MAX_SCALES:
+        raise ValueError(f"calibrate_lengths: 1..{abi.MAX_SCALES} groups")
+    model_name = f"{e0.name}-02" if e0.params.kinetic_dataset else e0.name
+    n_markers = e0.skeleton.n_markers
+    d_attach, d_marker_off = skeleton.length_derivatives(model_name, n_markers, groups)
+    prep = [_kin_prepare(e, monocular_constraints, disable_pose_prior, disable_motion_prior, pose_model_num_components, motion_model_window_size,
+                         motion_model_sparse_solution, None if q_init is None else q_init[i],
+                         None if options is None else _copy_options(options)) for i, e in enumerate(ests)]
+    pri = prep[0][2]
+    if len({ragged_group_key(e.skeleton, p[1], p[2], e.device) for e, p in zip(ests, prep)}) != 1:
+        raise ValueError("calibrate_lengths: the sequences of one call go through one ragged batch: same priors and batch-level solver options")
+    cost_scale = prep[0][1].cost_scale
+    # one model per distinct (rig, options); the skeleton of every model is this round's
+    rigs: Dict[bytes, int] = {}
+    of = [rigs.setdefault(b"".join(_struct_bytes(e.cams[c]) for c in range(len(e.cams))) + _struct_bytes(p[1]), len(rigs)) for e, p in zip(ests, prep)]
+    reps = [of.index(k) for k in range(len(rigs))]
+    meas, weight = [e.meas for e in ests], [e.weight for e in ests]
+    tabs = (np.broadcast_to(d_attach, (len(reps),) + d_attach.shape), np.broadcast_to(d_marker_off, (len(reps),) + d_marker_off.shape))
+    build = lambda s: skeleton.build_skeleton(model_name, n_markers, e0.params.kinetic_dataset, length_scale=s, groups=groups)
+
+    def handle(s):
+        sk = build(s)
+        return _lib.Handle.multi([sk] * len(reps), [ests[i].cams for i in reps], [prep[i][1] for i in reps], pri, device=e0.device)
+
+    def solve(s, state):
+        h = handle(s)
+        try:
+            res = h.solve_ragged_host([p[0] for p in prep] if state is None else state, meas, weight, of)
+        finally:
+            h.close()
+        if any(st.status == abi.NUMERICAL for st in res["stats"]):
+            raise _lib.CpeError("calibrate_lengths: a pose solve failed numerically")
+        return sum(st.cost for st in res["stats"]) / cost_scale, res["q"]
+
+    def system(s, state):
+        h = handle(s)
+        try:
+            out = h.scale_system_host(state, meas, weight, tabs[0], tabs[1], ridge, model_list=of)
+        finally:
+            h.close()
+        if out["status"] != abi.OK:
+            raise _lib.CpeError(f"calibrate_lengths: the Gauss-Newton matrix of the poses has no Cholesky factor at ridge {ridge:g} "
+                                "(the data leave a coordinate undetermined; a positive ridge regularises it)")
+        return out["A_red"].sum(axis=0), out["b_red"].sum(axis=0)
+
+    r = calibrate_loop(solve, system, G, prior_sigma, length_scale_init, tol, max_rounds, log=print if solver_output else None)
+    sk = build(r["s"])
+    if not r["converged"]:
+        import warnings
+        warnings.warn(f"calibrate_lengths ({e0.name}): not converged after {r['rounds']} rounds (last step {r['history'][-1][1]:.2e}, tolerance "
+                      f"{tol:g}); the scales are the last iterate, up to {np.abs(r['s'] - 1.0).max():.3f} from 1", RuntimeWarning, stacklevel=2)
+    how = dict(converged=bool(r["converged"]), rounds=int(r["rounds"]), prior_sigma=None if prior_sigma is None else float(prior_sigma),
+               ridge=float(ridge), objective=float(r["objective"]))
+    for e in ests:
+        e.length_scale, e.length_scale_cov, e.length_groups, e.length_calibration = r["s"].copy(), r["cov"].copy(), groups, dict(how)
+        e.skeleton = abi.Skeleton.from_buffer_copy(bytes(sk))
+    r["q"] = r.pop("state")
+    return r
+
+
+def write_skeleton_scale(est: CheetahEstimator, out_dir: str) -> str:
+    """skeleton_scale.json beside fte.pickle: the groups, their scales, the covariance of the scales and how the fit ended (converged, rounds,
+    prior_sigma, ridge, objective)"""
+    path = os.path.join(out_dir, "skeleton_scale.json")
+    with open(path, "w", encoding="utf-8") as f:
+        json.dump(dict(animal=est.name, groups=[[n, list(l)] for n, l in est.length_groups], length_scale=[float(v) for v in est.length_scale],
+                       length_scale_cov=[[float(v) for v in row] for row in est.length_scale_cov], **(est.length_calibration or {})), f, indent=1)
+    return path
+
+
+def _check_lengths(ests, prior_sigma) -> None:
+    """what a length calibration over the estimators of ONE animal refuses (calibrate_lengths, and the fronts before anything else is looked at):
+    shutter-delay estimation, and no prior when every sequence has one camera -- scale and depth cannot be separated there"""
+    if any(e.params.enable_shutter_delay_estimation and e.scene.cam_idx is None for e in ests):
+        raise NotImplementedError("length calibration together with shutter-delay estimation")
+    if prior_sigma is None and all(e.scene.cam_idx is not None for e in ests):
+        raise ValueError("length calibration with one camera needs a prior (length_prior_sigma): scale and depth cannot be separated")
+
+
+def _animals(ests) -> Dict[tuple, List[int]]:
+    """the estimators of every animal (name, dataset kind), which share their scales: {key: indices}"""
+    out: Dict[tuple, List[int]] = {}
+    for i, est in enumerate(ests):
+        out.setdefault((est.name, est.params.kinetic_dataset), []).append(i)
+    return out
+
+
 def estimate_kinematics(estimator: CheetahEstimator, solver_output: bool = True, monocular_constraints: bool = False,
                         disable_pose_prior: bool = False, disable_motion_prior: bool = False,
                         pose_model_num_components: int = 5, motion_model_window_size: int = 4,
                         motion_model_sparse_solution: bool = True, out_dir_prefix: Optional[str] = None,
                         q_init: Optional[np.ndarray] = None, options: Optional[abi.Options] = None, uncertainty: bool = False,
                         uncertainty_ridge: float = 0.0, uncertainty_rates: bool = False, uncertainty_spans=None, uncertainty_samples: int = 0,
-                        uncertainty_seed: int = 0) -> bool:
+                        uncertainty_seed: int = 0, estimate_lengths: bool = False, length_prior_sigma: Optional[float] = 0.1,
+                        length_scale_init=None, length_ridge: float = 0.0) -> bool:
     """Same signature as acinoset_opt.estimate_kinematics (acinoset_opt.py:539-547) plus optional
     keyword arguments.  Returns True when the solve converged (IPOPT `ok`+`optimal` in the reference).
     uncertainty=True: after a converged solve the posterior covariance of the estimate (cpe_covariance at the stored q, damping
@@ -1008,11 +1190,28 @@ def estimate_kinematics(estimator: CheetahEstimator, solver_output: bool = True,
     error bar of any quantity computed from a trajectory: du = L^-T z with z = sample_normals(uncertainty_seed, K, N) and the covariance call's own
     factor L (cpe_band_sample), then the poses (cpe_posterior_samples).  They go to est.samples and to samples.npz beside uncertainty.npz
     (SAMPLE_FIELDS: seed, ridge, du [K, N, 28], q [K, N, nq], x = relative_angles(q), positions [K, N, L, 3], com_pos [K, N, 3]); est.uncertainty
-    and uncertainty.npz do not change.  Without a factor: est.samples = None and no file."""
+    and uncertainty.npz do not change.  Without a factor: est.samples = None and no file.
+    estimate_lengths=True: the segment lengths are fitted first (calibrate_lengths: one scale per group of skeleton.LENGTH_GROUPS, prior
+    s ~ N(1, length_prior_sigma^2), start length_scale_init or 1); the estimate is then made on the fitted skeleton, est.length_scale and
+    est.length_scale_cov hold the scales and their covariance, est.length_calibration how the fit ended (converged, rounds, prior_sigma, ridge,
+    objective), and skeleton_scale.json beside fte.pickle holds all of it.  A fit that did not converge warns and is marked there; its scales
+    are still used.  length_ridge: the damping of the poses' matrix in cpe_scale_system (a monocular run may need 1e-6 for a factor).  The
+    calibration's pose solves use this call's priors and options.  One camera needs a prior (length_prior_sigma=None: ValueError); together
+    with shutter-delay estimation: NotImplementedError.  uncertainty=True stays the covariance of the poses GIVEN the lengths."""
     _check_samples(uncertainty, uncertainty_samples)
     _check_rates(uncertainty, uncertainty_rates)
     _check_spans(uncertainty, uncertainty_spans)
-    est, params, scene, sk = estimator, estimator.params, estimator.scene, estimator.skeleton
+    if estimate_lengths:
+        _check_lengths([estimator], length_prior_sigma)
+    est, params, scene = estimator, estimator.params, estimator.scene
+    if estimate_lengths:
+        cal = calibrate_lengths([est], prior_sigma=length_prior_sigma, length_scale_init=length_scale_init, monocular_constraints=monocular_constraints,
+                                disable_pose_prior=disable_pose_prior, disable_motion_prior=disable_motion_prior, options=options, ridge=length_ridge,
+                                q_init=None if q_init is None else [q_init], solver_output=solver_output,
+                                pose_model_num_components=pose_model_num_components, motion_model_window_size=motion_model_window_size,
+                                motion_model_sparse_solution=motion_model_sparse_solution)
+        q_init = cal["q"][0]
+    sk = est.skeleton
     spans = resolve_spans(uncertainty_spans, params.end_frame - params.start_frame)
     q_init, opts, pri = _kin_prepare(est, monocular_constraints, disable_pose_prior, disable_motion_prior, pose_model_num_components,
                                      motion_model_window_size, motion_model_sparse_solution, q_init, options)
@@ -1057,7 +1256,8 @@ def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_out
                               disable_pose_prior: bool = False, disable_motion_prior: bool = False, out_dir_prefix: Optional[str] = None,
                               options: Optional[abi.Options] = None, ragged: bool = False, uncertainty: bool = False,
                               uncertainty_ridge: float = 0.0, uncertainty_rates: bool = False, uncertainty_spans=None, uncertainty_samples: int = 0,
-                              uncertainty_seed: int = 0) -> List[bool]:
+                              uncertainty_seed: int = 0, estimate_lengths: bool = False, length_prior_sigma: Optional[float] = 0.1,
+                              length_scale_init=None, length_ridge: float = 0.0) -> List[bool]:
     """estimate_kinematics for MANY sequences at once: the loop of run_dataset.py:1145-1196 (`for seq in dataset: init_trajectory; estimate_kinematics`)
     as batched launches.  Sequences that share a skeleton, a camera rig, a length and a frame rate go through ONE solver handle and ONE cpe_solve
     call (B = the group's size: the GPU solves thousands of sequences per second batched, one at a time it is latency-bound at 7 - 30 ms each);
@@ -1072,11 +1272,23 @@ def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_out
     estimate_kinematics, one cpe_rate_covariance (ragged: cpe_rate_covariance_ragged) call after each covariance call, with the same bit-equality.
     uncertainty_spans: as in estimate_kinematics, resolved for every sequence; one cpe_covariance_columns call per group, same bit-equality.
     uncertainty_samples, uncertainty_seed: as in estimate_kinematics, every sequence with the z of its own call (sample_normals); one cpe_band_sample
-    and one cpe_posterior_samples call per group, same bit-equality of est.samples and samples.npz."""
+    and one cpe_posterior_samples call per group, same bit-equality of est.samples and samples.npz.
+    estimate_lengths, length_prior_sigma, length_scale_init, length_ridge: as in estimate_kinematics; the estimators of one animal (name and dataset kind) share
+    their scales: one calibrate_lengths call per animal over all its sequences, before the solves."""
     _check_samples(uncertainty, uncertainty_samples)
     _check_rates(uncertainty, uncertainty_rates)
     _check_spans(uncertainty, uncertainty_spans)
     ests = list(estimators)
+    cal_q: Dict[int, np.ndarray] = {}
+    if estimate_lengths:
+        animals = _animals(ests)
+        for idx in animals.values():                                                 # (every refusal before the first solve)
+            _check_lengths([ests[i] for i in idx], length_prior_sigma)
+        for idx in animals.values():
+            cal = calibrate_lengths([ests[i] for i in idx], prior_sigma=length_prior_sigma, length_scale_init=length_scale_init,
+                                    monocular_constraints=monocular_constraints, disable_pose_prior=disable_pose_prior,
+                                    disable_motion_prior=disable_motion_prior, options=options, ridge=length_ridge, solver_output=solver_output)
+            cal_q.update({i: cal["q"][b] for b, i in enumerate(idx)})
     spans = [resolve_spans(uncertainty_spans, e.params.end_frame - e.params.start_frame) for e in ests]      # (a bad pair: before any solve)
     group_spans = lambda idx: None if uncertainty_spans is None else [spans[i] for i in idx]
     out: List[Optional[bool]] = [None] * len(ests)
@@ -1088,7 +1300,7 @@ def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_out
                                          uncertainty=uncertainty, uncertainty_ridge=uncertainty_ridge, uncertainty_rates=uncertainty_rates,
                                          uncertainty_spans=uncertainty_spans, uncertainty_samples=uncertainty_samples, uncertainty_seed=uncertainty_seed)
             continue
-        q_init, opts, pri = _kin_prepare(est, monocular_constraints, disable_pose_prior, disable_motion_prior, 5, 4, True, None,
+        q_init, opts, pri = _kin_prepare(est, monocular_constraints, disable_pose_prior, disable_motion_prior, 5, 4, True, cal_q.get(i),
                                          None if options is None else _copy_options(options))
         prepared[i] = (q_init, opts, pri)
         if uncertainty:
@@ -1530,7 +1742,7 @@ def _kinetic_prepare(est: CheetahEstimator, auto: bool, use_2d_reprojections: bo
     opts.h = 1.0 / scene.fps
     if options is None:
         opts.tol_cost, opts.max_iter = 1e-6, 1500          # the physics term is stiff: see DESIGN.md 2b (the reference stops IPOPT at Tol = 1e-3; a monocular start with a missed contact window has taken 1 200 iterations)
-    ko = kinetic_options if kinetic_options is not None else abi.default_kinetic_options(skeleton.dyn_options(est.name), scene.fps, params.kinetic_dataset)
+    ko = kinetic_options if kinetic_options is not None else abi.default_kinetic_options(skeleton.dyn_options(est.name, **_length_kw(est)), scene.fps, params.kinetic_dataset)
     if not no_slip and not joint_estimation:
         ko.slip_max = 0.0                                                            # `no_slip` guards the rules of the prescribed-force branch only (acinoset_opt.py:855-866);
         ko.zvel_max = 0.0                                                            # the joint-estimation branch always has them (:803-810)
@@ -1857,7 +2069,7 @@ def estimate_grf(estimator: CheetahEstimator, solver_output: bool = True, out_di
     opts.h = 1.0 / scene.fps
     if options is None:
         opts.tol_cost, opts.max_iter = 1e-6, 1500
-    ko = kinetic_options if kinetic_options is not None else abi.default_kinetic_options(skeleton.dyn_options(est.name), scene.fps, True)
+    ko = kinetic_options if kinetic_options is not None else abi.default_kinetic_options(skeleton.dyn_options(est.name, **_length_kw(est)), scene.fps, True)
     if kinetic_options is None:
         ko.foot_height_tol = 0.03                                                    # foot_height in [-0.03, 0.03] during a contact (:1010-1012)
         ko.slip_max = 0.0                                                            # this NLP has no no-slip rule (estimate_kinetics adds it to ITS model)

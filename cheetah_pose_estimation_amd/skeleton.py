@@ -47,18 +47,6 @@ def dof(link: str, angle: int) -> int:
     return 3 + 3 * LINKS.index(link) + angle
 
 
-def load_params(animal: str) -> dict:
-    """Link mass/length/radius exported from cheetah_params.py (tools/export_skeleton_params.py).
-    Animal naming follows acinoset_opt.py:455-457."""
-    with open(_PARAMS_JSON) as f:
-        allp = json.load(f)
-    if animal.endswith("-02"):
-        animal = animal[:-3]
-    if animal not in allp:
-        animal = "acinoset"
-    return allp[animal]
-
-
 def _link_param(p: dict, name: str) -> dict:
     if name == "base":
         return p["body_B"]
@@ -81,13 +69,60 @@ def measurement_sigma(n_markers: int = 24, kinetic_dataset: bool = False) -> np.
     return R[:n_markers]
 
 
-def build_skeleton(animal: str = "phantom", n_markers: int = 24, kinetic_dataset: bool = False) -> abi.Skeleton:
-    p = load_params(animal)
-    L = {n: _link_param(p, n)["length"] for n in LINKS}
-    r = {n: _link_param(p, n)["radius"] for n in LINKS}
-    m = {n: _link_param(p, n)["mass"] for n in LINKS}
-    sk = abi.Skeleton()
-    sk.n_links = len(LINKS)
+# segment groups of the length calibration (estimator.calibrate_lengths): one scale s_g per group multiplies `length` of the group's links;
+# radii, body-fixed marker offsets and masses stay as they are.  Left and right limbs share a scale.
+LENGTH_GROUPS = (("base", ("base",)), ("bodyF", ("bodyF",)), ("neck", ("neck",)), ("tail0", ("tail0",)), ("tail1", ("tail1",)),
+                 ("front_thigh", ("UFL", "UFR")), ("front_calf", ("LFL", "LFR")), ("front_hock", ("HFL", "HFR")),
+                 ("back_thigh", ("UBL", "UBR")), ("back_calf", ("LBL", "LBR")), ("back_hock", ("HBL", "HBR")))
+
+
+def link_scales(length_scale, groups=LENGTH_GROUPS) -> dict:
+    """{link: scale of its length}: length_scale[g] for the links of group g, 1.0 for a link in no group (a group may be empty)"""
+    s = np.asarray(length_scale, dtype=np.float64)
+    if s.shape != (len(groups),) or not np.all(np.isfinite(s)) or np.any(s <= 0):
+        raise ValueError(f"length_scale: one positive scale per group ({len(groups)} groups)")
+    out = {n: 1.0 for n in LINKS}
+    named = [n for _, links in groups for n in links]
+    if len(set(named)) != len(named) or not set(named) <= set(LINKS):
+        raise ValueError("length groups: every link at most once, by its name in LINKS")
+    for sg, (_, links) in zip(s, groups):
+        for n in links:
+            out[n] = float(sg)
+    return out
+
+
+def _scaled_params(p: dict, length_scale, groups) -> dict:
+    """copy of the parameter tree `p` with `length` of every link multiplied by its scale.  The tree has one entry for a left and right limb
+    segment: groups that give the two sides different scales cannot be written into it (build_skeleton takes them)."""
+    scale = link_scales(length_scale, groups)
+    p = json.loads(json.dumps(p))
+    done = {}
+    for n in LINKS:
+        lp = _link_param(p, n)
+        if id(lp) in done:
+            if done[id(lp)] != scale[n]:
+                raise ValueError("length groups: the left and right segment of a limb share one parameter entry and need one scale")
+            continue
+        done[id(lp)] = scale[n]
+        if scale[n] != 1.0:
+            lp["length"] = lp["length"] * scale[n]
+    return p
+
+
+def load_params(animal: str, length_scale=None, groups=LENGTH_GROUPS) -> dict:
+    """Link mass/length/radius exported from cheetah_params.py (tools/export_skeleton_params.py).
+    Animal naming follows acinoset_opt.py:455-457.  length_scale [len(groups)]: the lengths times the scale of their group."""
+    with open(_PARAMS_JSON) as f:
+        allp = json.load(f)
+    if animal.endswith("-02"):
+        animal = animal[:-3]
+    if animal not in allp:
+        animal = "acinoset"
+    return allp[animal] if length_scale is None else _scaled_params(allp[animal], length_scale, groups)
+
+
+def _geometry(L: dict, r: dict, c: float):
+    """(attach, com, markers = {name: (link, offset)}) of link lengths L, radii r and c times the body-fixed marker offsets: linear in (L, r, c)"""
     # link-local end points (SURVEY A.2)
     bottom, top, com = {}, {}, {}
     for n in LINKS:
@@ -108,15 +143,9 @@ def build_skeleton(animal: str = "phantom", n_markers: int = 24, kinetic_dataset
         for fb in "FB":
             attach["L" + fb + side] = bottom["U" + fb + side]
             attach["H" + fb + side] = bottom["L" + fb + side]
-    for i, n in enumerate(LINKS):
-        sk.parent[i] = -1 if PARENT[n] is None else LINKS.index(PARENT[n])
-        for d in range(3):
-            sk.attach[i][d] = attach[n][d]
-            sk.com[i][d] = com[n][d]
-        sk.mass[i] = m[n]
 
     def add(a, b):
-        return tuple(x + y for x, y in zip(a, b))
+        return tuple(x + c * y for x, y in zip(a, b))
 
     # marker = (link, body-frame offset)   acinoset_misc.py:1586-1659
     mk = {
@@ -138,6 +167,45 @@ def build_skeleton(animal: str = "phantom", n_markers: int = 24, kinetic_dataset
             mk[f"{side}_{fb}_knee"] = ("U" + FB + s, bottom["U" + FB + s])
             mk[f"{side}_{fb}_ankle"] = ("L" + FB + s, bottom["L" + FB + s])   # hock.top
             mk[f"{side}_{fb}_paw"] = ("H" + FB + s, bottom["H" + FB + s])
+    return attach, com, mk
+
+
+def length_derivatives(animal: str = "phantom", n_markers: int = 24, groups=LENGTH_GROUPS):
+    """(d_attach [G, n_links, 3], d_marker_off [G, n_markers, 3]): the derivatives of build_skeleton's `attach` and `marker_off` by the scale of
+    every group.  Both are linear in the lengths, so these are constants and build(s) = build(1) + sum_g (s_g - 1) d_g entry for entry."""
+    p = load_params(animal)
+    zero = {n: 0.0 for n in LINKS}
+    d_attach = np.zeros((len(groups), len(LINKS), 3))
+    d_marker = np.zeros((len(groups), n_markers, 3))
+    for g, (_, links) in enumerate(groups):
+        Lg = {n: (_link_param(p, n)["length"] if n in links else 0.0) for n in LINKS}
+        attach, _, mk = _geometry(Lg, zero, 0.0)
+        for i, n in enumerate(LINKS):
+            d_attach[g, i] = attach[n]
+        for l, n in enumerate(MARKERS[:n_markers]):          # (a benchmark-only extra marker sits at the base COM: no length moves it)
+            d_marker[g, l] = mk[n][1]
+    return d_attach, d_marker
+
+
+def build_skeleton(animal: str = "phantom", n_markers: int = 24, kinetic_dataset: bool = False, length_scale=None,
+                   groups=LENGTH_GROUPS) -> abi.Skeleton:
+    """length_scale [len(groups)] (None: the parameter file's lengths as they are): the scale of every segment group"""
+    p = load_params(animal)
+    L = {n: _link_param(p, n)["length"] for n in LINKS}
+    if length_scale is not None:
+        L = {n: L[n] * sc for n, sc in link_scales(length_scale, groups).items()}
+    r = {n: _link_param(p, n)["radius"] for n in LINKS}
+    m = {n: _link_param(p, n)["mass"] for n in LINKS}
+    sk = abi.Skeleton()
+    sk.n_links = len(LINKS)
+    attach, com, mk = _geometry(L, r, 1.0)
+    for i, n in enumerate(LINKS):
+        sk.parent[i] = -1 if PARENT[n] is None else LINKS.index(PARENT[n])
+        for d in range(3):
+            sk.attach[i][d] = attach[n][d]
+            sk.com[i][d] = com[n][d]
+        sk.mass[i] = m[n]
+
     names = list(MARKERS)
     if n_markers > 24:
         for e in range(n_markers - 24):
@@ -237,10 +305,10 @@ FEET = ("HFL", "HFR", "HBL", "HBR")                   # pe.foot.feet(robot): add
 FOOT_MARKERS = ("l_front_paw", "r_front_paw", "l_back_paw", "r_back_paw")
 
 
-def grf_options(animal: str = "phantom", iterations: int = 2000) -> abi.GrfOptions:
+def grf_options(animal: str = "phantom", iterations: int = 2000, length_scale=None, groups=LENGTH_GROUPS) -> abi.GrfOptions:
     """Options of the per-frame GRF fit (acinoset_opt.py:176-270): feet = hock bottoms = the paw markers, root inertia =
     solid cylinder along the body axis x (I_axis = m r^2 / 2, I_perp = m L^2 / 12 + m r^2 / 4)."""
-    p = load_params(animal)["body_B"]
+    p = load_params(animal, length_scale, groups)["body_B"]
     m, L, r = p["mass"], p["length"], p["radius"]
     o = abi.GrfOptions()
     o.root_inertia[0] = 0.5 * m * r * r
@@ -253,11 +321,11 @@ def grf_options(animal: str = "phantom", iterations: int = 2000) -> abi.GrfOptio
     return o
 
 
-def eom_options(animal: str = "phantom") -> abi.EomOptions:
+def eom_options(animal: str = "phantom", length_scale=None, groups=LENGTH_GROUPS) -> abi.EomOptions:
     """gravity and the principal moments of every link: solid cylinders (I_axis = m r^2 / 2,
     I_perp = m L^2 / 12 + m r^2 / 4) along the link's aligned axis -- x for the trunk and tail links, z for the leg links
     (cheetah.py:19-200)."""
-    p = load_params(animal)
+    p = load_params(animal, length_scale, groups)
     o = abi.EomOptions()
     o.gravity = 9.81
     for i, name in enumerate(LINKS):
@@ -278,9 +346,9 @@ MOTORS = ([("bodyF", "base", a) for a in "xyz"] + [("neck", "bodyF", a) for a in
            for m in ((body, "U" + leg, "y"), ("U" + leg, "L" + leg, "y"), ("L" + leg, "H" + leg, "y"))])
 
 
-def dyn_options(animal: str = "phantom") -> abi.DynOptions:
+def dyn_options(animal: str = "phantom", length_scale=None, groups=LENGTH_GROUPS) -> abi.DynOptions:
     o = abi.DynOptions()
-    o.eom = eom_options(animal)
+    o.eom = eom_options(animal, length_scale, groups)
     o.n_feet = 4
     for i, name in enumerate(FOOT_MARKERS):
         o.foot_marker[i] = MARKERS.index(name)

@@ -767,6 +767,33 @@ cpe_status cpe_posterior_samples(cpe_handle* h, int32_t B, int32_t N, const int3
 cpe_status cpe_posterior_samples_host(cpe_handle* h, int32_t B, int32_t N, const int32_t* model, const int32_t* n_frames, const double* q, int32_t S,
                                       const double* du, double* q_s, double* positions_s);
 
+/* ---- segment lengths as unknowns of the kinematic estimate ("What is calibrated").  One scale s_g per segment group, G groups,
+ * multiplies the lengths of the group's links; marker positions are linear in the scales.  With J(s, u) the objective of cpe_solve,
+ * cpe_scale_system returns, per sequence, the Gauss-Newton system of the scales with the poses eliminated (variable projection):
+ *     A = d2 J / ds ds,   b = d J / ds,   E = d2 J / du ds     (the measurement terms: only they depend on the lengths; loss gradient weight and
+ *                                                               PSD curvature weight of opts.curvature, as in the solve's own normal equations)
+ *     A_red = A - E^T (H + ridge D)^-1 E,     b_red = b - E^T (H + ridge D)^-1 g
+ * with H, D, g the matrix, damping diagonal and gradient of cpe_covariance: it runs that entry's first pass at Euler q [B][N][nq] to the factor
+ * L L^T = H + ridge D, then Y = L^-1 [E | g] by forward substitution, A_red = A - Y^T Y and b_red = b - Y^T L^-1 g.  The Newton step of the
+ * scales at re-adapted poses is -A_red^-1 b_red, and A_red^-1 is the covariance of the scales.
+ * Device pointers: q, meas, weight (as cpe_covariance takes them) and the outputs A, A_red [B][G][G], b, b_red [B][G], cost [B] = the measurement
+ * cost at q.  HOST: d_attach [M][G][n_links][3] and d_marker_off [M][G][n_markers][3], the derivatives of cpe_skeleton's `attach` and `marker_off`
+ * by every scale for each of the handle's M models (1 for cpe_create); model, n_frames [B], both NULL or both given (cpe_covariance_ragged's
+ * layout); status [B]: CPE_OK, or CPE_NUMERICAL where the matrix has no factor -- that sequence's outputs are all 0.0.  A and A_red are exactly
+ * symmetric, a group no marker depends on has exactly zero rows and columns, every sum has a fixed order (no atomics): results are reproducible
+ * bit for bit and a sequence's do not depend on the batch.
+ * Refused with CPE_BAD_ARG before the device is touched, the reason in cpe_last_error(): G outside 1..CPE_MAX_SCALES; a negative or non-finite
+ * ridge; negative sizes; model without n_frames or the reverse; a frame count outside 1..N; a NULL argument other than model and n_frames; a
+ * half-bandwidth above 4; a model index out of range. */
+#define CPE_MAX_SCALES 16
+cpe_status cpe_scale_system(cpe_handle* h, int32_t B, int32_t N, const int32_t* model /*[B] host, or NULL*/, const int32_t* n_frames /*[B] host, or NULL*/,
+                            const double* q, const double* meas, const double* weight, double ridge, int32_t G, const double* d_attach /*host*/,
+                            const double* d_marker_off /*host*/, double* A, double* b, double* A_red, double* b_red, double* cost, cpe_status* status);
+/* host-pointer twin (stages through HBM) */
+cpe_status cpe_scale_system_host(cpe_handle* h, int32_t B, int32_t N, const int32_t* model, const int32_t* n_frames, const double* q, const double* meas,
+                                 const double* weight, double ridge, int32_t G, const double* d_attach, const double* d_marker_off, double* A,
+                                 double* b, double* A_red, double* b_red, double* cost, cpe_status* status);
+
 /* ---- posterior covariance of the physics-based estimate: coordinates, and the node forces (torques, joint constraint forces, net foot forces)
  * the solve infers ("What is inverted").  Runs the launches of the first pass of cpe_solve_kinetic at Euler q -- cold start, multipliers
  * zero, node forces minimised from a cold start, as cpe_eval_kinetic_system / cpe_eval_lm_step -- at damping `ridge` in place of opts.lambda0, up to
