@@ -601,28 +601,50 @@ RATE_FIELDS = ("du_std", "ddu_std", "velocities_cov", "velocities_std", "com_cov
 _RATE_WANT = ("cov_du", "cov_ddu", "cov_vel", "cov_com", "cov_com_vel")
 
 
-def _check_rates(uncertainty: bool, uncertainty_rates: bool) -> None:
-    """uncertainty_rates=True propagates the covariance uncertainty=True computes: alone it is refused, before anything is looked at"""
-    if uncertainty_rates and not uncertainty:
-        raise ValueError("uncertainty_rates=True needs uncertainty=True: the rates are propagated from the covariance that keyword computes")
-
-
-def _check_spans(uncertainty: bool, uncertainty_spans) -> None:
-    """uncertainty_spans propagates the covariance uncertainty=True computes: alone it is refused, before anything is looked at"""
-    if uncertainty_spans is not None and not uncertainty:
-        raise ValueError("uncertainty_spans needs uncertainty=True: the spans are propagated from the covariance that keyword computes")
-
-
 SAMPLE_FIELDS = ("seed", "ridge", "du", "q", "x", "positions", "com_pos")
 
 
-def _check_samples(uncertainty: bool, uncertainty_samples: int) -> None:
-    """uncertainty_samples draws from the covariance uncertainty=True computes: alone it is refused, as is a negative count, before anything is
-    looked at"""
+@dataclass(frozen=True)
+class PosteriorRequest:
+    """what the uncertainty keywords of ONE public call ask of the posterior (posterior_request makes it; None stands for uncertainty=False):
+    the damping, whether the rates are propagated, uncertainty_spans as given, the number of draws and their seed"""
+    ridge: float = 0.0
+    rates: bool = False
+    spans: object = None
+    samples: int = 0
+    seed: int = 0
+
+    @property
+    def want_L(self) -> bool:
+        """spans and samples read the covariance call's factor"""
+        return self.spans is not None or self.samples > 0
+
+    def spans_for(self, n_frames: int):
+        return resolve_spans(self.spans, n_frames)
+
+
+def posterior_request(uncertainty: bool, uncertainty_ridge: float, uncertainty_rates: bool, uncertainty_spans, uncertainty_samples: int,
+                      uncertainty_seed: int) -> Optional[PosteriorRequest]:
+    """the six public keywords -> the request, or None for uncertainty=False.  Samples, rates and spans propagate the covariance uncertainty=True
+    computes: alone each is refused, as is a negative sample count, before anything is looked at."""
     if uncertainty_samples < 0:
         raise ValueError(f"uncertainty_samples must be >= 0, not {uncertainty_samples}")
     if uncertainty_samples and not uncertainty:
         raise ValueError("uncertainty_samples needs uncertainty=True: the samples are drawn from the covariance that keyword computes")
+    if uncertainty_rates and not uncertainty:
+        raise ValueError("uncertainty_rates=True needs uncertainty=True: the rates are propagated from the covariance that keyword computes")
+    if uncertainty_spans is not None and not uncertainty:
+        raise ValueError("uncertainty_spans needs uncertainty=True: the spans are propagated from the covariance that keyword computes")
+    if not uncertainty:
+        return None
+    return PosteriorRequest(uncertainty_ridge, bool(uncertainty_rates), uncertainty_spans, int(uncertainty_samples), uncertainty_seed)
+
+
+def _spans_of(req: Optional[PosteriorRequest], ests) -> Optional[list]:
+    """the resolved spans of every estimator, or None where none are asked for (a bad pair raises here: before any solve)"""
+    if req is None or req.spans is None:
+        return None
+    return [req.spans_for(e.params.end_frame - e.params.start_frame) for e in ests]
 
 
 def sample_normals(seed: int, K: int, N: int) -> np.ndarray:
@@ -644,22 +666,6 @@ def sample_force_normals(seed: int, K: int, N: int) -> np.ndarray:
     return np.random.default_rng([seed, 1]).standard_normal((K, N, 64))
 
 
-def _with_force_samples(cov: dict, K: int, seed: int, call) -> dict:
-    """a kinetic covariance result that _with_samples has completed with, for uncertainty_samples=K > 0, the node forces of the same draws under
-    "samples": ONE cpe_force_samples call per group.  call(du [B, K, Nm, 28], zeta [B, K, Nm, 64], lens) makes it with the covariance call's own
-    arguments and returns its padded outputs (f_s [B, K, Nm, 64], f [B, Nm, 64])."""
-    if K <= 0:
-        return cov
-    sm = cov["samples"]
-    B, _, Nm = sm["du"].shape[:3]
-    zeta = np.zeros((B, K, Nm, 64))
-    for b, n in enumerate(sm["lens"]):
-        zeta[b, :, :n] = sample_force_normals(seed, K, n)
-    fs = call(sm["du"], zeta, sm["lens"])
-    sm.update(f_s=fs["f_s"], f=fs["f"])
-    return cov
-
-
 def force_sample_fields(f_s: np.ndarray, f: np.ndarray, n_motors: int, n_con: int, n_feet: int) -> dict:
     """f_s [K, N, 64] and f [N, 64] of cpe_force_samples in the layout tau | lambda | (z, x, y) per foot -> the force fields of
     KINETIC_SAMPLE_FIELDS"""
@@ -670,25 +676,73 @@ def force_sample_fields(f_s: np.ndarray, f: np.ndarray, n_motors: int, n_con: in
     return dict(tau=tau, lam=lam, grf_net=grf, tau_mean=tau_m, lam_mean=lam_m, grf_net_mean=grf_m)
 
 
-def _with_samples(h, cov: dict, q, K: int, seed: int, model_list=None) -> dict:
-    """a covariance result (made with want_L=True) with, for uncertainty_samples=K > 0, K draws of every sequence under "samples": ONE
-    cpe_band_sample call on the factor the covariance call returned -- no second factorisation; a sequence without a factor takes no part (frame
-    count 0) -- and ONE cpe_posterior_samples call at the same q (model_list: the ragged form, lists per sequence)."""
-    if K <= 0:
-        return cov
-    ragged = isinstance(cov["cov_diag"], list)
-    L = cov["padded"]["L"] if ragged else cov["L"]
-    B, Nm = L.shape[:2]
+@dataclass
+class _Group:
+    """how the library is called for the sequences of one group, after q: `args` = the covariance call's own arguments (meas, weight; physics:
+    meas, weight, stance, kinetic options).  of = None: the plain form (one model, arrays stacked to [B, N, ...], the *_host methods); of = the
+    model of every sequence on a Handle.multi: the ragged form (lists of per-sequence arrays, the *_ragged_host methods).  force = None: a
+    kinematic group; else the physics variant arrays (grf_fixed / tau_box / grf_box, at most one) that the covariance call and the force-sample
+    call share."""
+    args: tuple
+    of: Optional[list] = None
+    force: Optional[dict] = None
+
+
+def _gather(arrays, ragged: bool):
+    """the per-sequence arrays of a group in its form: a list (ragged) or stacked (plain); None where the group has none"""
+    return None if arrays[0] is None else (list(arrays) if ragged else np.stack(arrays))
+
+
+def _posterior(h, req: PosteriorRequest, spans: Optional[list], q, group: _Group) -> dict:
+    """THE posterior chain of every estimate, on the handle h that solved the group, at its stored q:
+      1. ONE covariance call (cpe_covariance / cpe_covariance_kinetic, plain or ragged) with the factor where spans or samples read it;
+      2. req.rates or spans: ONE cpe_rate_covariance call with that call's cov_diag and cov_off -> "rates", and the point Jacobians of the spans;
+      3. spans (the resolved spans of every sequence): ONE cpe_covariance_columns call above the distinct last frames of every sequence's spans
+         -- no anchor for a sequence without a factor -> "spans";
+      4. req.samples = K > 0: ONE cpe_band_sample call on the covariance call's own factor (no second factorisation; a sequence without a factor
+         takes no part: frame count 0) with z = sample_normals(seed, K, n) per sequence at its own length, ONE cpe_posterior_samples call at the
+         same q and, for a physics group, ONE cpe_force_samples call with the covariance call's own arguments and
+         zeta = sample_force_normals(seed, K, n) -> "samples".
+    Returns the covariance call's dict with those additions; _uncertainty_of / _kinetic_uncertainty_of / _samples_of cut a sequence out of it."""
+    ragged = group.of is not None
+    models = (group.of,) if ragged else ()
+    form = "_ragged_host" if ragged else "_host"
+    a, force = (q,) + tuple(group.args), group.force or {}
+    cov = getattr(h, ("covariance" if group.force is None else "covariance_kinetic") + form)(*a, *models, req.ridge, want_L=req.want_L, **force)
+    src = cov["padded"] if ragged else cov
+    B, Nm = src["cov_diag"].shape[:2]
     lens = [len(c) for c in cov["cov_diag"]] if ragged else [Nm] * B
-    z = np.zeros((B, K, Nm, abi.NX))
-    for b, n in enumerate(lens):
-        z[b, :, :n] = sample_normals(seed, K, n)
-    du = h.band_sample_host(L, z, [n if cov["seq_status"][b] == abi.OK else 0 for b, n in enumerate(lens)])
-    if ragged:
-        ps = h.posterior_samples_host(list(q), [np.ascontiguousarray(du[b, :, :n]) for b, n in enumerate(lens)], model_list)
-    else:
-        ps = h.posterior_samples_host(q, du)
-    cov["samples"] = dict(du=du, lens=lens, q=ps["q"], positions=ps["positions"], seed=int(seed))
+    factor = [s == abi.OK for s in cov["seq_status"]]
+    want = (_RATE_WANT if req.rates else ()) + (("jac_pos", "jac_com") if spans is not None else ())
+    if want:
+        r = getattr(h, "rate_covariance" + form)(q, cov["cov_diag"], cov["cov_off"], *models, want=want)
+        if req.rates:
+            cov["rates"] = r
+    if spans is not None:
+        lasts = [sorted({b for _, b in sp}) if factor[k] else [] for k, sp in enumerate(spans)]
+        anchors = np.full((len(spans), max(1, max(len(l) for l in lasts))), -1, dtype=np.int32)
+        for k, l in enumerate(lasts):
+            anchors[k, :len(l)] = l
+        cols = h.covariance_columns_host(src["L"], src["cov_diag"], src["cov_off"], anchors, lens if ragged else None)
+        cov["spans"] = dict(columns=cols, anchors=anchors, spans=spans, jac_pos=r["jac_pos"], jac_com=r["jac_com"])
+    K = req.samples
+    if K > 0:
+        z = np.zeros((B, K, Nm, abi.NX))
+        for b, n in enumerate(lens):
+            z[b, :, :n] = sample_normals(req.seed, K, n)
+        du = h.band_sample_host(src["L"], z, [n if factor[b] else 0 for b, n in enumerate(lens)])
+        cuts = lambda v: [np.ascontiguousarray(v[b, :, :n]) for b, n in enumerate(lens)]
+        ps = h.posterior_samples_host(list(q), cuts(du), group.of) if ragged else h.posterior_samples_host(q, du)
+        cov["samples"] = dict(du=du, lens=lens, q=ps["q"], positions=ps["positions"], seed=int(req.seed))
+        if group.force is not None:
+            zeta = np.zeros((B, K, Nm, 64))
+            for b, n in enumerate(lens):
+                zeta[b, :, :n] = sample_force_normals(req.seed, K, n)
+            if ragged:
+                fs = h.force_samples_ragged_host(*a, cuts(du), cuts(zeta), group.of, req.ridge, **force)["padded"]
+            else:
+                fs = h.force_samples_host(*a, du, zeta, req.ridge, **force)
+            cov["samples"].update(f_s=fs["f_s"], f=fs["f"])
     return cov
 
 
@@ -701,17 +755,27 @@ def _samples_of(cov: Optional[dict], b: int, ridge: float) -> Optional[dict]:
                 q=np.ascontiguousarray(sm["q"][b]), positions=np.ascontiguousarray(sm["positions"][b]))
 
 
-def _complete_samples(est, h, samples: Optional[dict]) -> Optional[dict]:
-    """the sample fields of this sequence with those computed from q (h: a handle of its model): x and com_pos; None stays None"""
-    if samples is None or "x" in samples:
-        return samples
+def _com_of(h, est, q: np.ndarray) -> np.ndarray:
+    """the centre of mass [B, N, 3] at the poses q [B, N, nq] (cpe_forward_kinematics; h: a handle of the sequence's model)"""
     import torch
-    q = samples["q"]
     dev = torch.device("cuda", est.device)
     pos = torch.empty(q.shape[:2] + (est.skeleton.n_markers, 3), dtype=torch.float64, device=dev)
     com = torch.empty(q.shape[:2] + (3,), dtype=torch.float64, device=dev)
     h.forward_kinematics(torch.tensor(q, device=dev), pos, com); h.synchronize()
-    return dict(samples, x=est.relative_angles(q), com_pos=com.cpu().numpy())
+    return com.cpu().numpy()
+
+
+def _store_com(est, h, q: np.ndarray) -> None:
+    """est.com_pos and est.com_vel of the ONE sequence q [1, N, nq] (acinoset_misc.py:742)"""
+    est.com_pos = _com_of(h, est, q)[0]
+    est.com_vel = (est.com_pos[1:] - est.com_pos[:-1]) * est.scene.fps
+
+
+def _complete_samples(est, h, samples: Optional[dict]) -> Optional[dict]:
+    """the sample fields of this sequence with those computed from q (h: a handle of its model): x and com_pos; None stays None"""
+    if samples is None or "x" in samples:
+        return samples
+    return dict(samples, x=est.relative_angles(samples["q"]), com_pos=_com_of(h, est, samples["q"]))
 
 
 def _store_samples(est, h, samples: Optional[dict], out_dir: str, fields=SAMPLE_FIELDS) -> None:
@@ -779,32 +843,6 @@ def span_uncertainty(columns: np.ndarray, anchors, cov_diag: np.ndarray, jac_com
                 span_positions_displacement_cov=pcov, span_positions_displacement_std=std(pcov))
 
 
-def _with_rates(h, cov: dict, q, rates: bool, model_list=None, spans=None) -> dict:
-    """a covariance result with, for uncertainty_rates=True, the rate covariances of the same sequences under "rates": ONE cpe_rate_covariance call
-    on the same handle at the same q with that call's cov_diag and cov_off (model_list: the ragged form, lists per sequence).
-    spans (uncertainty_spans: the resolved spans of every sequence; the covariance call was made with want_L=True): that rate call also returns the
-    point Jacobians, and ONE cpe_covariance_columns call gives the columns of Sigma above the distinct last frames of every sequence's spans -- no
-    anchor for a sequence without a factor.  Both go under "spans"."""
-    want = (_RATE_WANT if rates else ()) + (("jac_pos", "jac_com") if spans is not None else ())
-    ragged = isinstance(cov["cov_diag"], list)
-    if want:
-        if ragged:
-            r = h.rate_covariance_ragged_host(q, cov["cov_diag"], cov["cov_off"], model_list, want=want)
-        else:
-            r = h.rate_covariance_host(q, cov["cov_diag"], cov["cov_off"], want=want)
-        if rates:
-            cov["rates"] = r
-    if spans is not None:
-        lasts = [sorted({b for _, b in sp}) if cov["seq_status"][k] == abi.OK else [] for k, sp in enumerate(spans)]
-        anchors = np.full((len(spans), max(1, max(len(a) for a in lasts))), -1, dtype=np.int32)
-        for k, a in enumerate(lasts):
-            anchors[k, :len(a)] = a
-        src = cov["padded"] if ragged else cov
-        cols = h.covariance_columns_host(src["L"], src["cov_diag"], src["cov_off"], anchors, [len(c) for c in cov["cov_diag"]] if ragged else None)
-        cov["spans"] = dict(columns=cols, anchors=anchors, spans=spans, jac_pos=r["jac_pos"], jac_com=r["jac_com"])
-    return cov
-
-
 def _rate_fields(rates: dict, b: int) -> dict:
     """the rate fields of est.uncertainty of sequence b, all but speed_std (which needs the centre-of-mass velocity: speed_std_of).  com_vel_cov
     row k is the library's row k + 1: the velocity between the frames k and k + 1, as com_vel[k]."""
@@ -839,7 +877,7 @@ def _add_speed_std(est) -> None:
 
 def _uncertainty_of(cov: dict, b: int, ridge: float) -> Optional[dict]:
     """est.uncertainty of sequence b from a covariance_host / covariance_ragged_host result (None where the matrix has no Cholesky factor); with
-    the rate fields where _with_rates added the rate covariances"""
+    the rate fields where _posterior added the rate covariances"""
     if cov["seq_status"][b] != abi.OK:
         return None
     cu, cp = np.ascontiguousarray(cov["cov_diag"][b]), np.ascontiguousarray(cov["cov_pos"][b])
@@ -910,21 +948,37 @@ def _kinetic_uncertainty_of(cov: dict, b: int, ridge: float, res: dict) -> Kinet
     return KineticUncertainty(fields=unc, samples=sm)
 
 
-def _kinetic_uncertainty(h, ko: abi.KineticOptions, res: dict, meas: np.ndarray, weight: np.ndarray, stance: np.ndarray, ridge: float,
-                         grf_fixed=None, tau_box=None, grf_box=None, rates: bool = False, spans=None,
-                         samples: Tuple[int, int] = (0, 0)) -> KineticUncertainty:
-    """cpe_covariance_kinetic at the solution res["q"] of a converged physics-based solve, with the solve's own stance, options and variant arrays;
-    samples = (uncertainty_samples, uncertainty_seed): the draws of _with_samples and, with the same arguments, their node forces"""
-    if res["stats"][0].status != abi.OK:
-        return KineticUncertainty()
-    one = lambda a: None if a is None else a[None]
-    force = dict(grf_fixed=one(grf_fixed), tau_box=one(tau_box), grf_box=one(grf_box))
-    cov = h.covariance_kinetic_host(res["q"], meas[None], weight[None], stance[None], ko, ridge, want_L=spans is not None or samples[0] > 0, **force)
-    cov = _with_rates(h, cov, res["q"], rates, spans=None if spans is None else [spans])
-    cov = _with_samples(h, cov, res["q"], samples[0], samples[1])
-    cov = _with_force_samples(cov, samples[0], samples[1], lambda du, zeta, lens: h.force_samples_host(
-        res["q"], meas[None], weight[None], stance[None], ko, du, zeta, ridge, **force))
-    return _kinetic_uncertainty_of(cov, 0, ridge, res)
+def _kinetic_options_of(preps, of):
+    """the kinetic options of a group in its form: those of its one model (plain), or of the first sequence of every model (ragged)"""
+    return preps[0]["ko"] if of is None else [preps[of.index(k)]["ko"] for k in range(max(of) + 1)]
+
+
+def _batch_kinetic_uncertainty(h, req: Optional[PosteriorRequest], spans: Optional[list], res: dict, preps, meas, weight,
+                               of=None) -> Dict[int, KineticUncertainty]:
+    """uncertainty of every sequence of a solved physics group, keyed by its place b in the group (empty: not asked for): ONE posterior chain
+    (_posterior) over the places whose solve converged, with the solve's own stance, options and variant arrays; the others get
+    KineticUncertainty(): nothing is asked of the library for them.  preps: per sequence a dict with stance, ko and at most one of grf_fixed /
+    tau_box / grf_box (a _kinetic_prepare dict); meas, weight, spans (or None): per sequence; of: as in _kinetic_solve."""
+    if req is None:
+        return {}
+    unc = {b: KineticUncertainty() for b in range(len(preps))}
+    conv = [b for b in unc if res["stats"][b].status == abi.OK]
+    if conv:
+        pick = lambda v: _gather([v[b] for b in conv], of is not None)
+        force = {k: pick([p[k] for p in preps]) for k in ("grf_fixed", "tau_box", "grf_box") if preps[0].get(k) is not None}
+        group = _Group((pick(meas), pick(weight), pick([p["stance"] for p in preps]), _kinetic_options_of(preps, of)),
+                       None if of is None else [of[b] for b in conv], force)
+        cov = _posterior(h, req, None if spans is None else [spans[b] for b in conv], pick(res["q"]), group)
+        for k, b in enumerate(conv):
+            unc[b] = _kinetic_uncertainty_of(cov, k, req.ridge, _sequence_of(res, b))
+    return unc
+
+
+def _kinetic_uncertainty(h, ko: abi.KineticOptions, res: dict, meas: np.ndarray, weight: np.ndarray, stance: np.ndarray, req: PosteriorRequest,
+                         spans=None, **force) -> KineticUncertainty:
+    """the group of one, from arrays: the posterior at the solution res["q"] of ONE physics-based solve with its stance, options and variant
+    array (force: grf_fixed, tau_box or grf_box of that sequence); spans: its resolved spans"""
+    return _batch_kinetic_uncertainty(h, req, None if spans is None else [spans], res, [dict(stance=stance, ko=ko, **force)], [meas], [weight])[0]
 
 
 def _store_kinetic_uncertainty(est: CheetahEstimator, unc: Optional[KineticUncertainty], ok: bool, out_dir: Optional[str],
@@ -958,15 +1012,8 @@ def _kin_finish(est: CheetahEstimator, h, res: dict, seconds: float, solver_outp
     samples: what _samples_of returned for this sequence (uncertainty_samples; None: none): completed, stored and written as samples.npz."""
     est.samples = None
     params, scene = est.params, est.scene
-    N = params.end_frame - params.start_frame
     est.opt_time_s = seconds
-    import torch
-    dev = torch.device("cuda", est.device)
-    qd = torch.tensor(res["q"], device=dev)
-    pos = torch.empty((1, N, 24, 3), dtype=torch.float64, device=dev); com = torch.empty((1, N, 3), dtype=torch.float64, device=dev)
-    h.forward_kinematics(qd, pos, com); h.synchronize()
-    est.com_pos = com[0].cpu().numpy()
-    est.com_vel = (est.com_pos[1:] - est.com_pos[:-1]) * scene.fps     # acinoset_misc.py:742
+    _store_com(est, h, res["q"])
     st = res["stats"][0]
     est.result = res
     est.costs = {"measurement": st.cost_meas, "model": st.cost_model, "pose": st.cost_pose, "motion": st.cost_motion}
@@ -1087,15 +1134,13 @@ def calibrate_lengths(estimators: Sequence[CheetahEstimator], groups=skeleton.LE
     d_attach, d_marker_off = skeleton.length_derivatives(model_name, n_markers, groups)
     prep = [_kin_prepare(e, monocular_constraints, disable_pose_prior, disable_motion_prior, pose_model_num_components, motion_model_window_size,
                          motion_model_sparse_solution, None if q_init is None else q_init[i],
-                         None if options is None else _copy_options(options)) for i, e in enumerate(ests)]
+                         None if options is None else _struct_copy(options)) for i, e in enumerate(ests)]
     pri = prep[0][2]
     if len({ragged_group_key(e.skeleton, p[1], p[2], e.device) for e, p in zip(ests, prep)}) != 1:
         raise ValueError("calibrate_lengths: the sequences of one call go through one ragged batch: same priors and batch-level solver options")
     cost_scale = prep[0][1].cost_scale
     # one model per distinct (rig, options); the skeleton of every model is this round's
-    rigs: Dict[bytes, int] = {}
-    of = [rigs.setdefault(b"".join(_struct_bytes(e.cams[c]) for c in range(len(e.cams))) + _struct_bytes(p[1]), len(rigs)) for e, p in zip(ests, prep)]
-    reps = [of.index(k) for k in range(len(rigs))]
+    of, reps = _models_of(b"".join(_struct_bytes(e.cams[c]) for c in range(len(e.cams))) + _struct_bytes(p[1]) for e, p in zip(ests, prep))
     meas, weight = [e.meas for e in ests], [e.weight for e in ests]
     tabs = (np.broadcast_to(d_attach, (len(reps),) + d_attach.shape), np.broadcast_to(d_marker_off, (len(reps),) + d_marker_off.shape))
     build = lambda s: skeleton.build_skeleton(model_name, n_markers, e0.params.kinetic_dataset, length_scale=s, groups=groups)
@@ -1198,9 +1243,7 @@ def estimate_kinematics(estimator: CheetahEstimator, solver_output: bool = True,
     are still used.  length_ridge: the damping of the poses' matrix in cpe_scale_system (a monocular run may need 1e-6 for a factor).  The
     calibration's pose solves use this call's priors and options.  One camera needs a prior (length_prior_sigma=None: ValueError); together
     with shutter-delay estimation: NotImplementedError.  uncertainty=True stays the covariance of the poses GIVEN the lengths."""
-    _check_samples(uncertainty, uncertainty_samples)
-    _check_rates(uncertainty, uncertainty_rates)
-    _check_spans(uncertainty, uncertainty_spans)
+    req = posterior_request(uncertainty, uncertainty_ridge, uncertainty_rates, uncertainty_spans, uncertainty_samples, uncertainty_seed)
     if estimate_lengths:
         _check_lengths([estimator], length_prior_sigma)
     est, params, scene = estimator, estimator.params, estimator.scene
@@ -1211,39 +1254,35 @@ def estimate_kinematics(estimator: CheetahEstimator, solver_output: bool = True,
                                 pose_model_num_components=pose_model_num_components, motion_model_window_size=motion_model_window_size,
                                 motion_model_sparse_solution=motion_model_sparse_solution)
         q_init = cal["q"][0]
-    sk = est.skeleton
-    spans = resolve_spans(uncertainty_spans, params.end_frame - params.start_frame)
+    spans = _spans_of(req, [est])
     q_init, opts, pri = _kin_prepare(est, monocular_constraints, disable_pose_prior, disable_motion_prior, pose_model_num_components,
                                      motion_model_window_size, motion_model_sparse_solution, q_init, options)
-    if uncertainty:
-        _check_uncertainty(est, pri, uncertainty_ridge)
-    h = _lib.Handle(sk, est.cams, opts, pri, device=est.device)
-    try:
-        t0 = time()
-        if params.enable_shutter_delay_estimation and scene.cam_idx is None:
+    if req is not None:
+        _check_uncertainty(est, pri, req.ridge)
+    finish = (solver_output, monocular_constraints, out_dir_prefix)
+    if params.enable_shutter_delay_estimation and scene.cam_idx is None:            # (never with uncertainty: _check_uncertainty)
+        h = _lib.Handle(est.skeleton, est.cams, opts, pri, device=est.device)
+        try:
+            t0 = time()
             # m.shutter_delay, bounds +-hm0, camera 1 fixed (acinoset_misc.py:182-183, 273-275)
             res = h.solve_shutter_host(q_init[None], est.meas[None], est.weight[None], opts.h, max_rounds=20, tol_tau=1e-5)
             est.shutter_delay = res["tau"][0]
-        else:
-            res = h.solve_host(q_init[None], est.meas[None], est.weight[None])
-            est.shutter_delay = None
-        dt = time() - t0
-        unc = None
-        if uncertainty:
-            cov = h.covariance_host(res["q"], est.meas[None], est.weight[None], uncertainty_ridge, want_L=spans is not None or uncertainty_samples > 0) \
-                if res["stats"][0].status == abi.OK else None
-            cov = None if cov is None else _with_rates(h, cov, res["q"], uncertainty_rates, spans=None if spans is None else [spans])
-            cov = None if cov is None else _with_samples(h, cov, res["q"], uncertainty_samples, uncertainty_seed)
-            unc = (None if cov is None else _uncertainty_of(cov, 0, uncertainty_ridge), uncertainty_ridge)
-        return _kin_finish(est, h, res, dt, solver_output, monocular_constraints, out_dir_prefix, uncertainty=unc,
-                           samples=_samples_of(cov if uncertainty else None, 0, uncertainty_ridge))
-    finally:
-        h.close()
+            return _kin_finish(est, h, res, time() - t0, *finish)
+        finally:
+            h.close()
+    out = [None]
+    _solve_kinematic_group([est], [0], {0: (q_init, opts, pri)}, out, False, req, spans, finish, single=True)
+    return out[0]
 
 
 def _struct_bytes(x) -> bytes:
-    import ctypes as _C
-    return bytes(_C.string_at(_C.addressof(x), _C.sizeof(x)))
+    """the bytes of a ctypes struct"""
+    return bytes(x)
+
+
+def _struct_copy(x):
+    """a ctypes struct of the same type with the same bytes"""
+    return type(x).from_buffer_copy(x)
 
 
 def ragged_group_key(sk: abi.Skeleton, opts: abi.Options, pri: Optional[abi.Priors], device: int) -> tuple:
@@ -1275,9 +1314,7 @@ def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_out
     and one cpe_posterior_samples call per group, same bit-equality of est.samples and samples.npz.
     estimate_lengths, length_prior_sigma, length_scale_init, length_ridge: as in estimate_kinematics; the estimators of one animal (name and dataset kind) share
     their scales: one calibrate_lengths call per animal over all its sequences, before the solves."""
-    _check_samples(uncertainty, uncertainty_samples)
-    _check_rates(uncertainty, uncertainty_rates)
-    _check_spans(uncertainty, uncertainty_spans)
+    req = posterior_request(uncertainty, uncertainty_ridge, uncertainty_rates, uncertainty_spans, uncertainty_samples, uncertainty_seed)
     ests = list(estimators)
     cal_q: Dict[int, np.ndarray] = {}
     if estimate_lengths:
@@ -1289,8 +1326,7 @@ def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_out
                                     monocular_constraints=monocular_constraints, disable_pose_prior=disable_pose_prior,
                                     disable_motion_prior=disable_motion_prior, options=options, ridge=length_ridge, solver_output=solver_output)
             cal_q.update({i: cal["q"][b] for b, i in enumerate(idx)})
-    spans = [resolve_spans(uncertainty_spans, e.params.end_frame - e.params.start_frame) for e in ests]      # (a bad pair: before any solve)
-    group_spans = lambda idx: None if uncertainty_spans is None else [spans[i] for i in idx]
+    spans = _spans_of(req, ests)
     out: List[Optional[bool]] = [None] * len(ests)
     groups: Dict[tuple, List[int]] = {}
     prepared = {}
@@ -1301,44 +1337,18 @@ def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_out
                                          uncertainty_spans=uncertainty_spans, uncertainty_samples=uncertainty_samples, uncertainty_seed=uncertainty_seed)
             continue
         q_init, opts, pri = _kin_prepare(est, monocular_constraints, disable_pose_prior, disable_motion_prior, 5, 4, True, cal_q.get(i),
-                                         None if options is None else _copy_options(options))
+                                         None if options is None else _struct_copy(options))
         prepared[i] = (q_init, opts, pri)
-        if uncertainty:
-            _check_uncertainty(est, pri, uncertainty_ridge)
+        if req is not None:
+            _check_uncertainty(est, pri, req.ridge)
         if ragged:
             key = ragged_group_key(est.skeleton, opts, pri, est.device)
         else:
             key = (_struct_bytes(est.skeleton), b"".join(_struct_bytes(est.cams[c]) for c in range(len(est.cams))), q_init.shape[0], _struct_bytes(opts),
                    None if pri is None else _struct_bytes(pri), est.device)
         groups.setdefault(key, []).append(i)
-    if ragged:
-        for idx in groups.values():
-            _solve_ragged_group(ests, idx, prepared, out, solver_output, monocular_constraints, out_dir_prefix,
-                                uncertainty_ridge if uncertainty else None, uncertainty_rates, group_spans(idx), (uncertainty_samples, uncertainty_seed))
-        return [bool(v) for v in out]
     for idx in groups.values():
-        e0 = ests[idx[0]]
-        _, opts, pri = prepared[idx[0]]
-        h = _lib.Handle(e0.skeleton, e0.cams, opts, pri, device=e0.device)
-        try:
-            t0 = time()
-            res = h.solve_host(np.stack([prepared[i][0] for i in idx]), np.stack([ests[i].meas for i in idx]), np.stack([ests[i].weight for i in idx]))
-            dt = (time() - t0) / len(idx)                                            # processing_time_s of a sequence: its share of the batched solve
-            cov = None
-            if uncertainty:
-                cov = h.covariance_host(res["q"], np.stack([ests[i].meas for i in idx]), np.stack([ests[i].weight for i in idx]), uncertainty_ridge,
-                                        want_L=uncertainty_spans is not None or uncertainty_samples > 0)
-                cov = _with_rates(h, cov, res["q"], uncertainty_rates, spans=group_spans(idx))
-                cov = _with_samples(h, cov, res["q"], uncertainty_samples, uncertainty_seed)
-            for b, i in enumerate(idx):
-                one = {k: (v[b:b + 1] if isinstance(v, np.ndarray) else v) for k, v in res.items() if k not in ("stats", "status")}
-                one["stats"] = [res["stats"][b]]; one["status"] = res["stats"][b].status
-                ests[i].shutter_delay = None
-                unc = None if cov is None else (_uncertainty_of(cov, b, uncertainty_ridge), uncertainty_ridge)
-                out[i] = _kin_finish(ests[i], h, one, dt, solver_output, monocular_constraints, out_dir_prefix, uncertainty=unc,
-                                     samples=_samples_of(cov, b, uncertainty_ridge))
-        finally:
-            h.close()
+        _solve_kinematic_group(ests, idx, prepared, out, ragged, req, spans, (solver_output, monocular_constraints, out_dir_prefix))
     return [bool(v) for v in out]
 
 
@@ -1346,54 +1356,75 @@ def _model_bytes(est: CheetahEstimator, opts: abi.Options) -> bytes:
     return _struct_bytes(est.skeleton) + b"".join(_struct_bytes(est.cams[c]) for c in range(len(est.cams))) + _struct_bytes(opts)
 
 
-def _solve_ragged_group(ests, idx, prepared, out, solver_output, monocular_constraints, out_dir_prefix, uncertainty_ridge: Optional[float] = None,
-                        uncertainty_rates: bool = False, spans=None, samples: Tuple[int, int] = (0, 0)) -> None:
-    """estimate_kinematics_batch(ragged=True) for one group: one model per distinct (skeleton, rig, options), one cpe_solve_ragged call, then every
-    sequence's centre of mass, costs and files through _kin_finish with a plain handle of its own model (forward kinematics of that skeleton).
-    samples: (uncertainty_samples, uncertainty_seed)"""
+def _models_of(keys) -> Tuple[List[int], List[int]]:
+    """model de-duplication of a group: (of = the model of every sequence, numbered in order of first appearance; the place of every model's
+    first sequence) from what tells the sequences' models apart"""
     models: Dict[bytes, int] = {}
-    of = []
-    for i in idx:
-        of.append(models.setdefault(_model_bytes(ests[i], prepared[i][1]), len(models)))
-    first = {}
-    for b, i in enumerate(idx):
-        first.setdefault(of[b], i)
-    reps = [first[k] for k in range(len(models))]
-    pri = prepared[idx[0]][2]
-    dev = ests[idx[0]].device
-    h = _lib.Handle.multi([ests[i].skeleton for i in reps], [ests[i].cams for i in reps], [prepared[i][1] for i in reps], pri, device=dev)
-    fk = {}
+    of = [models.setdefault(k, len(models)) for k in keys]
+    return of, [of.index(k) for k in range(len(models))]
+
+
+class _GroupHandles:
+    """The handles of one group in its form.  models: (skeleton, cameras, options) of every sequence; keys: what tells their models apart.
+    Plain (keys None): `solve` is ONE handle of the first sequence's model and serves every sequence's forward kinematics as well; `of` is None.
+    Ragged: `solve` is a Handle.multi over the distinct models, `of` the model of every sequence, and fk(b) a plain handle of sequence b's model
+    (forward kinematics of that skeleton), made when first asked for and kept per model."""
+
+    def __init__(self, models, pri, device: int, keys=None):
+        self.of, self._fk = None, {}
+        if keys is None:
+            self.solve = _lib.Handle(*models[0], pri, device=device)
+        else:
+            self.of, reps = _models_of(keys)
+            self._models, self._device = [models[b] for b in reps], device
+            self.solve = _lib.Handle.multi(*(list(v) for v in zip(*self._models)), pri, device=device)
+
+    def fk(self, b: int):
+        if self.of is None:
+            return self.solve
+        k = self.of[b]
+        if k not in self._fk:
+            self._fk[k] = _lib.Handle(*self._models[k], None, device=self._device)
+        return self._fk[k]
+
+    def close(self) -> None:
+        for h in [self.solve] + list(self._fk.values()):
+            h.close()
+
+
+def _sequence_of(res: dict, b: int) -> dict:
+    """sequence b of a batched solve's result (plain: arrays [B, N, ...]; ragged: lists of per-sequence arrays) as the result of ONE sequence"""
+    one = {k: (res[k][b][None] if isinstance(res[k], list) else res[k][b:b + 1]) for k in _lib.KINETIC_OUTPUTS if k in res}
+    one.update({k: [res[k][b]] for k in ("stats", "kstats") if k in res}, status=res["stats"][b].status)
+    return one
+
+
+def _solve_kinematic_group(ests, idx, prepared, out, ragged: bool, req: Optional[PosteriorRequest], spans: Optional[list], finish: tuple,
+                           single: bool = False) -> None:
+    """estimate_kinematics (single: the group of one) and estimate_kinematics_batch for one group, plain (one model and length: ONE cpe_solve call
+    with B = the group's size) or ragged (one model per distinct (skeleton, rig, options): ONE cpe_solve_ragged call): the solve, with req the
+    posterior chain on the same handle at the stored q, then every sequence's centre of mass, costs and files through _kin_finish(..., *finish).
+    spans: the resolved spans of ALL estimators, or None."""
+    seqs = [ests[i] for i in idx]
+    a = tuple(_gather(v, ragged) for v in ([prepared[i][0] for i in idx], [e.meas for e in seqs], [e.weight for e in seqs]))
+    hs = _GroupHandles([(e.skeleton, e.cams, prepared[i][1]) for e, i in zip(seqs, idx)], prepared[idx[0]][2], seqs[0].device,
+                       [_model_bytes(e, prepared[i][1]) for e, i in zip(seqs, idx)] if ragged else None)
     try:
         t0 = time()
-        res = h.solve_ragged_host([prepared[i][0] for i in idx], [ests[i].meas for i in idx], [ests[i].weight for i in idx], of)
+        res = hs.solve.solve_ragged_host(*a, hs.of) if ragged else hs.solve.solve_host(*a)
         dt = (time() - t0) / len(idx)                                                # processing_time_s of a sequence: its share of the batched solve
         cov = None
-        if uncertainty_ridge is not None:                                            # (uncertainty=True) at the stored q of every sequence, same handle
-            cov = h.covariance_ragged_host(res["q"], [ests[i].meas for i in idx], [ests[i].weight for i in idx], of, uncertainty_ridge,
-                                           want_L=spans is not None or samples[0] > 0)
-            cov = _with_rates(h, cov, res["q"], uncertainty_rates, of, spans)
-            cov = _with_samples(h, cov, res["q"], samples[0], samples[1], of)
+        # THE asymmetry of the kinematic stage, kept as it is: a single call asks nothing of the library after a solve that did not converge; a
+        # batch asks for its whole group and discards what such a sequence does not need
+        if req is not None and not (single and res["stats"][0].status != abi.OK):
+            cov = _posterior(hs.solve, req, None if spans is None else [spans[i] for i in idx], res["q"], _Group(a[1:], hs.of))
         for b, i in enumerate(idx):
-            one = {k: res[k][b][None] for k in ("q", "dq", "ddq", "positions", "meas_err")}
-            one["stats"] = [res["stats"][b]]; one["status"] = res["stats"][b].status
-            if of[b] not in fk:
-                r = reps[of[b]]
-                fk[of[b]] = _lib.Handle(ests[r].skeleton, ests[r].cams, prepared[r][1], None, device=dev)
             ests[i].shutter_delay = None
-            unc = None if cov is None else (_uncertainty_of(cov, b, uncertainty_ridge), uncertainty_ridge)
-            out[i] = _kin_finish(ests[i], fk[of[b]], one, dt, solver_output, monocular_constraints, out_dir_prefix, uncertainty=unc,
-                                 samples=_samples_of(cov, b, uncertainty_ridge))
+            unc = None if req is None else (None if cov is None else _uncertainty_of(cov, b, req.ridge), req.ridge)
+            out[i] = _kin_finish(ests[i], hs.fk(b), _sequence_of(res, b), dt, *finish, uncertainty=unc,
+                                 samples=None if cov is None else _samples_of(cov, b, req.ridge))
     finally:
-        h.close()
-        for f in fk.values():
-            f.close()
-
-
-def _copy_options(o: abi.Options) -> abi.Options:
-    import ctypes as _C
-    c = abi.Options()
-    _C.memmove(_C.byref(c), _C.byref(o), _C.sizeof(abi.Options))
-    return c
+        hs.close()
 
 
 def _dataset_worker(rank: int, n_ranks: int, device: int, jobs: List[dict], estimate_kwargs: dict, queue) -> None:
@@ -1600,31 +1631,25 @@ def estimate_kinetics(estimator: CheetahEstimator, init_torques: bool = True, au
     W_n = (track_scale / 2) (X Sigma_nn X^T)^-1 from cov_u of the uncertainty.npz that estimate_kinematics(uncertainty=True) wrote beside the
     kinematic result (one cpe_track_precision call, then cpe_solve_kinetic_tracked_weighted; DESIGN.md 2b has the approximation and what
     track_scale is for).  "posterior" with use_2d_reprojections=True, or any other string, is a ValueError."""
-    _check_samples(uncertainty, uncertainty_samples)
-    _check_rates(uncertainty, uncertainty_rates)
-    _check_spans(uncertainty, uncertainty_spans)
+    req = posterior_request(uncertainty, uncertainty_ridge, uncertainty_rates, uncertainty_spans, uncertainty_samples, uncertainty_seed)
     _check_track_weights(track_weights, track_scale, use_2d_reprojections)
-    spans = resolve_spans(uncertainty_spans, estimator.params.end_frame - estimator.params.start_frame)
-    if uncertainty and not use_2d_reprojections:
-        raise NotImplementedError("uncertainty together with use_2d_reprojections=False: cpe_covariance_kinetic takes the reprojection cost; the covariance "
-                                  "of the 3D kinematic cost (cpe_solve_kinetic_tracked) is not built")
+    spans = _spans_of(req, [estimator])
+    _check_tracked_uncertainty(req, use_2d_reprojections)
     prep = _kinetic_prepare(estimator, auto, use_2d_reprojections, init_prev_kinematic_solution, synthesised_grf, no_slip, joint_estimation, fix_grf,
                             ground_constraint, disable_pose_prior, disable_motion_prior, out_dir_prefix, options, kinetic_options,
                             track_weights=track_weights, track_scale=track_scale)
-    est = estimator
-    if uncertainty:
-        _lib.covariance_supported(prep["pri"], uncertainty_ridge)          # raises with the library's reason (negative or non-finite ridge)
-    h = _lib.Handle(prep["skeleton"], est.cams, prep["opts"], prep["pri"], device=est.device)
-    try:
-        t0 = time()
-        res = _kinetic_solve(h, [prep], [est])                                       # the plain batch of one sequence
-        dt = time() - t0
-        unc = _kinetic_uncertainty(h, prep["ko"], res, est.meas, est.weight, prep["stance"], uncertainty_ridge, grf_fixed=prep["grf_fixed"],
-                                   grf_box=prep["grf_box"], rates=uncertainty_rates, spans=spans,
-                                   samples=(uncertainty_samples, uncertainty_seed)) if uncertainty else None
-        return _kinetic_finish(est, h, res, dt, prep, solver_output, out_fname, out_dir_prefix, uncertainty=unc)
-    finally:
-        h.close()
+    if req is not None:
+        _lib.covariance_supported(prep["pri"], req.ridge)                  # raises with the library's reason (negative or non-finite ridge)
+    out = [None]
+    _solve_kinetic_group([estimator], [0], {0: prep}, out, False, req, spans, (solver_output, out_fname, out_dir_prefix))      # the plain group of one
+    return out[0]
+
+
+def _check_tracked_uncertainty(req: Optional[PosteriorRequest], use_2d_reprojections: bool) -> None:
+    """what the physics-based stage refuses of uncertainty=True before anything is prepared"""
+    if req is not None and not use_2d_reprojections:
+        raise NotImplementedError("uncertainty together with use_2d_reprojections=False: cpe_covariance_kinetic takes the reprojection cost; the covariance "
+                                  "of the 3D kinematic cost (cpe_solve_kinetic_tracked) is not built")
 
 
 def kinematic_result_path(data_dir: str, cam_idx: Optional[int], init_prev_kinematic_solution: bool) -> str:
@@ -1770,15 +1795,9 @@ def _kinetic_finish(est: CheetahEstimator, h, res: dict, seconds: float, prep: d
     uncertainty: what _kinetic_uncertainty returned, or None (not asked for); stored after the solve's own files (_store_kinetic_uncertainty, which
     no_factor goes to)."""
     params, scene = est.params, est.scene
-    N, q_init, stance, ko = prep["N"], prep["q_init"], prep["stance"], prep["ko"]
+    q_init, stance, ko = prep["q_init"], prep["stance"], prep["ko"]
     est.opt_time_s = seconds
-    import torch
-    dev = torch.device("cuda", est.device)
-    qd = torch.tensor(res["q"], device=dev)
-    pos = torch.empty((1, N, 24, 3), dtype=torch.float64, device=dev); com = torch.empty((1, N, 3), dtype=torch.float64, device=dev)
-    h.forward_kinematics(qd, pos, com); h.synchronize()
-    est.com_pos = com[0].cpu().numpy()
-    est.com_vel = (est.com_pos[1:] - est.com_pos[:-1]) * scene.fps
+    _store_com(est, h, res["q"])
     st, ks = res["stats"][0], res["kstats"][0]
     est.result = res
     est.kinetic = dict(tau=res["tau"][0], lam=res["lam"][0], grf=res["grf"][0], slack=res["slack"][0], stance=stance, ground_height=ko.ground_height)
@@ -1809,10 +1828,10 @@ def _kinetic_solve(h, preps, ests, of=None) -> dict:
     arrays are stacked to [B, N, ...]).  of = the model index of every sequence on a Handle.multi: a ragged batch (lists of per-sequence arrays;
     the kinetic options of model k are those of its first sequence).  Returns the result of the *_host / *_ragged_host method."""
     p0 = preps[0]
-    gather = (lambda v: None if v[0] is None else np.stack(v)) if of is None else (lambda v: None if v[0] is None else list(v))
+    gather = lambda v: _gather(v, of is not None)
     a = {k: gather([p[k] for p in preps]) for k in ("q_init", "q_target", "stance", "cov_u", "grf_fixed", "grf_box")}
     meas, weight = gather([e.meas for e in ests]), gather([e.weight for e in ests])
-    ko, form, kw = (p0["ko"], "_host", {}) if of is None else ([preps[of.index(k)]["ko"] for k in range(max(of) + 1)], "_ragged_host", dict(model_list=of))
+    ko, (form, kw) = _kinetic_options_of(preps, of), ("_host", {}) if of is None else ("_ragged_host", dict(model_list=of))
     force = dict(grf_fixed=a["grf_fixed"], grf_box=a["grf_box"])
     if p0["weighted"]:
         W = h.track_precision_host(a["cov_u"], p0["track_scale"], **kw)
@@ -1820,13 +1839,6 @@ def _kinetic_solve(h, preps, ests, of=None) -> dict:
     if p0["tracked"]:
         return getattr(h, "solve_kinetic_tracked" + form)(ko, a["q_init"], a["q_target"], a["stance"], meas, weight, **kw, **force)
     return getattr(h, "solve_kinetic" + form)(ko, a["q_init"], meas, weight, a["stance"], **kw, **force)
-
-
-def _copy_kinetic_options(o: abi.KineticOptions) -> abi.KineticOptions:
-    import ctypes as _C
-    c = abi.KineticOptions()
-    _C.memmove(_C.byref(c), _C.byref(o), _C.sizeof(abi.KineticOptions))
-    return c
 
 
 def kinetic_ragged_group_key(sk: abi.Skeleton, opts: abi.Options, ko: abi.KineticOptions, pri: Optional[abi.Priors], variant: str, device: int,
@@ -1843,13 +1855,6 @@ def kinetic_ragged_group_key(sk: abi.Skeleton, opts: abi.Options, ko: abi.Kineti
 
 def _kinetic_model_bytes(est: CheetahEstimator, prep: dict) -> bytes:
     return _model_bytes(est, prep["opts"]) + _struct_bytes(prep["skeleton"]) + _struct_bytes(prep["ko"])
-
-
-def _kinetic_one(res: dict, b: int) -> dict:
-    """sequence b of a batched kinetic result as solve_kinetic_host returns ONE sequence"""
-    one = {k: (res[k][b][None] if isinstance(res[k], list) else res[k][b:b + 1]) for k in ("q", "dq", "ddq", "positions", "meas_err", "tau", "lam", "grf", "slack")}
-    one["stats"] = [res["stats"][b]]; one["kstats"] = [res["kstats"][b]]; one["status"] = res["stats"][b].status
-    return one
 
 
 def estimate_kinetics_batch(estimators: Sequence[CheetahEstimator], init_torques: bool = True, auto: bool = True, use_2d_reprojections: bool = True,
@@ -1877,22 +1882,18 @@ def estimate_kinetics_batch(estimators: Sequence[CheetahEstimator], init_torques
     cpe_posterior_samples and one cpe_force_samples (ragged: cpe_force_samples_ragged) call per group, same bit-equality of est.samples and
     samples.npz.
     track_weights / track_scale: as in estimate_kinetics; "posterior" makes ONE cpe_track_precision call per group on the group's handle."""
-    _check_samples(uncertainty, uncertainty_samples)
-    _check_rates(uncertainty, uncertainty_rates)
-    _check_spans(uncertainty, uncertainty_spans)
+    req = posterior_request(uncertainty, uncertainty_ridge, uncertainty_rates, uncertainty_spans, uncertainty_samples, uncertainty_seed)
     _check_track_weights(track_weights, track_scale, use_2d_reprojections)
-    if uncertainty and not use_2d_reprojections:
-        raise NotImplementedError("uncertainty together with use_2d_reprojections=False: cpe_covariance_kinetic takes the reprojection cost; the covariance "
-                                  "of the 3D kinematic cost (cpe_solve_kinetic_tracked) is not built")
+    _check_tracked_uncertainty(req, use_2d_reprojections)
     ests = list(estimators)
-    spans = [resolve_spans(uncertainty_spans, e.params.end_frame - e.params.start_frame) for e in ests]      # (a bad pair: before any solve)
+    spans = _spans_of(req, ests)
     out: List[Optional[bool]] = [None] * len(ests)
     groups: Dict[tuple, List[int]] = {}
     prepared = {}
     for i, est in enumerate(ests):
         p = _kinetic_prepare(est, auto, use_2d_reprojections, init_prev_kinematic_solution, synthesised_grf, no_slip, joint_estimation, fix_grf,
                              ground_constraint, disable_pose_prior, disable_motion_prior, out_dir_prefix,
-                             None if options is None else _copy_options(options), None if kinetic_options is None else _copy_kinetic_options(kinetic_options),
+                             None if options is None else _struct_copy(options), None if kinetic_options is None else _struct_copy(kinetic_options),
                              track_weights=track_weights, track_scale=track_scale)
         prepared[i] = p
         if ragged:
@@ -1902,105 +1903,36 @@ def estimate_kinetics_batch(estimators: Sequence[CheetahEstimator], init_torques
             key = (_kinetic_model_bytes(est, p), p["N"], None if p["pri"] is None else _struct_bytes(p["pri"]), p["variant"], est.device, p["tracked"],
                    p["weighted"])
         groups.setdefault(key, []).append(i)
-    if uncertainty:                                  # what is refused, before anything is solved
+    if req is not None:                              # what is refused, before anything is solved
         for idx in groups.values():
-            _lib.covariance_supported(prepared[idx[0]]["pri"], uncertainty_ridge)
+            _lib.covariance_supported(prepared[idx[0]]["pri"], req.ridge)
     no_factor: List[CheetahEstimator] = []
     for idx in groups.values():
-        (_solve_kinetic_ragged_group if ragged else _solve_kinetic_group)(ests, idx, prepared, out, solver_output, out_fname, out_dir_prefix,
-                                                                          uncertainty_ridge if uncertainty else None, no_factor, uncertainty_rates,
-                                                                          None if uncertainty_spans is None else [spans[i] for i in idx],
-                                                                          (uncertainty_samples, uncertainty_seed))
+        _solve_kinetic_group(ests, idx, prepared, out, ragged, req, spans, (solver_output, out_fname, out_dir_prefix), no_factor)
     if no_factor:
-        raise _lib.CpeError(_no_factor_reason(uncertainty_ridge, [f"{e.name} {e.data_path}" for e in no_factor]))
+        raise _lib.CpeError(_no_factor_reason(req.ridge, [f"{e.name} {e.data_path}" for e in no_factor]))
     return [bool(v) for v in out]
 
 
-def _batch_kinetic_uncertainty(res: dict, idx, ridge: Optional[float], covariance) -> Dict[int, KineticUncertainty]:
-    """uncertainty of every sequence of a solved group, keyed by its place b in the group (empty: not asked for).  covariance(conv): ONE
-    covariance call over the places `conv` of the group, those whose solve converged; the others get nothing, as in _kinetic_uncertainty."""
-    if ridge is None:
-        return {}
-    unc = {b: KineticUncertainty() for b in range(len(idx))}
-    conv = [b for b in range(len(idx)) if res["stats"][b].status == abi.OK]
-    if conv:
-        cov = covariance(conv)
-        for k, b in enumerate(conv):
-            unc[b] = _kinetic_uncertainty_of(cov, k, ridge, _kinetic_one(res, b))
-    return unc
-
-
-def _solve_kinetic_group(ests, idx, prepared, out, solver_output, out_fname, out_dir_prefix, uncertainty_ridge: Optional[float] = None,
-                         no_factor: Optional[list] = None, uncertainty_rates: bool = False, spans=None, samples: Tuple[int, int] = (0, 0)) -> None:
-    """estimate_kinetics_batch(ragged=False) for one group: one handle, one solve_kinetic_host call with B = the group's size (and, with
-    uncertainty_ridge, one covariance_kinetic_host call; with samples = (uncertainty_samples, uncertainty_seed) the draws and their forces)"""
-    e0, p0 = ests[idx[0]], prepared[idx[0]]
-    stack = lambda k: None if p0[k] is None else np.stack([prepared[i][k] for i in idx])
-    h = _lib.Handle(p0["skeleton"], e0.cams, p0["opts"], p0["pri"], device=e0.device)
+def _solve_kinetic_group(ests, idx, prepared, out, ragged: bool, req: Optional[PosteriorRequest], spans: Optional[list], finish: tuple,
+                         no_factor: Optional[list] = None) -> None:
+    """estimate_kinetics (the group of one) and estimate_kinetics_batch for one group, plain (one model and length: ONE solve call with B = the
+    group's size) or ragged (one model per distinct (skeleton, rig, options, kinetic options): ONE ragged solve call): _kinetic_solve, with req
+    ONE posterior chain on the same handle over the converged sequences (_batch_kinetic_uncertainty), then every sequence's centre of mass,
+    costs and files through _kinetic_finish(..., *finish, its uncertainty, no_factor).  spans: the resolved spans of ALL estimators, or None."""
+    seqs, preps = [ests[i] for i in idx], [prepared[i] for i in idx]
+    hs = _GroupHandles([(p["skeleton"], e.cams, p["opts"]) for e, p in zip(seqs, preps)], preps[0]["pri"], seqs[0].device,
+                       [_kinetic_model_bytes(e, p) for e, p in zip(seqs, preps)] if ragged else None)
     try:
         t0 = time()
-        res = _kinetic_solve(h, [prepared[i] for i in idx], [ests[i] for i in idx])
+        res = _kinetic_solve(hs.solve, preps, seqs, hs.of)
         dt = (time() - t0) / len(idx)                                                # processing_time_s of a sequence: its share of the batched solve
-        cut = lambda a, conv: None if a is None else a[conv]
-
-        def covariance(conv):
-            a = (res["q"][conv], np.stack([ests[idx[b]].meas for b in conv]), np.stack([ests[idx[b]].weight for b in conv]), stack("stance")[conv], p0["ko"])
-            force = dict(grf_fixed=cut(stack("grf_fixed"), conv), grf_box=cut(stack("grf_box"), conv))
-            cov = h.covariance_kinetic_host(*a, uncertainty_ridge, want_L=spans is not None or samples[0] > 0, **force)
-            cov = _with_rates(h, cov, a[0], uncertainty_rates, spans=None if spans is None else [spans[b] for b in conv])
-            cov = _with_samples(h, cov, a[0], samples[0], samples[1])
-            return _with_force_samples(cov, samples[0], samples[1], lambda du, zeta, lens: h.force_samples_host(*a, du, zeta, uncertainty_ridge, **force))
-
-        unc = _batch_kinetic_uncertainty(res, idx, uncertainty_ridge, covariance)
+        unc = _batch_kinetic_uncertainty(hs.solve, req, None if spans is None else [spans[i] for i in idx], res, preps, [e.meas for e in seqs],
+                                         [e.weight for e in seqs], hs.of)
         for b, i in enumerate(idx):
-            out[i] = _kinetic_finish(ests[i], h, _kinetic_one(res, b), dt, prepared[i], solver_output, out_fname, out_dir_prefix, unc.get(b), no_factor)
+            out[i] = _kinetic_finish(ests[i], hs.fk(b), _sequence_of(res, b), dt, preps[b], *finish, unc.get(b), no_factor)
     finally:
-        h.close()
-
-
-def _solve_kinetic_ragged_group(ests, idx, prepared, out, solver_output, out_fname, out_dir_prefix, uncertainty_ridge: Optional[float] = None,
-                                no_factor: Optional[list] = None, uncertainty_rates: bool = False, spans=None,
-                                samples: Tuple[int, int] = (0, 0)) -> None:
-    """estimate_kinetics_batch(ragged=True) for one group: one model per distinct (skeleton, rig, options, kinetic options), one
-    cpe_solve_kinetic_ragged call (and, with uncertainty_ridge, one cpe_covariance_kinetic_ragged call on the same handle), then every sequence's
-    centre of mass, costs and files through _kinetic_finish with a plain handle of its model"""
-    models: Dict[bytes, int] = {}
-    of = [models.setdefault(_kinetic_model_bytes(ests[i], prepared[i]), len(models)) for i in idx]
-    first = {}
-    for b, i in enumerate(idx):
-        first.setdefault(of[b], i)
-    reps = [first[k] for k in range(len(models))]
-    p0, dev = prepared[idx[0]], ests[idx[0]].device
-    h = _lib.Handle.multi([prepared[i]["skeleton"] for i in reps], [ests[i].cams for i in reps], [prepared[i]["opts"] for i in reps], p0["pri"], device=dev)
-    fk = {}
-    try:
-        force = "grf_fixed" if p0["variant"] == "fixed" else ("grf_box" if p0["variant"] == "force_box" else None)
-        t0 = time()
-        fkw = {} if force is None else {force: [prepared[i][force] for i in idx]}
-        res = _kinetic_solve(h, [prepared[i] for i in idx], [ests[i] for i in idx], of)
-        dt = (time() - t0) / len(idx)                                                # processing_time_s of a sequence: its share of the batched solve
-        def covariance(conv):
-            a = ([res["q"][b] for b in conv], [ests[idx[b]].meas for b in conv], [ests[idx[b]].weight for b in conv],
-                 [prepared[idx[b]]["stance"] for b in conv], [prepared[i]["ko"] for i in reps])
-            ofc, force = [of[b] for b in conv], {k: [v[b] for b in conv] for k, v in fkw.items()}
-            cov = h.covariance_kinetic_ragged_host(*a, ofc, uncertainty_ridge, want_L=spans is not None or samples[0] > 0, **force)
-            cov = _with_rates(h, cov, a[0], uncertainty_rates, ofc, None if spans is None else [spans[b] for b in conv])
-            cov = _with_samples(h, cov, a[0], samples[0], samples[1], ofc)
-            cuts = lambda v, lens: [np.ascontiguousarray(v[b, :, :n]) for b, n in enumerate(lens)]
-            return _with_force_samples(cov, samples[0], samples[1], lambda du, zeta, lens: h.force_samples_ragged_host(
-                *a, cuts(du, lens), cuts(zeta, lens), ofc, uncertainty_ridge, **force)["padded"])
-
-        unc = _batch_kinetic_uncertainty(res, idx, uncertainty_ridge, covariance)
-        for b, i in enumerate(idx):
-            if of[b] not in fk:
-                r = reps[of[b]]
-                fk[of[b]] = _lib.Handle(prepared[r]["skeleton"], ests[r].cams, prepared[r]["opts"], None, device=dev)
-            out[i] = _kinetic_finish(ests[i], fk[of[b]], _kinetic_one(res, b), dt, prepared[i], solver_output, out_fname, out_dir_prefix, unc.get(b),
-                                     no_factor)
-    finally:
-        h.close()
-        for f in fk.values():
-            f.close()
+        hs.close()
 
 
 def bound_value(val, slack_percentage: float) -> np.ndarray:
@@ -2031,11 +1963,9 @@ def estimate_grf(estimator: CheetahEstimator, solver_output: bool = True, out_di
     uncertainty_spans (with uncertainty=True): the span fields of estimate_kinematics (SPAN_FIELDS), from that covariance.
     uncertainty_samples, uncertainty_seed (with uncertainty=True): as in estimate_kinetics (KINETIC_SAMPLE_FIELDS), with the torque boxes of this
     solve; samples.npz goes beside uncertainty.npz."""
-    _check_samples(uncertainty, uncertainty_samples)
-    _check_rates(uncertainty, uncertainty_rates)
-    _check_spans(uncertainty, uncertainty_spans)
+    req = posterior_request(uncertainty, uncertainty_ridge, uncertainty_rates, uncertainty_spans, uncertainty_samples, uncertainty_seed)
     est, params, scene, sk = estimator, estimator.params, estimator.scene, estimator.skeleton
-    spans = resolve_spans(uncertainty_spans, params.end_frame - params.start_frame)
+    spans = None if req is None else req.spans_for(params.end_frame - params.start_frame)
     assert params.kinetic_dataset, "Cannot determine GRF on a dataset other than the kinetic dataset from Penny Hudson and Co."
     if est.kinematic_model:
         raise AssertionError("Dynamic model of the cheetah is required.")
@@ -2077,25 +2007,18 @@ def estimate_grf(estimator: CheetahEstimator, solver_output: bool = True, out_di
     if est.bound_eom_error is not None:
         ko.slack_lo, ko.slack_hi = float(est.bound_eom_error[0]), float(est.bound_eom_error[1])      # make_pyomo_model(bound_eom_error=...), acinoset_opt.py:510-514
     skk = skeleton.without_motion_model(sk)
-    if uncertainty:
-        _lib.covariance_supported(None, uncertainty_ridge)                 # raises with the library's reason (negative or non-finite ridge)
+    if req is not None:
+        _lib.covariance_supported(None, req.ridge)                         # raises with the library's reason (negative or non-finite ridge)
     h = _lib.Handle(skk, est.cams, opts, None, device=est.device)
     unc = None
     try:
         t0 = time()
         res = h.solve_kinetic_host(ko, q_init[None], est.meas[None], est.weight[None], stance[None], tau_box=tau_box[None])
         est.opt_time_s = time() - t0
-        if uncertainty:
-            unc = _kinetic_uncertainty(h, ko, res, est.meas, est.weight, stance, uncertainty_ridge, tau_box=tau_box, rates=uncertainty_rates, spans=spans,
-                                       samples=(uncertainty_samples, uncertainty_seed))
+        if req is not None:
+            unc = _kinetic_uncertainty(h, ko, res, est.meas, est.weight, stance, req, spans, tau_box=tau_box)
             unc.samples = _complete_samples(est, h, unc.samples)
-        import torch
-        dev = torch.device("cuda", est.device)
-        qd = torch.tensor(res["q"], device=dev)
-        pos = torch.empty((1, N, 24, 3), dtype=torch.float64, device=dev); com = torch.empty((1, N, 3), dtype=torch.float64, device=dev)
-        h.forward_kinematics(qd, pos, com); h.synchronize()
-        est.com_pos = com[0].cpu().numpy()
-        est.com_vel = (est.com_pos[1:] - est.com_pos[:-1]) * scene.fps
+        _store_com(est, h, res["q"])
     finally:
         h.close()
     st, ks = res["stats"][0], res["kstats"][0]

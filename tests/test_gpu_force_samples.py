@@ -324,7 +324,8 @@ def test_estimator_torque_box_samples(oracle, gpu_handle_factory):
     K, seed = 3, 7
     nm, nf = c["ko"].dyn.n_motors, c["ko"].dyn.n_feet
     res = dict(q=c["q"][None], stats=[SimpleNamespace(status=abi.OK)], tau=np.zeros((1, N, nm)), lam=np.zeros((1, N, 26)), grf=np.zeros((1, N, nf, 5)))
-    unc = E._kinetic_uncertainty(h, c["ko"], res, c["meas"], c["weight"], c["stance"], 0.0, tau_box=c["var"]["tau_box"], samples=(K, seed))
+    req = E.PosteriorRequest(ridge=0.0, samples=K, seed=seed)
+    unc = E._kinetic_uncertainty(h, c["ko"], res, c["meas"], c["weight"], c["stance"], req, tau_box=c["var"]["tau_box"])
     assert unc.reason is None and unc.fields is not None and unc.samples is not None
     sm = unc.samples
     du = h.band_sample_host(cov["L"], E.sample_normals(seed, K, N)[None])[0]
