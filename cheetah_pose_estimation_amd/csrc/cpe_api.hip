@@ -883,10 +883,11 @@ cpe_status cpe_eval_resjac(cpe_handle* h, int32_t B, int32_t N, const double* q,
 }
 
 cpe_status cpe_project_joints(cpe_handle* h, int32_t B, int32_t N, double* q) {
-    if (!h || !q) return fail(CPE_BAD_ARG, "null argument");
+    if (!h) return fail(CPE_BAD_ARG, "null argument");
     size_t F;
     if (cpe_status s = frames(B, N, &F); s != CPE_OK) return s;
-    if (F == 0) return CPE_OK;
+    if (F == 0) return CPE_OK;                      // empty batch: q may be null
+    if (!q) return fail(CPE_BAD_ARG, "null argument");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipMemsetAsync(h->flag, 0, sizeof(int), h->stream));
     hipLaunchKernelGGL(k_project, dim3((unsigned)F), dim3(WAVE), sizeof(double) * (h->hm.nq + 6 * h->hm.nl), h->stream, h->dm, q, h->flag);

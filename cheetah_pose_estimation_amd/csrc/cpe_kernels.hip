@@ -81,6 +81,8 @@ __device__ __forceinline__ void hooke_roll(const double* a, double st, double ct
 // band |cos(theta)| < |a_z| where the equalities have no solution.
 __device__ __forceinline__ int wave_project_joints(const DevModel* __restrict__ M, double* sq, double* ssc, int lane, bool hooke_only = false) {
     int clamped = 0;
+    double psi0 = 0.0;          // a revolute child's psi as the closed form gives it, before the whole turns towards its parent's psi
+    bool rev = false;
     for (int level = 0; level < 2; level++) {
         if (lane < M->nj && !(hooke_only && M->joint_kind[lane] == CPE_JOINT_REVOLUTE_Y)) {
             const int kind = M->joint_kind[lane], p = M->joint_parent[lane], c = M->joint_child[lane];
@@ -94,13 +96,10 @@ __device__ __forceinline__ int wave_project_joints(const DevModel* __restrict__ 
                     if (sphi > 1.0) { sphi = 1.0; clamped = 1; }
                     if (sphi < -1.0) { sphi = -1.0; clamped = 1; }
                     const double cphi = sqrt(fmax(0.0, 1.0 - sphi * sphi));
-                    double psi = atan2(a[1], a[0]) - atan2(cphi, sphi * st);
-                    const double ref = sq[3 + 3 * p + 2];
-                    psi += 6.283185307179586476925286766559 * rint((ref - psi) / 6.283185307179586476925286766559);
-                    sq[3 + 3 * c] = asin(sphi); sq[3 + 3 * c + 2] = psi;
+                    psi0 = atan2(a[1], a[0]) - atan2(cphi, sphi * st);
+                    rev = true;
+                    sq[3 + 3 * c] = asin(sphi);
                     ssc[6 * c] = sphi; ssc[6 * c + 1] = cphi;
-                    double s, co; sincos(psi, &s, &co);
-                    ssc[6 * c + 4] = s; ssc[6 * c + 5] = co;
                 } else {
                     rot_ycol(ssc + 6 * p, a);
                     double phi, sphi, cphi;
@@ -108,6 +107,30 @@ __device__ __forceinline__ int wave_project_joints(const DevModel* __restrict__ 
                     sq[3 + 3 * c] = phi;
                     ssc[6 * c] = sphi; ssc[6 * c + 1] = cphi;
                 }
+            }
+        }
+        if (level == 0) {
+            // whole turns of every revolute child's psi towards its parent's psi.  The parent may be a revolute child of this very pass
+            // (hock -> calf -> thigh -> body) whose psi another lane is writing, so the turns are taken again until no psi moves: each
+            // child then has seen its parent's final psi, as if the joints had been walked parents first (chain depth + 1 rounds).
+            // Every round reads in all lanes before any lane writes.
+            const int c = rev ? M->joint_child[lane] : 0, p = rev ? M->joint_parent[lane] : 0;
+            for (int round = 0; round <= CPE_MAX_JOINTS; round++) {
+                wave_lds_sync();
+                double psi = 0.0;
+                bool moved = false;
+                if (rev) {
+                    const double ref = sq[3 + 3 * p + 2];
+                    psi = psi0 + 6.283185307179586476925286766559 * rint((ref - psi0) / 6.283185307179586476925286766559);
+                    moved = psi != sq[3 + 3 * c + 2];
+                }
+                wave_lds_sync();
+                if (moved) sq[3 + 3 * c + 2] = psi;
+                if (!__any(moved)) break;
+            }
+            if (rev) {
+                double s, co; sincos(sq[3 + 3 * c + 2], &s, &co);
+                ssc[6 * c + 4] = s; ssc[6 * c + 5] = co;
             }
         }
         wave_lds_sync();
@@ -635,39 +658,40 @@ __global__ __launch_bounds__(256) void k_triangulate(const DevModel* __restrict_
         double xb, yb;
         undistort_pixel(cb, uv_b[2 * i], uv_b[2 * i + 1], xb, yb);
         // rows of A: x P[2] - P[0], y P[2] - P[1] for both views, P = [R | t]; the solution is the right singular vector of
-        // the smallest singular value = eigenvector of the smallest eigenvalue of A^T A (cyclic Jacobi, 4 x 4)
-        double A[4][4];
+        // the smallest singular value.  One-sided (Hestenes) cyclic Jacobi on A itself: pairs of columns of A V are rotated until they are
+        // orthogonal; the column of the smallest norm then belongs to the smallest singular value.  (Jacobi on A^T A squares the
+        // condition number: at baseline / depth 1e-3 it lost three to four digits against the SVD, tests/test_gpu_ingest_output.py.)
+        double A[4][4], V[4][4];
         for (int k = 0; k < 4; k++) {
             const double a0 = k < 3 ? ca.R[k] : ca.t[0], a1 = k < 3 ? ca.R[3 + k] : ca.t[1], a2 = k < 3 ? ca.R[6 + k] : ca.t[2];
             const double b0 = k < 3 ? cb.R[k] : cb.t[0], b1 = k < 3 ? cb.R[3 + k] : cb.t[1], b2 = k < 3 ? cb.R[6 + k] : cb.t[2];
             A[0][k] = xa * a2 - a0; A[1][k] = ya * a2 - a1; A[2][k] = xb * b2 - b0; A[3][k] = yb * b2 - b1;
         }
-        double S[4][4], V[4][4];
         for (int r = 0; r < 4; r++)
-            for (int c = 0; c < 4; c++) {
-                S[r][c] = A[0][r] * A[0][c] + A[1][r] * A[1][c] + A[2][r] * A[2][c] + A[3][r] * A[3][c];
-                V[r][c] = r == c ? 1.0 : 0.0;
-            }
+            for (int c = 0; c < 4; c++) V[r][c] = r == c ? 1.0 : 0.0;
         for (int sweep = 0; sweep < 12; sweep++)
 #pragma unroll
             for (int p = 0; p < 3; p++)
 #pragma unroll
                 for (int q = p + 1; q < 4; q++) {
-                    const double apq = S[p][q];
-                    if (fabs(apq) < 1e-300) continue;
-                    const double tau = (S[q][q] - S[p][p]) / (2.0 * apq);
+                    double al = 0.0, be = 0.0, ga = 0.0;
+#pragma unroll
+                    for (int k = 0; k < 4; k++) { al += A[k][p] * A[k][p]; be += A[k][q] * A[k][q]; ga += A[k][p] * A[k][q]; }
+                    if (fabs(ga) < 1e-300) continue;
+                    const double tau = (be - al) / (2.0 * ga);
                     const double t = (tau >= 0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
                     const double cs = 1.0 / sqrt(1.0 + t * t), sn = t * cs;
 #pragma unroll
-                    for (int k = 0; k < 4; k++) { const double skp = S[k][p], skq = S[k][q]; S[k][p] = cs * skp - sn * skq; S[k][q] = sn * skp + cs * skq; }
-#pragma unroll
-                    for (int k = 0; k < 4; k++) { const double spk = S[p][k], sqk = S[q][k]; S[p][k] = cs * spk - sn * sqk; S[q][k] = sn * spk + cs * sqk; }
+                    for (int k = 0; k < 4; k++) { const double akp = A[k][p], akq = A[k][q]; A[k][p] = cs * akp - sn * akq; A[k][q] = sn * akp + cs * akq; }
 #pragma unroll
                     for (int k = 0; k < 4; k++) { const double vkp = V[k][p], vkq = V[k][q]; V[k][p] = cs * vkp - sn * vkq; V[k][q] = sn * vkp + cs * vkq; }
                 }
+        double nrm[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) nrm[k] = A[0][k] * A[0][k] + A[1][k] * A[1][k] + A[2][k] * A[2][k] + A[3][k] * A[3][k];
         int m = 0;
 #pragma unroll
-        for (int k = 1; k < 4; k++) if (S[k][k] < S[m][m]) m = k;
+        for (int k = 1; k < 4; k++) if (nrm[k] < nrm[m]) m = k;
         double h[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) h[k] = m == 0 ? V[k][0] : m == 1 ? V[k][1] : m == 2 ? V[k][2] : V[k][3];
