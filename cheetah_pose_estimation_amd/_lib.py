@@ -1015,6 +1015,86 @@ class Handle:
         out.update(status=st, seq_status=list(seq)[:B])
         return out
 
+    # ---- the pose covariance marginalised over the scales (include/cpe.h, cpe_scale_response / cpe_covariance_add_scales) ------------------
+    def scale_response(self, q, meas, weight, d_attach, d_marker_off, A_red, resp_u, resp_pos=None, ridge=0.0, model=None, n_frames=None):
+        """cpe_scale_response on device tensors: scale_system's inputs -> A_red [B, G, G] (scale_system's, bit for bit), resp_u [B, N, 28, G] =
+        du / ds of the re-adapted poses, resp_pos [B, N, L, 3, G] = d p / d s in total (or None).  Returns (status, [status of every sequence])."""
+        B, N = q.shape[0], q.shape[1]
+        G, da, dm = self._scale_tables("scale_response", d_attach, d_marker_off)
+        if (model is None) != (n_frames is None):
+            raise ValueError("scale_response: model and n_frames are given together or not at all")
+        mo = nf = None
+        if model is not None:
+            if len(model) != B or len(n_frames) != B:
+                raise ValueError("scale_response: one model index and one frame count per sequence")
+            mo, nf = _int32s(B, model), _int32s(B, n_frames)
+        for name, t, shape in (("A_red", A_red, (B, G, G)), ("resp_u", resp_u, (B, N, 28, G)), ("resp_pos", resp_pos, (B, N, self.L, 3, G))):
+            if name == "resp_pos" and t is None:
+                continue
+            if t is None or tuple(t.shape) != shape or t.element_size() != 8 or not t.dtype.is_floating_point or not t.is_contiguous():
+                raise ValueError(f"scale_response: {name} is a contiguous float64 tensor of shape {shape}")
+        seq = _int32s(B)
+        st = self._call(self.lib.cpe_scale_response, "cpe_scale_response", B, N, mo, nf, _ptr(q), _ptr(meas), _ptr(weight), float(ridge), G, _ptr(da),
+                        _ptr(dm), _ptr(A_red), _ptr(resp_u), _ptr(resp_pos), seq, allow=(abi.OK, abi.NUMERICAL))
+        return st, list(seq)[:B]
+
+    def scale_response_host(self, q, meas, weight, d_attach, d_marker_off, ridge=0.0, model_list=None, want_pos=True):
+        """cpe_scale_response_host: q [B, N, nq], meas, weight numpy -> dict(A_red [B, G, G], resp_u [B, N, 28, G], resp_pos [B, N, L, 3, G] or
+        None, status, seq_status); or, for sequences of their own length and model (lists, as scale_system_host takes them), ONE ragged call:
+        resp_u and resp_pos are then lists of [N_b, ...] and `padded` holds the padded arrays and `lens` the lengths"""
+        ragged = isinstance(q, (list, tuple))
+        if ragged:
+            p = self._ragged_batch("scale_response_host", "one q, meas, weight and model", model_list, q_init=q, meas=meas, weight=weight)
+            qp, mp, wp, mo, nf = p["q_init"], p["meas"], p["weight"], p["model_arr"], p["len_arr"]
+        else:
+            qp, mp, wp, mo, nf = _f64(q), _f64(meas), _f64(weight), None, None
+        B, N = qp.shape[:2]
+        G, da, dm = self._scale_tables("scale_response_host", d_attach, d_marker_off)
+        out = dict(A_red=np.empty((B, G, G)), resp_u=np.empty((B, N, 28, G)), resp_pos=np.empty((B, N, self.L, 3, G)) if want_pos else None)
+        seq = _int32s(B)
+        st = self.lib.cpe_scale_response_host(self._h, B, N, mo, nf, _ptr(qp), _ptr(mp), _ptr(wp), float(ridge), G, _ptr(da), _ptr(dm),
+                                              _ptr(out["A_red"]), _ptr(out["resp_u"]), _ptr(out["resp_pos"]), seq)
+        _check(st, "cpe_scale_response_host", allow=(abi.OK, abi.NUMERICAL))
+        if ragged:
+            pad = dict(resp_u=out["resp_u"], resp_pos=out["resp_pos"])
+            out.update(unpad_kinetic(pad, p["lens"], p["cams"]), padded=pad, lens=list(p["lens"]))
+        out.update(status=st, seq_status=list(seq)[:B])
+        return out
+
+    def _add_scales_args(self, who, cov_s, resp_u, n_frames):
+        """B, N, G and the host array n_frames [B] (or None = all N) of an add_scales call, from the shapes of resp_u and cov_s"""
+        if len(resp_u.shape) != 4 or resp_u.shape[2] != 28 or tuple(cov_s.shape) != (resp_u.shape[0], resp_u.shape[3], resp_u.shape[3]):
+            raise ValueError(f"{who}: resp_u is [B, N, 28, G] and cov_s [B, G, G]")
+        B, N, G = int(resp_u.shape[0]), int(resp_u.shape[1]), int(resp_u.shape[3])
+        nf = None if n_frames is None else np.ascontiguousarray(n_frames, dtype=np.int32)
+        if nf is not None and nf.shape != (B,):
+            raise ValueError(f"{who}: one frame count per sequence")
+        return B, N, G, nf, None if nf is None else nf.ctypes.data_as(ip)
+
+    def covariance_add_scales(self, cov_s, resp_u, resp_pos, cov_diag, cov_off, cov_pos, cov_diag_m, cov_off_m, cov_pos_m, n_frames=None):
+        """cpe_covariance_add_scales on device tensors: cov_s [B, G, G], scale_response's resp_u and resp_pos, a covariance entry's cov_diag,
+        cov_off and cov_pos -> the same three with the scale terms added (resp_pos, cov_pos and cov_pos_m: all three or None).  n_frames [B] on
+        the host (or None = all N)"""
+        B, N, G, _nf, pn = self._add_scales_args("covariance_add_scales", cov_s, resp_u, n_frames)
+        self._call(self.lib.cpe_covariance_add_scales, "cpe_covariance_add_scales", B, N, pn, G, _ptr(cov_s), _ptr(resp_u), _ptr(resp_pos), _ptr(cov_diag),
+                   _ptr(cov_off), _ptr(cov_pos), _ptr(cov_diag_m), _ptr(cov_off_m), _ptr(cov_pos_m))
+
+    def covariance_add_scales_host(self, cov_s, resp_u, resp_pos, cov_diag, cov_off, cov_pos, n_frames=None):
+        """cpe_covariance_add_scales_host: numpy in (padded arrays [B, N, ...]; resp_pos and cov_pos both None or both given), dict(cov_diag,
+        cov_off, cov_pos or None) out: the marginal band and marker covariances"""
+        cov_s, resp_u, cov_diag, cov_off = _f64(cov_s), _f64(resp_u), _f64(cov_diag), _f64(cov_off)
+        resp_pos, cov_pos = _f64(resp_pos, True), _f64(cov_pos, True)
+        B, N, G, _nf, pn = self._add_scales_args("covariance_add_scales_host", cov_s, resp_u, n_frames)
+        if cov_diag.shape != (B, N, 28, 28) or cov_off.shape != (B, N, self.pb, 28, 28):
+            raise ValueError(f"covariance_add_scales_host: cov_diag / cov_off do not have the shapes of the handle's half-bandwidth {self.pb}")
+        if (resp_pos is None) != (cov_pos is None) or (cov_pos is not None and (cov_pos.shape != (B, N, self.L, 3, 3) or resp_pos.shape != (B, N, self.L, 3, G))):
+            raise ValueError("covariance_add_scales_host: resp_pos [B, N, L, 3, G] and cov_pos [B, N, L, 3, 3] are given together or not at all")
+        out = dict(cov_diag=np.empty_like(cov_diag), cov_off=np.empty_like(cov_off), cov_pos=None if cov_pos is None else np.empty_like(cov_pos))
+        _check(self.lib.cpe_covariance_add_scales_host(self._h, B, N, pn, G, _ptr(cov_s), _ptr(resp_u), _ptr(resp_pos), _ptr(cov_diag), _ptr(cov_off),
+                                                       _ptr(cov_pos), _ptr(out["cov_diag"]), _ptr(out["cov_off"]), _ptr(out["cov_pos"])),
+               "cpe_covariance_add_scales_host")
+        return out
+
     # ---- posterior covariance of the rates (include/cpe.h, cpe_rate_covariance) -----------------------------------------------------------
     def rate_covariance(self, q, cov_diag, cov_off, cov_du=None, cov_ddu=None, cov_vel=None, cov_com=None, cov_com_vel=None, jac_pos=None,
                         jac_com=None):

@@ -235,6 +235,16 @@ SCALE_ENTRIES = {
     "cpe_scale_system": _SCALE_SYSTEM,
     "cpe_scale_system_host": _SCALE_SYSTEM,
 }
+# the pose covariance marginalised over the scales (cpe_scale_response: cpe_scale_system's inputs | A_red, resp_u, resp_pos | status;
+# cpe_covariance_add_scales: h, B, N | n_frames | G | cov_s, resp_u, resp_pos | cov_diag, cov_off, cov_pos | cov_diag_m, cov_off_m, cov_pos_m)
+_SCALE_RESPONSE = _BN + _RAGGED + ("p", "p", "p", "d", "i", "p", "p") + ("p",) * 3 + ("ip",)
+_ADD_SCALES = _BN + ("ip", "i") + ("p",) * 9
+SCALE_RESPONSE_ENTRIES = {
+    "cpe_scale_response": _SCALE_RESPONSE,
+    "cpe_scale_response_host": _SCALE_RESPONSE,
+    "cpe_covariance_add_scales": _ADD_SCALES,
+    "cpe_covariance_add_scales_host": _ADD_SCALES,
+}
 COVARIANCE_MAX_PB = 4        # largest half-bandwidth (frames) the covariance sweep supports: motion-prior windows 5 and 6 are refused
 ENTRIES = {
     "cpe_create": ("sk", "cam", "i", "op", "pr", "i", "hp"),
@@ -301,7 +311,7 @@ ENTRIES = {
     "cpe_eval_active_list": ("h", "i", "i", "ip", "ip", "ip"),         # B, window | status | act, n_act (host)
     **COVARIANCE_ENTRIES, **KINETIC_COVARIANCE_ENTRIES, **KINETIC_COVARIANCE_RAGGED_ENTRIES, **RATE_COVARIANCE_ENTRIES,
     **{name: _COLUMNS for name in COLUMN_COVARIANCE_ENTRIES}, **SAMPLE_ENTRIES, **FORCE_SAMPLE_ENTRIES,
-    **SCALE_ENTRIES,
+    **SCALE_ENTRIES, **SCALE_RESPONSE_ENTRIES,
 }
 
 

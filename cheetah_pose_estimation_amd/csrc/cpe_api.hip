@@ -2705,6 +2705,10 @@ static_assert(sizeof(double) * (CPE_MAX_NQ + LM_MAX_REV + 6 * CPE_MAX_LINKS + 2 
                                 2 * 3 * CPE_MAX_MARKERS * CPE_MAX_SCALES) +
                   sizeof(int) * (CPE_MAX_MARKERS * CPE_NX + CPE_MAX_MARKERS * CPE_MAX_MCOL) <= 65536, "k_scale_cross: dynamic LDS within the default limit");
 
+// k_scale_points (cpe_scale_cov.hip.inc) adds R_n [28][G] behind that carve, after an int of padding: 60 892 B at every limit
+static size_t lds_scale_points(const DevModel& m, int G) { return lds_scale(m, G) + sizeof(int) + sizeof(double) * (size_t)(CPE_NX * G); }
+static_assert(57304 + sizeof(int) + sizeof(double) * CPE_NX * CPE_MAX_SCALES <= 65536, "k_scale_points: dynamic LDS within the default limit");
+
 // What both forms refuse, before the device is touched and in this order -- what needs no handle first: G outside 1..CPE_MAX_SCALES, a negative
 // or non-finite ridge, negative sizes, model without n_frames or the reverse, a frame count outside 1..N, a null handle or array; then a
 // half-bandwidth above 4 and a model index out of range.  Fills F and, for the ragged form, the table.
@@ -2723,14 +2727,20 @@ static cpe_status scale_check(const char* who, const cpe_handle* h, int32_t B, i
     return CPE_OK;
 }
 
-// the device entry after its checks: q .. cost are device pointers, d_attach / d_marker_off / status host
+// the device entry after its checks: q .. cost are device pointers, d_attach / d_marker_off / status host.  cpe_scale_system: resp_u and resp_pos
+// null.  cpe_scale_response: A, bvec, b_red and cost null (scratch here), resp_u given and resp_pos given or null; k_band_forward then leaves -Y_E as
+// well, the factor goes to the plain layout (k_cov_export), k_band_sample solves L^T X = -Y_E for the G columns and k_scale_points forms resp_u and
+// resp_pos.
 static cpe_status scale_launch(cpe_handle* h, int32_t B, int32_t N, size_t F, const std::vector<int2>& seq, const double* q, const double* meas,
                                const double* weight, double ridge, int32_t G, const double* d_attach, const double* d_marker_off, double* A,
-                               double* bvec, double* A_red, double* b_red, double* cost, cpe_status* status) {
+                               double* bvec, double* A_red, double* b_red, double* cost, cpe_status* status, double* resp_u = nullptr,
+                               double* resp_pos = nullptr) {
     const bool ragged = !seq.empty();
     const int nm = n_models(h), L = h->hm.L, nl = h->hm.nl;
     size_t lds = 0;
     for (int k = 0; k < nm; k++) lds = std::max(lds, lds_scale(h->models.empty() ? h->hm : h->models[k], G));
+    size_t lds_pts = 0;
+    for (int k = 0; k < nm; k++) lds_pts = std::max(lds_pts, lds_scale_points(h->models.empty() ? h->hm : h->models[k], G));
     cpe_status s = ensure_ws(h, B, N);
     if (s != CPE_OK) return s;
     RaggedArgs rgv;
@@ -2753,9 +2763,21 @@ static cpe_status scale_launch(cpe_handle* h, int32_t B, int32_t N, size_t F, co
     Staging sc(h->stream);
     const double* d_dcv = sc.in(dcv.data(), dcv.size());
     double* rec = sc.alloc<double>(F * SC);
+    const size_t BB = (size_t)CPE_NX * CPE_NX, FG = F * (size_t)G * CPE_NX;
+    double *Yneg = nullptr, *X = nullptr, *Lp = nullptr;
+    int* d_len = nullptr;
+    if (resp_u) {
+        A = sc.alloc<double>((size_t)B * G * G); bvec = sc.alloc<double>((size_t)B * G); b_red = sc.alloc<double>((size_t)B * G); cost = sc.alloc<double>(B);
+        Yneg = sc.alloc<double>(FG); X = sc.alloc<double>(FG); Lp = sc.alloc<double>(F * (h->pb + 1) * BB); d_len = sc.alloc<int>(B);
+    }
     HIPCHK(sc.err);
     const size_t w = sizeof(double);
     // a sequence without a factor has all outputs zero
+    if (resp_u) {
+        HIPCHK(hipMemsetAsync(resp_u, 0, w * FG, h->stream));
+        if (resp_pos) HIPCHK(hipMemsetAsync(resp_pos, 0, w * F * L * 3 * G, h->stream));
+        HIPCHK(hipMemsetAsync(Yneg, 0, w * FG, h->stream));            // (the frames past a sequence's own: never read, kept defined)
+    }
     HIPCHK(hipMemsetAsync(A, 0, w * B * G * G, h->stream));
     HIPCHK(hipMemsetAsync(A_red, 0, w * B * G * G, h->stream));
     HIPCHK(hipMemsetAsync(bvec, 0, w * B * G, h->stream));
@@ -2768,8 +2790,15 @@ static cpe_status scale_launch(cpe_handle* h, int32_t B, int32_t N, size_t F, co
     with_ragged(rg, [&](auto r, RaggedArgs a) {
         constexpr bool R = decltype(r)::value;
         hipLaunchKernelGGL(k_scale_cross<R>, dim3((unsigned)F), dim3(WAVE), lds, h->stream, h->dm, h->st, N, F, h->qbuf, meas, weight, d_dcv, G, rec, a);
-        if (h->pb == 3) hipLaunchKernelGGL((k_band_forward<3, R>), dim3(B), dim3(WAVE), 0, h->stream, h->st, h->Lbuf, h->gtbuf, h->costbuf, rec, N, F, G, A, bvec, A_red, b_red, cost, a);
-        else hipLaunchKernelGGL((k_band_forward<4, R>), dim3(B), dim3(WAVE), 0, h->stream, h->st, h->Lbuf, h->gtbuf, h->costbuf, rec, N, F, G, A, bvec, A_red, b_red, cost, a);
+        if (h->pb == 3) hipLaunchKernelGGL((k_band_forward<3, R>), dim3(B), dim3(WAVE), 0, h->stream, h->st, h->Lbuf, h->gtbuf, h->costbuf, rec, N, F, G, A, bvec, A_red, b_red, cost, Yneg, a);
+        else hipLaunchKernelGGL((k_band_forward<4, R>), dim3(B), dim3(WAVE), 0, h->stream, h->st, h->Lbuf, h->gtbuf, h->costbuf, rec, N, F, G, A, bvec, A_red, b_red, cost, Yneg, a);
+        if (!resp_u) return;
+        hipLaunchKernelGGL(k_response_lens<R>, dim3((B + WAVE - 1) / WAVE), dim3(WAVE), 0, h->stream, h->st, B, N, d_len, a);
+        hipLaunchKernelGGL(k_cov_export<R>, dim3((unsigned)F), dim3(COV_THREADS), 0, h->stream, h->st, h->Lbuf, Lp, N, (int)((h->pb + 1) * BB), a);
+        // (X needs no zeroing: k_scale_points reads it only where k_band_sample wrote it)
+        if (h->pb == 3) hipLaunchKernelGGL((k_band_sample<3>), dim3(B), dim3(2 * WAVE), 0, h->stream, Lp, Yneg, X, d_len, N, G);
+        else hipLaunchKernelGGL((k_band_sample<4>), dim3(B), dim3(2 * WAVE), 0, h->stream, Lp, Yneg, X, d_len, N, G);
+        hipLaunchKernelGGL(k_scale_points<R>, dim3((unsigned)F), dim3(WAVE), lds_pts, h->stream, h->dm, h->st, N, F, h->qbuf, d_dcv, G, X, resp_u, resp_pos, a);
     });
     HIPCHK(hipGetLastError());
     std::vector<SeqState> hs((size_t)B);
@@ -2815,6 +2844,116 @@ cpe_status cpe_scale_system_host(cpe_handle* h, int32_t B, int32_t N, const int3
     if (s < 0) return s;
     HIPCHK(st.fetch());
     return s;
+}
+
+// ---- the pose covariance marginalised over the scales (include/cpe.h, cpe_scale_response / cpe_covariance_add_scales; kernels in
+// cpe_scale_cov.hip.inc) ---------------------------------------------------------------------------------------------------------------------
+cpe_status cpe_scale_response(cpe_handle* h, int32_t B, int32_t N, const int32_t* model, const int32_t* n_frames, const double* q, const double* meas,
+                              const double* weight, double ridge, int32_t G, const double* d_attach, const double* d_marker_off, double* A_red,
+                              double* resp_u, double* resp_pos, cpe_status* status) {
+    size_t F;
+    std::vector<int2> seq;
+    const bool arrays = q && meas && weight && d_attach && d_marker_off && A_red && resp_u && status;
+    if (cpe_status s = scale_check("cpe_scale_response", h, B, N, model, n_frames, arrays, ridge, G, &F, seq); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    HIPCHK(hipSetDevice(h->device));
+    return scale_launch(h, B, N, F, seq, q, meas, weight, ridge, G, d_attach, d_marker_off, nullptr, nullptr, A_red, nullptr, nullptr, status, resp_u, resp_pos);
+}
+
+cpe_status cpe_scale_response_host(cpe_handle* h, int32_t B, int32_t N, const int32_t* model, const int32_t* n_frames, const double* q,
+                                   const double* meas, const double* weight, double ridge, int32_t G, const double* d_attach,
+                                   const double* d_marker_off, double* A_red, double* resp_u, double* resp_pos, cpe_status* status) {
+    size_t F;
+    std::vector<int2> seq;
+    const bool arrays = q && meas && weight && d_attach && d_marker_off && A_red && resp_u && status;
+    if (cpe_status s = scale_check("cpe_scale_response_host", h, B, N, model, n_frames, arrays, ridge, G, &F, seq); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    const DevModel& m = h->hm;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t nmeas = F * cams_max(h) * m.L;
+    Staging st(h->stream);
+    const double *dq = st.in(q, F * m.nq), *dmeas = st.in(meas, nmeas * 2), *dweight = st.in(weight, nmeas);
+    double *oAr = st.out(A_red, (size_t)B * G * G), *oru = st.out(resp_u, F * CPE_NX * G), *orp = st.out_opt(resp_pos, F * m.L * 3 * G);
+    HIPCHK(st.err);
+    const cpe_status s = scale_launch(h, B, N, F, seq, dq, dmeas, dweight, ridge, G, d_attach, d_marker_off, nullptr, nullptr, oAr, nullptr, nullptr, status, oru, orp);
+    if (s < 0) return s;
+    HIPCHK(st.fetch());
+    return s;
+}
+
+// What both forms of cpe_covariance_add_scales refuse, before the device is touched -- what needs no handle first: G outside 1..CPE_MAX_SCALES,
+// negative sizes, a frame count outside 0..N, a null handle or array (n_frames may be null; cov_pos, resp_pos and cov_pos_m are null together);
+// then a half-bandwidth above 4.  Fills F and lens = the frame count of every sequence.
+static cpe_status add_scales_check(const char* who, const cpe_handle* h, int32_t B, int32_t N, const int32_t* n_frames, int32_t G, bool arrays,
+                                   int markers_given, size_t* F, std::vector<int>& lens) {
+    const std::string w = std::string(who) + ": ";
+    if (G < 1 || G > CPE_MAX_SCALES) return fail(CPE_BAD_ARG, w + "G = " + std::to_string(G) + " outside 1.." + std::to_string(CPE_MAX_SCALES));
+    if (cpe_status s = frames(B, N, F); s != CPE_OK) return fail(s, w + g_err);
+    lens.assign((size_t)B, N);
+    for (int b = 0; n_frames && b < B; b++) {
+        if (n_frames[b] < 0 || n_frames[b] > N) return fail(CPE_BAD_ARG, w + "frame count of sequence " + std::to_string(b) + " outside 0..N");
+        lens[(size_t)b] = n_frames[b];
+    }
+    if (!h || !arrays) return fail(CPE_BAD_ARG, w + "null argument (only n_frames and the three marker arrays may be null)");
+    if (markers_given != 0 && markers_given != 3) return fail(CPE_BAD_ARG, w + "cov_pos, resp_pos and cov_pos_m are null together or given together");
+    return cov_check(who, h->pb, 0.0);
+}
+
+// the device entry after its checks: d_len = the frame counts on the device, or null (all N)
+static cpe_status add_scales_launch(cpe_handle* h, int32_t B, int32_t N, size_t F, const int* d_len, int32_t G, const double* cov_s, const double* resp_u,
+                                    const double* resp_pos, const double* cov_diag, const double* cov_off, const double* cov_pos, double* cov_diag_m,
+                                    double* cov_off_m, double* cov_pos_m) {
+    const size_t BB = (size_t)CPE_NX * CPE_NX, w = sizeof(double);
+    const int L = h->hm.L;
+    // past a sequence's frames, and the blocks (n + i, n) with n + i past them
+    HIPCHK(hipMemsetAsync(cov_diag_m, 0, w * F * BB, h->stream));
+    HIPCHK(hipMemsetAsync(cov_off_m, 0, w * F * h->pb * BB, h->stream));
+    if (cov_pos_m) HIPCHK(hipMemsetAsync(cov_pos_m, 0, w * F * L * 9, h->stream));
+    hipLaunchKernelGGL(k_cov_add_scales, dim3((unsigned)F), dim3(WAVE), 0, h->stream, d_len, N, h->pb, G, L, cov_s, resp_u, resp_pos, cov_diag, cov_off, cov_pos,
+                       cov_diag_m, cov_off_m, cov_pos_m);
+    HIPCHK(hipGetLastError());
+    return CPE_OK;
+}
+
+cpe_status cpe_covariance_add_scales(cpe_handle* h, int32_t B, int32_t N, const int32_t* n_frames, int32_t G, const double* cov_s, const double* resp_u,
+                                     const double* resp_pos, const double* cov_diag, const double* cov_off, const double* cov_pos, double* cov_diag_m,
+                                     double* cov_off_m, double* cov_pos_m) {
+    size_t F;
+    std::vector<int> lens;
+    const bool arrays = cov_s && resp_u && cov_diag && cov_off && cov_diag_m && cov_off_m;
+    const int mg = (resp_pos != nullptr) + (cov_pos != nullptr) + (cov_pos_m != nullptr);
+    if (cpe_status s = add_scales_check("cpe_covariance_add_scales", h, B, N, n_frames, G, arrays, mg, &F, lens); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    HIPCHK(hipSetDevice(h->device));
+    Staging st(h->stream);
+    const int* d_len = n_frames ? st.in(lens.data(), lens.size()) : nullptr;
+    HIPCHK(st.err);
+    if (cpe_status s = add_scales_launch(h, B, N, F, d_len, G, cov_s, resp_u, resp_pos, cov_diag, cov_off, cov_pos, cov_diag_m, cov_off_m, cov_pos_m); s != CPE_OK)
+        return s;
+    if (n_frames) HIPCHK(hipStreamSynchronize(h->stream));          // (lens is pageable and the staged copy is freed on return)
+    return CPE_OK;
+}
+
+cpe_status cpe_covariance_add_scales_host(cpe_handle* h, int32_t B, int32_t N, const int32_t* n_frames, int32_t G, const double* cov_s,
+                                          const double* resp_u, const double* resp_pos, const double* cov_diag, const double* cov_off,
+                                          const double* cov_pos, double* cov_diag_m, double* cov_off_m, double* cov_pos_m) {
+    size_t F;
+    std::vector<int> lens;
+    const bool arrays = cov_s && resp_u && cov_diag && cov_off && cov_diag_m && cov_off_m;
+    const int mg = (resp_pos != nullptr) + (cov_pos != nullptr) + (cov_pos_m != nullptr);
+    if (cpe_status s = add_scales_check("cpe_covariance_add_scales_host", h, B, N, n_frames, G, arrays, mg, &F, lens); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t BB = (size_t)CPE_NX * CPE_NX, L = h->hm.L;
+    Staging st(h->stream);
+    const int* d_len = n_frames ? st.in(lens.data(), lens.size()) : nullptr;
+    const double *dcs = st.in(cov_s, (size_t)B * G * G), *dru = st.in(resp_u, F * CPE_NX * G), *drp = st.in(resp_pos, F * L * 3 * G);
+    const double *dcd = st.in(cov_diag, F * BB), *dco = st.in(cov_off, F * h->pb * BB), *dcp = st.in(cov_pos, F * L * 9);
+    double *od = st.out(cov_diag_m, F * BB), *oo = st.out(cov_off_m, F * h->pb * BB), *op = st.out_opt(cov_pos_m, F * L * 9);
+    HIPCHK(st.err);
+    if (cpe_status s = add_scales_launch(h, B, N, F, d_len, G, dcs, dru, drp, dcd, dco, dcp, od, oo, op); s != CPE_OK) return s;
+    HIPCHK(st.fetch());
+    return CPE_OK;
 }
 
 // ---- posterior covariance of the rates (include/cpe.h, cpe_rate_covariance; kernels in cpe_rate_cov.hip.inc) --------------------------------

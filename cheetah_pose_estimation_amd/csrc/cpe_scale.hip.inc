@@ -31,6 +31,68 @@ __device__ __forceinline__ void lower_entry(int e, int& g, int& h) {
 // dynamic LDS (doubles): state | sin / cos | leg sin / cos | trunk R, dR | dynamic vectors | S rows | Dp | positions | cameras | M_l, r_l
 //                        | R of every link | Ds [L][G][3] | M Ds [L][G][3] | item of (marker, reduced column) (int) | first term of every item (int)
 // dcv: dchain_vec of every model [model][G][L][CPE_MAX_CHAIN][3]
+// The carve of a frame's dynamic LDS, in the order of the comment above, and what k_scale_cross and k_scale_points (cpe_scale_cov.hip.inc) share.
+struct ScaleLds {
+    double *sq, *sal, *ssc, *ssa, *sR, *sdyn, *sSv, *sDp, *spos, *scam, *sMv, *sRf, *sDs, *sMD;
+    int *sIdx, *sBeg;
+};
+// The first half of a frame, one wave: the carve, the state and the cameras into LDS, the state phases, the reduced marker columns Dp, the rotation
+// of every link and the item of every (marker, reduced column) (-1: the marker does not depend on that column).  stf: the frame's state.  Ends
+// with a wave_lds_sync.
+__device__ __forceinline__ void wave_scale_head(const DevModel* __restrict__ M, const double* __restrict__ stf, int G, double* smem, ScaleLds& s,
+                                                int lane) {
+    const int nq = M->nq, nl = M->nl, L = M->L, C = M->C, nrev = M->nrev, ns = M->ns, svn = M->sv_n, mct = M->mc_total;
+    s.sq = smem;
+    s.sal = s.sq + nq;
+    s.ssc = s.sal + nrev;
+    s.ssa = s.ssc + 6 * nl;
+    s.sR = s.ssa + 2 * nrev;
+    s.sdyn = s.sR + 36 * M->n_trunk;
+    s.sSv = s.sdyn + 3 * svn;
+    s.sDp = s.sSv + CPE_MAX_SCOL * M->n_srow;
+    s.spos = s.sDp + 3 * mct;
+    s.scam = s.spos + 3 * L;
+    s.sMv = s.scam + CAMW * C;
+    s.sRf = s.sMv + 9 * L;
+    s.sDs = s.sRf + 9 * nl;
+    s.sMD = s.sDs + 3 * L * G;
+    s.sIdx = reinterpret_cast<int*>(s.sMD + 3 * L * G);
+    s.sBeg = s.sIdx + L * NU;
+
+    const int4 fw = *reinterpret_cast<const int4*>(M->fn_lane[lane]);
+    const int hj_n = M->hj_n, hk_n = M->hk_n;
+    const int2 hkw = *reinterpret_cast<const int2*>(M->hk_w[lane]);
+    for (int t = lane; t < ns; t += WAVE) s.sq[t] = stf[t];
+    const double* camw = reinterpret_cast<const double*>(M->cam);
+    for (int t = lane; t < CAMW * C; t += WAVE) s.scam[t] = camw[t];
+    for (int t = lane; t < L * NU; t += WAVE) s.sIdx[t] = -1;
+    wave_lds_sync();
+    // ---- the state phases (cpe_kernels.hip); the legs' Euler angles are not rebuilt: the state holds them
+    wave_state_sincos(M, s.sq, s.sal, s.ssc, s.ssa, nrev, lane);
+    wave_lds_sync();
+    wave_tail_roll(s.sq, s.ssc, hj_n, fw.x, lane);
+    wave_trunk_rotations(M, s.ssc, s.sR, fw.y, lane);
+    wave_lds_sync();
+    wave_hooke_srows(s.sR, s.sSv, hk_n, hkw, lane);
+    wave_point_columns(M, s.ssa, s.sR, s.sSv, s.sdyn, s.sDp, s.sBeg, lane);
+    // ---- the rotation of every link, the item of every (marker, reduced column)
+    if (lane < nl) rot_kind(s.ssc + 6 * lane, 0, s.sRf + 9 * lane);
+    for (int t = lane; t < mct; t += WAVE) { const int l = M->mc_marker[t]; s.sIdx[l * NU + M->mcol[l][M->mc_j[t]]] = t; }
+    wave_lds_sync();
+}
+// Ds_l[g] = d p_l / d s_g = sum_k R_{chain_link[l][k]} dchain_vec[g][l][k], over the chain in its order; dv: the model's dchain_vec, sRf: wave_scale_head's
+__device__ __forceinline__ void scale_point_derivative(const DevModel* __restrict__ M, const double* __restrict__ dv, const double* sRf, int l, int g,
+                                                       double& d0, double& d1, double& d2) {
+    const double* v = dv + ((size_t)g * M->L + l) * (CPE_MAX_CHAIN * 3);
+    const int n = M->chain_len[l];
+    d0 = 0.0; d1 = 0.0; d2 = 0.0;
+    for (int k = 0; k < n; k++) {
+        const double* R = sRf + 9 * M->chain_link[l][k];
+        const double v0 = v[3 * k], v1 = v[3 * k + 1], v2 = v[3 * k + 2];
+        d0 += R[0] * v0 + R[1] * v1 + R[2] * v2; d1 += R[3] * v0 + R[4] * v1 + R[5] * v2; d2 += R[6] * v0 + R[7] * v1 + R[8] * v2;
+    }
+}
+
 template <bool RAGGED = false>
 __global__ __launch_bounds__(WAVE) void k_scale_cross(const DevModel* __restrict__ M, const SeqState* __restrict__ st, int N, size_t n_frames,
                                                       const double* __restrict__ qbuf, const double* __restrict__ meas,
@@ -45,43 +107,13 @@ __global__ __launch_bounds__(WAVE) void k_scale_cross(const DevModel* __restrict
     if (!cov_seq_ok(st, b)) return;
     const size_t f = (size_t)b * N + fs.n;
     const int buf = st[b].cur;
-    const int nq = M->nq, nl = M->nl, L = M->L, C = M->C, nrev = M->nrev, ns = M->ns, svn = M->sv_n, mct = M->mc_total;
+    const int L = M->L, C = M->C, ns = M->ns;
     const double* dv = dcv + (size_t)fs.model * G * L * (CPE_MAX_CHAIN * 3);
-    double* sq = smem;
-    double* sal = sq + nq;
-    double* ssc = sal + nrev;
-    double* ssa = ssc + 6 * nl;
-    double* sR = ssa + 2 * nrev;
-    double* sdyn = sR + 36 * M->n_trunk;
-    double* sSv = sdyn + 3 * svn;
-    double* sDp = sSv + CPE_MAX_SCOL * M->n_srow;
-    double* spos = sDp + 3 * mct;
-    double* scam = spos + 3 * L;
-    double* sMv = scam + CAMW * C;
-    double* sRf = sMv + 9 * L;
-    double* sDs = sRf + 9 * nl;
-    double* sMD = sDs + 3 * L * G;
-    int* sIdx = reinterpret_cast<int*>(sMD + 3 * L * G);
-    int* sBeg = sIdx + L * NU;
-
-    const int4 fw = *reinterpret_cast<const int4*>(M->fn_lane[lane]);
-    const int hj_n = M->hj_n, hk_n = M->hk_n;
-    const int2 hkw = *reinterpret_cast<const int2*>(M->hk_w[lane]);
-    const double* stf = qbuf + (size_t)buf * n_frames * ns + f * ns;
-    for (int t = lane; t < ns; t += WAVE) sq[t] = stf[t];
-    const double* camw = reinterpret_cast<const double*>(M->cam);
-    for (int t = lane; t < CAMW * C; t += WAVE) scam[t] = camw[t];
-    for (int t = lane; t < L * NU; t += WAVE) sIdx[t] = -1;
-    wave_lds_sync();
-    // ---- the state phases (cpe_kernels.hip); the legs' Euler angles are not rebuilt: the state holds them
-    wave_state_sincos(M, sq, sal, ssc, ssa, nrev, lane);
-    wave_lds_sync();
-    wave_tail_roll(sq, ssc, hj_n, fw.x, lane);
-    wave_trunk_rotations(M, ssc, sR, fw.y, lane);
-    wave_lds_sync();
-    wave_hooke_srows(sR, sSv, hk_n, hkw, lane);
-    wave_point_columns(M, ssa, sR, sSv, sdyn, sDp, sBeg, lane);
-    // ---- marker positions (k_frame_normal's formula), the rotation of every link, the item of every (marker, reduced column)
+    ScaleLds s;
+    wave_scale_head(M, qbuf + (size_t)buf * n_frames * ns + f * ns, G, smem, s, lane);
+    double *sq = s.sq, *sR = s.sR, *sdyn = s.sdyn, *sDp = s.sDp, *spos = s.spos, *scam = s.scam, *sMv = s.sMv, *sRf = s.sRf, *sDs = s.sDs, *sMD = s.sMD;
+    int* sIdx = s.sIdx;
+    // ---- marker positions (k_frame_normal's formula)
     if (lane < L) {
         double p0 = sq[0], p1 = sq[1], p2 = sq[2];
 #pragma unroll
@@ -98,8 +130,6 @@ __global__ __launch_bounds__(WAVE) void k_scale_cross(const DevModel* __restrict
         }
         spos[3 * lane] = p0; spos[3 * lane + 1] = p1; spos[3 * lane + 2] = p2;
     }
-    if (lane < nl) rot_kind(ssc + 6 * lane, 0, sRf + 9 * lane);
-    for (int t = lane; t < mct; t += WAVE) { const int l = M->mc_marker[t]; sIdx[l * NU + M->mcol[l][M->mc_j[t]]] = t; }
     wave_lds_sync();
     // ---- M_l and r_l: the marker's lane walks its cameras in order
     const size_t pair0 = f * (size_t)((RAGGED ? rg.cstride : C) * L);
@@ -128,14 +158,8 @@ __global__ __launch_bounds__(WAVE) void k_scale_cross(const DevModel* __restrict
     // ---- Ds_l[g] and M_l Ds_l[g], one (marker, group) per lane and round
     for (int t = lane; t < L * G; t += WAVE) {
         const int l = t / G, g = t - l * G;
-        const double* v = dv + ((size_t)g * L + l) * (CPE_MAX_CHAIN * 3);
-        const int n = M->chain_len[l];
-        double d0 = 0.0, d1 = 0.0, d2 = 0.0;
-        for (int k = 0; k < n; k++) {
-            const double* R = sRf + 9 * M->chain_link[l][k];
-            const double v0 = v[3 * k], v1 = v[3 * k + 1], v2 = v[3 * k + 2];
-            d0 += R[0] * v0 + R[1] * v1 + R[2] * v2; d1 += R[3] * v0 + R[4] * v1 + R[5] * v2; d2 += R[6] * v0 + R[7] * v1 + R[8] * v2;
-        }
+        double d0, d1, d2;
+        scale_point_derivative(M, dv, sRf, l, g, d0, d1, d2);
         const double* Mv = sMv + 9 * l;
         sDs[3 * t] = d0; sDs[3 * t + 1] = d1; sDs[3 * t + 2] = d2;
         sMD[3 * t] = Mv[0] * d0 + Mv[1] * d1 + Mv[2] * d2;
@@ -185,11 +209,14 @@ __global__ __launch_bounds__(WAVE) void k_scale_cross(const DevModel* __restrict
 // products Y^T Y and Y^T (L^-1 g) and the sums of A_n, b_n and of the measurement cost grow frame by frame in the registers of the lane that
 // stores them: entry (g, h) and its mirror come from one register, so A and A_red are exactly symmetric.
 // A sequence without a factor is left alone (the caller zeroed its outputs); RAGGED: the sequence's own length.
+// Yneg (or null): -Y_E = -L^-1 E, column g of frame n at [b][g][n][row] -- the right-hand sides from which k_band_sample's back substitution gives
+// the response of the poses to the scales, R = -(H + ridge D)^-1 E (cpe_scale_response); storing it changes nothing of the other outputs.
 template <int PB, bool RAGGED = false>
 __global__ __launch_bounds__(WAVE) void k_band_forward(const SeqState* __restrict__ st, const double* __restrict__ Lbuf, const double* __restrict__ gtbuf,
                                                        const double* __restrict__ costbuf, const double* __restrict__ rec, int NS, size_t n_frames,
                                                        int G, double* __restrict__ A, double* __restrict__ bv, double* __restrict__ A_red,
-                                                       double* __restrict__ b_red, double* __restrict__ cost, RaggedArgs rg = RaggedArgs{}) {
+                                                       double* __restrict__ b_red, double* __restrict__ cost, double* __restrict__ Yneg,
+                                                       RaggedArgs rg = RaggedArgs{}) {
     constexpr int RING = PB + 1, BB = NU * NU, COLD = RING * BB;
     static_assert(PB >= 3 && PB <= 4, "the half-bandwidths of the covariance entries");
     __shared__ double col[COLD];
@@ -240,6 +267,11 @@ __global__ __launch_bounds__(WAVE) void k_band_forward(const SeqState* __restric
             }
 #pragma unroll
             for (int k = 0; k < NU; k++) sY[k * SCALE_RHS + j] = t[k];
+            if (Yneg && j < G) {                             // -Y_E as right-hand side j of k_band_sample: [b][j][n][row]
+                double* yo = Yneg + (((size_t)b * G + j) * NS + n) * NU;
+#pragma unroll
+                for (int k = 0; k < NU; k++) yo[k] = -t[k];
+            }
         }
         wave_lds_sync();
         if (live) {

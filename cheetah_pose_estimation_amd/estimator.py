@@ -327,6 +327,7 @@ class CheetahEstimator:
     # [N, 3(, 3)], and, aligned with com_vel, com_vel_cov / _std [N-1, 3(, 3)] and speed_std [N-1]
     # uncertainty_spans adds SPAN_FIELDS (cpe_covariance_columns, span_uncertainty): per span (first, last) the centre of mass's displacement, distance,
     # mean velocity and mean speed with covariances / standard deviations, and span_positions_displacement_cov / _std [S, L, 3(, 3)]
+    # uncertainty_lengths adds LENGTH_FIELDS (cpe_scale_response, cpe_covariance_add_scales): the covariance marginalised over the fitted lengths
     uncertainty: Optional[dict] = None
     # estimate_kinematics(uncertainty=True, uncertainty_samples=K): SAMPLE_FIELDS, K trajectories drawn from the posterior (cpe_band_sample,
     # cpe_posterior_samples): du [K, N, 28], q [K, N, nq], x [K, N, 28], positions [K, N, L, 3], com_pos [K, N, 3], seed, ridge; None where not
@@ -602,17 +603,24 @@ _RATE_WANT = ("cov_du", "cov_ddu", "cov_vel", "cov_com", "cov_com_vel")
 
 
 SAMPLE_FIELDS = ("seed", "ridge", "du", "q", "x", "positions", "com_pos")
+# uncertainty_lengths=True: the covariance marginalised over the fitted segment lengths ("What is marginalised") -- the diagonal blocks
+# and marker blocks of cov_u / positions_cov with the scale terms added and their standard deviations, scale_cov [G, G] = the covariance of the scales
+# that was used, u_scale_response [N, 28, G] = du / ds of the re-adapted poses and positions_scale_response [N, L, 3, G] = d p / d s in total
+LENGTH_FIELDS = ("cov_u_marginal", "u_std_marginal", "positions_cov_marginal", "positions_std_marginal", "scale_cov", "u_scale_response",
+                 "positions_scale_response")
 
 
 @dataclass(frozen=True)
 class PosteriorRequest:
     """what the uncertainty keywords of ONE public call ask of the posterior (posterior_request makes it; None stands for uncertainty=False):
-    the damping, whether the rates are propagated, uncertainty_spans as given, the number of draws and their seed"""
+    the damping, whether the rates are propagated, uncertainty_spans as given, the number of draws and their seed, and whether the covariance is
+    also marginalised over the fitted segment lengths.  Rates, spans and samples stay conditional on the lengths."""
     ridge: float = 0.0
     rates: bool = False
     spans: object = None
     samples: int = 0
     seed: int = 0
+    lengths: bool = False
 
     @property
     def want_L(self) -> bool:
@@ -624,9 +632,10 @@ class PosteriorRequest:
 
 
 def posterior_request(uncertainty: bool, uncertainty_ridge: float, uncertainty_rates: bool, uncertainty_spans, uncertainty_samples: int,
-                      uncertainty_seed: int) -> Optional[PosteriorRequest]:
-    """the six public keywords -> the request, or None for uncertainty=False.  Samples, rates and spans propagate the covariance uncertainty=True
-    computes: alone each is refused, as is a negative sample count, before anything is looked at."""
+                      uncertainty_seed: int, uncertainty_lengths: bool = False, estimate_lengths: bool = False) -> Optional[PosteriorRequest]:
+    """the public keywords -> the request, or None for uncertainty=False.  Samples, rates and spans propagate the covariance uncertainty=True
+    computes: alone each is refused, as is a negative sample count, before anything is looked at.  uncertainty_lengths adds the scale terms to
+    that covariance and needs the lengths fitted in the same call (estimate_lengths); rates, spans and samples stay conditional on the lengths."""
     if uncertainty_samples < 0:
         raise ValueError(f"uncertainty_samples must be >= 0, not {uncertainty_samples}")
     if uncertainty_samples and not uncertainty:
@@ -635,9 +644,14 @@ def posterior_request(uncertainty: bool, uncertainty_ridge: float, uncertainty_r
         raise ValueError("uncertainty_rates=True needs uncertainty=True: the rates are propagated from the covariance that keyword computes")
     if uncertainty_spans is not None and not uncertainty:
         raise ValueError("uncertainty_spans needs uncertainty=True: the spans are propagated from the covariance that keyword computes")
+    if uncertainty_lengths and not uncertainty:
+        raise ValueError("uncertainty_lengths=True needs uncertainty=True: the scale terms are added to the covariance that keyword computes")
+    if uncertainty_lengths and not estimate_lengths:
+        raise ValueError("uncertainty_lengths=True needs estimate_lengths=True: the covariance is marginalised over the lengths the same call fits")
     if not uncertainty:
         return None
-    return PosteriorRequest(uncertainty_ridge, bool(uncertainty_rates), uncertainty_spans, int(uncertainty_samples), uncertainty_seed)
+    return PosteriorRequest(uncertainty_ridge, bool(uncertainty_rates), uncertainty_spans, int(uncertainty_samples), uncertainty_seed,
+                            bool(uncertainty_lengths))
 
 
 def _spans_of(req: Optional[PosteriorRequest], ests) -> Optional[list]:
@@ -682,15 +696,40 @@ class _Group:
     meas, weight, stance, kinetic options).  of = None: the plain form (one model, arrays stacked to [B, N, ...], the *_host methods); of = the
     model of every sequence on a Handle.multi: the ragged form (lists of per-sequence arrays, the *_ragged_host methods).  force = None: a
     kinematic group; else the physics variant arrays (grf_fixed / tau_box / grf_box, at most one) that the covariance call and the force-sample
-    call share."""
+    call share.  lengths = None, or what the length step of a kinematic group needs (_length_group): d_attach [M, G, n_links, 3] and d_marker_off
+    [M, G, n_markers, 3] = the derivative tables of every model of the handle, animal = what names the animal of every sequence (sequences of one
+    animal share their scales), prior_sigma = the calibration's prior of every sequence (None: none)."""
     args: tuple
     of: Optional[list] = None
     force: Optional[dict] = None
+    lengths: Optional[dict] = None
 
 
 def _gather(arrays, ragged: bool):
     """the per-sequence arrays of a group in its form: a list (ragged) or stacked (plain); None where the group has none"""
     return None if arrays[0] is None else (list(arrays) if ragged else np.stack(arrays))
+
+
+def scale_covariance(A_red, prior_sigma: Optional[float]) -> np.ndarray:
+    """cov_s = (sum A_red + P)^-1 over the reduced matrices of one animal's sequences, summed in list order; P = I / prior_sigma^2 (None: 0)"""
+    S = np.array(A_red[0], dtype=np.float64)
+    for A in A_red[1:]:
+        S = S + A
+    if prior_sigma is not None:
+        S = S + np.eye(S.shape[0]) / float(prior_sigma) ** 2
+    return np.linalg.inv(S)
+
+
+def _length_group(seqs, of) -> dict:
+    """_Group.lengths of the estimators `seqs` of one group (of: the model of every sequence, or None = one model): raises ValueError for an
+    estimator without fitted lengths"""
+    if any(getattr(e, "length_scale", None) is None or not e.length_calibration for e in seqs):
+        raise ValueError("uncertainty_lengths=True: an estimator of the group has no fitted lengths (calibrate_lengths did not run on it)")
+    reps = [0] if of is None else [of.index(k) for k in range(max(of) + 1)]
+    tabs = [skeleton.length_derivatives(f"{e.name}-02" if e.params.kinetic_dataset else e.name, e.skeleton.n_markers, e.length_groups)
+            for e in (seqs[i] for i in reps)]
+    return dict(d_attach=np.stack([t[0] for t in tabs]), d_marker_off=np.stack([t[1] for t in tabs]),
+                animal=[(e.name, e.params.kinetic_dataset) for e in seqs], prior_sigma=[e.length_calibration["prior_sigma"] for e in seqs])
 
 
 def _posterior(h, req: PosteriorRequest, spans: Optional[list], q, group: _Group) -> dict:
@@ -702,7 +741,11 @@ def _posterior(h, req: PosteriorRequest, spans: Optional[list], q, group: _Group
       4. req.samples = K > 0: ONE cpe_band_sample call on the covariance call's own factor (no second factorisation; a sequence without a factor
          takes no part: frame count 0) with z = sample_normals(seed, K, n) per sequence at its own length, ONE cpe_posterior_samples call at the
          same q and, for a physics group, ONE cpe_force_samples call with the covariance call's own arguments and
-         zeta = sample_force_normals(seed, K, n) -> "samples".
+         zeta = sample_force_normals(seed, K, n) -> "samples";
+      5. req.lengths (kinematic groups only; group.lengths), after the covariance call and at the same ridge: ONE cpe_scale_response call over
+         the group, cov_s = scale_covariance of the A_red of every animal's sequences that have a factor (in list order, with the calibration's
+         prior), ONE cpe_covariance_add_scales call on the covariance call's own band -> "lengths".  Steps 2 - 4 read the covariance GIVEN the
+         lengths, whatever req.lengths.
     Returns the covariance call's dict with those additions; _uncertainty_of / _kinetic_uncertainty_of / _samples_of cut a sequence out of it."""
     ragged = group.of is not None
     models = (group.of,) if ragged else ()
@@ -713,6 +756,19 @@ def _posterior(h, req: PosteriorRequest, spans: Optional[list], q, group: _Group
     B, Nm = src["cov_diag"].shape[:2]
     lens = [len(c) for c in cov["cov_diag"]] if ragged else [Nm] * B
     factor = [s == abi.OK for s in cov["seq_status"]]
+    if req.lengths and group.force is None:
+        lg = group.lengths
+        rs = h.scale_response_host(*a, lg["d_attach"], lg["d_marker_off"], req.ridge, **(dict(model_list=group.of) if ragged else {}))
+        rp = rs["padded"] if ragged else rs
+        cov_s = np.zeros((B,) + rs["A_red"].shape[1:])
+        for key in dict.fromkeys(lg["animal"]):
+            idx = [b for b in range(B) if lg["animal"][b] == key]
+            have = [rs["A_red"][b] for b in idx if rs["seq_status"][b] == abi.OK]
+            if have:
+                cov_s[idx] = scale_covariance(have, lg["prior_sigma"][idx[0]])
+        m = h.covariance_add_scales_host(cov_s, rp["resp_u"], rp["resp_pos"], src["cov_diag"], src["cov_off"], src["cov_pos"], lens if ragged else None)
+        cov["lengths"] = dict(cov_diag=m["cov_diag"], cov_pos=m["cov_pos"], cov_s=cov_s, resp_u=rp["resp_u"], resp_pos=rp["resp_pos"], lens=lens,
+                              seq_status=rs["seq_status"])
     want = (_RATE_WANT if req.rates else ()) + (("jac_pos", "jac_com") if spans is not None else ())
     if want:
         r = getattr(h, "rate_covariance" + form)(q, cov["cov_diag"], cov["cov_off"], *models, want=want)
@@ -885,6 +941,13 @@ def _uncertainty_of(cov: dict, b: int, ridge: float) -> Optional[dict]:
                ridge=float(ridge))
     if "rates" in cov:
         unc.update(_rate_fields(cov["rates"], b))
+    if "lengths" in cov:                            # LENGTH_FIELDS
+        lg = cov["lengths"]
+        n = lg["lens"][b]
+        cm, pm = np.ascontiguousarray(lg["cov_diag"][b, :n]), np.ascontiguousarray(lg["cov_pos"][b, :n])
+        unc.update(cov_u_marginal=cm, u_std_marginal=np.sqrt(np.diagonal(cm, axis1=1, axis2=2)), positions_cov_marginal=pm,
+                   positions_std_marginal=np.sqrt(np.diagonal(pm, axis1=2, axis2=3)), scale_cov=lg["cov_s"][b].copy(),
+                   u_scale_response=np.ascontiguousarray(lg["resp_u"][b, :n]), positions_scale_response=np.ascontiguousarray(lg["resp_pos"][b, :n]))
     if "spans" in cov:                              # (SPAN_FIELDS need the centre of mass: _add_speed_std)
         sp = cov["spans"]
         unc["_spans"] = dict(columns=sp["columns"][b], anchors=sp["anchors"][b], spans=sp["spans"][b], jac_pos=np.ascontiguousarray(sp["jac_pos"][b]),
@@ -1218,7 +1281,7 @@ def estimate_kinematics(estimator: CheetahEstimator, solver_output: bool = True,
                         motion_model_sparse_solution: bool = True, out_dir_prefix: Optional[str] = None,
                         q_init: Optional[np.ndarray] = None, options: Optional[abi.Options] = None, uncertainty: bool = False,
                         uncertainty_ridge: float = 0.0, uncertainty_rates: bool = False, uncertainty_spans=None, uncertainty_samples: int = 0,
-                        uncertainty_seed: int = 0, estimate_lengths: bool = False, length_prior_sigma: Optional[float] = 0.1,
+                        uncertainty_seed: int = 0, uncertainty_lengths: bool = False, estimate_lengths: bool = False, length_prior_sigma: Optional[float] = 0.1,
                         length_scale_init=None, length_ridge: float = 0.0) -> bool:
     """Same signature as acinoset_opt.estimate_kinematics (acinoset_opt.py:539-547) plus optional
     keyword arguments.  Returns True when the solve converged (IPOPT `ok`+`optimal` in the reference).
@@ -1242,8 +1305,13 @@ def estimate_kinematics(estimator: CheetahEstimator, solver_output: bool = True,
     objective), and skeleton_scale.json beside fte.pickle holds all of it.  A fit that did not converge warns and is marked there; its scales
     are still used.  length_ridge: the damping of the poses' matrix in cpe_scale_system (a monocular run may need 1e-6 for a factor).  The
     calibration's pose solves use this call's priors and options.  One camera needs a prior (length_prior_sigma=None: ValueError); together
-    with shutter-delay estimation: NotImplementedError.  uncertainty=True stays the covariance of the poses GIVEN the lengths."""
-    req = posterior_request(uncertainty, uncertainty_ridge, uncertainty_rates, uncertainty_spans, uncertainty_samples, uncertainty_seed)
+    with shutter-delay estimation: NotImplementedError.  uncertainty=True stays the covariance of the poses GIVEN the lengths.
+    uncertainty_lengths=True (with uncertainty=True and estimate_lengths=True; else ValueError): est.uncertainty and uncertainty.npz gain
+    LENGTH_FIELDS, the covariance marginalised over the fitted lengths ("What is marginalised": cpe_scale_response and
+    cpe_covariance_add_scales at uncertainty_ridge, cov_s from this sequence's A_red and the calibration's prior); every other field keeps its bits.
+    The rates, spans and samples stay conditional on the lengths."""
+    req = posterior_request(uncertainty, uncertainty_ridge, uncertainty_rates, uncertainty_spans, uncertainty_samples, uncertainty_seed,
+                            uncertainty_lengths, estimate_lengths)
     if estimate_lengths:
         _check_lengths([estimator], length_prior_sigma)
     est, params, scene = estimator, estimator.params, estimator.scene
@@ -1295,7 +1363,7 @@ def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_out
                               disable_pose_prior: bool = False, disable_motion_prior: bool = False, out_dir_prefix: Optional[str] = None,
                               options: Optional[abi.Options] = None, ragged: bool = False, uncertainty: bool = False,
                               uncertainty_ridge: float = 0.0, uncertainty_rates: bool = False, uncertainty_spans=None, uncertainty_samples: int = 0,
-                              uncertainty_seed: int = 0, estimate_lengths: bool = False, length_prior_sigma: Optional[float] = 0.1,
+                              uncertainty_seed: int = 0, uncertainty_lengths: bool = False, estimate_lengths: bool = False, length_prior_sigma: Optional[float] = 0.1,
                               length_scale_init=None, length_ridge: float = 0.0) -> List[bool]:
     """estimate_kinematics for MANY sequences at once: the loop of run_dataset.py:1145-1196 (`for seq in dataset: init_trajectory; estimate_kinematics`)
     as batched launches.  Sequences that share a skeleton, a camera rig, a length and a frame rate go through ONE solver handle and ONE cpe_solve
@@ -1313,8 +1381,12 @@ def estimate_kinematics_batch(estimators: Sequence[CheetahEstimator], solver_out
     uncertainty_samples, uncertainty_seed: as in estimate_kinematics, every sequence with the z of its own call (sample_normals); one cpe_band_sample
     and one cpe_posterior_samples call per group, same bit-equality of est.samples and samples.npz.
     estimate_lengths, length_prior_sigma, length_scale_init, length_ridge: as in estimate_kinematics; the estimators of one animal (name and dataset kind) share
-    their scales: one calibrate_lengths call per animal over all its sequences, before the solves."""
-    req = posterior_request(uncertainty, uncertainty_ridge, uncertainty_rates, uncertainty_spans, uncertainty_samples, uncertainty_seed)
+    their scales: one calibrate_lengths call per animal over all its sequences, before the solves.
+    uncertainty_lengths: as in estimate_kinematics; per group one cpe_scale_response and one cpe_covariance_add_scales call, and cov_s of an animal
+    from the A_red of its sequences IN THAT GROUP (a plain batch splits an animal's sequences by length and rig; ragged=True keeps them together).
+    Rates, spans and samples stay conditional on the lengths."""
+    req = posterior_request(uncertainty, uncertainty_ridge, uncertainty_rates, uncertainty_spans, uncertainty_samples, uncertainty_seed,
+                            uncertainty_lengths, estimate_lengths)
     ests = list(estimators)
     cal_q: Dict[int, np.ndarray] = {}
     if estimate_lengths:
@@ -1417,7 +1489,8 @@ def _solve_kinematic_group(ests, idx, prepared, out, ragged: bool, req: Optional
         # THE asymmetry of the kinematic stage, kept as it is: a single call asks nothing of the library after a solve that did not converge; a
         # batch asks for its whole group and discards what such a sequence does not need
         if req is not None and not (single and res["stats"][0].status != abi.OK):
-            cov = _posterior(hs.solve, req, None if spans is None else [spans[i] for i in idx], res["q"], _Group(a[1:], hs.of))
+            cov = _posterior(hs.solve, req, None if spans is None else [spans[i] for i in idx], res["q"],
+                             _Group(a[1:], hs.of, None, _length_group(seqs, hs.of) if req.lengths else None))
         for b, i in enumerate(idx):
             ests[i].shutter_delay = None
             unc = None if req is None else (None if cov is None else _uncertainty_of(cov, b, req.ridge), req.ridge)

@@ -794,6 +794,40 @@ cpe_status cpe_scale_system_host(cpe_handle* h, int32_t B, int32_t N, const int3
                                  const double* weight, double ridge, int32_t G, const double* d_attach, const double* d_marker_off, double* A,
                                  double* b, double* A_red, double* b_red, double* cost, cpe_status* status);
 
+/* ---- the pose covariance marginalised over the fitted scales ("What is marginalised").  cpe_covariance is the covariance of the
+ * poses GIVEN the lengths.  Over (u, s) the joint Gauss-Newton matrix of one animal is a block arrow -- pose blocks H + ridge D, borders E, corner
+ * sum A + P with P the prior precision of the scales -- and its inverse is, exactly,
+ *     cov_s = (sum_b A_red,b + P)^-1     R_b = du_b / ds = -(H_b + ridge D_b)^-1 E_b     cov(u_b) = Sigma_b + R_b cov_s R_b^T     cov(u_b, s) = R_b cov_s
+ * and, a marker position depending on the scales directly (Ds_l = d p_l / d s) and through the poses (P_l = d p_l / d u),
+ *     W_l = Ds_l + P_l R_n     cov(p_l) = P_l Sigma(n,n) P_l^T + W_l cov_s W_l^T.
+ * cpe_scale_response: arguments, statuses and refusals of cpe_scale_system.  A_red [B][G][G] is bit-equal to that entry's; resp_u [B][N][28][G] = R,
+ * the response of the re-adapted poses to the scales; resp_pos [B][N][L][3][G] = W, how far a marker moves per unit of a scale once the poses have
+ * re-adapted (may be NULL).  Layouts, ragged included, as cpe_covariance_ragged's cov_pos; everything is 0.0 past a sequence's frames and for a
+ * sequence without a factor (CPE_NUMERICAL in status[b]).  It runs cpe_scale_system's launches, keeps Y_E = L^-1 E, solves L^T X = -Y_E for the G
+ * columns (cpe_band_sample's kernel) and forms W per frame.  The named deviations of cpe_covariance and cpe_scale_system carry over. */
+cpe_status cpe_scale_response(cpe_handle* h, int32_t B, int32_t N, const int32_t* model /*[B] host, or NULL*/, const int32_t* n_frames /*[B] host, or NULL*/,
+                              const double* q, const double* meas, const double* weight, double ridge, int32_t G, const double* d_attach /*host*/,
+                              const double* d_marker_off /*host*/, double* A_red, double* resp_u, double* resp_pos, cpe_status* status);
+/* host-pointer twin (stages through HBM) */
+cpe_status cpe_scale_response_host(cpe_handle* h, int32_t B, int32_t N, const int32_t* model, const int32_t* n_frames, const double* q, const double* meas,
+                                   const double* weight, double ridge, int32_t G, const double* d_attach, const double* d_marker_off, double* A_red,
+                                   double* resp_u, double* resp_pos, cpe_status* status);
+/* cpe_covariance_add_scales: the band of cov(u) and the marker covariances with the scale terms added, blocks in cpe_band_inverse's layout:
+ *     cov_diag_m[n] = cov_diag[n] + R_n cov_s R_n^T     cov_off_m[n][i-1] = cov_off[n][i-1] + R_{n+i} cov_s R_n^T     cov_pos_m[n][l] = cov_pos[n][l] + W_l cov_s W_l^T
+ * Device pointers: cov_s [B][G][G] (only its lower triangle is read), resp_u, resp_pos (cpe_scale_response's), cov_diag, cov_off, cov_pos (a covariance
+ * entry's) and the outputs, which must not overlap the inputs.  n_frames [B] HOST, or NULL = all N.  cov_pos, resp_pos and cov_pos_m are NULL together
+ * or given together.  cov_diag_m and cov_pos_m are exactly symmetric; the outputs are 0.0 past a sequence's frames and where n + i is past them; a
+ * sequence of 0 frames is not read.  Every sum runs over the scales in ascending order (no atomics) and a result depends on its own sequence alone.
+ * Refused with CPE_BAD_ARG before the device is touched, the reason in cpe_last_error(): G outside 1..CPE_MAX_SCALES; negative sizes; a frame count
+ * outside 0..N; a NULL argument other than those named; a half-bandwidth above 4. */
+cpe_status cpe_covariance_add_scales(cpe_handle* h, int32_t B, int32_t N, const int32_t* n_frames /*[B] host, or NULL*/, int32_t G, const double* cov_s,
+                                     const double* resp_u, const double* resp_pos, const double* cov_diag, const double* cov_off, const double* cov_pos,
+                                     double* cov_diag_m, double* cov_off_m, double* cov_pos_m);
+/* host-pointer twin (stages through HBM) */
+cpe_status cpe_covariance_add_scales_host(cpe_handle* h, int32_t B, int32_t N, const int32_t* n_frames, int32_t G, const double* cov_s, const double* resp_u,
+                                          const double* resp_pos, const double* cov_diag, const double* cov_off, const double* cov_pos, double* cov_diag_m,
+                                          double* cov_off_m, double* cov_pos_m);
+
 /* ---- posterior covariance of the physics-based estimate: coordinates, and the node forces (torques, joint constraint forces, net foot forces)
  * the solve infers ("What is inverted").  Runs the launches of the first pass of cpe_solve_kinetic at Euler q -- cold start, multipliers
  * zero, node forces minimised from a cold start, as cpe_eval_kinetic_system / cpe_eval_lm_step -- at damping `ridge` in place of opts.lambda0, up to
