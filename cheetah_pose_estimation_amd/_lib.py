@@ -358,6 +358,31 @@ class Handle:
         self.synchronize()
         return uv.cpu().numpy()
 
+    def detection_report(self, positions, cov_pos, uv, cov_px, meas=None, weight=None, weight_fit=None, uv_loo=None, cov_loo=None, d2=None,
+                         leverage=None):
+        """cpe_detection_report on device tensors: positions [B, N, L, 3], cov_pos [B, N, L, 3, 3] (covariance()'s) -> uv [B, N, C, L, 2], cov_px
+        [B, N, C, L, 3] = (xx, xy, yy); with meas [B, N, C, L, 2] and weight [B, N, C, L] (weight_fit: the weights of the fit, None = weight) also
+        uv_loo, cov_loo, d2 [B, N, C, L], leverage, each of which may be None"""
+        self._call(self.lib.cpe_detection_report, "cpe_detection_report", positions.shape[0], positions.shape[1], _ptr(positions), _ptr(cov_pos),
+                   _ptr(meas), _ptr(weight), _ptr(weight_fit), _ptr(uv), _ptr(cov_px), _ptr(uv_loo), _ptr(cov_loo), _ptr(d2), _ptr(leverage))
+
+    def detection_report_host(self, positions, cov_pos, meas=None, weight=None, weight_fit=None):
+        """cpe_detection_report_host: numpy in, dict of numpy arrays out -- uv, cov_px [B, N, C, L, 2, 2] and, with meas and weight, uv_loo, cov_loo
+        [.., 2, 2], d2, leverage"""
+        positions, cov_pos = _f64(positions), _f64(cov_pos)
+        meas, weight, weight_fit = _f64(meas, True), _f64(weight, True), _f64(weight_fit, True)
+        B, N = positions.shape[:2]
+        pair = (B, N, self.n_cams, self.L)
+        raw = dict(uv=np.empty(pair + (2,)), cov_px=np.empty(pair + (3,)))
+        if meas is not None or weight is not None:
+            raw.update(uv_loo=np.empty(pair + (2,)), cov_loo=np.empty(pair + (3,)), d2=np.empty(pair), leverage=np.empty(pair))
+        _check(self.lib.cpe_detection_report_host(self._h, B, N, _ptr(positions), _ptr(cov_pos), _ptr(meas), _ptr(weight), _ptr(weight_fit),
+                                                  *[_ptr(raw.get(k)) for k in abi.DETECTION_OUTPUTS]), "cpe_detection_report_host")
+        for k in ("cov_px", "cov_loo"):
+            if k in raw:
+                raw[k] = raw[k][..., [0, 1, 1, 2]].reshape(pair + (2, 2))
+        return raw
+
     def triangulate_host(self, cam_a, cam_b, uv_a, uv_b, depth=3.0):
         """n detection pairs -> xyz [n, 3] (cpe_triangulate; cam_b < 0: back-projection of uv_a to `depth`); numpy in / out"""
         ca, cb = self._to_device(cam_a, np.int32), self._to_device(cam_b, np.int32)

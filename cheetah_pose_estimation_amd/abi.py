@@ -245,6 +245,13 @@ SCALE_RESPONSE_ENTRIES = {
     "cpe_covariance_add_scales": _ADD_SCALES,
     "cpe_covariance_add_scales_host": _ADD_SCALES,
 }
+# the detection report (cpe_detection_report): h, B, N | positions, cov_pos | meas, weight, weight_fit | uv, cov_px | uv_loo, cov_loo, d2, leverage
+_DETECTION = _BN + ("p",) * 11
+DETECTION_ENTRIES = {
+    "cpe_detection_report": _DETECTION,
+    "cpe_detection_report_host": _DETECTION,
+}
+DETECTION_OUTPUTS = ("uv", "cov_px", "uv_loo", "cov_loo", "d2", "leverage")        # in the order of the arguments
 COVARIANCE_MAX_PB = 4        # largest half-bandwidth (frames) the covariance sweep supports: motion-prior windows 5 and 6 are refused
 ENTRIES = {
     "cpe_create": ("sk", "cam", "i", "op", "pr", "i", "hp"),
@@ -311,7 +318,7 @@ ENTRIES = {
     "cpe_eval_active_list": ("h", "i", "i", "ip", "ip", "ip"),         # B, window | status | act, n_act (host)
     **COVARIANCE_ENTRIES, **KINETIC_COVARIANCE_ENTRIES, **KINETIC_COVARIANCE_RAGGED_ENTRIES, **RATE_COVARIANCE_ENTRIES,
     **{name: _COLUMNS for name in COLUMN_COVARIANCE_ENTRIES}, **SAMPLE_ENTRIES, **FORCE_SAMPLE_ENTRIES,
-    **SCALE_ENTRIES, **SCALE_RESPONSE_ENTRIES,
+    **SCALE_ENTRIES, **SCALE_RESPONSE_ENTRIES, **DETECTION_ENTRIES,
 }
 
 

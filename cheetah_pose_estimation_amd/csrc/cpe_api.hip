@@ -986,6 +986,75 @@ cpe_status cpe_reproject(cpe_handle* h, int32_t B, int32_t N, const double* posi
     return CPE_OK;
 }
 
+// ---- the detection report (include/cpe.h, cpe_detection_report; kernel in cpe_detection.hip.inc) ---------------------------------------------
+// the refusals of both entries, in one place: everything that can be told from the arguments alone, then the handle.  F == 0 asks for nothing,
+// so its arrays may be null (cpe_reproject's convention).
+static cpe_status detection_args(const char* who, const cpe_handle* h, int32_t B, int32_t N, const double* positions, const double* cov_pos,
+                                 const double* meas, const double* weight, const double* weight_fit, const double* uv, const double* cov_px,
+                                 const double* uv_loo, const double* cov_loo, const double* d2, const double* leverage, size_t* F) {
+    const std::string w = std::string(who) + ": ";
+    if (B < 0 || N < 0) return fail(CPE_BAD_ARG, w + "negative size");
+    if (cpe_status s = frames(B, N, F); s != CPE_OK) return fail(s, w + g_err);
+    if ((meas == nullptr) != (weight == nullptr)) return fail(CPE_BAD_ARG, w + "meas and weight are given together");
+    if (weight_fit && !weight) return fail(CPE_BAD_ARG, w + "weight_fit without weight");
+    if (!meas) {
+        const char* name = uv_loo ? "uv_loo" : cov_loo ? "cov_loo" : d2 ? "d2" : leverage ? "leverage" : nullptr;
+        if (name) return fail(CPE_BAD_ARG, w + name + " requested without measurements");
+    }
+    if (*F > 0) {
+        const char* name = !positions ? "positions" : !cov_pos ? "cov_pos" : !uv ? "uv" : !cov_px ? "cov_px" : nullptr;
+        if (name) return fail(CPE_BAD_ARG, w + name + " is null");
+    }
+    if (!h) return fail(CPE_BAD_ARG, w + "the handle is null");
+    return CPE_OK;
+}
+
+cpe_status cpe_detection_report(cpe_handle* h, int32_t B, int32_t N, const double* positions, const double* cov_pos, const double* meas,
+                                const double* weight, const double* weight_fit, double* uv, double* cov_px, double* uv_loo, double* cov_loo,
+                                double* d2, double* leverage) {
+    size_t F;
+    if (cpe_status s = detection_args("cpe_detection_report", h, B, N, positions, cov_pos, meas, weight, weight_fit, uv, cov_px, uv_loo, cov_loo, d2,
+                                      leverage, &F); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    HIPCHK(hipSetDevice(h->device));
+    if (meas)
+        hipLaunchKernelGGL(k_detection_report<true>, dim3((unsigned)F), dim3(WAVE), 0, h->stream, h->dm, positions, cov_pos, meas, weight,
+                           weight_fit ? weight_fit : weight, uv, cov_px, uv_loo, cov_loo, d2, leverage);
+    else
+        hipLaunchKernelGGL(k_detection_report<false>, dim3((unsigned)F), dim3(WAVE), 0, h->stream, h->dm, positions, cov_pos, nullptr, nullptr,
+                           nullptr, uv, cov_px, nullptr, nullptr, nullptr, nullptr);
+    HIPCHK(hipGetLastError());
+    return CPE_OK;
+}
+
+cpe_status cpe_detection_report_host(cpe_handle* h, int32_t B, int32_t N, const double* positions, const double* cov_pos, const double* meas,
+                                     const double* weight, const double* weight_fit, double* uv, double* cov_px, double* uv_loo, double* cov_loo,
+                                     double* d2, double* leverage) {
+    size_t F;
+    if (cpe_status s = detection_args("cpe_detection_report_host", h, B, N, positions, cov_pos, meas, weight, weight_fit, uv, cov_px, uv_loo, cov_loo,
+                                      d2, leverage, &F); s != CPE_OK) return s;
+    if (F == 0) return CPE_OK;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t nL = F * (size_t)h->hm.L, nCL = F * (size_t)h->hm.C * h->hm.L;
+    Staging st(h->stream);
+    const double* dp = st.in(positions, 3 * nL);
+    const double* dc = st.in(cov_pos, 9 * nL);
+    const double* dz = st.in(meas, 2 * nCL);
+    const double* dw = st.in(weight, nCL);
+    const double* dwf = st.in(weight_fit, nCL);
+    double* ouv = st.out(uv, 2 * nCL);
+    double* ocp = st.out(cov_px, 3 * nCL);
+    double* oul = st.out_opt(uv_loo, 2 * nCL);
+    double* ocl = st.out_opt(cov_loo, 3 * nCL);
+    double* od2 = st.out_opt(d2, nCL);
+    double* olv = st.out_opt(leverage, nCL);
+    HIPCHK(st.err);
+    const cpe_status s = cpe_detection_report(h, B, N, dp, dc, dz, dw, dwf, ouv, ocp, oul, ocl, od2, olv);
+    if (s != CPE_OK) return s;
+    HIPCHK(st.fetch());
+    return CPE_OK;
+}
+
 cpe_status cpe_triangulate(cpe_handle* h, int32_t n, const int32_t* cam_a, const int32_t* cam_b, const double* uv_a, const double* uv_b,
                            double depth, double* xyz) {
     if (!h) return fail(CPE_BAD_ARG, "null argument");

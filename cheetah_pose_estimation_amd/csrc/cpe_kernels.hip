@@ -753,3 +753,4 @@ __global__ __launch_bounds__(WAVE) void k_project(const DevModel* __restrict__ M
 #include "cpe_force_sample.hip.inc"
 #include "cpe_scale.hip.inc"
 #include "cpe_scale_cov.hip.inc"
+#include "cpe_detection.hip.inc"

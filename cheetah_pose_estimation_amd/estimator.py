@@ -342,6 +342,9 @@ class CheetahEstimator:
     # how that fit ended: dict(converged, rounds, prior_sigma, ridge, objective).  converged False: the loop stopped at max_rounds or found no
     # descent step; the scales are then the last iterate, not a minimiser (a warning is issued, and skeleton_scale.json says so)
     length_calibration: Optional[dict] = None
+    # detection_report: DETECTION_FIELDS, every marker's predicted pixel in every camera with its covariance, the leave-one-out prediction of every
+    # detection and its chi-square distance (cpe_detection_report); None until asked for
+    detections: Optional[dict] = None
 
     def get_objective_cost(self) -> float:
         return float(self.result["stats"][0].cost) if self.result else float("nan")
@@ -1581,6 +1584,168 @@ def determine_contacts(estimator: CheetahEstimator, monocular: bool = False, ver
             cj = json.load(fh)
         ct.write_synth_grf(os.path.join(grf_dir, f"{oname}.csv"), ct.synth_grf(cj, names, speed, direction))
     return contacts, by_height
+
+
+DETECTION_FIELDS = ("uv", "uv_cov", "uv_std", "uv_loo", "uv_loo_cov", "residual", "residual_loo", "d2_loo", "leverage", "outlier", "held_out", "chi2",
+                    "p_outlier", "ridge", "n_detections", "dof_measurements", "log_score", "log_score_held_out")
+DETECTION_CSV_COLUMNS = ("x", "y", "x_std", "y_std", "xy_corr", "x_loo", "y_loo", "d2_loo", "leverage", "outlier", "held_out")
+
+
+def loss_centre_curvature(a: float, b: float, c: float) -> float:
+    """kappa0 = rho''(0) of the redescending loss with knots a < b < c (acinoset_misc.py:2001-2015): the loss is the Gaussian of variance 1 / kappa0 at
+    its centre (1.0392 with the default knots 3, 10, 20: the switch at a = 3 is not quite off at the centre)"""
+    with np.errstate(over="ignore"):                                        # (knots out of reach: exp overflows to a switch that is off)
+        sa, sb, sc = (1.0 / (1.0 + np.exp(k)) for k in (a, b, c))           # the three sigmoid switches at e = 0
+    d1 = lambda x: x * (1.0 - x)
+    d2 = lambda x: x * (1.0 - x) * (1.0 - 2.0 * x)
+    cb = c - b
+    lin, kq, K = -0.5 * a * a, a * b - 0.5 * a * a + 0.5 * a * cb * (1.0 - (c / cb) ** 2), a * b - 0.5 * a * a + 0.5 * a * cb
+    k1, k2 = a * c / cb, -a / cb
+    return max(0.0, float((1.0 - sa) + (d2(sa) - d2(sb)) * lin + 2.0 * (d1(sa) - d1(sb)) * a + (d2(sb) - d2(sc)) * kq + 2.0 * (d1(sb) - d1(sc)) * k1
+                          + (sb - sc) * k2 + d2(sc) * K))
+
+
+def _kinematic_dir(est: CheetahEstimator, out_dir_prefix: Optional[str]) -> str:
+    """the directory _kin_finish saved the kinematic estimate to: the one of its names (with or without monocular constraints) whose fte.pickle is the
+    newest; FileNotFoundError naming the first where there is none"""
+    params, scene = est.params, est.scene
+    data_dir = params.data_dir if out_dir_prefix is None else os.path.join(out_dir_prefix, est.data_path)
+    base = f"fte_kinematic{'_gt' if params.hand_labeled_data else ''}"
+    names = [base] if scene.cam_idx is None else [f"{base}_{scene.cam_idx}", f"{base}_orig_{scene.cam_idx}"]
+    found = [d for d in (os.path.join(data_dir, n) for n in names) if os.path.exists(os.path.join(d, "fte.pickle"))]
+    if not found:
+        raise FileNotFoundError(os.path.join(data_dir, names[0], "fte.pickle"))
+    return max(found, key=lambda d: os.path.getmtime(os.path.join(d, "fte.pickle")))
+
+
+def detection_fields(raw: dict, meas: np.ndarray, weight: np.ndarray, weight_fit: np.ndarray, mult: np.ndarray, kappa0: float, p_outlier: float,
+                     ridge: float, held_out_cams: np.ndarray) -> dict:
+    """DETECTION_FIELDS of one sequence from Handle.detection_report_host's arrays [N, C, L, ..]: the residuals, the outlier flags at the exact
+    chi-square quantile -2 ln(p_outlier), and the sums -- the detections counted, the degrees of freedom they buy (the hat matrix's trace) and the
+    leave-one-out log predictive score -log(2 pi) - log det(S_loo + sigma2 I) / 2 - d2 / 2, over the fitted and over the held-out detections"""
+    w = mult[None, :, None] * weight
+    seen = w > 0.0
+    d2 = raw["d2"]
+    chi2 = -2.0 * np.log(p_outlier)
+    held = np.broadcast_to(held_out_cams[None, :, None], weight.shape).copy()
+    fitted = seen & (mult[None, :, None] * weight_fit > 0.0) & ~held
+    defined = seen & np.isfinite(d2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        C = raw["cov_loo"] + (1.0 / (w * w * kappa0))[..., None, None] * np.eye(2)
+        dens = -np.log(2.0 * np.pi) - 0.5 * np.log(C[..., 0, 0] * C[..., 1, 1] - C[..., 0, 1] * C[..., 1, 0]) - 0.5 * d2
+    nan2 = np.where(seen[..., None], 0.0, np.nan)
+    return dict(uv=raw["uv"], uv_cov=raw["cov_px"], uv_std=np.sqrt(np.diagonal(raw["cov_px"], axis1=-2, axis2=-1)), uv_loo=raw["uv_loo"],
+                uv_loo_cov=raw["cov_loo"], residual=meas - raw["uv"] + nan2, residual_loo=meas - raw["uv_loo"] + nan2, d2_loo=d2,
+                leverage=raw["leverage"], outlier=defined & (d2 > chi2), held_out=held, chi2=float(chi2), p_outlier=float(p_outlier), ridge=float(ridge),
+                n_detections=int(defined.sum()), dof_measurements=float(raw["leverage"][fitted].sum()),
+                log_score=float(dens[defined & fitted].sum()), log_score_held_out=float(dens[defined & held].sum()))
+
+
+def write_detection_csv(path: str, det: dict, c: int, start_frame: int) -> None:
+    """one camera's rows of the report: a plain header, then one row per frame and marker (DETECTION_CSV_COLUMNS; numbers as repr, flags as 0 / 1)"""
+    S = det["uv_cov"][:, c]
+    std = det["uv_std"][:, c]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        corr = S[..., 0, 1] / (std[..., 0] * std[..., 1])
+    cols = [det["uv"][:, c, :, 0], det["uv"][:, c, :, 1], std[..., 0], std[..., 1], corr, det["uv_loo"][:, c, :, 0], det["uv_loo"][:, c, :, 1],
+            det["d2_loo"][:, c], det["leverage"][:, c]]
+    flags = [det["outlier"][:, c], det["held_out"][:, c]]
+    N, L = cols[0].shape
+    names = [skeleton.MARKERS[l] if l < len(skeleton.MARKERS) else f"marker{l}" for l in range(L)]
+    with open(path, "w") as f:
+        f.write("frame,marker," + ",".join(DETECTION_CSV_COLUMNS) + "\n")
+        for n in range(N):
+            for l in range(L):
+                f.write(f"{start_frame + n},{names[l]}," + ",".join(repr(float(a[n, l])) for a in cols) + "," +
+                        ",".join(str(int(a[n, l])) for a in flags) + "\n")
+
+
+def detection_report(estimator: CheetahEstimator, validate_with: Optional[CheetahEstimator] = None, p_outlier: float = 1e-3,
+                     out_dir_prefix: Optional[str] = None, write: bool = True, options: Optional[abi.Options] = None) -> dict:
+    """Where in every camera's image every marker is, give or take how many pixels, and which detections disagree with everything else the estimate
+    knows ("What is predicted in the image"; cpe_detection_report).  Runs after estimate_kinematics(uncertainty=True) or
+    estimate_kinematics_batch, as determine_contacts does: the positions and their CONDITIONAL covariance (positions_cov, never the _marginal one:
+    the leave-one-out identity needs the covariance of the fit the detections were in) come from the estimator where it holds them, else from
+    fte.pickle and uncertainty.npz in the directory `save` wrote (FileNotFoundError names the missing file).  Returns DETECTION_FIELDS, keeps them
+    as est.detections and, with write=True, writes detections.npz beside uncertainty.npz and one cam{c+1}_detections.csv per camera, numbered as the
+    scene's cameras are; cam*_fte.csv, fte.pickle and uncertainty.npz are not touched.
+    validate_with: a second estimator of the same sequence initialised multi-view (same frame range and skeleton, else ValueError).  Its cameras,
+    meas and weight span the report; the cameras outside `estimator`'s fit are held out (weight_fit = 0), so with a monocular `estimator` this is
+    the cross-validation of the one-camera posterior: log_score_held_out is its predictive score on the cameras it did not see.
+    outlier = d2_loo > chi2 = -2 ln(p_outlier), the exact upper quantile of a chi-square with 2 degrees of freedom.
+    options: the options the estimate was made with where they were not the defaults (the loss's knots and curvature mode enter the report).
+    NotImplementedError: pairwise pseudo-measurements (the three slices of a camera are not independent detections) and a physics-stage result."""
+    est = estimator
+    if not (0.0 < p_outlier < 1.0):
+        raise ValueError(f"p_outlier must lie inside (0, 1), got {p_outlier!r}")
+    for e, who in ((est, "estimator"), (validate_with, "validate_with")):
+        if e is not None and e.params.enable_ppms:
+            raise NotImplementedError(f"detection_report: {who} was built with pairwise pseudo-measurements; the three slices of a camera are not "
+                                      "independent detections, and leaving one slice out does not leave the detection out")
+    if est.kinetic is not None:
+        raise NotImplementedError("detection_report: the estimator holds a physics-stage result; the report is that of the kinematic estimate "
+                                  "(the force unknowns are out of scope)")
+    params, scene = est.params, est.scene
+    if validate_with is not None:
+        v = validate_with
+        if v.scene.cam_idx is not None:
+            raise ValueError("detection_report: validate_with must be initialised multi-view")
+        if (v.params.start_frame, v.params.end_frame) != (params.start_frame, params.end_frame):
+            raise ValueError(f"detection_report: validate_with covers frames {v.params.start_frame}..{v.params.end_frame}, the estimator "
+                             f"{params.start_frame}..{params.end_frame}")
+        if _struct_bytes(v.skeleton) != _struct_bytes(est.skeleton):
+            raise ValueError("detection_report: validate_with has a different skeleton")
+    # the estimate: from the estimator where set, otherwise from the files of its save
+    out_dir = None
+    if est.result is not None and est.uncertainty is None:
+        raise ValueError("detection_report: the estimate has no covariance (est.uncertainty is None: not asked for, or the Gauss-Newton matrix had no "
+                         "Cholesky factor); run estimate_kinematics(uncertainty=True)")
+    if est.result is not None:
+        pos, unc = est.result["positions"][0], est.uncertainty
+    else:
+        out_dir = _kinematic_dir(est, out_dir_prefix)
+        pos = load_result_pickle(os.path.join(out_dir, "fte.pickle"))["positions"]
+        if not os.path.exists(os.path.join(out_dir, "uncertainty.npz")):
+            raise FileNotFoundError(os.path.join(out_dir, "uncertainty.npz"))
+        with np.load(os.path.join(out_dir, "uncertainty.npz")) as z:
+            unc = dict(positions_cov=z["positions_cov"], ridge=float(z["ridge"]))
+    if "tau_std" in unc:
+        raise NotImplementedError("detection_report: the covariance is that of a physics-stage result (out of scope)")
+    if write and out_dir is None:
+        out_dir = _kinematic_dir(est, out_dir_prefix)
+    # the cameras, detections and weights the report spans, and the weights the fit used
+    own = list(range(scene.n_cams)) if scene.cam_idx is None else [scene.cam_idx]
+    if validate_with is None:
+        cams, cam_ids, meas, weight, weight_fit = est.cams, own, est.meas, est.weight, est.weight
+    else:
+        cams, cam_ids, meas, weight = v.cams, list(range(v.scene.n_cams)), v.meas, v.weight
+        weight_fit = np.zeros_like(weight)
+        for j, c in enumerate(own):
+            weight_fit[:, c] = est.weight[:, j]
+    held_cams = np.array([c not in own for c in cam_ids])
+    opts = options if options is not None else abi.default_options(scene.fps)
+    if options is None and params.hand_labeled_data:
+        opts.loss_a, opts.loss_b, opts.loss_c = 1e6, 2e6, 3e6          # (_kin_prepare)
+    h = _lib.Handle(est.skeleton, cams, opts, device=est.device)
+    try:
+        raw = h.detection_report_host(pos[None], unc["positions_cov"][None], meas[None], weight[None], weight_fit[None])
+    finally:
+        h.close()
+    raw = {k: a[0] for k, a in raw.items()}
+    mult = np.array([cams[j].mult for j in range(len(cams))])
+    det = detection_fields(raw, np.asarray(meas, dtype=np.float64), np.asarray(weight, dtype=np.float64), np.asarray(weight_fit, dtype=np.float64), mult,
+                           loss_centre_curvature(opts.loss_a, opts.loss_b, opts.loss_c), p_outlier, float(unc["ridge"]), held_cams)
+    assert tuple(det) == DETECTION_FIELDS
+    est.detections = det
+    if write:
+        np.savez(os.path.join(out_dir, "detections.npz"), **det)
+        off = [0] * scene.n_cams
+        if params.sync_offset is not None:
+            for o in params.sync_offset:
+                off[o["cam"]] = o["frame"]
+        for j, c in enumerate(cam_ids):                              # rows numbered as cam{c+1}_fte.csv's are (save)
+            write_detection_csv(os.path.join(out_dir, f"cam{c + 1}_detections.csv"), det, j, params.start_frame - off[c])
+    return det
 
 
 def stance_from_contacts(contact_json: dict, n_frames: int) -> np.ndarray:

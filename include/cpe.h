@@ -947,6 +947,39 @@ cpe_status cpe_marker_velocities(cpe_handle* h, int32_t B, int32_t N, const doub
 cpe_status cpe_reproject(cpe_handle* h, int32_t B, int32_t N, const double* positions /*[B][N][L][3]*/,
                          double* uv /*[B][N][C][L][2]*/);
 
+/* The detection report ("What is predicted in the image"): where in every camera's image every marker is, give or take how many
+ * pixels, and -- with detections -- how far each detection is from what everything else predicts for it.  Per frame, camera c, marker l, with p
+ * the marker's position, Sigma_p its 3 x 3 block of cpe_covariance's cov_pos, z the detection, w = cam[c].mult * weight (the solver's scale of the
+ * residual) and w_f = cam[c].mult * weight_fit (the weight the detection had in the fit whose covariance Sigma_p is; weight_fit NULL = weight, 0 =
+ * held out):
+ *   uv, G       the projection and its 2 x 3 derivative by p; uv is bit-equal to cpe_reproject's
+ *   cov_px      S = G Sigma_p G^T as (xx, xy, yy): the covariance of the predicted pixel, exact to first order
+ *   l_d         the loss at w_f (uv_d - z_d), d = 0, 1 (the handle's knots and curvature mode); g_d = l_d' w_f and W = diag(kappa_d w_f^2) are the
+ *               gradient and curvature terms this detection put into H;  a_d = sqrt(W_dd);  T = I - diag(a) S diag(a)
+ *   leverage    W_00 S_00 + W_11 S_11 = tr(W S), the detection's share of the hat matrix's trace
+ *   cov_loo     S_loo = S + S diag(a) T^-1 diag(a) S  (= S (I - W S)^-1, stored symmetric as (xx, xy, yy)): the detection taken out of the fit
+ *   uv_loo      uv + S_loo g: one Gauss-Newton step about the estimate, exact for a quadratic objective
+ *   d2          r^T (S_loo + sigma2 I)^-1 r with r = z - uv_loo and sigma2 = 1 / (w^2 kappa0), kappa0 the loss's curvature at its centre: chi-square
+ *               with 2 degrees of freedom where the model holds
+ * Where the smaller eigenvalue of T is not finite or not above 1e-9 the detection alone determines a direction: uv_loo, cov_loo and d2 are NaN,
+ * leverage is still written.  w == 0 (no detection): uv_loo = uv and cov_loo = cov_px bit for bit, leverage 0, d2 NaN.  w_f == 0 < w (held out):
+ * W = 0 and g = 0, so uv_loo = uv, cov_loo = cov_px and d2 = r^T (S + sigma2 I)^-1 r.  A redescended outlier has W = 0 too: it is out of the fit
+ * already.  With a ridge in cov_pos the report is that of the damped posterior; multipliers are zero as in cpe_covariance.
+ * Device pointers, enqueued on the handle's stream; no workspace, no atomics: reproducible bit for bit, and a sequence's outputs do not depend on
+ * the batch it is in.  meas and weight come together or not at all; without them the call is the pixel-ellipse part alone and the four outputs
+ * after cov_px must be NULL; with them each of the four may be NULL.  CPE_BAD_ARG with the argument named in cpe_last_error(), before the device is
+ * touched: negative sizes; meas without weight or weight without meas; weight_fit without weight; uv_loo, cov_loo, d2 or leverage without
+ * measurements; null positions, cov_pos, uv or cov_px (B N > 0); a null handle.  B = 0 or N = 0 returns CPE_OK and touches nothing. */
+cpe_status cpe_detection_report(cpe_handle* h, int32_t B, int32_t N, const double* positions /*[B][N][L][3]*/, const double* cov_pos /*[B][N][L][3][3]*/,
+                                const double* meas /*[B][N][C][L][2] or NULL*/, const double* weight /*[B][N][C][L] or NULL*/,
+                                const double* weight_fit /*[B][N][C][L] or NULL = weight*/, double* uv /*[B][N][C][L][2]*/,
+                                double* cov_px /*[B][N][C][L][3]*/, double* uv_loo /*[B][N][C][L][2]*/, double* cov_loo /*[B][N][C][L][3]*/,
+                                double* d2 /*[B][N][C][L]*/, double* leverage /*[B][N][C][L]*/);
+/* host-pointer twin (stages through HBM) */
+cpe_status cpe_detection_report_host(cpe_handle* h, int32_t B, int32_t N, const double* positions, const double* cov_pos, const double* meas,
+                                     const double* weight, const double* weight_fit, double* uv, double* cov_px, double* uv_loo, double* cov_loo,
+                                     double* d2, double* leverage);
+
 /* initial-guess ingestion: two-view linear triangulation of n detection pairs, i.e. triangulate_points[_fisheye]
  * (acinoset_misc.py:1432-1453: cv[.fisheye].undistortPoints of both pixels with the cameras' K and D, cv.triangulatePoints with
  * [R | t]).  cam_a / cam_b index the handle's cameras; cam_b[i] < 0 asks for the monocular rule instead: the first detection
